@@ -7,15 +7,21 @@ per-workgroup partial mixes up and applies the master volume (N = 1); for N > 1 
 one RCCL reduce(sum) of float[F][2] onto rank 0, master volume there.  State and tables are resident in HBM before the
 timed region starts; the output frames stay in HBM (a real-time host would copy 8*F bytes).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c1|c2|c3|c4] [--frames F] [--full] [--dump-outputs DIR]
 
 Default workload: BASELINE config 3 -- ONE bank of 2^20 voices (mixed notamy LUTs + biquad + ADSR), F = 512 frames
 per launch (the reference's callback size, skred.h:12), 48 kHz.  With N > 1 (the driver launches one rank per GPU
-through torch.distributed.run) that bank is SPLIT over the GPUs -- the literal config 3, "scaling": "strong" -- and the
-line also carries `weak_scaling` (a 2^20-voice bank per GPU) for comparison.  With N = 1 the line also carries the
-other BASELINE workloads (`c1`, `c2`, `c4`), two other block lengths (`low_latency`, `long_block`), the recipe from its
-first frame (`envelopes_in_motion`), a bank under control traffic (`live_control`), the fixed-point path and the CPU
-baseline.
+through torch.distributed.run) that bank is SPLIT over the GPUs -- the literal config 3, "scaling": "strong".
+
+A plain run measures the headline only: set-up, the recipe's warm-up, K timed steps (after W warm-up steps) and the
+result line with the main roofline (kernel times bracketed inside the timed steps).  The GPU is brought out of idle on a
+twin of the bank, so the timed bank renders exactly the same frames from run to run.  --full adds everything else: with
+N > 1 `weak_scaling` (a 2^20-voice bank per GPU); with N = 1 the other BASELINE workloads (`c1`, `c2`, `c4`), linear
+lookup, two other block lengths (`low_latency`, `long_block`), the recipe from its first frame (`envelopes_in_motion`),
+a bank under control traffic (`live_control`), `roofline_valu` (tools/issue_rate), the scaling proxy, the shipped
+patches, the fixed-point path and the CPU baseline.
+
+--dump-outputs DIR writes what the timed path's last step returned (the master mix, float32 [F][2]) as DIR/mix.npy.
 """
 from __future__ import annotations
 
@@ -220,7 +226,12 @@ def main():
     ap.add_argument("--voices", type=int, default=0, help="override the bank's voice count")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"],
                     help="N > 1 -- strong (default): ONE bank of the workload size split over the GPUs (BASELINE config 3 as written); "
-                         "weak: a bank of that size on every GPU.  The default run reports both (`weak_scaling`)")
+                         "weak: a bank of that size on every GPU.  A --full run reports both (`weak_scaling`)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other leg (other workloads, precisions, block lengths, control traffic, scaling "
+                         "proxy, shipped patches, roofline_valu, cpu_baseline; weak_scaling with N > 1); the --no-* options trim it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's output of its last step (the master mix, float32 [F][2]) as DIR/mix.npy")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-extra", action="store_true", help="N = 1: only the main line (no other workloads / block lengths / legs)")
     ap.add_argument("--no-low-latency", action="store_true", help="(older name of --no-extra)")
@@ -234,7 +245,7 @@ def main():
                     help="bracket the render kernel of every n-th launch with HIP events (kernel duration for the roofline); "
                          "0 = choose so that at least 8 launches of the timed region are bracketed")
     ap.add_argument("--spinup-ms", type=float, default=40.0,
-                    help="untimed rendering before the W warm-up steps until this much wall time has passed: a GPU taken from idle "
+                    help="untimed rendering on a twin of the bank before the W warm-up steps until this much wall time has passed: a GPU taken from idle "
                          "needs ~25 ms of work before clocks and caches settle (20 steps right after first touch time ~10 %% slow)")
     ap.add_argument("--rehearse-dist", action="store_true",
                     help="with one process: run the N > 1 code path (the shard's RCCL reduce, with one rank) on a single-GPU box")
@@ -246,8 +257,10 @@ def main():
     ap.add_argument("--fast2-min-voices", type=int, default=-1,
                     help="override the bank size from which the two-voices-per-lane kernel is used (-1: library default)")
     a = ap.parse_args()
-    if a.no_low_latency:
+    if a.no_low_latency or not a.full:
         a.no_extra = True
+    if not a.full:
+        a.no_cpu = True
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -292,7 +305,7 @@ def main():
                 e0.record(); e1.record()
             torch.cuda.synchronize()
         EVENT_PAIR_MS = float(np.median([e0.elapsed_time(e1) for e0, e1 in pairs]))
-    ISSUE_PEAK = issue_peak() if rank == 0 else None
+    ISSUE_PEAK = issue_peak() if rank == 0 and a.full else None
 
     def fence():
         torch.cuda.synchronize()
@@ -320,6 +333,27 @@ def main():
             n += 8
         return n
 
+    def twin_spinup(src, first, n, tables, g, itp, frames):
+        """spinup() on a TWIN of the timed bank (voices first .. first + n of `src`): how many blocks the wall-time spin-up takes
+        varies from run to run, and the timed bank must render the same frames every run (--dump-outputs compares builds).
+        The twin is returned open, to be closed after the timed region (freeing it in between would stall the stream)."""
+        tw = device.DeviceBank(n, local)
+        tw.set_tables(tables)
+        tw.upload(src, first, 0, n)
+        tw.set_globals(g)
+        if a.fast2_min_voices >= 0:
+            tw.fast2_min_voices(a.fast2_min_voices)
+        o = torch.zeros(frames, 2, device=dev, dtype=torch.float32)
+        return spinup(lambda fr: tw.render_mix(fr, o.data_ptr(), 2, 0, itp, stream), frames), tw
+
+    def dump_outputs(**arrays):
+        """--dump-outputs: what the timed path returned in its last step, float32 / float64, as DIR/<name>.npy"""
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, x in arrays.items():
+            x = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+            x = x.astype(np.float64 if x.dtype == np.float64 else np.float32)
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), x)
+
     def timed(render_block, db, frames, steps, warmup, timing_every):
         """warm-up launches, then EXACTLY `steps` launches between two fences; max over ranks."""
         db.kernel_timing(timing_every)
@@ -345,18 +379,20 @@ def main():
         bank_voices = a.voices
     F = a.frames
 
-    def sharded_leg(total, scaling):
+    def sharded_leg(total, scaling, dump=False):
         """One bank of `total` voices split over the ranks (strong) or one bank of `total / world`... see caller."""
         sh = Shard(total, rank, world, local)
         if scaling == "strong" or world == 1:
             whole, tables, g = banks.RECIPES[recipe](total)          # the one global bank, generated on every rank
             sh.bank.set_tables(tables)
             sh.upload(whole)
+            src, first = whole, sh.lo
             del whole
         else:                                                        # weak: every rank holds its own bank (seed + rank)
             mine, tables, g = banks.RECIPES[recipe](sh.n_local, seed=banks.SEED + rank)
             sh.bank.set_tables(tables)
             sh.bank.upload(mine)
+            src, first = mine, 0
             del mine
         sh.bank.set_globals(g)
         if a.fast2_min_voices >= 0:
@@ -379,7 +415,8 @@ def main():
                 sh.render_mix_pipelined(frames, outs[kblk[0] & 1].data_ptr(), 2, interp, stream)
                 kblk[0] += 1
         warm = 0 if a.no_recipe_warmup else recipe_warmup(block, F)
-        spun = spinup(block, F)
+        spun, twin = twin_spinup(src, first, sh.n_local, tables, g, interp, F)
+        del src
         fence()
         calib = None
         if not a.serial_collective and not a.pipelined_collective:
@@ -392,10 +429,14 @@ def main():
             a.serial_collective = calib["serial_ms"] <= calib["pipelined_ms"]
         dt, k_mean, k_min, k_cnt = timed(block, sh.bank, F, a.steps, a.warmup, every)
         form_used = "serial" if a.serial_collective else "pipelined"
+        last = out if a.serial_collective else outs[(kblk[0] - 1) & 1]
         if calib is not None:
             a.serial_collective = False
         sh.flush(stream)
         torch.cuda.synchronize()
+        twin.close()
+        if a.dump_outputs and rank == 0 and dump:
+            dump_outputs(mix=last)
         finite = bool(all(torch.isfinite(o).all().item() for o in outs)) if rank == 0 else True
         res = {"dt": dt, "k": (k_mean, k_min, k_cnt), "kernel": KERNELS.get(sh.bank.last_kernel(), "?"), "finite": finite,
                "warm": warm, "spun": spun, "n_local": sh.n_local, "form": form_used, "calib": calib}
@@ -405,7 +446,7 @@ def main():
     res = None
     if use_dist:
         total = bank_voices if a.scaling == "strong" else bank_voices * world
-        m = sharded_leg(total, a.scaling)
+        m = sharded_leg(total, a.scaling, dump=True)
         if rank == 0:
             value = total * F * a.steps / m["dt"]
             rl = roofline(a.workload, m["n_local"], F, gather_bytes, *m["k"], m["kernel"])
@@ -441,7 +482,7 @@ def main():
         return
 
     # ------------------------------------------------------------------ one GPU
-    def single_leg(wl, frames, steps, warmup, timing_every, voices=0, warm_recipe=True):
+    def single_leg(wl, frames, steps, warmup, timing_every, voices=0, warm_recipe=True, dump=False):
         rec, n, itp, gbytes = WORKLOADS[wl]
         n = voices or n
         bank, tables, g = banks.RECIPES[rec](n)
@@ -456,9 +497,12 @@ def main():
         def block(fr):
             db.render_mix(fr, out.data_ptr(), 2, 0, itp, stream)
         warm = recipe_warmup(block, frames) if warm_recipe else 0
-        spun = spinup(block, frames)
+        spun, twin = twin_spinup(bank, 0, n, tables, g, itp, frames)
         fence()
         dt, k_mean, k_min, k_cnt = timed(block, db, frames, steps, warmup, timing_every)
+        twin.close()
+        if dump:
+            dump_outputs(mix=out)
         r = roofline(wl, n, frames, gbytes, k_mean, k_min, k_cnt, KERNELS.get(db.last_kernel(), "?"))
         r["value"] = n * frames * steps / dt
         r["ms_per_step"] = dt / steps * 1e3
@@ -467,7 +511,8 @@ def main():
         finite = bool(torch.isfinite(out).all().item())
         return r, dt, (warm, spun), finite, (db, bank, tables, g, out)
 
-    rl, dt, warm, finite, keep = single_leg(a.workload, F, a.steps, a.warmup, every, bank_voices, not a.no_recipe_warmup)
+    rl, dt, warm, finite, keep = single_leg(a.workload, F, a.steps, a.warmup, every, bank_voices, not a.no_recipe_warmup,
+                                            dump=bool(a.dump_outputs))
     db, bank, tables, g, out = keep
     value = bank_voices * F * a.steps / dt
     rl.pop("value"); rl.pop("ms_per_step"); rl.pop("realtime_factor_48k"); rl.pop("voices")

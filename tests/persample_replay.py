@@ -173,5 +173,24 @@ def main():
     print("RESULT " + json.dumps(out))
 
 
+def write_golden(path):
+    """tests/golden/persample_ref.json: the compiled reference's digests for the cases tests/test_dropin.py checks (one fresh
+    process per case), so that the comparison also runs where the reference tree is absent."""
+    import subprocess
+    res = {}
+    for case in GOLDEN_CASES:
+        o = subprocess.run([sys.executable, os.path.abspath(__file__), "ref", case], capture_output=True, text=True, check=True)
+        res[case] = json.loads([l for l in o.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    with open(path, "w") as f:
+        json.dump(res, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote", path, sorted(res))
+
+
+GOLDEN_CASES = ["edge_mod", "edge_basic", "c4_pcm_oneshot", "c1_sine_adsr64", "korg_waves"]
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1] == "--write-golden":
+        write_golden(os.path.join(HERE, "golden", "persample_ref.json"))
+    else:
+        main()

@@ -73,10 +73,13 @@ def test_per_sample_functions_match_reference(case):
     """The eight per-sample functions of synth.h (osc_next, cz_phasor, quantize_bits_int, mmf_process,
     amp_envelope_step, audio_rng_*) and voice_format() of the drop-in against the compiled reference: same calls on the
     same voice state (the libraries' own tables incl. the Korg slots, then the fixture's), every returned float, the
-    state left behind and the text, bit for bit."""
-    if not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libskred_ref.so")):
-        pytest.skip("oracle/_ref/libskred_ref.so not built (needs the reference tree)")
-    ref, mine = persample("ref", case), persample("mine", case)
+    state left behind and the text, bit for bit.  The reference's digests are stored (tests/golden/persample_ref.json,
+    written by `persample_replay.py --write-golden`); where the reference is built, they are checked against it too."""
+    with open(os.path.join(HERE, "golden", "persample_ref.json")) as f:
+        ref = json.load(f)[case]
+    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libskred_ref.so")):
+        assert persample("ref", case) == ref, "fixture is stale"
+    mine = persample("mine", case)
     assert mine["stateless"] == ref["stateless"]
     assert mine["state_and_values"] == ref["state_and_values"]
     assert mine["text"] == ref["text"], (mine["text_sample"], ref["text_sample"])
