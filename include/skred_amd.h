@@ -362,6 +362,12 @@ int  skred_bank_last_split(const skred_bank_t *bank);     /* 1: the latest block
 #define SKRED_PROBE_MAX 64
 int  skred_bank_set_probe(skred_bank_t *bank, const int32_t *voices, int n, float *d_probe);
 
+/* Which form the modulated kernel's wavefronts ran (tests): with `d_counts` set (device memory, two words the caller owns and
+ * zeroes), every pass of every wavefront of the modulated kernel adds 1 to d_counts[0] when it runs the frame-lag form
+ * (SKRED_OPT_FM_SKEW) and to d_counts[1] when it runs the level loop of a bank with same-frame dependencies.  NULL ends it;
+ * unset, the kernel pays one scalar branch per pass. */
+int  skred_bank_set_form_counter(skred_bank_t *bank, uint32_t *d_counts);
+
 /* Cross-check of the motion list of the two-voices-per-lane path ("The motion list"): voices whose envelope may be
  * in motion are kept on a per-voice list ON THE DEVICE (every control action lists the voices it touches, the envelope kernel
  * keeps its voices listed until they rest) and rendered by the envelope kernel beside the steady kernel, which never has to be

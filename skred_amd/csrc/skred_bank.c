@@ -378,6 +378,14 @@ int skred_bank_set_probe(skred_bank_t *b, const int32_t *voices, int n, float *d
   return SKRED_OK;
 }
 
+int skred_bank_set_form_counter(skred_bank_t *b, uint32_t *d_counts) {
+  if (!b) return fail(SKRED_E_BAD_ARG, "set_form_counter: no bank");
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipDeviceSynchronize());                   /* (a block in flight may still count into the old words) */
+  b->d_form_counts = d_counts;
+  return SKRED_OK;
+}
+
 int skred_bank_last_kernel(const skred_bank_t *b) { return b ? b->last_kernel : -1; }
 int skred_bank_last_in_place(const skred_bank_t *b) { return b ? b->last_in_place : 0; }
 int skred_bank_last_split(const skred_bank_t *b) { return b ? b->last_split : 0; }
@@ -583,6 +591,7 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
   a.pack_shift = 6;
   a.fm_skew = b->fm_skew && (a.fast_mode & SKM_FM) && a.lds_table_floats > 0 && !d_stems;   /* (the launcher drops it when the ring does not fit) */
   if (modulated) a.fm_skew = b->fm_skew && !d_stems;        /* (the modulated kernel: its frame-lag form, same option) */
+  a.form_counts = modulated ? b->d_form_counts : NULL;
   int pack_s = 0;
   if (b->pack_mode && (modulated || ((a.fast_mode & SKM_FAST) && !(a.fast_mode & SKM_FM_PAIR))) && !d_stems) {   /* (the modulated kernel packs the same way) */
     const int most = pack_refresh(b);

@@ -225,6 +225,8 @@ typedef struct {
   int32_t pack_passes;       /* workgroup passes: ceil(pack_groups / (4 << (6 - pack_shift))) */
   /* ---- skewed blocks of frequency-modulated wavefronts (one-voice family, extended instantiation; SKRED_OPT_FM_SKEW) ---- */
   int32_t fm_skew;           /* 1: the launch carries the per-wave sample ring (SK_SKEW_RING floats) behind the reduction tiles */
+  /* ---- which form the modulated kernel's waves ran (tests; skred_bank_set_form_counter), NULL: not counted ---- */
+  uint32_t *form_counts;     /* [2] += 1 per wave and pass: [0] the frame-lag form, [1] the level loop with max_level >= 1 */
 } sk_render_args_t;
 #define SK_PROBE_MAX 64
 

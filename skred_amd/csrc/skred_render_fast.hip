@@ -751,7 +751,7 @@ __global__ __launch_bounds__(SK_GROUP, TAB_LDS ? (STOPS ? ((FILTER || ENV || INT
         const uint4 mf = *reinterpret_cast<const uint4 *>(&a.ro[SKP_MODF][v]);
         int fm_lane = (int)mi.x;
         int am_lane = (int)mi.y, pm_lane = (int)mi.z;
-        if (absent) fm_lane = am_lane = pm_lane = -1;
+        if (dead) fm_lane = am_lane = pm_lane = -1;            // (a dead lane never reads them: not translated, nothing counted)
         if (packed) {                                      // the planes number modulators by their lane in the 64-voice group
           if (fm_lane >= 0) fm_lane = sk_packed_lane(a, pmask, lane, fm_lane);
           if (am_lane >= 0) am_lane = am_lane == ppos ? lane : sk_packed_lane(a, pmask, lane, am_lane);

@@ -318,7 +318,14 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
       const uint4 mx = *reinterpret_cast<const uint4 *>(&a.ro[SKP_MODX][v]);
       const uint4 fl = *reinterpret_cast<const uint4 *>(&a.ro[SKP_FILT][v]);
       m.fm = (int)mi.x; m.am = (int)mi.y; m.pm = (int)mi.z; m.cz = (int)mi.w;
-      if (packed && !absent) {                                 // (the planes number modulators by their lane in the 64-voice group)
+      // a lane that is dead as loaded stays dead for the whole launch (amp and voice_finished only change between launches): its
+      // own modulators are never read, so they are not translated (a packed lane may be there only because a live voice names it,
+      // while the modulators it names have no lane) and take no part in the lag vote.  Its level stays: it decides in which
+      // iteration of the frame-lag form the lane's voice_sample turns to 0.  An empty lane (voice 0 loaded) has no routing at all.
+      const bool dead0 = absent || (r.rw & SKR_FINISHED) || r.amp == 0.0f || (r.flags & SKF_INERT);
+      if (packed && dead0) {
+        m.fm = m.am = m.pm = m.cz = -1;
+      } else if (packed) {                                     // (the planes number modulators by their lane in the 64-voice group)
         if (m.fm >= 0) m.fm = sk_packed_lane(a, pmask, lane, m.fm);
         if (m.am >= 0) m.am = sk_packed_lane(a, pmask, lane, m.am);
         if (m.pm >= 0) m.pm = sk_packed_lane(a, pmask, lane, m.pm);
@@ -326,9 +333,9 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
       }
       m.fm_depth = __uint_as_float(mf.x); m.freq_scale = __uint_as_float(mf.y);
       m.am_depth = __uint_as_float(mf.z); m.pm_depth = __uint_as_float(mf.w);
-      m.cz_depth = __uint_as_float(mx.x); m.cz_mode = (int)mx.y;
+      m.cz_depth = __uint_as_float(mx.x); m.cz_mode = absent ? 0 : (int)mx.y;
       m.cz_dist = __uint_as_float(fl.w);
-      m.level = levels[v];
+      m.level = absent ? 0 : levels[v];
       m.inc_raw = (r.flags & SKF_REVERSE) ? -r.inc : r.inc;    // load_voice applied the direction sign
     }
     incs[lane] = m.inc_raw;
@@ -355,6 +362,8 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
       lag = __all(ok) && __any(m.level == 1);
       SK_MOD_WAVE_SYNC()
     }
+    if (a.form_counts && lane == 0 && (lag || max_level >= 1))   // (tests: skred_bank_set_form_counter) which form this wave runs
+      atomicAdd(&a.form_counts[lag ? 0 : 1], 1u);
     float hl = 0.0f, hr = 0.0f, white_prev = 0.0f;            // (lag) the level-0 lanes' (L, R) and the noise draw of the frame before
     if (lag) {                                                 // iteration 0: the level-0 lanes render frame 0
       rng = rng * LCG_A + LCG_C;
@@ -362,7 +371,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
       float *cur = xch0 + cur_i * 64;
       const float *prev = xch0 + (cur_i ^ 1) * 64;
       const bool live = !((r.rw & SKR_FINISHED) || r.amp == 0.0f || (r.flags & SKF_INERT));
-      if (!live) r.sample = 0.0f;
+      if (!live && m.level == 0) r.sample = 0.0f;              // (a level-1 lane is still at frame -1: its sample stays for its readers)
       SK_MOD_WAVE_SYNC()
       float l = 0.0f, rr = 0.0f;
       if (live && m.level == 0) voice_frame_mod<TAB_LDS>(r, m, lane, prev, cur, incs, lds_tab, a.tables, a.count0 + 1, white, a.interp, l, rr, true);
@@ -382,8 +391,8 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
           float *cur = xch0 + cur_i * 64;
           const float *prev = xch0 + (cur_i ^ 1) * 64;
           const bool live = !((r.rw & SKR_FINISHED) || r.amp == 0.0f || (r.flags & SKF_INERT));
-          if (!live) r.sample = 0.0f;
-          SK_MOD_WAVE_SYNC()
+          if (!live && (m.level == 1 || more)) r.sample = 0.0f;  // only in an iteration that has a frame for this lane (synth.c:531-541:
+          SK_MOD_WAVE_SYNC()                                     // the sample of a voice that finished on the last frame stays until the next callback)
           float l = 0.0f, rr = 0.0f;
           if (live && (m.level == 1 || more))
             voice_frame_mod<TAB_LDS>(r, m, lane, prev, cur, incs, lds_tab, a.tables, a.count0 + (uint64_t)(i - m.level) + 1,

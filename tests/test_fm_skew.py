@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import golden_io as gio
+import mod_forms
 from oracle import cpuref
 from skred_amd import banks
 
@@ -67,11 +68,13 @@ def run(dev, bank, tables, g, interp, segments, skew, probe_ids=None):
     db.set_globals(g)
     db.set_fm_skew(skew)
     fmax = max(f for f, _ in segments)
+    counts = torch.zeros(2, dtype=torch.int32, device="cuda")     # which form the modulated kernel's waves ran
+    db.set_form_counter(counts.data_ptr())
     buf = None
     if probe_ids is not None:
         buf = torch.zeros(fmax * len(probe_ids) * 2, device="cuda")
         db.set_probe(probe_ids, buf.data_ptr())
-    mixes, probes, kernels = [], [], []
+    mixes, probes, kernels, states, forms = [], [], [], [], []
     for frames, event in segments:
         if event is not None:
             db.download(host)
@@ -79,6 +82,7 @@ def run(dev, bank, tables, g, interp, segments, skew, probe_ids=None):
             db.upload(host)
         if buf is not None:
             buf.zero_()
+        counts.zero_()
         # (other kernels' leftovers in LDS between our launches: the sample ring must not depend on what the previous launch of
         # the same bank left in it -- an uninitialised row once happened to hold exactly the right numbers that way)
         torch.sort(torch.rand(1 << 22, device="cuda"))
@@ -87,26 +91,38 @@ def run(dev, bank, tables, g, interp, segments, skew, probe_ids=None):
         torch.cuda.synchronize()
         mixes.append(out.cpu().numpy())
         kernels.append(db.last_kernel())
+        forms.append(counts.cpu().numpy().tolist())
         if buf is not None:
             probes.append(buf[:frames * len(probe_ids) * 2].cpu().numpy().reshape(frames, len(probe_ids), 2).copy())
-    db.download(host)
+        db.download(host)                   # (the device bank stays as it is: the state after every launch)
+        states.append(host.copy())
     if buf is not None:
         db.set_probe([], 0)
+    db.set_form_counter(0)
     db.close()
-    return np.concatenate(mixes), host, probes, kernels
+    return np.concatenate(mixes), states, probes, kernels, forms
 
 
 def oracle(bank, tables, g, interp, segments, probe_ids=None):
     host, gl = bank.copy(), g.copy()
-    mixes, stems = [], []
+    mixes, stems, states = [], [], []
     for frames, event in segments:
         if event is not None:
             event(host, gl.synth_sample_count)
         r = cpuref.render(host, gl, tables, frames, interp, want_stems=probe_ids is not None)
         mixes.append(cpuref.master(gl, r["sum64"].astype(np.float32)))
+        states.append(host.copy())
         if probe_ids is not None:
             stems.append(r["stems"][:, probe_ids, :].copy())
-    return np.concatenate(mixes), host, stems
+    return np.concatenate(mixes), states, stems
+
+
+def check_states(states, ref_states, tag):
+    """The device bank's state after every launch, bit for bit against the oracle's after the same launch."""
+    assert len(states) == len(ref_states)
+    for k, (got, want) in enumerate(zip(states, ref_states)):
+        bad = got.rw_equal(want)
+        assert not bad, (tag, f"launch {k}", bad)
 
 
 def _release_some(host, now):
@@ -135,10 +151,9 @@ def test_skewed_blocks_state_probes_and_mix(dev, recipe, interp, wild, hold):
     ref_mix, ref_state, ref_stems = oracle(bank, tables, g, interp, SEGS, ids)
     res = {}
     for skew in (1, 0):
-        mix, state, probes, kernels = run(dev, bank, tables, g, interp, SEGS, skew, ids)
+        mix, state, probes, kernels, _ = run(dev, bank, tables, g, interp, SEGS, skew, ids)
         assert kernels == [1] * len(SEGS), kernels
-        bad = state.rw_equal(ref_state)
-        assert not bad, (skew, bad)
+        check_states(state, ref_state, skew)
         for k, (got, want) in enumerate(zip(probes, ref_stems)):
             d = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
             assert len(d) == 0, f"skew={skew} launch {k}: {len(d)} probed values differ; first (frame, probe, ch) {d[0]}, voice {ids[d[0][1]]}: {got[tuple(d[0])]} vs {want[tuple(d[0])]}"
@@ -162,9 +177,9 @@ def test_waves_that_must_not_be_skewed(dev):
     ids = np.unique(np.concatenate([np.arange(64, 80), np.arange(128 + 8, 128 + 16), [192, 193, 194, 195, 192 + 43], np.arange(0, 8)])).astype(np.int32)
     segs = [(512, None), (100, None)]
     ref_mix, ref_state, ref_stems = oracle(bank, tables, g, 0, segs, ids)
-    mix, state, probes, kernels = run(dev, bank, tables, g, 0, segs, 1, ids)
+    mix, state, probes, kernels, _ = run(dev, bank, tables, g, 0, segs, 1, ids)
     assert kernels == [1, 1]
-    assert not state.rw_equal(ref_state), state.rw_equal(ref_state)
+    check_states(state, ref_state, 1)
     for got, want in zip(probes, ref_stems):
         assert gio.bits_equal(got, want)
     assert rel_rms(mix, ref_mix) <= 1e-5
@@ -217,10 +232,9 @@ def test_rich_skewed_blocks_chains_amp_pan_hold(dev, recipe, interp, wild):
     ref_mix, ref_state, ref_stems = oracle(bank, tables, g, interp, SEGS, ids)
     res = {}
     for skew in (1, 0):
-        mix, state, probes, kernels = run(dev, bank, tables, g, interp, SEGS, skew, ids)
+        mix, state, probes, kernels, _ = run(dev, bank, tables, g, interp, SEGS, skew, ids)
         assert kernels == [1] * len(SEGS), kernels
-        bad = state.rw_equal(ref_state)
-        assert not bad, (skew, bad)
+        check_states(state, ref_state, skew)
         for k, (got, want) in enumerate(zip(probes, ref_stems)):
             d = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
             assert len(d) == 0, f"skew={skew} launch {k}: {len(d)} probed values differ; first (frame, probe, ch) {d[0]}, voice {ids[d[0][1]]}: {got[tuple(d[0])]} vs {want[tuple(d[0])]}"
@@ -248,9 +262,9 @@ def test_audible_sources(dev):
     ref_mix, ref_state, ref_stems = oracle(bank, tables, g, 0, SEGS, ids)
     res = {}
     for skew in (1, 0):
-        mix, state, probes, kernels = run(dev, bank, tables, g, 0, SEGS, skew, ids)
+        mix, state, probes, kernels, _ = run(dev, bank, tables, g, 0, SEGS, skew, ids)
         assert kernels == [1] * len(SEGS), kernels
-        assert not state.rw_equal(ref_state), (skew, state.rw_equal(ref_state))
+        check_states(state, ref_state, skew)
         for k, (got, want) in enumerate(zip(probes, ref_stems)):
             d = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
             assert len(d) == 0, f"skew={skew} launch {k}: {len(d)} probed values differ; first (frame, probe, ch) {d[0]}, voice {ids[d[0][1]]}: {got[tuple(d[0])]} vs {want[tuple(d[0])]}"
@@ -269,9 +283,9 @@ def test_patch_bank_skewed_equals_exchange(dev, patch):
     ref_mix, ref_state, _ = oracle(bank, tables, g, 0, segs)
     res = {}
     for skew in (1, 0):
-        mix, state, _, kernels = run(dev, bank, tables, g, 0, segs, skew)
+        mix, state, _, kernels, _ = run(dev, bank, tables, g, 0, segs, skew)
         assert kernels == [1, 1]
-        assert not state.rw_equal(ref_state), (skew, state.rw_equal(ref_state))
+        check_states(state, ref_state, skew)
         assert rel_rms(mix, ref_mix) <= 1e-5
         res[skew] = mix
     assert gio.bits_equal(res[1], res[0])
@@ -370,10 +384,12 @@ def test_frame_lag_form_of_the_modulated_kernel(dev, recipe, interp):
     ref_mix, ref_state, _ = oracle(bank, tables, g, interp, segs)
     res = {}
     for lag in (1, 0):
-        mix, state, _, kernels = run(dev, bank, tables, g, interp, segs, lag)
+        mix, state, _, kernels, forms = run(dev, bank, tables, g, interp, segs, lag)
         assert kernels == [2] * len(segs), kernels
-        bad = state.rw_equal(ref_state)
-        assert not bad, (lag, bad)
+        check_states(state, ref_state, lag)
+        # every wavefront holds two-level (kind 2) and cross-level (kind 3) copies: all of them stay on the level loop
+        assert not mod_forms.lag_groups(bank).any()
+        assert forms == [mod_forms.expected_counts(bank, f, lag) for f, _ in segs] == [[0, n // 64]] * len(segs), forms
         assert rel_rms(mix, ref_mix) <= 1e-5
         res[lag] = mix
     assert gio.bits_equal(res[1], res[0])

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 import golden_io as gio
+import mod_forms
 from oracle import cpuref
 from skred_amd import banks
 from skred_amd.bank import VoiceBank
@@ -151,12 +152,15 @@ def expected_slots_mod(bank, limit=32):
     return s if s <= limit else 0
 
 
-def run_blocks(dev, bank, tables, g, blocks, pack, probe_ids=None, actions=None):
+def run_blocks(dev, bank, tables, g, blocks, pack, probe_ids=None, actions=None, skew=1):
     """Render `blocks` (frame counts) on a fresh device bank; actions[k](db, host_bank) runs before block k.  Returns the device
-    bank's downloaded state, the mixes, the probe rows, (last_kernel, last_pack) per block, violations."""
+    bank's downloaded state, the mixes, the probe rows, (last_kernel, last_pack, expected slots, [lag waves, level-loop waves] of
+    the modulated kernel) per block, violations."""
     import torch
     db = dev.DeviceBank(bank.n)
-    db.set_tables(tables); db.upload(bank); db.set_globals(g); db.set_pack(pack)
+    db.set_tables(tables); db.upload(bank); db.set_globals(g); db.set_pack(pack); db.set_fm_skew(skew)
+    counts = torch.zeros(2, dtype=torch.int32, device="cuda")
+    db.set_form_counter(counts.data_ptr())
     host = bank.copy()
     buf = None
     if probe_ids is not None:
@@ -167,12 +171,14 @@ def run_blocks(dev, bank, tables, g, blocks, pack, probe_ids=None, actions=None)
         if actions and k in actions:
             actions[k](db, host)
         out = torch.zeros(f, 2, device="cuda")
+        counts.zero_()
         db.render_mix(f, out.data_ptr(), 2, 0, 0)
         torch.cuda.synchronize()
         mixes.append(out.cpu().numpy())
         if buf is not None:
             probes.append(buf[:f * len(probe_ids) * 2].cpu().numpy().reshape(f, len(probe_ids), 2).copy())
-        kinds.append((db.last_kernel(), db.last_pack(), expected_slots(host)))
+        kinds.append((db.last_kernel(), db.last_pack(), expected_slots(host), counts.cpu().numpy().tolist()))
+    db.set_form_counter(0)
     got = bank.copy()
     db.download(got)
     viol = db.list_violations()
@@ -312,9 +318,53 @@ def test_tiled_18sk_runs_packed_on_the_modulated_kernel(dev):
     ref, ref_mixes, _ = oracle_blocks(bank, tables, g, blocks)
     got, mixes, _, kinds, viol = run_blocks(dev, bank, tables, g, blocks, 2)
     assert viol == 0 and all(k[0] == 2 and k[1] == 16 for k in kinds), kinds
+    # every 64-voice group of 18.sk passes the lag vote, so every packed wave (four groups of 16 lanes) runs the frame-lag form
+    assert mod_forms.lag_groups(bank).all()
+    assert all(k[3] == [n // 64 * 16 // 64, 0] for k in kinds), kinds
     assert not got.rw_equal(ref), got.rw_equal(ref)
     for k in range(len(blocks)):
         assert rel_rms(mixes[k], ref_mixes[k]) <= 1e-5
+
+
+@pytest.mark.parametrize("seed", [41, 42])
+def test_silent_named_voice_with_a_modulator_of_its_own(dev, seed):
+    """A voice that cannot sound (amp 0) keeps a lane because a sounding voice names it as its frequency modulator, and itself names
+    a modulator that has no lane (silent, named by nobody that sounds).  Its routing is never used: packed, with the skewed blocks
+    on and off, the one-voice kernel renders the whole bank's state bit for bit against the oracle."""
+    n = 4096
+    bank, tables, g = sparse_bank(seed, n, 5)
+    rng = np.random.default_rng(seed)
+    amp = np.asarray(bank["voice_amp"])
+    planted = 0
+    for g0 in range(0, n, 64):
+        live = np.flatnonzero(amp[g0:g0 + 64] != 0)
+        named = set()
+        for key in ("voice_freq_mod_osc", "voice_amp_mod_osc", "voice_pan_mod_osc"):
+            m = np.asarray(bank[key])[g0 + live]
+            named |= set((m[m >= 0] - g0).tolist())
+        c = int(live.min())
+        quiet = [l for l in range(c + 1, 64) if amp[g0 + l] == 0 and l not in named]
+        if len(quiet) < 2:
+            continue
+        s, t = sorted(rng.choice(quiet, 2, replace=False))
+        bank["voice_freq_mod_osc"][g0 + c] = g0 + s
+        bank["voice_freq_mod_depth"][g0 + c] = np.float32(0.3)
+        bank["voice_freq_mod_osc"][g0 + s] = g0 + t
+        bank["voice_freq_mod_depth"][g0 + s] = np.float32(0.5)
+        planted += 1
+    assert planted > n // 64 // 2
+    blocks = [400, 64, 33]
+    ref, ref_mixes, _ = oracle_blocks(bank, tables, g, blocks)
+    mixes = {}
+    for skew in (1, 0):
+        got, mixes[skew], _, kinds, viol = run_blocks(dev, bank, tables, g, blocks, 2, skew=skew)
+        assert all(k[0] == 1 and k[1] > 0 and k[1] == k[2] for k in kinds), kinds
+        bad = got.rw_equal(ref)
+        assert not bad, (skew, bad)
+        for k in range(len(blocks)):
+            assert rel_rms(mixes[skew][k], ref_mixes[k]) <= 1e-5, (skew, k)
+    for a, b in zip(mixes[1], mixes[0]):
+        assert gio.bits_equal(a, b)
 
 
 def test_voices_switched_on_and_off_between_blocks(dev):
