@@ -344,13 +344,25 @@ enum { SKRED_OPT_FORCE_GENERIC = 1, SKRED_OPT_FAST2_MIN_VOICES = 2 /* bank size 
                              the exchange.  0: the per-frame ds_bpermute exchange everywhere.  The same option
                              governs the modulated kernel's FRAME-LAG form (a modulator BELOW its carrier -- a same-frame dependency,
                              18.sk -- with one dependency level: the dependent lanes run one frame behind instead of every frame being
-                             rendered once per level).  Same bits either way */ };
+                             rendered once per level).  Same bits either way */,
+       SKRED_OPT_CROSS_GROUP = 11 /* modulators outside the carrier's aligned 64-voice group (an LFO voice read by thousands of voices,
+                             patches laid out back to back across group edges).  0 (default): a bank with such a routing is refused
+                             (SKRED_E_UNSUPPORTED) at every render.  1: rendered through a per-block SOURCE TAPE -- the sample
+                             sequences of the cross-group modulators ("sources") are rendered ahead of the block by pre-pass launches
+                             of the modulated kernel, one launch per level of the graph of groups (an edge from a reader's group to
+                             its source's group), and read by their readers; same bits as the reference's index-order walk.  Limits
+                             (each refused with SKRED_E_UNSUPPORTED / SKRED_E_RANGE, the bank stays usable): modulators outside the
+                             bank; a cycle between groups; chains that need more than 16 pre-pass launches; a tape of more than
+                             256 MiB (sources x (frames + 1) x 4 bytes).  Such banks run on the modulated kernel; the specialised
+                             kernels, shards and the drop-in mode do not read the tape (skred_bank_last_cross_group) */ };
 enum { SKRED_KERNEL_GENERIC = 0, SKRED_KERNEL_FAST = 1, SKRED_KERNEL_MODULATED = 2, SKRED_KERNEL_FAST2 = 3 };
 int  skred_bank_set_option(skred_bank_t *bank, int option, int value);
 int  skred_bank_last_kernel(const skred_bank_t *bank);   /* SKRED_KERNEL_* of the latest render */
 int  skred_bank_last_in_place(const skred_bank_t *bank);  /* 1: the latest block rendered its motion list in place (SKRED_OPT_IN_PLACE) */
 int  skred_bank_last_pack(const skred_bank_t *bank);      /* lanes per 64-voice group in the latest block (SKRED_OPT_PACK), 0: not packed */
 int  skred_bank_last_split(const skred_bank_t *bank);     /* 1: the latest block ran the split form of the one-voice kernel (SKRED_OPT_SPLIT) */
+/* SKRED_OPT_CROSS_GROUP: for the latest block, the number of tape sources and of pre-pass launches (0, 0: it read no tape) */
+int  skred_bank_last_cross_group(const skred_bank_t *bank, int *n_sources, int *n_levels);
 
 /* Per-frame evidence from INSIDE the fast paths (tests).  A launch with the full stem buffer takes the kernels' frame-by-frame
  * paths, so the 8-frame block paths the benchmarks time were only ever seen through end-of-block state and the mix.  A probe names

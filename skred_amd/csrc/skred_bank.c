@@ -173,6 +173,10 @@ void skred_bank_destroy(skred_bank_t *b) {
   if (b->d_stems) hipFree(b->d_stems);
   free(b->h_class); free(b->h_mod); free(b->h_level);
   free(b->h_pack_mask); free(b->h_pack_dirty);
+  free(b->h_esc); free(b->h_slot);
+  if (b->d_slot) hipFree(b->d_slot);
+  if (b->d_tape_groups) hipFree(b->d_tape_groups);
+  if (b->d_tape) hipFree(b->d_tape);
   if (b->d_pack_mask) hipFree(b->d_pack_mask);
   sk_queue_free(b);
   sk_patterns_free(b);
@@ -283,6 +287,7 @@ static int pack_refresh(skred_bank_t *b) {
       uint64_t w = 0;
       for (int l = 0; l < 64; l++) {
         const int v = g * 64 + l;
+        if (b->h_slot && b->h_slot[v] >= 0) w |= (uint64_t)1 << l;   /* a tape source keeps its lane (and its voice_sample) */
         if (!(b->h_class[v] & SKC_LIVE)) continue;
         w |= (uint64_t)1 << l;
         for (int k = 0; k < 4; k++) {
@@ -305,11 +310,142 @@ static int pack_refresh(skred_bank_t *b) {
   return most;
 }
 
+/* Cross-group modulation (SKRED_OPT_CROSS_GROUP): the plan of the tape, made again whenever a cross-group routing changed.
+ * Every distinct source gets a slot (in the order its first reader comes); the groups form a graph, an edge from a reader's
+ * group to its source's group; a source group's pre-pass level is 0 when it reads no tape, else 1 + the highest level it reads.
+ * A cycle between groups, or a chain that needs more than SK_TAPE_MAX_LEVELS pre-pass launches, is refused (the refusal stands,
+ * render after render, until the routing changes).  A refused or empty plan leaves no source. */
+typedef struct { int rg, sg, reader, source; } sk_tape_edge_t;
+static int tape_refuse(skred_bank_t *b, const char *fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b->tape_msg, sizeof(b->tape_msg), fmt, ap);
+  va_end(ap);
+  b->tape_rc = SKRED_E_UNSUPPORTED;
+  b->tape_sources = b->tape_levels = 0;
+  return fail(b->tape_rc, "%s", b->tape_msg);
+}
+static int tape_plan(skred_bank_t *b) {
+  if (!b->tape_dirty) return b->tape_rc ? fail(b->tape_rc, "%s", b->tape_msg) : SKRED_OK;
+  b->tape_dirty = 0;
+  b->tape_rc = 0;
+  b->tape_sources = b->tape_levels = 0;
+  if (!b->h_esc) return SKRED_OK;
+  const int n = b->n_padded, G = n / 64;
+  /* the sources of the old plan lose their lanes (pack_refresh), those of the new one get theirs */
+  for (int v = 0; v < n; v++)
+    if (b->h_slot[v] >= 0) { b->h_slot[v] = -1; b->h_pack_dirty[v >> 6] = 1; b->pack_any_dirty = 1; }
+  size_t n_edges = 0, cap = 0;
+  sk_tape_edge_t *edges = NULL;
+  int *first = (int *)calloc((size_t)G + 1, sizeof(int));
+  int *lvl = (int *)malloc((size_t)G * sizeof(int)), *state = (int *)calloc((size_t)G, sizeof(int));
+  int *stack = (int *)malloc((size_t)G * sizeof(int)), *iter = (int *)malloc((size_t)G * sizeof(int));
+  int rc = SKRED_OK, n_src = 0;
+  if (!first || !lvl || !state || !stack || !iter) { rc = fail(SKRED_E_NO_MEM, "cross-group plan"); goto out; }
+  for (int g = 0; g < G; g++) {
+    first[g] = (int)n_edges;
+    for (int l = 0; l < 64; l++) {
+      const int v = g * 64 + l;
+      for (int k = 0; k < 4; k++) {
+        const int md = b->h_esc[(size_t)k * n + v];
+        if (md < 0) continue;
+        if (b->h_slot[md] < 0) { b->h_slot[md] = n_src++; b->h_pack_dirty[md >> 6] = 1; b->pack_any_dirty = 1; }
+        int dup = 0;                                   /* (a group's readers mostly name the same few groups) */
+        for (size_t e = n_edges; e > (size_t)first[g] && e + 16 > n_edges; e--) if (edges[e - 1].sg == (md >> 6)) { dup = 1; break; }
+        if (dup) continue;
+        if (n_edges == cap) {
+          cap = cap ? 2 * cap : 1024;
+          sk_tape_edge_t *ne = (sk_tape_edge_t *)realloc(edges, cap * sizeof(*edges));
+          if (!ne) { rc = fail(SKRED_E_NO_MEM, "cross-group plan"); goto out; }
+          edges = ne;
+        }
+        edges[n_edges++] = (sk_tape_edge_t){ g, md >> 6, v, md };
+      }
+    }
+  }
+  first[G] = (int)n_edges;
+  if (n_src == 0) goto out;
+  /* pre-pass levels: depth-first from every source group, iteratively (a chain may run through many groups) */
+  for (int g = 0; g < G; g++) lvl[g] = 0;
+  for (int s0 = 0; s0 < G && rc == SKRED_OK; s0++) {
+    if (state[s0] != 0) continue;
+    int src_here = 0;
+    for (int l = 0; l < 64 && !src_here; l++) src_here = b->h_slot[s0 * 64 + l] >= 0;
+    if (!src_here) continue;
+    int top = 0;
+    stack[0] = s0; iter[0] = first[s0]; state[s0] = 1;
+    while (top >= 0) {
+      const int g = stack[top];
+      if (iter[top] < first[g + 1]) {
+        const sk_tape_edge_t *e = &edges[iter[top]++];
+        const int h = e->sg;
+        if (state[h] == 1) {
+          rc = tape_refuse(b, "cross-group modulation: the groups of voice %d and voice %d read each other (a cycle between "
+                              "64-voice groups: voice %d reads voice %d)", e->reader, e->source, e->reader, e->source);
+          break;
+        }
+        if (state[h] == 0) { state[h] = 1; ++top; stack[top] = h; iter[top] = first[h]; }
+        else if (lvl[h] + 1 > lvl[g]) lvl[g] = lvl[h] + 1;
+      } else {
+        state[g] = 2;
+        if (lvl[g] >= SK_TAPE_MAX_LEVELS) {
+          const sk_tape_edge_t *e = &edges[first[g]];
+          rc = tape_refuse(b, "cross-group modulation: a chain of groups %d deep (voice %d reads voice %d, which ...): at most %d "
+                              "pre-pass levels", lvl[g] + 1, e->reader, e->source, SK_TAPE_MAX_LEVELS);
+          break;
+        }
+        if (--top >= 0 && lvl[g] + 1 > lvl[stack[top]]) lvl[stack[top]] = lvl[g] + 1;
+      }
+    }
+  }
+  if (rc) { n_src = 0; goto out; }
+  {
+    /* the source groups, level by level */
+    int n_sg = 0, levels = 0;
+    for (int g = 0; g < G; g++) {
+      int src_here = 0;
+      for (int l = 0; l < 64 && !src_here; l++) src_here = b->h_slot[g * 64 + l] >= 0;
+      state[g] = src_here;
+      if (src_here) { n_sg++; if (lvl[g] + 1 > levels) levels = lvl[g] + 1; }
+    }
+    int at = 0;
+    for (int l = 0; l < levels; l++) {
+      b->tape_level_off[l] = at;
+      for (int g = 0; g < G; g++) if (state[g] && lvl[g] == l) stack[at++] = g;
+    }
+    b->tape_level_off[levels] = at;
+    /* (the previous block may still read the maps) */
+    if (hipDeviceSynchronize() != hipSuccess) { rc = fail(SKRED_E_NO_DEVICE, "cross-group plan: synchronize"); n_src = 0; goto out; }
+    if ((size_t)n_sg > b->tape_groups_cap) {
+      if (b->d_tape_groups) hipFree(b->d_tape_groups);
+      b->d_tape_groups = NULL; b->tape_groups_cap = 0;
+      if (hipMalloc((void **)&b->d_tape_groups, (size_t)n_sg * sizeof(int32_t)) != hipSuccess) { rc = fail(SKRED_E_NO_MEM, "tape groups"); n_src = 0; goto out; }
+      b->tape_groups_cap = (size_t)n_sg;
+    }
+    if (!b->d_slot && hipMalloc((void **)&b->d_slot, (size_t)n * sizeof(int32_t)) != hipSuccess) { b->d_slot = NULL; rc = fail(SKRED_E_NO_MEM, "tape slots"); n_src = 0; goto out; }
+    if (hipMemcpy(b->d_tape_groups, stack, (size_t)n_sg * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->d_slot, b->h_slot, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+      rc = fail(SKRED_E_NO_DEVICE, "cross-group plan: upload"); n_src = 0; goto out;
+    }
+    b->tape_levels = levels;
+  }
+out:
+  if (rc && rc != SKRED_E_UNSUPPORTED) b->tape_dirty = 1;   /* (no memory / device: try again at the next render) */
+  if (n_src == 0) for (int v = 0; v < n; v++) b->h_slot[v] = -1;   /* (no plan: no source keeps a lane for the tape) */
+  b->tape_sources = n_src;
+  free(edges); free(first); free(lvl); free(state); free(stack); free(iter);
+  return rc;
+}
+
 /* Pick the kernel.  The fast kernel (skred_render_fast.hip: sk_render_fast_kernel) is valid when, over
  * all voices that can sound: none is "exotic" (stopping one-shot, reverse, sample&hold, bit-crush,
  * noise, modulated, smoother off, non-finite phase data), and the biquad / the envelope are each used
  * by all of them or by none.  Anything else runs the generic kernel; both give identical samples. */
 static int classify(skred_bank_t *b) {
+  if (b->tape_dirty || b->tape_rc) {                         /* (the cross-group routings changed; or they were refused) */
+    const int rc = tape_plan(b);
+    if (rc) return rc;
+  }
   if (!b->class_dirty) return SKRED_OK;
   const int real = b->cnt_real, filt = b->cnt_filter, env = b->cnt_env, exotic = b->cnt_exotic;
   uint32_t m = 0;
@@ -359,6 +495,7 @@ int skred_bank_set_option(skred_bank_t *b, int option, int value) {
     case SKRED_OPT_SPLIT: b->split_mode = value < 0 ? 0 : value > 3 ? 3 : value; return SKRED_OK;
     case SKRED_OPT_PACK: b->pack_mode = value < 0 ? 0 : value > 2 ? 2 : value; return SKRED_OK;
     case SKRED_OPT_FM_SKEW: b->fm_skew = value != 0; return SKRED_OK;
+    case SKRED_OPT_CROSS_GROUP: b->cross_group = value != 0; return SKRED_OK;
     default: return fail(SKRED_E_BAD_ARG, "unknown option %d", option);
   }
 }
@@ -390,6 +527,12 @@ int skred_bank_last_kernel(const skred_bank_t *b) { return b ? b->last_kernel : 
 int skred_bank_last_in_place(const skred_bank_t *b) { return b ? b->last_in_place : 0; }
 int skred_bank_last_split(const skred_bank_t *b) { return b ? b->last_split : 0; }
 int skred_bank_last_pack(const skred_bank_t *b) { return b ? b->last_pack : 0; }
+int skred_bank_last_cross_group(const skred_bank_t *b, int *n_sources, int *n_levels) {
+  if (!b) return fail(SKRED_E_BAD_ARG, "last_cross_group: no bank");
+  if (n_sources) *n_sources = b->last_tape_sources;
+  if (n_levels) *n_levels = b->last_tape_levels;
+  return SKRED_OK;
+}
 unsigned skred_bank_list_violations(const skred_bank_t *b) { return b ? b->violations_seen : 0u; }
 
 int skred_bank_download(skred_bank_t *b, skred_voice_bank_t *h, int src_first, int dst_first, int count) {
@@ -512,12 +655,34 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
                         int num_channels, hipStream_t s) {
   if (interp != SKRED_INTERP_TRUNCATE && interp != SKRED_INTERP_LINEAR) return fail(SKRED_E_BAD_ARG, "render: interp %d", interp);
   if (!b->d_tables) return fail(SKRED_E_BAD_ARG, "render: no table pool set");
-  if ((b->features & (SKB_ANY_MOD | SKB_ANY_FM)) && b->cnt_escapes > 0)
-    return fail(SKRED_E_UNSUPPORTED, "a voice is modulated by a voice outside its aligned 64-voice group: "
-                                     "keep modulator and carrier in the same group (SURVEY 8e)");
+  if ((b->features & (SKB_ANY_MOD | SKB_ANY_FM)) && b->cnt_escapes > 0) {
+    if (!b->cross_group)
+      return fail(SKRED_E_UNSUPPORTED, "a voice is modulated by a voice outside its aligned 64-voice group: "
+                                       "keep modulator and carrier in the same group (SURVEY 8e)");
+    if (b->cnt_outside > 0) return fail(SKRED_E_UNSUPPORTED, "a voice is modulated by a voice outside the bank");
+  }
+  if (b->esc_nomem) return fail(SKRED_E_NO_MEM, "cross-group modulators: host storage");
   HIP_TRY(hipSetDevice(b->device));
   int rc = classify(b);
   if (rc) return rc;
+  /* cross-group modulation: the tape of this block (a voice's cross-group modulators are tape codes in its SKP_MODI word from the
+   * moment it was written, so such a bank never runs without the tape) */
+  const int tape = b->cross_group && b->tape_sources > 0;
+  sk_tape_args_t ta;
+  memset(&ta, 0, sizeof(ta));
+  if (tape) {
+    if (!(b->features & SKB_ANY_MOD)) return fail(SKRED_E_UNSUPPORTED, "cross-group modulation outside the modulated kernel");
+    const size_t need = (size_t)b->tape_sources * ((size_t)num_frames + 1);
+    if (need * sizeof(float) > SK_TAPE_MAX_BYTES)
+      return fail(SKRED_E_RANGE, "cross-group modulation: %d sources x %d frames need a tape of %zu bytes (at most %zu)",
+                  b->tape_sources, num_frames + 1, need * sizeof(float), (size_t)SK_TAPE_MAX_BYTES);
+    if (need > b->tape_cap) {
+      HIP_TRY(hipDeviceSynchronize());               /* (a block on another stream may still read the old tape) */
+      if ((rc = grow(&b->d_tape, &b->tape_cap, need))) return rc;
+    }
+    ta.tape = b->d_tape;
+    ta.slot = b->d_slot;
+  }
   poll_reports(b);
   /* the modulated kernel serves every kind of modulation; banks whose only modulation is previous-frame FM stay on
    * the one-per-lane kernel when they are otherwise clean */
@@ -798,7 +963,17 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
     if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "gain kernel launch -> %s", hipGetErrorString(e));
     b->mask_p ^= 1;                                                  /* it wrote the next block's list */
   }
-  if (modulated) {
+  if (modulated && tape) {
+    /* the pre-pass, level by level, then the main launch: same stream, after every launch of the block that writes state */
+    for (int l = 0; l < b->tape_levels; l++) {
+      sk_tape_args_t tl = ta;
+      tl.groups = b->d_tape_groups + b->tape_level_off[l];
+      tl.n_list = b->tape_level_off[l + 1] - b->tape_level_off[l];
+      e = (hipError_t)sk_launch_tape_prepass(&a, b->d_level, b->max_level, &tl, s);
+      if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "tape pre-pass launch -> %s", hipGetErrorString(e));
+    }
+    e = (hipError_t)sk_launch_render_mod_tape(&a, n_wg, b->d_level, b->max_level, &ta, s);
+  } else if (modulated) {
     e = (hipError_t)sk_launch_render_mod(&a, n_wg, b->d_level, b->max_level, s);
   } else {
     e = (hipError_t)sk_launch_render(&a, n_wg, s);
@@ -817,6 +992,8 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
   b->last_in_place = inplace;
   b->last_split = split;
   b->last_pack = pack_s;
+  b->last_tape_sources = tape ? b->tape_sources : 0;
+  b->last_tape_levels = tape ? b->tape_levels : 0;
 
   /* advance the timeline exactly as synth.c:521,525 do: one count and one LCG draw per frame */
   b->g.synth_sample_count += (uint64_t)num_frames;

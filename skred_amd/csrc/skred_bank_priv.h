@@ -111,6 +111,23 @@ struct skred_bank {
   int cnt_pair_ap;            /* pair-shaped carriers whose amplitude or pan is modulated too (SKC_PAIR_AP) */
   int cnt_fm_odd;             /* SKC_FM voices that are not the even half of a (carrier, next voice) pair (SKC_FM_ODD) */
   int cnt_escapes;            /* voices naming a modulator outside their aligned 64-voice group (SKC_ESCAPES) */
+  int cnt_outside;            /* ... of them, voices naming a modulator outside the bank (SKC_OUTSIDE): refused even with cross_group */
+  /* cross-group modulation (SKRED_OPT_CROSS_GROUP; skred_device_layout.h: sk_tape_args_t; skred_bank.c: tape_plan) */
+  int cross_group;            /* SKRED_OPT_CROSS_GROUP: 0 refuse such banks (default), 1 render them through the tape */
+  int32_t *h_esc;             /* [4][n_padded] each voice's fm / am / pan / cz modulator when it sits in another group of the bank, else -1;
+                                 allocated when the first such routing appears (NULL until then) */
+  int esc_nomem;              /* ... that allocation failed: the bank refuses to render */
+  int tape_dirty;             /* h_esc changed: the sources, the group graph and the pre-pass levels are planned again */
+  int tape_rc;                /* != 0: the current plan was refused (a cycle, too deep); tape_msg says why */
+  char tape_msg[256];
+  int32_t *h_slot, *d_slot;   /* [n_padded] voice -> its tape slot, -1: not a source (allocated with h_esc) */
+  int32_t *d_tape_groups;     /* the source groups, level by level (ascending inside a level) */
+  size_t tape_groups_cap;     /* entries */
+  int tape_level_off[SK_TAPE_MAX_LEVELS + 1];   /* level l: d_tape_groups[off[l], off[l + 1]) */
+  int tape_sources, tape_levels;                /* of the current plan */
+  float *d_tape;              /* [tape_sources][num_frames + 1] */
+  size_t tape_cap;            /* floats */
+  int last_tape_sources, last_tape_levels;      /* of the latest block (0, 0: it read no tape) */
   int mod_dirty;              /* modulator lanes changed: dependency levels must be recomputed */
   uint32_t fast_mode;         /* SKM_* from classify() */
   int force_generic;          /* SKRED_OPT_FORCE_GENERIC */
@@ -164,7 +181,9 @@ struct skred_bank {
                            linear lookup runs the instantiations without the fold test */
 #define SKC_LIVE 1024u  /* can sound as far as its parameters say: a usable table and voice_amp != 0 (synth.c:537; a voice that has
                            finished is a matter of state, not of class) */
-#define SKC_ESCAPES 128u /* names a modulator outside its aligned 64-voice group: the bank cannot be rendered until that is fixed */
+#define SKC_ESCAPES 128u /* names a modulator outside its aligned 64-voice group: the bank cannot be rendered until that is fixed
+                            (SKRED_OPT_CROSS_GROUP: unless the modulator is in the bank -- then it is read from the tape) */
+#define SKC_OUTSIDE 2048u /* with SKC_ESCAPES: the modulator is outside the bank (md < 0 or md >= n_voices): always refused */
 
 
 int skred_amd_set_error(int code, const char *fmt, ...);
@@ -183,6 +202,7 @@ int skred_amd_set_error(int code, const char *fmt, ...);
 typedef struct {
   uint16_t cls;         /* SKC_* */
   int8_t mod_lane[4];   /* modulator lane inside the 64-voice group (fm, am, pan, cz) or -1 */
+  int32_t esc[4];       /* the modulator's voice index when it sits in another group of the bank (a tape source), else -1 */
   uint32_t features;    /* SKB_* this voice needs */
 } sk_voice_meta_t;
 

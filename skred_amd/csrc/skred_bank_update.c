@@ -33,6 +33,7 @@ int sk_pack_voice(const skred_bank_t *b, const skred_voice_bank_t *h, int v, int
   memset(ro, 0, SKP_COUNT * sizeof(sk_plane_t));
   memset(rw, 0, SKS_COUNT * sizeof(sk_plane_t));
   memset(meta, 0, sizeof(*meta));
+  for (int k = 0; k < 4; k++) meta->esc[k] = -1;
   const int size = h->voice_table_size[v];
   const int64_t off = h->voice_table_offset[v];
   const int noise = h->voice_wave_table_index[v] == SKRED_WAVE_TABLE_NOISE_ALT;
@@ -131,19 +132,22 @@ int sk_pack_voice(const skred_bank_t *b, const skred_voice_bank_t *h, int v, int
   ro[SKP_FILT].w[2] = f2u(f->a2); ro[SKP_FILT].w[3] = f2u(h->voice_cz_distortion[v]);
   {
     /* modulator indices: host index -> lane inside the carrier's 64-voice device group, -1 = unused
-     * (FM ignores a self reference, synth.c:549; the CZ source only matters with CZ on, synth.c:262) */
+     * (FM ignores a self reference, synth.c:549; the CZ source only matters with CZ on, synth.c:262).  A modulator in another
+     * group of the bank: the tape code -2 - md (skred_device_layout.h: sk_tape_args_t); the lane stays -1, so the dependency
+     * levels and the packed words of the carrier's group do not see it */
     int src[4] = { h->voice_freq_mod_osc[v], h->voice_amp_mod_osc[v], h->voice_pan_mod_osc[v],
                    h->voice_cz_mode[v] ? h->voice_cz_mod_osc[v] : -1 };
     if (src[0] == v) src[0] = -1;
     for (int k = 0; k < 4; k++) {
-      int lane_k = -1;
+      int lane_k = -1, word = -1;
       if (src[k] >= 0) {
         const int md = src[k] + (dst - v);
-        if (md < 0 || md >= b->n_voices || (md >> 6) != (dst >> 6)) meta->cls |= SKC_ESCAPES;
-        else lane_k = md & 63;
+        if (md < 0 || md >= b->n_voices) meta->cls |= SKC_ESCAPES | SKC_OUTSIDE;
+        else if ((md >> 6) != (dst >> 6)) { meta->cls |= SKC_ESCAPES; meta->esc[k] = md; word = -2 - md; }
+        else lane_k = word = md & 63;
       }
       meta->mod_lane[k] = (int8_t)lane_k;
-      ro[SKP_MODI].w[k] = (uint32_t)(int32_t)lane_k;
+      ro[SKP_MODI].w[k] = (uint32_t)(int32_t)word;
     }
   }
   ro[SKP_MODF].w[0] = f2u(h->voice_freq_mod_depth[v]); ro[SKP_MODF].w[1] = f2u(h->voice_freq_scale[v]);
@@ -170,6 +174,7 @@ void sk_apply_meta(skred_bank_t *b, int dst, const sk_voice_meta_t *m, int param
     /* per-voice bits that are not kernel classes: counted whether or not the voice can sound, and recounted whenever the
      * voice is written again -- a routing that escaped its group stops blocking the bank once it is fixed */
     b->cnt_escapes += ((now & SKC_ESCAPES) != 0) - ((old & SKC_ESCAPES) != 0);
+    b->cnt_outside += ((now & SKC_OUTSIDE) != 0) - ((old & SKC_OUTSIDE) != 0);
     b->h_class[dst] = now;
     b->class_dirty = 1;
     if ((old ^ now) & SKC_LIVE) { b->h_pack_dirty[dst >> 6] = 1; b->pack_any_dirty = 1; }
@@ -179,6 +184,21 @@ void sk_apply_meta(skred_bank_t *b, int dst, const sk_voice_meta_t *m, int param
     if (*slot != m->mod_lane[k]) { *slot = m->mod_lane[k]; b->mod_dirty = 1; b->class_dirty = 1; b->h_pack_dirty[dst >> 6] = 1; b->pack_any_dirty = 1; }
   }
   if ((b->features | m->features) != b->features) { b->features |= m->features; b->class_dirty = 1; b->mod_dirty = 1; }
+  /* cross-group modulators: kept on the host (the tape's plan is made from them); nothing is allocated before the first one */
+  if (!b->h_esc && (m->esc[0] >= 0 || m->esc[1] >= 0 || m->esc[2] >= 0 || m->esc[3] >= 0)) {
+    const size_t n = (size_t)b->n_padded;
+    b->h_esc = (int32_t *)malloc(4 * n * sizeof(int32_t));
+    b->h_slot = (int32_t *)malloc(n * sizeof(int32_t));
+    if (!b->h_esc || !b->h_slot) { free(b->h_esc); free(b->h_slot); b->h_esc = b->h_slot = NULL; b->esc_nomem = 1; return; }
+    memset(b->h_esc, -1, 4 * n * sizeof(int32_t));
+    memset(b->h_slot, -1, n * sizeof(int32_t));
+  }
+  if (b->h_esc) {
+    for (int k = 0; k < 4; k++) {
+      int32_t *slot = &b->h_esc[(size_t)k * b->n_padded + dst];
+      if (*slot != m->esc[k]) { *slot = m->esc[k]; b->tape_dirty = 1; b->class_dirty = 1; }
+    }
+  }
 }
 
 /* ------------------------------------------------------------------ batches of voice updates */

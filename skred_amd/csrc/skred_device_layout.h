@@ -230,6 +230,21 @@ typedef struct {
 } sk_render_args_t;
 #define SK_PROBE_MAX 64
 
+/* ---- cross-group modulation (SKRED_OPT_CROSS_GROUP; skred_render_generic.hip: sk_render_mod_tape_kernel) ----
+ * A voice whose modulator sits in another aligned 64-voice group holds a TAPE CODE in its SKP_MODI word instead of a lane:
+ * -2 - md (md: the modulator's voice index, any value below -1).  The block's per-voice sample sequences of those modulators
+ * ("sources") are rendered ahead of the main launch, one pre-pass launch per level of the group graph, into the tape:
+ * tape[slot][num_frames + 1], entry 0 the voice_sample of the state at block start, entry i + 1 the sample after frame i
+ * (0 on a frame the source is skipped). */
+#define SK_TAPE_MAX_LEVELS 16                        /* pre-pass launches per block at most */
+#define SK_TAPE_MAX_BYTES ((size_t)256 << 20)        /* n_sources * (num_frames + 1) * 4 bytes at most */
+typedef struct {
+  float *tape;              /* [n_sources][num_frames + 1] */
+  const int32_t *slot;      /* [n_padded] voice -> its tape slot, -1: not a source */
+  const int32_t *groups;    /* pre-pass only: the 64-voice groups of this level, one per wavefront */
+  int32_t n_list;           /* ... their number */
+} sk_tape_args_t;
+
 #define SK_FINISH_SLABS 32     /* slabs of the two-level mix-down (a multiple of 8: the workgroups of a slab share an XCD's L2
                                   under round-robin placement -- speed only) */
 #define SK_FINISH_FLAT_MAX 64  /* up to this many rows the last arriver adds the rows directly */

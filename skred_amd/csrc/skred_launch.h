@@ -2,7 +2,7 @@
  * skred_launch.h -- C-linkage launch entry points of the HIP translation units (internal to
  * libskred_amd.so; the public ABI is include/skred_amd.h).
  *
- *   skred_render_generic.hip  sk_launch_render (dispatcher), sk_launch_render_mod
+ *   skred_render_generic.hip  sk_launch_render (dispatcher), sk_launch_render_mod, sk_launch_render_mod_tape, sk_launch_tape_prepass
  *   skred_render_fast.hip     sk_launch_render_fast
  *   skred_render_split.hip    sk_launch_render_split, sk_split_lds_bytes
  *   skred_render_fast2.hip    sk_launch_render_fast2, sk_launch_env_fast2, sk_env2_grid, sk_launch_classify
@@ -34,6 +34,13 @@ int sk_launch_render(const sk_render_args_t *args, int n_workgroups, hipStream_t
 /* banks with modulators: one aligned 64-voice group per wavefront, dependency levels in `levels` */
 int sk_launch_render_mod(const sk_render_args_t *args, int n_workgroups, const int *levels, int max_level,
                          hipStream_t stream);
+/* cross-group modulation (SKRED_OPT_CROSS_GROUP): the main launch, whose modulator fields below -1 are read from t->tape, and one
+ * pre-pass launch that writes the tape rows of the sources in the t->n_list groups t->groups (one wavefront each); the pre-pass
+ * launches of a block go level by level ahead of the main launch, all on the same stream */
+int sk_launch_render_mod_tape(const sk_render_args_t *args, int n_workgroups, const int *levels, int max_level,
+                              const sk_tape_args_t *t, hipStream_t stream);
+int sk_launch_tape_prepass(const sk_render_args_t *args, const int *levels, int max_level, const sk_tape_args_t *t,
+                           hipStream_t stream);
 /* the two specialised families (called by sk_launch_render only) */
 int sk_launch_render_fast(const sk_render_args_t *args, int n_workgroups, size_t lds_bytes, hipStream_t stream);
 int sk_launch_render_fast2(const sk_render_args_t *args, int n_workgroups, size_t lds_bytes, hipStream_t stream);

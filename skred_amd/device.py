@@ -25,7 +25,7 @@ ABI_SYMBOLS = [
     "skred_bank_render", "skred_bank_master", "skred_bank_render_mix", "skred_bank_render_host",
     "skred_bank_last_render_ms", "skred_bank_timing_reset", "skred_bank_timing_summary",
     "skred_bank_set_option", "skred_bank_last_kernel", "skred_bank_last_in_place", "skred_bank_last_split", "skred_bank_last_pack", "skred_bank_list_violations", "skred_bank_set_probe",
-    "skred_bank_set_form_counter",
+    "skred_bank_set_form_counter", "skred_bank_last_cross_group",
     "skred_bank_update", "skred_bank_defer", "skred_bank_run_queue", "skred_bank_queue_pending",
     "skred_shard_partition", "skred_shard_cut_ok", "skred_shard_create", "skred_shard_create_custom", "skred_shard_destroy",
     "skred_shard_bank", "skred_shard_range", "skred_shard_upload", "skred_shard_set_ops", "skred_shard_rccl_unique_id",
@@ -91,6 +91,7 @@ def load() -> C.CDLL:
     L.skred_bank_last_pack.argtypes = [vp]
     L.skred_bank_set_probe.argtypes = [vp, vp, i32, vp]
     L.skred_bank_set_form_counter.argtypes = [vp, vp]
+    L.skred_bank_last_cross_group.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.skred_bank_list_violations.argtypes = [vp]
     L.skred_bank_list_violations.restype = C.c_uint
     L.skred_bank_timing_reset.argtypes = [vp]
@@ -285,6 +286,17 @@ class DeviceBank:
     def set_fm_skew(self, on: int) -> None:
         """SKRED_OPT_FM_SKEW: 1 (default) modulator lanes of a frequency-modulated wavefront run a block ahead of their carriers, 0 per-frame exchange."""
         _check(self.L.skred_bank_set_option(self.h, 10, int(on)), "skred_bank_set_option")
+
+    def set_cross_group(self, on: bool) -> None:
+        """SKRED_OPT_CROSS_GROUP: 1 modulators in another aligned 64-voice group of the bank are rendered through the source tape,
+        0 (default) such banks are refused."""
+        _check(self.L.skred_bank_set_option(self.h, 11, int(bool(on))), "skred_bank_set_option")
+
+    def last_cross_group(self):
+        """(n_sources, n_levels) of the latest block: tape sources and pre-pass launches; (0, 0) when it read no tape."""
+        ns, nl = C.c_int32(0), C.c_int32(0)
+        _check(self.L.skred_bank_last_cross_group(self.h, C.byref(ns), C.byref(nl)), "skred_bank_last_cross_group")
+        return int(ns.value), int(nl.value)
 
     def last_pack(self) -> int:
         """Lanes per 64-voice group in the latest block, 0: not packed."""

@@ -11,6 +11,9 @@
   patches    2^20-voice banks made by tiling a reference patch (banks.bank_patch: the routings of 3.sk, 37.sk, 1.sk, 7.sk, 18.sk)
   linear     C1 / C2 / C3 with linear interpolation, pools with and without guard samples
   mid        mid-size enveloped banks: which kernel family renders them, steady
+  cross      modulators in other 64-voice groups (SKRED_OPT_CROSS_GROUP: the source tape and its pre-pass launches): a 2^20-voice C3
+             bank whose voice 0 modulates the amplitude and pan of every voice, 3.sk / 18.sk laid out back to back across group
+             edges -- each beside the same routings kept inside the groups
 
 Each line: ms per block over the timed blocks (wall clock), voice-samples/s, and the render kernel's duration from the
 library's own event pair around the latest bracketed launch (a bracketed launch runs alone).  kernels / fm / noise print
@@ -26,13 +29,14 @@ sys.path.insert(0, ".")
 from skred_amd import banks, device  # noqa: E402
 
 
-def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=False, overlap=None, timing=4):
+def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=False, overlap=None, timing=4, cross=False):
     n = bank.n
     out = torch.zeros(F, 2, device="cuda")
     db = device.DeviceBank(n)
     db.set_tables(tables)
     db.upload(bank)
     db.set_globals(g)
+    db.set_cross_group(cross)
     if min2 is not None:
         db.fast2_min_voices(min2)
     db.force_generic(generic)
@@ -59,8 +63,9 @@ def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=Fal
             best = (d_, t0, t1)
     dt, t0, t1 = best
     k = f"{db.last_render_ms():.4f}" if timing else "-"
+    tape = "  tape sources %d, pre-pass launches %d" % db.last_cross_group() if cross else ""
     print(f"{name:66s} kernel={db.last_kernel()} {dt * 1e3:.4f} ms/block {n * F / dt:.3e} voice-samples/s  "
-          f"render kernel {k} ms  host issue {(t1 - t0) / steps * 1e6:.1f} us")
+          f"render kernel {k} ms  host issue {(t1 - t0) / steps * 1e6:.1f} us{tape}")
     db.close()
 
 
@@ -152,6 +157,43 @@ def patches():
         run(f"patch {p} tiled over 2^20 voices", b, t, g, steps=20)
 
 
+def straddle(patch, n, stride, offset):
+    """`patch` laid out back to back: a copy every `stride` voices from `offset` on (copies straddle the 64-voice groups)."""
+    one, t, g = banks.bank_patch(patch, 64)
+    used = np.where((one["voice_amp"] != 0) & (one["voice_table_size"] > 0))[0]
+    K = int(used.max()) + 1
+    b = banks.VoiceBank(n)
+    for c in range((n - offset) // stride):
+        o = offset + c * stride
+        if o + K > n:
+            break
+        for name in b.a:
+            b.a[name][o:o + K] = one.a[name][:K]
+        for f in ("voice_freq_mod_osc", "voice_amp_mod_osc", "voice_pan_mod_osc", "voice_cz_mod_osc"):
+            m = one.a[f][:K]
+            b.a[f][o:o + K] = np.where(m >= 0, m + o, m)
+    return b, t, g
+
+
+def cross():
+    n = 1 << 20
+    for label, src in (("voice 0 of the bank", lambda v: np.zeros_like(v)), ("voice 0 of each voice's own group", lambda v: v & ~63)):
+        b, t, g = banks.bank_c2(n)
+        v = np.arange(n)
+        s = src(v)
+        keep = v != s
+        b["voice_phase_inc"][s[keep]] = np.float32(0.37)
+        b["voice_amp_mod_osc"][keep], b["voice_amp_mod_depth"][keep] = s[keep], np.float32(0.8)
+        b["voice_pan_mod_osc"][keep], b["voice_pan_mod_depth"][keep] = s[keep], np.float32(0.5)
+        run(f"c3 2^20, AM + pan from {label}", b, t, g, steps=20, cross=True)
+    # (18.sk at multiples of 4: a group edge never falls between its voices 0 and 1 or 1 and 2, which would make a cycle)
+    for p, stride, offset in (("3sk", 13, 5), ("18sk", 12, 4)):
+        b, t, g = straddle(p, n, stride, offset)
+        run(f"patch {p} every {stride} voices from {offset} (across group edges)", b, t, g, steps=20, cross=True)
+        b, t, g = banks.bank_patch(p, n)
+        run(f"patch {p} tiled over 2^20 voices (inside the groups)", b, t, g, steps=20, cross=True)
+
+
 def linear():
     for rec, n in (("c1", 4096), ("c2", 65536), ("c2", 1 << 20)):
         b, t, g = banks.RECIPES[rec](n)
@@ -208,7 +250,7 @@ def live():
 
 
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
