@@ -35,7 +35,9 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(1, os.path.dirname(HERE))                      # tests/: fuzz_banks, golden_io
 
+import fuzz_banks  # noqa: E402
 from skred_amd.bank import ENV_DTYPE, FIELDS, MMF_DTYPE, RW_FIELDS, GlobalsC, VoiceBank  # noqa: E402
 
 REF_DIR = os.environ.get("SKRED_REFERENCE", "/root/reference")
@@ -202,10 +204,26 @@ class Case:
             assert self.meta["segments"][0]["mix_fnv1a32"] == "4160cd81", self.meta["segments"][0]
         self.out["meta"] = np.array(json.dumps(self.meta))
         path = os.path.join(HERE, self.name + ".npz")
-        np.savez_compressed(path, **self.out)
+        save_npz(path, self.out)
         print(f"wrote {path} ({os.path.getsize(path)} bytes) segments={self.k}")
         for s in self.meta["segments"]:
             print("   ", s)
+
+
+def save_npz(path, arrays):
+    """np.savez_compressed with fixed member times, so that the same arrays always give the same file.  Every case is written this
+    way.  The ten fixtures older than the fuzz cases were written by np.savez_compressed itself, whose member times are the time of
+    writing: regenerating one of them gives the same arrays in a file of other bytes, as it always did (no test compares file
+    bytes; only the fuzz fixtures are byte-stable from their first commit)."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as zf:
+        for key, value in arrays.items():
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(value), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            zf.writestr(info, buf.getvalue())
 
 
 def lcg_uniform(n, seed):
@@ -306,9 +324,8 @@ PCM_GEOM = [(707, 342, 684, 89), (8186, 4282, 7439, 39), (2766, 1377, 2744, 45),
             (1311, 898, 1288, 52), (2276, 1164, 2254, 51)]
 
 
-def case_c4_pcm(ref, Case):
-    """BASELINE config 5 shape, truncate mode: one-shot PCM-like tables (synthetic, seeded) with the
-    real pcm_map geometry: forward, reverse, looped, finishing mid-block."""
+def install_pcm_tables(ref):
+    """The five synthetic one-shot tables of the c4_pcm_oneshot case in EXT slots 200-204."""
     for i, (n, ls, le, note) in enumerate(PCM_GEOM):
         data = lcg_uniform(n, 0x9C3 + i)
         data = np.convolve(data, np.ones(5, np.float32) / 5.0, mode="same").astype(np.float32)
@@ -316,6 +333,12 @@ def case_c4_pcm(ref, Case):
         hz = 440.0 * 2.0 ** ((note - 69.0) / 12.0)
         ref.ext_table(200 + i, data, rate=22050.0, one_shot=1, loop_enabled=0, loop_start=ls,
                       loop_end=le, midi_note=float(note), offset_hz=hz)
+
+
+def case_c4_pcm(ref, Case):
+    """BASELINE config 5 shape, truncate mode: one-shot PCM-like tables (synthetic, seeded) with the
+    real pcm_map geometry: forward, reverse, looped, finishing mid-block."""
+    install_pcm_tables(ref)
     lines = []
     v = 0
     for i, (n, ls, le, note) in enumerate(PCM_GEOM):
@@ -601,6 +624,91 @@ def case_bank256_sum(ref, Case):
     c.save()
 
 
+# ---- fuzzed banks: state written straight into the reference's arrays (tests/fuzz_banks.py) ----
+
+FUZZ_SLOTS = [0, 200, 201, 202, 203, 204]      # the sine and the five one-shot tables of install_pcm_tables()
+FUZZ_SEEDS = {"fuzz_mod_0": 0, "fuzz_mod_1": 1, "fuzz_mod_2": 2, "fuzz_mod_3": 3}
+FUZZ_BLOCKS = [512, 33, 64, 100, 1, 7, 65]
+
+
+def fuzz_setup(ref):
+    """Install the tables the fuzzed banks sit on; returns the (offset, size) catalogue fuzz_banks.wild_bank() draws from, entry
+    k standing for wave slot FUZZ_SLOTS[k] (the offsets only tell the entries apart: snapshot() lays the pool out again)."""
+    install_pcm_tables(ref)
+    sizes = ref.arr("wave_size", "<i4", ref.W)[FUZZ_SLOTS]
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    return [(int(o), int(n)) for o, n in zip(offs, sizes)]
+
+
+def write_bank(ref, bank):
+    """Every field of `bank` but the table binding into the reference's per-voice arrays."""
+    for name, dt, _ in FIELDS:
+        if name not in ("voice_table_offset", "voice_table_size"):
+            ref.arr(name, dt)[:] = bank.a[name]
+
+
+def inject_bank(ref, bank, cat, count0):
+    """Make `bank` (64 voices drawn over the catalogue of fuzz_setup) the reference's state: each voice is bound to its table with
+    `v<k> w<slot>` (voice_table is a pointer), everything else is stored into the arrays, the sample clock is set."""
+    assert bank.n == ref.V
+    slot_of = {o: FUZZ_SLOTS[k] for k, (o, _) in enumerate(cat)}
+    for v in range(bank.n):
+        ref.wire(f"v{v} w{slot_of[int(bank['voice_table_offset'][v])]}")
+    assert (ref.arr("voice_table_size", "<i4") == bank["voice_table_size"]).all()
+    write_bank(ref, bank)
+    ref.scalar("synth_sample_count", C.c_uint64).value = count0
+
+
+def apply_action(ref, action):
+    """One fuzz_banks.Action on the reference's state as it stands."""
+    mirror, _ = ref.snapshot()
+    action.apply(mirror, ref.scalar("synth_sample_count", C.c_uint64).value)
+    write_bank(ref, mirror)
+
+
+def fuzz_plan(seed, cat):
+    """(bank, [(frames, callback size, actions before the segment)]) of fuzz seed `seed`: four to six segments."""
+    rng = np.random.default_rng(7000 + seed)
+    bank, _ = fuzz_banks.wild_bank(rng, 64, cat, "any64")
+    k = int(rng.integers(4, 7))
+    acts = fuzz_banks.spread(rng, fuzz_banks.events(rng, bank, 2 * k), k)
+    segs = [(int(rng.integers(60, 260)), int(rng.choice(FUZZ_BLOCKS)), acts[i]) for i in range(k)]
+    return bank, segs, fuzz_banks.COUNT0
+
+
+def fuzz_case(name):
+    def case(ref, Case):
+        cat = fuzz_setup(ref)
+        bank, segs, count0 = fuzz_plan(FUZZ_SEEDS[name], cat)
+        inject_bank(ref, bank, cat, count0)
+        c = Case(name, f"fuzzed 64-voice bank, seed {FUZZ_SEEDS[name]} of tests/fuzz_banks.py: every feature at random, FM / AM / "
+                       "pan / CZ modulators anywhere in the bank, control actions between the segments")
+        for frames, block, acts in segs:
+            for a in acts:
+                apply_action(ref, a)
+            r = c.segment(ref, frames, block, note=" ".join(a.kind for a in acts))
+            assert np.isfinite(r[0]).all() and np.isfinite(r[1]).all(), f"{name}: the reference's output is not finite"
+        c.save()
+    return case
+
+
+def check_fuzz_coverage():
+    """Between them the fuzz fixtures drive all four modulator kinds and all seven CZ modes on voices that sound."""
+    import golden_io as gio
+    kinds, modes = set(), set()
+    for name in FUZZ_SEEDS:
+        for seg in gio.load(name).segments:
+            b = seg.bank_in
+            live = b["voice_amp"] != 0
+            for f in ("voice_freq_mod_osc", "voice_amp_mod_osc", "voice_pan_mod_osc"):
+                if ((b[f] >= 0) & live).any():
+                    kinds.add(f)
+            if ((b["voice_cz_mod_osc"] >= 0) & (b["voice_cz_mode"] != 0) & live).any():
+                kinds.add("voice_cz_mod_osc")
+            modes |= set(int(m) for m in b["voice_cz_mode"][live] if m)
+    assert len(kinds) == 4 and modes == set(range(1, 8)), (kinds, modes)
+
+
 CASES = {
     "c0_0sk": case_c0_0sk,
     "c1_sine_adsr64": case_c1_sine_adsr,
@@ -613,6 +721,7 @@ CASES = {
     "bank256_sum": case_bank256_sum,
     "korg_waves": case_korg_waves,
 }
+CASES.update({name: fuzz_case(name) for name in FUZZ_SEEDS})
 
 
 def main():
@@ -628,6 +737,7 @@ def main():
         return
     for name in CASES:   # fresh process per case: synth() has function-static state
         subprocess.run([sys.executable, os.path.abspath(__file__), "--case", name], check=True)
+    check_fuzz_coverage()   # over the four fuzz fixtures as just written (a run with --case may leave older siblings: not checked)
 
 
 if __name__ == "__main__":

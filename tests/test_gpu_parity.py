@@ -37,7 +37,7 @@ def dev():
     return device
 
 
-@pytest.mark.parametrize("case", gio.CASES)
+@pytest.mark.parametrize("case", gio.CASES + gio.FUZZ_CASES)
 def test_golden_case(dev, case):
     """The reference's own output, segment by segment, callback by callback."""
     g = gio.load(case)

@@ -11,7 +11,7 @@ import golden_io as gio
 from oracle import cpuref
 
 
-@pytest.mark.parametrize("case", gio.CASES)
+@pytest.mark.parametrize("case", gio.CASES + gio.FUZZ_CASES)
 def test_cpuref_bit_exact(case):
     g = gio.load(case)
     for seg in g.segments:
@@ -37,7 +37,7 @@ def test_cpuref_bit_exact(case):
         assert np.float32(gl.volume_smoother_gain).tobytes() == np.float32(seg.g_out.volume_smoother_gain).tobytes()
 
 
-@pytest.mark.parametrize("case", gio.CASES)
+@pytest.mark.parametrize("case", gio.CASES + gio.FUZZ_CASES)
 def test_cpuref_block_size_independent(case):
     """The reference renders the same bytes whatever the callback size; so must the oracle."""
     g = gio.load(case)
