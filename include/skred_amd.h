@@ -374,6 +374,27 @@ int  skred_bank_last_cross_group(const skred_bank_t *bank, int *n_sources, int *
 #define SKRED_PROBE_MAX 64
 int  skred_bank_set_probe(skred_bank_t *bank, const int32_t *voices, int n, float *d_probe);
 
+/* VOICE TAPS: the per-frame stems of chosen voices, from every kernel family.  A launch with the full stem buffer
+ * (float[frames][n_voices][2]: 8 MB per frame at 2^20 voices) is never packed, never takes the frame-lag form and renders frame by
+ * frame on the one-voice kernel.  A tap names up to SKRED_TAPS_MAX voices; every later block writes into
+ * d_taps[frame][k][2] (device memory, num_frames x n x 2 floats, overwritten by every block; zeroed on the render stream ahead of
+ * the launch) the (left, right) the reference stores into its stem buffer for voice voices[k] at that frame (synth.c:603-611) --
+ * exact zeros for a skipped, finished, muted or disconnected voice -- from the same launch and on the same kernel paths that render
+ * the block without taps: packed lanes, the frame-lag form, the cross-group tape, the generic kernel and the specialised families
+ * included.  The layout is what skred_recorder_append takes from a recorder created with n_voices = n: append d_taps after each
+ * block on the render stream, then save.  A tap does not change what the block computes: voice state, globals and the mix are
+ * bit-identical to the same block without taps, and skred_bank_last_kernel / _last_pack / _last_cross_group and the form counters
+ * report the same -- with one exception: a two-operator FM bank renders on the one-voice-per-lane kernel while taps are set, as
+ * it does below SKRED_OPT_FM2_MIN_VOICES (per-voice results are bit-identical across the kernel families, see the options above;
+ * its mix then differs by summation order only), and the split form (SKRED_OPT_SPLIT) is not taken.
+ * Refused: a voice outside the bank (SKRED_E_RANGE); n > SKRED_TAPS_MAX, or NULL pointers with n > 0 (SKRED_E_BAD_ARG); taps while
+ * a probe is set and a probe while taps are set (SKRED_E_BAD_ARG for the second setter); a render with taps set and a stem buffer
+ * (SKRED_E_UNSUPPORTED: the stems already contain the taps; the bank stays usable).  n = 0 ends it.  Not in the fixed-point bank,
+ * shards or the drop-in mode. */
+#define SKRED_TAPS_MAX 64
+int  skred_bank_set_taps(skred_bank_t *bank, const int32_t *voices, int n, float *d_taps);
+int  skred_bank_last_taps(const skred_bank_t *bank);     /* taps written by the latest block, 0: none */
+
 /* Which form the modulated kernel's wavefronts ran (tests): with `d_counts` set (device memory, two words the caller owns and
  * zeroes), every pass of every wavefront of the modulated kernel adds 1 to d_counts[0] when it runs the frame-lag form
  * (SKRED_OPT_FM_SKEW) and to d_counts[1] when it runs the level loop of a bank with same-frame dependencies.  NULL ends it;

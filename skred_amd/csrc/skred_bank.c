@@ -169,6 +169,7 @@ void skred_bank_destroy(skred_bank_t *b) {
   if (b->d_gain_state) hipFree(b->d_gain_state);
   if (b->d_pp_gains) hipFree(b->d_pp_gains);
   if (b->d_probe_ids) hipFree(b->d_probe_ids);
+  if (b->d_tap_ids) hipFree(b->d_tap_ids);
   if (b->d_out) hipFree(b->d_out);
   if (b->d_stems) hipFree(b->d_stems);
   free(b->h_class); free(b->h_mod); free(b->h_level);
@@ -502,6 +503,7 @@ int skred_bank_set_option(skred_bank_t *b, int option, int value) {
 
 int skred_bank_set_probe(skred_bank_t *b, const int32_t *voices, int n, float *d_probe) {
   if (!b || n < 0 || n > SK_PROBE_MAX || (n > 0 && (!voices || !d_probe))) return fail(SKRED_E_BAD_ARG, "set_probe: bad arguments");
+  if (n > 0 && b->n_taps > 0) return fail(SKRED_E_BAD_ARG, "set_probe: voice taps are set (skred_bank_set_taps)");
   for (int i = 0; i < n; i++)
     if (voices[i] < 0 || voices[i] >= b->n_voices) return fail(SKRED_E_RANGE, "set_probe: voice %d outside the bank", voices[i]);
   HIP_TRY(hipSetDevice(b->device));
@@ -512,6 +514,22 @@ int skred_bank_set_probe(skred_bank_t *b, const int32_t *voices, int n, float *d
   }
   b->n_probe = n;
   b->d_probe_out = n > 0 ? d_probe : NULL;
+  return SKRED_OK;
+}
+
+int skred_bank_set_taps(skred_bank_t *b, const int32_t *voices, int n, float *d_taps) {
+  if (!b || n < 0 || n > SK_TAPS_MAX || (n > 0 && (!voices || !d_taps))) return fail(SKRED_E_BAD_ARG, "set_taps: bad arguments");
+  if (n > 0 && b->n_probe > 0) return fail(SKRED_E_BAD_ARG, "set_taps: a probe is set (skred_bank_set_probe)");
+  for (int i = 0; i < n; i++)
+    if (voices[i] < 0 || voices[i] >= b->n_voices) return fail(SKRED_E_RANGE, "set_taps: voice %d outside the bank", voices[i]);
+  HIP_TRY(hipSetDevice(b->device));
+  HIP_TRY(hipDeviceSynchronize());                   /* (a block in flight may still read the old list) */
+  if (n > 0) {
+    if (!b->d_tap_ids) HIP_TRY(hipMalloc((void **)&b->d_tap_ids, SK_TAPS_MAX * sizeof(int32_t)));
+    HIP_TRY(hipMemcpy(b->d_tap_ids, voices, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+  }
+  b->n_taps = n;
+  b->d_taps_out = n > 0 ? d_taps : NULL;
   return SKRED_OK;
 }
 
@@ -527,6 +545,7 @@ int skred_bank_last_kernel(const skred_bank_t *b) { return b ? b->last_kernel : 
 int skred_bank_last_in_place(const skred_bank_t *b) { return b ? b->last_in_place : 0; }
 int skred_bank_last_split(const skred_bank_t *b) { return b ? b->last_split : 0; }
 int skred_bank_last_pack(const skred_bank_t *b) { return b ? b->last_pack : 0; }
+int skred_bank_last_taps(const skred_bank_t *b) { return b ? b->last_taps : 0; }
 int skred_bank_last_cross_group(const skred_bank_t *b, int *n_sources, int *n_levels) {
   if (!b) return fail(SKRED_E_BAD_ARG, "last_cross_group: no bank");
   if (n_sources) *n_sources = b->last_tape_sources;
@@ -655,6 +674,7 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
                         int num_channels, hipStream_t s) {
   if (interp != SKRED_INTERP_TRUNCATE && interp != SKRED_INTERP_LINEAR) return fail(SKRED_E_BAD_ARG, "render: interp %d", interp);
   if (!b->d_tables) return fail(SKRED_E_BAD_ARG, "render: no table pool set");
+  if (b->n_taps > 0 && d_stems) return fail(SKRED_E_UNSUPPORTED, "render: voice taps are set and the launch carries the full stem buffer, which already holds them");
   if ((b->features & (SKB_ANY_MOD | SKB_ANY_FM)) && b->cnt_escapes > 0) {
     if (!b->cross_group)
       return fail(SKRED_E_UNSUPPORTED, "a voice is modulated by a voice outside its aligned 64-voice group: "
@@ -739,7 +759,8 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
     a.fast_mode &= ~SKM_TWO_PER_LANE;
   /* two-operator FM (every carrier an even voice, modulated by the voice after it): carrier and modulator share a lane of
    * the two-per-lane kernel, so the per-frame exchange of the one-per-lane kernel disappears.  LDS-table banks. */
-  if (fast_ok && (a.fast_mode & SKM_FM_PAIR) && a.lds_table_floats > 0 && !d_stems && b->n_voices >= b->fm2_min_voices)
+  if (fast_ok && (a.fast_mode & SKM_FM_PAIR) && a.lds_table_floats > 0 && !d_stems && b->n_voices >= b->fm2_min_voices &&
+      b->n_taps == 0)                        /* (voice taps: the one-voice kernel has the tap rows; same per-voice bits) */
     a.fast_mode |= SKM_TWO_PER_LANE;
   else
     a.fast_mode &= ~(SKM_FM_PAIR | SKM_PAIR_AP);
@@ -819,6 +840,15 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
     a.n_probe = b->n_probe;
     a.probe_out = b->d_probe_out;
     HIP_TRY(hipMemsetAsync(b->d_probe_out, 0, (size_t)num_frames * (size_t)b->n_probe * 2 * sizeof(float), s));   /* (a skipped / muted voice writes nothing) */
+  }
+  if (b->n_taps > 0) {
+    /* voice taps: every kernel family writes them -- the specialised ones through their probe instantiations, the generic,
+     * modulated and tape kernels through their tap instantiations (the launchers forward on probe_out); the split form has none */
+    split = 0;
+    a.probe_ids = b->d_tap_ids;
+    a.n_probe = b->n_taps;
+    a.probe_out = b->d_taps_out;
+    HIP_TRY(hipMemsetAsync(b->d_taps_out, 0, (size_t)num_frames * (size_t)b->n_taps * 2 * sizeof(float), s));   /* (a skipped / muted voice writes nothing) */
   }
   if (split) a.fast_mode |= SKM_SPLIT | (split == 2 ? SKM_SPLIT2 : 0u);
   if (split == 2) n_wg = b->n_groups * 2;
@@ -992,6 +1022,7 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
   b->last_in_place = inplace;
   b->last_split = split;
   b->last_pack = pack_s;
+  b->last_taps = b->n_taps;
   b->last_tape_sources = tape ? b->tape_sources : 0;
   b->last_tape_levels = tape ? b->tape_levels : 0;
 

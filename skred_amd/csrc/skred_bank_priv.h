@@ -83,6 +83,10 @@ struct skred_bank {
   int32_t *d_probe_ids;       /* skred_bank_set_probe: the probed voices on the device, their number, the caller's buffer */
   int n_probe;
   float *d_probe_out;
+  int32_t *d_tap_ids;         /* skred_bank_set_taps: the same for the tapped voices (a bank has a probe or taps, never both) */
+  int n_taps;
+  float *d_taps_out;
+  int last_taps;              /* taps the latest block wrote */
   uint32_t *d_form_counts;    /* skred_bank_set_form_counter: the caller's [2] counters, or NULL */
   int split_mode;             /* SKRED_OPT_SPLIT: 0 never, 1 where it is the faster form (default), 2 whenever the bank qualifies */
   int split_pairs;            /* SKRED_OPT_SPLIT_PAIRS: 0 the library's choice, 2 / 4 forced (tests) */

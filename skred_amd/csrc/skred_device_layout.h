@@ -209,7 +209,8 @@ typedef struct {
   float vol_target, vol_k; /* volume_final, volume_smoother_smoothing */
   /* ---- per-frame probes (tests; skred_bank_set_probe): the (L, R) of every frame of up to SK_PROBE_MAX voices, written from INSIDE
    * the kernels' block paths by their probe instantiations (translation units compiled with -DSK_PROBE_TU; the ordinary
-   * instantiations contain none of this) ---- */
+   * instantiations contain none of this).  VOICE TAPS (skred_bank_set_taps) travel in the same three fields and are written by the
+   * same instantiations, and by those of the generic, modulated and tape kernels (skred_render_generic.hip) ---- */
   const int32_t *probe_ids; /* [n_probe] voice numbers */
   float *probe_out;         /* [num_frames][n_probe][2], zeroed by the host before the launch (a skipped / muted voice writes nothing) */
   int32_t n_probe;
@@ -229,6 +230,7 @@ typedef struct {
   uint32_t *form_counts;     /* [2] += 1 per wave and pass: [0] the frame-lag form, [1] the level loop with max_level >= 1 */
 } sk_render_args_t;
 #define SK_PROBE_MAX 64
+#define SK_TAPS_MAX 64
 
 /* ---- cross-group modulation (SKRED_OPT_CROSS_GROUP; skred_render_generic.hip: sk_render_mod_tape_kernel) ----
  * A voice whose modulator sits in another aligned 64-voice group holds a TAPE CODE in its SKP_MODI word instead of a lane:

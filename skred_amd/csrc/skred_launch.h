@@ -3,6 +3,7 @@
  * libskred_amd.so; the public ABI is include/skred_amd.h).
  *
  *   skred_render_generic.hip  sk_launch_render (dispatcher), sk_launch_render_mod, sk_launch_render_mod_tape, sk_launch_tape_prepass
+ *                             (with args->probe_out set they forward to the tap unit, the same source built with -DSK_PROBE_TU)
  *   skred_render_fast.hip     sk_launch_render_fast
  *   skred_render_split.hip    sk_launch_render_split, sk_split_lds_bytes
  *   skred_render_fast2.hip    sk_launch_render_fast2, sk_launch_env_fast2, sk_env2_grid, sk_launch_classify

@@ -28,6 +28,25 @@
 
 // ---------------------------------------------------------------- render kernel
 
+// VOICE TAPS (skred_bank_set_taps): this file compiled once more with -DSK_PROBE_TU is a translation unit of its own, whose
+// kernels -- the same text plus the SK_TAP_* lines -- also write each frame's (L, R) of the tapped voices (sk_render_args_t:
+// probe_ids / probe_out / n_probe); they carry names of their own, and the ordinary object contains none of it.
+#ifdef SK_PROBE_TU
+#define sk_render_kernel sk_render_tap_kernel
+#define sk_render_mod_kernel sk_render_mod_tap_kernel
+#define sk_render_mod_tape_kernel sk_render_mod_tape_tap_kernel
+// the lane's tap row of frame 0 (nullptr: not tapped, or `off`: no lane of its own / dead for the whole launch -- its rows keep
+// the host's zeros), resolved once per pass; and the store of frame `f`, what the reference stores into its stem buffer
+// (synth.c:603-611), under a wave-uniform test
+#define SK_TAP_RESOLVE(v, off)                                                  \
+  float2 *const tap = sk_probe_row(a, (v), (off) || (v) >= a.n_voices);         \
+  const bool tap_any = __any(tap != nullptr);
+#define SK_TAP_STORE_IF(c, f, l, rr) { if (tap_any && tap && (c)) tap[(size_t)(f) * (size_t)a.n_probe] = make_float2((l), (rr)); }
+#else
+#define SK_TAP_RESOLVE(v, off)
+#define SK_TAP_STORE_IF(c, f, l, rr)
+#endif
+
 // LDS: [lds_table_floats] staged table pool, then [4 waves][SK_CHUNK][2] wave sums.
 template <bool TAB_LDS, bool STEMS>
 __global__ __launch_bounds__(SK_GROUP) void sk_render_kernel(const sk_render_args_t a) {
@@ -59,6 +78,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_kernel(const sk_render_arg
     const bool publish = a.finish && g + a.n_rows >= a.n_groups;   // the pass that completes this workgroup's row
     VoiceRegs r;
     load_voice(a, v, r);
+    SK_TAP_RESOLVE(v, false)
 
     uint64_t rng = a.rng0;
     for (int c0 = 0; c0 < a.num_frames; c0 += SK_CHUNK) {
@@ -78,6 +98,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_kernel(const sk_render_arg
             reinterpret_cast<float2 *>(a.stems)[(size_t)i * (size_t)a.n_voices + (size_t)v] =
                 make_float2(l, rr);
         }
+        SK_TAP_STORE_IF(true, i, l, rr)
         SK_REDUCE_AND_STORE(j)
       }
       __syncthreads();
@@ -351,6 +372,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
     }
     incs[lane] = m.inc_raw;
     xch0[lane] = r.sample;                                     // voice_sample[] as the last callback left it
+    SK_TAP_RESOLVE(v, absent || (r.rw & SKR_FINISHED) || r.amp == 0.0f || (r.flags & SKF_INERT))
     SK_MOD_WAVE_SYNC()
 
     uint64_t rng = a.rng0;
@@ -388,6 +410,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
       if (live && m.level == 0) voice_frame_mod<TAB_LDS>(r, m, lane, prev, cur, incs, lds_tab, a.tables, a.count0 + 1, white, a.interp, l, rr, true);
       cur[lane] = r.sample;                                    // (a lane that sat out carries its sample along)
       SK_MOD_WAVE_SYNC()
+      SK_TAP_STORE_IF(m.level == 0, 0, l, rr)
       hl = l; hr = rr; white_prev = white;
       cur_i ^= 1;
     }
@@ -410,6 +433,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
                                      m.level == 0 ? white : white_prev, a.interp, l, rr, true);
           cur[lane] = r.sample;
           SK_MOD_WAVE_SYNC()
+          SK_TAP_STORE_IF(m.level == 1 || more, i - m.level, l, rr)   // the lane's own frame, ahead of the hold swap
           if (m.level == 0) { const float tl = l, tr = rr; l = hl; rr = hr; hl = tl; hr = tr; }   // frame c0 + j: what was held
           SK_REDUCE_AND_STORE(j)
           white_prev = white;
@@ -438,6 +462,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_kernel(const sk_render
           if (v < a.n_voices)
             reinterpret_cast<float2 *>(a.stems)[(size_t)i * (size_t)a.n_voices + (size_t)v] = make_float2(l, rr);
         }
+        SK_TAP_STORE_IF(true, i, l, rr)
         SK_REDUCE_AND_STORE(j)
         cur_i ^= 1;
       }
@@ -543,6 +568,7 @@ __device__ __forceinline__ void sk_render_mod_body(const sk_render_args_t &a, co
     }
     incs[lane] = m.inc_raw;
     xch0[lane] = r.sample;                                     // voice_sample[] as the last callback left it
+    SK_TAP_RESOLVE(v, absent || (r.rw & SKR_FINISHED) || r.amp == 0.0f || (r.flags & SKF_INERT))
     float *trow = nullptr;                                     // (DRY) this lane's tape row when its voice is a source
     if constexpr (DRY) {
       const int slot = t.slot[v];
@@ -586,6 +612,7 @@ __device__ __forceinline__ void sk_render_mod_body(const sk_render_args_t &a, co
       if (live && m.level == 0) voice_frame_mod<TAB_LDS, TAPE>(r, m, lane, prev, cur, incs, lds_tab, a.tables, a.count0 + 1, white, a.interp, l, rr, true, t.tape, 0);
       cur[lane] = r.sample;                                    // (a lane that sat out carries its sample along)
       SK_MOD_WAVE_SYNC()
+      SK_TAP_STORE_IF(m.level == 0, 0, l, rr)
       hl = l; hr = rr; white_prev = white;
       cur_i ^= 1;
     }
@@ -608,6 +635,7 @@ __device__ __forceinline__ void sk_render_mod_body(const sk_render_args_t &a, co
                                            m.level == 0 ? white : white_prev, a.interp, l, rr, true, t.tape, i - m.level);
           cur[lane] = r.sample;
           SK_MOD_WAVE_SYNC()
+          SK_TAP_STORE_IF(m.level == 1 || more, i - m.level, l, rr)   // the lane's own frame, ahead of the hold swap
           if (m.level == 0) { const float tl = l, tr = rr; l = hl; rr = hr; hl = tl; hr = tr; }   // frame c0 + j: what was held
           SK_REDUCE_AND_STORE(j)
           white_prev = white;
@@ -640,6 +668,7 @@ __device__ __forceinline__ void sk_render_mod_body(const sk_render_args_t &a, co
             if (v < a.n_voices)
               reinterpret_cast<float2 *>(a.stems)[(size_t)i * (size_t)a.n_voices + (size_t)v] = make_float2(l, rr);
           }
+          SK_TAP_STORE_IF(true, i, l, rr)
           SK_REDUCE_AND_STORE(j)
         }
         cur_i ^= 1;
@@ -669,6 +698,37 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_mod_tape_kernel(const sk_r
 }
 // ---------------------------------------------------------------- launchers (C linkage)
 
+#ifdef SK_PROBE_TU
+// the tap unit: the launchers below forward here while taps are set (never with stems: the host refuses that launch; the tape's
+// pre-pass launches write no taps and stay the ordinary ones)
+extern "C" int sk_launch_render_tap(const sk_render_args_t *args, int n_workgroups, hipStream_t stream) {
+  const bool tab_lds = args->lds_table_floats > 0;
+  const size_t lds_bytes = (size_t)(tab_lds ? args->lds_table_floats : 0) * sizeof(float) + (size_t)4 * SK_CHUNK * sizeof(float2);
+  dim3 grid((unsigned)(n_workgroups + args->wg_shift)), block(SK_GROUP);
+  if (tab_lds) hipLaunchKernelGGL((sk_render_kernel<true, false>), grid, block, lds_bytes, stream, *args);
+  else         hipLaunchKernelGGL((sk_render_kernel<false, false>), grid, block, lds_bytes, stream, *args);
+  return (int)hipGetLastError();
+}
+extern "C" int sk_launch_render_mod_tap(const sk_render_args_t *args, int n_workgroups, const int *levels, int max_level,
+                                        const sk_tape_args_t *t, hipStream_t stream) {
+  const bool tab_lds = args->lds_table_floats > 0;
+  const size_t lds_bytes = (size_t)(tab_lds ? args->lds_table_floats : 0) * sizeof(float) +
+                           (size_t)4 * SK_CHUNK * sizeof(float2) + (size_t)4 * 192 * sizeof(float);
+  dim3 grid((unsigned)(n_workgroups + args->wg_shift)), block(SK_GROUP);
+  if (t) {                                                     // cross-group modulation: the main launch
+    if (tab_lds) hipLaunchKernelGGL((sk_render_mod_tape_kernel<true, false, SK_MOD_TAPE>), grid, block, lds_bytes, stream, *args, levels, max_level, *t);
+    else         hipLaunchKernelGGL((sk_render_mod_tape_kernel<false, false, SK_MOD_TAPE>), grid, block, lds_bytes, stream, *args, levels, max_level, *t);
+  } else {
+    if (tab_lds) hipLaunchKernelGGL((sk_render_mod_kernel<true, false>), grid, block, lds_bytes, stream, *args, levels, max_level);
+    else         hipLaunchKernelGGL((sk_render_mod_kernel<false, false>), grid, block, lds_bytes, stream, *args, levels, max_level);
+  }
+  return (int)hipGetLastError();
+}
+#else
+extern "C" int sk_launch_render_tap(const sk_render_args_t *args, int n_workgroups, hipStream_t stream);
+extern "C" int sk_launch_render_mod_tap(const sk_render_args_t *args, int n_workgroups, const int *levels, int max_level,
+                                        const sk_tape_args_t *t, hipStream_t stream);
+
 extern "C" int sk_launch_render(const sk_render_args_t *args, int n_workgroups, hipStream_t stream) {
   const bool tab_lds = args->lds_table_floats > 0;
   const bool stems = args->stems != nullptr;
@@ -680,6 +740,7 @@ extern "C" int sk_launch_render(const sk_render_args_t *args, int n_workgroups, 
   if ((args->fast_mode & SKM_FAST) && (!stems || !(args->fast_mode & SKM_TWO_PER_LANE)))   // (stems: the one-voice kernel has them)
     return (args->fast_mode & SKM_TWO_PER_LANE) ? sk_launch_render_fast2(args, n_workgroups, lds_bytes, stream)
                                                 : sk_launch_render_fast(args, n_workgroups, lds_bytes, stream);
+  if (args->probe_out) return sk_launch_render_tap(args, n_workgroups, stream);   // voice taps (the host has ruled stems out)
   dim3 grid((unsigned)(n_workgroups + args->wg_shift)), block(SK_GROUP);
   if (tab_lds) {
     if (stems) hipLaunchKernelGGL((sk_render_kernel<true, true>), grid, block, lds_bytes, stream, *args);
@@ -693,6 +754,7 @@ extern "C" int sk_launch_render(const sk_render_args_t *args, int n_workgroups, 
 
 extern "C" int sk_launch_render_mod(const sk_render_args_t *args, int n_workgroups, const int *levels,
                                     int max_level, hipStream_t stream) {
+  if (args->probe_out) return sk_launch_render_mod_tap(args, n_workgroups, levels, max_level, nullptr, stream);
   const bool tab_lds = args->lds_table_floats > 0;
   const size_t lds_bytes = (size_t)(tab_lds ? args->lds_table_floats : 0) * sizeof(float) +
                            (size_t)4 * SK_CHUNK * sizeof(float2) + (size_t)4 * 192 * sizeof(float);
@@ -707,6 +769,7 @@ extern "C" int sk_launch_render_mod(const sk_render_args_t *args, int n_workgrou
 // Cross-group modulation: the main launch (as sk_launch_render_mod, tape codes read from t->tape) ...
 extern "C" int sk_launch_render_mod_tape(const sk_render_args_t *args, int n_workgroups, const int *levels, int max_level,
                                          const sk_tape_args_t *t, hipStream_t stream) {
+  if (args->probe_out) return sk_launch_render_mod_tap(args, n_workgroups, levels, max_level, t, stream);
   const bool tab_lds = args->lds_table_floats > 0;
   const size_t lds_bytes = (size_t)(tab_lds ? args->lds_table_floats : 0) * sizeof(float) +
                            (size_t)4 * SK_CHUNK * sizeof(float2) + (size_t)4 * 192 * sizeof(float);
@@ -730,3 +793,4 @@ extern "C" int sk_launch_tape_prepass(const sk_render_args_t *args, const int *l
   else         hipLaunchKernelGGL((sk_render_mod_tape_kernel<false, false, SK_MOD_DRY>), grid, block, lds_bytes, stream, *args, levels, max_level, *t);
   return (int)hipGetLastError();
 }
+#endif

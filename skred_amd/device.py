@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "skred_bank_render", "skred_bank_master", "skred_bank_render_mix", "skred_bank_render_host",
     "skred_bank_last_render_ms", "skred_bank_timing_reset", "skred_bank_timing_summary",
     "skred_bank_set_option", "skred_bank_last_kernel", "skred_bank_last_in_place", "skred_bank_last_split", "skred_bank_last_pack", "skred_bank_list_violations", "skred_bank_set_probe",
+    "skred_bank_set_taps", "skred_bank_last_taps",
     "skred_bank_set_form_counter", "skred_bank_last_cross_group",
     "skred_bank_update", "skred_bank_defer", "skred_bank_run_queue", "skred_bank_queue_pending",
     "skred_shard_partition", "skred_shard_cut_ok", "skred_shard_create", "skred_shard_create_custom", "skred_shard_destroy",
@@ -90,6 +91,8 @@ def load() -> C.CDLL:
     L.skred_bank_last_split.argtypes = [vp]
     L.skred_bank_last_pack.argtypes = [vp]
     L.skred_bank_set_probe.argtypes = [vp, vp, i32, vp]
+    L.skred_bank_set_taps.argtypes = [vp, vp, i32, vp]
+    L.skred_bank_last_taps.argtypes = [vp]
     L.skred_bank_set_form_counter.argtypes = [vp, vp]
     L.skred_bank_last_cross_group.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
     L.skred_bank_list_violations.argtypes = [vp]
@@ -273,6 +276,17 @@ class DeviceBank:
         inside the kernels' fast paths; an empty list ends it."""
         v = np.ascontiguousarray(voices, np.int32)
         _check(self.L.skred_bank_set_probe(self.h, v.ctypes.data if len(v) else None, len(v), d_probe or None), "skred_bank_set_probe")
+
+    def set_taps(self, voices, d_taps: int) -> None:
+        """skred_bank_set_taps: the (L, R) the reference stores into its stem buffer for the listed voices (64 at most), every frame of
+        every later block, into d_taps[frame][k][2] (device memory) -- from whichever kernel family renders the block; the layout a
+        wav.Recorder(len(voices), ...) appends.  An empty list ends it."""
+        v = np.ascontiguousarray(voices, np.int32)
+        _check(self.L.skred_bank_set_taps(self.h, v.ctypes.data if len(v) else None, len(v), d_taps or None), "skred_bank_set_taps")
+
+    def last_taps(self) -> int:
+        """Taps written by the latest block, 0: none."""
+        return int(self.L.skred_bank_last_taps(self.h))
 
     def set_form_counter(self, d_counts: int) -> None:
         """skred_bank_set_form_counter: per pass of each wavefront of the modulated kernel, +1 in d_counts[0] (uint32, device memory)

@@ -14,6 +14,8 @@
   cross      modulators in other 64-voice groups (SKRED_OPT_CROSS_GROUP: the source tape and its pre-pass launches): a 2^20-voice C3
              bank whose voice 0 modulates the amplitude and pan of every voice, 3.sk / 18.sk laid out back to back across group
              edges -- each beside the same routings kept inside the groups
+  taps       what voice taps cost (skred_bank_set_taps): 18.sk tiled over 2^20 voices, 512 frames, packed lanes, with 0 and with 64
+             taps (voices 0 and 10 -- a source and the carrier it modulates in its own frame -- of 32 copies spread over the bank)
 
 Each line: ms per block over the timed blocks (wall clock), voice-samples/s, and the render kernel's duration from the
 library's own event pair around the latest bracketed launch (a bracketed launch runs alone).  kernels / fm / noise print
@@ -29,7 +31,7 @@ sys.path.insert(0, ".")
 from skred_amd import banks, device  # noqa: E402
 
 
-def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=False, overlap=None, timing=4, cross=False):
+def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=False, overlap=None, timing=4, cross=False, taps=None):
     n = bank.n
     out = torch.zeros(F, 2, device="cuda")
     db = device.DeviceBank(n)
@@ -37,6 +39,9 @@ def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=Fal
     db.upload(bank)
     db.set_globals(g)
     db.set_cross_group(cross)
+    if taps is not None and len(taps):
+        d_taps = torch.zeros(F, len(taps), 2, device="cuda")
+        db.set_taps(taps, d_taps.data_ptr())
     if min2 is not None:
         db.fast2_min_voices(min2)
     db.force_generic(generic)
@@ -64,6 +69,9 @@ def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=Fal
     dt, t0, t1 = best
     k = f"{db.last_render_ms():.4f}" if timing else "-"
     tape = "  tape sources %d, pre-pass launches %d" % db.last_cross_group() if cross else ""
+    if taps is not None:
+        tape += f"  taps {db.last_taps()}, lanes per group {db.last_pack()}"
+        db.set_taps([], 0)
     print(f"{name:66s} kernel={db.last_kernel()} {dt * 1e3:.4f} ms/block {n * F / dt:.3e} voice-samples/s  "
           f"render kernel {k} ms  host issue {(t1 - t0) / steps * 1e6:.1f} us{tape}")
     db.close()
@@ -194,6 +202,16 @@ def cross():
         run(f"patch {p} tiled over 2^20 voices (inside the groups)", b, t, g, steps=20, cross=True)
 
 
+def taps():
+    n = 1 << 20
+    b, t, g = banks.bank_patch("18sk", n)
+    copies = (np.arange(32) * (n // 32) + 7000 * 16) % n                 # 16 voices per copy; the 7 000th copy among them
+    ids = np.sort(np.concatenate([copies, copies + 10])).astype(np.int32)
+    for _rep in range(2):
+        run("patch 18sk tiled over 2^20 voices, no taps", b, t, g, steps=40, taps=[])
+        run("patch 18sk tiled over 2^20 voices, 64 taps", b, t, g, steps=40, taps=ids)
+
+
 def linear():
     for rec, n in (("c1", 4096), ("c2", 65536), ("c2", 1 << 20)):
         b, t, g = banks.RECIPES[rec](n)
@@ -250,7 +268,7 @@ def live():
 
 
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
