@@ -409,6 +409,56 @@ int  skred_bank_set_form_counter(skred_bank_t *bank, uint32_t *d_counts);
  * the list is rebuilt from the voice state by itself and skred_amd_last_error() names the launch. */
 unsigned skred_bank_list_violations(const skred_bank_t *bank);
 
+/* ---- which voices are free: an asynchronous list of idle voices, built on the device ---------------------------------
+ *
+ * What a note-on needs before its skred_bank_update(..., SKRED_DIRTY_PARAMS | SKRED_STAMP_TRIGGER): a voice that is not
+ * sounding.  Whether a voice sounds is state only the device has (voice_finished of a one-shot that ran out mid-block,
+ * is_active cleared by the kernel when a release ended, the amp smoother's running gain); skred_bank_download() returns it,
+ * but waits for the whole device and copies every read-write plane of the range.  The query sweeps the words it needs where
+ * they are and leaves an ordered list of voice indices in device memory, on the caller's stream.
+ *
+ * The predicates are stated on the reference's fields AS THE DEVICE HOLDS THEM at that point of the stream (the values
+ * skred_bank_download would return there); every comparison is exact, so the list has one right answer.  A padding voice or
+ * a voice without a table follows the same field rules as any other.  Routing is read as the kernels read it: frequency
+ * modulation by the voice itself (ignored, synth.c:549) and a CZ source while voice_cz_mode == 0 (never read, synth.c:262)
+ * name nobody; amplitude or pan modulation by the voice itself names it; a modulator index outside the bank names nobody.
+ *
+ * ENV_DONE carries a level for a reason: after a release has ended the smoother's target is 0, and g += k * (0 - g) in
+ * float stalls on a non-zero subnormal instead of reaching 0 -- a comparison with zero would never list a smoothed voice. */
+enum {                                   /* criteria: a voice is idle when ANY selected criterion holds */
+  SKRED_IDLE_FINISHED = 1u << 0,         /* voice_finished != 0 (osc_next's finish rule; skipped at synth.c:531-542) */
+  SKRED_IDLE_ENV_DONE = 1u << 1,         /* voice_use_amp_envelope != 0 && voice_amp_envelope.is_active == 0
+                                            && (voice_smoother_enable == 0 || fabsf(voice_smoother_gain) <= settle_level) */
+  SKRED_IDLE_AMP_ZERO = 1u << 2,         /* voice_amp == 0.0f (the reference's own skip rule, synth.c:537) */
+  /* restrictions: a voice is listed only if ALL selected restrictions hold too */
+  SKRED_IDLE_UNNAMED  = 1u << 8          /* no voice of the bank names it as FM / AM / pan / CZ modulator (voice_*_mod_osc) */
+};
+typedef struct skred_idle_query {
+  int32_t  first, count;   /* voice range [first, first + count) inside the bank */
+  uint32_t which;          /* SKRED_IDLE_* ; at least one criterion */
+  float    settle_level;   /* see ENV_DONE; 0: the smoother's gain must be exactly +-0 */
+  int32_t  from;           /* listing order: ascending voice index starting at `from` (first <= from < first + count),
+                              wrapping to `first` -- a round-robin allocator passes last pick + 1; `first` = plain ascending */
+  int32_t  max_out;        /* room in d_voices; 0: count only */
+} skred_idle_query_t;
+
+/* Asynchronous on `stream`, ordered after the renders and updates queued on it.  Writes d_voices[0 .. written) and
+ * d_count[0] = written = min(total, max_out), d_count[1] = total idle voices in the range (device memory).  Entries of
+ * d_voices past `written` are not touched.  Reads the bank only: state, globals, mix, reports and counters of every later
+ * block are bit-identical to the same blocks without the query.  The order is by voice index, never by arrival: two queries
+ * on the same state write the same bytes.  Two launches (a count whose last-arriving workgroup makes the offsets, a scatter);
+ * with SKRED_IDLE_UNNAMED, after an upload or an update that changed the routing, one more that rebuilds the set of named
+ * voices.  The bank owns the scratch they use: issue the queries of one bank on one stream at a time, as its renders.
+ * Refused, before anything touches the device: SKRED_E_BAD_ARG -- NULL bank, query or d_count, NULL d_voices with
+ * max_out > 0, no criterion bit, unknown bits, negative max_out, a settle_level that is negative or not finite;
+ * SKRED_E_RANGE -- count <= 0, a range outside the bank, `from` outside the range.
+ * On a shard: through skred_shard_bank(), with that rank's local indices.  Not in the fixed-point bank or the drop-in mode
+ * (whose 64 voices are named by the patch). */
+int  skred_bank_find_idle(skred_bank_t *bank, const skred_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only (not for the device, unlike skred_bank_download).
+ * Returns `written` (>= 0) or a SKRED_E_* code; *total_out may be NULL. */
+int  skred_bank_find_idle_host(skred_bank_t *bank, const skred_idle_query_t *q, int32_t *voices, int *total_out, void *stream);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

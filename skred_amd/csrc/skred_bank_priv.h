@@ -166,6 +166,14 @@ struct skred_bank {
   uint32_t *d_upd_cnt;              /* device [SK_UPD_RING]: arrival counters of those kernels' workgroups */
   uint32_t upd_seq;
   uint32_t *upd_mark, upd_epoch;    /* per-voice epoch marks: duplicate voices inside one batch */
+  /* the free-voice query (skred_bank_idle.c), everything allocated on first use */
+  uint32_t *d_idle;                 /* SK_IDLE_W_COUNT words, idle_wgs counts, idle_wgs offsets (skred_launch.h) */
+  int idle_wgs;
+  uint64_t *d_named;                /* [n_padded / 64] the named set: bit v = some voice of the bank names voice v as a modulator */
+  int named_dirty;                  /* the routing changed since d_named was built (sk_apply_meta): rebuilt by the next query that asks */
+  int32_t *d_idle_out;              /* skred_bank_find_idle_host: [2] counts, then the list, and its pinned twin */
+  int32_t *h_idle_out;
+  size_t idle_out_cap;              /* entries of the list */
 };
 
 /* per-voice classification (host shadow) */
@@ -219,6 +227,7 @@ int sk_bank_render_sum_pp(skred_bank_t *b, int num_frames, int interp, float *d_
 int sk_bank_master_pp(skred_bank_t *b, const float *d_sum, int num_frames, int num_channels, float *d_out, int parity, void *stream);
 void sk_queue_free(skred_bank_t *b);
 void sk_patterns_free(skred_bank_t *b);
+void sk_idle_free(skred_bank_t *b);          /* skred_bank_idle.c: the query's scratch (skred_bank_destroy) */
 /* a control action reached the bank: what earlier launches reported about envelope activity no longer holds (the voices it
  * touched went on the motion list on the device: skred_update_kernels.hip) */
 static inline void sk_control_changed(skred_bank_t *b) { b->control_epoch++; b->env_quiet = 0; b->list_empty = 0; }

@@ -181,11 +181,12 @@ void sk_apply_meta(skred_bank_t *b, int dst, const sk_voice_meta_t *m, int param
   }
   for (int k = 0; k < 4; k++) {
     int8_t *slot = &b->h_mod[(size_t)k * b->n_padded + dst];
-    if (*slot != m->mod_lane[k]) { *slot = m->mod_lane[k]; b->mod_dirty = 1; b->class_dirty = 1; b->h_pack_dirty[dst >> 6] = 1; b->pack_any_dirty = 1; }
+    if (*slot != m->mod_lane[k]) { *slot = m->mod_lane[k]; b->mod_dirty = 1; b->class_dirty = 1; b->h_pack_dirty[dst >> 6] = 1; b->pack_any_dirty = 1; b->named_dirty = 1; }
   }
   if ((b->features | m->features) != b->features) { b->features |= m->features; b->class_dirty = 1; b->mod_dirty = 1; }
   /* cross-group modulators: kept on the host (the tape's plan is made from them); nothing is allocated before the first one */
   if (!b->h_esc && (m->esc[0] >= 0 || m->esc[1] >= 0 || m->esc[2] >= 0 || m->esc[3] >= 0)) {
+    b->named_dirty = 1;                 /* (the named set of the free-voice query: skred_bank_idle.c) */
     const size_t n = (size_t)b->n_padded;
     b->h_esc = (int32_t *)malloc(4 * n * sizeof(int32_t));
     b->h_slot = (int32_t *)malloc(n * sizeof(int32_t));
@@ -196,7 +197,7 @@ void sk_apply_meta(skred_bank_t *b, int dst, const sk_voice_meta_t *m, int param
   if (b->h_esc) {
     for (int k = 0; k < 4; k++) {
       int32_t *slot = &b->h_esc[(size_t)k * b->n_padded + dst];
-      if (*slot != m->esc[k]) { *slot = m->esc[k]; b->tape_dirty = 1; b->class_dirty = 1; }
+      if (*slot != m->esc[k]) { *slot = m->esc[k]; b->tape_dirty = 1; b->class_dirty = 1; b->named_dirty = 1; }
     }
   }
 }

@@ -1,0 +1,167 @@
+// skred_idle_kernels.hip -- which voices of a range are idle: an ordered list, built on the device (gfx950 / CDNA4).
+//
+// skred_bank_find_idle (include/skred_amd.h): a sweep over the few state words the predicate needs, and an ordered
+// compaction.  Two launches on the caller's stream, behind the renders and updates queued on it:
+//
+//   sk_idle_count_kernel    every workgroup takes SK_IDLE_SPAN consecutive voices (spans are aligned to 64 voices, so a
+//                           wavefront reads 1 KiB of a plane and one word of the named set), evaluates the predicate,
+//                           ballots per wave and publishes its count.  The workgroup that ARRIVES LAST
+//                           (skred_kernel_common.hpp: sk_arrive_last -- write-through stores, one ticket, re-armed for the
+//                           next launch) turns the counts into exclusive offsets and writes d_count and the rank of `from`.
+//                           No workgroup waits for another: nothing here can spin or hang.
+//   sk_idle_scatter_kernel  the same spans, evaluated again (the lines are in L2 for small banks, and the sweep is a few
+//                           words per voice): rank = workgroup offset + wave prefix + mbcnt of the ballot, rotated by the
+//                           rank of `from` modulo the total, stored when it is below max_out.
+//
+// The order is fixed by the voice index, never by arrival: two queries on the same state write the same bytes.  Both
+// kernels only READ the bank.  Only the planes the query's bits need are requested: flags (SKP_TAB.z) and the smoother
+// gain (SKS_OSC.y) for ENV_DONE, amp (SKP_OSC.w) for AMP_ZERO, rwflags (SKS_FILT.w) for FINISHED and ENV_DONE -- a word
+// costs its 16-byte plane entry, 64 bytes per voice at most.
+//
+//   sk_named_kernel         the named set (bit v: some voice of the bank names v as FM / AM / pan / CZ modulator), rebuilt
+//                           from the SKP_MODI plane when the routing changed and a query asks for SKRED_IDLE_UNNAMED.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "skred_kernel_common.hpp"
+#include "skred_launch.h"
+
+#define SK_IDLE_WAVES (SK_IDLE_SPAN / 64)
+
+// the predicate of one voice (v inside the padded bank; `in_range`: inside the query's range)
+__device__ __forceinline__ bool sk_idle_pred(const sk_idle_args_t &a, int v, bool in_range) {
+  if (!in_range) return false;
+  const uint32_t which = a.which;   // wave-uniform: the branches below are scalar
+  bool idle = false;
+  uint32_t rwf = 0;
+  if (which & (SK_IDLE_FINISHED | SK_IDLE_ENV_DONE)) rwf = a.filt[v].w[3];
+  if (which & SK_IDLE_FINISHED) idle = (rwf & SKR_FINISHED) != 0;
+  if (which & SK_IDLE_ENV_DONE) {
+    const uint32_t flags = a.tab[v].w[2];
+    const float gain = __uint_as_float(a.osc_rw[v].w[1]);
+    const bool settled = !(flags & SKF_SMOOTH) || fabsf(gain) <= a.settle_level;
+    idle = idle || ((flags & SKF_USE_ENV) && !(rwf & SKR_ENV_ACTIVE) && settled);
+  }
+  if (which & SK_IDLE_AMP_ZERO) idle = idle || __uint_as_float(a.osc_ro[v].w[3]) == 0.0f;
+  if (which & SK_IDLE_UNNAMED) idle = idle && !((a.named[v >> 6] >> (v & 63)) & 1);
+  return idle;
+}
+
+__device__ __forceinline__ int sk_idle_voice(const sk_idle_args_t &a, bool &in_range) {
+  const int v = a.base + (int)blockIdx.x * SK_IDLE_SPAN + (int)threadIdx.x;   // base: `first` rounded down to 64
+  in_range = v >= a.first && v < a.end;
+  return v;
+}
+
+__global__ __launch_bounds__(SK_IDLE_SPAN) void sk_idle_count_kernel(sk_idle_args_t a) {
+  __shared__ int lds[SK_IDLE_SPAN + 2 * SK_IDLE_WAVES + 1];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  bool in_range;
+  const int v = sk_idle_voice(a, in_range);
+  const bool idle = sk_idle_pred(a, v, in_range);
+  const unsigned long long ballot = __ballot(idle);
+  // the rank of `from`: the idle voices below it.  Its workgroup counts the ones inside its own span.
+  const unsigned long long below = __ballot(idle && v < a.from);
+  if ((tid & 63) == 0) { lds[wave] = __popcll(ballot); lds[SK_IDLE_WAVES + wave] = __popcll(below); }
+  __syncthreads();
+  if (tid == 0) {
+    int c = 0, p = 0;
+#pragma unroll
+    for (int w = 0; w < SK_IDLE_WAVES; ++w) { c += lds[w]; p += lds[SK_IDLE_WAVES + w]; }
+    __hip_atomic_store((sk_gu32 *)(a.counts + blockIdx.x), (uint32_t)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if ((int)blockIdx.x == a.from_wg)
+      __hip_atomic_store((sk_gu32 *)(a.words + SK_IDLE_W_PART), (uint32_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (!sk_arrive_last(a.words + SK_IDLE_W_TICKET, gridDim.x, tid, &lds[2 * SK_IDLE_WAVES])) return;
+  // ---- the last arriver: exclusive offsets of all workgroups, in index order.  Thread t owns a contiguous run of counts.
+  const int n = (int)gridDim.x;
+  const int per = (n + SK_IDLE_SPAN - 1) / SK_IDLE_SPAN;
+  const int lo = min(tid * per, n), hi = min(lo + per, n);
+  int sum = 0;
+  for (int i = lo; i < hi; ++i) sum += (int)a.counts[i];
+  int *scan = &lds[2 * SK_IDLE_WAVES + 1];
+  scan[tid] = sum;
+  __syncthreads();
+  for (int d = 1; d < SK_IDLE_SPAN; d <<= 1) {          // inclusive scan of the per-thread sums
+    const int add = tid >= d ? scan[tid - d] : 0;
+    __syncthreads();
+    scan[tid] += add;
+    __syncthreads();
+  }
+  int run = scan[tid] - sum;
+  for (int i = lo; i < hi; ++i) {
+    a.offsets[i] = (uint32_t)run;
+    if (i == a.from_wg) a.words[SK_IDLE_W_RANK] = (uint32_t)run + a.words[SK_IDLE_W_PART];
+    run += (int)a.counts[i];
+  }
+  if (tid == SK_IDLE_SPAN - 1) {
+    const uint32_t total = (uint32_t)scan[tid];
+    a.words[SK_IDLE_W_TOTAL] = total;
+    a.d_count[0] = total < (uint32_t)a.max_out ? total : (uint32_t)a.max_out;
+    a.d_count[1] = total;
+  }
+}
+
+__global__ __launch_bounds__(SK_IDLE_SPAN) void sk_idle_scatter_kernel(sk_idle_args_t a) {
+  __shared__ int lds[SK_IDLE_WAVES];
+  const int tid = threadIdx.x, wave = tid >> 6;
+  bool in_range;
+  const int v = sk_idle_voice(a, in_range);
+  const bool idle = sk_idle_pred(a, v, in_range);
+  const unsigned long long ballot = __ballot(idle);
+  if ((tid & 63) == 0) lds[wave] = __popcll(ballot);
+  __syncthreads();
+  if (!idle) return;
+  int rank = (int)a.offsets[blockIdx.x];
+  for (int w = 0; w < wave; ++w) rank += lds[w];
+  rank += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+  const int total = (int)a.words[SK_IDLE_W_TOTAL];
+  int at = rank - (int)a.words[SK_IDLE_W_RANK];       // the list starts at the first idle voice >= from and wraps
+  if (at < 0) at += total;
+  if (at >= 0 && at < a.max_out) a.d_voices[at] = v;
+}
+
+// one thread per voice of the padded bank; `named` was cleared ahead of the launch
+__global__ __launch_bounds__(256) void sk_named_kernel(const sk_plane_t *__restrict__ tab, const sk_plane_t *__restrict__ modi,
+                                                       int n_padded, int n_voices, uint64_t *named) {
+  const int v = blockIdx.x * 256 + threadIdx.x;
+  if (v >= n_padded) return;
+  if (!(tab[v].w[2] & SKF_HAS_MOD)) return;           // (a slot nobody uploaded holds zeros in SKP_MODI, not -1)
+  const uint4 m = *reinterpret_cast<const uint4 *>(&modi[v]);
+  const int32_t w[4] = { (int32_t)m.x, (int32_t)m.y, (int32_t)m.z, (int32_t)m.w };
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    // skred_bank_update.c, sk_pack_voice: a lane of the carrier's own 64-voice group, the tape code -2 - md of a voice in
+    // another group, or -1 (unused; FM by the voice itself; a CZ source with CZ off; a modulator outside the bank)
+    int md = -1;
+    if (w[k] >= 0 && w[k] < 64) md = (v & ~63) | w[k];
+    else if (w[k] <= -2) md = -2 - w[k];
+    if (md >= 0 && md < n_voices)
+      atomicOr(reinterpret_cast<unsigned long long *>(named) + (md >> 6), 1ull << (md & 63));
+  }
+}
+
+extern "C" int sk_launch_named(const sk_plane_t *tab, const sk_plane_t *modi, int n_padded, int n_voices, uint64_t *named,
+                               hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(named, 0, (size_t)(n_padded / 64) * sizeof(uint64_t), stream);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(sk_named_kernel, dim3((unsigned)((n_padded + 255) / 256)), dim3(256), 0, stream, tab, modi, n_padded, n_voices, named);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sk_idle_workgroups(int first, int count) {
+  const int base = first & ~63;
+  return (first + count - base + SK_IDLE_SPAN - 1) / SK_IDLE_SPAN;
+}
+
+extern "C" int sk_launch_idle(const sk_idle_args_t *args, hipStream_t stream) {
+  sk_idle_args_t a = *args;
+  a.base = a.first & ~63;
+  const int n_wg = sk_idle_workgroups(a.first, a.end - a.first);
+  a.from_wg = (a.from - a.base) / SK_IDLE_SPAN;
+  hipLaunchKernelGGL(sk_idle_count_kernel, dim3((unsigned)n_wg), dim3(SK_IDLE_SPAN), 0, stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess || a.max_out <= 0) return (int)e;
+  hipLaunchKernelGGL(sk_idle_scatter_kernel, dim3((unsigned)n_wg), dim3(SK_IDLE_SPAN), 0, stream, a);
+  return (int)hipGetLastError();
+}

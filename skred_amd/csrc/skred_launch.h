@@ -11,6 +11,7 @@
  *   skred_mix_kernels.hip     sk_launch_master, sk_launch_master_apply
  *   skred_update_kernels.hip  sk_launch_update, sk_launch_stamp, sk_launch_pack_zero
  *   skred_rec_kernels.hip     sk_launch_rec_minmax, sk_rec_partial_floats, sk_launch_rec_convert
+ *   skred_idle_kernels.hip    sk_launch_idle, sk_idle_workgroups, sk_launch_named
  *
  * Every launcher returns the hipError_t of the launch as an int.
  */
@@ -80,6 +81,37 @@ int sk_launch_stamp(const int32_t *d_ids, int n, uint32_t dirty, sk_plane_t *con
 
 /* packed lanes: voice_sample = 0 for every voice without a bit in d_mask (one bit per voice of the padded bank) */
 int sk_launch_pack_zero(const uint64_t *d_mask, sk_plane_t *filt, int n_voices_padded, hipStream_t stream);
+
+/* ---- the free-voice query (skred_bank_idle.c -> skred_idle_kernels.hip; include/skred_amd.h: skred_bank_find_idle) ----
+ * The bits equal SKRED_IDLE_* (checked at compile time in skred_bank_idle.c). */
+#define SK_IDLE_FINISHED (1u << 0)
+#define SK_IDLE_ENV_DONE (1u << 1)
+#define SK_IDLE_AMP_ZERO (1u << 2)
+#define SK_IDLE_UNNAMED  (1u << 8)
+#define SK_IDLE_SPAN 256           /* voices (and threads) per workgroup of both kernels */
+/* the bank's scratch: SK_IDLE_W_COUNT words, then the workgroups' counts, then their exclusive offsets */
+enum { SK_IDLE_W_TICKET = 0,      /* arrival ticket of the count kernel, re-armed by its last arriver */
+       SK_IDLE_W_PART,            /* idle voices below `from` inside from's own workgroup */
+       SK_IDLE_W_RANK,            /* idle voices of the range below `from` */
+       SK_IDLE_W_TOTAL,           /* idle voices of the range */
+       SK_IDLE_W_COUNT };
+typedef struct {
+  const sk_plane_t *osc_ro, *tab;  /* SKP_OSC (amp in .w), SKP_TAB (flags in .z) */
+  const sk_plane_t *osc_rw, *filt; /* SKS_OSC (smoother gain in .y), SKS_FILT (rwflags in .w) */
+  const uint64_t *named;           /* [n_padded / 64] or NULL without SK_IDLE_UNNAMED */
+  uint32_t *words, *counts, *offsets;
+  int32_t *d_voices;
+  uint32_t *d_count;
+  int32_t first, end, from;        /* the range [first, end), the voice the listing starts at */
+  int32_t max_out;
+  uint32_t which;
+  float settle_level;
+  int32_t base, from_wg;           /* filled by sk_launch_idle: first rounded down to 64, the workgroup that holds `from` */
+} sk_idle_args_t;
+int sk_idle_workgroups(int first, int count);           /* workgroups (entries of counts / offsets) a range takes */
+int sk_launch_idle(const sk_idle_args_t *args, hipStream_t stream);   /* count, then (max_out > 0) scatter */
+/* the named set: bit v of named[] = some voice of the bank names voice v as a modulator (cleared, then rebuilt from SKP_MODI) */
+int sk_launch_named(const sk_plane_t *tab, const sk_plane_t *modi, int n_padded, int n_voices, uint64_t *named, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

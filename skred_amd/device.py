@@ -35,12 +35,21 @@ ABI_SYMBOLS = [
     "skred_seq_mute_set", "skred_seq_modulo_set", "skred_seq_state_set", "skred_seq_pattern_reset", "skred_seq_pointer",
     "skred_seq_counter", "skred_seq_tick",
     "skred_bank_seq", "skred_bank_set_sample_rate", "skred_bank_pattern_step_set", "skred_bank_pattern_step_clear",
+    "skred_bank_find_idle", "skred_bank_find_idle_host",
 ]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
 DIRTY_FILTER_STATE, DIRTY_SMOOTHER, DIRTY_HOLD, DIRTY_SAMPLE = 16, 32, 64, 128
 STAMP_TRIGGER, STAMP_RELEASE, DIRTY_ENV_CLOCK = 256, 512, 1024
+# SKRED_IDLE_* (skred_bank_find_idle)
+IDLE_FINISHED, IDLE_ENV_DONE, IDLE_AMP_ZERO, IDLE_UNNAMED = 1, 2, 4, 256
+
+
+class IdleQueryC(C.Structure):
+    """ctypes image of ``skred_idle_query_t``."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("which", C.c_uint32), ("settle_level", C.c_float),
+                ("start", C.c_int32), ("max_out", C.c_int32)]          # `start`: the header's `from`
 
 _lib: Optional[C.CDLL] = None
 
@@ -122,6 +131,8 @@ def load() -> C.CDLL:
     L.skred_bank_set_sample_rate.argtypes = [vp, C.c_float]
     L.skred_bank_pattern_step_set.argtypes = [vp, i32, i32, C.POINTER(VoiceBankC), vp, i32, C.c_uint32]
     L.skred_bank_pattern_step_clear.argtypes = [vp, i32, i32]
+    L.skred_bank_find_idle.argtypes = [vp, C.POINTER(IdleQueryC), vp, vp, vp]
+    L.skred_bank_find_idle_host.argtypes = [vp, C.POINTER(IdleQueryC), vp, C.POINTER(i32), vp]
     _lib = L
     return L
 
@@ -249,6 +260,28 @@ class DeviceBank:
 
     def pattern_step_clear(self, pattern: int, step: int):
         _check(self.L.skred_bank_pattern_step_clear(self.h, pattern, step), "skred_bank_pattern_step_clear")
+
+    # ---- the free-voice query (include/skred_amd.h: skred_bank_find_idle / _find_idle_host) ----
+    def find_idle(self, first: int, count: int, which: int, settle_level: float = 0.0, start: Optional[int] = None,
+                  max_out: int = 0, d_voices: int = 0, d_count: int = 0, stream: int = 0):
+        """Asynchronous on `stream`: the idle voices of [first, first + count) in ascending order from `start` (default `first`),
+        wrapping, into d_voices[0 .. written) (int32, device memory); d_count[0] = written, d_count[1] = total (uint32)."""
+        q = IdleQueryC(int(first), int(count), int(which), float(settle_level), int(first if start is None else start), int(max_out))
+        _check(self.L.skred_bank_find_idle(self.h, C.byref(q), d_voices or None, d_count or None, stream or None),
+               "skred_bank_find_idle")
+
+    def find_idle_host(self, first: int, count: int, which: int, settle_level: float = 0.0, start: Optional[int] = None,
+                       max_out: Optional[int] = None, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the listed voices, total)."""
+        max_out = count if max_out is None else max_out
+        q = IdleQueryC(int(first), int(count), int(which), float(settle_level), int(first if start is None else start), int(max_out))
+        out = np.empty(max(max_out, 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_bank_find_idle_host(self.h, C.byref(q), out.ctypes.data if max_out > 0 else None, C.byref(total),
+                                             stream or None)
+        if n < 0:
+            _check(n, "skred_bank_find_idle_host")
+        return out[:n].copy(), int(total.value)
 
     def force_generic(self, on: bool = True):
         _check(self.L.skred_bank_set_option(self.h, 1, int(on)), "skred_bank_set_option")

@@ -16,6 +16,10 @@
              edges -- each beside the same routings kept inside the groups
   taps       what voice taps cost (skred_bank_set_taps): 18.sk tiled over 2^20 voices, 512 frames, packed lanes, with 0 and with 64
              taps (voices 0 and 10 -- a source and the carrier it modulates in its own frame -- of 32 copies spread over the bank)
+  idle       the free-voice query (skred_bank_find_idle) on c2 banks of 65 536 and 2^20 voices after ten blocks of note traffic: (a) its
+             launches between an event pair (every criterion, UNNAMED off and on, max_out 1 024; median and minimum of 50), beside one
+             512-frame block of the same bank; (b) what a host does for the same answer without it: skred_bank_download of the bank
+             plus the predicate in numpy
 
 Each line: ms per block over the timed blocks (wall clock), voice-samples/s, and the render kernel's duration from the
 library's own event pair around the latest bracketed launch (a bracketed launch runs alone).  kernels / fm / noise print
@@ -267,8 +271,65 @@ def live():
     db.close()
 
 
+def idle():
+    D = device
+    F, M = 512, 1024
+    for n in (65536, 1 << 20):
+        bank, tables, g = banks.bank_c2(n)
+        bank["voice_amp_envelope"]["release_time"] = np.float32(300.0)
+        db = device.DeviceBank(n)
+        db.set_tables(tables); db.upload(bank); db.set_globals(g); db.kernel_timing(1)
+        out = torch.zeros(F, 2, device="cuda")
+        rng = np.random.default_rng(1)
+        for _ in range(10):
+            vs = rng.choice(n, n // 8, replace=False).astype(np.int32)
+            db.update(bank, vs, D.STAMP_RELEASE)
+            db.render_mix(F, out.data_ptr(), 2)
+        torch.cuda.synchronize()
+        block_ms = db.last_render_ms()
+        dv = torch.full((M,), -1, dtype=torch.int32, device="cuda")
+        dc = torch.zeros(2, dtype=torch.int32, device="cuda")
+        crit = D.IDLE_FINISHED | D.IDLE_ENV_DONE | D.IDLE_AMP_ZERO
+        for label, which, planes in (("UNNAMED off", crit, 4), ("UNNAMED on", crit | D.IDLE_UNNAMED, 4)):
+            for _ in range(5):
+                db.find_idle(0, n, which, 1e-3, n // 2, M, dv.data_ptr(), dc.data_ptr())
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(50):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                db.find_idle(0, n, which, 1e-3, n // 2, M, dv.data_ptr(), dc.data_ptr())
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            med, mn = float(np.median(ms)), float(np.min(ms))
+            req = 2 * planes * 16 * n                            # both launches sweep the range; a word costs its 16-byte plane entry
+            print(f"c2 {n} find_idle, every criterion, {label}, max_out {M}: median {med:.4f} ms, min {mn:.4f} ms for count + scatter "
+                  f"(total idle {int(dc[1])}, written {int(dc[0])}); {2 * planes * 16} B requested per voice over both launches = "
+                  f"{req / (mn * 1e-3) / 1e12:.3f} TB/s at the minimum ({req / (mn * 1e-3) / 8e12 * 100:.1f} % of the 8 TB/s HBM peak); "
+                  f"one {F}-frame block of this bank: {block_ms:.4f} ms")
+        got = bank.copy()
+        ts = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            db.download(got)
+            a, e = got.a, got.a["voice_amp_envelope"]
+            lst = np.flatnonzero((a["voice_finished"] != 0) | (a["voice_amp"] == 0) |
+                                 ((a["voice_use_amp_envelope"] != 0) & (e["is_active"] == 0) &
+                                  ((a["voice_smoother_enable"] == 0) | (np.abs(a["voice_smoother_gain"]) <= np.float32(1e-3)))))
+            ts.append(time.perf_counter() - t0)
+        print(f"c2 {n} the same answer on the host: skred_bank_download of the bank + the predicate in numpy: best of 3 {min(ts) * 1e3:.3f} ms "
+              f"({len(lst)} idle voices)")
+        t0 = time.perf_counter()
+        for _ in range(20):
+            db.find_idle_host(0, n, crit, 1e-3, n // 2, M)
+        print(f"c2 {n} find_idle_host (launches, copy of {M} entries, stream synchronise): {(time.perf_counter() - t0) / 20 * 1e3:.4f} ms per call")
+        db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
