@@ -1,7 +1,8 @@
 /*
  * skred_bank_priv.h -- internals shared by the translation units behind include/skred_amd.h
- * (skred_bank.c: lifecycle, upload / download, render; skred_bank_update.c: block-granular updates
- * and the deferred queue).  Not installed.
+ * (skred_bank.c: lifecycle, tables, upload / download, options, class and tape plan; skred_bank_render.c:
+ * one block from request to kernels, as skred_bank_plan.c picks them; skred_bank_update.c: block-granular
+ * updates and the deferred queue).  Not installed.
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -11,6 +12,7 @@
 #include <stdint.h>
 
 #include "skred_amd.h"
+#include "skred_bank_plan.h"
 #include "skred_device_layout.h"
 #include "skred_launch.h"
 
@@ -24,11 +26,6 @@ typedef struct {
   uint32_t seq;               /* != 0: a batch read from this slot is in flight; its last kernel stores this number into the bank's
                                  h_upd_done[slot] when it has run (no event: skred_update_kernels.hip, sk_batch_done) */
 } sk_upd_slot_t;
-#define SK_SPLIT_MAX_LDS (160u * 1024u)   /* LDS of a CU: sk_render_split_kernel's workgroup must fit (twice, for two workgroups per CU) */
-#define SK_FM2_MIN_VOICES 1024      /* two-operator FM banks at least this large keep each (carrier, modulator) pair in one lane */
-#define SK_FAST2_MOTION_MIN_VOICES 278528   /* ... while envelopes move: banks smaller than this stay on the one-voice kernel (round 3, the envelope kernel
-                                               beside the steady one: 262 144 voices 184 vs 198 us per block, 294 912 voices 214 vs 202; tools/ab_env_mid.py) */
-#define SK_FAST2_MIN_VOICES 212992   /* banks at least this large use two voices per lane (measured crossover, 512-frame blocks, C2 recipe: 196608 voices 86 vs 95 us, 262144 voices 108 vs 101 us; profiles/r02_v1_measure_banks.txt) */
 
 struct skred_bank {
   int device;
@@ -71,7 +68,7 @@ struct skred_bank {
                                  the envelope kernel is then not launched -- with an empty list it has nothing to render */
   uint32_t *d_violations;     /* sticky device counter: sk_render_fast2_kernel found a moving voice that was not listed; the word behind
                                  it: sk_gain_kernel's row counter (skred_device_layout.h: env_count) */
-  /* listed voices rendered in place (render_block): the gain rows, and a proven upper bound on the current list's length --
+  /* listed voices rendered in place (skred_bank_plan.c: sk_plan_finish): the gain rows, and a proven upper bound on the current list's length --
    * the length launch t reported plus the voices control actions have touched since launch t was issued */
   float *d_env_gain;
   size_t env_gain_cap;        /* floats */
@@ -91,7 +88,7 @@ struct skred_bank {
   int split_mode;             /* SKRED_OPT_SPLIT: 0 never, 1 where it is the faster form (default), 2 whenever the bank qualifies */
   int split_pairs;            /* SKRED_OPT_SPLIT_PAIRS: 0 the library's choice, 2 / 4 forced (tests) */
   int last_split;             /* the latest block ran sk_render_split_kernel */
-  /* packed lanes of sparse banks (skred_device_layout.h: pack_mask; skred_bank.c: pack_refresh, render_block) */
+  /* packed lanes of sparse banks (skred_device_layout.h: pack_mask; skred_bank.c: sk_pack_refresh, skred_bank_plan.c: sk_plan_finish) */
   int pack_mode;              /* SKRED_OPT_PACK: 0 never, 1 where it pays (default) */
   int fm_skew;                /* SKRED_OPT_FM_SKEW: modulator lanes a block ahead of their carriers (default 1) */
   uint64_t *h_pack_mask;      /* [n_padded / 64] per aligned 64-voice group: voices that can sound, and the modulators they name */
@@ -133,7 +130,7 @@ struct skred_bank {
   size_t tape_cap;            /* floats */
   int last_tape_sources, last_tape_levels;      /* of the latest block (0, 0: it read no tape) */
   int mod_dirty;              /* modulator lanes changed: dependency levels must be recomputed */
-  uint32_t fast_mode;         /* SKM_* from classify() */
+  uint32_t fast_mode;         /* SKM_* from sk_classify() */
   int force_generic;          /* SKRED_OPT_FORCE_GENERIC */
   int fast2_min_voices;       /* SKRED_OPT_FAST2_MIN_VOICES */
   int fm2_min_voices;         /* SKRED_OPT_FM2_MIN_VOICES */
@@ -177,13 +174,10 @@ struct skred_bank {
 };
 
 /* per-voice classification (host shadow) */
-#define SK_INPLACE_WORD_ROWS 8                   /* gain rows every 64-voice word of the list owns */
-#define SK_INPLACE_DENOM 6                       /* lists up to n_voices / 6 are rendered in place (a 128-voice wave stages at most 32) */
-#define SK_INPLACE_MAX_BYTES ((size_t)4 << 30)   /* ... while the gain rows stay below this */
 #define SKC_REAL   1u   /* a voice was uploaded into this slot and it can sound (has a table) */
 #define SKC_FILTER 2u
 #define SKC_ENV    4u
-#define SKC_EXOTIC 8u   /* needs the generic kernel: see classify() */
+#define SKC_EXOTIC 8u   /* needs the generic kernel: see sk_plan_class_mode() */
 #define SKC_FM    32u   /* carrier of a higher-indexed modulator of its 64-voice group, nothing else modulated */
 #define SKC_STOPS 16u   /* one-shot without loop (plays to its table end and finishes) or reverse playback: the one-per-lane kernel's extended instantiation */
 #define SKC_FM_ODD 256u /* an SKC_FM voice that is anything but: even index, frequency-modulated by the voice after it and by nothing else
@@ -222,7 +216,11 @@ int sk_pack_voice(const skred_bank_t *b, const skred_voice_bank_t *h, int v, int
                   sk_plane_t ro[SKP_COUNT], sk_plane_t rw[SKS_COUNT], sk_voice_meta_t *meta);
 /* params_travel: the parameter planes were written, so `meta` applies (a pure clock / state update leaves the classes alone) */
 void sk_apply_meta(skred_bank_t *b, int dst, const sk_voice_meta_t *meta, int params_travel);
-/* the pipelined multi-GPU form's two halves of a block (skred_bank.c; used by skred_shard.c) */
+/* skred_bank.c, for render_block: the class mode, dependency levels and tape plan, made again where the voices changed; the lane
+ * words of the groups whose voices changed (returns the most lanes a group needs) */
+int sk_classify(skred_bank_t *b);
+int sk_pack_refresh(skred_bank_t *b);
+/* the pipelined multi-GPU form's two halves of a block (skred_bank_render.c; used by skred_shard.c) */
 int sk_bank_render_sum_pp(skred_bank_t *b, int num_frames, int interp, float *d_sum, int parity, void *stream);
 int sk_bank_master_pp(skred_bank_t *b, const float *d_sum, int num_frames, int num_channels, float *d_out, int parity, void *stream);
 void sk_queue_free(skred_bank_t *b);

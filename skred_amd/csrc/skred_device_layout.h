@@ -72,7 +72,7 @@ enum {
                                       semantics): the one-per-lane kernel can do it; sk_render_mod_kernel otherwise */
 
 /* fast_mode word (host -> launcher) */
-#define SKM_FAST        (1u << 0)  /* bank qualifies for sk_render_fast_kernel (see skred_bank.c:classify) */
+#define SKM_FAST        (1u << 0)  /* bank qualifies for sk_render_fast_kernel (see skred_bank_plan.c: sk_plan_class_mode) */
 #define SKM_FILTER_ALL  (1u << 1)  /* every live voice runs the biquad (with SKM_MIXED: some do) */
 #define SKM_ENV_ALL     (1u << 2)  /* every live voice uses the amp envelope (with SKM_MIXED: some do) */
 #define SKM_TWO_PER_LANE (1u << 3) /* large bank: sk_render_fast2_kernel (two voices per lane, packed fp32) */
@@ -214,7 +214,7 @@ typedef struct {
   const int32_t *probe_ids; /* [n_probe] voice numbers */
   float *probe_out;         /* [num_frames][n_probe][2], zeroed by the host before the launch (a skipped / muted voice writes nothing) */
   int32_t n_probe;
-  /* ---- packed lanes (sparse banks; skred_bank.c: render_block decides): most voices of the bank are skipped by the reference's own
+  /* ---- packed lanes (sparse banks; skred_bank_plan.c: sk_plan_finish decides): most voices of the bank are skipped by the reference's own
    * rule (voice_amp == 0, synth.c:537) for as long as nobody changes them, so a wave of the one-voice family takes the voices
    * that CAN sound of 2^(6 - pack_shift) aligned 64-voice groups instead of all 64 voices of one -- group j of the wave owns lanes
    * [j << pack_shift, (j + 1) << pack_shift), the k-th set bit of pack_mask[group] is the voice in its k-th lane.  A bit is set for

@@ -1,6 +1,6 @@
 // skred_gain_kernels.hip -- sk_gain_kernel: the envelopes of the voices on the motion list, one block ahead of the samples.
 //
-// Two-per-lane family, sparse lists (skred_bank.c: render_block decides).  The steady kernel has no room for envelope code
+// Two-per-lane family, sparse lists (skred_bank_plan.c: sk_plan_finish decides).  The steady kernel has no room for envelope code
 // (it sits at its register budget, and a voice in motion rendered by a second kernel BESIDE it costs a third round of
 // workgroups: DESIGN "The motion list"), but the envelope of a voice needs nothing from its samples: amp_envelope_step
 // (synth.c:398-431) is a function of the clock, the note's two time stamps and four constants.  So this kernel, ahead of the

@@ -225,7 +225,7 @@ __device__ __forceinline__ void sk_final_cols(const sk_render_args_t &a, int tid
       }
     }
   }
-  // what this launch found, straight into the host's pinned words (skred_bank.c: poll_reports)
+  // what this launch found, straight into the host's pinned words (skred_bank_render.c: poll_reports)
   if (a.report) {
     uint32_t w0 = 0, w1 = 0;
     if (a.fast_mode & SKM_TWO_PER_LANE) {

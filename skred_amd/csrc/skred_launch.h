@@ -13,7 +13,9 @@
  *   skred_rec_kernels.hip     sk_launch_rec_minmax, sk_rec_partial_floats, sk_launch_rec_convert
  *   skred_idle_kernels.hip    sk_launch_idle, sk_idle_workgroups, sk_launch_named
  *
- * Every launcher returns the hipError_t of the launch as an int.
+ * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
+ * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c
+ * and skred_recorder.c.
  */
 #ifndef SKRED_LAUNCH_H
 #define SKRED_LAUNCH_H

@@ -5,7 +5,7 @@
 // ---------------------------------------------------------------- fast render kernel
 //
 // Same arithmetic, per voice bit-identical to the generic kernel above, for "clean" banks -- the
-// host only selects it when (bank-wide, skred_bank.c:classify): no one-shot voice that stops at
+// host only selects it when (bank-wide, skred_bank_plan.c: sk_plan_class_mode): no one-shot voice that stops at
 // its table end, no reverse playback, no sample&hold / bit-crush / noise voices, no modulators,
 // smoother on everywhere, filter on for ALL voices or for none, envelope for ALL or none, and
 // every phase / increment / loop bound finite (so the !isfinite() branch of osc_next can never

@@ -12,7 +12,7 @@
 //     unfused, hence bit-identical), and
 //   * the 12-instruction cross-lane DPP reduction is paid once per 128 voices instead of per 64.
 // Compares, selects, float->int conversion and the LDS gathers stay per voice.  Used for large
-// clean banks (the host decides, skred_bank.c); per-voice results equal the other two kernels'.
+// clean banks (the host decides, skred_bank_plan.c); per-voice results equal the other two kernels'.
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -1295,7 +1295,7 @@ extern "C" int sk_launch_classify(const sk_render_args_t *args, uint64_t *mask, 
 // ---------------------------------------------------------------- launchers (C linkage)
 
 // sk_launch_render_fast2: the steady kernel (args->skip_env2: alone; otherwise the host has put sk_launch_render_env2 on
-// its second stream first -- skred_bank.c: render_block).  sk_launch_render_env2: collect + the envelope kernel.
+// its second stream first -- skred_bank_render.c: launch_block).  sk_launch_render_env2: collect + the envelope kernel.
 #ifdef SK_PROBE_TU
 #define SK_PROBE_FLAG true
 #else

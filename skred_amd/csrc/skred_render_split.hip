@@ -32,7 +32,7 @@
 // constant envelope level on every lane for the whole launch.  Anything else -- an envelope in motion because the host's
 // "nothing moves" hint was stale, a huge increment, stems -- is rendered by the owner wave alone, frame by frame, on the
 // general path of skred_fast_common.hpp (its oscillator wave idles): slow, rare, and the same bits.  The host launches this
-// kernel only while it believes nothing moves (skred_bank.c: render_block), so the hint decides speed, never samples.
+// kernel only while it believes nothing moves (skred_bank_plan.c: sk_plan_finish), so the hint decides speed, never samples.
 //
 // Where it pays (tools/ab_split.py, profiles/r04_*): banks of up to one 64-voice group per SIMD.  From two groups per SIMD on
 // (the 2^17-voice shard of config 3) the SIMD's VALU is the bound, not the wave's issue rate, and the ring traffic and the

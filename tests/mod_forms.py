@@ -1,5 +1,5 @@
 """Which form each wavefront of the modulated kernel (skred_render_generic.hip: sk_render_mod_kernel) takes, predicted from the bank:
-the host's dependency levels (skred_bank.c: classify) and the kernel's lag vote, for the unpacked layout (one 64-voice group per
+the host's dependency levels (skred_bank_plan.c: sk_plan_levels) and the kernel's lag vote, for the unpacked layout (one 64-voice group per
 wavefront).  The tests compare this with what the kernel counted (skred_bank_set_form_counter)."""
 import numpy as np
 
@@ -62,7 +62,7 @@ def expected_counts(bank, frames, skew):
     return [int(lag.sum()), waves - int(lag.sum())]
 
 
-# ---- packed lanes (SKRED_OPT_PACK; skred_bank.c: pack_refresh, skred_device_layout.h: pack_mask) ----
+# ---- packed lanes (SKRED_OPT_PACK; skred_bank.c: sk_pack_refresh, skred_device_layout.h: pack_mask) ----
 
 def far_sources(bank):
     """The distinct modulators that sit outside their reader's 64-voice group: the sources of the tape (SKRED_OPT_CROSS_GROUP)."""

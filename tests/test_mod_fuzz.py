@@ -71,7 +71,7 @@ def plan(routing, seed):
 
 
 def cross_plan(bank):
-    """(sources, pre-pass levels) the library must report for `bank` (skred_bank.c: tape_plan): the distinct modulators outside
+    """(sources, pre-pass levels) the library must report for `bank` (skred_bank_plan.c: sk_tape_plan_host): the distinct modulators outside
     their reader's 64-voice group; a source group's level is 0 when it reads no other group, else 1 + the highest it reads."""
     v = np.arange(bank.n)
     fm = np.asarray(bank["voice_freq_mod_osc"]).copy()
