@@ -459,6 +459,66 @@ int  skred_bank_find_idle(skred_bank_t *bank, const skred_idle_query_t *q, int32
  * Returns `written` (>= 0) or a SKRED_E_* code; *total_out may be NULL. */
 int  skred_bank_find_idle_host(skred_bank_t *bank, const skred_idle_query_t *q, int32_t *voices, int *total_out, void *stream);
 
+/* ---- device-side note-ons: notes placed on a voice list the device holds, without a host wait ---------------------------
+ *
+ * skred_bank_find_idle leaves its list in device memory; skred_bank_update takes voice indices from the host.  These calls
+ * close the gap: the notes are small records written on the host, the voices that receive them are picked ON THE DEVICE from
+ * a list in device memory, at that point of the stream.  A host that paces blocks ahead of the device never waits for the list.
+ *
+ * A note-on is the reference's `l` command (synth.c:1153-1156): a pitch, optionally a pan, osc_trigger (synth.c:316-339) and
+ * amp_envelope_trigger(voice, velocity) (synth.c:383-388).  None of these stores changes what the library's host side knows
+ * about a voice -- kernel selection, packed lanes, the named set and the cross-group tape depend on voice_amp == 0, the flags,
+ * the routing, the table geometry and on whether phase and increment are finite, never on the value of a finite increment,
+ * the velocity, a finite phase or the pans -- which is why it can be applied to a voice whose index only
+ * the device knows, provided non-finite values are refused here, on the host. */
+enum { SKRED_NOTE_SET_PHASE = 1u << 0,   /* osc_trigger: voice_phase = note.phase, voice_finished = 0 */
+       SKRED_NOTE_SET_PAN   = 1u << 1 }; /* pan_set: voice_pan_left / _right = note.pan_left / _right */
+typedef struct skred_note {              /* 32 bytes */
+  float phase_inc, velocity, phase, pan_left, pan_right;
+  uint32_t flags, reserved[2];           /* reserved must be 0 */
+} skred_note_t;
+
+/* Pure host, no device: SKRED_OK, or SKRED_E_BAD_ARG for NULL notes, n < 0, unknown flag bits, non-zero reserved words, a
+ * non-finite phase_inc or velocity, a non-finite phase under SET_PHASE, non-finite pans under SET_PAN (fields a note does not
+ * set are not looked at).  The entry points below call it before anything touches the device. */
+int  skred_notes_check(const skred_note_t *notes, int n);
+
+/* Note k (0 <= k < n) goes to voice d_voices[first_entry + k] if first_entry + k < d_count[0] and that entry lies in
+ * [0, n_voices); otherwise the note is dropped.  d_voices and d_count are device memory, read on the device at that point of
+ * the stream (d_count[0] is what skred_bank_find_idle writes there; d_count and the d_count[0] entries behind d_voices must be
+ * readable).  On the chosen voice the kernel stores, and nothing else: voice_phase_inc = phase_inc;
+ * voice_amp_envelope.velocity = velocity; with SET_PHASE the phase and voice_finished = 0; with SET_PAN the two pan words; the
+ * trigger stamp (sample_start = synth_sample_count as the bank has it at application time, sample_release = 0, is_active = 1);
+ * the voice's bit on the motion list.  Filter memory, hold, smoother, sample and every other parameter keep their values.
+ * d_assigned[k] (device, int32[n], may be NULL) = the voice, or -1 for a dropped note, for every k < n; d_result (device,
+ * uint32[2], required): [0] notes placed, [1] n minus placed.  The results are a pure function of the inputs: two identical
+ * calls on identical state write identical bytes.  The list must name distinct voices (find_idle's does); with duplicates,
+ * which of the competing notes a voice ends with is unspecified, and nothing else is affected.  `first_entry` is the cursor
+ * that lets several calls share one query: the second call of a block passes the number of notes sent since the query.
+ * Asynchronous on `stream`, ordered like skred_bank_update (the notes are staged before the call returns: the caller's array
+ * is free again).  n == 0: SKRED_OK, nothing is done, d_result is not written.
+ * Refused with SKRED_E_BAD_ARG before anything touches the device: NULL bank, notes, list, count or result; n < 0;
+ * first_entry < 0; whatever skred_notes_check refuses.
+ * Limits.  The host view does not learn which voice got which note: read d_assigned back a block later and mirror pitch,
+ * velocity (phase, pans) into it before a later SKRED_DIRTY_PARAMS update of those voices -- otherwise that update restores
+ * the host's stale values.  A voice whose increment or phase was non-finite when the host last wrote it keeps its class on the
+ * host: results stay correct, the bank stays on the generic kernel until the host rewrites that voice.  Not in the fixed-point
+ * bank or the drop-in mode.  On a shard: through skred_shard_bank(), with that rank's local indices. */
+int  skred_bank_notes_on_list(skred_bank_t *bank, const skred_note_t *notes, int n,
+                              const int32_t *d_voices, const uint32_t *d_count, int first_entry,
+                              int32_t *d_assigned, uint32_t *d_result, void *stream);
+/* One call: the query `q` into scratch the bank owns (q->max_out is ignored: the library uses n), then the placement with
+ * first_entry = 0.  Refusals of both, and SKRED_E_BAD_ARG for SKRED_IDLE_AMP_ZERO in q->which: a note-on leaves voice_amp
+ * alone, so such a voice would stay silent and be listed again.  One stream at a time per bank, as for the query. */
+int  skred_bank_note_on_idle(skred_bank_t *bank, const skred_idle_query_t *q, const skred_note_t *notes, int n,
+                             int32_t *d_assigned, uint32_t *d_result, void *stream);
+/* SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE (as skred_bank_update applies them) on the first min(n, *d_count_or_null)
+ * entries of a list in device memory (NULL: n entries).  Entries that are negative or >= n_voices are skipped, so a d_assigned
+ * array with its -1 holes can be handed back as the note-off list.  Asynchronous on `stream`.  SKRED_E_BAD_ARG: NULL bank or
+ * list, n < 0, no stamp bit or bits other than the two SKRED_STAMP_*; n == 0: SKRED_OK, nothing is done. */
+int  skred_bank_stamp_list(skred_bank_t *bank, const int32_t *d_voices, int n, const uint32_t *d_count_or_null,
+                           uint32_t stamps, void *stream);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

@@ -25,7 +25,7 @@ void sk_idle_free(skred_bank_t *b) {
 }
 
 /* everything that can be said without the device */
-static int idle_check(const skred_bank_t *b, const skred_idle_query_t *q, const void *voices, const void *count, const char *who) {
+int sk_idle_check(const skred_bank_t *b, const skred_idle_query_t *q, const void *voices, const void *count, const char *who) {
   if (!b || !q) return fail(SKRED_E_BAD_ARG, "%s: no bank or no query", who);
   if (!count) return fail(SKRED_E_BAD_ARG, "%s: nowhere to put the counts", who);
   if (q->max_out < 0) return fail(SKRED_E_BAD_ARG, "%s: max_out %d", who, q->max_out);
@@ -85,14 +85,14 @@ static int idle_launch(skred_bank_t *b, const skred_idle_query_t *q, int32_t *d_
 }
 
 int skred_bank_find_idle(skred_bank_t *b, const skred_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, void *stream) {
-  const int rc = idle_check(b, q, d_voices, d_count, "find_idle");
+  const int rc = sk_idle_check(b, q, d_voices, d_count, "find_idle");
   if (rc) return rc;
   return idle_launch(b, q, d_voices, d_count, (hipStream_t)stream);
 }
 
 int skred_bank_find_idle_host(skred_bank_t *b, const skred_idle_query_t *q, int32_t *voices, int *total_out, void *stream) {
-  int dummy;
-  int rc = idle_check(b, q, voices, &dummy, "find_idle_host");
+  int dummy = 0;
+  int rc = sk_idle_check(b, q, voices, &dummy, "find_idle_host");
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));

@@ -2,7 +2,8 @@
  * skred_bank_priv.h -- internals shared by the translation units behind include/skred_amd.h
  * (skred_bank.c: lifecycle, tables, upload / download, options, class and tape plan; skred_bank_render.c:
  * one block from request to kernels, as skred_bank_plan.c picks them; skred_bank_update.c: block-granular
- * updates and the deferred queue).  Not installed.
+ * updates and the deferred queue; skred_bank_idle.c: the free-voice query; skred_bank_notes.c: note-ons and stamps on voices a
+ * device-resident list names).  Not installed.
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -85,7 +86,7 @@ struct skred_bank {
   float *d_taps_out;
   int last_taps;              /* taps the latest block wrote */
   uint32_t *d_form_counts;    /* skred_bank_set_form_counter: the caller's [2] counters, or NULL */
-  int split_mode;             /* SKRED_OPT_SPLIT: 0 never, 1 where it is the faster form (default), 2 whenever the bank qualifies */
+  int split_mode;             /* SKRED_OPT_SPLIT: 0 never (default), 1 where it is the faster form, 2 whenever the bank qualifies */
   int split_pairs;            /* SKRED_OPT_SPLIT_PAIRS: 0 the library's choice, 2 / 4 forced (tests) */
   int last_split;             /* the latest block ran sk_render_split_kernel */
   /* packed lanes of sparse banks (skred_device_layout.h: pack_mask; skred_bank.c: sk_pack_refresh, skred_bank_plan.c: sk_plan_finish) */
@@ -171,6 +172,9 @@ struct skred_bank {
   int32_t *d_idle_out;              /* skred_bank_find_idle_host: [2] counts, then the list, and its pinned twin */
   int32_t *h_idle_out;
   size_t idle_out_cap;              /* entries of the list */
+  /* skred_bank_note_on_idle (skred_bank_notes.c): the list its query leaves for its placement, allocated on first use */
+  uint32_t *d_note_list;            /* [4] words (the query's d_count in the first two), then note_list_cap voice indices */
+  size_t note_list_cap;
 };
 
 /* per-voice classification (host shadow) */
@@ -226,6 +230,14 @@ int sk_bank_master_pp(skred_bank_t *b, const float *d_sum, int num_frames, int n
 void sk_queue_free(skred_bank_t *b);
 void sk_patterns_free(skred_bank_t *b);
 void sk_idle_free(skred_bank_t *b);          /* skred_bank_idle.c: the query's scratch (skred_bank_destroy) */
+void sk_notes_free(skred_bank_t *b);         /* skred_bank_notes.c: the list scratch of skred_bank_note_on_idle (skred_bank_destroy) */
+/* skred_bank_idle.c: everything skred_bank_find_idle refuses, without the device (`voices` / `count`: where the list and the
+ * counts would go; `who` names the caller in the error text) */
+int sk_idle_check(const skred_bank_t *b, const skred_idle_query_t *q, const void *voices, const void *count, const char *who);
+/* skred_bank_update.c, the staging ring of host-written batches: a free slot of at least `bytes` (waits for the batch that last
+ * used it); where the kernel reads the staged bytes from (the pinned buffer itself, or its device twin behind a copy on `s`) */
+int sk_staging_slot(skred_bank_t *b, size_t bytes, hipStream_t s, sk_upd_slot_t **out);
+const void *sk_stage(sk_upd_slot_t *sl, size_t bytes, hipStream_t s);
 /* a control action reached the bank: what earlier launches reported about envelope activity no longer holds (the voices it
  * touched went on the motion list on the device: skred_update_kernels.hip) */
 static inline void sk_control_changed(skred_bank_t *b) { b->control_epoch++; b->env_quiet = 0; b->list_empty = 0; }

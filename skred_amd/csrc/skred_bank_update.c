@@ -285,7 +285,7 @@ static int build_batch(const skred_bank_t *b, const skred_voice_bank_t *h, const
  * host only ever waits for a batch issued SK_UPD_RING batches ago (a host that queues blocks far ahead of the device is
  * held back here, as an event would hold it); a single slot would stall every update behind the render that precedes it in
  * the stream. */
-static int staging_slot(skred_bank_t *b, size_t bytes, hipStream_t s, sk_upd_slot_t **out) {
+int sk_staging_slot(skred_bank_t *b, size_t bytes, hipStream_t s, sk_upd_slot_t **out) {
   const int idx = (int)(b->upd_head++ % SK_UPD_RING);
   sk_upd_slot_t *sl = &b->upd[idx];
   if (!b->h_upd_done) {
@@ -331,7 +331,7 @@ static int staging_slot(skred_bank_t *b, size_t bytes, hipStream_t s, sk_upd_slo
  * cost the stream ~12 us each (the copy and the gap behind it), four times per block under note traffic.  A large batch goes
  * through the copy engine into the slot's device twin: bandwidth matters there, not latency. */
 #define SK_UPD_ZERO_COPY_MAX (256 * 1024)
-static const void *sk_stage(sk_upd_slot_t *sl, size_t bytes, hipStream_t s) {
+const void *sk_stage(sk_upd_slot_t *sl, size_t bytes, hipStream_t s) {
   if (bytes <= SK_UPD_ZERO_COPY_MAX) return sl->h;
   const hipError_t e = hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) { (void)fail(SKRED_E_NO_DEVICE, "update copy -> %s", hipGetErrorString(e)); return NULL; }
@@ -346,7 +346,7 @@ static int apply_batch(skred_bank_t *b, const sk_update_t *rec, const sk_voice_m
   sk_upd_slot_t *sl;
   if (SK_STAMP_ONLY(dirty)) {
     /* note-ons / note-offs: voice ids only (stamping the same voice twice with the same clock is idempotent) */
-    int rc = staging_slot(b, (size_t)n * sizeof(int32_t), s, &sl);
+    int rc = sk_staging_slot(b, (size_t)n * sizeof(int32_t), s, &sl);
     if (rc) return rc;
     int32_t *ids = (int32_t *)sl->h;
     for (int i = 0; i < n; i++) ids[i] = rec[i].voice;
@@ -362,7 +362,7 @@ static int apply_batch(skred_bank_t *b, const sk_update_t *rec, const sk_voice_m
     sk_control_changed(b);
     return SKRED_OK;
   }
-  int rc = staging_slot(b, (size_t)n * sizeof(sk_update_t), s, &sl);
+  int rc = sk_staging_slot(b, (size_t)n * sizeof(sk_update_t), s, &sl);
   if (rc) return rc;
   memcpy(sl->h, rec, (size_t)n * sizeof(sk_update_t));
   const sk_update_t *src = (const sk_update_t *)sk_stage(sl, (size_t)n * sizeof(sk_update_t), s);

@@ -12,10 +12,11 @@
  *   skred_update_kernels.hip  sk_launch_update, sk_launch_stamp, sk_launch_pack_zero
  *   skred_rec_kernels.hip     sk_launch_rec_minmax, sk_rec_partial_floats, sk_launch_rec_convert
  *   skred_idle_kernels.hip    sk_launch_idle, sk_idle_workgroups, sk_launch_named
+ *   skred_note_kernels.hip    sk_launch_notes, sk_launch_stamp_list
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
- * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c
- * and skred_recorder.c.
+ * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
+ * skred_bank_notes.c and skred_recorder.c.
  */
 #ifndef SKRED_LAUNCH_H
 #define SKRED_LAUNCH_H
@@ -114,6 +115,28 @@ int sk_idle_workgroups(int first, int count);           /* workgroups (entries o
 int sk_launch_idle(const sk_idle_args_t *args, hipStream_t stream);   /* count, then (max_out > 0) scatter */
 /* the named set: bit v of named[] = some voice of the bank names voice v as a modulator (cleared, then rebuilt from SKP_MODI) */
 int sk_launch_named(const sk_plane_t *tab, const sk_plane_t *modi, int n_padded, int n_voices, uint64_t *named, hipStream_t stream);
+
+/* ---- note-ons and stamps on voices named by a list in device memory (skred_bank_notes.c -> skred_note_kernels.hip;
+ * include/skred_amd.h: skred_bank_notes_on_list / _stamp_list) ----
+ * A note record is skred_note_t word for word (layout and flag bits checked at compile time in skred_bank_notes.c). */
+enum { SK_NOTE_PHASE_INC = 0, SK_NOTE_VELOCITY, SK_NOTE_PHASE, SK_NOTE_PAN_LEFT, SK_NOTE_PAN_RIGHT, SK_NOTE_FLAGS, SK_NOTE_WORDS = 8 };
+#define SK_NOTE_SET_PHASE (1u << 0)
+#define SK_NOTE_SET_PAN   (1u << 1)
+#define SK_NOTE_SPAN 256           /* notes (and threads) per workgroup of sk_notes_kernel */
+typedef struct {
+  uint32_t w[SK_NOTE_WORDS];
+} sk_note_t;
+/* note k -> voice d_voices[first_entry + k] while first_entry + k < d_count[0] and the entry names a voice of the bank;
+ * d_assigned[n] (or NULL) and d_result[2] = placed, dropped; `now`, `mask` and cnt / done / seq as for sk_launch_update
+ * (d_notes may be the pinned staging buffer).  More than SK_NOTE_SPAN notes: d_result is zeroed on `stream` ahead of the launch */
+int sk_launch_notes(const sk_note_t *d_notes, int n, const int32_t *d_voices, const uint32_t *d_count, int first_entry, int n_voices,
+                    sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask,
+                    int32_t *d_assigned, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* sk_launch_stamp for the first min(n, d_count[0]) entries (d_count NULL: n) of a list in device memory; entries outside
+ * [0, n_voices) are skipped */
+int sk_launch_stamp_list(const int32_t *d_voices, int n, const uint32_t *d_count, int n_voices, uint32_t dirty,
+                         sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask,
+                         hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

@@ -36,7 +36,10 @@ ABI_SYMBOLS = [
     "skred_seq_counter", "skred_seq_tick",
     "skred_bank_seq", "skred_bank_set_sample_rate", "skred_bank_pattern_step_set", "skred_bank_pattern_step_clear",
     "skred_bank_find_idle", "skred_bank_find_idle_host",
+    "skred_bank_notes_on_list", "skred_bank_note_on_idle", "skred_bank_stamp_list",
 ]
+# ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
+HOST_ABI_SYMBOLS = ["skred_notes_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -50,6 +53,24 @@ class IdleQueryC(C.Structure):
     """ctypes image of ``skred_idle_query_t``."""
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("which", C.c_uint32), ("settle_level", C.c_float),
                 ("start", C.c_int32), ("max_out", C.c_int32)]          # `start`: the header's `from`
+
+# SKRED_NOTE_* (skred_bank_notes_on_list)
+NOTE_SET_PHASE, NOTE_SET_PAN = 1, 2
+
+
+class NoteC(C.Structure):
+    """ctypes image of ``skred_note_t`` (32 bytes)."""
+    _fields_ = [("phase_inc", C.c_float), ("velocity", C.c_float), ("phase", C.c_float), ("pan_left", C.c_float),
+                ("pan_right", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def note_array(notes):
+    """A contiguous ``NoteC`` array from a sequence of NoteC (a ctypes array of NoteC passes through)."""
+    if isinstance(notes, C.Array) and notes._type_ is NoteC:
+        return notes
+    notes = list(notes)
+    return (NoteC * len(notes))(*notes)
+
 
 _lib: Optional[C.CDLL] = None
 
@@ -133,6 +154,10 @@ def load() -> C.CDLL:
     L.skred_bank_pattern_step_clear.argtypes = [vp, i32, i32]
     L.skred_bank_find_idle.argtypes = [vp, C.POINTER(IdleQueryC), vp, vp, vp]
     L.skred_bank_find_idle_host.argtypes = [vp, C.POINTER(IdleQueryC), vp, C.POINTER(i32), vp]
+    L.skred_notes_check.argtypes = [vp, i32]
+    L.skred_bank_notes_on_list.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_note_on_idle.argtypes = [vp, C.POINTER(IdleQueryC), vp, i32, vp, vp, vp]
+    L.skred_bank_stamp_list.argtypes = [vp, vp, i32, vp, C.c_uint32, vp]
     _lib = L
     return L
 
@@ -141,6 +166,12 @@ def _check(rc: int, what: str):
     if rc != 0:
         msg = load().skred_amd_last_error().decode(errors="replace")
         raise SkredAmdError(f"{what} failed (rc={rc}): {msg}")
+
+
+def notes_check(notes) -> int:
+    """skred_notes_check: 0, or SKRED_E_BAD_ARG (-2) for a note the bank entry points would refuse.  Pure host, no device."""
+    arr = note_array(notes)
+    return int(load().skred_notes_check(C.cast(arr, C.c_void_p), len(arr)))
 
 
 class DeviceBank:
@@ -283,6 +314,32 @@ class DeviceBank:
             _check(n, "skred_bank_find_idle_host")
         return out[:n].copy(), int(total.value)
 
+    # ---- device-side note-ons (include/skred_amd.h: skred_bank_notes_on_list / _note_on_idle / _stamp_list) ----
+    def notes_on_list(self, notes, d_voices: int, d_count: int, first_entry: int = 0, d_assigned: int = 0, d_result: int = 0,
+                      stream: int = 0):
+        """Asynchronous on `stream`: note k goes to voice d_voices[first_entry + k] while that entry is below d_count[0] (device
+        memory, as find_idle leaves them) and names a voice of the bank, else it is dropped.  d_assigned[k] (int32, may be 0) = the
+        voice or -1; d_result[0] = placed, d_result[1] = dropped (uint32)."""
+        arr = note_array(notes)
+        _check(self.L.skred_bank_notes_on_list(self.h, C.cast(arr, C.c_void_p), len(arr), d_voices or None, d_count or None,
+                                               int(first_entry), d_assigned or None, d_result or None, stream or None),
+               "skred_bank_notes_on_list")
+
+    def note_on_idle(self, notes, first: int, count: int, which: int, settle_level: float = 0.0, start: Optional[int] = None,
+                     d_assigned: int = 0, d_result: int = 0, stream: int = 0):
+        """The query of find_idle (room for len(notes) voices, in scratch the bank owns) and the placement of the notes on its list,
+        in one call; IDLE_AMP_ZERO is refused."""
+        arr = note_array(notes)
+        q = IdleQueryC(int(first), int(count), int(which), float(settle_level), int(first if start is None else start), 0)
+        _check(self.L.skred_bank_note_on_idle(self.h, C.byref(q), C.cast(arr, C.c_void_p), len(arr), d_assigned or None,
+                                              d_result or None, stream or None), "skred_bank_note_on_idle")
+
+    def stamp_list(self, d_voices: int, n: int, stamps: int, d_count: int = 0, stream: int = 0):
+        """STAMP_TRIGGER / STAMP_RELEASE on the first min(n, d_count[0]) entries of a list in device memory (d_count 0: n entries);
+        entries outside the bank -- the -1 of a dropped note -- are skipped."""
+        _check(self.L.skred_bank_stamp_list(self.h, d_voices or None, int(n), d_count or None, int(stamps), stream or None),
+               "skred_bank_stamp_list")
+
     def force_generic(self, on: bool = True):
         _check(self.L.skred_bank_set_option(self.h, 1, int(on)), "skred_bank_set_option")
 
@@ -300,7 +357,7 @@ class DeviceBank:
         _check(self.L.skred_bank_set_option(self.h, 6, int(mode)), "skred_bank_set_option")
 
     def set_split(self, mode: int) -> None:
-        """SKRED_OPT_SPLIT: 1 the oscillator-wave / post-wave form of the one-voice kernel where it is faster (default), 0 never,
+        """SKRED_OPT_SPLIT: 0 never (default), 1 the oscillator-wave / post-wave form of the one-voice kernel where it is faster,
         2 whenever the bank qualifies."""
         _check(self.L.skred_bank_set_option(self.h, 7, int(mode)), "skred_bank_set_option")
 
