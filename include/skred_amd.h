@@ -354,13 +354,29 @@ enum { SKRED_OPT_FORCE_GENERIC = 1, SKRED_OPT_FAST2_MIN_VOICES = 2 /* bank size 
                              (each refused with SKRED_E_UNSUPPORTED / SKRED_E_RANGE, the bank stays usable): modulators outside the
                              bank; a cycle between groups; chains that need more than 16 pre-pass launches; a tape of more than
                              256 MiB (sources x (frames + 1) x 4 bytes).  Such banks run on the modulated kernel; the specialised
-                             kernels, shards and the drop-in mode do not read the tape (skred_bank_last_cross_group) */ };
+                             kernels, shards and the drop-in mode do not read the tape (skred_bank_last_cross_group) */,
+       SKRED_OPT_CZ_FAST = 12 /* CZ phase distortion (`c<mode>,<dist>`, cz_phasor, synth.c:149-215) on the one-voice-per-lane kernel.  0
+                             (default): a bank with a CZ voice runs the modulated kernel, as it always did.  1: a bank whose CZ voices
+                             ALL QUALIFY, and which holds no other voice that needs the full-featured kernels, runs the CZ
+                             instantiations of the one-voice kernel (skred_bank_last_cz; skred_bank_last_kernel says
+                             SKRED_KERNEL_FAST).  A voice with cz mode 1..7 qualifies when (a) its CZ source (`C`) is absent or is a
+                             higher-indexed voice of the same aligned 64-voice group -- the carrier then reads the source's
+                             voice_sample of the previous frame, synth.c:262-267 in index order --, and (b) its frequency / amplitude
+                             / pan modulators, if any, are higher-indexed voices of that group too, or -- amplitude, pan -- the voice
+                             itself.  A CZ source below the carrier (16.sk's `v2 ... C1`), the carrier as its own CZ source, a
+                             source in another group, a mode outside 1..7 and non-finite phase data keep the modulated kernel; so do
+                             banks whose table pool is not staged in LDS, and SKRED_OPT_FORCE_GENERIC.  May be set at any time
+                             between renders; the next block follows it, in both directions, nothing is uploaded again.  A
+                             wavefront that holds a CZ lane keeps the per-frame exchange (it does not take the skewed blocks of
+                             SKRED_OPT_FM_SKEW; other wavefronts of the bank do).  Same per-voice bits either way; the mix differs
+                             by summation order only.  Shards, the fixed-point form and the drop-in mode never set it */ };
 enum { SKRED_KERNEL_GENERIC = 0, SKRED_KERNEL_FAST = 1, SKRED_KERNEL_MODULATED = 2, SKRED_KERNEL_FAST2 = 3 };
 int  skred_bank_set_option(skred_bank_t *bank, int option, int value);
 int  skred_bank_last_kernel(const skred_bank_t *bank);   /* SKRED_KERNEL_* of the latest render */
 int  skred_bank_last_in_place(const skred_bank_t *bank);  /* 1: the latest block rendered its motion list in place (SKRED_OPT_IN_PLACE) */
 int  skred_bank_last_pack(const skred_bank_t *bank);      /* lanes per 64-voice group in the latest block (SKRED_OPT_PACK), 0: not packed */
 int  skred_bank_last_split(const skred_bank_t *bank);     /* 1: the latest block ran the split form of the one-voice kernel (SKRED_OPT_SPLIT) */
+int  skred_bank_last_cz(const skred_bank_t *bank);        /* 1: the latest block ran a CZ instantiation of the one-voice kernel (SKRED_OPT_CZ_FAST) */
 /* SKRED_OPT_CROSS_GROUP: for the latest block, the number of tape sources and of pre-pass launches (0, 0: it read no tape) */
 int  skred_bank_last_cross_group(const skred_bank_t *bank, int *n_sources, int *n_levels);
 

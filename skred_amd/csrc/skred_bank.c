@@ -359,12 +359,19 @@ int sk_classify(skred_bank_t *b) {
   }
   if (!b->class_dirty) return SKRED_OK;
   b->fast_mode = sk_plan_class_mode(b->cnt_real, b->cnt_filter, b->cnt_env, b->cnt_exotic, b->cnt_stops, b->cnt_fm, b->cnt_fm_odd, b->cnt_pair_ap);
+  /* the same class with the CZ voices of the fast family taken for what the one-voice kernel renders (SKRED_OPT_CZ_FAST; the planner
+   * picks between the two words): only when they are the bank's only exotic voices.  A voice among them that reads a previous-frame
+   * source makes the launch exchange voice_sample (SKM_FM); no (carrier, next voice) pairs: that is the two-per-lane kernel's shape */
+  b->fast_mode_cz = 0;
+  if (b->cnt_cz > 0 && b->cnt_exotic == b->cnt_cz)
+    b->fast_mode_cz = (sk_plan_class_mode(b->cnt_real, b->cnt_filter, b->cnt_env, 0, b->cnt_stops, b->cnt_fm + b->cnt_cz_src, b->cnt_fm_odd + b->cnt_cz_src, b->cnt_pair_ap) &
+                       ~(uint32_t)(SKM_FM_PAIR | SKM_PAIR_AP)) | SKM_CZ;
   b->class_dirty = 0;
   /* dependency levels for modulated banks (skred_render_generic.hip: sk_render_mod_kernel) */
   if (!b->mod_dirty) return SKRED_OK;
   b->mod_dirty = 0;
   b->max_level = 0;
-  if (b->features & (SKB_ANY_MOD | SKB_ANY_FM)) {
+  if (b->features & (SKB_ANY_MOD | SKB_ANY_FM | SKB_ANY_CZ)) {
     b->max_level = sk_plan_levels(b->h_mod, b->n_padded, b->h_level);
     const hipError_t e = hipMemcpy(b->d_level, b->h_level, (size_t)b->n_padded * sizeof(int), hipMemcpyHostToDevice);
     if (e != hipSuccess) { b->mod_dirty = 1; return fail(SKRED_E_NO_DEVICE, "dependency levels -> %s", hipGetErrorString(e)); }
@@ -385,6 +392,7 @@ int skred_bank_set_option(skred_bank_t *b, int option, int value) {
     case SKRED_OPT_PACK: b->pack_mode = value < 0 ? 0 : value > 2 ? 2 : value; return SKRED_OK;
     case SKRED_OPT_FM_SKEW: b->fm_skew = value != 0; return SKRED_OK;
     case SKRED_OPT_CROSS_GROUP: b->cross_group = value != 0; return SKRED_OK;
+    case SKRED_OPT_CZ_FAST: b->cz_fast = value != 0; return SKRED_OK;    /* (read by the next block's plan: nothing is classified again) */
     default: return fail(SKRED_E_BAD_ARG, "unknown option %d", option);
   }
 }
@@ -433,6 +441,7 @@ int skred_bank_last_kernel(const skred_bank_t *b) { return b ? b->last_kernel : 
 int skred_bank_last_in_place(const skred_bank_t *b) { return b ? b->last_in_place : 0; }
 int skred_bank_last_split(const skred_bank_t *b) { return b ? b->last_split : 0; }
 int skred_bank_last_pack(const skred_bank_t *b) { return b ? b->last_pack : 0; }
+int skred_bank_last_cz(const skred_bank_t *b) { return b ? b->last_cz : 0; }
 int skred_bank_last_taps(const skred_bank_t *b) { return b ? b->last_taps : 0; }
 int skred_bank_last_cross_group(const skred_bank_t *b, int *n_sources, int *n_levels) {
   if (!b) return fail(SKRED_E_BAD_ARG, "last_cross_group: no bank");

@@ -49,16 +49,27 @@ void sk_plan_family(const sk_plan_in_t *in, sk_plan_t *plan) {
   *plan = (sk_plan_t){ 0 };
   /* the modulated kernel serves every kind of modulation; banks whose only modulation is previous-frame FM stay on
    * the one-per-lane kernel when they are otherwise clean */
-  const int fast_ok = (in->fast_mode & SKM_FAST) && !in->force_generic;
-  const int modulated = (in->features & SKB_ANY_MOD) != 0 || ((in->features & SKB_ANY_FM) && in->cnt_fm > 0 && !fast_ok);
+  /* SKRED_OPT_CZ_FAST: a bank whose only exotic voices are CZ voices of the fast family runs the one-voice kernel's CZ
+   * instantiations -- LDS-table banks only (the table windows of the others assume an index that moves forward), and not when the
+   * bank needs the modulated kernel for another reason.  The feature those voices ask for (SKB_ANY_CZ) is, like every feature
+   * bit, only ever set: with the option off it stands for SKB_ANY_MOD as it always did; with the option on it counts while such
+   * voices exist and this block cannot take them -- and SKB_ANY_MOD while a voice that needs the modulated kernel exists (the
+   * count of them), so that `cz_on` / `cz_off` and a source moved below its carrier and back change the family block by block. */
+  const int need_mod = (in->features & SKB_ANY_MOD) && !(in->cz_fast && in->cnt_mod == 0);
+  const int cz = in->cz_fast && in->cnt_cz > 0 && (in->fast_mode_cz & SKM_FAST) && !in->force_generic && in->lds_table_floats > 0 && !need_mod;
+  const int cz_mod = (in->features & SKB_ANY_CZ) && !(in->cz_fast && (cz || in->cnt_cz == 0));
+  const uint32_t class_mode = cz ? in->fast_mode_cz : in->fast_mode;
+  const int fast_ok = (class_mode & SKM_FAST) && !in->force_generic;
+  const int modulated = need_mod || cz_mod || ((in->features & SKB_ANY_FM) && in->cnt_fm > 0 && !fast_ok);
+  plan->cz = cz;
   plan->modulated = modulated;
   plan->n_wg = in->n_groups < SK_MAX_WORKGROUPS ? in->n_groups : SK_MAX_WORKGROUPS;   /* workgroups stride over 256-voice passes */
   plan->interp = in->interp;
-  plan->fast_mode = in->force_generic ? 0u : in->fast_mode;
+  plan->fast_mode = in->force_generic ? 0u : class_mode;
   /* two voices per lane pay off for large LDS-table banks (packed fp32); banks whose tables stay in L2 / HBM do
    * better with one voice per lane at every size measured (2^16 .. 2^20: twice the waves to hide the window
    * refills behind) unless the caller set the threshold explicitly */
-  if ((plan->fast_mode & SKM_FAST) && !(plan->fast_mode & (SKM_STOPS | SKM_FM)) && in->n_voices >= in->fast2_min_voices &&
+  if ((plan->fast_mode & SKM_FAST) && !(plan->fast_mode & (SKM_STOPS | SKM_FM | SKM_CZ)) && in->n_voices >= in->fast2_min_voices &&
       (in->lds_table_floats > 0 || in->fast2_min_user) && !in->stems)      /* (per-voice stems: the one-voice kernel writes them) */
     plan->fast_mode |= SKM_TWO_PER_LANE;        /* (voices that finish mid-launch are handled by the one-per-lane kernel only) */
   /* ... except where its 1024-voice passes fill the machine unevenly: one pass per CU up to n_cus passes, then SOME CUs with two
@@ -90,7 +101,7 @@ void sk_plan_family(const sk_plan_in_t *in, sk_plan_t *plan) {
   /* linear lookup on a bank whose every real voice loops over its whole table with a guard sample behind it: the specialised
    * kernels' instantiations without the fold test (two-operator FM banks keep the general form) */
   if (in->interp == SKRED_INTERP_LINEAR && (plan->fast_mode & SKM_FAST) && !(plan->fast_mode & SKM_FM_PAIR) && !modulated && in->cnt_real > 0 &&
-      in->cnt_guard == in->cnt_real && in->guard_current)
+      in->cnt_guard == in->cnt_real && in->guard_current && !cz)      /* (a warped position lands anywhere: CZ lanes keep the fold test) */
     plan->interp = 2;
   /* Sparse banks (most voices skipped by the reference's own rule, synth.c:537 -- the shipped patches use 3 to 6 voices of 64):
    * the one-voice family with the lanes PACKED -- a wave takes the voices that can sound of 64 / S aligned 64-voice groups, S = the
@@ -186,7 +197,7 @@ void sk_plan_finish(const sk_plan_in_t *in, int pack_most, sk_plan_t *plan) {
    * 131 072 -- so the library never picks it by itself; values 1 / 2 / 3 keep it reachable (the rule of value 1: banks of 32 768 ..
    * 65 536 filtered voices on a 256-CU device).  (Decided here, ahead of the row layout: the two-pair form has twice the rows.) */
   int split = 0;
-  if (!modulated && (plan->fast_mode & SKM_FAST) && !(plan->fast_mode & (SKM_TWO_PER_LANE | SKM_STOPS | SKM_FM | SKM_MIXED)) && in->lds_table_floats > 0 &&
+  if (!modulated && (plan->fast_mode & SKM_FAST) && !(plan->fast_mode & (SKM_TWO_PER_LANE | SKM_STOPS | SKM_FM | SKM_MIXED | SKM_CZ)) && in->lds_table_floats > 0 &&
       !in->stems && !plan->pack_s && in->split_mode && (!plan->one_env || in->env_quiet || in->split_mode == 3) && in->split_lds4 <= SK_SPLIT_MAX_LDS) {
     if (in->split_mode >= 2 || ((plan->fast_mode & SKM_FILTER_ALL) && in->n_groups * 2 >= in->n_cus && in->n_groups <= in->n_cus)) split = 4;
     if (split && in->split_pairs && (in->split_pairs == 4 || in->n_groups * 2 <= SK_MAX_WORKGROUPS)) split = in->split_pairs;   /* (tests) */

@@ -35,6 +35,12 @@ typedef struct {
   int bound_valid;
   uint64_t bound;                                          /* bound_len + touched_total - bound_touched */
   size_t split_lds4;                                       /* sk_split_lds_bytes(args, 4) */
+  /* SKRED_OPT_CZ_FAST (appended: tests/c_plan_cases.c fills the fields above by name and zeroes the rest) */
+  int cnt_cz;                                              /* real voices whose CZ the one-voice kernel can render (SKC_CZ) */
+  int cnt_mod;                                             /* voices whose modulation only the modulated kernel serves (SKC_MOD) */
+  int cz_fast;                                             /* the option */
+  uint32_t fast_mode_cz;                                   /* the class mode with those voices not counted as exotic, | SKM_CZ; 0 when the
+                                                              bank holds other exotic voices, or none of these */
 } sk_plan_in_t;
 
 typedef struct {
@@ -53,6 +59,7 @@ typedef struct {
   size_t stride, rows, own;   /* floats per gain row; rows in all; of them handed out per 64-voice word */
   int rc;                     /* != 0: the block is refused (a probe on a family without probe instantiations); msg says why */
   const char *msg;
+  int cz;                     /* the block runs a CZ instantiation of the one-voice kernel (fast_mode has SKM_CZ) */
 } sk_plan_t;
 
 /* Two pure steps: sk_plan_family decides everything up to and including plan->pack_candidate; sk_plan_finish the rest, given

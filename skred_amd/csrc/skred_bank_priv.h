@@ -112,6 +112,13 @@ struct skred_bank {
   uint32_t tables_epoch, guard_epoch;   /* pools set so far; the pool the whole bank was last packed against (guard flags are a property of the pool) */
   int cnt_pair_ap;            /* pair-shaped carriers whose amplitude or pan is modulated too (SKC_PAIR_AP) */
   int cnt_fm_odd;             /* SKC_FM voices that are not the even half of a (carrier, next voice) pair (SKC_FM_ODD) */
+  int cnt_cz;                 /* SKC_CZ voices: CZ phase distortion the one-voice kernel can render (they count in cnt_exotic too) */
+  int cnt_cz_src;             /* ... of them, voices that read a previous-frame source (SKC_CZ_SRC) */
+  uint32_t fast_mode_cz;      /* sk_classify(): the class mode with the SKC_CZ voices taken off the exotic count, | SKM_CZ; 0 when other
+                                 exotic voices remain or the bank has no such voice.  Kept whatever SKRED_OPT_CZ_FAST says */
+  int cnt_mod;                /* voices (real or not, like cnt_escapes) with SKC_MOD */
+  int cz_fast;                /* SKRED_OPT_CZ_FAST */
+  int last_cz;                /* the latest block ran a CZ instantiation of the one-voice kernel */
   int cnt_escapes;            /* voices naming a modulator outside their aligned 64-voice group (SKC_ESCAPES) */
   int cnt_outside;            /* ... of them, voices naming a modulator outside the bank (SKC_OUTSIDE): refused even with cross_group */
   /* cross-group modulation (SKRED_OPT_CROSS_GROUP; skred_device_layout.h: sk_tape_args_t; skred_bank.c: tape_plan) */
@@ -193,6 +200,12 @@ struct skred_bank {
                            finished is a matter of state, not of class) */
 #define SKC_ESCAPES 128u /* names a modulator outside its aligned 64-voice group: the bank cannot be rendered until that is fixed
                             (SKRED_OPT_CROSS_GROUP: unless the modulator is in the bank -- then it is read from the tape) */
+#define SKC_CZ 4096u    /* (with SKC_EXOTIC) a CZ voice of the fast family: cz_mode 1..7, finite phase data, its CZ source absent or a
+                           higher-indexed voice of its aligned 64-voice group (the previous-frame read), its FM / AM / pan modulators
+                           as SKC_FM asks (above it in the group; AM / pan also the voice itself) */
+#define SKC_CZ_SRC 8192u /* an SKC_CZ voice with any such source: the launch exchanges voice_sample (SKM_FM) */
+#define SKC_MOD 16384u  /* modulated in a way only the modulated kernel serves: what asks for SKB_ANY_MOD, as a bit that can be counted
+                           (the feature word is only ever set; with SKRED_OPT_CZ_FAST on the count decides: skred_bank_plan.c) */
 #define SKC_OUTSIDE 2048u /* with SKC_ESCAPES: the modulator is outside the bank (md < 0 or md >= n_voices): always refused */
 
 

@@ -105,6 +105,7 @@ static void plan_input(const skred_bank_t *b, int num_frames, int interp, int st
   in->mask_dirty = b->mask_dirty; in->bound_valid = b->bound_valid;
   in->bound = (uint64_t)b->bound_len + (b->touched_total - b->bound_touched);
   in->split_lds4 = sk_split_lds_bytes(&lds, 4);            /* (it reads the table size only) */
+  in->cnt_cz = b->cnt_cz; in->cnt_mod = b->cnt_mod; in->cz_fast = b->cz_fast; in->fast_mode_cz = b->fast_mode_cz;
 }
 
 /* the render args as far as the bank, the request and the plan fix them (the rows follow: inplace_rows, partial_rows) */
@@ -353,6 +354,7 @@ static int render_block(skred_bank_t *b, int num_frames, int interp, float *d_st
   b->last_in_place = p.inplace;
   b->last_split = p.split;
   b->last_pack = p.pack_s;
+  b->last_cz = p.cz;
   b->last_taps = b->n_taps;
   b->last_tape_sources = ta.tape ? b->tape_sources : 0;
   b->last_tape_levels = ta.tape ? b->tape_levels : 0;

@@ -78,7 +78,23 @@ int sk_pack_voice(const skred_bank_t *b, const skred_voice_bank_t *h, int v, int
       if (!above && !self_ok) fm_only = 0;
     }
   }
-  if (has_mod) { flags |= SKF_HAS_MOD; features |= fm_only ? SKB_ANY_FM : SKB_ANY_MOD; }
+  /* CZ the one-per-lane kernel can serve (SKRED_OPT_CZ_FAST): cz_phasor (synth.c:149-215) warps the voice's own lookup position;
+   * its amount is a constant, or follows a HIGHER-indexed voice of the group (last frame's voice_sample, synth.c:262-267 in index
+   * order) -- the read the rule above allows FM / AM / pan.  The voice's other modulators: by that rule. */
+  int cz_fast = 0, cz_src = 0;
+  if (h->voice_cz_mode[v] >= 1 && h->voice_cz_mode[v] <= 7) {
+    const int src[4] = { h->voice_freq_mod_osc[v] == v ? -1 : h->voice_freq_mod_osc[v], h->voice_amp_mod_osc[v], h->voice_pan_mod_osc[v],
+                         h->voice_cz_mod_osc[v] };
+    cz_fast = 1;
+    for (int k = 0; k < 4; k++) {
+      if (src[k] < 0) continue;
+      const int md = src[k] + (dst - v);
+      const int above = md >= 0 && md < b->n_voices && (md >> 6) == (dst >> 6) && md > dst;
+      const int self_ok = (k == 1 || k == 2) && md == dst;
+      if (!above && !self_ok) cz_fast = 0;
+      cz_src = 1;
+    }
+  }
   int quant = h->voice_quantize[v], hold = h->voice_sample_hold_max[v];
   if (quant < 0 || quant > 30) quant = quant < 0 ? 0 : 30;
   if (hold < 0) hold = 0;
@@ -101,6 +117,8 @@ int sk_pack_voice(const skred_bank_t *b, const skred_voice_bank_t *h, int v, int
     if ((has_mod && !fm_only) || (!finite && !noise))        /* (a noise voice never runs its oscillator: synth.c:543-546) */
       c |= SKC_EXOTIC;
     if (fm_only) c |= SKC_FM;
+    cz_fast = cz_fast && (finite || noise);
+    if (cz_fast) c |= SKC_CZ | (cz_src ? SKC_CZ_SRC : 0u);
     {
       /* the pair shape: an even voice whose frequency, amplitude and pan modulators are each the voice after it -- or, amplitude
        * and pan, the voice itself (`F1`, `A1`, `P1`, `A0`, `P0` on voice 0) */
@@ -111,6 +129,9 @@ int sk_pack_voice(const skred_bank_t *b, const skred_voice_bank_t *h, int v, int
     }
     meta->cls = c;
   }
+  /* (a CZ voice of the fast family asks for SKB_ANY_CZ, which stands for SKB_ANY_MOD wherever SKRED_OPT_CZ_FAST is off) */
+  if (has_mod) { flags |= SKF_HAS_MOD; features |= fm_only ? SKB_ANY_FM : cz_fast ? SKB_ANY_CZ : SKB_ANY_MOD; }
+  if (has_mod && !fm_only && !cz_fast) meta->cls |= SKC_MOD;
   meta->features = features;
   const skred_envelope_t *e = &h->voice_amp_envelope[v];
   const skred_mmf_t *f = &h->voice_filter[v];
@@ -169,12 +190,13 @@ void sk_apply_meta(skred_bank_t *b, int dst, const sk_voice_meta_t *m, int param
   if (!params_travel) return;
   const uint16_t old = b->h_class[dst], now = m->cls;
   if (old != now) {
-    if (old & SKC_REAL) { b->cnt_real--; if (old & SKC_FILTER) b->cnt_filter--; if (old & SKC_ENV) b->cnt_env--; if (old & SKC_EXOTIC) b->cnt_exotic--; if (old & SKC_STOPS) b->cnt_stops--; if (old & SKC_FM) b->cnt_fm--; if (old & SKC_FM_ODD) b->cnt_fm_odd--; if (old & SKC_PAIR_AP) b->cnt_pair_ap--; if (old & SKC_GUARD) b->cnt_guard--; }
-    if (now & SKC_REAL) { b->cnt_real++; if (now & SKC_FILTER) b->cnt_filter++; if (now & SKC_ENV) b->cnt_env++; if (now & SKC_EXOTIC) b->cnt_exotic++; if (now & SKC_STOPS) b->cnt_stops++; if (now & SKC_FM) b->cnt_fm++; if (now & SKC_FM_ODD) b->cnt_fm_odd++; if (now & SKC_PAIR_AP) b->cnt_pair_ap++; if (now & SKC_GUARD) b->cnt_guard++; }
+    if (old & SKC_REAL) { b->cnt_real--; if (old & SKC_FILTER) b->cnt_filter--; if (old & SKC_ENV) b->cnt_env--; if (old & SKC_EXOTIC) b->cnt_exotic--; if (old & SKC_STOPS) b->cnt_stops--; if (old & SKC_FM) b->cnt_fm--; if (old & SKC_FM_ODD) b->cnt_fm_odd--; if (old & SKC_PAIR_AP) b->cnt_pair_ap--; if (old & SKC_GUARD) b->cnt_guard--; if (old & SKC_CZ) b->cnt_cz--; if (old & SKC_CZ_SRC) b->cnt_cz_src--; }
+    if (now & SKC_REAL) { b->cnt_real++; if (now & SKC_FILTER) b->cnt_filter++; if (now & SKC_ENV) b->cnt_env++; if (now & SKC_EXOTIC) b->cnt_exotic++; if (now & SKC_STOPS) b->cnt_stops++; if (now & SKC_FM) b->cnt_fm++; if (now & SKC_FM_ODD) b->cnt_fm_odd++; if (now & SKC_PAIR_AP) b->cnt_pair_ap++; if (now & SKC_GUARD) b->cnt_guard++; if (now & SKC_CZ) b->cnt_cz++; if (now & SKC_CZ_SRC) b->cnt_cz_src++; }
     /* per-voice bits that are not kernel classes: counted whether or not the voice can sound, and recounted whenever the
      * voice is written again -- a routing that escaped its group stops blocking the bank once it is fixed */
     b->cnt_escapes += ((now & SKC_ESCAPES) != 0) - ((old & SKC_ESCAPES) != 0);
     b->cnt_outside += ((now & SKC_OUTSIDE) != 0) - ((old & SKC_OUTSIDE) != 0);
+    b->cnt_mod += ((now & SKC_MOD) != 0) - ((old & SKC_MOD) != 0);
     b->h_class[dst] = now;
     b->class_dirty = 1;
     if ((old ^ now) & SKC_LIVE) { b->h_pack_dirty[dst >> 6] = 1; b->pack_any_dirty = 1; }

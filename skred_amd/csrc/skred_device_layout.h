@@ -70,6 +70,8 @@ enum {
 #define SKB_ANY_MOD    (1u << 4)   /* modulation that needs sk_render_mod_kernel (same-frame dependencies, AM, pan, CZ) */
 #define SKB_ANY_FM     (1u << 5)   /* frequency modulation by a higher-indexed voice of the group only (previous-frame
                                       semantics): the one-per-lane kernel can do it; sk_render_mod_kernel otherwise */
+#define SKB_ANY_CZ     (1u << 6)   /* CZ phase distortion of the kind the one-per-lane kernel can do (skred_bank_priv.h: SKC_CZ); it stands for
+                                      SKB_ANY_MOD unless SKRED_OPT_CZ_FAST is on (skred_bank_plan.c: sk_plan_family) */
 
 /* fast_mode word (host -> launcher) */
 #define SKM_FAST        (1u << 0)  /* bank qualifies for sk_render_fast_kernel (see skred_bank_plan.c: sk_plan_class_mode) */
@@ -87,6 +89,9 @@ enum {
                                       every 64 voices get an oscillator wave and a post wave, so that small and mid-size banks give a SIMD
                                       twice the independent instruction streams */
 #define SKM_SPLIT2      (1u << 10) /* ... with SKM_SPLIT: two pairs per workgroup (256 threads, 128 voices per pass: args->n_rows counts those) */
+#define SKM_CZ          (1u << 11) /* SKRED_OPT_CZ_FAST: the bank's CZ voices are of the kind the one-voice kernel renders (skred_bank_priv.h: SKC_CZ):
+                                      its CZ instantiations (sk_render_fast_kernel<..., CZ>, LDS-table banks), with SKM_FM when any voice
+                                      reads a previous-frame source */
 #define SKM_STOPS       (1u << 4)  /* some voice is a forward one-shot that finishes at its table end (sk_render_fast_kernel<STOPS>) */
 
 #define SK_GROUP 256               /* voices per workgroup pass (4 wavefronts) */

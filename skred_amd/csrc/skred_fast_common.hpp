@@ -143,6 +143,61 @@ __device__ __forceinline__ float fast_advance(FastRegs &r, float inc) {
 #define XF_NOISE 32    /* the noise source */
 #define XF_STOP 64     /* a one-shot that can finish */
 #define XF_ALL 127
+#define XF_CZ 128      /* (CZ instantiations) a lane with CZ phase distortion: the frame loop, no skewed blocks */
+#define XF_CZ_SRC 256  /* ... whose amount follows a source: exchanged and worked out per frame */
+
+// CZ phase distortion (CZ instantiations of sk_render_fast_kernel only; cz_phasor, synth.c:149-215): the warp of the lookup position
+// between the phase wrap and the table fetch.  d / ka / kb: the clamped amount and the quotients / exponents the warp takes from it
+// (fast_cz_amount) -- per-lane constants of the launch unless the voice has a CZ source.  (A struct of its own: FastRegs is shared
+// with kernels that have no such lanes.)
+struct FastCz {
+  int mode;                     // 0: none (also: a skipped lane, a noise lane)
+  int addr;                     // source lane * 4 (ds_bpermute address), -1: none
+  float dist, depth, size;      // voice_cz_distortion, voice_cz_mod_depth, (float)table_size
+  float d, ka, kb;
+};
+
+// The amount-dependent half of cz_phasor (synth.c:149-215; cz_warp in skred_render_generic.hip): d = clamp(amount, 0, 0.999f) and
+// what each mode divides by / raises to, the reference's own expressions.  Without a CZ source the amount is a constant of the
+// launch and this runs once per lane; the per-frame half (fast_cz_warp) then performs the same operations on the same values as
+// the reference does when it evaluates all of them per sample.  (Mode 1 with d == 0: k_lo = 0.5f / 0 = inf, as in the reference,
+// whose `x < d` branch can then not be taken by a position >= 0.)
+__device__ __forceinline__ void fast_cz_amount(FastCz &r, float amount) {
+  float d = amount;
+  if (d < 0.0f) d = 0.0f; else if (d > 0.999f) d = 0.999f;
+  float ka = 0.0f, kb = 0.0f;
+  switch (r.mode) {
+    case 1: ka = 0.5f / d; kb = 0.5f / (1.0f - d); break;
+    case 2:
+    case 3: ka = 0.5f / (0.5f - d * 0.5f); kb = ka; break;
+    case 5: { const float h = d * 0.5f; ka = 0.5f / (0.5f - h); kb = 0.5f / (0.5f + h); break; }
+    case 6: ka = 1.0f + 4.0f * d; break;
+    case 7: ka = 1.0f + 8.0f * d; break;
+    default: break;
+  }
+  r.d = d; r.ka = ka; r.kb = kb;
+}
+
+// ... and the per-frame half: the table-domain position the lookup takes for phase `ph`.  x = ph / size is the IEEE quotient;
+// modes 1, 3 and 5 are one expression with the lane's threshold (d, or one half); mode 4 is the reference's fmodf (x == 1.0f -- a
+// one-shot parked at its end, or a rounded quotient -- gives 0); modes 6 / 7 are fast_pow on the bits (pow_bits).
+__device__ __forceinline__ float fast_cz_warp(const FastCz &r, float ph) {
+  const int mode = r.mode;
+  float x = ph / r.size;
+  if (mode == 1 || mode == 3 || mode == 5) {
+    const float t = mode == 1 ? r.d : 0.5f;
+    x = (x < t) ? x * r.ka : 0.5f + (x - t) * r.kb;
+  } else if (mode == 2) {
+    x = (x < 0.5f) ? x * r.ka : 1.0f - (1.0f - x) * r.ka;
+  } else if (mode == 4) {
+    x = fmodf(x * 2.0f, 1.0f);
+  } else if (mode == 6 || mode == 7) {
+    x = pow_bits(x, r.ka);
+  } else {
+    return ph;
+  }
+  return x * r.size;
+}
 
 // The rest of the frame: biquad, envelope / gain, smoother, pan.
 // STALL (steady waves only): the smoother no longer moves in any lane (fast_smoother_stalled) and is skipped.
@@ -456,12 +511,13 @@ __device__ __forceinline__ bool fast_smoother_stalled(const FastRegs &r) {
 // fmodf returns it unchanged: hi - (lo - ph0).  (That difference can round to hi itself: the fetch keeps its index clamp.)
 // LOZ (with TAME and NOSTOP): no lane of the wave has a loop window -- fast_advance<LOZ>'s two-instruction wrap.
 template <bool TAB_LDS, bool FILTER, bool ENV, bool STEADY, bool TAME, int INTERP, bool STOPS = false, bool EXTMS = false, bool NOSTOP = false,
-          bool BIDIR = false, bool LOZ = false>
+          bool BIDIR = false, bool LOZ = false, bool CZ = false>
 __device__ __forceinline__ void fast_frame(FastRegs &r, float &xn, float &xo, float &yn, float &yo,
                                            const bool released, const char *lds_tab,
                                            const char *__restrict__ glb_tab, float &out_l, float &out_r,
                                            const int xf = 0, const bool muted = false, const float white = 0.0f,
-                                           const float ms_ext = 0.0f, const float am_ext = 0.0f, const float pm_ext = 0.0f) {
+                                           const float ms_ext = 0.0f, const float am_ext = 0.0f, const float pm_ext = 0.0f,
+                                           FastCz *cz = nullptr) {
   float inc = r.inc;
   if (STOPS && (xf & (XF_FM | XF_AP))) {                // wave-uniform: some lane of the wave is modulated
     // voice_sample[m] as the previous frame left it (a modulator that is skipped this frame holds exact zero)
@@ -476,6 +532,14 @@ __device__ __forceinline__ void fast_frame(FastRegs &r, float &xn, float &xo, fl
       r.pm_prev = EXTMS ? pm_ext : __int_as_float(__builtin_amdgcn_ds_bpermute(max(r.pm_addr, 0), mine));
     }
   }
+  if constexpr (CZ) {
+    // a CZ source's sample: the exchange the frequency modulators use (last frame's voice_sample[m], synth.c:262-267 for m above
+    // the carrier), then the amount-dependent half of the warp for the lanes that have one
+    if (xf & XF_CZ_SRC) {
+      const float cs = __int_as_float(__builtin_amdgcn_ds_bpermute(max(cz->addr, 0), __float_as_int(r.sample)));
+      if (cz->addr >= 0) fast_cz_amount(*cz, cz->dist + cs * cz->depth);
+    }
+  }
   if (STOPS && (xf & XF_REV) && r.rev) inc = -inc;      // reverse playback, applied to the modulated increment
   float ph;
   if (BIDIR) {
@@ -486,7 +550,10 @@ __device__ __forceinline__ void fast_frame(FastRegs &r, float &xn, float &xo, fl
   } else {
     ph = fast_advance<TAME, STOPS && !NOSTOP, LOZ && TAME && (!STOPS || NOSTOP)>(r, inc);
   }
-  float s = fast_fetch<TAB_LDS, INTERP, TAME && !BIDIR && (!STOPS || NOSTOP)>(lds_tab, glb_tab, r, ph);   // a finishing phase needs the index clamp
+  if constexpr (CZ) {
+    if ((xf & XF_CZ) && cz->mode) ph = fast_cz_warp(*cz, ph);    // synth.c:262-267: the lookup position only, voice_phase keeps the wrapped phase
+  }
+  float s = fast_fetch<TAB_LDS, INTERP, TAME && !BIDIR && (!STOPS || NOSTOP) && !CZ>(lds_tab, glb_tab, r, ph);   // a finishing phase (a warped position) needs the index clamp
   if (STOPS && (xf & XF_NOISE) && r.noise) s = white;   // synth.c:543-546 (the lane's oscillator idles on inert numbers)
   if (STOPS && (xf & XF_HOLDQ)) {
     if (r.hold_max) {                                    // sample & hold, synth.c:560-571

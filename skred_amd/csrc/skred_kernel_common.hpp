@@ -416,6 +416,15 @@ __device__ __forceinline__ sk_motion_t sk_env_motion(uint64_t first_now, bool de
   return m;
 }
 
+// == fast_pow, synth.c:140-147.  The float->int cast saturates on the GPU exactly where the x86
+// conversion of the reference returns INT_MIN (large negative products), so the bits agree.
+__device__ __forceinline__ float pow_bits(float base, float expo) {
+  if (base <= 0.0f) return 0.0f;
+  int i = __float_as_int(base);
+  i = (int)(expo * (float)(i - 1065353216) + 1065353216.0f);
+  return __int_as_float(i);
+}
+
 // ---------------------------------------------------------------- per-voice registers
 
 struct VoiceRegs {

@@ -135,7 +135,7 @@ __device__ __forceinline__ void fast_finish(const sk_render_args_t &a, FastRegs 
   {                                                                                                      \
     float l, rr;                                                                                         \
     SK_FAST_DRAW()                                                                                       \
-    fast_frame<TAB_LDS, FILTER, ENV, STEADY_, false, INTERP, STOPS>(r, XN, XO, YN, YO, released, lds_tab, glb_tab, l, rr, xf, muted, white_); \
+    fast_frame<TAB_LDS, FILTER, ENV, STEADY_, false, INTERP, STOPS, false, false, false, false, CZ>(r, XN, XO, YN, YO, released, lds_tab, glb_tab, l, rr, xf, muted, white_, 0.0f, 0.0f, 0.0f, &cz); \
     l = silent ? 0.0f : l; rr = silent ? 0.0f : rr;                                                      \
     SK_FAST_STEM(J, l, rr)                                                                               \
     if (STOPS && (xf & XF_STOP) && __any(r.fin)) fast_finish(a, r, v, dead, silent, sample_final, SWAPPED_, c0 + (J) == a.num_frames - 1, misc_xy); \
@@ -311,7 +311,7 @@ __device__ __forceinline__ void fast_finish(const sk_render_args_t &a, FastRegs 
   {                                                                                                      \
     float l, rr;                                                                                         \
     SK_FAST_DRAW()                                                                                       \
-    fast_frame<TAB_LDS, FILTER, ENV, true, false, INTERP, STOPS>(r, XN, XO, YN, YO, released, lds_tab, glb_tab, l, rr, xf, muted, white_); \
+    fast_frame<TAB_LDS, FILTER, ENV, true, false, INTERP, STOPS, false, false, false, false, CZ>(r, XN, XO, YN, YO, released, lds_tab, glb_tab, l, rr, xf, muted, white_, 0.0f, 0.0f, 0.0f, &cz); \
     l = silent ? 0.0f : l; rr = silent ? 0.0f : rr;                                                      \
     SK_FAST_STEM(Q, l, rr)                                                                               \
     if (STOPS && (xf & XF_STOP) && __any(r.fin)) fast_finish(a, r, v, dead, silent, sample_final, SWAPPED_, c0 + (Q) == a.num_frames - 1, misc_xy); \
@@ -629,11 +629,16 @@ __device__ __forceinline__ void fast_finish(const sk_render_args_t &a, FastRegs 
 // once a launch has reported that none did (the general frames are in both, so the choice only decides speed).
 // PROBE: the same kernel compiled with -DSK_PROBE_TU (fast_post / fast_post_v then also write the probe rows of
 // skred_bank_set_probe): a template parameter only so that those instantiations are symbols of their own.
-template <bool TAB_LDS, bool FILTER, bool ENV, int INTERP, bool STOPS, bool RAMPK = false, bool PROBE = false>
+// CZ (SKRED_OPT_CZ_FAST; extended LDS-table instantiations only, units of their own: SK_FAST_PART 4 / 5): lanes with CZ phase
+// distortion (fast_cz_warp between the phase wrap and the table fetch of fast_frame).  A wavefront that holds such a lane (XF_CZ)
+// walks the extended frame loop -- SK_FAST_X_BLOCK's eight frames per reduction tile, or frame by frame with the stem buffer --,
+// its CZ sources come through the same per-frame exchange as frequency modulators, and it never takes the skewed blocks; the
+// other wavefronts of the bank run whatever they would run in the extended instantiation without CZ.
+template <bool TAB_LDS, bool FILTER, bool ENV, int INTERP, bool STOPS, bool RAMPK = false, bool PROBE = false, bool CZ = false>
 // (the extended LDS-table instantiation WITHOUT biquad and envelope, truncating lookup -- what every shipped patch but 18.sk runs on -- needs 129
 // registers, three of them holding spilled SGPRs: bounded to 128 it keeps four waves per SIMD where the pool leaves room for
 // four workgroups per CU -- 7.sk, 16 KB of tables: 1.29 -> 1.00 ms)
-__global__ __launch_bounds__(SK_GROUP, TAB_LDS ? (STOPS ? ((FILTER || ENV || INTERP != 0) ? SK_FAST_EXT_MIN_WAVES : SK_FAST_EXT_BARE_MIN_WAVES) : SK_FAST_MIN_WAVES) : (STOPS ? SK_FAST_WIN_EXT_MIN_WAVES : SK_FAST_WIN_MIN_WAVES)) void sk_render_fast_kernel(const sk_render_args_t a) {
+__global__ __launch_bounds__(SK_GROUP, TAB_LDS ? (STOPS ? ((FILTER || ENV || INTERP != 0 || CZ) ? SK_FAST_EXT_MIN_WAVES : SK_FAST_EXT_BARE_MIN_WAVES) : SK_FAST_MIN_WAVES) : (STOPS ? SK_FAST_WIN_EXT_MIN_WAVES : SK_FAST_WIN_MIN_WAVES)) void sk_render_fast_kernel(const sk_render_args_t a) {
   extern __shared__ float lds[];
   float2 *wsum = reinterpret_cast<float2 *>(lds + (TAB_LDS ? a.lds_table_floats : 0));
   const char *lds_tab = reinterpret_cast<const char *>(lds);
@@ -680,6 +685,8 @@ __global__ __launch_bounds__(SK_GROUP, TAB_LDS ? (STOPS ? ((FILTER || ENV || INT
     if (packed) { v = sk_packed_voice(a, g * (SK_GROUP / 64) + wave, lane, pmask, ppos); absent = v < 0; if (absent) { v = 0; ppos = 0; } }
     const bool publish = a.finish && g + a.n_rows >= n_pass;   // the pass that completes this workgroup's row
     FastRegs r;
+    FastCz cz;                    // (CZ instantiations) the lane's phase distortion; never touched elsewhere
+    (void)cz;
     bool dead, silent;            // dead: skipped by synth.c:531-542; silent: dead or muted
     bool muted = false;           // voice_disconnect
     uint2 misc_xy = make_uint2(0u, 0u);   // (EXT) sample&hold words of the MISC plane, kept for a pan-modulated store
@@ -768,6 +775,22 @@ __global__ __launch_bounds__(SK_GROUP, TAB_LDS ? (STOPS ? ((FILTER || ENV || INT
           r.fm_depth = __uint_as_float(mf.x);
         }
       }
+      if constexpr (CZ) {
+        // (a skipped lane and a noise lane -- whose oscillator never runs, synth.c:543-546 -- have no warp; the planes number the
+        // source by its lane in the 64-voice group, like the other modulators)
+        const uint4 mx = *reinterpret_cast<const uint4 *>(&a.ro[SKP_MODX][v]);
+        const uint4 mi = *reinterpret_cast<const uint4 *>(&a.ro[SKP_MODI][v]);
+        int mode = (int)mx.y;
+        if (dead || r.noise || mode < 1 || mode > 7) mode = 0;
+        int cz_lane = mode ? (int)mi.w : -1;
+        if (packed && cz_lane >= 0) cz_lane = sk_packed_lane(a, pmask, lane, cz_lane);
+        cz.mode = mode;
+        cz.addr = cz_lane >= 0 ? cz_lane << 2 : -1;
+        cz.dist = __uint_as_float(reinterpret_cast<const uint32_t *>(&a.ro[SKP_FILT][v])[3]);
+        cz.depth = __uint_as_float(mx.x);
+        cz.size = (float)(int)tab.y;
+        fast_cz_amount(cz, cz.dist + 1.0f);             // no source: the amount is voice_cz_distortion + 1.0f (synth.c:262-267)
+      }
     }
     bool sample_final = false;                         // (STOPS) the voice finished in this launch: its planes are final
     // wrap can only ever be the simple one (see fast_frame<TAME>): decided once per pass
@@ -800,6 +823,10 @@ __global__ __launch_bounds__(SK_GROUP, TAB_LDS ? (STOPS ? ((FILTER || ENV || INT
       if (__any(r.nosmooth)) xf |= XF_NOSMOOTH;
       if (__any(r.noise)) xf |= XF_NOISE;
       if (__any(r.stop)) xf |= XF_STOP;                    // (a lane that finishes turns its flag off: the bit stays, harmless)
+      if constexpr (CZ) {
+        if (__any(cz.mode != 0)) xf |= XF_CZ;             // (any_fm below: the frame loop; neither fm_only nor the skewed blocks)
+        if (__any(cz.addr >= 0)) xf |= XF_CZ_SRC;
+      }
     }
     // features the block paths do not serve (modulation exchange, reverse, the noise source): such a wave walks frame by
     // frame; sample & hold, bit-crush and smoother-off ride the block paths (fast_post_v), stopping voices while far from their end
@@ -1073,10 +1100,11 @@ __global__ __launch_bounds__(SK_GROUP, TAB_LDS ? (STOPS ? ((FILTER || ENV || INT
 
 // specialisation key: table residency x filter x envelope x interpolation
 //
-// The template matrix is compiled as FOUR translation units from this one source (-DSK_FAST_PART=n; the extended instantiations
+// The template matrix is compiled as SIX translation units from this one source (-DSK_FAST_PART=n; the extended instantiations
 // with the skewed blocks take minutes each): part 0 the clean instantiations and the launcher, part 1 / 2 the extended
-// instantiations of LDS-table banks without / with the biquad, part 3 those of global-table banks.  (-DSK_FAST_ONE_CASE=...:
-// one instantiation pair in one unit, for compile-time experiments.)
+// instantiations of LDS-table banks without / with the biquad, part 3 those of global-table banks, part 4 / 5 the CZ instantiations
+// (SKRED_OPT_CZ_FAST: extended, LDS-table banks, without / with the biquad; lookup 0 / 1 only -- the planner keeps the fold test
+// for banks with CZ lanes).  (-DSK_FAST_ONE_CASE=...: one instantiation pair in one unit, for compile-time experiments.)
 #ifndef SK_FAST_PART
 #define SK_FAST_PART 0
 #endif
@@ -1093,6 +1121,8 @@ extern "C" int sk_launch_render_fastp(const sk_render_args_t *args, int n_workgr
 extern "C" int SK_FAST_CASES(1)(const sk_render_args_t *args, unsigned grid_x, size_t lds_bytes, hipStream_t stream, int key, int rampk, int guard);
 extern "C" int SK_FAST_CASES(2)(const sk_render_args_t *args, unsigned grid_x, size_t lds_bytes, hipStream_t stream, int key, int rampk, int guard);
 extern "C" int SK_FAST_CASES(3)(const sk_render_args_t *args, unsigned grid_x, size_t lds_bytes, hipStream_t stream, int key, int rampk, int guard);
+extern "C" int SK_FAST_CASES(4)(const sk_render_args_t *args, unsigned grid_x, size_t lds_bytes, hipStream_t stream, int key, int rampk, int guard);
+extern "C" int SK_FAST_CASES(5)(const sk_render_args_t *args, unsigned grid_x, size_t lds_bytes, hipStream_t stream, int key, int rampk, int guard);
 
 #define SK_FAST_BIG_LDS_(K)                                                                                                 \
   if (lds_bytes > 65536) {   /* (per launch: the attribute belongs to the device the calling thread is on) */              \
@@ -1100,6 +1130,10 @@ extern "C" int SK_FAST_CASES(3)(const sk_render_args_t *args, unsigned grid_x, s
 #define SK_FAST_LAUNCH_(T, F, E, I, X)                                                                                      \
   { if (E && rampk) { SK_FAST_BIG_LDS_((sk_render_fast_kernel<T, F, E, I, X, E, SK_PROBE_FLAG>)) hipLaunchKernelGGL((sk_render_fast_kernel<T, F, E, I, X, E, SK_PROBE_FLAG>), grid, block, lds_bytes, stream, *args); }   \
     else { SK_FAST_BIG_LDS_((sk_render_fast_kernel<T, F, E, I, X, false, SK_PROBE_FLAG>)) hipLaunchKernelGGL((sk_render_fast_kernel<T, F, E, I, X, false, SK_PROBE_FLAG>), grid, block, lds_bytes, stream, *args); } }
+#define SK_FAST_LAUNCH_CZ_(F, E, I)                                                                                         \
+  { if (E && rampk) { SK_FAST_BIG_LDS_((sk_render_fast_kernel<true, F, E, I, true, E, SK_PROBE_FLAG, true>)) hipLaunchKernelGGL((sk_render_fast_kernel<true, F, E, I, true, E, SK_PROBE_FLAG, true>), grid, block, lds_bytes, stream, *args); }   \
+    else { SK_FAST_BIG_LDS_((sk_render_fast_kernel<true, F, E, I, true, false, SK_PROBE_FLAG, true>)) hipLaunchKernelGGL((sk_render_fast_kernel<true, F, E, I, true, false, SK_PROBE_FLAG, true>), grid, block, lds_bytes, stream, *args); } }
+#define SK_FAST_CASE_Z(K, F, E, I) case 16 + K: SK_FAST_LAUNCH_CZ_(F, E, I) break;
 #define SK_FAST_CASE_C(K, T, F, E, I) case K: if (I && guard) SK_FAST_LAUNCH_(T, F, E, (I ? 2 : 0), false) else SK_FAST_LAUNCH_(T, F, E, I, false) break;
 #define SK_FAST_CASE_X(K, T, F, E, I) case 16 + K: if (I && guard) SK_FAST_LAUNCH_(T, F, E, (I ? 2 : 0), true) else SK_FAST_LAUNCH_(T, F, E, I, true) break;
 
@@ -1109,8 +1143,12 @@ extern "C" int SK_FAST_CASES(3)(const sk_render_args_t *args, unsigned grid_x, s
 extern "C" int SK_FAST_CASES(1)
 #elif SK_FAST_PART == 2
 extern "C" int SK_FAST_CASES(2)
-#else
+#elif SK_FAST_PART == 3
 extern "C" int SK_FAST_CASES(3)
+#elif SK_FAST_PART == 4
+extern "C" int SK_FAST_CASES(4)
+#else
+extern "C" int SK_FAST_CASES(5)
 #endif
     (const sk_render_args_t *args, unsigned grid_x, size_t lds_bytes, hipStream_t stream, int key, int rampk, int guard) {
   dim3 grid(grid_x), block(SK_GROUP);
@@ -1121,6 +1159,12 @@ extern "C" int SK_FAST_CASES(3)
 #elif SK_FAST_PART == 2
     SK_FAST_CASE_X(12, true, true, false, 0)  SK_FAST_CASE_X(13, true, true, false, 1)
     SK_FAST_CASE_X(14, true, true, true, 0)   SK_FAST_CASE_X(15, true, true, true, 1)
+#elif SK_FAST_PART == 4
+    SK_FAST_CASE_Z(8, false, false, 0)  SK_FAST_CASE_Z(9, false, false, 1)
+    SK_FAST_CASE_Z(10, false, true, 0)  SK_FAST_CASE_Z(11, false, true, 1)
+#elif SK_FAST_PART == 5
+    SK_FAST_CASE_Z(12, true, false, 0)  SK_FAST_CASE_Z(13, true, false, 1)
+    SK_FAST_CASE_Z(14, true, true, 0)   SK_FAST_CASE_Z(15, true, true, 1)
 #else
     SK_FAST_CASE_X(0, false, false, false, 0) SK_FAST_CASE_X(1, false, false, false, 1)
     SK_FAST_CASE_X(2, false, false, true, 0)  SK_FAST_CASE_X(3, false, false, true, 1)
@@ -1151,7 +1195,7 @@ extern "C" int SK_FAST_LAUNCHER(const sk_render_args_t *args, int n_workgroups, 
     args = &skew_args;
   }
   dim3 grid((unsigned)(n_workgroups + args->wg_shift)), block(SK_GROUP);
-  const int key = (((args->fast_mode & (SKM_STOPS | SKM_FM | SKM_MIXED)) || args->pack_shift < 6) ? 16 : 0) |   /* the extended instantiation */ (tab_lds ? 8 : 0) | ((args->fast_mode & SKM_FILTER_ALL) ? 4 : 0) |
+  const int key = (((args->fast_mode & (SKM_STOPS | SKM_FM | SKM_MIXED | SKM_CZ)) || args->pack_shift < 6) ? 16 : 0) |   /* the extended instantiation */ (tab_lds ? 8 : 0) | ((args->fast_mode & SKM_FILTER_ALL) ? 4 : 0) |
                   ((args->fast_mode & SKM_ENV_ALL) ? 2 : 0) | (args->interp != 0 ? 1 : 0);
   const bool rampk = !args->skip_env2;   /* envelopes may be moving (skip_env2: a launch has reported that none did) */
   const bool guard = args->interp == 2;  /* linear lookup, every live voice on a guarded whole-table loop (SKF_GUARD; the host counts) */
@@ -1159,6 +1203,10 @@ extern "C" int SK_FAST_LAUNCHER(const sk_render_args_t *args, int n_workgroups, 
 #define SK_FAST_CASE_BOTH(...) SK_FAST_CASE_C(__VA_ARGS__) SK_FAST_CASE_X(__VA_ARGS__)
   switch (key) { SK_FAST_CASE_BOTH(SK_FAST_ONE_CASE) }
 #else
+  if (args->fast_mode & SKM_CZ) {   /* the CZ instantiations (the planner sends LDS-table banks only, lookup 0 / 1) */
+    if (!tab_lds || guard) return (int)hipErrorInvalidValue;
+    return (key & 4) ? SK_FAST_CASES(5)(args, grid.x, lds_bytes, stream, key, rampk, guard) : SK_FAST_CASES(4)(args, grid.x, lds_bytes, stream, key, rampk, guard);
+  }
   if (key >= 24) return (key & 4) ? SK_FAST_CASES(2)(args, grid.x, lds_bytes, stream, key, rampk, guard) : SK_FAST_CASES(1)(args, grid.x, lds_bytes, stream, key, rampk, guard);
   if (key >= 16) return SK_FAST_CASES(3)(args, grid.x, lds_bytes, stream, key, rampk, guard);
   switch (key) {

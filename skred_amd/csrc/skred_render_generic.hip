@@ -130,14 +130,7 @@ __global__ __launch_bounds__(SK_GROUP) void sk_render_kernel(const sk_render_arg
 // voice_sample through two LDS arrays (previous / current frame).  Cost = (max level + 1) passes per
 // frame -- irrelevant for the 64-voice drop-in, and banks without modulators never come here.
 
-// == fast_pow, synth.c:140-147.  The float->int cast saturates on the GPU exactly where the x86
-// conversion of the reference returns INT_MIN (large negative products), so the bits agree.
-__device__ __forceinline__ float pow_bits(float base, float expo) {
-  if (base <= 0.0f) return 0.0f;
-  int i = __float_as_int(base);
-  i = (int)(expo * (float)(i - 1065353216) + 1065353216.0f);
-  return __int_as_float(i);
-}
+// (fast_pow, synth.c:140-147: pow_bits, skred_kernel_common.hpp -- the one-voice kernel's CZ lanes use it too)
 
 // == cz_phasor, synth.c:149-215
 __device__ float cz_warp(int mode, float table_phase, float amount, int table_size) {

@@ -24,7 +24,7 @@ ABI_SYMBOLS = [
     "skred_bank_set_globals", "skred_bank_get_globals",
     "skred_bank_render", "skred_bank_master", "skred_bank_render_mix", "skred_bank_render_host",
     "skred_bank_last_render_ms", "skred_bank_timing_reset", "skred_bank_timing_summary",
-    "skred_bank_set_option", "skred_bank_last_kernel", "skred_bank_last_in_place", "skred_bank_last_split", "skred_bank_last_pack", "skred_bank_list_violations", "skred_bank_set_probe",
+    "skred_bank_set_option", "skred_bank_last_kernel", "skred_bank_last_in_place", "skred_bank_last_split", "skred_bank_last_pack", "skred_bank_last_cz", "skred_bank_list_violations", "skred_bank_set_probe",
     "skred_bank_set_taps", "skred_bank_last_taps",
     "skred_bank_set_form_counter", "skred_bank_last_cross_group",
     "skred_bank_update", "skred_bank_defer", "skred_bank_run_queue", "skred_bank_queue_pending",
@@ -120,6 +120,7 @@ def load() -> C.CDLL:
     L.skred_bank_last_in_place.argtypes = [vp]
     L.skred_bank_last_split.argtypes = [vp]
     L.skred_bank_last_pack.argtypes = [vp]
+    L.skred_bank_last_cz.argtypes = [vp]
     L.skred_bank_set_probe.argtypes = [vp, vp, i32, vp]
     L.skred_bank_set_taps.argtypes = [vp, vp, i32, vp]
     L.skred_bank_last_taps.argtypes = [vp]
@@ -405,6 +406,15 @@ class DeviceBank:
     def last_pack(self) -> int:
         """Lanes per 64-voice group in the latest block, 0: not packed."""
         return int(self.L.skred_bank_last_pack(self.h))
+
+    def set_cz_fast(self, on: bool) -> None:
+        """SKRED_OPT_CZ_FAST: 1 banks whose CZ voices all qualify (mode 1..7, no CZ source or one above the carrier in its 64-voice
+        group, other modulators as for the one-voice kernel) render on the one-voice-per-lane kernel, 0 (default) on the modulated one."""
+        _check(self.L.skred_bank_set_option(self.h, 12, int(bool(on))), "skred_bank_set_option")
+
+    def last_cz(self) -> bool:
+        """The latest block ran a CZ instantiation of the one-voice-per-lane kernel (SKRED_OPT_CZ_FAST)."""
+        return bool(self.L.skred_bank_last_cz(self.h))
 
     def set_split_pairs(self, pairs: int) -> None:
         """SKRED_OPT_SPLIT_PAIRS (tests): 0 the library's choice, 2 / 4 pairs per workgroup forced."""

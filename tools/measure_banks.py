@@ -20,6 +20,10 @@
              launches between an event pair (every criterion, UNNAMED off and on, max_out 1 024; median and minimum of 50), beside one
              512-frame block of the same bank; (b) what a host does for the same answer without it: skred_bank_download of the bank
              plus the predicate in numpy
+  cz         CZ phase distortion on the one-voice kernel (SKRED_OPT_CZ_FAST): one 512-frame block at 2^20 and 2^16 voices of (a) the C2
+             recipe with `c1,0.5` on every voice, (b) a three-voice group shaped like 42.sk's v0-v2 (`v0 c1,0.5 C2,0.5 F1,1`, v1 and
+             v2 `m1` modulators above it) tiled over the bank, each with the option 0 and 1.  Run from a directory that holds an
+             older build of the package, it times option 0 only: the baseline
 
 Each line: ms per block over the timed blocks (wall clock), voice-samples/s, and the render kernel's duration from the
 library's own event pair around the latest bracketed launch (a bracketed launch runs alone).  kernels / fm / noise print
@@ -35,7 +39,7 @@ sys.path.insert(0, ".")
 from skred_amd import banks, device  # noqa: E402
 
 
-def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=False, overlap=None, timing=4, cross=False, taps=None):
+def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=False, overlap=None, timing=4, cross=False, taps=None, cz_fast=None):
     n = bank.n
     out = torch.zeros(F, 2, device="cuda")
     db = device.DeviceBank(n)
@@ -43,6 +47,8 @@ def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=Fal
     db.upload(bank)
     db.set_globals(g)
     db.set_cross_group(cross)
+    if cz_fast is not None:
+        db.set_cz_fast(cz_fast)
     if taps is not None and len(taps):
         d_taps = torch.zeros(F, len(taps), 2, device="cuda")
         db.set_taps(taps, d_taps.data_ptr())
@@ -76,6 +82,8 @@ def run(name, bank, tables, g, interp=0, F=512, steps=60, min2=None, generic=Fal
     if taps is not None:
         tape += f"  taps {db.last_taps()}, lanes per group {db.last_pack()}"
         db.set_taps([], 0)
+    if cz_fast is not None:
+        tape += f"  cz {int(db.last_cz())}, lanes per group {db.last_pack()}"
     print(f"{name:66s} kernel={db.last_kernel()} {dt * 1e3:.4f} ms/block {n * F / dt:.3e} voice-samples/s  "
           f"render kernel {k} ms  host issue {(t1 - t0) / steps * 1e6:.1f} us{tape}")
     db.close()
@@ -328,8 +336,40 @@ def idle():
         db.close()
 
 
+def cz_banks(n):
+    """(a) C2 with `c1,0.5` everywhere; (b) 42.sk's v0-v2 as a triple -- carrier, FM modulator, CZ source, the two `m1` -- 21 times per
+    64-voice group (lane 63 silent)."""
+    b, t, g = banks.bank_c2(n)
+    b["voice_cz_mod_osc"] = -1
+    b["voice_cz_mode"] = 1
+    b["voice_cz_distortion"] = 0.5
+    yield "c2 + c1,0.5 on every voice", b, t, g
+    b, t, g = banks.bank_c2(n)
+    v = np.arange(n)
+    lane = v % 64
+    role = np.where(lane < 63, lane % 3, 3)                # 0 carrier, 1 / 2 its modulators, 3 unused
+    car = role == 0
+    b["voice_cz_mod_osc"] = np.where(car, v + 2, -1).astype(np.int32)
+    b["voice_cz_mod_depth"] = 0.5
+    b["voice_cz_mode"] = car.astype(np.int32)
+    b["voice_cz_distortion"] = 0.5
+    b["voice_freq_mod_osc"] = np.where(car, v + 1, -1).astype(np.int32)
+    b["voice_freq_mod_depth"] = 1.0
+    b["voice_disconnect"] = ((role == 1) | (role == 2)).astype(np.int32)
+    b["voice_amp"] = np.where(role == 3, 0.0, 1.0).astype(np.float32)
+    yield "42.sk v0-v2 (c1,0.5 C2,0.5 F1,1; two m1 modulators) tiled", b, t, g
+
+
+def cz():
+    has_opt = hasattr(device.DeviceBank, "set_cz_fast")   # (an older build of the package: option 0 only -- the baseline)
+    for n in (1 << 20, 1 << 16):
+        for name, b, t, g in cz_banks(n):
+            for opt in ((0, 1) if has_opt else (None,)):
+                run(f"{n} {name}, option {'-' if opt is None else opt}", b, t, g, steps=30 if n > 100000 else 60, cz_fast=opt)
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "cz": cz}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
