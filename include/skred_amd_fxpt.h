@@ -23,6 +23,13 @@
  *            smoother (optional): g += ((target - g) * k_q15) >> 15, gain = g
  *   output   v = (s * gain) >> 15 (product in 64 bits) ; L = (v * pan_left_q15) >> 15 ; R = (v * pan_right_q15) >> 15
  *            every other product is an int32 one (keep it inside 32 bits: Q15 gains, velocity <= 65535)
+ *   range    PROMISED only while each of those int32 products stays inside int32 -- e * velocity, the two envelope products,
+ *            (target - g) * k_q15, v * pan_left_q15, v * pan_right_q15 -- with gains, velocity and smoother state >= 0:
+ *            beyond that the scalar definition is signed overflow in C and defines nothing (skred_fxbank_upload checks only
+ *            the table window, amp_q15 and the delay line; a smoother state of 2^20 with a pan of 8192 is already outside).
+ *            (b - a) * f of the linear lookup cannot leave int32 (|b - a| <= 65535, f < 32768).  sample_start and
+ *            sample_release may lie AHEAD of the clock: now - sample_start wraps and saturates, so the note plays its
+ *            sustain level until now reaches sample_start and attacks then; a release ahead of the clock has run out
  *   mix      int64 sum of L and of R over all voices, per frame
  *   skipped  amp_q15 == 0 or finished: v = 0, state frozen (as synth.c:531-542 does for the float path)
  *   one-shot a voice with one_shot != 0 plays ONE cycle of its table: in the frame where phase + phase_inc carries out of

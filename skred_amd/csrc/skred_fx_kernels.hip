@@ -404,10 +404,13 @@ __global__ __launch_bounds__(SKX_GROUP, 4) void sk_fx_render_kernel(const skx_ar
     for (int c0 = 0; c0 < a.num_frames; c0 += SKX_CHUNK) {
       const int cn = min(SKX_CHUNK, a.num_frames - c0);
       // steady: the envelope level of every live lane is one constant over this chunk -- no envelope, an inactive one
-      // (it stays inactive), or a held note past its decay (t only grows; note-off arrives between launches)
-      const uint32_t t_first = sat32(a.count0 + (uint64_t)c0 + 1 - t_start);
+      // (it stays inactive), or a held note past its decay (t only grows; note-off arrives between launches).  A note start
+      // AHEAD of the clock is not one: now - sample_start wraps and saturates, which reads as "past the decay", until now
+      // reaches the start inside some chunk and t restarts at 0 -- such a lane goes frame by frame
+      const uint64_t now_first = a.count0 + (uint64_t)c0 + 1;
+      const uint32_t t_first = sat32(now_first - t_start);
       // (a wave with a live one-shot voice checks for its end frame by frame: no blocks)
-      const bool steady = __all(dead || !uses_env || !active || (t_release == 0 && (uint64_t)t_first >= AD)) &&
+      const bool steady = __all(dead || !uses_env || !active || (t_release == 0 && t_start <= now_first && (uint64_t)t_first >= AD)) &&
                           !__any(one_shot && !dead && !finished);
       int j = 0;
       if (steady && cn >= 8) {
