@@ -39,6 +39,7 @@ struct Fast2Regs {
   int toff4[2], tsize_m1[2];
   v2f k, b0, b1, b2, a1, a2, gain_const;   // gain_const: gain of a constant-level lane
   v2f pan_lr[2];                           // (pan_left, pan_right) of voice 0 / voice 1: packed by channel, not by voice
+                                           // (after fast2_fold_pan: pan x sgain, the folded gains of the EM 7 frames)
   // MIXED instantiations: banks in which only some voices run the biquad / use the envelope
   bool filt[2];                            // this voice runs the biquad
   bool fake_active[2];                     // an un-enveloped voice is rendered as a held note at level 1 (amp * (1*1) == amp):
@@ -63,6 +64,7 @@ struct Fast2Regs {
   float2 *probe[2];                        // this frame's probe row of the lane's voices (nullptr: not probed / silent / rendered elsewhere)
   int probe_stride;                        // float2 per frame
   bool probe_any;                          // (wave-uniform) some lane of the wave writes probes
+  v2f pan0[2];                             // pan_lr as loaded, kept by fast2_fold_pan: the stem rows stay (y * sgain) * pan
 #endif
 };
 
@@ -260,7 +262,8 @@ __device__ __forceinline__ v2f fast2_osc(Fast2Regs &r, const char *lds_tab, cons
 // EM (envelope mode): 0 every lane has a constant gain; 1 "ramp": every lane keeps one stage, straight-line
 // with the short exact division; 2 general; 3 constant gain AND the amp smoother has stalled in every lane
 // (fast2_smoother_stalled: its update no longer changes it, so it is skipped); 6: as 0 with the lane's listed voices taking
-// this frame's gain from r.gt (in-place instantiation).  TAME: see fast_frame.
+// this frame's gain from r.gt (in-place instantiation); 7: as 3 with gain and pan folded into one constant per lane and
+// channel (fast2_fold_pan; sk_render_fast2_kernel's tame waves).  TAME: see fast_frame.
 template <bool FILTER, int EM, bool TAME, bool MIXED = false, bool MUTESEL = false, int FMP = 0>
 __device__ __forceinline__ void fast2_post(Fast2Regs &r, Env2Regs &e, v2f s, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
                                            const bool rel0, const bool rel1, const bool silent0,
@@ -281,6 +284,33 @@ __device__ __forceinline__ void fast2_post(Fast2Regs &r, Env2Regs &e, v2f s, v2f
       yo = y;
       s = y;
     }
+  }
+  if (EM == 7) {
+    // ---- folded: the mix straight from the filtered samples ----
+    // A mix-only launch stores no stems, and sgain does not change any more, so (y * sgain) * pan of every frame is y times a
+    // per-lane constant gA = pan * sgain (fast2_fold_pan left it in r.pan_lr): one packed multiply and one packed FMA give the
+    // lane's (L, R) where gain, two pan products and their sum took four.  Per voice that is one rounding apart from
+    // (y * sgain) * pan, and the FMA takes one more out of the sum (1e-7 relative against the mix bar of 1e-5); no state
+    // is computed from it.  r.sample travels as y: the caller multiplies it by r.sgain -- today's product -- behind the last
+    // folded frame (SK_FAST2_FOLD_SAMPLE), before anything reads it.
+    static_assert(EM != 7 || TAME, "folded frames: tame waves only");
+    r.sample = s;
+    v2f so = s;
+    if (MUTESEL) {                                     // muted live lanes: selected away as ever, never 0 * y
+      so.x = silent0 ? 0.0f : s.x;
+      so.y = silent1 ? 0.0f : s.y;
+    }
+#ifdef SK_PROBE_TU
+    if (r.probe_any) {                                 // the stem rows keep the reference's own products (synth.c:603-608)
+      const v2f sg = s * r.sgain;
+      if (r.probe[0]) { *r.probe[0] = make_float2(sg.x * r.pan0[0].x, sg.x * r.pan0[0].y); r.probe[0] += r.probe_stride; }
+      if (r.probe[1]) { *r.probe[1] = make_float2(sg.y * r.pan0[1].x, sg.y * r.pan0[1].y); r.probe[1] += r.probe_stride; }
+    }
+#endif
+    const v2f lr = __builtin_elementwise_fma(r.pan_lr[1], (v2f){so.y, so.y}, r.pan_lr[0] * (v2f){so.x, so.x});
+    out_l = lr.x;
+    out_r = lr.y;
+    return;
   }
   // ---- gain ----
   v2f gain;
@@ -368,13 +398,28 @@ __device__ __forceinline__ bool fast2_smoother_stalled(const Fast2Regs &r) {
   return __all(!r.am_on && __float_as_uint(nxt.x) == __float_as_uint(r.sgain.x) && __float_as_uint(nxt.y) == __float_as_uint(r.sgain.y));
 }
 
-template <bool TAB_LDS, bool FILTER, int EM, bool TAME, int INTERP, bool MIXED = false, int FMP = 0>
+// A wave whose smoother has stalled in every lane of a pass without modulation stays that way to the end of the pass:
+// gain_const, k and sgain no longer change.  From the first such chunk on, sk_render_fast2_kernel's tame waves render
+// EM 7 frames with the folded gains pan x sgain IN PLACE of the pan gains (the steady instantiation has no four registers
+// to carry both; nothing stores pan_lr back but a modulated pan, which such a wave does not have).  A listed voice's pan
+// gains are zero, and so are its folded gains.
+__device__ __forceinline__ void fast2_fold_pan(Fast2Regs &r) {
+#ifdef SK_PROBE_TU
+  r.pan0[0] = r.pan_lr[0]; r.pan0[1] = r.pan_lr[1];
+#endif
+  r.pan_lr[0] = r.pan_lr[0] * (v2f){r.sgain.x, r.sgain.x};
+  r.pan_lr[1] = r.pan_lr[1] * (v2f){r.sgain.y, r.sgain.y};
+}
+// behind the last folded frame of a block or a tail: voice_sample = y * sgain, the product every unfolded frame forms
+#define SK_FAST2_FOLD_SAMPLE() r.sample = r.sample * r.sgain;
+
+template <bool TAB_LDS, bool FILTER, int EM, bool TAME, int INTERP, bool MIXED = false, int FMP = 0, bool MUTESEL = false>
 __device__ __forceinline__ void fast2_frame(Fast2Regs &r, Env2Regs &e, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
                                             const bool rel0, const bool rel1, const bool silent0,
                                             const bool silent1, const char *lds_tab,
                                             const char *__restrict__ glb_tab, float &out_l, float &out_r) {
   const v2f s = fast2_osc<TAB_LDS, TAME, INTERP, false, FMP>(r, lds_tab, glb_tab);
-  fast2_post<FILTER, EM, TAME, MIXED, false, FMP>(r, e, s, xn, xo, yn, yo, rel0, rel1, silent0, silent1, out_l, out_r);
+  fast2_post<FILTER, EM, TAME, MIXED, MUTESEL, FMP>(r, e, s, xn, xo, yn, yo, rel0, rel1, silent0, silent1, out_l, out_r);
 }
 
 // ---- table windows for pools that do not fit in LDS (PCM banks) ----
@@ -472,6 +517,21 @@ __device__ __forceinline__ v2f fast2_osc_win(Fast2Regs &r, const WinRegs &w, con
     fast2_frame<TAB_LDS, FILTER, EM_, TAME_, INTERP, MIXED, FMP>(r, e, r.x2, r.x1, r.y2, r.y1, SK_F2_ARGS, l1, r1);  \
     SK_REDUCE4_AND_STORE(J)                                                                              \
   }
+// the same in the folded form (EM 7: tame waves, and with MUTE_ tame waves with muted live lanes)
+#define SK_FAST2_ONE_F(J, MUTE_)                                                                         \
+  {                                                                                                      \
+    float l, rr;                                                                                         \
+    fast2_frame<TAB_LDS, FILTER, 7, true, INTERP, MIXED, FMP, MUTE_>(r, e, r.x1, r.x2, r.y1, r.y2, SK_F2_ARGS, l, rr); \
+    SK_REDUCE_AND_STORE(J)                                                                               \
+    { v2f t_ = r.x1; r.x1 = r.x2; r.x2 = t_; t_ = r.y1; r.y1 = r.y2; r.y2 = t_; }                        \
+  }
+#define SK_FAST2_PAIR_F(J, MUTE_)                                                                        \
+  {                                                                                                      \
+    float l0, r0, l1, r1;                                                                                \
+    fast2_frame<TAB_LDS, FILTER, 7, true, INTERP, MIXED, FMP, MUTE_>(r, e, r.x1, r.x2, r.y1, r.y2, SK_F2_ARGS, l0, r0); \
+    fast2_frame<TAB_LDS, FILTER, 7, true, INTERP, MIXED, FMP, MUTE_>(r, e, r.x2, r.x1, r.y2, r.y1, SK_F2_ARGS, l1, r1); \
+    SK_REDUCE4_AND_STORE(J)                                                                              \
+  }
 // Eight frames (J..J+7) with the cross-lane sum through LDS instead of the VALU: every lane parks its (L,R) of
 // 8 frames in a wave-private transposition tile xp[8][65] (one ds_write_b64 per frame, row stride 65 keeps the
 // column reads conflict-free); then lane (f = lane&7, seg = lane>>3) adds the 8 lanes of segment seg for frame f,
@@ -498,6 +558,7 @@ __device__ __forceinline__ v2f fast2_osc_win(Fast2Regs &r, const WinRegs &w, con
       xt_[q_ * SK_XT2 + lane] = fold_lr(l0, r0);                                                         \
       xt_[(q_ + 1) * SK_XT2 + lane] = fold_lr(l1, r1);                                                   \
     }                                                                                                    \
+    if ((EM_) == 7) { SK_FAST2_FOLD_SAMPLE() }   /* one packed multiply per eight frames */              \
     SK_WAVE_SYNC()                                                                                       \
     {   /* lane (f, seg) adds 8 floats of tile row f: segments 0..3 hold L pair sums, 4..7 R pair sums */ \
       const float4 *src_ = reinterpret_cast<const float4 *>(xt_ + (lane & 7) * SK_XT2 + (lane >> 3) * 8); \
@@ -616,20 +677,38 @@ __device__ __forceinline__ v2f fast2_osc_win(Fast2Regs &r, const WinRegs &w, con
   }
 // a whole chunk of cn frames in mode EM_: LDS blocks of 8 when tame, DPP pairs otherwise, single-frame tail
 #if SK_LDS_REDUCE
-#define SK_FAST2_CHUNK(EM_)                                                     \
-  {                                                                             \
-    int j = 0;                                                                  \
-    if (tame) { if (TAB_LDS) { if ((EM_) == 0 && fast2_smoother_stalled(r)) for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK(j, (EM_) == 0 ? 3 : (EM_)) \
+// fold_on (a constexpr in scope: sk_render_fast2_kernel's plain instantiations) / folded (wave-uniform, per pass): from the
+// first chunk at which the smoother has stalled, a tame (or tame_m) wave of an LDS-table bank renders every frame -- blocks
+// and ragged tail -- in the folded form, see fast2_fold_pan
+// NO3_: this instantiation folds its stalled tame waves (SK_FAST2_CHUNK), so their unfolded EM 3 blocks are never needed
+#define SK_FAST2_CHUNK_PLAIN(EM_, NO3_)                                         \
+    if (tame) { if (TAB_LDS) { if ((EM_) == 0 && !(NO3_) && fast2_smoother_stalled(r)) for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK(j, (EM_) == 0 ? 3 : (EM_)) \
                                else for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK(j, EM_) } \
                 else for (; j + 8 <= cn; j += 8) SK_FAST2_WIN_BLOCK(j, EM_)     \
                 for (; j + 1 < cn; j += 2) SK_FAST2_PAIR(j, EM_, true)          \
                 if (j < cn) SK_FAST2_ONE(j, EM_, true) }                        \
-    else      { if (tame_m && TAB_LDS) { if ((EM_) == 0 && fast2_smoother_stalled(r)) for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_M(j, (EM_) == 0 ? 3 : (EM_)) \
+    else      { if (tame_m && TAB_LDS) { if ((EM_) == 0 && !(NO3_) && fast2_smoother_stalled(r)) for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_M(j, (EM_) == 0 ? 3 : (EM_)) \
                                          else for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_M(j, EM_) } \
                 else if (FMP && TAB_LDS) { if ((EM_) == 0 && fast2_smoother_stalled(r)) for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_U(j, (EM_) == 0 ? 3 : (EM_)) \
                                            else for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_U(j, EM_) } \
                 for (; j + 1 < cn; j += 2) SK_FAST2_PAIR(j, EM_, false)         \
-                if (j < cn) SK_FAST2_ONE(j, EM_, false) }                       \
+                if (j < cn) SK_FAST2_ONE(j, EM_, false) }
+#define SK_FAST2_CHUNK(EM_)                                                     \
+  {                                                                             \
+    int j = 0;                                                                  \
+    if constexpr (fold_on && TAB_LDS && (EM_) == 0) {                           \
+      if (!folded && (tame || tame_m) && fast2_smoother_stalled(r)) { fast2_fold_pan(r); folded = true; } \
+      if (folded) {                                                             \
+        if (tame) { for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK(j, 7)        \
+                    if (j < cn) { for (; j + 1 < cn; j += 2) SK_FAST2_PAIR_F(j, false) \
+                                  if (j < cn) SK_FAST2_ONE_F(j, false)          \
+                                  SK_FAST2_FOLD_SAMPLE() } }                    \
+        else      { for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_M(j, 7)      \
+                    if (j < cn) { for (; j + 1 < cn; j += 2) SK_FAST2_PAIR_F(j, true) \
+                                  if (j < cn) SK_FAST2_ONE_F(j, true)           \
+                                  SK_FAST2_FOLD_SAMPLE() } }                    \
+      } else { SK_FAST2_CHUNK_PLAIN(EM_, true) }                                \
+    } else { SK_FAST2_CHUNK_PLAIN(EM_, false) }                                 \
   }
 #else
 #define SK_FAST2_CHUNK(EM_)                                                     \
@@ -839,12 +918,14 @@ template <bool TAB_LDS> struct Fast2Shape { static constexpr int NW = TAB_LDS ? 
 // FMP == 2 (SKM_PAIR_AP): some carrier's amplitude or pan is modulated too (by the voice after it or by itself).
 // GT: the in-place instantiation (LDS-table banks with envelopes; a.env_gain set): listed voices stay in their lanes, their
 // gains come from the rows sk_gain_kernel wrote just before on this stream.  A kernel of its own so that the steady
-// instantiation keeps its registers (it sits at 126 of 128).
+// instantiation keeps its registers (it sits at the 128 of four waves per SIMD, with two or three registers spilled once per
+// pass outside the chunk and frame loops: profiles/fold_usage_*.txt).
 // PROBE: the same kernel compiled in a translation unit with -DSK_PROBE_TU (fast2_post then also writes the probe rows of
 // skred_bank_set_probe): a template parameter only so that its instantiations are symbols of their own.
 template <bool TAB_LDS, bool FILTER, bool ENV, int INTERP, bool MIXED, int FMP = 0, bool GT = false, bool PROBE = false>
 __global__ __launch_bounds__(Fast2Shape<TAB_LDS>::NW * 64, SK_FAST2_MIN_WAVES) void sk_render_fast2_kernel(const sk_render_args_t a) {
   constexpr int NW = Fast2Shape<TAB_LDS>::NW;
+  constexpr bool fold_on = !GT;      // the in-place instantiation keeps its frames as they are
   SK_FAST2_PROLOGUE()
   (void)n_flags;
   // GT: per wave, behind the tiles: gtile[8][SK_GT_RANKS] (the listed voices' gains of one 8-frame block) and
@@ -875,6 +956,8 @@ __global__ __launch_bounds__(Fast2Shape<TAB_LDS>::NW * 64, SK_FAST2_MIN_WAVES) v
     r.probe_any = __any(r.probe[0] != nullptr || r.probe[1] != nullptr);
 #endif
     bool wave_ok = true;
+    bool folded = false;              // the wave renders folded frames from here on (SK_FAST2_CHUNK)
+    (void)folded;
     r.lst[0] = r.lst[1] = false; r.gt = (v2f){0.0f, 0.0f};
     int grank[2] = {0, 0};            // GT: the lane's listed voices' numbers within the wave (ascending voice order)
     int gcnt = 0;                     // GT: listed voices of the wave
@@ -991,6 +1074,9 @@ __global__ __launch_bounds__(Fast2Shape<TAB_LDS>::NW * 64, SK_FAST2_MIN_WAVES) v
 template <bool TAB_LDS, bool FILTER, int INTERP, bool MIXED, int FMP = 0, bool PROBE = false>
 __global__ __launch_bounds__(SK_GROUP, SK_ENV2_MIN_WAVES) void sk_render_env2_kernel(const sk_render_args_t a) {
   constexpr int NW = 4;              // always 512 voices per pass: its register budget allows 3 waves per SIMD anyway
+  constexpr bool fold_on = false;    // (SK_FAST2_CHUNK: the folded frames are sk_render_fast2_kernel's)
+  bool folded = false;
+  (void)folded;
   // the listed voices in ascending order (sk_collect_scan_kernel + sk_collect_expand_kernel, just before on this stream):
   // every workgroup pass takes 512 of them, so the launch costs what those voices cost; the grid is what the device holds at
   // once (a grid of more rendering workgroups than fit runs in rounds, the last one mostly empty) and strides over the passes
