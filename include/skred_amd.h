@@ -535,6 +535,73 @@ int  skred_bank_note_on_idle(skred_bank_t *bank, const skred_idle_query_t *q, co
 int  skred_bank_stamp_list(skred_bank_t *bank, const int32_t *d_voices, int n, const uint32_t *d_count_or_null,
                            uint32_t stamps, void *stream);
 
+/* ---- voice stealing: the sounding voices that matter least, ranked on the device ------------------------------------------
+ *
+ * When the idle list is shorter than a batch of notes, a polyphonic synthesizer takes the voice that matters least: the one
+ * released longest ago, then the one held longest, or the quietest.  Everything such a policy reads is on the device, current at
+ * every point of the stream: sample_start and sample_release (written by the stamp and note kernels), is_active (cleared by the
+ * render kernels), the amp smoother's running gain, the named set.  The query ranks the candidates of a range by a 64-bit key
+ * and leaves the first max_out of them in device memory, on the caller's stream, without a host wait.
+ *
+ * The definition, on the fields AS THE DEVICE HOLDS THEM at that point of the stream; every comparison is exact.  `now` is
+ * synth_sample_count as the bank has it at application time (the value the stamps use).
+ *   released  := sample_release != 0
+ *   age       := sample_start > now ? 0 : now - sample_start
+ *   candidate := inside the range && voice_use_amp_envelope != 0 && is_active != 0 && age >= min_age
+ *                && (released, with RELEASED_ONLY) && (not in the named set, with UNNAMED)
+ *                && the voice does NOT satisfy the idle predicate of (exclude_idle, settle_level) -- skred_bank_find_idle's,
+ *                   criteria and SKRED_IDLE_UNNAMED restriction as there; exclude_idle == 0 excludes nobody
+ *   class     := 0 when RELEASED_FIRST is set and the voice is released, else 1
+ *   primary   := OLDEST: sample_release of a class-0 voice, sample_start otherwise;
+ *                QUIETEST: the bits of fabsf(voice_smoother_gain) when voice_smoother_enable != 0, else 0x7fffffff
+ *   key       := class << 62 | min(primary, 2^62 - 1)
+ * Victim order: ascending key, ties by ascending voice index.  Padding voices and voices without a table follow the same rules. */
+#define SKRED_STEAL_MAX 1024
+enum { SKRED_STEAL_OLDEST = 0, SKRED_STEAL_QUIETEST = 1 };          /* policy */
+enum { SKRED_STEAL_RELEASED_FIRST = 1u << 0,   /* voices in release rank ahead of held ones */
+       SKRED_STEAL_RELEASED_ONLY  = 1u << 1,   /* held voices are not candidates */
+       SKRED_STEAL_UNNAMED        = 1u << 8 }; /* as SKRED_IDLE_UNNAMED */
+typedef struct skred_steal_query {
+  int32_t  first, count;     /* voice range */
+  uint32_t policy, flags;
+  uint64_t min_age;          /* frames: younger notes are protected */
+  uint32_t exclude_idle;     /* SKRED_IDLE_* criteria (0: none): voices these call idle are not candidates */
+  float    settle_level;     /* for exclude_idle's ENV_DONE */
+  int32_t  max_out;          /* 0 .. SKRED_STEAL_MAX; 0: count only */
+  int32_t  reserved;         /* 0 */
+} skred_steal_query_t;
+
+/* Pure host, no device: SKRED_OK, or SKRED_E_BAD_ARG for a NULL query, an unknown policy, unknown bits in flags or exclude_idle,
+ * reserved != 0, max_out outside [0, SKRED_STEAL_MAX], a settle_level that is negative or not finite; SKRED_E_RANGE for
+ * count <= 0 or a range outside a bank of n_voices voices.  The entry points below call it before anything touches the device. */
+int  skred_steal_check(const skred_steal_query_t *q, int n_voices);
+
+/* Asynchronous on `stream`, ordered after the renders and updates queued on it.  Writes the first min(total, max_out) voices of
+ * the victim order into d_voices, d_count[0] = written, d_count[1] = total candidates (device memory).  Entries of d_voices past
+ * `written` are not touched.  Reads the bank only: state, globals, mix, reports and counters of every later block are
+ * bit-identical to the same blocks without the query; the same state gives the same bytes.  A radix select over the keys: nine
+ * launches whatever the data (one with max_out == 0), no workgroup ever waits for another; with UNNAMED (here or in
+ * exclude_idle) one more when the routing changed.  The bank owns the scratch (8 bytes per voice, allocated by the first
+ * query): issue the queries of one bank on one stream at a time, as its renders.
+ * Refused before anything touches the device: what skred_steal_check refuses, and SKRED_E_BAD_ARG for a NULL bank, query or
+ * d_count, or a NULL d_voices with max_out > 0.  On a shard: through skred_shard_bank(), with that rank's local indices.  Not
+ * in the fixed-point bank or the drop-in mode. */
+int  skred_bank_find_steal(skred_bank_t *bank, const skred_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only.  Returns `written` (>= 0) or a SKRED_E_* code; *total_out may be NULL. */
+int  skred_bank_find_steal_host(skred_bank_t *bank, const skred_steal_query_t *q, int32_t *voices, int *total_out, void *stream);
+/* A batch of notes on a bank whose polyphony may be used up, all on the device: the idle query `idle_q` into scratch the bank
+ * owns (max_out = n; SKRED_IDLE_AMP_ZERO is refused as in skred_bank_note_on_idle), the steal query `steal_q` with
+ * exclude_idle = idle_q->which, settle_level = idle_q->settle_level and max_out = min(n, SKRED_STEAL_MAX) (the library overrides
+ * those three fields; because of the exclusion the two lists are disjoint), the victims appended behind the idle entries, and the
+ * notes placed on the joined list as skred_bank_notes_on_list places them, first_entry = 0: idle voices take the first notes,
+ * victims the next, in victim order; what is left is dropped.  A stolen voice gets exactly a note-on's stores: it is re-triggered
+ * with the new pitch and velocity, its filter memory and smoother carry on.
+ * d_result (device, uint32[3], required): [0] placed, [1] dropped, [2] how many of the placed notes went to stolen voices;
+ * d_assigned as for skred_bank_notes_on_list.  The host never learns the counts.  n == 0: SKRED_OK, nothing is done.
+ * Refusals: those of skred_bank_note_on_idle and of skred_bank_find_steal, before anything touches the device. */
+int  skred_bank_note_on_steal(skred_bank_t *bank, const skred_idle_query_t *idle_q, const skred_steal_query_t *steal_q,
+                              const skred_note_t *notes, int n, int32_t *d_assigned, uint32_t *d_result, void *stream);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

@@ -40,6 +40,20 @@ int sk_idle_check(const skred_bank_t *b, const skred_idle_query_t *q, const void
   return SKRED_OK;
 }
 
+/* the named set, rebuilt on `s` when the routing changed since it was built (shared with skred_bank_steal.c) */
+int sk_named_ensure(skred_bank_t *b, hipStream_t s) {
+  if (!b->d_named) {
+    HIP_TRY(hipMalloc((void **)&b->d_named, (size_t)(b->n_padded / 64) * sizeof(uint64_t)));
+    b->named_dirty = 1;
+  }
+  if (b->named_dirty) {
+    const hipError_t e = (hipError_t)sk_launch_named(b->d_ro[SKP_TAB], b->d_ro[SKP_MODI], b->n_padded, b->n_voices, b->d_named, s);
+    if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "named-set launch -> %s", hipGetErrorString(e));
+    b->named_dirty = 0;
+  }
+  return SKRED_OK;
+}
+
 static int idle_launch(skred_bank_t *b, const skred_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
   HIP_TRY(hipSetDevice(b->device));
   if (!b->d_idle) {
@@ -50,15 +64,8 @@ static int idle_launch(skred_bank_t *b, const skred_idle_query_t *q, int32_t *d_
     HIP_TRY(hipMemsetAsync(b->d_idle, 0, (size_t)SK_IDLE_W_COUNT * sizeof(uint32_t), s));   /* the ticket: zero once, re-armed by every last arriver */
   }
   if (q->which & SKRED_IDLE_UNNAMED) {
-    if (!b->d_named) {
-      HIP_TRY(hipMalloc((void **)&b->d_named, (size_t)(b->n_padded / 64) * sizeof(uint64_t)));
-      b->named_dirty = 1;
-    }
-    if (b->named_dirty) {
-      const hipError_t e = (hipError_t)sk_launch_named(b->d_ro[SKP_TAB], b->d_ro[SKP_MODI], b->n_padded, b->n_voices, b->d_named, s);
-      if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "named-set launch -> %s", hipGetErrorString(e));
-      b->named_dirty = 0;
-    }
+    const int rc = sk_named_ensure(b, s);
+    if (rc) return rc;
   }
   sk_idle_args_t a;
   memset(&a, 0, sizeof(a));

@@ -1,6 +1,6 @@
 /*
  * skred_bank_notes.c -- note-ons and stamps on voices that a list in device memory names (include/skred_amd.h:
- * skred_notes_check, skred_bank_notes_on_list / _note_on_idle / _stamp_list).
+ * skred_notes_check, skred_bank_notes_on_list / _note_on_idle / _note_on_steal / _stamp_list).
  *
  * The host side of skred_note_kernels.hip: the checks (made before anything touches the device), the notes' way through the
  * staging ring of the update path, the launches, and the list skred_bank_note_on_idle's query leaves for its placement.
@@ -23,7 +23,7 @@ _Static_assert(sizeof(skred_note_t) == sizeof(sk_note_t) && sizeof(skred_note_t)
 _Static_assert(SK_NOTE_SET_PHASE == SKRED_NOTE_SET_PHASE && SK_NOTE_SET_PAN == SKRED_NOTE_SET_PAN,
                "device note flags must equal the public SKRED_NOTE_* values");
 
-#define SK_NOTE_LIST_WORDS 4       /* in front of the list: the query's two counts, padded to 16 bytes */
+#define SK_NOTE_LIST_WORDS 4       /* in front of the list: the query's two counts, the joined list's length (note_on_steal), padded to 16 bytes */
 
 void sk_notes_free(skred_bank_t *b) {
   if (b->d_note_list) hipFree(b->d_note_list);
@@ -83,6 +83,18 @@ int skred_bank_notes_on_list(skred_bank_t *b, const skred_note_t *notes, int n, 
   return notes_launch(b, notes, n, d_voices, d_count, first_entry, d_assigned, d_result, (hipStream_t)stream);
 }
 
+/* room for n entries in the bank's own list */
+static int note_list_room(skred_bank_t *b, int n) {
+  if ((size_t)n <= b->note_list_cap) return SKRED_OK;
+  /* (hipFree waits for the device: no earlier placement still reads the old list) */
+  sk_notes_free(b);
+  size_t cap = 1024;
+  while (cap < (size_t)n) cap *= 2;
+  HIP_TRY(hipMalloc((void **)&b->d_note_list, (SK_NOTE_LIST_WORDS + cap) * sizeof(uint32_t)));
+  b->note_list_cap = cap;
+  return SKRED_OK;
+}
+
 int skred_bank_note_on_idle(skred_bank_t *b, const skred_idle_query_t *q, const skred_note_t *notes, int n, int32_t *d_assigned,
                             uint32_t *d_result, void *stream) {
   if (!b || !q || !notes || !d_result) return fail(SKRED_E_BAD_ARG, "note_on_idle: no bank, query, notes or result");
@@ -97,18 +109,43 @@ int skred_bank_note_on_idle(skred_bank_t *b, const skred_idle_query_t *q, const 
   if ((rc = skred_notes_check(notes, n))) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((size_t)n > b->note_list_cap) {
-    /* (hipFree waits for the device: no earlier placement still reads the old list) */
-    sk_notes_free(b);
-    size_t cap = 1024;
-    while (cap < (size_t)n) cap *= 2;
-    HIP_TRY(hipMalloc((void **)&b->d_note_list, (SK_NOTE_LIST_WORDS + cap) * sizeof(uint32_t)));
-    b->note_list_cap = cap;
-  }
+  if ((rc = note_list_room(b, n))) return rc;
   uint32_t *d_count = b->d_note_list;
   int32_t *d_list = (int32_t *)(b->d_note_list + SK_NOTE_LIST_WORDS);
   if ((rc = skred_bank_find_idle(b, &qq, d_list, d_count, stream))) return rc;
   return notes_launch(b, notes, n, d_list, d_count, 0, d_assigned, d_result, s);
+}
+
+int skred_bank_note_on_steal(skred_bank_t *b, const skred_idle_query_t *idle_q, const skred_steal_query_t *steal_q,
+                             const skred_note_t *notes, int n, int32_t *d_assigned, uint32_t *d_result, void *stream) {
+  if (!b || !idle_q || !steal_q || !notes || !d_result) return fail(SKRED_E_BAD_ARG, "note_on_steal: no bank, query, notes or result");
+  if (n < 0) return fail(SKRED_E_BAD_ARG, "note_on_steal: n = %d", n);
+  if (idle_q->which & SKRED_IDLE_AMP_ZERO)
+    return fail(SKRED_E_BAD_ARG, "note_on_steal: SKRED_IDLE_AMP_ZERO -- a note-on leaves voice_amp alone: the voice would stay silent and be listed again");
+  skred_idle_query_t iq = *idle_q;
+  iq.max_out = n;
+  skred_steal_query_t sq = *steal_q;
+  sq.exclude_idle = idle_q->which;
+  sq.settle_level = idle_q->settle_level;
+  sq.max_out = n < SKRED_STEAL_MAX ? n : SKRED_STEAL_MAX;
+  int rc = sk_idle_check(b, &iq, b, b, "note_on_steal");   /* (the lists and the counts go into the bank's own scratch) */
+  if (rc) return rc;
+  if ((rc = sk_steal_check_bank(b, &sq, b, b, "note_on_steal"))) return rc;
+  if (n == 0) return SKRED_OK;
+  if ((rc = skred_notes_check(notes, n))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(b->device));
+  if ((rc = note_list_room(b, n))) return rc;
+  uint32_t *d_idle_count = b->d_note_list, *d_joined = b->d_note_list + 2;
+  int32_t *d_list = (int32_t *)(b->d_note_list + SK_NOTE_LIST_WORDS);
+  if ((rc = skred_bank_find_idle(b, &iq, d_list, d_idle_count, stream))) return rc;
+  if ((rc = sk_steal_into_scratch(b, &sq, s))) return rc;
+  /* the victims behind the idle entries, as far as the batch reaches; d_result[2]: the notes that will land on them (every entry
+   * of the joined list names a voice, and the list is no longer than the batch) */
+  const hipError_t e = (hipError_t)sk_launch_list_append(d_list, d_idle_count, b->d_steal_out + 2, (const uint32_t *)b->d_steal_out, n,
+                                                         d_joined, d_result + 2, s);
+  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "list append launch -> %s", hipGetErrorString(e));
+  return notes_launch(b, notes, n, d_list, d_joined, 0, d_assigned, d_result, s);
 }
 
 int skred_bank_stamp_list(skred_bank_t *b, const int32_t *d_voices, int n, const uint32_t *d_count_or_null, uint32_t stamps,

@@ -2,7 +2,7 @@
  * skred_bank_priv.h -- internals shared by the translation units behind include/skred_amd.h
  * (skred_bank.c: lifecycle, tables, upload / download, options, class and tape plan; skred_bank_render.c:
  * one block from request to kernels, as skred_bank_plan.c picks them; skred_bank_update.c: block-granular
- * updates and the deferred queue; skred_bank_idle.c: the free-voice query; skred_bank_notes.c: note-ons and stamps on voices a
+ * updates and the deferred queue; skred_bank_idle.c: the free-voice query; skred_bank_steal.c: the victim query; skred_bank_notes.c: note-ons and stamps on voices a
  * device-resident list names).  Not installed.
  */
 #ifndef SKRED_BANK_PRIV_H
@@ -180,8 +180,14 @@ struct skred_bank {
   int32_t *h_idle_out;
   size_t idle_out_cap;              /* entries of the list */
   /* skred_bank_note_on_idle (skred_bank_notes.c): the list its query leaves for its placement, allocated on first use */
-  uint32_t *d_note_list;            /* [4] words (the query's d_count in the first two), then note_list_cap voice indices */
+  uint32_t *d_note_list;            /* [4] words (the query's d_count in the first two; skred_bank_note_on_steal: the joined list's length
+                                       in the third), then note_list_cap voice indices */
   size_t note_list_cap;
+  /* voice stealing (skred_bank_steal.c), everything allocated on first use */
+  uint32_t *d_steal;                /* the radix select's scratch (skred_launch.h: SK_STEAL_W_*, histogram, counts, offsets, winners, keys) */
+  int steal_wgs;
+  int32_t *d_steal_out;             /* [2] counts, then SK_STEAL_MAX victims: skred_bank_find_steal_host's list and skred_bank_note_on_steal's */
+  int32_t *h_steal_out;             /* ... its pinned twin */
 };
 
 /* per-voice classification (host shadow) */
@@ -243,6 +249,13 @@ int sk_bank_master_pp(skred_bank_t *b, const float *d_sum, int num_frames, int n
 void sk_queue_free(skred_bank_t *b);
 void sk_patterns_free(skred_bank_t *b);
 void sk_idle_free(skred_bank_t *b);          /* skred_bank_idle.c: the query's scratch (skred_bank_destroy) */
+void sk_steal_free(skred_bank_t *b);         /* skred_bank_steal.c: the victim query's scratch (skred_bank_destroy) */
+/* skred_bank_idle.c: the named set is current on `s` (allocated and rebuilt when the routing changed) */
+int sk_named_ensure(skred_bank_t *b, hipStream_t s);
+/* skred_bank_steal.c, for skred_bank_note_on_steal: the query's checks (`voices`: where the list would go), and the query into the
+ * bank's own d_steal_out (counts in its first two words) */
+int sk_steal_check_bank(const skred_bank_t *b, const skred_steal_query_t *q, const void *voices, const void *count, const char *who);
+int sk_steal_into_scratch(skred_bank_t *b, const skred_steal_query_t *q, hipStream_t s);
 void sk_notes_free(skred_bank_t *b);         /* skred_bank_notes.c: the list scratch of skred_bank_note_on_idle (skred_bank_destroy) */
 /* skred_bank_idle.c: everything skred_bank_find_idle refuses, without the device (`voices` / `count`: where the list and the
  * counts would go; `who` names the caller in the error text) */

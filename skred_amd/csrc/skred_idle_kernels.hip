@@ -23,29 +23,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "skred_idle_common.hpp"   // sk_idle_pred: the predicate of one voice
 #include "skred_kernel_common.hpp"
 #include "skred_launch.h"
 
 #define SK_IDLE_WAVES (SK_IDLE_SPAN / 64)
-
-// the predicate of one voice (v inside the padded bank; `in_range`: inside the query's range)
-__device__ __forceinline__ bool sk_idle_pred(const sk_idle_args_t &a, int v, bool in_range) {
-  if (!in_range) return false;
-  const uint32_t which = a.which;   // wave-uniform: the branches below are scalar
-  bool idle = false;
-  uint32_t rwf = 0;
-  if (which & (SK_IDLE_FINISHED | SK_IDLE_ENV_DONE)) rwf = a.filt[v].w[3];
-  if (which & SK_IDLE_FINISHED) idle = (rwf & SKR_FINISHED) != 0;
-  if (which & SK_IDLE_ENV_DONE) {
-    const uint32_t flags = a.tab[v].w[2];
-    const float gain = __uint_as_float(a.osc_rw[v].w[1]);
-    const bool settled = !(flags & SKF_SMOOTH) || fabsf(gain) <= a.settle_level;
-    idle = idle || ((flags & SKF_USE_ENV) && !(rwf & SKR_ENV_ACTIVE) && settled);
-  }
-  if (which & SK_IDLE_AMP_ZERO) idle = idle || __uint_as_float(a.osc_ro[v].w[3]) == 0.0f;
-  if (which & SK_IDLE_UNNAMED) idle = idle && !((a.named[v >> 6] >> (v & 63)) & 1);
-  return idle;
-}
 
 __device__ __forceinline__ int sk_idle_voice(const sk_idle_args_t &a, bool &in_range) {
   const int v = a.base + (int)blockIdx.x * SK_IDLE_SPAN + (int)threadIdx.x;   // base: `first` rounded down to 64

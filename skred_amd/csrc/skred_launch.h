@@ -13,10 +13,11 @@
  *   skred_rec_kernels.hip     sk_launch_rec_minmax, sk_rec_partial_floats, sk_launch_rec_convert
  *   skred_idle_kernels.hip    sk_launch_idle, sk_idle_workgroups, sk_launch_named
  *   skred_note_kernels.hip    sk_launch_notes, sk_launch_stamp_list
+ *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_list_append
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
- * skred_bank_notes.c and skred_recorder.c.
+ * skred_bank_steal.c, skred_bank_notes.c and skred_recorder.c.
  */
 #ifndef SKRED_LAUNCH_H
 #define SKRED_LAUNCH_H
@@ -137,6 +138,54 @@ int sk_launch_notes(const sk_note_t *d_notes, int n, const int32_t *d_voices, co
 int sk_launch_stamp_list(const int32_t *d_voices, int n, const uint32_t *d_count, int n_voices, uint32_t dirty,
                          sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask,
                          hipStream_t stream);
+
+/* ---- voice stealing (skred_bank_steal.c -> skred_steal_kernels.hip; include/skred_amd.h: skred_bank_find_steal) ----
+ * The k = min(max_out, candidates) smallest 64-bit keys of a range, ties by voice index: a most-significant-digit radix select
+ * over SK_STEAL_DIGITS digits of SK_STEAL_BITS bits, an index-ordered count and scatter of the winners, and a sort of the at most
+ * SK_STEAL_MAX winners by one workgroup.  The policy and flag bits equal SKRED_STEAL_* (checked in skred_bank_steal.c). */
+#define SK_STEAL_MAX 1024
+#define SK_STEAL_OLDEST 0u
+#define SK_STEAL_QUIETEST 1u
+#define SK_STEAL_RELEASED_FIRST (1u << 0)
+#define SK_STEAL_RELEASED_ONLY  (1u << 1)
+#define SK_STEAL_UNNAMED        (1u << 8)
+#define SK_STEAL_BITS 11
+#define SK_STEAL_BINS (1 << SK_STEAL_BITS)
+#define SK_STEAL_DIGITS 6          /* 6 * 11 = 66 >= 64: the first digit holds the key's top 9 bits */
+#define SK_STEAL_NOKEY (~0ull)     /* what a voice that is no candidate holds in `keys` (a key never has bit 63) */
+/* the bank's scratch: SK_STEAL_W_COUNT words (zeroed once; every last arriver re-arms what it used), the digit histogram
+ * (SK_STEAL_BINS words, zero between launches), four arrays of one word per workgroup (counts and exclusive offsets of the keys
+ * below / equal to the threshold), the winners (SK_STEAL_MAX keys, then SK_STEAL_MAX voices), and one key per voice of the spans */
+enum { SK_STEAL_W_TICKET = 0,     /* arrival ticket, shared by the launches of a query (they follow one another on the stream) */
+       SK_STEAL_W_TOTAL,          /* candidates of the range */
+       SK_STEAL_W_K,              /* min(max_out, total): how many the list will hold */
+       SK_STEAL_W_REMAIN,         /* ... of them, how many lie in the histogram bin the digits so far select */
+       SK_STEAL_W_PREFIX_LO,      /* the digits fixed so far (after the last digit pass: the threshold key) */
+       SK_STEAL_W_PREFIX_HI,
+       SK_STEAL_W_COUNT = 8 };
+typedef struct {
+  sk_idle_args_t idle;             /* the exclusion: planes, named set, which = exclude_idle, settle_level (first / end as below) */
+  const sk_plane_t *env_s;         /* SKP_ENV_S: sample_start, sample_release */
+  uint32_t *words, *hist;
+  uint32_t *cnt_lt, *cnt_eq, *off_lt, *off_eq;
+  unsigned long long *win_keys;    /* [SK_STEAL_MAX] */
+  int32_t *win_voices;             /* [SK_STEAL_MAX] */
+  unsigned long long *keys;        /* [workgroups * SK_IDLE_SPAN] */
+  int32_t *d_voices;
+  uint32_t *d_count;
+  uint64_t now, min_age;
+  int32_t first, end, base;        /* the range [first, end); base: filled by sk_launch_steal (first rounded down to 64) */
+  int32_t max_out;
+  uint32_t policy, flags;
+  int32_t digit;                   /* filled by sk_launch_steal: which digit a histogram launch counts */
+} sk_steal_args_t;
+/* the keys and the first digit's histogram; SK_STEAL_DIGITS - 1 further digit launches; count; scatter; sort (one workgroup, writes
+ * d_voices and d_count): SK_STEAL_DIGITS + 3 launches whatever the data.  max_out == 0: the first launch alone, which writes d_count */
+int sk_launch_steal(const sk_steal_args_t *args, hipStream_t stream);
+/* dst[at + t] = src[t] for t < min(src_count[0], room - at), at = dst_count[0] (<= room); out_count[0] = at + copied;
+ * stolen[0] = copied.  One workgroup: room - at is at most SK_STEAL_MAX entries (src holds no more) */
+int sk_launch_list_append(int32_t *dst, const uint32_t *dst_count, const int32_t *src, const uint32_t *src_count, int room,
+                          uint32_t *out_count, uint32_t *stolen, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

@@ -37,9 +37,10 @@ ABI_SYMBOLS = [
     "skred_bank_seq", "skred_bank_set_sample_rate", "skred_bank_pattern_step_set", "skred_bank_pattern_step_clear",
     "skred_bank_find_idle", "skred_bank_find_idle_host",
     "skred_bank_notes_on_list", "skred_bank_note_on_idle", "skred_bank_stamp_list",
+    "skred_bank_find_steal", "skred_bank_find_steal_host", "skred_bank_note_on_steal",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
-HOST_ABI_SYMBOLS = ["skred_notes_check"]
+HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -53,6 +54,24 @@ class IdleQueryC(C.Structure):
     """ctypes image of ``skred_idle_query_t``."""
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("which", C.c_uint32), ("settle_level", C.c_float),
                 ("start", C.c_int32), ("max_out", C.c_int32)]          # `start`: the header's `from`
+
+# SKRED_STEAL_* (skred_bank_find_steal)
+STEAL_MAX = 1024
+STEAL_OLDEST, STEAL_QUIETEST = 0, 1
+STEAL_RELEASED_FIRST, STEAL_RELEASED_ONLY, STEAL_UNNAMED = 1, 2, 256
+
+
+class StealQueryC(C.Structure):
+    """ctypes image of ``skred_steal_query_t`` (40 bytes)."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("policy", C.c_uint32), ("flags", C.c_uint32),
+                ("min_age", C.c_uint64), ("exclude_idle", C.c_uint32), ("settle_level", C.c_float),
+                ("max_out", C.c_int32), ("reserved", C.c_int32)]
+
+
+def steal_query(first: int, count: int, policy: int = STEAL_OLDEST, flags: int = 0, min_age: int = 0, exclude_idle: int = 0,
+                settle_level: float = 0.0, max_out: int = 0) -> StealQueryC:
+    return StealQueryC(int(first), int(count), int(policy), int(flags), int(min_age), int(exclude_idle), float(settle_level),
+                       int(max_out), 0)
 
 # SKRED_NOTE_* (skred_bank_notes_on_list)
 NOTE_SET_PHASE, NOTE_SET_PAN = 1, 2
@@ -159,6 +178,10 @@ def load() -> C.CDLL:
     L.skred_bank_notes_on_list.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.skred_bank_note_on_idle.argtypes = [vp, C.POINTER(IdleQueryC), vp, i32, vp, vp, vp]
     L.skred_bank_stamp_list.argtypes = [vp, vp, i32, vp, C.c_uint32, vp]
+    L.skred_steal_check.argtypes = [C.POINTER(StealQueryC), i32]
+    L.skred_bank_find_steal.argtypes = [vp, C.POINTER(StealQueryC), vp, vp, vp]
+    L.skred_bank_find_steal_host.argtypes = [vp, C.POINTER(StealQueryC), vp, C.POINTER(i32), vp]
+    L.skred_bank_note_on_steal.argtypes = [vp, C.POINTER(IdleQueryC), C.POINTER(StealQueryC), vp, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -173,6 +196,11 @@ def notes_check(notes) -> int:
     """skred_notes_check: 0, or SKRED_E_BAD_ARG (-2) for a note the bank entry points would refuse.  Pure host, no device."""
     arr = note_array(notes)
     return int(load().skred_notes_check(C.cast(arr, C.c_void_p), len(arr)))
+
+
+def steal_check(q: StealQueryC, n_voices: int) -> int:
+    """skred_steal_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for a query the bank entry points would refuse.  Pure host."""
+    return int(load().skred_steal_check(C.byref(q) if q is not None else None, int(n_voices)))
 
 
 class DeviceBank:
@@ -340,6 +368,30 @@ class DeviceBank:
         entries outside the bank -- the -1 of a dropped note -- are skipped."""
         _check(self.L.skred_bank_stamp_list(self.h, d_voices or None, int(n), d_count or None, int(stamps), stream or None),
                "skred_bank_stamp_list")
+
+    # ---- voice stealing (include/skred_amd.h: skred_bank_find_steal / _find_steal_host / skred_bank_note_on_steal) ----
+    def find_steal(self, q: StealQueryC, d_voices: int = 0, d_count: int = 0, stream: int = 0):
+        """Asynchronous on `stream`: the first q.max_out candidates of the victim order (ascending key, ties by voice index) into
+        d_voices[0 .. written) (int32, device memory); d_count[0] = written, d_count[1] = total candidates (uint32)."""
+        _check(self.L.skred_bank_find_steal(self.h, C.byref(q), d_voices or None, d_count or None, stream or None),
+               "skred_bank_find_steal")
+
+    def find_steal_host(self, q: StealQueryC, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the victims, total candidates)."""
+        out = np.empty(max(int(q.max_out), 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_bank_find_steal_host(self.h, C.byref(q), out.ctypes.data if q.max_out > 0 else None, C.byref(total),
+                                              stream or None)
+        if n < 0:
+            _check(n, "skred_bank_find_steal_host")
+        return out[:n].copy(), int(total.value)
+
+    def note_on_steal(self, notes, idle_q: IdleQueryC, steal_q: StealQueryC, d_assigned: int = 0, d_result: int = 0, stream: int = 0):
+        """The idle query, the steal query (exclude_idle, settle_level and max_out overridden by the library), the victims appended
+        behind the idle entries and the placement of the notes, in one call; d_result[0..3) = placed, dropped, stolen (uint32)."""
+        arr = note_array(notes)
+        _check(self.L.skred_bank_note_on_steal(self.h, C.byref(idle_q), C.byref(steal_q), C.cast(arr, C.c_void_p), len(arr),
+                                               d_assigned or None, d_result or None, stream or None), "skred_bank_note_on_steal")
 
     def force_generic(self, on: bool = True):
         _check(self.L.skred_bank_set_option(self.h, 1, int(on)), "skred_bank_set_option")

@@ -20,6 +20,10 @@
              launches between an event pair (every criterion, UNNAMED off and on, max_out 1 024; median and minimum of 50), beside one
              512-frame block of the same bank; (b) what a host does for the same answer without it: skred_bank_download of the bank
              plus the predicate in numpy
+  steal      voice stealing on a 2^20-voice c2 bank whose polyphony is used up but for 64 idle voices, a burst of 256 notes: (a)
+             skred_bank_note_on_steal between an event pair (median, minimum and maximum of 12; nothing is waited for); (b) the only
+             way without it: skred_bank_download of the bank, the victim order in numpy, skred_bank_update -- host-held time, and the
+             stream time of the update alone; (c) skred_bank_find_steal alone at max_out 0 (its first launch), 16 and 1 024
   cz         CZ phase distortion on the one-voice kernel (SKRED_OPT_CZ_FAST): one 512-frame block at 2^20 and 2^16 voices of (a) the C2
              recipe with `c1,0.5` on every voice, (b) a three-voice group shaped like 42.sk's v0-v2 (`v0 c1,0.5 C2,0.5 F1,1`, v1 and
              v2 `m1` modulators above it) tiled over the bank, each with the option 0 and 1.  Run from a directory that holds an
@@ -336,6 +340,94 @@ def idle():
         db.close()
 
 
+def steal():
+    D = device
+    n, F, K, IDLE = 1 << 20, 512, 256, 64
+    bank, tables, g = banks.bank_c2(n)
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.upload(bank); db.set_globals(g); db.kernel_timing(1)
+    out = torch.zeros(F, 2, device="cuda")
+    for _ in range(3):
+        db.render_mix(F, out.data_ptr(), 2)
+    torch.cuda.synchronize()
+    block_ms = db.last_render_ms()
+    free = (np.arange(IDLE, dtype=np.int32) * 16381 + 5) % n           # the 64 voices that are idle ahead of every burst
+    rest = bank.copy()
+    rest["voice_amp_envelope"]["is_active"][free] = 0
+    rest["voice_smoother_gain"][free] = 0.0
+    which = D.IDLE_FINISHED | D.IDLE_ENV_DONE
+    notes = D.note_array([D.NoteC(0.4 + 0.001 * k, 0.8, 0.0, 0.5, 0.5, D.NOTE_SET_PHASE) for k in range(K)])
+    iq = D.IdleQueryC(0, n, which, 1e-3, 0, 0)
+    sq = D.steal_query(0, n, D.STEAL_OLDEST, D.STEAL_RELEASED_FIRST, 64)
+    da = torch.full((K,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+
+    def make_idle():
+        db.update(rest, free, D.DIRTY_ENV_STATE | D.DIRTY_SMOOTHER)
+        torch.cuda.synchronize()
+
+    ms = []
+    for it in range(3 + 12):                                             # three warm-up bursts, then the twelve that count
+        make_idle()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        db.note_on_steal(notes, iq, sq, da.data_ptr(), dr.data_ptr())
+        e1.record()
+        e1.synchronize()
+        if it >= 3:
+            ms.append(e0.elapsed_time(e1))
+    res = dr.cpu().numpy().tolist()
+    print(f"c2 {n} note_on_steal, {K} notes, {IDLE} idle voices, OLDEST | RELEASED_FIRST, min_age 64: stream time median {np.median(ms):.4f} ms, "
+          f"min {np.min(ms):.4f}, max {np.max(ms):.4f} of {len(ms)} (placed, dropped, stolen = {res}); nothing waited for; "
+          f"one {F}-frame block of this bank: {block_ms:.4f} ms")
+    got = bank.copy()
+    held, upd = [], []
+    for it in range(2 + 12):
+        make_idle()
+        t0 = time.perf_counter()
+        db.download(got)
+        a, e = got.a, got.a["voice_amp_envelope"]
+        now = int(db.get_globals().synth_sample_count)
+        idle = np.flatnonzero((a["voice_finished"] != 0) | ((a["voice_use_amp_envelope"] != 0) & (e["is_active"] == 0) &
+                              ((a["voice_smoother_enable"] == 0) | (np.abs(a["voice_smoother_gain"]) <= np.float32(1e-3)))))[:K]
+        start, release = bank["voice_amp_envelope"]["sample_start"], bank["voice_amp_envelope"]["sample_release"]   # (the host's own clocks)
+        cand = (a["voice_use_amp_envelope"] != 0) & (e["is_active"] != 0) & (np.uint64(now) - np.minimum(start, np.uint64(now)) >= np.uint64(64))
+        cand[idle] = False
+        key = np.where(release != 0, release, start | np.uint64(1 << 62))
+        c = np.flatnonzero(cand)
+        part = c[np.argpartition(key[c], K)[:K]] if len(c) > K else c
+        victims = part[np.lexsort((part, key[part]))]
+        picks = np.concatenate([idle, victims])[:K].astype(np.int32)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        db.update(bank, picks, D.DIRTY_PARAMS | D.DIRTY_PHASE | D.STAMP_TRIGGER)
+        e1.record()
+        dt = time.perf_counter() - t0
+        e1.synchronize()
+        if it >= 2:
+            held.append(dt * 1e3)
+            upd.append(e0.elapsed_time(e1))
+    print(f"c2 {n} the same notes without it: skred_bank_download of the bank (waits for the device) + the victim order in numpy + "
+          f"skred_bank_update of {len(picks)} voices: host held median {np.median(held):.3f} ms, min {np.min(held):.3f}, max {np.max(held):.3f} "
+          f"of {len(held)}; the update's stream time median {np.median(upd):.4f} ms")
+    dv = torch.full((D.STEAL_MAX,), -1, dtype=torch.int32, device="cuda")
+    dc = torch.zeros(2, dtype=torch.int32, device="cuda")
+    for m in (0, 16, D.STEAL_MAX):
+        q = D.steal_query(0, n, D.STEAL_OLDEST, D.STEAL_RELEASED_FIRST, 64, which, 1e-3, m)
+        ms = []
+        for it in range(3 + 12):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            db.find_steal(q, dv.data_ptr(), dc.data_ptr())
+            e1.record()
+            e1.synchronize()
+            if it >= 3:
+                ms.append(e0.elapsed_time(e1))
+        print(f"c2 {n} find_steal alone, max_out {m}: stream time median {np.median(ms):.4f} ms, min {np.min(ms):.4f}, max {np.max(ms):.4f} "
+              f"of {len(ms)} (candidates {int(dc[1])}, written {int(dc[0])})")
+    db.close()
+
+
 def cz_banks(n):
     """(a) C2 with `c1,0.5` everywhere; (b) 42.sk's v0-v2 as a triple -- carrier, FM modulator, CZ source, the two `m1` -- 21 times per
     64-voice group (lane 63 silent)."""
@@ -369,7 +461,7 @@ def cz():
 
 
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "cz": cz}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
