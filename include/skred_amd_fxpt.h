@@ -110,9 +110,95 @@ int  skred_fxbank_render_mix(skred_fxbank_t *fx, int num_frames, int interp, int
 int  skred_fxbank_master(skred_fxbank_t *fx, const int64_t *d_sum, int num_frames, int64_t *d_out, void *stream);
 int  skred_fxbank_set_master(skred_fxbank_t *fx, int64_t target_q31, int32_t k_q15, int64_t gain_q31);   /* synchronous */
 int64_t skred_fxbank_get_master_gain(skred_fxbank_t *fx);                                                  /* synchronous; < 0: error */
-/* Note-ons / note-offs on device-resident voices (the float path's SKRED_STAMP_TRIGGER / _RELEASE), on `stream`. */
+/* Note-ons / note-offs on device-resident voices (the float path's SKRED_STAMP_TRIGGER / _RELEASE), on `stream`; the ids travel
+ * through the staging ring of the live-control calls below: the call does not synchronise the stream. */
 enum { SKRED_FX_STAMP_TRIGGER = 1, SKRED_FX_STAMP_RELEASE = 2 };
 int  skred_fxbank_stamp(skred_fxbank_t *fx, const int32_t *voices, int n_voices, int which, void *stream);
+/* ---- live control: updates, the free-voice list, note-ons --------------------------------------------------------------
+ *
+ * The control plane of the float bank (include/skred_amd.h: skred_bank_update, skred_bank_find_idle, skred_bank_notes_on_list
+ * and their kin) on the fixed-point planes, with the same vocabulary: SKRED_DIRTY_* / SKRED_STAMP_*, SKRED_IDLE_*, SKRED_NOTE_*
+ * keep their bit values.  Everything is asynchronous on the caller's stream, ordered like the renders queued on it; nothing here
+ * waits for the device.  The calls work on a shard through skred_fxshard_bank(), with that rank's LOCAL voice indices.
+ * Not here (yet): stealing, the deferred queue and the step clock, taps.
+ *
+ * Transport.  Records travel through a ring of SKRED_FX_RING_SLOTS pinned staging slots: one hipMemcpyAsync per batch into the
+ * slot's device twin on `stream`, then the kernels, then an event of the slot's own.  The caller's arrays are free again when a
+ * call returns.  A call that finds its slot still in flight -- the bank is SKRED_FX_RING_SLOTS batches ahead of the device --
+ * waits for that slot's event, for as long as it takes: there is no wall-clock limit after which an update would be dropped.
+ * (Consequence: do not issue more than SKRED_FX_RING_SLOTS batches on a stream that is blocked behind something the same
+ * thread has yet to submit.)  One stream at a time per bank, as for its renders.
+ *
+ * skred_fxbank_update -- the `dirty` parts of the listed voices, from the host view, onto the resident voices:
+ *   SKRED_DIRTY_PARAMS        phase_inc, table_offset, log2_size, the flags (use_envelope, smoother_enable, disconnect, filter_mode,
+ *                             one_shot), amp_q15, attack / decay / release frames and their reciprocals, sustain_q15, b0..a2,
+ *                             smoother_k_q15, velocity_q15.  Not the pans, not the envelope clock.
+ *   SKRED_DIRTY_PAN           pan_left_q15, pan_right_q15
+ *   SKRED_DIRTY_PHASE         phase, finished
+ *   SKRED_DIRTY_ENV_STATE     is_active
+ *   SKRED_DIRTY_FILTER_STATE  x1 x2 y1 y2
+ *   SKRED_DIRTY_SMOOTHER      smoother_gain_q15
+ *   SKRED_DIRTY_SAMPLE        voice_sample
+ *   SKRED_DIRTY_ENV_CLOCK     sample_start, sample_release as the host has them
+ *   SKRED_STAMP_TRIGGER / _RELEASE   the stamps of skred_fxbank_stamp with now = the bank's sample count at the call, applied
+ *                             after an ENV_CLOCK write of the same record
+ *   SKRED_DIRTY_HOLD          refused (SKRED_E_BAD_ARG): the definition has no sample-and-hold
+ * Everything not named keeps the value the device last computed (skred_fxbank_upload would overwrite the running phase, the
+ * smoother, voice_sample, is_active / finished and the delay line with the host's stale copies).  A voice may be listed more than
+ * once: the copies take effect in order.  n == 0: SKRED_OK.  Refused before anything touches the device: SKRED_E_BAD_ARG -- NULL
+ * bank, host view or list, n < 0, no bit or unknown bits in dirty; SKRED_E_RANGE -- a voice outside the bank or the host view,
+ * and, per listed voice and only for the kinds named, what skred_fxbank_upload refuses: the table window and amp_q15 outside
+ * 0..65535 under PARAMS, a delay line outside +-2^29 under FILTER_STATE. */
+enum { SKRED_FX_RING_SLOTS = 8 };
+int  skred_fxbank_update(skred_fxbank_t *fx, const skred_fxpt_bank_t *host, const int32_t *voices, int n, uint32_t dirty, void *stream);
+
+/* The free-voice list: skred_bank_find_idle's contract (ascending from `from`, wrapping to `first`; d_count[0] = written =
+ * min(total, max_out), d_count[1] = total; entries past `written` are not touched; reads the bank only; the same state gives the
+ * same bytes; two launches, no workgroup waits for another) with the criteria read on the fixed-point fields, exactly:
+ *   SKRED_IDLE_FINISHED   finished != 0
+ *   SKRED_IDLE_ENV_DONE   use_envelope != 0 && is_active == 0 && (smoother_enable == 0 || |smoother_gain_q15| <= settle_q15)
+ *                         (the absolute value taken in 64 bits)
+ *   SKRED_IDLE_AMP_ZERO   amp_q15 == 0
+ * settle_q15 = 0 IS a usable level here, unlike the float path's: with k_q15 > 0 the integer smoother g += ((0 - g) * k) >> 15
+ * moves a positive g down by at least 1 per frame (the shift is arithmetic: -(g * k) >> 15 <= -1 whenever g * k > 0), so after a
+ * release has ended the gain reaches exactly 0 in at most g frames.  (A NEGATIVE g -- outside the promised range -- moves up by
+ * floor(-g * k / 2^15), which is 0 once |g| * k < 2^15: it stalls.)
+ * skred_fx_idle_check is pure host: SKRED_E_BAD_ARG -- NULL query, negative max_out, no criterion, unknown bits, among them
+ * SKRED_IDLE_UNNAMED (the definition has no modulators), a negative settle_q15; SKRED_E_RANGE -- count <= 0, a range outside
+ * [0, n_voices), `from` outside the range.  The bank calls add: NULL bank or d_count, NULL d_voices with max_out > 0. */
+typedef struct skred_fx_idle_query {
+  int32_t first, count; uint32_t which; int32_t settle_q15; int32_t from; int32_t max_out;
+} skred_fx_idle_query_t;
+int  skred_fx_idle_check(const skred_fx_idle_query_t *q, int n_voices);
+int  skred_fxbank_find_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only.  Returns `written` (>= 0) or a SKRED_E_* code; *total_out may be NULL. */
+int  skred_fxbank_find_idle_host(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *voices, int *total_out, void *stream);
+
+/* Device-side note-ons: skred_bank_notes_on_list / _note_on_idle / _stamp_list, argument for argument.  Note k goes to voice
+ * d_voices[first_entry + k] if first_entry + k < d_count[0] and that entry lies in [0, n_voices); otherwise it is dropped.  A
+ * placed note stores, as words: phase_inc and velocity_q15; with SKRED_NOTE_SET_PHASE the phase, and `finished` is cleared; with
+ * SKRED_NOTE_SET_PAN the two pans; then the trigger stamp (sample_start = the bank's sample count at the call, sample_release = 0,
+ * is_active = 1).  Nothing else: amp, table, smoother k, filter and delay line keep what they hold.  d_assigned[k] (device
+ * int32[n], may be NULL) = the voice or -1; d_result (device uint32[2], required) = placed, dropped.  Integer sums: the same bytes
+ * in any arrival order.  The list must name distinct voices.  The notes are staged before the call returns.  n == 0: SKRED_OK,
+ * nothing is done.  skred_fx_notes_check (pure host) refuses with SKRED_E_BAD_ARG: NULL notes, n < 0, unknown flags, non-zero
+ * reserved words, velocity_q15 outside 0..65535, and under SET_PAN a pan outside 0..65535. */
+typedef struct skred_fx_note {            /* 32 bytes */
+  uint32_t phase_inc; int32_t velocity_q15; uint32_t phase; int32_t pan_left_q15, pan_right_q15;
+  uint32_t flags, reserved[2];            /* SKRED_NOTE_SET_PHASE / SKRED_NOTE_SET_PAN; reserved 0 */
+} skred_fx_note_t;
+int  skred_fx_notes_check(const skred_fx_note_t *notes, int n);
+int  skred_fxbank_notes_on_list(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices,
+                                const uint32_t *d_count, int first_entry, int32_t *d_assigned, uint32_t *d_result, void *stream);
+/* The query `q` into scratch the bank owns (q->max_out is ignored: the library uses n), then the placement with first_entry = 0.
+ * SKRED_IDLE_AMP_ZERO is refused: a note-on leaves amp_q15 alone, so such a voice would stay silent and be listed again. */
+int  skred_fxbank_note_on_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, const skred_fx_note_t *notes, int n,
+                               int32_t *d_assigned, uint32_t *d_result, void *stream);
+/* SKRED_STAMP_TRIGGER and / or _RELEASE on the first min(n, *d_count_or_null) entries of a list in device memory (NULL: n
+ * entries); entries outside the bank -- the -1 of a dropped note -- are skipped. */
+int  skred_fxbank_stamp_list(skred_fxbank_t *fx, const int32_t *d_voices, int n, const uint32_t *d_count_or_null, uint32_t stamps,
+                             void *stream);
+
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);
 float skred_fxbank_last_render_ms(skred_fxbank_t *fx);

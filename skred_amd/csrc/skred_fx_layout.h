@@ -60,4 +60,44 @@ typedef struct {
 
 #define SKX_FINISH_SLABS 32
 #define SKX_FINISH_FLAT_MAX 64
+
+/* ---- live control (skred_fx_live_kernels.hip; include/skred_amd_fxpt.h: skred_fxbank_update / _find_idle / _notes_on_list) ---- */
+
+/* bits of word 3 of read-write plane 0 */
+#define SKXR_ACTIVE   1u
+#define SKXR_FINISHED 2u
+
+/* one record of an update batch: the voice as skred_fxbank_upload would pack it; `dirty` (SKRED_DIRTY_* / SKRED_STAMP_*) says
+ * which of its words travel */
+typedef struct __attribute__((aligned(16))) {
+  int32_t voice;
+  uint32_t dirty;
+  uint32_t pad[2];
+  skx_plane_t ro[SKX_COUNT];
+  skx_plane_t rw[SKX_RW_COUNT];
+} skx_update_t;                    /* 160 bytes */
+
+/* the device's image of skred_fx_note_t, word for word */
+enum { SKX_NOTE_PHASE_INC = 0, SKX_NOTE_VELOCITY, SKX_NOTE_PHASE, SKX_NOTE_PAN_LEFT, SKX_NOTE_PAN_RIGHT, SKX_NOTE_FLAGS, SKX_NOTE_WORDS = 8 };
+typedef struct { uint32_t w[SKX_NOTE_WORDS]; } skx_note_t;
+#define SKX_NOTE_SPAN 256          /* notes (and threads) per workgroup of sk_fx_notes_kernel */
+
+#define SKX_IDLE_SPAN 256          /* voices (and threads) per workgroup of the two query kernels; spans are aligned to 64 voices */
+/* the bank's query scratch: SKX_IDLE_W_COUNT words, then the workgroups' counts, then their exclusive offsets */
+enum { SKX_IDLE_W_TICKET = 0,      /* arrival ticket of the count kernel, re-armed by its last arriver */
+       SKX_IDLE_W_PART,            /* idle voices below `from` inside from's own workgroup */
+       SKX_IDLE_W_RANK,            /* idle voices of the range below `from` */
+       SKX_IDLE_W_TOTAL,           /* idle voices of the range */
+       SKX_IDLE_W_COUNT };
+typedef struct {
+  const skx_plane_t *osc;          /* SKX_OSC: flags (ENV_DONE), amp_q15 (AMP_ZERO) */
+  const skx_plane_t *rw0;          /* smoother gain (ENV_DONE), is_active / finished (ENV_DONE, FINISHED) */
+  uint32_t *words, *counts, *offsets;
+  int32_t *d_voices;
+  uint32_t *d_count;
+  int32_t first, end, from, max_out;
+  uint32_t which;                  /* SKRED_IDLE_FINISHED | _ENV_DONE | _AMP_ZERO */
+  int32_t settle_q15;
+  int32_t base, from_wg;           /* filled in by the launcher: `first` rounded down to 64; the workgroup that holds `from` */
+} skx_idle_args_t;
 #endif

@@ -3,50 +3,15 @@
  * skred_bank.c: owns the HBM planes, packs the host arrays, sequences sk_fx_render_kernel and the
  * int64 partial reduction.  No CPU rendering.
  */
-#define __HIP_PLATFORM_AMD__ 1
-#include <hip/hip_runtime_api.h>
-
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "skred_amd.h"
-#include "skred_amd_fxpt.h"
-#include "skred_fx_layout.h"
+#include "skred_fxbank_priv.h"
 
 int skx_launch_render(const skx_args_t *args, int n_workgroups, hipStream_t stream);
 int skx_launch_master_apply(const long long *sum, const int32_t *gains, long long *out, int num_frames, const long long *gain_pending,
                             long long *gain_state, hipStream_t stream);
-int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);
-int skred_amd_set_error(int code, const char *fmt, ...);   /* skred_bank.c */
-
-struct skred_fxbank {
-  int device, n_voices, n_padded, n_groups;
-  skx_plane_t *d_ro[SKX_COUNT];
-  skx_plane_t *d_rw[SKX_RW_COUNT];
-  int n_filter;                 /* voices with filter_mode != 0 (recounted on whole-bank uploads, grown otherwise) */
-  int16_t *d_tables;
-  size_t table_entries, table_bytes_padded;
-  long long *d_partial; size_t partial_cap;  /* [n_wg][F][2] rows, [SKX_FINISH_SLABS][F][2] slab sums, then int32 gains[F] */
-  uint32_t *d_tickets;          /* [SKX_FINISH_SLABS + 1] arrival counters of the in-kernel mix-down */
-  long long *d_gain_state;      /* [0] Q31 master gain carried between blocks; [1] the gain a sum-only render prepared for skred_fxbank_master */
-  long long master_target_q31;  /* default: 0.025 (the float path's volume_final) in Q31 */
-  int32_t master_k_q15;         /* default: 0.002 in Q15 */
-  int gains_frames;             /* > 0: the latest sum-only render left the gains of a block of this many frames */
-  size_t gains_offset;          /* ... at this int64 offset into d_partial */
-  int32_t *d_ids; int32_t *h_ids; size_t ids_cap;   /* staging of skred_fxbank_stamp */
-  long long *d_mix; size_t mix_cap;
-  int32_t *d_stems; size_t stems_cap;
-  uint64_t count;
-  hipEvent_t ev0, ev1;
-  int timed;
-};
-
-#define HIP_TRY(call)                                                                       \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) return skred_amd_set_error(SKRED_E_NO_DEVICE, "%s -> %s", #call, hipGetErrorString(e_)); \
-  } while (0)
 
 static int grow_bytes(void **buf, size_t *cap, size_t need) {
   if (*cap >= need) return SKRED_OK;
@@ -98,8 +63,7 @@ void skred_fxbank_destroy(skred_fxbank_t *fx) {
   if (fx->d_partial) hipFree(fx->d_partial);
   if (fx->d_tickets) hipFree(fx->d_tickets);
   if (fx->d_gain_state) hipFree(fx->d_gain_state);
-  if (fx->d_ids) hipFree(fx->d_ids);
-  if (fx->h_ids) hipHostFree(fx->h_ids);
+  skx_live_free(fx);
   if (fx->d_mix) hipFree(fx->d_mix);
   if (fx->d_stems) hipFree(fx->d_stems);
   if (fx->ev0) hipEventDestroy(fx->ev0);
@@ -120,9 +84,48 @@ int skred_fxbank_set_tables_i16(skred_fxbank_t *fx, const int16_t *pool, size_t 
 }
 
 static uint32_t recip32(uint32_t x) { return x ? (uint32_t)(0x100000000ull / x) : 0u; }
-/* the fields the biquad and the one-shots brought (filter_mode .. y2): a caller that zero-initialises the struct and leaves
- * them NULL gets what it got before they existed -- no filter, no one-shot, a delay line at rest */
-#define FX_OPT(arr, v) ((arr) ? (arr)[v] : 0)
+
+int skx_pack_voice(const skred_fxbank_t *fx, const skred_fxpt_bank_t *h, int v, uint32_t check, skx_plane_t ro[SKX_COUNT],
+                   skx_plane_t rw[SKX_RW_COUNT]) {
+  const int L = h->log2_size[v];
+  if (check & SKRED_DIRTY_PARAMS) {
+    if (L < 3 || L > 15 || h->table_offset[v] < 0 ||
+        (size_t)h->table_offset[v] + ((size_t)1 << L) > fx->table_entries)
+      return skred_amd_set_error(SKRED_E_RANGE, "fx voice %d: table [%d,+2^%d) outside pool of %zu entries", v, h->table_offset[v], L, fx->table_entries);
+    if (h->amp_q15[v] < 0 || h->amp_q15[v] > 65535) return skred_amd_set_error(SKRED_E_RANGE, "fx voice %d: amp_q15 %d outside 0..65535", v, h->amp_q15[v]);
+  }
+  uint32_t flags = 0;
+  if (h->use_envelope[v]) flags |= SKXF_USE_ENV;
+  if (h->smoother_enable[v]) flags |= SKXF_SMOOTH;
+  if (h->disconnect[v]) flags |= SKXF_MUTED;
+  if (FX_OPT(h->filter_mode, v)) flags |= SKXF_FILTER;
+  if (FX_OPT(h->one_shot, v)) flags |= SKXF_ONE_SHOT;
+  if (check & SKRED_DIRTY_FILTER_STATE) {
+    const int64_t lim = (int64_t)1 << 29;      /* the delay line the definition can produce: |x|, |y| < 2^29 */
+    const int32_t d[4] = { FX_OPT(h->x1, v), FX_OPT(h->x2, v), FX_OPT(h->y1, v), FX_OPT(h->y2, v) };
+    for (int k = 0; k < 4; k++)
+      if (d[k] < -lim || d[k] >= lim) return skred_amd_set_error(SKRED_E_RANGE, "fx voice %d: filter state %d outside +-2^29", v, d[k]);
+  }
+  memset(ro, 0, SKX_COUNT * sizeof(skx_plane_t));
+  ro[SKX_OSC].w[0] = h->phase_inc[v]; ro[SKX_OSC].w[1] = (uint32_t)h->table_offset[v];
+  ro[SKX_OSC].w[2] = (uint32_t)L | (flags << 8); ro[SKX_OSC].w[3] = (uint32_t)h->amp_q15[v];
+  ro[SKX_GAIN].w[0] = (uint32_t)h->pan_left_q15[v]; ro[SKX_GAIN].w[1] = (uint32_t)h->pan_right_q15[v];
+  ro[SKX_GAIN].w[2] = (uint32_t)h->smoother_k_q15[v]; ro[SKX_GAIN].w[3] = (uint32_t)h->velocity_q15[v];
+  ro[SKX_ENV].w[0] = h->attack_frames[v]; ro[SKX_ENV].w[1] = h->decay_frames[v];
+  ro[SKX_ENV].w[2] = h->release_frames[v]; ro[SKX_ENV].w[3] = (uint32_t)h->sustain_q15[v];
+  ro[SKX_RECIP].w[0] = recip32(h->attack_frames[v]); ro[SKX_RECIP].w[1] = recip32(h->decay_frames[v]);
+  ro[SKX_RECIP].w[2] = recip32(h->release_frames[v]);
+  ro[SKX_TIME].w[0] = (uint32_t)h->sample_start[v]; ro[SKX_TIME].w[1] = (uint32_t)(h->sample_start[v] >> 32);
+  ro[SKX_TIME].w[2] = (uint32_t)h->sample_release[v]; ro[SKX_TIME].w[3] = (uint32_t)(h->sample_release[v] >> 32);
+  ro[SKX_FILT].w[0] = (uint32_t)FX_OPT(h->b0_q30, v); ro[SKX_FILT].w[1] = (uint32_t)FX_OPT(h->b1_q30, v);
+  ro[SKX_FILT].w[2] = (uint32_t)FX_OPT(h->b2_q30, v); ro[SKX_FILT].w[3] = (uint32_t)FX_OPT(h->a1_q30, v);
+  ro[SKX_FILT2].w[0] = (uint32_t)FX_OPT(h->a2_q30, v);
+  rw[0].w[0] = h->phase[v]; rw[0].w[1] = (uint32_t)h->smoother_gain_q15[v];
+  rw[0].w[2] = (uint32_t)h->voice_sample[v]; rw[0].w[3] = (h->is_active[v] ? SKXR_ACTIVE : 0u) | (FX_OPT(h->finished, v) ? SKXR_FINISHED : 0u);
+  rw[1].w[0] = (uint32_t)FX_OPT(h->x1, v); rw[1].w[1] = (uint32_t)FX_OPT(h->x2, v);
+  rw[1].w[2] = (uint32_t)FX_OPT(h->y1, v); rw[1].w[3] = (uint32_t)FX_OPT(h->y2, v);
+  return SKRED_OK;
+}
 
 int skred_fxbank_upload(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, int src_first, int dst_first, int count) {
   if (!fx || !h || count < 0) return skred_amd_set_error(SKRED_E_BAD_ARG, "fx upload: bad arguments");
@@ -132,47 +135,15 @@ int skred_fxbank_upload(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, int src_
   HIP_TRY(hipSetDevice(fx->device));
   skx_plane_t *st = (skx_plane_t *)calloc((size_t)(SKX_COUNT + SKX_RW_COUNT) * (size_t)count, sizeof(skx_plane_t));
   if (!st) return skred_amd_set_error(SKRED_E_NO_MEM, "fx upload staging");
-  if (dst_first == 0 && count == fx->n_voices) fx->n_filter = 0;          /* whole bank replaced */
+  int n_filter = 0;
   for (int i = 0; i < count; i++) {
     const int v = src_first + i;
-    const int L = h->log2_size[v];
-    if (L < 3 || L > 15 || h->table_offset[v] < 0 ||
-        (size_t)h->table_offset[v] + ((size_t)1 << L) > fx->table_entries) {
-      free(st);
-      return skred_amd_set_error(SKRED_E_RANGE, "fx voice %d: table [%d,+2^%d) outside pool of %zu entries", v, h->table_offset[v], L, fx->table_entries);
-    }
-    if (h->amp_q15[v] < 0 || h->amp_q15[v] > 65535) { free(st); return skred_amd_set_error(SKRED_E_RANGE, "fx voice %d: amp_q15 %d outside 0..65535", v, h->amp_q15[v]); }
-    uint32_t flags = 0;
-    if (h->use_envelope[v]) flags |= SKXF_USE_ENV;
-    if (h->smoother_enable[v]) flags |= SKXF_SMOOTH;
-    if (h->disconnect[v]) flags |= SKXF_MUTED;
-    if (FX_OPT(h->filter_mode, v)) { flags |= SKXF_FILTER; fx->n_filter++; }
-    if (FX_OPT(h->one_shot, v)) flags |= SKXF_ONE_SHOT;
-    {
-      const int64_t lim = (int64_t)1 << 29;      /* the delay line the definition can produce: |x|, |y| < 2^29 */
-      const int32_t d[4] = { FX_OPT(h->x1, v), FX_OPT(h->x2, v), FX_OPT(h->y1, v), FX_OPT(h->y2, v) };
-      for (int k = 0; k < 4; k++)
-        if (d[k] < -lim || d[k] >= lim) { free(st); return skred_amd_set_error(SKRED_E_RANGE, "fx voice %d: filter state %d outside +-2^29", v, d[k]); }
-    }
-#define P(p) st[(size_t)(p) * count + i]
-    P(SKX_OSC).w[0] = h->phase_inc[v]; P(SKX_OSC).w[1] = (uint32_t)h->table_offset[v];
-    P(SKX_OSC).w[2] = (uint32_t)L | (flags << 8); P(SKX_OSC).w[3] = (uint32_t)h->amp_q15[v];
-    P(SKX_GAIN).w[0] = (uint32_t)h->pan_left_q15[v]; P(SKX_GAIN).w[1] = (uint32_t)h->pan_right_q15[v];
-    P(SKX_GAIN).w[2] = (uint32_t)h->smoother_k_q15[v]; P(SKX_GAIN).w[3] = (uint32_t)h->velocity_q15[v];
-    P(SKX_ENV).w[0] = h->attack_frames[v]; P(SKX_ENV).w[1] = h->decay_frames[v];
-    P(SKX_ENV).w[2] = h->release_frames[v]; P(SKX_ENV).w[3] = (uint32_t)h->sustain_q15[v];
-    P(SKX_RECIP).w[0] = recip32(h->attack_frames[v]); P(SKX_RECIP).w[1] = recip32(h->decay_frames[v]);
-    P(SKX_RECIP).w[2] = recip32(h->release_frames[v]);
-    P(SKX_TIME).w[0] = (uint32_t)h->sample_start[v]; P(SKX_TIME).w[1] = (uint32_t)(h->sample_start[v] >> 32);
-    P(SKX_TIME).w[2] = (uint32_t)h->sample_release[v]; P(SKX_TIME).w[3] = (uint32_t)(h->sample_release[v] >> 32);
-    P(SKX_FILT).w[0] = (uint32_t)FX_OPT(h->b0_q30, v); P(SKX_FILT).w[1] = (uint32_t)FX_OPT(h->b1_q30, v);
-    P(SKX_FILT).w[2] = (uint32_t)FX_OPT(h->b2_q30, v); P(SKX_FILT).w[3] = (uint32_t)FX_OPT(h->a1_q30, v);
-    P(SKX_FILT2).w[0] = (uint32_t)FX_OPT(h->a2_q30, v);
-    P(SKX_COUNT).w[0] = h->phase[v]; P(SKX_COUNT).w[1] = (uint32_t)h->smoother_gain_q15[v];
-    P(SKX_COUNT).w[2] = (uint32_t)h->voice_sample[v]; P(SKX_COUNT).w[3] = (h->is_active[v] ? 1u : 0u) | (FX_OPT(h->finished, v) ? 2u : 0u);
-    P(SKX_COUNT + 1).w[0] = (uint32_t)FX_OPT(h->x1, v); P(SKX_COUNT + 1).w[1] = (uint32_t)FX_OPT(h->x2, v);
-    P(SKX_COUNT + 1).w[2] = (uint32_t)FX_OPT(h->y1, v); P(SKX_COUNT + 1).w[3] = (uint32_t)FX_OPT(h->y2, v);
-#undef P
+    skx_plane_t ro[SKX_COUNT], rw[SKX_RW_COUNT];
+    const int rc = skx_pack_voice(fx, h, v, SKRED_DIRTY_PARAMS | SKRED_DIRTY_FILTER_STATE, ro, rw);
+    if (rc) { free(st); return rc; }
+    if (FX_OPT(h->filter_mode, v)) n_filter++;
+    for (int p = 0; p < SKX_COUNT; p++) st[(size_t)p * count + i] = ro[p];
+    for (int p = 0; p < SKX_RW_COUNT; p++) st[(size_t)(SKX_COUNT + p) * count + i] = rw[p];
   }
   const size_t bytes = (size_t)count * sizeof(skx_plane_t);
   hipError_t e = hipSuccess;
@@ -182,6 +153,8 @@ int skred_fxbank_upload(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, int src_
     e = hipMemcpy(fx->d_rw[p] + dst_first, st + (size_t)(SKX_COUNT + p) * count, bytes, hipMemcpyHostToDevice);
   free(st);
   HIP_TRY(e);
+  if (dst_first == 0 && count == fx->n_voices) fx->n_filter = n_filter;   /* whole bank replaced */
+  else fx->n_filter += n_filter;
   return SKRED_OK;
 }
 
@@ -308,24 +281,7 @@ int skred_fxbank_stamp(skred_fxbank_t *fx, const int32_t *voices, int n, int whi
   for (int i = 0; i < n; i++)
     if (voices[i] < 0 || voices[i] >= fx->n_voices) return skred_amd_set_error(SKRED_E_RANGE, "fx stamp: voice %d outside the bank", voices[i]);
   HIP_TRY(hipSetDevice(fx->device));
-  const size_t bytes = (size_t)n * sizeof(int32_t);
-  if (bytes > fx->ids_cap) {
-    HIP_TRY(hipDeviceSynchronize());
-    if (fx->d_ids) { (void)hipFree(fx->d_ids); fx->d_ids = NULL; }
-    if (fx->h_ids) { (void)hipHostFree(fx->h_ids); fx->h_ids = NULL; }
-    size_t cap = 4096;
-    while (cap < bytes) cap *= 2;
-    HIP_TRY(hipMalloc((void **)&fx->d_ids, cap));
-    HIP_TRY(hipHostMalloc((void **)&fx->h_ids, cap, hipHostMallocDefault));
-    fx->ids_cap = cap;
-  } else {
-    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));   /* (one staging buffer: the previous batch must have been read) */
-  }
-  memcpy(fx->h_ids, voices, bytes);
-  HIP_TRY(hipMemcpyAsync(fx->d_ids, fx->h_ids, bytes, hipMemcpyHostToDevice, (hipStream_t)stream));
-  const hipError_t e = (hipError_t)skx_launch_stamp(fx->d_ids, n, which, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, (hipStream_t)stream);
-  if (e != hipSuccess) return skred_amd_set_error(SKRED_E_NO_DEVICE, "fx stamp launch -> %s", hipGetErrorString(e));
-  return SKRED_OK;
+  return skx_stamp_ids(fx, voices, n, which, (hipStream_t)stream);   /* through the staging ring: no wait for the stream */
 }
 
 int skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems) {

@@ -1,0 +1,88 @@
+/* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
+ * skred_fx_live.c: updates, the free-voice list, note-ons). */
+#ifndef SKRED_FXBANK_PRIV_H
+#define SKRED_FXBANK_PRIV_H
+
+#define __HIP_PLATFORM_AMD__ 1
+#include <hip/hip_runtime_api.h>
+
+#include <stdint.h>
+#include <stddef.h>
+
+#include "skred_amd.h"
+#include "skred_amd_fxpt.h"
+#include "skred_fx_layout.h"
+
+/* One staging slot of the control ring: a pinned host buffer, its device twin, and an event recorded behind the slot's copy and
+ * the kernels that read the twin.  A slot that is still in flight is waited for through ITS event alone: the host never waits
+ * for the device, and never gives up after some wall-clock time -- a stream that is legitimately backlogged (a long offline
+ * block, a profiled run) holds the caller back exactly as long as it takes. */
+#define SKX_RING SKRED_FX_RING_SLOTS
+typedef struct {
+  void *h, *d;
+  size_t cap;
+  hipEvent_t ev;
+  int in_flight;
+} skx_slot_t;
+
+struct skred_fxbank {
+  int device, n_voices, n_padded, n_groups;
+  skx_plane_t *d_ro[SKX_COUNT];
+  skx_plane_t *d_rw[SKX_RW_COUNT];
+  int n_filter;                 /* voices with filter_mode != 0 (recounted on whole-bank uploads, grown otherwise) */
+  int16_t *d_tables;
+  size_t table_entries, table_bytes_padded;
+  long long *d_partial; size_t partial_cap;  /* [n_wg][F][2] rows, [SKX_FINISH_SLABS][F][2] slab sums, then int32 gains[F] */
+  uint32_t *d_tickets;          /* [SKX_FINISH_SLABS + 1] arrival counters of the in-kernel mix-down */
+  long long *d_gain_state;      /* [0] Q31 master gain carried between blocks; [1] the gain a sum-only render prepared for skred_fxbank_master */
+  long long master_target_q31;  /* default: 0.025 (the float path's volume_final) in Q31 */
+  int32_t master_k_q15;         /* default: 0.002 in Q15 */
+  int gains_frames;             /* > 0: the latest sum-only render left the gains of a block of this many frames */
+  size_t gains_offset;          /* ... at this int64 offset into d_partial */
+  skx_slot_t ring[SKX_RING];    /* staging of updates, stamps and notes (skred_fx_live.c) */
+  unsigned ring_head;
+  uint32_t *upd_mark; uint32_t upd_epoch;    /* per-voice epoch marks: a batch that names a voice twice is split into launches */
+  uint32_t *d_idle; int idle_wgs;            /* the query's scratch: SKX_IDLE_W_COUNT words, idle_wgs counts, idle_wgs offsets */
+  int32_t *d_idle_out, *h_idle_out; size_t idle_out_cap;   /* skred_fxbank_find_idle_host: counts + list, device and pinned */
+  uint32_t *d_note_list; size_t note_list_cap;             /* skred_fxbank_note_on_idle: counts + list */
+  long long *d_mix; size_t mix_cap;
+  int32_t *d_stems; size_t stems_cap;
+  uint64_t count;
+  hipEvent_t ev0, ev1;
+  int timed;
+};
+
+int skred_amd_set_error(int code, const char *fmt, ...);   /* skred_bank.c */
+
+#define HIP_TRY(call)                                                                       \
+  do {                                                                                      \
+    hipError_t e_ = (call);                                                                 \
+    if (e_ != hipSuccess) return skred_amd_set_error(SKRED_E_NO_DEVICE, "%s -> %s", #call, hipGetErrorString(e_)); \
+  } while (0)
+
+/* the fields the biquad and the one-shots brought (filter_mode .. y2): a caller that zero-initialises the struct and leaves
+ * them NULL gets what it got before they existed -- no filter, no one-shot, a delay line at rest */
+#define FX_OPT(arr, v) ((arr) ? (arr)[v] : 0)
+
+/* skred_fxbank.c: voice v of the host view as the planes hold it.  `check`: SKRED_DIRTY_PARAMS -- the table window and the amp
+ * range, SKRED_DIRTY_FILTER_STATE -- the delay line; refusals as skred_fxbank_upload states them. */
+int skx_pack_voice(const skred_fxbank_t *fx, const skred_fxpt_bank_t *h, int v, uint32_t check, skx_plane_t ro[SKX_COUNT],
+                   skx_plane_t rw[SKX_RW_COUNT]);
+
+/* skred_fx_live.c */
+void skx_live_free(skred_fxbank_t *fx);
+int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, hipStream_t s);
+
+/* skred_fx_kernels.hip, skred_fx_live_kernels.hip */
+int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);
+int skx_launch_update(const skx_update_t *d_updates, int n, skx_plane_t *const ro[SKX_COUNT], skx_plane_t *const rw[SKX_RW_COUNT],
+                      uint64_t now, hipStream_t stream);
+int skx_idle_workgroups(int first, int count);
+int skx_launch_idle(const skx_idle_args_t *args, hipStream_t stream);
+int skx_launch_notes(const skx_note_t *d_notes, int n, const int32_t *d_voices, const uint32_t *d_count, int first_entry, int n_voices,
+                     skx_plane_t *const ro[SKX_COUNT], skx_plane_t *const rw[SKX_RW_COUNT], uint64_t now, int32_t *d_assigned,
+                     uint32_t *d_result, hipStream_t stream);
+int skx_launch_stamp_list(const int32_t *d_voices, int n, const uint32_t *d_count, int n_voices, uint32_t stamps,
+                          skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);
+
+#endif

@@ -33,14 +33,55 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_get_sample_count", "skred_fxbank_render", "skred_fxbank_render_host",
                   "skred_fxbank_last_render_ms", "skred_fxbank_render_mix", "skred_fxbank_master", "skred_fxbank_set_master",
                   "skred_fxbank_get_master_gain", "skred_fxbank_stamp",
+                  "skred_fxbank_update", "skred_fxbank_find_idle", "skred_fxbank_find_idle_host",
+                  "skred_fxbank_notes_on_list", "skred_fxbank_note_on_idle", "skred_fxbank_stamp_list",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
+FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check"]      # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
+# live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
+DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
+DIRTY_SMOOTHER, DIRTY_HOLD, DIRTY_SAMPLE, STAMP_TRIGGER, STAMP_RELEASE, DIRTY_ENV_CLOCK = 32, 64, 128, 256, 512, 1024
+IDLE_FINISHED, IDLE_ENV_DONE, IDLE_AMP_ZERO, IDLE_UNNAMED = 1, 2, 4, 256
+NOTE_SET_PHASE, NOTE_SET_PAN = 1, 2
+FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
+FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
 MASTER_TARGET_Q31 = int(0.025 * 2147483648.0)     # the library's default: volume_user 1 x AMY_FACTOR
 MASTER_K_Q15 = 66                                 # 0.002
 
 
 class FxBankC(C.Structure):
     _fields_ = [("n_voices", C.c_int32)] + [(n, C.c_void_p) for n, _, _ in FX_FIELDS]
+
+
+class FxIdleQueryC(C.Structure):
+    """ctypes image of ``skred_fx_idle_query_t``."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("which", C.c_uint32), ("settle_q15", C.c_int32),
+                ("start", C.c_int32), ("max_out", C.c_int32)]          # `start`: the header's `from`
+
+
+class FxNoteC(C.Structure):
+    """ctypes image of ``skred_fx_note_t`` (32 bytes)."""
+    _fields_ = [("phase_inc", C.c_uint32), ("velocity_q15", C.c_int32), ("phase", C.c_uint32), ("pan_left_q15", C.c_int32),
+                ("pan_right_q15", C.c_int32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def fx_note_array(notes):
+    """A contiguous ``FxNoteC`` array from a sequence of FxNoteC (a ctypes array of FxNoteC passes through)."""
+    if isinstance(notes, C.Array) and notes._type_ is FxNoteC:
+        return notes
+    notes = list(notes)
+    return (FxNoteC * len(notes))(*notes)
+
+
+def fx_notes_check(notes) -> int:
+    """skred_fx_notes_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device."""
+    arr = fx_note_array(notes)
+    return int(_bind(load()).skred_fx_notes_check(C.cast(arr, C.c_void_p), len(arr)))
+
+
+def fx_idle_check(q: "FxIdleQueryC", n_voices: int) -> int:
+    """skred_fx_idle_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host, no device."""
+    return int(_bind(load()).skred_fx_idle_check(C.byref(q) if q is not None else None, int(n_voices)))
 
 
 class FxVoiceBank:
@@ -104,6 +145,14 @@ def _bind(L):
     L.skred_fxbank_get_master_gain.argtypes = [vp]
     L.skred_fxbank_get_master_gain.restype = C.c_int64
     L.skred_fxbank_stamp.argtypes = [vp, vp, i32, i32, vp]
+    L.skred_fxbank_update.argtypes = [vp, C.POINTER(FxBankC), vp, i32, C.c_uint32, vp]
+    L.skred_fx_idle_check.argtypes = [vp, i32]
+    L.skred_fxbank_find_idle.argtypes = [vp, vp, vp, vp, vp]
+    L.skred_fxbank_find_idle_host.argtypes = [vp, vp, vp, C.POINTER(C.c_int), vp]
+    L.skred_fx_notes_check.argtypes = [vp, i32]
+    L.skred_fxbank_notes_on_list.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_note_on_idle.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_stamp_list.argtypes = [vp, vp, i32, vp, C.c_uint32, vp]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -187,6 +236,61 @@ class DeviceFxBank:
     def stamp(self, voices, which: int, stream: int = 0):
         v = np.ascontiguousarray(voices, np.int32)
         _check(self.L.skred_fxbank_stamp(self.h, v.ctypes.data, len(v), which, stream or None), "skred_fxbank_stamp")
+
+    # ---- live control (include/skred_amd_fxpt.h): asynchronous on `stream`, nothing waits for the device ----
+    def update(self, bank: FxVoiceBank, voices, dirty: int, stream: int = 0):
+        """Push the `dirty` parts (DIRTY_* | STAMP_*) of the listed voices from the host view."""
+        v = np.ascontiguousarray(voices, np.int32)
+        cb = bank.as_c()
+        _check(self.L.skred_fxbank_update(self.h, C.byref(cb), v.ctypes.data, len(v), dirty, stream or None), "skred_fxbank_update")
+
+    @staticmethod
+    def _query(first, count, which, settle_q15, start, max_out) -> FxIdleQueryC:
+        return FxIdleQueryC(int(first), int(count), int(which), int(settle_q15), int(first if start is None else start), int(max_out))
+
+    def find_idle(self, first: int, count: int, which: int, settle_q15: int = 0, start: Optional[int] = None,
+                  max_out: int = 0, d_voices: int = 0, d_count: int = 0, stream: int = 0):
+        """The idle voices of [first, first + count) in ascending order from `start` (default `first`), wrapping, into
+        d_voices[0 .. written) (int32, device memory); d_count[0] = written, d_count[1] = total (uint32)."""
+        q = self._query(first, count, which, settle_q15, start, max_out)
+        _check(self.L.skred_fxbank_find_idle(self.h, C.byref(q), d_voices or None, d_count or None, stream or None),
+               "skred_fxbank_find_idle")
+
+    def find_idle_host(self, first: int, count: int, which: int, settle_q15: int = 0, start: Optional[int] = None,
+                       max_out: Optional[int] = None, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the listed voices, total)."""
+        max_out = count if max_out is None else max_out
+        q = self._query(first, count, which, settle_q15, start, max_out)
+        out = np.empty(max(max_out, 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_fxbank_find_idle_host(self.h, C.byref(q), out.ctypes.data if max_out > 0 else None, C.byref(total),
+                                               stream or None)
+        if n < 0:
+            _check(n, "skred_fxbank_find_idle_host")
+        return out[:n].copy(), int(total.value)
+
+    def notes_on_list(self, notes, d_voices: int, d_count: int, first_entry: int = 0, d_assigned: int = 0, d_result: int = 0,
+                      stream: int = 0):
+        """Note k goes to voice d_voices[first_entry + k] while that entry is below d_count[0] and names a voice of the bank, else
+        it is dropped.  d_assigned[k] (int32, may be 0) = the voice or -1; d_result[0] = placed, d_result[1] = dropped (uint32)."""
+        arr = fx_note_array(notes)
+        _check(self.L.skred_fxbank_notes_on_list(self.h, C.cast(arr, C.c_void_p), len(arr), d_voices or None, d_count or None,
+                                                 int(first_entry), d_assigned or None, d_result or None, stream or None),
+               "skred_fxbank_notes_on_list")
+
+    def note_on_idle(self, notes, first: int, count: int, which: int, settle_q15: int = 0, start: Optional[int] = None,
+                     d_assigned: int = 0, d_result: int = 0, stream: int = 0):
+        """find_idle (room for len(notes) voices, in scratch the bank owns) and the placement on its list, in one call."""
+        arr = fx_note_array(notes)
+        q = self._query(first, count, which, settle_q15, start, 0)
+        _check(self.L.skred_fxbank_note_on_idle(self.h, C.byref(q), C.cast(arr, C.c_void_p), len(arr), d_assigned or None,
+                                                d_result or None, stream or None), "skred_fxbank_note_on_idle")
+
+    def stamp_list(self, d_voices: int, n: int, stamps: int, d_count: int = 0, stream: int = 0):
+        """STAMP_TRIGGER / STAMP_RELEASE on the first min(n, d_count[0]) entries of a list in device memory (d_count 0: n entries);
+        entries outside the bank are skipped."""
+        _check(self.L.skred_fxbank_stamp_list(self.h, d_voices or None, int(n), d_count or None, int(stamps), stream or None),
+               "skred_fxbank_stamp_list")
 
 
 # ------------------------------------------------------------------ synthetic fixed-point bank

@@ -28,6 +28,10 @@
              recipe with `c1,0.5` on every voice, (b) a three-voice group shaped like 42.sk's v0-v2 (`v0 c1,0.5 C2,0.5 F1,1`, v1 and
              v2 `m1` modulators above it) tiled over the bank, each with the option 0 and 1.  Run from a directory that holds an
              older build of the package, it times option 0 only: the baseline
+  fxlive     note-ons on the FIXED-POINT bank: 256 notes on a 2^20-voice fxbank.bank_fx bank with 64 idle voices ahead of every burst
+             (medians of 12): (a) skred_fxbank_note_on_idle between an event pair -- stream time, and the time the call held the host;
+             (b) the only route without it: skred_fxbank_download of the bank, picking on the CPU, skred_fxbank_upload of those voices,
+             skred_fxbank_stamp -- host-held time and the stream time of upload + stamp; beside one 512-frame block of the bank
 
 Each line: ms per block over the timed blocks (wall clock), voice-samples/s, and the render kernel's duration from the
 library's own event pair around the latest bracketed launch (a bracketed launch runs alone).  kernels / fm / noise print
@@ -460,8 +464,78 @@ def cz():
                 run(f"{n} {name}, option {'-' if opt is None else opt}", b, t, g, steps=30 if n > 100000 else 60, cz_fast=opt)
 
 
+def fxlive():
+    from skred_amd import fxbank as X
+    n, F, K, IDLE = 1 << 20, 512, 256, 64
+    bank, pool, c0 = X.bank_fx(n)
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    for _ in range(3):
+        db.render_mix(F, out.data_ptr(), 1)
+    torch.cuda.synchronize()
+    block_ms = db.last_render_ms()
+    free = ((np.arange(IDLE, dtype=np.int64) * 16381 + 5) % n).astype(np.int32)   # the 64 voices that are idle ahead of every burst
+    rest = bank.copy()
+    rest["is_active"][free] = 0
+    rest["smoother_gain_q15"][free] = 0
+    which = X.IDLE_FINISHED | X.IDLE_ENV_DONE
+    notes = X.fx_note_array([X.FxNoteC(3000017 + 40009 * k, 26000, 0, 16384, 16384, X.NOTE_SET_PHASE) for k in range(K)])
+    da = torch.full((K,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(2, dtype=torch.int32, device="cuda")
+
+    def make_idle():
+        db.update(rest, free, X.DIRTY_ENV_STATE | X.DIRTY_SMOOTHER)
+        torch.cuda.synchronize()
+
+    ms, held = [], []
+    for it in range(3 + 12):                                             # three warm-up bursts, then the twelve that count
+        make_idle()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        db.note_on_idle(notes, 0, n, which, 0, 0, da.data_ptr(), dr.data_ptr())
+        dt = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        if it >= 3:
+            ms.append(e0.elapsed_time(e1))
+            held.append(dt * 1e3)
+    res = dr.cpu().numpy().tolist()
+    print(f"fx {n} note_on_idle, {K} notes, {IDLE} idle voices: stream time median {np.median(ms):.4f} ms, min {np.min(ms):.4f}, "
+          f"max {np.max(ms):.4f} of {len(ms)}; host held median {np.median(held):.4f} ms, max {np.max(held):.4f} (placed, dropped = {res}); "
+          f"nothing waited for; one {F}-frame block of this bank: {block_ms:.4f} ms")
+    got = bank.copy()
+    held, upd = [], []
+    for it in range(2 + 12):
+        make_idle()
+        t0 = time.perf_counter()
+        db.download(got)
+        a = got.a
+        picks = np.flatnonzero((a["finished"] != 0) | ((a["use_envelope"] != 0) & (a["is_active"] == 0) &
+                               ((a["smoother_enable"] == 0) | (a["smoother_gain_q15"] == 0))))[:K].astype(np.int32)
+        for k, v in enumerate(picks):                                    # the notes' values into the host view
+            got["phase_inc"][v], got["velocity_q15"][v], got["phase"][v], got["finished"][v] = notes[k].phase_inc, notes[k].velocity_q15, 0, 0
+        cb = got.as_c()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for v in picks:                                                  # (upload takes windows: one call per voice)
+            X._check(db.L.skred_fxbank_upload(db.h, cb, int(v), int(v), 1), "skred_fxbank_upload")
+        db.stamp(picks, X.FX_STAMP_TRIGGER)
+        e1.record()
+        dt = time.perf_counter() - t0
+        e1.synchronize()
+        if it >= 2:
+            held.append(dt * 1e3)
+            upd.append(e0.elapsed_time(e1))
+    print(f"fx {n} the same notes without it: skred_fxbank_download of the bank (waits for the device) + the pick in numpy + "
+          f"skred_fxbank_upload of {len(picks)} voices + skred_fxbank_stamp: host held median {np.median(held):.3f} ms, min {np.min(held):.3f}, "
+          f"max {np.max(held):.3f} of {len(held)}; upload + stamp between the events: median {np.median(upd):.4f} ms")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
