@@ -120,7 +120,7 @@ int  skred_fxbank_stamp(skred_fxbank_t *fx, const int32_t *voices, int n_voices,
  * and their kin) on the fixed-point planes, with the same vocabulary: SKRED_DIRTY_* / SKRED_STAMP_*, SKRED_IDLE_*, SKRED_NOTE_*
  * keep their bit values.  Everything is asynchronous on the caller's stream, ordered like the renders queued on it; nothing here
  * waits for the device.  The calls work on a shard through skred_fxshard_bank(), with that rank's LOCAL voice indices.
- * Not here (yet): stealing, the deferred queue and the step clock, taps.
+ * Not here (yet): the deferred queue and the step clock, taps.
  *
  * Transport.  Records travel through a ring of SKRED_FX_RING_SLOTS pinned staging slots: one hipMemcpyAsync per batch into the
  * slot's device twin on `stream`, then the kernels, then an event of the slot's own.  The caller's arrays are free again when a
@@ -198,6 +198,53 @@ int  skred_fxbank_note_on_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *
  * entries); entries outside the bank -- the -1 of a dropped note -- are skipped. */
 int  skred_fxbank_stamp_list(skred_fxbank_t *fx, const int32_t *d_voices, int n, const uint32_t *d_count_or_null, uint32_t stamps,
                              void *stream);
+
+/* ---- voice stealing: which sounding voices matter least, ranked on the device ------------------------------------------
+ *
+ * skred_bank_find_steal / _find_steal_host / _note_on_steal (include/skred_amd.h), argument for argument, on the fixed-point
+ * fields as the device holds them at that point of the stream; SKRED_STEAL_OLDEST / _QUIETEST, SKRED_STEAL_RELEASED_FIRST /
+ * _RELEASED_ONLY and SKRED_STEAL_MAX keep their values.  `now` is the bank's sample count when the call is made (the clock the
+ * stamps use).  Every comparison is exact:
+ *   released   sample_release != 0
+ *   age        sample_start > now ? 0 : now - sample_start      (a start ahead of the clock, which this path allows, has age 0)
+ *   candidate  the voice lies in [first, first + count)  &&  use_envelope != 0  &&  is_active != 0  &&  age >= min_age
+ *              &&  (released, under SKRED_STEAL_RELEASED_ONLY)
+ *              &&  the voice does NOT satisfy skred_fxbank_find_idle's predicate for (which = exclude_idle, settle_q15);
+ *                  exclude_idle = 0 excludes nobody
+ *   class      0 if SKRED_STEAL_RELEASED_FIRST is set and the voice is released, else 1
+ *   primary    SKRED_STEAL_OLDEST:    sample_release for class 0, sample_start otherwise, as full 64-bit counts
+ *              SKRED_STEAL_QUIETEST:  min(|smoother_gain_q15| taken in 64 bits, 0x7fffffff) when smoother_enable != 0, else 0x7fffffff
+ *   key        class << 62 | min(primary, 2^62 - 1)
+ *   order      ascending key, ties by ascending voice index
+ * d_count[0] = written = min(total, max_out), d_count[1] = total candidates; entries past `written` are not touched; the query
+ * reads the bank only; the same state gives the same bytes; max_out == 0 counts only.  SKRED_STEAL_DIGITS + 3 = nine launches
+ * whatever the data (one with max_out == 0), no workgroup waits for another, nothing waits for the device.  Only the first launch
+ * reads the bank -- SKX_OSC's flags and the read-write flags always, the envelope clock for OLDEST, min_age > 0 or a RELEASED_*
+ * flag, the smoother's gain for QUIETEST or an ENV_DONE exclusion, amp_q15 for an AMP_ZERO exclusion -- and leaves one key per
+ * voice; the rest is the float bank's select.  The bank owns the scratch (8 bytes per voice, allocated by the first query): one
+ * stream at a time.  The calls work on a shard through skred_fxshard_bank(), with that rank's LOCAL voice indices.
+ * skred_fx_steal_check is pure host: SKRED_E_BAD_ARG -- NULL query, unknown policy, unknown bits in flags or exclude_idle, among
+ * them SKRED_STEAL_UNNAMED and SKRED_IDLE_UNNAMED (the definition has no modulators), reserved != 0, max_out outside
+ * [0, SKRED_STEAL_MAX], a negative settle_q15; SKRED_E_RANGE -- count <= 0, a range outside [0, n_voices).  The bank calls add:
+ * NULL bank or d_count, NULL d_voices with max_out > 0.  All refusals come before anything touches the device. */
+typedef struct skred_fx_steal_query {     /* 40 bytes */
+  int32_t first, count; uint32_t policy, flags; uint64_t min_age;
+  uint32_t exclude_idle; int32_t settle_q15; int32_t max_out; int32_t reserved;
+} skred_fx_steal_query_t;
+int  skred_fx_steal_check(const skred_fx_steal_query_t *q, int n_voices);
+int  skred_fxbank_find_steal(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only.  Returns `written` (>= 0) or a SKRED_E_* code; *total_out may be NULL. */
+int  skred_fxbank_find_steal_host(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, int32_t *voices, int *total_out, void *stream);
+/* Notes at full polyphony: the idle query (max_out = n) into the bank's own list, the steal query with exclude_idle =
+ * idle_q->which, settle_q15 = idle_q->settle_q15 and max_out = min(n, SKRED_STEAL_MAX) (the library overrides those three fields
+ * of *steal_q: a victim is never a voice the idle list already offers), the victims appended behind the idle entries as far as
+ * the batch reaches, then the placement of skred_fxbank_notes_on_list with first_entry = 0: idle voices take the first notes,
+ * victims the next ones in victim order, the rest is dropped.  d_assigned as there; d_result (device uint32[3], required) =
+ * placed, dropped, placed on stolen voices.  The notes travel through the staging ring as skred_fxbank_notes_on_list's do.
+ * n == 0: SKRED_OK, nothing is done.  Refused before anything touches the device: what skred_fxbank_note_on_idle refuses
+ * (SKRED_IDLE_AMP_ZERO among it), what skred_fx_steal_check refuses, what skred_fx_notes_check refuses. */
+int  skred_fxbank_note_on_steal(skred_fxbank_t *fx, const skred_fx_idle_query_t *idle_q, const skred_fx_steal_query_t *steal_q,
+                                const skred_fx_note_t *notes, int n, int32_t *d_assigned, uint32_t *d_result, void *stream);
 
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);

@@ -31,7 +31,6 @@ _Static_assert(SKRED_FX_STAMP_TRIGGER == SKRED_STAMP_TRIGGER >> 8 && SKRED_FX_ST
 
 #define SKX_STAMPS (SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)
 #define SKX_IDLE_CRITERIA (SKRED_IDLE_FINISHED | SKRED_IDLE_ENV_DONE | SKRED_IDLE_AMP_ZERO)
-#define SKX_NOTE_LIST_WORDS 4      /* in front of note_on_idle's list: the query's two counts, padded to 16 bytes */
 
 void skx_live_free(skred_fxbank_t *fx) {
   for (int i = 0; i < SKX_RING; i++) {
@@ -49,6 +48,7 @@ void skx_live_free(skred_fxbank_t *fx) {
   if (fx->d_note_list) hipFree(fx->d_note_list);
   fx->d_idle = NULL; fx->d_idle_out = NULL; fx->h_idle_out = NULL; fx->d_note_list = NULL;
   fx->idle_wgs = 0; fx->idle_out_cap = 0; fx->note_list_cap = 0;
+  skx_steal_free(fx);
 }
 
 /* ------------------------------------------------------------------ the staging ring */
@@ -190,7 +190,7 @@ static int idle_check_bank(const skred_fxbank_t *fx, const skred_fx_idle_query_t
   return SKRED_OK;
 }
 
-static int idle_launch(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
+int skx_idle_launch(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
   HIP_TRY(hipSetDevice(fx->device));
   if (!fx->d_idle) {
     /* sized once, for the whole bank from any `first` (a range's spans start at `first` rounded down to 64) */
@@ -223,7 +223,7 @@ static int idle_launch(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32
 int skred_fxbank_find_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, void *stream) {
   const int rc = idle_check_bank(fx, q, d_voices, d_count, "fx find_idle");
   if (rc) return rc;
-  return idle_launch(fx, q, d_voices, d_count, (hipStream_t)stream);
+  return skx_idle_launch(fx, q, d_voices, d_count, (hipStream_t)stream);
 }
 
 int skred_fxbank_find_idle_host(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *voices, int *total_out, void *stream) {
@@ -244,7 +244,7 @@ int skred_fxbank_find_idle_host(skred_fxbank_t *fx, const skred_fx_idle_query_t 
     HIP_TRY(hipHostMalloc((void **)&fx->h_idle_out, (2 + cap) * sizeof(int32_t), hipHostMallocDefault));
     fx->idle_out_cap = cap;
   }
-  rc = idle_launch(fx, q, fx->d_idle_out + 2, (uint32_t *)fx->d_idle_out, s);
+  rc = skx_idle_launch(fx, q, fx->d_idle_out + 2, (uint32_t *)fx->d_idle_out, s);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(fx->h_idle_out, fx->d_idle_out, (2 + need) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
@@ -271,8 +271,8 @@ int skred_fx_notes_check(const skred_fx_note_t *notes, int n) {
 }
 
 /* the checked notes -> a staging slot -> the placement kernel */
-static int notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
-                        int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s) {
+int skx_notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
+                     int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s) {
   const size_t bytes = (size_t)n * sizeof(skred_fx_note_t);
   skx_slot_t *sl;
   int rc = ring_take(fx, bytes, &sl);
@@ -294,7 +294,20 @@ int skred_fxbank_notes_on_list(skred_fxbank_t *fx, const skred_fx_note_t *notes,
   const int rc = skred_fx_notes_check(notes, n);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(fx->device));
-  return notes_launch(fx, notes, n, d_voices, d_count, first_entry, d_assigned, d_result, (hipStream_t)stream);
+  return skx_notes_launch(fx, notes, n, d_voices, d_count, first_entry, d_assigned, d_result, (hipStream_t)stream);
+}
+
+/* room for n entries in the bank's own list */
+int skx_note_list_room(skred_fxbank_t *fx, int n) {
+  if ((size_t)n <= fx->note_list_cap) return SKRED_OK;
+  /* (hipFree waits for the device: no earlier placement still reads the old list) */
+  if (fx->d_note_list) { (void)hipFree(fx->d_note_list); fx->d_note_list = NULL; }
+  fx->note_list_cap = 0;
+  size_t cap = 1024;
+  while (cap < (size_t)n) cap *= 2;
+  HIP_TRY(hipMalloc((void **)&fx->d_note_list, (SKX_NOTE_LIST_WORDS + cap) * sizeof(uint32_t)));
+  fx->note_list_cap = cap;
+  return SKRED_OK;
 }
 
 int skred_fxbank_note_on_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, const skred_fx_note_t *notes, int n, int32_t *d_assigned,
@@ -311,19 +324,11 @@ int skred_fxbank_note_on_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q
   if ((rc = skred_fx_notes_check(notes, n))) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
-  if ((size_t)n > fx->note_list_cap) {
-    /* (hipFree waits for the device: no earlier placement still reads the old list) */
-    if (fx->d_note_list) { (void)hipFree(fx->d_note_list); fx->d_note_list = NULL; }
-    fx->note_list_cap = 0;
-    size_t cap = 1024;
-    while (cap < (size_t)n) cap *= 2;
-    HIP_TRY(hipMalloc((void **)&fx->d_note_list, (SKX_NOTE_LIST_WORDS + cap) * sizeof(uint32_t)));
-    fx->note_list_cap = cap;
-  }
+  if ((rc = skx_note_list_room(fx, n))) return rc;
   uint32_t *d_count = fx->d_note_list;
   int32_t *d_list = (int32_t *)(fx->d_note_list + SKX_NOTE_LIST_WORDS);
-  if ((rc = idle_launch(fx, &qq, d_list, d_count, s))) return rc;
-  return notes_launch(fx, notes, n, d_list, d_count, 0, d_assigned, d_result, s);
+  if ((rc = skx_idle_launch(fx, &qq, d_list, d_count, s))) return rc;
+  return skx_notes_launch(fx, notes, n, d_list, d_count, 0, d_assigned, d_result, s);
 }
 
 int skred_fxbank_stamp_list(skred_fxbank_t *fx, const int32_t *d_voices, int n, const uint32_t *d_count_or_null, uint32_t stamps,

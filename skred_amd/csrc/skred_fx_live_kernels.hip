@@ -26,15 +26,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "skred_fx_idle_common.hpp" // skx_idle_pred, SKXI_*: shared with skred_fx_steal_kernels.hip
 #include "skred_fx_layout.h"
 #include "skred_kernel_common.hpp"   // sk_arrive_last, sk_gu32
 
-// the public bit values (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*; checked against the
-// header in skred_fx_live.c)
+// the public bit values (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_NOTE_*, and SKRED_IDLE_* in
+// skred_fx_idle_common.hpp; checked against the header in skred_fx_live.c)
 enum { SKXU_PARAMS = 1u << 0, SKXU_PHASE = 1u << 1, SKXU_ENV_STATE = 1u << 2, SKXU_PAN = 1u << 3, SKXU_FILTER_STATE = 1u << 4,
        SKXU_SMOOTHER = 1u << 5, SKXU_SAMPLE = 1u << 7, SKXU_STAMP_TRIGGER = 1u << 8, SKXU_STAMP_RELEASE = 1u << 9,
        SKXU_ENV_CLOCK = 1u << 10 };
-enum { SKXI_FINISHED = 1u << 0, SKXI_ENV_DONE = 1u << 1, SKXI_AMP_ZERO = 1u << 2 };
 enum { SKXN_SET_PHASE = 1u << 0, SKXN_SET_PAN = 1u << 1 };
 
 struct skx_plane_ptrs_t {
@@ -100,24 +100,6 @@ __device__ __forceinline__ int skx_idle_voice(const skx_idle_args_t &a, bool &in
   const int v = a.base + (int)blockIdx.x * SKX_IDLE_SPAN + (int)threadIdx.x;   // base: `first` rounded down to 64
   in_range = v >= a.first && v < a.end;
   return v;
-}
-
-// the predicate of one voice; every comparison is exact
-__device__ __forceinline__ bool skx_idle_pred(const skx_idle_args_t &a, int v, bool in_range) {
-  if (!in_range) return false;
-  const uint32_t which = a.which;   // wave-uniform: the branches below are scalar
-  bool idle = false;
-  uint32_t rwf = 0;
-  if (which & (SKXI_FINISHED | SKXI_ENV_DONE)) rwf = a.rw0[v].w[3];
-  if (which & SKXI_FINISHED) idle = (rwf & SKXR_FINISHED) != 0;
-  if (which & SKXI_ENV_DONE) {
-    const uint32_t flags = a.osc[v].w[2] >> 8;
-    const long long gain = (long long)(int32_t)a.rw0[v].w[1];
-    const bool settled = !(flags & SKXF_SMOOTH) || (gain < 0 ? -gain : gain) <= (long long)a.settle_q15;
-    idle = idle || ((flags & SKXF_USE_ENV) && !(rwf & SKXR_ACTIVE) && settled);
-  }
-  if (which & SKXI_AMP_ZERO) idle = idle || a.osc[v].w[3] == 0u;
-  return idle;
 }
 
 __global__ __launch_bounds__(SKX_IDLE_SPAN) void sk_fx_idle_count_kernel(skx_idle_args_t a) {

@@ -1,5 +1,5 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
- * skred_fx_live.c: updates, the free-voice list, note-ons). */
+ * skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c: voice stealing). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -44,7 +44,10 @@ struct skred_fxbank {
   uint32_t *upd_mark; uint32_t upd_epoch;    /* per-voice epoch marks: a batch that names a voice twice is split into launches */
   uint32_t *d_idle; int idle_wgs;            /* the query's scratch: SKX_IDLE_W_COUNT words, idle_wgs counts, idle_wgs offsets */
   int32_t *d_idle_out, *h_idle_out; size_t idle_out_cap;   /* skred_fxbank_find_idle_host: counts + list, device and pinned */
-  uint32_t *d_note_list; size_t note_list_cap;             /* skred_fxbank_note_on_idle: counts + list */
+  uint32_t *d_note_list; size_t note_list_cap;             /* skred_fxbank_note_on_idle / _note_on_steal: SKX_NOTE_LIST_WORDS words (the idle
+                                                            * query's two counts, the joined list's length), then the list */
+  uint32_t *d_steal; int steal_wgs;          /* skred_fxbank_find_steal's scratch, laid out as the float bank's (skred_bank_steal.c) */
+  int32_t *d_steal_out, *h_steal_out;        /* [2] counts, then SK_STEAL_MAX victims: _find_steal_host's list and _note_on_steal's */
   long long *d_mix; size_t mix_cap;
   int32_t *d_stems; size_t stems_cap;
   uint64_t count;
@@ -70,8 +73,18 @@ int skx_pack_voice(const skred_fxbank_t *fx, const skred_fxpt_bank_t *h, int v, 
                    skx_plane_t rw[SKX_RW_COUNT]);
 
 /* skred_fx_live.c */
+#define SKX_NOTE_LIST_WORDS 4      /* in front of the bank's note list: the idle query's two counts, the joined list's length, padding */
 void skx_live_free(skred_fxbank_t *fx);
 int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, hipStream_t s);
+/* ... for skred_fxbank_note_on_steal: the idle query's launches (q checked by the caller), room for n entries in d_note_list, and
+ * the checked notes through a staging slot into the placement kernel */
+int skx_idle_launch(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s);
+int skx_note_list_room(skred_fxbank_t *fx, int n);
+int skx_notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
+                     int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s);
+
+/* skred_fx_steal.c */
+void skx_steal_free(skred_fxbank_t *fx);
 
 /* skred_fx_kernels.hip, skred_fx_live_kernels.hip */
 int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);

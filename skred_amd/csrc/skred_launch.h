@@ -13,7 +13,7 @@
  *   skred_rec_kernels.hip     sk_launch_rec_minmax, sk_rec_partial_floats, sk_launch_rec_convert
  *   skred_idle_kernels.hip    sk_launch_idle, sk_idle_workgroups, sk_launch_named
  *   skred_note_kernels.hip    sk_launch_notes, sk_launch_stamp_list
- *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_list_append
+ *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_steal_select, sk_launch_list_append
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
@@ -182,6 +182,10 @@ typedef struct {
 /* the keys and the first digit's histogram; SK_STEAL_DIGITS - 1 further digit launches; count; scatter; sort (one workgroup, writes
  * d_voices and d_count): SK_STEAL_DIGITS + 3 launches whatever the data.  max_out == 0: the first launch alone, which writes d_count */
 int sk_launch_steal(const sk_steal_args_t *args, hipStream_t stream);
+/* everything behind the key pass, which reads `keys` and `words` and no plane: digits 1 .. SK_STEAL_DIGITS - 1, count, scatter,
+ * sort (nothing with max_out == 0).  sk_launch_steal ends in it; the fixed-point bank's key pass (skred_fx_steal_kernels.hip)
+ * enters here with `idle` and env_s left zero */
+int sk_launch_steal_select(const sk_steal_args_t *args, hipStream_t stream);
 /* dst[at + t] = src[t] for t < min(src_count[0], room - at), at = dst_count[0] (<= room); out_count[0] = at + copied;
  * stolen[0] = copied.  One workgroup: room - at is at most SK_STEAL_MAX entries (src holds no more) */
 int sk_launch_list_append(int32_t *dst, const uint32_t *dst_count, const int32_t *src, const uint32_t *src_count, int room,

@@ -25,6 +25,9 @@
 // No workgroup waits for another: nothing here can spin or hang.  Integer sums and index-ordered ranks: the same state gives the
 // same bytes.  Every kernel only READS the bank.  Branches on query bits depend on kernel arguments only: they are wave-uniform.
 //
+//   sk_launch_steal_select launches everything behind the key pass.  None of it reads a plane, so the fixed-point bank's query
+//   (skred_fx_steal_kernels.hip: sk_fx_steal_keys_kernel) runs its own key pass into the same scratch layout and enters there.
+//
 //   sk_list_append_kernel    skred_bank_note_on_steal: the victims copied behind the idle list's entries, at the offset the idle
 //                            query's count word holds on the device.
 #include <hip/hip_runtime.h>
@@ -33,14 +36,10 @@
 #include "skred_idle_common.hpp"
 #include "skred_kernel_common.hpp"
 #include "skred_launch.h"
+#include "skred_steal_common.hpp"   // sk_key_t, sk_steal_histogram / _scan / _pick: shared with the fixed-point bank's key pass
 
 #define SK_STEAL_WAVES (SK_IDLE_SPAN / 64)
-#define SK_STEAL_PER (SK_STEAL_BINS / SK_IDLE_SPAN)   // histogram bins per thread of the last arriver
 #define SK_STEAL_SORT_THREADS 512
-
-typedef unsigned long long sk_key_t;
-
-__device__ __forceinline__ int sk_steal_shift(int digit) { return SK_STEAL_BITS * (SK_STEAL_DIGITS - 1 - digit); }
 
 __device__ __forceinline__ int sk_steal_voice(const sk_steal_args_t &a, bool &in_range) {
   const int v = a.base + (int)blockIdx.x * SK_IDLE_SPAN + (int)threadIdx.x;   // base: `first` rounded down to 64
@@ -79,91 +78,6 @@ __device__ __forceinline__ sk_key_t sk_steal_key(const sk_steal_args_t &a, int v
   }
   const sk_key_t cap = (1ull << 62) - 1;
   return (cls << 62) | (primary < cap ? primary : cap);
-}
-
-// One workgroup's share of a digit histogram: `hist` (LDS, SK_STEAL_BINS words) is zeroed, filled and its non-empty bins added
-// to the global histogram.  A wave whose counted keys all hold the same digit -- a bank uploaded in one go has one sample_start --
-// adds once instead of 64 times to one LDS word.
-__device__ __forceinline__ void sk_steal_histogram(const sk_steal_args_t &a, bool counted, uint32_t digit, uint32_t *hist, int tid) {
-  for (int b = tid; b < SK_STEAL_BINS; b += SK_IDLE_SPAN) hist[b] = 0;
-  __syncthreads();
-  const unsigned long long m = __ballot(counted);
-  if (m) {                                                     // wave-uniform
-    const int lead = __ffsll((long long)m) - 1;
-    const uint32_t d0 = (uint32_t)__shfl((int)digit, lead);
-    const unsigned long long same = __ballot(counted && digit == d0);
-    if (same == m) {
-      if ((tid & 63) == lead) atomicAdd(&hist[d0], (uint32_t)__popcll(m));
-    } else if (counted) {
-      atomicAdd(&hist[digit], 1u);
-    }
-  }
-  __syncthreads();
-  for (int b = tid; b < SK_STEAL_BINS; b += SK_IDLE_SPAN) {
-    const uint32_t c = hist[b];
-    if (c) __hip_atomic_fetch_add((sk_gu32 *)(a.hist + b), c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// inclusive scan of one word per thread of a SK_IDLE_SPAN-thread workgroup (as sk_idle_count_kernel's)
-__device__ __forceinline__ uint32_t sk_steal_scan(uint32_t *scan, uint32_t mine, int tid) {
-  __syncthreads();
-  scan[tid] = mine;
-  __syncthreads();
-  for (int d = 1; d < SK_IDLE_SPAN; d <<= 1) {
-    const uint32_t add = tid >= d ? scan[tid - d] : 0u;
-    __syncthreads();
-    scan[tid] += add;
-    __syncthreads();
-  }
-  return scan[tid];
-}
-
-// The last arriver of a digit launch: the bin of this digit in which the remain-th smallest of the counted keys lies.  Thread t owns
-// SK_STEAL_PER consecutive bins.  `prefix` / `remain`: what the launch started from (digit 0: nothing fixed, remain = k, made here).
-__device__ __forceinline__ void sk_steal_pick(const sk_steal_args_t &a, int digit, sk_key_t prefix, uint32_t remain, uint32_t *scan, int tid) {
-  uint32_t c[SK_STEAL_PER], sum = 0;
-#pragma unroll
-  for (int i = 0; i < SK_STEAL_PER; ++i) {
-    sk_gu32 *bin = (sk_gu32 *)(a.hist + tid * SK_STEAL_PER + i);
-    c[i] = __hip_atomic_load(bin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(bin, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next launch (stream-ordered)
-    sum += c[i];
-  }
-  const uint32_t incl = sk_steal_scan(scan, sum, tid), excl = incl - sum;
-  if (digit == 0) {
-    const uint32_t total = scan[SK_IDLE_SPAN - 1];
-    remain = total < (uint32_t)a.max_out ? total : (uint32_t)a.max_out;
-    if (tid == 0) {
-      a.words[SK_STEAL_W_TOTAL] = total;
-      a.words[SK_STEAL_W_K] = remain;
-      if (a.max_out <= 0) { a.d_count[0] = 0u; a.d_count[1] = total; }   // count only: this launch is the query
-    }
-  }
-  if (remain == 0) {                                           // an empty list: no key is below or equal to a threshold of 0 ...
-    if (tid == 0) {                                            // ... that counts (`remain` of the equal ones are taken: none)
-      a.words[SK_STEAL_W_REMAIN] = 0u;
-      a.words[SK_STEAL_W_PREFIX_LO] = 0u;
-      a.words[SK_STEAL_W_PREFIX_HI] = 0u;
-    }
-    return;
-  }
-  if (excl < remain && remain <= incl) {                       // exactly one thread: the counts are a partition of >= remain keys
-    uint32_t run = excl;
-    int d = 0;
-    bool found = false;
-#pragma unroll
-    for (int i = 0; i < SK_STEAL_PER; ++i) {
-      if (!found) {
-        if (run + c[i] >= remain) { found = true; d = i; }
-        else run += c[i];
-      }
-    }
-    const sk_key_t longer = (prefix << SK_STEAL_BITS) | (sk_key_t)(tid * SK_STEAL_PER + d);
-    a.words[SK_STEAL_W_REMAIN] = remain - run;
-    a.words[SK_STEAL_W_PREFIX_LO] = (uint32_t)longer;
-    a.words[SK_STEAL_W_PREFIX_HI] = (uint32_t)(longer >> 32);
-  }
 }
 
 __global__ __launch_bounds__(SK_IDLE_SPAN) void sk_steal_keys_kernel(sk_steal_args_t a) {
@@ -312,16 +226,13 @@ __global__ __launch_bounds__(SK_STEAL_MAX) void sk_list_append_kernel(int32_t *d
   if (t == 0) { out_count[0] = at + n; stolen[0] = n; }
 }
 
-extern "C" int sk_launch_steal(const sk_steal_args_t *args, hipStream_t stream) {
+// everything behind a key pass: it reads a.keys and the words the key pass's last arriver left, never a plane
+extern "C" int sk_launch_steal_select(const sk_steal_args_t *args, hipStream_t stream) {
   sk_steal_args_t a = *args;
   a.base = a.first & ~63;
-  a.idle.first = a.first;
-  a.idle.end = a.end;
+  if (a.max_out <= 0) return (int)hipSuccess;
   const dim3 grid((unsigned)sk_idle_workgroups(a.first, a.end - a.first)), block(SK_IDLE_SPAN);
-  a.digit = 0;
-  hipLaunchKernelGGL(sk_steal_keys_kernel, grid, block, 0, stream, a);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess || a.max_out <= 0) return (int)e;
+  hipError_t e;
   for (int d = 1; d < SK_STEAL_DIGITS; ++d) {
     a.digit = d;
     hipLaunchKernelGGL(sk_steal_digit_kernel, grid, block, 0, stream, a);
@@ -333,6 +244,19 @@ extern "C" int sk_launch_steal(const sk_steal_args_t *args, hipStream_t stream) 
   if ((e = hipGetLastError()) != hipSuccess) return (int)e;
   hipLaunchKernelGGL(sk_steal_sort_kernel, dim3(1), dim3(SK_STEAL_SORT_THREADS), 0, stream, a);
   return (int)hipGetLastError();
+}
+
+extern "C" int sk_launch_steal(const sk_steal_args_t *args, hipStream_t stream) {
+  sk_steal_args_t a = *args;
+  a.base = a.first & ~63;
+  a.idle.first = a.first;
+  a.idle.end = a.end;
+  const dim3 grid((unsigned)sk_idle_workgroups(a.first, a.end - a.first)), block(SK_IDLE_SPAN);
+  a.digit = 0;
+  hipLaunchKernelGGL(sk_steal_keys_kernel, grid, block, 0, stream, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  return sk_launch_steal_select(&a, stream);
 }
 
 extern "C" int sk_launch_list_append(int32_t *dst, const uint32_t *dst_count, const int32_t *src, const uint32_t *src_count, int room,

@@ -35,14 +35,18 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_get_master_gain", "skred_fxbank_stamp",
                   "skred_fxbank_update", "skred_fxbank_find_idle", "skred_fxbank_find_idle_host",
                   "skred_fxbank_notes_on_list", "skred_fxbank_note_on_idle", "skred_fxbank_stamp_list",
+                  "skred_fxbank_find_steal", "skred_fxbank_find_steal_host", "skred_fxbank_note_on_steal",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
-FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check"]      # pure host: no bank, no device
+FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check"]      # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
 DIRTY_SMOOTHER, DIRTY_HOLD, DIRTY_SAMPLE, STAMP_TRIGGER, STAMP_RELEASE, DIRTY_ENV_CLOCK = 32, 64, 128, 256, 512, 1024
 IDLE_FINISHED, IDLE_ENV_DONE, IDLE_AMP_ZERO, IDLE_UNNAMED = 1, 2, 4, 256
 NOTE_SET_PHASE, NOTE_SET_PAN = 1, 2
+STEAL_OLDEST, STEAL_QUIETEST = 0, 1               # SKRED_STEAL_*: policy; flags; the longest list
+STEAL_RELEASED_FIRST, STEAL_RELEASED_ONLY, STEAL_UNNAMED = 1, 2, 256
+STEAL_MAX = 1024
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
 MASTER_TARGET_Q31 = int(0.025 * 2147483648.0)     # the library's default: volume_user 1 x AMY_FACTOR
@@ -57,6 +61,21 @@ class FxIdleQueryC(C.Structure):
     """ctypes image of ``skred_fx_idle_query_t``."""
     _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("which", C.c_uint32), ("settle_q15", C.c_int32),
                 ("start", C.c_int32), ("max_out", C.c_int32)]          # `start`: the header's `from`
+
+
+class FxStealQueryC(C.Structure):
+    """ctypes image of ``skred_fx_steal_query_t`` (40 bytes)."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("policy", C.c_uint32), ("flags", C.c_uint32), ("min_age", C.c_uint64),
+                ("exclude_idle", C.c_uint32), ("settle_q15", C.c_int32), ("max_out", C.c_int32), ("reserved", C.c_int32)]
+
+
+def fx_steal_query(first, count, policy=STEAL_OLDEST, flags=0, min_age=0, exclude_idle=0, settle_q15=0, max_out=0) -> FxStealQueryC:
+    return FxStealQueryC(int(first), int(count), int(policy), int(flags), int(min_age), int(exclude_idle), int(settle_q15), int(max_out), 0)
+
+
+def fx_steal_check(q: "FxStealQueryC", n_voices: int) -> int:
+    """skred_fx_steal_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host, no device."""
+    return int(_bind(load()).skred_fx_steal_check(C.byref(q) if q is not None else None, int(n_voices)))
 
 
 class FxNoteC(C.Structure):
@@ -153,6 +172,10 @@ def _bind(L):
     L.skred_fxbank_notes_on_list.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp]
     L.skred_fxbank_note_on_idle.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.skred_fxbank_stamp_list.argtypes = [vp, vp, i32, vp, C.c_uint32, vp]
+    L.skred_fx_steal_check.argtypes = [vp, i32]
+    L.skred_fxbank_find_steal.argtypes = [vp, vp, vp, vp, vp]
+    L.skred_fxbank_find_steal_host.argtypes = [vp, vp, vp, C.POINTER(C.c_int), vp]
+    L.skred_fxbank_note_on_steal.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -291,6 +314,31 @@ class DeviceFxBank:
         entries outside the bank are skipped."""
         _check(self.L.skred_fxbank_stamp_list(self.h, d_voices or None, int(n), d_count or None, int(stamps), stream or None),
                "skred_fxbank_stamp_list")
+
+    # ---- voice stealing (include/skred_amd_fxpt.h: skred_fxbank_find_steal / _find_steal_host / _note_on_steal) ----
+    def find_steal(self, q: FxStealQueryC, d_voices: int = 0, d_count: int = 0, stream: int = 0):
+        """The q.max_out least important sounding voices of the range into d_voices (int32, device memory), most stealable first;
+        d_count[0] = written, d_count[1] = total candidates (uint32)."""
+        _check(self.L.skred_fxbank_find_steal(self.h, C.byref(q), d_voices or None, d_count or None, stream or None),
+               "skred_fxbank_find_steal")
+
+    def find_steal_host(self, q: FxStealQueryC, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the victims, total)."""
+        out = np.empty(max(q.max_out, 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_fxbank_find_steal_host(self.h, C.byref(q), out.ctypes.data if q.max_out > 0 else None, C.byref(total),
+                                                stream or None)
+        if n < 0:
+            _check(n, "skred_fxbank_find_steal_host")
+        return out[:n].copy(), int(total.value)
+
+    def note_on_steal(self, notes, idle_q: FxIdleQueryC, steal_q: FxStealQueryC, d_assigned: int = 0, d_result: int = 0,
+                      stream: int = 0):
+        """Idle voices take the first notes, the victims of steal_q the next ones; d_result[0..2] = placed, dropped, placed on
+        stolen voices (uint32)."""
+        arr = fx_note_array(notes)
+        _check(self.L.skred_fxbank_note_on_steal(self.h, C.byref(idle_q), C.byref(steal_q), C.cast(arr, C.c_void_p), len(arr),
+                                                 d_assigned or None, d_result or None, stream or None), "skred_fxbank_note_on_steal")
 
 
 # ------------------------------------------------------------------ synthetic fixed-point bank

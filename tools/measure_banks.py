@@ -32,6 +32,12 @@
              (medians of 12): (a) skred_fxbank_note_on_idle between an event pair -- stream time, and the time the call held the host;
              (b) the only route without it: skred_fxbank_download of the bank, picking on the CPU, skred_fxbank_upload of those voices,
              skred_fxbank_stamp -- host-held time and the stream time of upload + stamp; beside one 512-frame block of the bank
+  fxsteal    voice stealing on the FIXED-POINT bank: 2^20 voices of fxbank.bank_fx whose polyphony is used up but for 64 idle voices,
+             a burst of 256 notes (medians of 12 with minimum and maximum): (a) skred_fxbank_note_on_steal between an event pair --
+             stream time, and the time the call held the host; nothing is waited for; (b) the only route without it:
+             skred_fxbank_download of the bank, the idle pick and the victim order in numpy, skred_fxbank_upload of the chosen voices,
+             skred_fxbank_stamp -- host-held time and the stream time of upload + stamp; (c) skred_fxbank_find_steal alone at max_out
+             0 (its first launch), 16 and 1 024
 
 Each line: ms per block over the timed blocks (wall clock), voice-samples/s, and the render kernel's duration from the
 library's own event pair around the latest bracketed launch (a bracketed launch runs alone).  kernels / fm / noise print
@@ -534,8 +540,103 @@ def fxlive():
     db.close()
 
 
+def fxsteal():
+    from skred_amd import fxbank as X
+    n, F, K, IDLE = 1 << 20, 512, 256, 64
+    bank, pool, c0 = X.bank_fx(n)
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    for _ in range(3):
+        db.render_mix(F, out.data_ptr(), 1)
+    torch.cuda.synchronize()
+    block_ms = db.last_render_ms()
+    now = db.sample_count()
+    free = ((np.arange(IDLE, dtype=np.int64) * 16381 + 5) % n).astype(np.int32)   # the 64 voices that are idle ahead of every burst
+    rest = bank.copy()
+    rest["is_active"][free] = 0
+    rest["smoother_gain_q15"][free] = 0
+    which = X.IDLE_FINISHED | X.IDLE_ENV_DONE
+    released = ((np.arange(4096, dtype=np.int64) * 257 + 11) % n).astype(np.int32)   # some voices in release: both classes occur
+    db.stamp(released, X.FX_STAMP_RELEASE)
+    notes = X.fx_note_array([X.FxNoteC(3000017 + 40009 * k, 26000, 0, 16384, 16384, X.NOTE_SET_PHASE) for k in range(K)])
+    da = torch.full((K,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+    iq = X.FxIdleQueryC(0, n, which, 0, 0, 0)
+    sq = X.fx_steal_query(0, n, X.STEAL_OLDEST, X.STEAL_RELEASED_FIRST, 64)
+
+    def make_idle():
+        db.update(rest, free, X.DIRTY_ENV_STATE | X.DIRTY_SMOOTHER)
+        torch.cuda.synchronize()
+
+    ms, held = [], []
+    for it in range(3 + 12):                                             # three warm-up bursts, then the twelve that count
+        make_idle()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        db.note_on_steal(notes, iq, sq, da.data_ptr(), dr.data_ptr())
+        dt = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        if it >= 3:
+            ms.append(e0.elapsed_time(e1))
+            held.append(dt * 1e3)
+    res = dr.cpu().numpy().tolist()
+    print(f"fx {n} note_on_steal, {K} notes, {IDLE} idle voices, OLDEST | RELEASED_FIRST, min_age 64: stream time median {np.median(ms):.4f} ms, "
+          f"min {np.min(ms):.4f}, max {np.max(ms):.4f} of {len(ms)}; host held median {np.median(held):.4f} ms, max {np.max(held):.4f} "
+          f"(placed, dropped, on stolen voices = {res}); nothing waited for; one {F}-frame block of this bank: {block_ms:.4f} ms")
+    got = bank.copy()
+    held, upd = [], []
+    for it in range(2 + 12):
+        make_idle()
+        t0 = time.perf_counter()
+        db.download(got)                                                 # (the read-write fields; the clocks are the host's own record)
+        a = got.a
+        idle = (a["finished"] != 0) | ((a["use_envelope"] != 0) & (a["is_active"] == 0) & ((a["smoother_enable"] == 0) | (a["smoother_gain_q15"] == 0)))
+        start, release = a["sample_start"], a["sample_release"]
+        cand = (a["use_envelope"] != 0) & (a["is_active"] != 0) & ~idle & (np.uint64(now) - np.minimum(start, np.uint64(now)) >= 64)
+        key = np.where(release != 0, release, start | np.uint64(1 << 62))
+        v = np.flatnonzero(cand)
+        order = v[np.lexsort((v, key[v]))]
+        picks = np.concatenate([np.flatnonzero(idle), order])[:K].astype(np.int32)
+        for k, v in enumerate(picks):                                    # the notes' values into the host view
+            got["phase_inc"][v], got["velocity_q15"][v], got["phase"][v], got["finished"][v] = notes[k].phase_inc, notes[k].velocity_q15, 0, 0
+        cb = got.as_c()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for v in picks:                                                  # (upload takes windows: one call per voice)
+            X._check(db.L.skred_fxbank_upload(db.h, cb, int(v), int(v), 1), "skred_fxbank_upload")
+        db.stamp(picks, X.FX_STAMP_TRIGGER)
+        e1.record()
+        dt = time.perf_counter() - t0
+        e1.synchronize()
+        if it >= 2:
+            held.append(dt * 1e3)
+            upd.append(e0.elapsed_time(e1))
+    print(f"fx {n} the same notes without it: skred_fxbank_download of the bank (waits for the device) + the idle pick and the victim "
+          f"order in numpy + skred_fxbank_upload of {len(picks)} voices + skred_fxbank_stamp: host held median {np.median(held):.3f} ms, "
+          f"min {np.min(held):.3f}, max {np.max(held):.3f} of {len(held)}; upload + stamp between the events: median {np.median(upd):.4f} ms")
+    dv = torch.full((X.STEAL_MAX,), -1, dtype=torch.int32, device="cuda")
+    dc = torch.zeros(2, dtype=torch.int32, device="cuda")
+    for max_out in (0, 16, X.STEAL_MAX):
+        q = X.fx_steal_query(0, n, X.STEAL_OLDEST, X.STEAL_RELEASED_FIRST, 64, which, 0, max_out)
+        ms = []
+        for it in range(3 + 12):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            db.find_steal(q, dv.data_ptr(), dc.data_ptr())
+            e1.record()
+            e1.synchronize()
+            if it >= 3:
+                ms.append(e0.elapsed_time(e1))
+        print(f"fx {n} find_steal alone, max_out {max_out}: stream time median {np.median(ms):.4f} ms, min {np.min(ms):.4f}, max {np.max(ms):.4f} "
+              f"of {len(ms)} (written, total = {dc.cpu().numpy().tolist()})")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
