@@ -602,6 +602,80 @@ int  skred_bank_find_steal_host(skred_bank_t *bank, const skred_steal_query_t *q
 int  skred_bank_note_on_steal(skred_bank_t *bank, const skred_idle_query_t *idle_q, const skred_steal_query_t *steal_q,
                               const skred_note_t *notes, int n, int32_t *d_assigned, uint32_t *d_result, void *stream);
 
+/* ---- patch notes: idle SLOTS of a tiled patch, and notes and stamps on all voices of a slot ---------------------------------
+ *
+ * What is rendered at scale is patches: an instrument of several voices -- a carrier with its modulators, some of them enveloped
+ * -- tiled over the bank, every copy an aligned run of K voices (skred_amd.banks.bank_patch).  A note on such an instrument is a
+ * note on ALL voices of one copy, and a copy is free only when ALL its enveloped voices have come to rest; idle voices of
+ * different copies interleave in skred_bank_find_idle's list, and a note that landed on voices of two copies would play nonsense
+ * through the copies' routing.  These calls are the voice calls above, stated on slots.
+ *
+ * A SLOT is an aligned run of K = slot_voices voices, K in {1, 2, 4, 8, 16, 32, 64}: its first voice is a multiple of K (so it
+ * never straddles an aligned 64-voice group), and the slot is named by its first voice.
+ * A slot is IDLE if and only if every MEMBER voice -- voice l of the slot with bit l of member_mask set -- satisfies
+ * skred_bank_find_idle's predicate for (which, settle_level), on the fields as the device holds them at that point of the stream.
+ * Voices outside member_mask are never looked at: the unused voices of a patch, or an LFO without an envelope that runs forever.
+ * SKRED_IDLE_UNNAMED is refused: the voices of a patch name one another by design.
+ * With K = 1 and both masks 1 every call below writes the bytes of its per-voice counterpart. */
+typedef struct skred_slot_query {
+  int32_t  first, count;    /* voice range; first % K == 0, count % K == 0, count > 0, inside the bank */
+  int32_t  slot_voices;     /* K */
+  uint64_t member_mask;     /* bit l: voice l of a slot takes part in the idle test; non-zero, no bits at or above K */
+  uint32_t which;           /* SKRED_IDLE_FINISHED | _ENV_DONE | _AMP_ZERO; at least one; SKRED_IDLE_UNNAMED refused */
+  float    settle_level;    /* as skred_idle_query_t */
+  int32_t  from;            /* a slot's first voice inside the range: listing starts there and wraps to `first` */
+  int32_t  max_out;         /* room in d_slots, in slots; 0: count only */
+} skred_slot_query_t;
+
+/* Pure host, no device: SKRED_OK, or what skred_bank_find_idle_slots refuses about the query itself on a bank of n_voices voices.
+ * SKRED_E_BAD_ARG: NULL query, negative max_out, SKRED_IDLE_UNNAMED or unknown bits in which, no criterion, a settle_level that is
+ * negative or not finite, a member_mask that is 0 or has bits at or above K.  SKRED_E_RANGE: K not a power of two in 1 .. 64,
+ * count <= 0, a range outside the bank, `from` outside the range, first, count or from not a multiple of K. */
+int  skred_slot_query_check(const skred_slot_query_t *q, int n_voices);
+/* Pure host, no device: skred_notes_check's rules on the n * K records of n patch notes, applied ONLY to the records of voices
+ * with a bit in voice_mask (the others are not looked at), and SKRED_E_RANGE for a bad K, SKRED_E_BAD_ARG for a voice_mask that
+ * is 0 or has bits at or above K. */
+int  skred_slot_notes_check(const skred_note_t *notes, int n, int slot_voices, uint64_t voice_mask);
+
+/* skred_bank_find_idle on slots.  d_slots[0 .. written) = the first voices of the idle slots of the range, ascending from `from`
+ * and wrapping to `first`; d_count[0] = written = min(total, max_out), d_count[1] = total; entries past `written` are not
+ * touched.  Asynchronous on `stream`, reads the bank only, the same state gives the same bytes (the order is by voice index,
+ * never by arrival).  Two launches, on the scratch the voice query uses: one stream at a time per bank.  Refused before anything
+ * touches the device: what skred_slot_query_check refuses, and SKRED_E_BAD_ARG for a NULL bank or d_count, or a NULL d_slots with
+ * max_out > 0.  On a shard: through skred_shard_bank(), with local indices.  Not in the fixed-point bank or the drop-in mode. */
+int  skred_bank_find_idle_slots(skred_bank_t *bank, const skred_slot_query_t *q, int32_t *d_slots, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only.  Returns `written` (>= 0) or a SKRED_E_* code; *total_out may be NULL. */
+int  skred_bank_find_idle_slots_host(skred_bank_t *bank, const skred_slot_query_t *q, int32_t *slots, int *total_out, void *stream);
+/* skred_bank_notes_on_list on slots.  `notes` holds n * K records: record k * K + l is the skred_note_t for voice l of note k.
+ * Note k takes the slot e = d_slots[first_entry + k] if that entry exists (first_entry + k < d_count[0]), 0 <= e, e % K == 0 and
+ * e + K <= n_voices; otherwise the note is dropped whole.  On a taken slot every voice l with bit l of voice_mask set receives
+ * exactly skred_bank_notes_on_list's stores for its record (increment, velocity, with SET_PHASE the phase and voice_finished = 0,
+ * with SET_PAN the pans, the trigger stamp with synth_sample_count at application time, its bit on the motion list); voices without
+ * a bit are not touched, their records neither read nor checked.  There is no arithmetic on the device: the pitch ratios between a
+ * carrier and its modulators are the host's business and arrive as finished increments, which keeps the result bit-equal to the
+ * host route.  d_assigned[k] (device, int32[n], may be NULL) = the slot's first voice or -1; d_result (device, uint32[2],
+ * required) = notes placed, notes dropped -- in notes, not voices.  first_entry: the cursor of skred_bank_notes_on_list.
+ * The list must name distinct slots (skred_bank_find_idle_slots' does; a hand-made list or a reused d_assigned may not): with a
+ * slot named twice, which of the competing notes each of its voices ends with is unspecified -- voice by voice, so a copy may end
+ * with records of both -- and nothing else is affected.
+ * Asynchronous on `stream`; n == 0: SKRED_OK, nothing is done.  Refused before anything touches the device: SKRED_E_BAD_ARG for a
+ * NULL bank, notes, list, count or result, n < 0, first_entry < 0, and what skred_slot_notes_check refuses. */
+int  skred_bank_notes_on_slots(skred_bank_t *bank, const skred_note_t *notes, int n, int slot_voices, uint64_t voice_mask,
+                               const int32_t *d_slots, const uint32_t *d_count, int first_entry,
+                               int32_t *d_assigned, uint32_t *d_result, void *stream);
+/* One call: the query `q` into scratch the bank owns (q->max_out is ignored: the library uses n), then the placement with
+ * K = q->slot_voices and first_entry = 0.  Refusals of both, and SKRED_E_BAD_ARG for SKRED_IDLE_AMP_ZERO as in
+ * skred_bank_note_on_idle. */
+int  skred_bank_note_on_idle_slots(skred_bank_t *bank, const skred_slot_query_t *q, const skred_note_t *notes, int n,
+                                   uint64_t voice_mask, int32_t *d_assigned, uint32_t *d_result, void *stream);
+/* skred_bank_stamp_list on slots: SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE on the voices with a bit in voice_mask of the
+ * first min(n, *d_count_or_null) listed slots (NULL: n).  Entries that are no slot of the bank (negative, not a multiple of K,
+ * past the bank) are skipped, so an earlier d_assigned with its -1 holes is the note-off list of a chord.  A slot named twice is
+ * stamped twice with the same clock and the same bits, which is the same as once.  SKRED_E_BAD_ARG: NULL
+ * bank or list, n < 0, no stamp bit or other bits, a bad voice_mask; SKRED_E_RANGE: a bad K; n == 0: SKRED_OK, nothing is done. */
+int  skred_bank_stamp_slots(skred_bank_t *bank, const int32_t *d_slots, int n, const uint32_t *d_count_or_null,
+                            int slot_voices, uint64_t voice_mask, uint32_t stamps, void *stream);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

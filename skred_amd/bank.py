@@ -105,6 +105,18 @@ class GlobalsC(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class SlotQueryC(C.Structure):
+    """ctypes image of ``skred_slot_query_t`` (40 bytes): the idle-slot query of a tiled patch."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("slot_voices", C.c_int32), ("member_mask", C.c_uint64),
+                ("which", C.c_uint32), ("settle_level", C.c_float), ("start", C.c_int32), ("max_out", C.c_int32)]   # `start`: the header's `from`
+
+
+def slot_query(first: int, count: int, slot_voices: int, member_mask: int, which: int, settle_level: float = 0.0,
+               start: Optional[int] = None, max_out: int = 0) -> SlotQueryC:
+    return SlotQueryC(int(first), int(count), int(slot_voices), int(member_mask), int(which), float(settle_level),
+                      int(first if start is None else start), int(max_out))
+
+
 class VoiceBank:
     """N voices, one numpy array per reference field.  Defaults follow voice_reset (synth.c:1090-1132)
     for everything that does not need a table: silent (amp 0), centre pan, smoother on (k=0.02),

@@ -54,40 +54,67 @@ int sk_named_ensure(skred_bank_t *b, hipStream_t s) {
   return SKRED_OK;
 }
 
+/* the bank's scratch of both list queries (this one and skred_bank_slots.c's), allocated on first use */
+int sk_idle_scratch(skred_bank_t *b, hipStream_t s) {
+  if (b->d_idle) return SKRED_OK;
+  /* sized once, for the whole bank from any `first` (a range's spans start at `first` rounded down to 64) */
+  const int wgs = sk_idle_workgroups(63, b->n_padded);
+  HIP_TRY(hipMalloc((void **)&b->d_idle, ((size_t)SK_IDLE_W_COUNT + 2 * (size_t)wgs) * sizeof(uint32_t)));
+  b->idle_wgs = wgs;
+  HIP_TRY(hipMemsetAsync(b->d_idle, 0, (size_t)SK_IDLE_W_COUNT * sizeof(uint32_t), s));   /* the ticket: zero once, re-armed by every last arriver */
+  return SKRED_OK;
+}
+
+/* the kernels' view of a query on this bank: planes, scratch, range and criteria (`named` stays NULL) */
+void sk_idle_args(const skred_bank_t *b, sk_idle_args_t *a, int first, int count, int from, int max_out, uint32_t which,
+                  float settle_level, int32_t *d_voices, uint32_t *d_count) {
+  memset(a, 0, sizeof(*a));
+  a->osc_ro = b->d_ro[SKP_OSC];
+  a->tab = b->d_ro[SKP_TAB];
+  a->osc_rw = b->d_rw[SKS_OSC];
+  a->filt = b->d_rw[SKS_FILT];
+  a->words = b->d_idle;
+  a->counts = b->d_idle + SK_IDLE_W_COUNT;
+  a->offsets = a->counts + b->idle_wgs;
+  a->d_voices = d_voices;
+  a->d_count = d_count;
+  a->first = first;
+  a->end = first + count;
+  a->from = from;
+  a->max_out = max_out;
+  a->which = which;
+  a->settle_level = settle_level;
+}
+
 static int idle_launch(skred_bank_t *b, const skred_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
   HIP_TRY(hipSetDevice(b->device));
-  if (!b->d_idle) {
-    /* sized once, for the whole bank from any `first` (a range's spans start at `first` rounded down to 64) */
-    const int wgs = sk_idle_workgroups(63, b->n_padded);
-    HIP_TRY(hipMalloc((void **)&b->d_idle, ((size_t)SK_IDLE_W_COUNT + 2 * (size_t)wgs) * sizeof(uint32_t)));
-    b->idle_wgs = wgs;
-    HIP_TRY(hipMemsetAsync(b->d_idle, 0, (size_t)SK_IDLE_W_COUNT * sizeof(uint32_t), s));   /* the ticket: zero once, re-armed by every last arriver */
-  }
+  int rc = sk_idle_scratch(b, s);
+  if (rc) return rc;
   if (q->which & SKRED_IDLE_UNNAMED) {
-    const int rc = sk_named_ensure(b, s);
+    rc = sk_named_ensure(b, s);
     if (rc) return rc;
   }
   sk_idle_args_t a;
-  memset(&a, 0, sizeof(a));
-  a.osc_ro = b->d_ro[SKP_OSC];
-  a.tab = b->d_ro[SKP_TAB];
-  a.osc_rw = b->d_rw[SKS_OSC];
-  a.filt = b->d_rw[SKS_FILT];
+  sk_idle_args(b, &a, q->first, q->count, q->from, q->max_out, q->which, q->settle_level, d_voices, d_count);
   a.named = (q->which & SKRED_IDLE_UNNAMED) ? b->d_named : NULL;
-  a.words = b->d_idle;
-  a.counts = b->d_idle + SK_IDLE_W_COUNT;
-  a.offsets = a.counts + b->idle_wgs;
-  a.d_voices = d_voices;
-  a.d_count = d_count;
-  a.first = q->first;
-  a.end = q->first + q->count;
-  a.from = q->from;
-  a.max_out = q->max_out;
-  a.which = q->which;
-  a.settle_level = q->settle_level;
   if (sk_idle_workgroups(a.first, q->count) > b->idle_wgs) return fail(SKRED_E_RANGE, "find_idle: scratch too small");   /* (unreachable: sized above) */
   const hipError_t e = (hipError_t)sk_launch_idle(&a, s);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "find_idle launch -> %s", hipGetErrorString(e));
+  return SKRED_OK;
+}
+
+/* room for `need` entries behind the two counts in d_idle_out and its pinned twin (the _host forms of both list queries) */
+int sk_idle_out_room(skred_bank_t *b, size_t need) {
+  if (b->d_idle_out && need <= b->idle_out_cap) return SKRED_OK;
+  /* (the previous call waited for its copy: nothing reads the old buffers) */
+  if (b->d_idle_out) { (void)hipFree(b->d_idle_out); b->d_idle_out = NULL; }
+  if (b->h_idle_out) { (void)hipHostFree(b->h_idle_out); b->h_idle_out = NULL; }
+  b->idle_out_cap = 0;
+  size_t cap = 1024;
+  while (cap < need) cap *= 2;
+  HIP_TRY(hipMalloc((void **)&b->d_idle_out, (2 + cap) * sizeof(int32_t)));
+  HIP_TRY(hipHostMalloc((void **)&b->h_idle_out, (2 + cap) * sizeof(int32_t), hipHostMallocDefault));
+  b->idle_out_cap = cap;
   return SKRED_OK;
 }
 
@@ -104,17 +131,7 @@ int skred_bank_find_idle_host(skred_bank_t *b, const skred_idle_query_t *q, int3
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
   const size_t need = (size_t)q->max_out;
-  if (!b->d_idle_out || need > b->idle_out_cap) {
-    /* (the previous call waited for its copy: nothing reads the old buffers) */
-    if (b->d_idle_out) { (void)hipFree(b->d_idle_out); b->d_idle_out = NULL; }
-    if (b->h_idle_out) { (void)hipHostFree(b->h_idle_out); b->h_idle_out = NULL; }
-    b->idle_out_cap = 0;
-    size_t cap = 1024;
-    while (cap < need) cap *= 2;
-    HIP_TRY(hipMalloc((void **)&b->d_idle_out, (2 + cap) * sizeof(int32_t)));
-    HIP_TRY(hipHostMalloc((void **)&b->h_idle_out, (2 + cap) * sizeof(int32_t), hipHostMallocDefault));
-    b->idle_out_cap = cap;
-  }
+  if ((rc = sk_idle_out_room(b, need))) return rc;
   rc = idle_launch(b, q, b->d_idle_out + 2, (uint32_t *)b->d_idle_out, s);
   if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(b->h_idle_out, b->d_idle_out, (2 + need) * sizeof(int32_t), hipMemcpyDeviceToHost, s));

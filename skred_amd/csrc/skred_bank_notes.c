@@ -23,26 +23,30 @@ _Static_assert(sizeof(skred_note_t) == sizeof(sk_note_t) && sizeof(skred_note_t)
 _Static_assert(SK_NOTE_SET_PHASE == SKRED_NOTE_SET_PHASE && SK_NOTE_SET_PAN == SKRED_NOTE_SET_PAN,
                "device note flags must equal the public SKRED_NOTE_* values");
 
-#define SK_NOTE_LIST_WORDS 4       /* in front of the list: the query's two counts, the joined list's length (note_on_steal), padded to 16 bytes */
-
 void sk_notes_free(skred_bank_t *b) {
   if (b->d_note_list) hipFree(b->d_note_list);
   b->d_note_list = NULL;
   b->note_list_cap = 0;
 }
 
+/* one record (`k`: its number in the error text) */
+int sk_note_check_one(const skred_note_t *t, int k) {
+  if (t->flags & ~(uint32_t)(SKRED_NOTE_SET_PHASE | SKRED_NOTE_SET_PAN)) return fail(SKRED_E_BAD_ARG, "note %d: unknown bits in flags = 0x%x", k, t->flags);
+  if (t->reserved[0] || t->reserved[1]) return fail(SKRED_E_BAD_ARG, "note %d: reserved words must be 0", k);
+  /* a non-finite increment or phase would change the voice's class (sk_pack_voice: SKC_EXOTIC) behind the host's back */
+  if (!isfinite(t->phase_inc)) return fail(SKRED_E_BAD_ARG, "note %d: phase_inc %g", k, (double)t->phase_inc);
+  if (!isfinite(t->velocity)) return fail(SKRED_E_BAD_ARG, "note %d: velocity %g", k, (double)t->velocity);
+  if ((t->flags & SKRED_NOTE_SET_PHASE) && !isfinite(t->phase)) return fail(SKRED_E_BAD_ARG, "note %d: phase %g", k, (double)t->phase);
+  if ((t->flags & SKRED_NOTE_SET_PAN) && (!isfinite(t->pan_left) || !isfinite(t->pan_right)))
+    return fail(SKRED_E_BAD_ARG, "note %d: pan (%g, %g)", k, (double)t->pan_left, (double)t->pan_right);
+  return SKRED_OK;
+}
+
 int skred_notes_check(const skred_note_t *notes, int n) {
   if (!notes || n < 0) return fail(SKRED_E_BAD_ARG, "notes: no notes or n = %d", n);
   for (int k = 0; k < n; k++) {
-    const skred_note_t *t = &notes[k];
-    if (t->flags & ~(uint32_t)(SKRED_NOTE_SET_PHASE | SKRED_NOTE_SET_PAN)) return fail(SKRED_E_BAD_ARG, "note %d: unknown bits in flags = 0x%x", k, t->flags);
-    if (t->reserved[0] || t->reserved[1]) return fail(SKRED_E_BAD_ARG, "note %d: reserved words must be 0", k);
-    /* a non-finite increment or phase would change the voice's class (sk_pack_voice: SKC_EXOTIC) behind the host's back */
-    if (!isfinite(t->phase_inc)) return fail(SKRED_E_BAD_ARG, "note %d: phase_inc %g", k, (double)t->phase_inc);
-    if (!isfinite(t->velocity)) return fail(SKRED_E_BAD_ARG, "note %d: velocity %g", k, (double)t->velocity);
-    if ((t->flags & SKRED_NOTE_SET_PHASE) && !isfinite(t->phase)) return fail(SKRED_E_BAD_ARG, "note %d: phase %g", k, (double)t->phase);
-    if ((t->flags & SKRED_NOTE_SET_PAN) && (!isfinite(t->pan_left) || !isfinite(t->pan_right)))
-      return fail(SKRED_E_BAD_ARG, "note %d: pan (%g, %g)", k, (double)t->pan_left, (double)t->pan_right);
+    const int rc = sk_note_check_one(&notes[k], k);
+    if (rc) return rc;
   }
   return SKRED_OK;
 }
@@ -83,8 +87,8 @@ int skred_bank_notes_on_list(skred_bank_t *b, const skred_note_t *notes, int n, 
   return notes_launch(b, notes, n, d_voices, d_count, first_entry, d_assigned, d_result, (hipStream_t)stream);
 }
 
-/* room for n entries in the bank's own list */
-static int note_list_room(skred_bank_t *b, int n) {
+/* room for n entries in the bank's own list (skred_bank_slots.c: the slot list of skred_bank_note_on_idle_slots) */
+int sk_note_list_room(skred_bank_t *b, int n) {
   if ((size_t)n <= b->note_list_cap) return SKRED_OK;
   /* (hipFree waits for the device: no earlier placement still reads the old list) */
   sk_notes_free(b);
@@ -109,7 +113,7 @@ int skred_bank_note_on_idle(skred_bank_t *b, const skred_idle_query_t *q, const 
   if ((rc = skred_notes_check(notes, n))) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = note_list_room(b, n))) return rc;
+  if ((rc = sk_note_list_room(b, n))) return rc;
   uint32_t *d_count = b->d_note_list;
   int32_t *d_list = (int32_t *)(b->d_note_list + SK_NOTE_LIST_WORDS);
   if ((rc = skred_bank_find_idle(b, &qq, d_list, d_count, stream))) return rc;
@@ -135,7 +139,7 @@ int skred_bank_note_on_steal(skred_bank_t *b, const skred_idle_query_t *idle_q, 
   if ((rc = skred_notes_check(notes, n))) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = note_list_room(b, n))) return rc;
+  if ((rc = sk_note_list_room(b, n))) return rc;
   uint32_t *d_idle_count = b->d_note_list, *d_joined = b->d_note_list + 2;
   int32_t *d_list = (int32_t *)(b->d_note_list + SK_NOTE_LIST_WORDS);
   if ((rc = skred_bank_find_idle(b, &iq, d_list, d_idle_count, stream))) return rc;

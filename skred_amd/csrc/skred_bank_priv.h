@@ -3,7 +3,7 @@
  * (skred_bank.c: lifecycle, tables, upload / download, options, class and tape plan; skred_bank_render.c:
  * one block from request to kernels, as skred_bank_plan.c picks them; skred_bank_update.c: block-granular
  * updates and the deferred queue; skred_bank_idle.c: the free-voice query; skred_bank_steal.c: the victim query; skred_bank_notes.c: note-ons and stamps on voices a
- * device-resident list names).  Not installed.
+ * device-resident list names; skred_bank_slots.c: the same for the slots of a tiled patch).  Not installed.
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -257,6 +257,16 @@ int sk_named_ensure(skred_bank_t *b, hipStream_t s);
 int sk_steal_check_bank(const skred_bank_t *b, const skred_steal_query_t *q, const void *voices, const void *count, const char *who);
 int sk_steal_into_scratch(skred_bank_t *b, const skred_steal_query_t *q, hipStream_t s);
 void sk_notes_free(skred_bank_t *b);         /* skred_bank_notes.c: the list scratch of skred_bank_note_on_idle (skred_bank_destroy) */
+/* skred_bank_notes.c, for skred_bank_slots.c: skred_notes_check's rules on one record; room for n entries in d_note_list */
+int sk_note_check_one(const skred_note_t *t, int k);
+int sk_note_list_room(skred_bank_t *b, int n);
+#define SK_NOTE_LIST_WORDS 4       /* in front of d_note_list's entries: a query's two counts, the joined list's length (note_on_steal), padded to 16 bytes */
+/* skred_bank_idle.c, for skred_bank_slots.c: the scratch both list queries share (allocated on first use), the kernels' view of a
+ * query on this bank, and room for `need` entries in d_idle_out / h_idle_out */
+int sk_idle_scratch(skred_bank_t *b, hipStream_t s);
+void sk_idle_args(const skred_bank_t *b, sk_idle_args_t *a, int first, int count, int from, int max_out, uint32_t which,
+                  float settle_level, int32_t *d_voices, uint32_t *d_count);
+int sk_idle_out_room(skred_bank_t *b, size_t need);
 /* skred_bank_idle.c: everything skred_bank_find_idle refuses, without the device (`voices` / `count`: where the list and the
  * counts would go; `who` names the caller in the error text) */
 int sk_idle_check(const skred_bank_t *b, const skred_idle_query_t *q, const void *voices, const void *count, const char *who);

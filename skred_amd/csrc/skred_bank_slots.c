@@ -1,0 +1,194 @@
+/*
+ * skred_bank_slots.c -- patch notes: idle slots, and note-ons and stamps on the voices of listed slots (include/skred_amd.h:
+ * skred_slot_query_check, skred_slot_notes_check, skred_bank_find_idle_slots / _find_idle_slots_host / _notes_on_slots /
+ * _note_on_idle_slots / _stamp_slots).
+ *
+ * The host side of skred_slot_kernels.hip, built like skred_bank_idle.c and skred_bank_notes.c and on their pieces: the checks (made
+ * before anything touches the device), the bank's idle scratch, the notes' way through the staging ring of the update path, the
+ * launches.  Nothing here waits for the device except the _host query, which waits for its stream.  What a call tells the bank is
+ * what every control action tells it -- with n * popcount(voice_mask) voices, not n: that many more voices may be on the motion
+ * list (touched_total, the bound behind the in-place rule), and earlier launches' reports are out of date.
+ */
+#include <math.h>
+#include <string.h>
+
+#include "skred_bank_priv.h"
+
+#define SK_SLOT_CRITERIA (SKRED_IDLE_FINISHED | SKRED_IDLE_ENV_DONE | SKRED_IDLE_AMP_ZERO)
+
+/* K and a mask over its voices (`what`: which mask, for the error text) */
+static int slot_shape_check(int slot_voices, uint64_t mask, const char *who, const char *what) {
+  if (slot_voices < 1 || slot_voices > 64 || (slot_voices & (slot_voices - 1)))
+    return fail(SKRED_E_RANGE, "%s: slot_voices = %d (a power of two, 1 .. 64)", who, slot_voices);
+  if (!mask) return fail(SKRED_E_BAD_ARG, "%s: %s is 0", who, what);
+  if (slot_voices < 64 && (mask >> slot_voices)) return fail(SKRED_E_BAD_ARG, "%s: %s = 0x%llx has bits at or above slot_voices = %d", who, what, (unsigned long long)mask, slot_voices);
+  return SKRED_OK;
+}
+
+static int slot_query_check(const skred_slot_query_t *q, int n_voices, const char *who) {
+  if (!q) return fail(SKRED_E_BAD_ARG, "%s: no query", who);
+  if (q->max_out < 0) return fail(SKRED_E_BAD_ARG, "%s: max_out %d", who, q->max_out);
+  if (q->which & SKRED_IDLE_UNNAMED) return fail(SKRED_E_BAD_ARG, "%s: SKRED_IDLE_UNNAMED -- the voices of a patch name one another by design", who);
+  if (q->which & ~(uint32_t)SK_SLOT_CRITERIA) return fail(SKRED_E_BAD_ARG, "%s: unknown bits in which = 0x%x", who, q->which);
+  if (!(q->which & SK_SLOT_CRITERIA)) return fail(SKRED_E_BAD_ARG, "%s: which = 0x%x selects no criterion", who, q->which);
+  if (!(q->settle_level >= 0.0f) || isinf(q->settle_level)) return fail(SKRED_E_BAD_ARG, "%s: settle_level %g", who, (double)q->settle_level);
+  const int rc = slot_shape_check(q->slot_voices, q->member_mask, who, "member_mask");
+  if (rc) return rc;
+  const int K = q->slot_voices;
+  if (q->count <= 0 || q->first < 0 || q->first >= n_voices || q->count > n_voices - q->first)
+    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, q->first, q->count, n_voices);
+  if ((q->first & (K - 1)) || (q->count & (K - 1)))
+    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) is not made of whole slots of %d voices", who, q->first, q->count, K);
+  if (q->from < q->first || q->from - q->first >= q->count)
+    return fail(SKRED_E_RANGE, "%s: from = %d outside the range [%d,+%d)", who, q->from, q->first, q->count);
+  if (q->from & (K - 1)) return fail(SKRED_E_RANGE, "%s: from = %d is not the first voice of a slot of %d voices", who, q->from, K);
+  return SKRED_OK;
+}
+
+int skred_slot_query_check(const skred_slot_query_t *q, int n_voices) { return slot_query_check(q, n_voices, "slot_query_check"); }
+
+static int slot_notes_check(const skred_note_t *notes, int n, int slot_voices, uint64_t voice_mask, const char *who) {
+  if (!notes || n < 0) return fail(SKRED_E_BAD_ARG, "%s: no notes or n = %d", who, n);
+  const int rc = slot_shape_check(slot_voices, voice_mask, who, "voice_mask");
+  if (rc) return rc;
+  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);   /* (n * K stays an int) */
+  for (int k = 0; k < n; k++)
+    for (int l = 0; l < slot_voices; l++) {
+      if (!((voice_mask >> l) & 1)) continue;              /* a record no voice receives is not looked at */
+      const int at = k * slot_voices + l, rc1 = sk_note_check_one(&notes[at], at);
+      if (rc1) return rc1;
+    }
+  return SKRED_OK;
+}
+
+int skred_slot_notes_check(const skred_note_t *notes, int n, int slot_voices, uint64_t voice_mask) {
+  return slot_notes_check(notes, n, slot_voices, voice_mask, "slot_notes_check");
+}
+
+static int slots_launch(skred_bank_t *b, const skred_slot_query_t *q, int32_t *d_slots, uint32_t *d_count, hipStream_t s) {
+  HIP_TRY(hipSetDevice(b->device));
+  const int rc = sk_idle_scratch(b, s);
+  if (rc) return rc;
+  sk_slot_args_t a;
+  memset(&a, 0, sizeof(a));
+  sk_idle_args(b, &a.idle, q->first, q->count, q->from, q->max_out, q->which, q->settle_level, d_slots, d_count);
+  a.member_mask = q->member_mask;
+  a.slot_voices = q->slot_voices;
+  if (sk_idle_workgroups(q->first, q->count) > b->idle_wgs) return fail(SKRED_E_RANGE, "find_idle_slots: scratch too small");   /* (unreachable: sized for the bank) */
+  const hipError_t e = (hipError_t)sk_launch_slots(&a, s);
+  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "find_idle_slots launch -> %s", hipGetErrorString(e));
+  return SKRED_OK;
+}
+
+static int slots_check(const skred_bank_t *b, const skred_slot_query_t *q, const void *slots, const void *count, const char *who) {
+  if (!b || !q) return fail(SKRED_E_BAD_ARG, "%s: no bank or no query", who);
+  if (!count) return fail(SKRED_E_BAD_ARG, "%s: nowhere to put the counts", who);
+  if (q->max_out > 0 && !slots) return fail(SKRED_E_BAD_ARG, "%s: max_out %d and no list to fill", who, q->max_out);
+  return slot_query_check(q, b->n_voices, who);
+}
+
+int skred_bank_find_idle_slots(skred_bank_t *b, const skred_slot_query_t *q, int32_t *d_slots, uint32_t *d_count, void *stream) {
+  const int rc = slots_check(b, q, d_slots, d_count, "find_idle_slots");
+  if (rc) return rc;
+  return slots_launch(b, q, d_slots, d_count, (hipStream_t)stream);
+}
+
+int skred_bank_find_idle_slots_host(skred_bank_t *b, const skred_slot_query_t *q, int32_t *slots, int *total_out, void *stream) {
+  int dummy = 0;
+  int rc = slots_check(b, q, slots, &dummy, "find_idle_slots_host");
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(b->device));
+  const size_t need = (size_t)q->max_out;
+  if ((rc = sk_idle_out_room(b, need))) return rc;
+  rc = slots_launch(b, q, b->d_idle_out + 2, (uint32_t *)b->d_idle_out, s);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(b->h_idle_out, b->d_idle_out, (2 + need) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int written = b->h_idle_out[0];
+  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "find_idle_slots_host: the device reported %d slots written of %d", written, q->max_out);
+  if (written > 0) memcpy(slots, b->h_idle_out + 2, (size_t)written * sizeof(int32_t));
+  if (total_out) *total_out = b->h_idle_out[1];
+  return written;
+}
+
+/* what a call adds to touched_total: every voice it MAY put on the motion list -- an upper bound whether or not every note is placed
+ * or every entry is a slot (the count word and the entries are on the device); the bound behind the in-place rule only has to hold */
+static uint64_t slot_touched(int n, uint64_t voice_mask) { return (uint64_t)n * (uint64_t)__builtin_popcountll(voice_mask); }
+
+/* the checked records -> a staging slot (sized for all n * K of them) -> the placement kernel */
+static int slot_notes_launch(skred_bank_t *b, const skred_note_t *notes, int n, int slot_voices, uint64_t voice_mask,
+                             const int32_t *d_slots, const uint32_t *d_count, int first_entry, int32_t *d_assigned,
+                             uint32_t *d_result, hipStream_t s) {
+  HIP_TRY(hipSetDevice(b->device));
+  const size_t bytes = (size_t)n * (size_t)slot_voices * sizeof(skred_note_t);
+  sk_upd_slot_t *sl;
+  const int rc = sk_staging_slot(b, bytes, s, &sl);
+  if (rc) return rc;
+  memcpy(sl->h, notes, bytes);
+  const sk_note_t *src = (const sk_note_t *)sk_stage(sl, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  const int idx = (int)(sl - b->upd);
+  if (++b->upd_seq == 0) b->upd_seq = 1;
+  const hipError_t e = (hipError_t)sk_launch_slot_notes(src, n, slot_voices, voice_mask, d_slots, d_count, first_entry, b->n_voices,
+                                                        b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], d_assigned,
+                                                        d_result, b->d_upd_cnt + idx, (uint32_t *)b->h_upd_done + idx, b->upd_seq, s);
+  if (e != hipSuccess) {
+    (void)hipStreamSynchronize(s);                      /* (a copy into the slot's device twin may be queued: it reads the slot) */
+    return fail(SKRED_E_NO_DEVICE, "slot notes launch -> %s", hipGetErrorString(e));
+  }
+  sl->seq = b->upd_seq;
+  b->touched_total += slot_touched(n, voice_mask);
+  sk_control_changed(b);
+  return SKRED_OK;
+}
+
+int skred_bank_notes_on_slots(skred_bank_t *b, const skred_note_t *notes, int n, int slot_voices, uint64_t voice_mask,
+                              const int32_t *d_slots, const uint32_t *d_count, int first_entry, int32_t *d_assigned,
+                              uint32_t *d_result, void *stream) {
+  if (!b || !notes || !d_slots || !d_count || !d_result) return fail(SKRED_E_BAD_ARG, "notes_on_slots: no bank, notes, list, count or result");
+  if (n < 0 || first_entry < 0) return fail(SKRED_E_BAD_ARG, "notes_on_slots: n = %d, first_entry = %d", n, first_entry);
+  const int rc = slot_notes_check(notes, n, slot_voices, voice_mask, "notes_on_slots");
+  if (rc) return rc;
+  if (n == 0) return SKRED_OK;
+  return slot_notes_launch(b, notes, n, slot_voices, voice_mask, d_slots, d_count, first_entry, d_assigned, d_result, (hipStream_t)stream);
+}
+
+int skred_bank_note_on_idle_slots(skred_bank_t *b, const skred_slot_query_t *q, const skred_note_t *notes, int n, uint64_t voice_mask,
+                                  int32_t *d_assigned, uint32_t *d_result, void *stream) {
+  if (!b || !q || !notes || !d_result) return fail(SKRED_E_BAD_ARG, "note_on_idle_slots: no bank, query, notes or result");
+  if (n < 0) return fail(SKRED_E_BAD_ARG, "note_on_idle_slots: n = %d", n);
+  if (q->which & SKRED_IDLE_AMP_ZERO)
+    return fail(SKRED_E_BAD_ARG, "note_on_idle_slots: SKRED_IDLE_AMP_ZERO -- a note-on leaves voice_amp alone: the slot would stay silent and be listed again");
+  skred_slot_query_t qq = *q;
+  qq.max_out = n;
+  int rc = slots_check(b, &qq, b, b, "note_on_idle_slots");   /* (the list and the counts go into the bank's own scratch) */
+  if (rc) return rc;
+  if ((rc = slot_notes_check(notes, n, q->slot_voices, voice_mask, "note_on_idle_slots"))) return rc;
+  if (n == 0) return SKRED_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(b->device));
+  if ((rc = sk_note_list_room(b, n))) return rc;
+  uint32_t *d_count = b->d_note_list;
+  int32_t *d_list = (int32_t *)(b->d_note_list + SK_NOTE_LIST_WORDS);
+  if ((rc = slots_launch(b, &qq, d_list, d_count, s))) return rc;
+  return slot_notes_launch(b, notes, n, q->slot_voices, voice_mask, d_list, d_count, 0, d_assigned, d_result, s);
+}
+
+int skred_bank_stamp_slots(skred_bank_t *b, const int32_t *d_slots, int n, const uint32_t *d_count_or_null, int slot_voices,
+                           uint64_t voice_mask, uint32_t stamps, void *stream) {
+  if (!b || !d_slots || n < 0) return fail(SKRED_E_BAD_ARG, "stamp_slots: no bank, no list or n = %d", n);
+  if (!stamps || (stamps & ~(uint32_t)(SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)))
+    return fail(SKRED_E_BAD_ARG, "stamp_slots: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", stamps);
+  const int rc = slot_shape_check(slot_voices, voice_mask, "stamp_slots", "voice_mask");
+  if (rc) return rc;
+  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "stamp_slots: n = %d", n);
+  if (n == 0) return SKRED_OK;
+  HIP_TRY(hipSetDevice(b->device));
+  const hipError_t e = (hipError_t)sk_launch_slot_stamps(d_slots, n, d_count_or_null, slot_voices, voice_mask, b->n_voices, stamps,
+                                                         b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], (hipStream_t)stream);
+  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "stamp_slots launch -> %s", hipGetErrorString(e));
+  b->touched_total += slot_touched(n, voice_mask);
+  sk_control_changed(b);
+  return SKRED_OK;
+}

@@ -24,83 +24,22 @@
 #include <stdint.h>
 
 #include "skred_idle_common.hpp"   // sk_idle_pred: the predicate of one voice
+#include "skred_idle_scan.hpp"     // the counts, the last arriver's offsets and the rotated scatter (shared with skred_slot_kernels.hip)
 #include "skred_kernel_common.hpp"
 #include "skred_launch.h"
 
-#define SK_IDLE_WAVES (SK_IDLE_SPAN / 64)
-
-__device__ __forceinline__ int sk_idle_voice(const sk_idle_args_t &a, bool &in_range) {
-  const int v = a.base + (int)blockIdx.x * SK_IDLE_SPAN + (int)threadIdx.x;   // base: `first` rounded down to 64
-  in_range = v >= a.first && v < a.end;
-  return v;
-}
-
 __global__ __launch_bounds__(SK_IDLE_SPAN) void sk_idle_count_kernel(sk_idle_args_t a) {
-  __shared__ int lds[SK_IDLE_SPAN + 2 * SK_IDLE_WAVES + 1];
-  const int tid = threadIdx.x, wave = tid >> 6;
+  __shared__ int lds[SK_IDLE_COUNT_LDS];
   bool in_range;
   const int v = sk_idle_voice(a, in_range);
-  const bool idle = sk_idle_pred(a, v, in_range);
-  const unsigned long long ballot = __ballot(idle);
-  // the rank of `from`: the idle voices below it.  Its workgroup counts the ones inside its own span.
-  const unsigned long long below = __ballot(idle && v < a.from);
-  if ((tid & 63) == 0) { lds[wave] = __popcll(ballot); lds[SK_IDLE_WAVES + wave] = __popcll(below); }
-  __syncthreads();
-  if (tid == 0) {
-    int c = 0, p = 0;
-#pragma unroll
-    for (int w = 0; w < SK_IDLE_WAVES; ++w) { c += lds[w]; p += lds[SK_IDLE_WAVES + w]; }
-    __hip_atomic_store((sk_gu32 *)(a.counts + blockIdx.x), (uint32_t)c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if ((int)blockIdx.x == a.from_wg)
-      __hip_atomic_store((sk_gu32 *)(a.words + SK_IDLE_W_PART), (uint32_t)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!sk_arrive_last(a.words + SK_IDLE_W_TICKET, gridDim.x, tid, &lds[2 * SK_IDLE_WAVES])) return;
-  // ---- the last arriver: exclusive offsets of all workgroups, in index order.  Thread t owns a contiguous run of counts.
-  const int n = (int)gridDim.x;
-  const int per = (n + SK_IDLE_SPAN - 1) / SK_IDLE_SPAN;
-  const int lo = min(tid * per, n), hi = min(lo + per, n);
-  int sum = 0;
-  for (int i = lo; i < hi; ++i) sum += (int)a.counts[i];
-  int *scan = &lds[2 * SK_IDLE_WAVES + 1];
-  scan[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < SK_IDLE_SPAN; d <<= 1) {          // inclusive scan of the per-thread sums
-    const int add = tid >= d ? scan[tid - d] : 0;
-    __syncthreads();
-    scan[tid] += add;
-    __syncthreads();
-  }
-  int run = scan[tid] - sum;
-  for (int i = lo; i < hi; ++i) {
-    a.offsets[i] = (uint32_t)run;
-    if (i == a.from_wg) a.words[SK_IDLE_W_RANK] = (uint32_t)run + a.words[SK_IDLE_W_PART];
-    run += (int)a.counts[i];
-  }
-  if (tid == SK_IDLE_SPAN - 1) {
-    const uint32_t total = (uint32_t)scan[tid];
-    a.words[SK_IDLE_W_TOTAL] = total;
-    a.d_count[0] = total < (uint32_t)a.max_out ? total : (uint32_t)a.max_out;
-    a.d_count[1] = total;
-  }
+  sk_idle_count_tail(a, v, sk_idle_pred(a, v, in_range), lds);
 }
 
 __global__ __launch_bounds__(SK_IDLE_SPAN) void sk_idle_scatter_kernel(sk_idle_args_t a) {
   __shared__ int lds[SK_IDLE_WAVES];
-  const int tid = threadIdx.x, wave = tid >> 6;
   bool in_range;
   const int v = sk_idle_voice(a, in_range);
-  const bool idle = sk_idle_pred(a, v, in_range);
-  const unsigned long long ballot = __ballot(idle);
-  if ((tid & 63) == 0) lds[wave] = __popcll(ballot);
-  __syncthreads();
-  if (!idle) return;
-  int rank = (int)a.offsets[blockIdx.x];
-  for (int w = 0; w < wave; ++w) rank += lds[w];
-  rank += (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
-  const int total = (int)a.words[SK_IDLE_W_TOTAL];
-  int at = rank - (int)a.words[SK_IDLE_W_RANK];       // the list starts at the first idle voice >= from and wraps
-  if (at < 0) at += total;
-  if (at >= 0 && at < a.max_out) a.d_voices[at] = v;
+  sk_idle_scatter_tail(a, v, sk_idle_pred(a, v, in_range), lds);
 }
 
 // one thread per voice of the padded bank; `named` was cleared ahead of the launch

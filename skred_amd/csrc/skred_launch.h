@@ -14,10 +14,11 @@
  *   skred_idle_kernels.hip    sk_launch_idle, sk_idle_workgroups, sk_launch_named
  *   skred_note_kernels.hip    sk_launch_notes, sk_launch_stamp_list
  *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_steal_select, sk_launch_list_append
+ *   skred_slot_kernels.hip    sk_launch_slots, sk_launch_slot_notes, sk_launch_slot_stamps
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
- * skred_bank_steal.c, skred_bank_notes.c and skred_recorder.c.
+ * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c and skred_recorder.c.
  */
 #ifndef SKRED_LAUNCH_H
 #define SKRED_LAUNCH_H
@@ -190,6 +191,31 @@ int sk_launch_steal_select(const sk_steal_args_t *args, hipStream_t stream);
  * stolen[0] = copied.  One workgroup: room - at is at most SK_STEAL_MAX entries (src holds no more) */
 int sk_launch_list_append(int32_t *dst, const uint32_t *dst_count, const int32_t *src, const uint32_t *src_count, int room,
                           uint32_t *out_count, uint32_t *stolen, hipStream_t stream);
+
+/* ---- patch notes: idle slots, and notes and stamps on the voices of listed slots (skred_bank_slots.c -> skred_slot_kernels.hip;
+ * include/skred_amd.h: skred_bank_find_idle_slots / _notes_on_slots / _stamp_slots) ----
+ * A slot: slot_voices = K consecutive voices from a multiple of K (K a power of two <= 64), named by its first voice.  The query is
+ * the free-voice query with another notion of "listed": `idle` holds the planes, the range, `from`, max_out, the criteria (never
+ * SK_IDLE_UNNAMED) and the bank's idle scratch; d_voices receives first voices of slots. */
+typedef struct {
+  sk_idle_args_t idle;
+  uint64_t member_mask;            /* bit l: voice l of a slot takes part in the idle test */
+  int32_t slot_voices;
+} sk_slot_args_t;
+int sk_launch_slots(const sk_slot_args_t *args, hipStream_t stream);   /* count, then (max_out > 0) scatter */
+/* note k (records d_notes[k * K .. k * K + K)) -> the slot d_slots[first_entry + k] while first_entry + k < d_count[0] and the entry
+ * is a slot of the bank (>= 0, a multiple of K, entry + K <= n_voices); only voices with a bit in voice_mask are stored to, only
+ * their records read.  d_assigned[n] (or NULL) and d_result[2] = placed, dropped notes; the rest as sk_launch_notes.  More than
+ * one workgroup (n * K > SK_NOTE_SPAN): d_result is zeroed on `stream` ahead of the launch */
+int sk_launch_slot_notes(const sk_note_t *d_notes, int n, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
+                         const uint32_t *d_count, int first_entry, int n_voices, sk_plane_t *const ro[SKP_COUNT],
+                         sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask, int32_t *d_assigned, uint32_t *d_result,
+                         uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* sk_launch_stamp_list on the masked voices of the first min(n, d_count[0]) listed slots (d_count NULL: n); entries that are no
+ * slot of the bank are skipped */
+int sk_launch_slot_stamps(const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, uint64_t voice_mask, int n_voices,
+                          uint32_t dirty, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t now,
+                          uint64_t *mask, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

@@ -43,20 +43,7 @@ __global__ __launch_bounds__(SK_NOTE_SPAN) void sk_notes_kernel(const sk_note_t 
   }
   if (v >= 0) {
     const sk_note_t r = notes[k];
-    sk_list_voice(mask, v);
-    reinterpret_cast<uint32_t *>(&p.ro[SKP_OSC][v])[0] = r.w[SK_NOTE_PHASE_INC];
-    reinterpret_cast<uint32_t *>(&p.ro[SKP_GAIN][v])[0] = r.w[SK_NOTE_VELOCITY];
-    const uint32_t flags = r.w[SK_NOTE_FLAGS];
-    uint32_t *rwflags = reinterpret_cast<uint32_t *>(&p.rw[SKS_FILT][v]) + 3;
-    uint32_t f = *rwflags | SKR_ENV_ACTIVE;
-    if (flags & SK_NOTE_SET_PHASE) {
-      reinterpret_cast<uint32_t *>(&p.rw[SKS_OSC][v])[0] = r.w[SK_NOTE_PHASE];
-      f &= ~SKR_FINISHED;
-    }
-    *rwflags = f;
-    if (flags & SK_NOTE_SET_PAN)
-      *reinterpret_cast<uint2 *>(reinterpret_cast<uint32_t *>(&p.rw[SKS_MISC][v]) + 2) = make_uint2(r.w[SK_NOTE_PAN_LEFT], r.w[SK_NOTE_PAN_RIGHT]);
-    *reinterpret_cast<uint4 *>(&p.ro[SKP_ENV_S][v]) = make_uint4((uint32_t)now, (uint32_t)(now >> 32), 0u, 0u);
+    sk_note_store(p, now, mask, v, r);
   }
   if (d_assigned && k < n) d_assigned[k] = v;
   const unsigned long long placed = __ballot(v >= 0);
@@ -80,19 +67,7 @@ __global__ __launch_bounds__(256) void sk_stamp_list_kernel(const int32_t *d_voi
   if (d_count && (uint32_t)i >= d_count[0]) return;
   const int v = d_voices[i];
   if (v < 0 || v >= n_voices) return;
-  sk_list_voice(mask, v);
-  uint32_t *rwflags = reinterpret_cast<uint32_t *>(&p.rw[SKS_FILT][v]) + 3;
-  uint4 es = *reinterpret_cast<const uint4 *>(&p.ro[SKP_ENV_S][v]);
-  uint32_t f = *rwflags;
-  if (dirty & SKU_STAMP_TRIGGER) {
-    es.x = (uint32_t)now; es.y = (uint32_t)(now >> 32); es.z = 0; es.w = 0;
-    f |= SKR_ENV_ACTIVE;
-  }
-  if ((dirty & SKU_STAMP_RELEASE) && (f & SKR_ENV_ACTIVE)) {
-    es.z = (uint32_t)now; es.w = (uint32_t)(now >> 32);
-  }
-  *reinterpret_cast<uint4 *>(&p.ro[SKP_ENV_S][v]) = es;
-  *rwflags = f;
+  sk_stamp_store(p, now, mask, v, dirty);
 }
 
 static void sk_note_planes(sk_plane_ptrs_t &p, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT]) {

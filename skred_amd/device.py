@@ -11,7 +11,7 @@ from typing import Optional
 
 import numpy as np
 
-from .bank import GlobalsC, VoiceBank, VoiceBankC
+from .bank import GlobalsC, SlotQueryC, VoiceBank, VoiceBankC, slot_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKRED_AMD_LIB", os.path.join(_HERE, "libskred_amd.so"))   # override: A/B builds
@@ -38,9 +38,11 @@ ABI_SYMBOLS = [
     "skred_bank_find_idle", "skred_bank_find_idle_host",
     "skred_bank_notes_on_list", "skred_bank_note_on_idle", "skred_bank_stamp_list",
     "skred_bank_find_steal", "skred_bank_find_steal_host", "skred_bank_note_on_steal",
+    "skred_bank_find_idle_slots", "skred_bank_find_idle_slots_host", "skred_bank_notes_on_slots", "skred_bank_note_on_idle_slots",
+    "skred_bank_stamp_slots",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
-HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check"]
+HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -182,6 +184,13 @@ def load() -> C.CDLL:
     L.skred_bank_find_steal.argtypes = [vp, C.POINTER(StealQueryC), vp, vp, vp]
     L.skred_bank_find_steal_host.argtypes = [vp, C.POINTER(StealQueryC), vp, C.POINTER(i32), vp]
     L.skred_bank_note_on_steal.argtypes = [vp, C.POINTER(IdleQueryC), C.POINTER(StealQueryC), vp, i32, vp, vp, vp]
+    L.skred_slot_query_check.argtypes = [C.POINTER(SlotQueryC), i32]
+    L.skred_slot_notes_check.argtypes = [vp, i32, i32, C.c_uint64]
+    L.skred_bank_find_idle_slots.argtypes = [vp, C.POINTER(SlotQueryC), vp, vp, vp]
+    L.skred_bank_find_idle_slots_host.argtypes = [vp, C.POINTER(SlotQueryC), vp, C.POINTER(i32), vp]
+    L.skred_bank_notes_on_slots.argtypes = [vp, vp, i32, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_note_on_idle_slots.argtypes = [vp, C.POINTER(SlotQueryC), vp, i32, C.c_uint64, vp, vp, vp]
+    L.skred_bank_stamp_slots.argtypes = [vp, vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp]
     _lib = L
     return L
 
@@ -201,6 +210,18 @@ def notes_check(notes) -> int:
 def steal_check(q: StealQueryC, n_voices: int) -> int:
     """skred_steal_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for a query the bank entry points would refuse.  Pure host."""
     return int(load().skred_steal_check(C.byref(q) if q is not None else None, int(n_voices)))
+
+
+def slot_query_check(q: SlotQueryC, n_voices: int) -> int:
+    """skred_slot_query_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for a query find_idle_slots would refuse.  Pure host."""
+    return int(load().skred_slot_query_check(C.byref(q) if q is not None else None, int(n_voices)))
+
+
+def slot_notes_check(notes, slot_voices: int, voice_mask: int) -> int:
+    """skred_slot_notes_check on len(notes) // slot_voices patch notes (record k * K + l: voice l of note k).  Pure host."""
+    arr = note_array(notes)
+    return int(load().skred_slot_notes_check(C.cast(arr, C.c_void_p), len(arr) // max(int(slot_voices), 1), int(slot_voices),
+                                             int(voice_mask)))
 
 
 class DeviceBank:
@@ -392,6 +413,47 @@ class DeviceBank:
         arr = note_array(notes)
         _check(self.L.skred_bank_note_on_steal(self.h, C.byref(idle_q), C.byref(steal_q), C.cast(arr, C.c_void_p), len(arr),
                                                d_assigned or None, d_result or None, stream or None), "skred_bank_note_on_steal")
+
+    # ---- patch notes (include/skred_amd.h: skred_bank_find_idle_slots / _notes_on_slots / _note_on_idle_slots / _stamp_slots) ----
+    def find_idle_slots(self, q: SlotQueryC, d_slots: int = 0, d_count: int = 0, stream: int = 0):
+        """Asynchronous on `stream`: the first voices of the idle slots of q's range, ascending from q.start and wrapping, into
+        d_slots[0 .. written) (int32, device memory); d_count[0] = written, d_count[1] = total (uint32)."""
+        _check(self.L.skred_bank_find_idle_slots(self.h, C.byref(q), d_slots or None, d_count or None, stream or None),
+               "skred_bank_find_idle_slots")
+
+    def find_idle_slots_host(self, q: SlotQueryC, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the listed slots, total)."""
+        out = np.empty(max(int(q.max_out), 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_bank_find_idle_slots_host(self.h, C.byref(q), out.ctypes.data if q.max_out > 0 else None, C.byref(total),
+                                                   stream or None)
+        if n < 0:
+            _check(n, "skred_bank_find_idle_slots_host")
+        return out[:n].copy(), int(total.value)
+
+    def notes_on_slots(self, notes, slot_voices: int, voice_mask: int, d_slots: int, d_count: int, first_entry: int = 0,
+                       d_assigned: int = 0, d_result: int = 0, stream: int = 0):
+        """Asynchronous on `stream`: patch note k (records notes[k * K : k * K + K]) goes to the slot d_slots[first_entry + k] while
+        that entry is below d_count[0] and is a slot of the bank, else it is dropped; only voices with a bit in voice_mask are
+        stored to.  d_assigned[k] (int32, may be 0) = the slot or -1; d_result[0] = placed, d_result[1] = dropped notes (uint32)."""
+        arr = note_array(notes)
+        _check(self.L.skred_bank_notes_on_slots(self.h, C.cast(arr, C.c_void_p), len(arr) // int(slot_voices), int(slot_voices),
+                                                int(voice_mask), d_slots or None, d_count or None, int(first_entry),
+                                                d_assigned or None, d_result or None, stream or None), "skred_bank_notes_on_slots")
+
+    def note_on_idle_slots(self, notes, q: SlotQueryC, voice_mask: int, d_assigned: int = 0, d_result: int = 0, stream: int = 0):
+        """The query of find_idle_slots (room for the batch, in scratch the bank owns) and the placement of the patch notes on its
+        list, in one call; IDLE_AMP_ZERO is refused."""
+        arr = note_array(notes)
+        _check(self.L.skred_bank_note_on_idle_slots(self.h, C.byref(q), C.cast(arr, C.c_void_p), len(arr) // int(q.slot_voices),
+                                                    int(voice_mask), d_assigned or None, d_result or None, stream or None),
+               "skred_bank_note_on_idle_slots")
+
+    def stamp_slots(self, d_slots: int, n: int, slot_voices: int, voice_mask: int, stamps: int, d_count: int = 0, stream: int = 0):
+        """STAMP_TRIGGER / STAMP_RELEASE on the masked voices of the first min(n, d_count[0]) listed slots (d_count 0: n entries);
+        entries that are no slot of the bank -- the -1 of a dropped note -- are skipped."""
+        _check(self.L.skred_bank_stamp_slots(self.h, d_slots or None, int(n), d_count or None, int(slot_voices), int(voice_mask),
+                                             int(stamps), stream or None), "skred_bank_stamp_slots")
 
     def force_generic(self, on: bool = True):
         _check(self.L.skred_bank_set_option(self.h, 1, int(on)), "skred_bank_set_option")

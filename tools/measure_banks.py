@@ -38,6 +38,11 @@
              skred_fxbank_download of the bank, the idle pick and the victim order in numpy, skred_fxbank_upload of the chosen voices,
              skred_fxbank_stamp -- host-held time and the stream time of upload + stamp; (c) skred_fxbank_find_steal alone at max_out
              0 (its first launch), 16 and 1 024
+  slots      patch notes: 256 notes on bank_patch("3sk", 2^20) with the three carriers of every copy enveloped and 600 copies at rest
+             (medians of 12 with minimum and maximum): (a) skred_bank_note_on_idle_slots -- stream time between an event pair and
+             the time the call held the host; (b) skred_bank_find_idle_host, the grouping of its voices into copies in numpy,
+             skred_bank_update of the chosen copies' voices; (c) skred_bank_download, the predicate and the grouping in numpy,
+             skred_bank_update -- (b) and (c): the time the route held the host
 
 Each line: ms per block over the timed blocks (wall clock), voice-samples/s, and the render kernel's duration from the
 library's own event pair around the latest bracketed launch (a bracketed launch runs alone).  kernels / fm / noise print
@@ -635,8 +640,103 @@ def fxsteal():
     db.close()
 
 
+def slots():
+    """256 patch notes on bank_patch("3sk", 2**20) -- the three carriers of every copy enveloped, a few hundred copies at rest -- through
+    skred_bank_note_on_idle_slots, against the two routes a host had before it: find_idle_host + grouping in numpy + skred_bank_update,
+    and skred_bank_download + the predicate and the grouping in numpy + skred_bank_update.  Medians of 12."""
+    D = device
+    n, K, NOTES, REST, REPS = 1 << 20, 4, 256, 600, 12
+    MEMBERS, VOICES = 0x7, 0xF                                # the enveloped carriers; a note re-pitches the shared modulator too
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    lane = np.arange(n) % K
+    sel = lane < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel], e["sample_start"][sel] = 1.0, 1, np.uint64(now - 40000)
+    rng = np.random.default_rng(3)
+    rest = np.sort(rng.choice(n // K, REST, replace=False)) * K
+    for l in range(3):
+        e["is_active"][rest + l] = 0                          # at rest: envelope over, smoother gain exactly 0
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g)
+    which = D.IDLE_ENV_DONE
+    q = D.slot_query(0, n, K, MEMBERS, which, 1e-3, n // 2, NOTES)
+    notes = D.note_array([D.NoteC(0.4 + 0.001 * i, 0.8, 0.0, 0.5, 0.5, D.NOTE_SET_PHASE) for i in range(NOTES * K)])
+    da = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(2, dtype=torch.int32, device="cuda")
+    mirror = bank.copy()
+    dirty = D.DIRTY_PARAMS | D.DIRTY_PHASE | D.STAMP_TRIGGER
+    inc = np.array([t.phase_inc for t in notes], np.float32).reshape(NOTES, K)
+
+    def place_on_host(picks):
+        vs = (picks[:, None] + np.arange(K)[None, :]).astype(np.int32)
+        mirror["voice_phase_inc"][vs] = inc[:len(picks)]
+        mirror["voice_amp_envelope"]["velocity"][vs] = np.float32(0.8)
+        mirror["voice_phase"][vs] = 0.0
+        mirror["voice_finished"][vs] = 0
+        db.update(mirror, vs.reshape(-1), dirty)
+
+    def group(idle_voices):
+        s, c = np.unique(idle_voices[(idle_voices % K) < 3] // K, return_counts=True)
+        free = s[c == 3] * K
+        k = int(np.searchsorted(free, n // 2))
+        return np.concatenate([free[k:], free[:k]])[:NOTES]
+
+    def device_route():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        db.note_on_idle_slots(notes, q, VOICES, da.data_ptr(), dr.data_ptr())
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1), dr.cpu().numpy().tolist()
+
+    def list_route():
+        t0 = time.perf_counter()
+        voices, total = db.find_idle_host(0, n, which, 1e-3, None, 8192)
+        assert total <= 8192
+        picks = group(voices)
+        place_on_host(picks)
+        return (time.perf_counter() - t0) * 1e3, None, [len(picks), NOTES - len(picks)]
+
+    got = bank.copy()
+
+    def download_route():
+        t0 = time.perf_counter()
+        db.download(got)
+        a, env = got.a, got.a["voice_amp_envelope"]
+        idle = np.flatnonzero((a["voice_use_amp_envelope"] != 0) & (env["is_active"] == 0) &
+                              ((a["voice_smoother_enable"] == 0) | (np.abs(a["voice_smoother_gain"]) <= np.float32(1e-3))))
+        picks = group(idle)
+        place_on_host(picks)
+        return (time.perf_counter() - t0) * 1e3, None, [len(picks), NOTES - len(picks)]
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, {REST} slots at rest, {NOTES} patch notes ({NOTES * K} records), medians of {REPS}")
+    for label, route in (("note_on_idle_slots (query + placement on the device)", device_route),
+                         ("find_idle_host + grouping in numpy + skred_bank_update", list_route),
+                         ("skred_bank_download + predicate and grouping in numpy + skred_bank_update", download_route)):
+        host, stream, res = [], [], None
+        for it in range(2 + REPS):
+            db.upload(bank)
+            torch.cuda.synchronize()
+            h, s_ms, res = route()
+            torch.cuda.synchronize()
+            if it >= 2:
+                host.append(h)
+                if s_ms is not None:
+                    stream.append(s_ms)
+        line = f"  {label}: host time median {np.median(host):.4f} ms (min {np.min(host):.4f}, max {np.max(host):.4f})"
+        if stream:
+            line += f"; stream time between events median {np.median(stream):.4f} ms (min {np.min(stream):.4f}, max {np.max(stream):.4f})"
+        print(line + f"; placed, dropped = {res}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
