@@ -676,6 +676,81 @@ int  skred_bank_note_on_idle_slots(skred_bank_t *bank, const skred_slot_query_t 
 int  skred_bank_stamp_slots(skred_bank_t *bank, const int32_t *d_slots, int n, const uint32_t *d_count_or_null,
                             int slot_voices, uint64_t voice_mask, uint32_t stamps, void *stream);
 
+/* ---- slot stealing: the sounding copies of a tiled patch that matter least, ranked on the device ------------------------------
+ *
+ * skred_bank_note_on_idle_slots drops what the idle slots cannot take; a synthesizer steals.  The victims of skred_bank_find_steal
+ * are single voices of many different copies and cannot serve a patch: these calls are the stealing calls above, stated on slots.
+ *
+ * A slot, K = slot_voices and member_mask mean what they mean for skred_slot_query_t; voice_mask what it means for
+ * skred_bank_notes_on_slots.  The definition, on the fields AS THE DEVICE HOLDS THEM at that point of the stream; every comparison
+ * is exact; `now` is synth_sample_count as the bank has it at application time.  For voice l of a slot:
+ *   member(l)   := bit l of member_mask
+ *   live(l)     := member(l) && voice_use_amp_envelope != 0 && is_active != 0
+ *   released(l) := sample_release != 0
+ *   age(l)      := sample_start > now ? 0 : now - sample_start
+ *   idle(l)     := skred_bank_find_idle's predicate for (exclude_idle, settle_level)
+ *   slot candidate := the slot inside the range
+ *                  && some l is live
+ *                  && every live l has age(l) >= min_age
+ *                  && (with RELEASED_ONLY: every live l is released)
+ *                  && NOT (exclude_idle != 0 && every member l is idle(l))
+ *   class   := 0 when RELEASED_FIRST is set and every live l is released, else 1
+ *   primary := OLDEST:   max over live l of (sample_release in class 0, sample_start in class 1)
+ *              QUIETEST: max over live l of (the bits of fabsf(voice_smoother_gain) when voice_smoother_enable != 0, else 0x7fffffff)
+ *   key     := class << 62 | min(primary, 2^62 - 1)
+ * A slot is as young as its youngest live member, released as late as its last released member and as loud as its loudest live
+ * member.  Victim order: ascending key, ties by ascending first voice.  Voices outside member_mask are never read; members that are
+ * not live count for nothing in age, class or key.  SKRED_STEAL_UNNAMED is refused, in flags and in exclude_idle: the voices of a
+ * patch name one another by design.  With K = 1 and mask 1 every line is the per-voice definition, and the calls write the bytes
+ * of skred_bank_find_steal and skred_bank_note_on_steal. */
+typedef struct skred_slot_steal_query {   /* 56 bytes */
+  int32_t  first, count;     /* voice range; first % K == 0, count % K == 0, count > 0, inside the bank */
+  int32_t  slot_voices;      /* K: a power of two, 1 .. 64 */
+  uint32_t policy;           /* SKRED_STEAL_OLDEST or SKRED_STEAL_QUIETEST */
+  uint64_t member_mask;      /* bit l: voice l of a slot takes part; non-zero, no bits at or above K */
+  uint64_t min_age;          /* frames: a slot with a younger live member is protected */
+  uint32_t flags;            /* SKRED_STEAL_RELEASED_FIRST | _RELEASED_ONLY; SKRED_STEAL_UNNAMED refused */
+  uint32_t exclude_idle;     /* SKRED_IDLE_FINISHED | _ENV_DONE | _AMP_ZERO (0: none): slots these call idle are no candidates */
+  float    settle_level;     /* for exclude_idle's ENV_DONE */
+  int32_t  max_out;          /* 0 .. SKRED_STEAL_MAX, in slots; 0: count only */
+  uint32_t reserved[2];      /* 0 */
+} skred_slot_steal_query_t;
+
+/* Pure host, no device: SKRED_OK, or SKRED_E_BAD_ARG for a NULL query, an unknown policy, unknown bits or SKRED_STEAL_UNNAMED in
+ * flags, unknown bits or SKRED_IDLE_UNNAMED in exclude_idle, non-zero reserved words, max_out outside [0, SKRED_STEAL_MAX], a
+ * settle_level that is negative or not finite, a member_mask that is 0 or has bits at or above K; SKRED_E_RANGE for K not a power
+ * of two in 1 .. 64, count <= 0, a range outside a bank of n_voices voices, first or count not a multiple of K.  The entry points
+ * below call it before anything touches the device. */
+int  skred_slot_steal_check(const skred_slot_steal_query_t *q, int n_voices);
+
+/* skred_bank_find_steal on slots, under its contract: asynchronous on `stream`; d_slots[0 .. written) = the first voices of the
+ * first min(total, max_out) slots of the victim order, d_count[0] = written, d_count[1] = total candidate slots (device memory);
+ * entries past `written` are not touched.  Reads the bank only; the same state gives the same bytes.  The radix select of
+ * skred_bank_find_steal behind a key pass of its own (one key per slot, reduced over the members inside a wavefront): the same nine
+ * launches (one with max_out == 0), the same scratch -- one stream at a time per bank --, no workgroup ever waits for another.
+ * Refused before anything touches the device: what skred_slot_steal_check refuses, and SKRED_E_BAD_ARG for a NULL bank, query or
+ * d_count, or a NULL d_slots with max_out > 0.  On a shard: through skred_shard_bank(), with that rank's local indices.  Not in
+ * the fixed-point bank or the drop-in mode. */
+int  skred_bank_find_steal_slots(skred_bank_t *bank, const skred_slot_steal_query_t *q, int32_t *d_slots, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only.  Returns `written` (>= 0) or a SKRED_E_* code; *total_out may be NULL. */
+int  skred_bank_find_steal_slots_host(skred_bank_t *bank, const skred_slot_steal_query_t *q, int32_t *slots, int *total_out, void *stream);
+/* A burst of n patch notes (n * K records, as for skred_bank_notes_on_slots) on a tiled instrument whose polyphony may be used
+ * up, all on the device: the idle-slot query `idle_q` into scratch the bank owns (max_out = n), the slot steal query `steal_q` with
+ * exclude_idle = idle_q->which, settle_level = idle_q->settle_level and max_out = min(n, SKRED_STEAL_MAX) (the library overrides
+ * those three fields; because of the exclusion the two lists are disjoint), the victims appended behind the idle slots, and the
+ * notes placed on the joined list as skred_bank_notes_on_slots places them, first_entry = 0: idle slots take the first notes,
+ * victims the next, in victim order; what is left is dropped whole.  A stolen slot gets exactly a patch note's stores on its
+ * voice_mask voices: they are re-triggered, their filter memory and smoothers carry on; voices outside voice_mask are untouched.
+ * d_result (device, uint32[3], required): [0] notes placed, [1] notes dropped, [2] how many of the placed notes went to stolen
+ * slots; d_assigned as for skred_bank_notes_on_slots.  The host never learns the counts and waits for nothing.  n == 0: SKRED_OK,
+ * nothing is done.  Refused before anything touches the device: what skred_bank_note_on_idle_slots (SKRED_IDLE_AMP_ZERO among it)
+ * and skred_bank_find_steal_slots refuse, and SKRED_E_BAD_ARG when the two queries differ in slot_voices or member_mask (their
+ * ranges may differ; each is made of whole slots).  On a shard: through skred_shard_bank().  Not in the fixed-point bank or the
+ * drop-in mode. */
+int  skred_bank_note_on_steal_slots(skred_bank_t *bank, const skred_slot_query_t *idle_q, const skred_slot_steal_query_t *steal_q,
+                                    const skred_note_t *notes, int n, uint64_t voice_mask, int32_t *d_assigned, uint32_t *d_result,
+                                    void *stream);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

@@ -117,6 +117,19 @@ def slot_query(first: int, count: int, slot_voices: int, member_mask: int, which
                       int(first if start is None else start), int(max_out))
 
 
+class SlotStealQueryC(C.Structure):
+    """ctypes image of ``skred_slot_steal_query_t`` (56 bytes): the victim query on the slots of a tiled patch."""
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("slot_voices", C.c_int32), ("policy", C.c_uint32),
+                ("member_mask", C.c_uint64), ("min_age", C.c_uint64), ("flags", C.c_uint32), ("exclude_idle", C.c_uint32),
+                ("settle_level", C.c_float), ("max_out", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+def slot_steal_query(first: int, count: int, slot_voices: int, member_mask: int, policy: int = 0, flags: int = 0, min_age: int = 0,
+                     exclude_idle: int = 0, settle_level: float = 0.0, max_out: int = 0) -> SlotStealQueryC:
+    return SlotStealQueryC(int(first), int(count), int(slot_voices), int(policy), int(member_mask), int(min_age), int(flags),
+                           int(exclude_idle), float(settle_level), int(max_out))
+
+
 class VoiceBank:
     """N voices, one numpy array per reference field.  Defaults follow voice_reset (synth.c:1090-1132)
     for everything that does not need a table: silent (amp 0), centre pan, smoother on (k=0.02),

@@ -256,6 +256,10 @@ int sk_named_ensure(skred_bank_t *b, hipStream_t s);
  * bank's own d_steal_out (counts in its first two words) */
 int sk_steal_check_bank(const skred_bank_t *b, const skred_steal_query_t *q, const void *voices, const void *count, const char *who);
 int sk_steal_into_scratch(skred_bank_t *b, const skred_steal_query_t *q, hipStream_t s);
+/* ... for skred_bank_slots.c (slot stealing): the scratch (allocated by the first query) and every argument of a query's launches
+ * (`now` as the stamps take it); the bank's d_steal_out / h_steal_out */
+int sk_steal_prepare(skred_bank_t *b, const skred_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s, sk_steal_args_t *a);
+int sk_steal_out_buffers(skred_bank_t *b);
 void sk_notes_free(skred_bank_t *b);         /* skred_bank_notes.c: the list scratch of skred_bank_note_on_idle (skred_bank_destroy) */
 /* skred_bank_notes.c, for skred_bank_slots.c: skred_notes_check's rules on one record; room for n entries in d_note_list */
 int sk_note_check_one(const skred_note_t *t, int k);

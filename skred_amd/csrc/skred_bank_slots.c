@@ -1,7 +1,8 @@
 /*
  * skred_bank_slots.c -- patch notes: idle slots, and note-ons and stamps on the voices of listed slots (include/skred_amd.h:
  * skred_slot_query_check, skred_slot_notes_check, skred_bank_find_idle_slots / _find_idle_slots_host / _notes_on_slots /
- * _note_on_idle_slots / _stamp_slots).
+ * _note_on_idle_slots / _stamp_slots), and slot stealing (skred_slot_steal_check, skred_bank_find_steal_slots / _find_steal_slots_host /
+ * _note_on_steal_slots): the victim query of skred_bank_steal.c behind the key pass of skred_slot_steal_kernels.hip.
  *
  * The host side of skred_slot_kernels.hip, built like skred_bank_idle.c and skred_bank_notes.c and on their pieces: the checks (made
  * before anything touches the device), the bank's idle scratch, the notes' way through the staging ring of the update path, the
@@ -10,9 +11,14 @@
  * list (touched_total, the bound behind the in-place rule), and earlier launches' reports are out of date.
  */
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 #include "skred_bank_priv.h"
+
+_Static_assert(sizeof(skred_slot_steal_query_t) == 56 && offsetof(skred_slot_steal_query_t, member_mask) == 16 &&
+               offsetof(skred_slot_steal_query_t, flags) == 32 && offsetof(skred_slot_steal_query_t, reserved) == 48,
+               "skred_slot_steal_query_t is 56 bytes (skred_amd/bank.py: SlotStealQueryC)");
 
 #define SK_SLOT_CRITERIA (SKRED_IDLE_FINISHED | SKRED_IDLE_ENV_DONE | SKRED_IDLE_AMP_ZERO)
 
@@ -191,4 +197,115 @@ int skred_bank_stamp_slots(skred_bank_t *b, const int32_t *d_slots, int n, const
   b->touched_total += slot_touched(n, voice_mask);
   sk_control_changed(b);
   return SKRED_OK;
+}
+
+/* ---- slot stealing ---- */
+
+#define SK_SLOT_STEAL_FLAGS (SKRED_STEAL_RELEASED_FIRST | SKRED_STEAL_RELEASED_ONLY)
+
+static int slot_steal_check(const skred_slot_steal_query_t *q, int n_voices, const char *who) {
+  if (!q) return fail(SKRED_E_BAD_ARG, "%s: no query", who);
+  if (q->policy != SKRED_STEAL_OLDEST && q->policy != SKRED_STEAL_QUIETEST) return fail(SKRED_E_BAD_ARG, "%s: unknown policy %u", who, q->policy);
+  if ((q->flags & SKRED_STEAL_UNNAMED) || (q->exclude_idle & SKRED_IDLE_UNNAMED))
+    return fail(SKRED_E_BAD_ARG, "%s: UNNAMED -- the voices of a patch name one another by design", who);
+  if (q->flags & ~(uint32_t)SK_SLOT_STEAL_FLAGS) return fail(SKRED_E_BAD_ARG, "%s: unknown bits in flags = 0x%x", who, q->flags);
+  if (q->exclude_idle & ~(uint32_t)SK_SLOT_CRITERIA) return fail(SKRED_E_BAD_ARG, "%s: unknown bits in exclude_idle = 0x%x", who, q->exclude_idle);
+  if (q->reserved[0] || q->reserved[1]) return fail(SKRED_E_BAD_ARG, "%s: reserved words must be 0", who);
+  if (q->max_out < 0 || q->max_out > SKRED_STEAL_MAX) return fail(SKRED_E_BAD_ARG, "%s: max_out %d outside [0, %d]", who, q->max_out, SKRED_STEAL_MAX);
+  if (!(q->settle_level >= 0.0f) || isinf(q->settle_level)) return fail(SKRED_E_BAD_ARG, "%s: settle_level %g", who, (double)q->settle_level);
+  const int rc = slot_shape_check(q->slot_voices, q->member_mask, who, "member_mask");
+  if (rc) return rc;
+  const int K = q->slot_voices;
+  if (n_voices <= 0) return fail(SKRED_E_BAD_ARG, "%s: a bank of %d voices", who, n_voices);
+  if (q->count <= 0 || q->first < 0 || q->first >= n_voices || q->count > n_voices - q->first)
+    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, q->first, q->count, n_voices);
+  if ((q->first & (K - 1)) || (q->count & (K - 1)))
+    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) is not made of whole slots of %d voices", who, q->first, q->count, K);
+  return SKRED_OK;
+}
+
+int skred_slot_steal_check(const skred_slot_steal_query_t *q, int n_voices) { return slot_steal_check(q, n_voices, "slot_steal_check"); }
+
+static int slot_steal_check_bank(const skred_bank_t *b, const skred_slot_steal_query_t *q, const void *slots, const void *count, const char *who) {
+  if (!b || !q) return fail(SKRED_E_BAD_ARG, "%s: no bank or no query", who);
+  if (!count) return fail(SKRED_E_BAD_ARG, "%s: nowhere to put the counts", who);
+  const int rc = slot_steal_check(q, b->n_voices, who);
+  if (rc) return rc;
+  if (q->max_out > 0 && !slots) return fail(SKRED_E_BAD_ARG, "%s: max_out %d and no list to fill", who, q->max_out);
+  return SKRED_OK;
+}
+
+/* the voice query's arguments (its scratch, `now`) around the slot key pass */
+static int slot_steal_launch(skred_bank_t *b, const skred_slot_steal_query_t *q, int32_t *d_slots, uint32_t *d_count, hipStream_t s) {
+  const skred_steal_query_t vq = { q->first, q->count, q->policy, q->flags, q->min_age, q->exclude_idle, q->settle_level, q->max_out, 0 };
+  sk_steal_args_t a;
+  const int rc = sk_steal_prepare(b, &vq, d_slots, d_count, s, &a);
+  if (rc) return rc;
+  const hipError_t e = (hipError_t)sk_launch_slot_steal(&a, q->member_mask, q->slot_voices, s);
+  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "find_steal_slots launch -> %s", hipGetErrorString(e));
+  return SKRED_OK;
+}
+
+int skred_bank_find_steal_slots(skred_bank_t *b, const skred_slot_steal_query_t *q, int32_t *d_slots, uint32_t *d_count, void *stream) {
+  const int rc = slot_steal_check_bank(b, q, d_slots, d_count, "find_steal_slots");
+  if (rc) return rc;
+  return slot_steal_launch(b, q, d_slots, d_count, (hipStream_t)stream);
+}
+
+static int slot_steal_into_scratch(skred_bank_t *b, const skred_slot_steal_query_t *q, hipStream_t s) {
+  HIP_TRY(hipSetDevice(b->device));
+  const int rc = sk_steal_out_buffers(b);
+  if (rc) return rc;
+  return slot_steal_launch(b, q, b->d_steal_out + 2, (uint32_t *)b->d_steal_out, s);
+}
+
+int skred_bank_find_steal_slots_host(skred_bank_t *b, const skred_slot_steal_query_t *q, int32_t *slots, int *total_out, void *stream) {
+  int dummy = 0;
+  int rc = slot_steal_check_bank(b, q, slots, &dummy, "find_steal_slots_host");
+  if (rc) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if ((rc = slot_steal_into_scratch(b, q, s))) return rc;
+  HIP_TRY(hipMemcpyAsync(b->h_steal_out, b->d_steal_out, (2 + (size_t)q->max_out) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const int written = b->h_steal_out[0];
+  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "find_steal_slots_host: the device reported %d slots written of %d", written, q->max_out);
+  if (written > 0) memcpy(slots, b->h_steal_out + 2, (size_t)written * sizeof(int32_t));
+  if (total_out) *total_out = b->h_steal_out[1];
+  return written;
+}
+
+int skred_bank_note_on_steal_slots(skred_bank_t *b, const skred_slot_query_t *idle_q, const skred_slot_steal_query_t *steal_q,
+                                   const skred_note_t *notes, int n, uint64_t voice_mask, int32_t *d_assigned, uint32_t *d_result,
+                                   void *stream) {
+  if (!b || !idle_q || !steal_q || !notes || !d_result) return fail(SKRED_E_BAD_ARG, "note_on_steal_slots: no bank, query, notes or result");
+  if (n < 0) return fail(SKRED_E_BAD_ARG, "note_on_steal_slots: n = %d", n);
+  if (idle_q->which & SKRED_IDLE_AMP_ZERO)
+    return fail(SKRED_E_BAD_ARG, "note_on_steal_slots: SKRED_IDLE_AMP_ZERO -- a note-on leaves voice_amp alone: the slot would stay silent and be listed again");
+  skred_slot_query_t iq = *idle_q;
+  iq.max_out = n;
+  skred_slot_steal_query_t sq = *steal_q;
+  sq.exclude_idle = idle_q->which;
+  sq.settle_level = idle_q->settle_level;
+  sq.max_out = n < SKRED_STEAL_MAX ? n : SKRED_STEAL_MAX;
+  int rc = slots_check(b, &iq, b, b, "note_on_steal_slots");   /* (the lists and the counts go into the bank's own scratch) */
+  if (rc) return rc;
+  if ((rc = slot_steal_check_bank(b, &sq, b, b, "note_on_steal_slots"))) return rc;
+  if (iq.slot_voices != sq.slot_voices || iq.member_mask != sq.member_mask)   /* (each range is made of whole slots of that K: checked above) */
+    return fail(SKRED_E_BAD_ARG, "note_on_steal_slots: the idle query has K = %d, mask 0x%llx, the steal query K = %d, mask 0x%llx", iq.slot_voices,
+                (unsigned long long)iq.member_mask, sq.slot_voices, (unsigned long long)sq.member_mask);
+  if ((rc = slot_notes_check(notes, n, iq.slot_voices, voice_mask, "note_on_steal_slots"))) return rc;
+  if (n == 0) return SKRED_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(b->device));
+  if ((rc = sk_note_list_room(b, n))) return rc;
+  uint32_t *d_idle_count = b->d_note_list, *d_joined = b->d_note_list + 2;
+  int32_t *d_list = (int32_t *)(b->d_note_list + SK_NOTE_LIST_WORDS);
+  if ((rc = slots_launch(b, &iq, d_list, d_idle_count, s))) return rc;
+  if ((rc = slot_steal_into_scratch(b, &sq, s))) return rc;
+  /* the victims behind the idle slots, as far as the burst reaches; d_result[2]: the notes that will land on them (every entry of
+   * the joined list names a slot, and the list is no longer than the burst) */
+  const hipError_t e = (hipError_t)sk_launch_list_append(d_list, d_idle_count, b->d_steal_out + 2, (const uint32_t *)b->d_steal_out, n,
+                                                         d_joined, d_result + 2, s);
+  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "list append launch -> %s", hipGetErrorString(e));
+  return slot_notes_launch(b, notes, n, iq.slot_voices, voice_mask, d_list, d_joined, 0, d_assigned, d_result, s);
 }

@@ -52,7 +52,7 @@ int sk_steal_check_bank(const skred_bank_t *b, const skred_steal_query_t *q, con
   return SKRED_OK;
 }
 
-static int steal_launch(skred_bank_t *b, const skred_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
+int sk_steal_prepare(skred_bank_t *b, const skred_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s, sk_steal_args_t *out) {
   HIP_TRY(hipSetDevice(b->device));
   /* the scratch, sized once for the whole bank from any `first` (as the idle query's): words and histogram | four words per
    * workgroup | the winners' keys, then their voices | one key per voice of the spans */
@@ -99,7 +99,15 @@ static int steal_launch(skred_bank_t *b, const skred_steal_query_t *q, int32_t *
   a.max_out = q->max_out;
   a.policy = q->policy;
   a.flags = q->flags;
-  if (sk_idle_workgroups(a.first, q->count) > wgs) return fail(SKRED_E_RANGE, "find_steal: scratch too small");   /* (unreachable: sized above) */
+  if (sk_idle_workgroups(a.first, q->count) > wgs) return fail(SKRED_E_RANGE, "steal query: scratch too small");   /* (unreachable: sized above) */
+  *out = a;
+  return SKRED_OK;
+}
+
+static int steal_launch(skred_bank_t *b, const skred_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
+  sk_steal_args_t a;
+  const int rc = sk_steal_prepare(b, q, d_voices, d_count, s, &a);
+  if (rc) return rc;
   const hipError_t e = (hipError_t)sk_launch_steal(&a, s);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "find_steal launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
@@ -111,7 +119,7 @@ int skred_bank_find_steal(skred_bank_t *b, const skred_steal_query_t *q, int32_t
   return steal_launch(b, q, d_voices, d_count, (hipStream_t)stream);
 }
 
-static int steal_out_buffers(skred_bank_t *b) {
+int sk_steal_out_buffers(skred_bank_t *b) {
   if (!b->d_steal_out) HIP_TRY(hipMalloc((void **)&b->d_steal_out, (2 + SK_STEAL_MAX) * sizeof(int32_t)));
   if (!b->h_steal_out) HIP_TRY(hipHostMalloc((void **)&b->h_steal_out, (2 + SK_STEAL_MAX) * sizeof(int32_t), hipHostMallocDefault));
   return SKRED_OK;
@@ -119,7 +127,7 @@ static int steal_out_buffers(skred_bank_t *b) {
 
 int sk_steal_into_scratch(skred_bank_t *b, const skred_steal_query_t *q, hipStream_t s) {
   HIP_TRY(hipSetDevice(b->device));
-  const int rc = steal_out_buffers(b);
+  const int rc = sk_steal_out_buffers(b);
   if (rc) return rc;
   return steal_launch(b, q, b->d_steal_out + 2, (uint32_t *)b->d_steal_out, s);
 }

@@ -15,6 +15,7 @@
  *   skred_note_kernels.hip    sk_launch_notes, sk_launch_stamp_list
  *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_steal_select, sk_launch_list_append
  *   skred_slot_kernels.hip    sk_launch_slots, sk_launch_slot_notes, sk_launch_slot_stamps
+ *   skred_slot_steal_kernels.hip  sk_launch_slot_steal
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
@@ -216,6 +217,13 @@ int sk_launch_slot_notes(const sk_note_t *d_notes, int n, int slot_voices, uint6
 int sk_launch_slot_stamps(const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, uint64_t voice_mask, int n_voices,
                           uint32_t dirty, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t now,
                           uint64_t *mask, hipStream_t stream);
+
+/* ---- slot stealing (skred_bank_slots.c -> skred_slot_steal_kernels.hip; include/skred_amd.h: skred_bank_find_steal_slots) ----
+ * sk_launch_steal with another key pass: one key per SLOT of slot_voices voices, stored at the slot's first voice (every other voice
+ * of the spans holds SK_STEAL_NOKEY), made of the terms of the voices with a bit in member_mask; then sk_launch_steal_select as it
+ * is.  `args` as for sk_launch_steal (first and end multiples of slot_voices, never SK_STEAL_UNNAMED / SK_IDLE_UNNAMED); d_voices
+ * receives first voices of slots.  max_out == 0: the key pass alone, which writes d_count */
+int sk_launch_slot_steal(const sk_steal_args_t *args, uint64_t member_mask, int slot_voices, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

@@ -2,6 +2,8 @@
 // sk_steal_keys_kernel and every launch behind it; skred_fx_steal_kernels.hip: the fixed-point bank's sk_fx_steal_keys_kernel).
 // A key pass evaluates its bank's candidate predicate, stores one key per voice, counts the first digit with sk_steal_histogram
 // and lets its last arriver pick the first bin with sk_steal_pick; nothing behind it reads a plane.
+// The float bank has two key passes -- one key per voice (sk_steal_keys_kernel) and one per slot of a tiled patch
+// (skred_slot_steal_kernels.hip: sk_slot_steal_keys_kernel); the per-voice terms both are made of are stated once, below.
 #ifndef SKRED_STEAL_COMMON_HPP
 #define SKRED_STEAL_COMMON_HPP
 
@@ -16,6 +18,45 @@
 typedef unsigned long long sk_key_t;
 
 __device__ __forceinline__ int sk_steal_shift(int digit) { return SK_STEAL_BITS * (SK_STEAL_DIGITS - 1 - digit); }
+
+// ---- the terms of one voice of the float bank (include/skred_amd.h states the definition field by field), read from the planes the
+// query's bits ask for: flags and rwflags always; SKP_ENV_S for OLDEST, min_age > 0 or a RELEASED_* flag; SKS_OSC for QUIETEST
+__device__ __forceinline__ int sk_steal_voice(const sk_steal_args_t &a, bool &in_range) {
+  const int v = a.base + (int)blockIdx.x * SK_IDLE_SPAN + (int)threadIdx.x;   // base: `first` rounded down to 64
+  in_range = v >= a.first && v < a.end;
+  return v;
+}
+
+// voice_use_amp_envelope != 0 && is_active != 0 (`flags`: the voice's flag word, for sk_steal_loudness)
+__device__ __forceinline__ bool sk_steal_live(const sk_steal_args_t &a, int v, uint32_t &flags) {
+  flags = a.idle.tab[v].w[2];
+  const uint32_t rwf = a.idle.filt[v].w[3];
+  return (flags & SKF_USE_ENV) && (rwf & SKR_ENV_ACTIVE);
+}
+
+// the query reads sample_start / sample_release (kernel arguments only: wave-uniform)
+__device__ __forceinline__ bool sk_steal_reads_clocks(const sk_steal_args_t &a) {
+  return a.policy == SK_STEAL_OLDEST || a.min_age > 0 || (a.flags & (SK_STEAL_RELEASED_FIRST | SK_STEAL_RELEASED_ONLY));
+}
+
+__device__ __forceinline__ void sk_steal_clocks(const sk_steal_args_t &a, int v, uint64_t &t_start, uint64_t &t_release) {
+  const uint4 es = *reinterpret_cast<const uint4 *>(&a.env_s[v]);
+  t_start = ((uint64_t)es.y << 32) | es.x;
+  t_release = ((uint64_t)es.w << 32) | es.z;
+}
+
+__device__ __forceinline__ uint64_t sk_steal_age(const sk_steal_args_t &a, uint64_t t_start) { return t_start > a.now ? 0 : a.now - t_start; }
+
+// QUIETEST's primary: the bits of fabsf(voice_smoother_gain), 0x7fffffff without a smoother
+__device__ __forceinline__ sk_key_t sk_steal_loudness(const sk_steal_args_t &a, int v, uint32_t flags) {
+  const uint32_t gain = a.idle.osc_rw[v].w[1] & 0x7fffffffu;
+  return (flags & SKF_SMOOTH) ? gain : 0x7fffffffu;
+}
+
+__device__ __forceinline__ sk_key_t sk_steal_pack(sk_key_t cls, sk_key_t primary) {
+  const sk_key_t cap = (1ull << 62) - 1;
+  return (cls << 62) | (primary < cap ? primary : cap);
+}
 
 // One workgroup's share of a digit histogram: `hist` (LDS, SK_STEAL_BINS words) is zeroed, filled and its non-empty bins added
 // to the global histogram.  A wave whose counted keys all hold the same digit -- a bank uploaded in one go has one sample_start --

@@ -36,48 +36,29 @@
 #include "skred_idle_common.hpp"
 #include "skred_kernel_common.hpp"
 #include "skred_launch.h"
-#include "skred_steal_common.hpp"   // sk_key_t, sk_steal_histogram / _scan / _pick: shared with the fixed-point bank's key pass
+#include "skred_steal_common.hpp"   // sk_key_t, the per-voice terms (shared with the slot key pass), sk_steal_histogram / _scan / _pick
 
 #define SK_STEAL_WAVES (SK_IDLE_SPAN / 64)
 #define SK_STEAL_SORT_THREADS 512
 
-__device__ __forceinline__ int sk_steal_voice(const sk_steal_args_t &a, bool &in_range) {
-  const int v = a.base + (int)blockIdx.x * SK_IDLE_SPAN + (int)threadIdx.x;   // base: `first` rounded down to 64
-  in_range = v >= a.first && v < a.end;
-  return v;
-}
-
-// the key of one voice, SK_STEAL_NOKEY when it is no candidate (include/skred_amd.h states the definition field by field)
+// the key of one voice, SK_STEAL_NOKEY when it is no candidate (skred_steal_common.hpp: the terms it is made of)
 __device__ __forceinline__ sk_key_t sk_steal_key(const sk_steal_args_t &a, int v, bool in_range) {
   if (!in_range) return SK_STEAL_NOKEY;
-  const uint32_t flags = a.idle.tab[v].w[2];
-  const uint32_t rwf = a.idle.filt[v].w[3];
-  bool cand = (flags & SKF_USE_ENV) && (rwf & SKR_ENV_ACTIVE);
-  uint64_t t_start = 0, t_release = 0;
-  if (a.policy == SK_STEAL_OLDEST || a.min_age > 0 || (a.flags & (SK_STEAL_RELEASED_FIRST | SK_STEAL_RELEASED_ONLY))) {
-    const uint4 es = *reinterpret_cast<const uint4 *>(&a.env_s[v]);
-    t_start = ((uint64_t)es.y << 32) | es.x;
-    t_release = ((uint64_t)es.w << 32) | es.z;
-  }
+  uint32_t flags;
+  bool cand = sk_steal_live(a, v, flags);
+  uint64_t t_release = 0, t_start = 0;
+  if (sk_steal_reads_clocks(a)) sk_steal_clocks(a, v, t_start, t_release);
   const bool released = t_release != 0;
-  if (a.min_age > 0) {
-    const uint64_t age = t_start > a.now ? 0 : a.now - t_start;
-    cand = cand && age >= a.min_age;
-  }
+  if (a.min_age > 0) cand = cand && sk_steal_age(a, t_start) >= a.min_age;
   if (a.flags & SK_STEAL_RELEASED_ONLY) cand = cand && released;
   if (a.flags & SK_STEAL_UNNAMED) cand = cand && !((a.idle.named[v >> 6] >> (v & 63)) & 1);
   if (a.idle.which) cand = cand && !sk_idle_pred(a.idle, v, true);
   if (!cand) return SK_STEAL_NOKEY;
   const sk_key_t cls = ((a.flags & SK_STEAL_RELEASED_FIRST) && released) ? 0ull : 1ull;
   sk_key_t primary;
-  if (a.policy == SK_STEAL_OLDEST) {
-    primary = cls == 0 ? t_release : t_start;
-  } else {
-    const uint32_t gain = a.idle.osc_rw[v].w[1] & 0x7fffffffu;   // the bits of fabsf(voice_smoother_gain)
-    primary = (flags & SKF_SMOOTH) ? gain : 0x7fffffffu;
-  }
-  const sk_key_t cap = (1ull << 62) - 1;
-  return (cls << 62) | (primary < cap ? primary : cap);
+  if (a.policy == SK_STEAL_OLDEST) primary = cls == 0 ? t_release : t_start;
+  else primary = sk_steal_loudness(a, v, flags);
+  return sk_steal_pack(cls, primary);
 }
 
 __global__ __launch_bounds__(SK_IDLE_SPAN) void sk_steal_keys_kernel(sk_steal_args_t a) {

@@ -11,7 +11,7 @@ from typing import Optional
 
 import numpy as np
 
-from .bank import GlobalsC, SlotQueryC, VoiceBank, VoiceBankC, slot_query  # noqa: F401
+from .bank import GlobalsC, SlotQueryC, SlotStealQueryC, VoiceBank, VoiceBankC, slot_query, slot_steal_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SKRED_AMD_LIB", os.path.join(_HERE, "libskred_amd.so"))   # override: A/B builds
@@ -40,9 +40,10 @@ ABI_SYMBOLS = [
     "skred_bank_find_steal", "skred_bank_find_steal_host", "skred_bank_note_on_steal",
     "skred_bank_find_idle_slots", "skred_bank_find_idle_slots_host", "skred_bank_notes_on_slots", "skred_bank_note_on_idle_slots",
     "skred_bank_stamp_slots",
+    "skred_bank_find_steal_slots", "skred_bank_find_steal_slots_host", "skred_bank_note_on_steal_slots",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
-HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check"]
+HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -191,6 +192,10 @@ def load() -> C.CDLL:
     L.skred_bank_notes_on_slots.argtypes = [vp, vp, i32, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
     L.skred_bank_note_on_idle_slots.argtypes = [vp, C.POINTER(SlotQueryC), vp, i32, C.c_uint64, vp, vp, vp]
     L.skred_bank_stamp_slots.argtypes = [vp, vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp]
+    L.skred_slot_steal_check.argtypes = [C.POINTER(SlotStealQueryC), i32]
+    L.skred_bank_find_steal_slots.argtypes = [vp, C.POINTER(SlotStealQueryC), vp, vp, vp]
+    L.skred_bank_find_steal_slots_host.argtypes = [vp, C.POINTER(SlotStealQueryC), vp, C.POINTER(i32), vp]
+    L.skred_bank_note_on_steal_slots.argtypes = [vp, C.POINTER(SlotQueryC), C.POINTER(SlotStealQueryC), vp, i32, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
 
@@ -215,6 +220,11 @@ def steal_check(q: StealQueryC, n_voices: int) -> int:
 def slot_query_check(q: SlotQueryC, n_voices: int) -> int:
     """skred_slot_query_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for a query find_idle_slots would refuse.  Pure host."""
     return int(load().skred_slot_query_check(C.byref(q) if q is not None else None, int(n_voices)))
+
+
+def slot_steal_check(q: SlotStealQueryC, n_voices: int) -> int:
+    """skred_slot_steal_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for a query find_steal_slots would refuse.  Pure host."""
+    return int(load().skred_slot_steal_check(C.byref(q) if q is not None else None, int(n_voices)))
 
 
 def slot_notes_check(notes, slot_voices: int, voice_mask: int) -> int:
@@ -454,6 +464,32 @@ class DeviceBank:
         entries that are no slot of the bank -- the -1 of a dropped note -- are skipped."""
         _check(self.L.skred_bank_stamp_slots(self.h, d_slots or None, int(n), d_count or None, int(slot_voices), int(voice_mask),
                                              int(stamps), stream or None), "skred_bank_stamp_slots")
+
+    # ---- slot stealing (include/skred_amd.h: skred_bank_find_steal_slots / _find_steal_slots_host / _note_on_steal_slots) ----
+    def find_steal_slots(self, q: SlotStealQueryC, d_slots: int = 0, d_count: int = 0, stream: int = 0):
+        """Asynchronous on `stream`: the first voices of the first q.max_out candidate slots of the victim order (ascending key, ties
+        by first voice) into d_slots[0 .. written) (int32, device memory); d_count[0] = written, d_count[1] = total (uint32)."""
+        _check(self.L.skred_bank_find_steal_slots(self.h, C.byref(q), d_slots or None, d_count or None, stream or None),
+               "skred_bank_find_steal_slots")
+
+    def find_steal_slots_host(self, q: SlotStealQueryC, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the victim slots, total candidates)."""
+        out = np.empty(max(int(q.max_out), 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_bank_find_steal_slots_host(self.h, C.byref(q), out.ctypes.data if q.max_out > 0 else None, C.byref(total),
+                                                    stream or None)
+        if n < 0:
+            _check(n, "skred_bank_find_steal_slots_host")
+        return out[:n].copy(), int(total.value)
+
+    def note_on_steal_slots(self, notes, idle_q: SlotQueryC, steal_q: SlotStealQueryC, voice_mask: int, d_assigned: int = 0,
+                            d_result: int = 0, stream: int = 0):
+        """The idle-slot query, the slot steal query (exclude_idle, settle_level and max_out overridden by the library), the victims
+        appended behind the idle slots and the placement of the patch notes, in one call; d_result[0..3) = placed, dropped, stolen."""
+        arr = note_array(notes)
+        _check(self.L.skred_bank_note_on_steal_slots(self.h, C.byref(idle_q), C.byref(steal_q), C.cast(arr, C.c_void_p),
+                                                     len(arr) // int(idle_q.slot_voices), int(voice_mask), d_assigned or None,
+                                                     d_result or None, stream or None), "skred_bank_note_on_steal_slots")
 
     def force_generic(self, on: bool = True):
         _check(self.L.skred_bank_set_option(self.h, 1, int(on)), "skred_bank_set_option")

@@ -735,8 +735,132 @@ def slots():
     db.close()
 
 
+def slotsteal():
+    """A burst of 256 patch notes on bank_patch("3sk", 2**20) -- the carriers enveloped, every copy sounding but 64 -- through
+    skred_bank_note_on_steal_slots: 64 notes land on idle slots, 192 on stolen ones.  Every repetition uploads the bank and RENDERS a
+    block of 64 frames first, so the calls meet the state a running instrument holds (the smoother gains ENV_DONE reads among it).
+    The per-voice skred_bank_find_steal at max_out 16 runs on the same bank in the same run, for the comparison of the two key passes.  skred_bank_find_steal_slots alone at max_out 0,
+    16 and 1024.  Against the only route a host had before: skred_bank_download + grouping and victim order in numpy +
+    skred_bank_update.  Medians of 12 with minimum and maximum, stream events around the device calls."""
+    D = device
+    n, K, NOTES, REST, REPS = 1 << 20, 4, 256, 64, 12
+    MEMBERS, VOICES = 0x7, 0xF
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 1e6
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = (now - 40000 - ((v[sel] // K) * 7919) % 30000 - (v[sel] % K)).astype(np.uint64)   # every copy its own age
+    rel = sel & ((v // K) % 3 == 0)
+    e["sample_release"][rel] = (now - 2000 + ((v[rel] // K) * 104729) % 1000).astype(np.uint64)             # a third of them in release
+    rng = np.random.default_rng(4)
+    rest = np.sort(rng.choice(n // K, REST, replace=False)) * K
+    for l in range(3):
+        e["is_active"][rest + l] = 0
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g)
+    which = D.IDLE_ENV_DONE
+    iq = D.slot_query(0, n, K, MEMBERS, which, 1e-3, 0, NOTES)
+    notes = D.note_array([D.NoteC(0.4 + 0.001 * i, 0.8, 0.0, 0.5, 0.5, D.NOTE_SET_PHASE) for i in range(NOTES * K)])
+    da = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+    dv = torch.full((D.STEAL_MAX,), -1, dtype=torch.int32, device="cuda")
+    dc = torch.zeros(2, dtype=torch.int32, device="cuda")
+    mirror = bank.copy()
+    dirty = D.DIRTY_PARAMS | D.DIRTY_PHASE | D.STAMP_TRIGGER
+    inc = np.array([t.phase_inc for t in notes], np.float32).reshape(NOTES, K)
+
+    def sq(max_out):
+        return D.slot_steal_query(0, n, K, MEMBERS, D.STEAL_OLDEST, D.STEAL_RELEASED_FIRST, 0, which, 1e-3, max_out)
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def device_route():
+        h, s_ms = timed(lambda: db.note_on_steal_slots(notes, iq, sq(0), VOICES, da.data_ptr(), dr.data_ptr()))
+        return h, s_ms, dr.cpu().numpy().tolist()
+
+    def query_only(max_out):
+        def run():
+            h, s_ms = timed(lambda: db.find_steal_slots(sq(max_out), dv.data_ptr(), dc.data_ptr()))
+            return h, s_ms, dc.cpu().numpy().tolist()
+        return run
+
+    def voice_query():
+        vq = D.steal_query(0, n, D.STEAL_OLDEST, D.STEAL_RELEASED_FIRST, 0, which, 1e-3, 16)
+        h, s_ms = timed(lambda: db.find_steal(vq, dv.data_ptr(), dc.data_ptr()))
+        return h, s_ms, dc.cpu().numpy().tolist()
+
+    block = torch.zeros(64, 2, device="cuda")
+    got = bank.copy()
+    clocks = bank["voice_amp_envelope"]                       # (download returns the read-write fields; the clocks are the host's own)
+
+    def download_route():
+        t0 = time.perf_counter()
+        db.download(got)
+        a, env = got.a, got.a["voice_amp_envelope"]
+        heads = np.arange(0, n, K)
+        mv = heads[:, None] + np.arange(3)[None, :]
+        use, act = a["voice_use_amp_envelope"][mv] != 0, env["is_active"][mv] != 0
+        settled = (a["voice_smoother_enable"][mv] == 0) | (np.abs(a["voice_smoother_gain"][mv]) <= np.float32(1e-3))
+        idle = use & ~act & settled
+        free = heads[idle.all(1)][:NOTES]
+        live = use & act
+        rls = clocks["sample_release"][mv]
+        allrel = ~(live & (rls == 0)).any(1)
+        cand = live.any(1) & ~idle.all(1)
+        primary = np.where(live, np.where(allrel[:, None], rls, clocks["sample_start"][mv]), np.uint64(0)).max(1)
+        key = (np.where(allrel, 0, 1).astype(np.uint64) << np.uint64(62)) | primary.astype(np.uint64)
+        need = NOTES - len(free)
+        ch, ck = heads[cand], key[cand]
+        part = ck <= np.partition(ck, need - 1)[need - 1] if 0 < need < len(ck) else np.ones(len(ck), bool)   # (ties at the cut: all of them)
+        victims = ch[part][np.lexsort((ch[part], ck[part]))][:max(need, 0)]
+        picks = np.concatenate([free, victims])[:NOTES]
+        vs = (picks[:, None] + np.arange(K)[None, :]).astype(np.int32)
+        mirror["voice_phase_inc"][vs] = inc[:len(picks)]
+        mirror["voice_amp_envelope"]["velocity"][vs] = np.float32(0.8)
+        mirror["voice_phase"][vs] = 0.0
+        mirror["voice_finished"][vs] = 0
+        db.update(mirror, vs.reshape(-1), dirty)
+        return (time.perf_counter() - t0) * 1e3, None, [len(picks), NOTES - len(picks), len(picks) - len(free)]
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, {REST} slots at rest, a block of 64 frames, then a burst of {NOTES} patch notes ({NOTES * K} records), medians of {REPS}")
+    for label, route in (("note_on_steal_slots (both queries, append and placement on the device)", device_route),
+                         ("find_steal_slots alone, max_out 0 (the key pass)", query_only(0)),
+                         ("find_steal_slots alone, max_out 16", query_only(16)),
+                         ("find_steal_slots alone, max_out 1024", query_only(1024)),
+                         ("find_steal (the per-voice query) on the same bank, max_out 16", voice_query),
+                         ("skred_bank_download + grouping and victim order in numpy + skred_bank_update", download_route)):
+        host, stream, res = [], [], None
+        for it in range(2 + REPS):
+            db.upload(bank)
+            db.render_mix(64, block.data_ptr(), 2, 0, 0)
+            torch.cuda.synchronize()
+            h, s_ms, res = route()
+            torch.cuda.synchronize()
+            if it >= 2:
+                host.append(h)
+                if s_ms is not None:
+                    stream.append(s_ms)
+        line = f"  {label}: host time median {np.median(host):.4f} ms (min {np.min(host):.4f}, max {np.max(host):.4f})"
+        if stream:
+            line += f"; stream time between events median {np.median(stream):.4f} ms (min {np.min(stream):.4f}, max {np.max(stream):.4f})"
+        print(line + f"; result words = {res}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
