@@ -751,6 +751,78 @@ int  skred_bank_note_on_steal_slots(skred_bank_t *bank, const skred_slot_query_t
                                     const skred_note_t *notes, int n, uint64_t voice_mask, int32_t *d_assigned, uint32_t *d_result,
                                     void *stream);
 
+/* ---- patch controllers: a few parameter words of every copy of a tiled patch, changed on the device ----------------------------
+ *
+ * A performance moves controls as well as keys: a filter sweep, a volume or expression change, a pan, a modulation-depth wheel, a
+ * pitch bend, a longer release -- on all copies of a patch, or on the copies of one chord.  Through skred_bank_update that is a full
+ * host record per voice; the write itself is a few words.  These calls store those words with a kernel, on voices the host never
+ * lists: every slot of a range, or the slots a list in device memory names (an earlier d_assigned: "this chord only").
+ *
+ * A slot, K = slot_voices and voice_mask mean what they mean for skred_bank_notes_on_slots.  `ctl` holds K records: record l is for
+ * voice l of a slot, only voices with bit l of voice_mask set are touched, the other records are neither read nor checked.  With
+ * K = 1 and mask 1 these are per-voice calls.  A record names the fields it stores in `set`; exactly those words are stored, as
+ * given, and nothing else: the running phase, the filter memory, the smoother gain, the envelope clock, the flags and the routing
+ * keep what the device computed.  Two stores look at the device's value first:
+ *   SKRED_CTL_INC_SCALE  voice_phase_inc = voice_phase_inc * inc_scale, ONE fp32 multiply, never fused; a product that is not
+ *                        finite is not stored (the voice keeps its increment).  A pitch bend of voices whose pitches the host
+ *                        never learned (device-side note-ons).
+ *   SKRED_CTL_AMP        stored on voices whose voice_amp != 0.0f ON THE DEVICE; a voice with amp 0 (or -0) keeps it.
+ * Why those, and why the refusals below: of the words a controller stores the host-side planner reads three things -- whether
+ * voice_amp == 0 (which voices can sound: the packed lanes), whether increment and phase data are finite (the voice's kernel
+ * class), and the routing.  Finite values, an amp that keeps its zero-ness and no routing field leave the bank's classes, counters,
+ * lane words, named set and tape plan right without the host knowing which voice holds what -- the argument skred_bank_notes_on_list
+ * makes for notes.
+ * Voices whose record names AMP, ENV_TIMES, VELOCITY or SMOOTHING go on the motion list (those are the words that can set an envelope
+ * or a smoother moving); the other controllers do not, so a bank-wide filter sweep costs the next block nothing.
+ * LIMIT, as for notes: the host view goes stale.  Before a later skred_bank_update with SKRED_DIRTY_PARAMS (or SKRED_DIRTY_PAN) of
+ * such a voice, mirror the values into the host view; skred_bank_download_ctl reads them back where the host cannot know them (a
+ * scaled increment, a withheld amp).  On a shard: through skred_shard_bank(), with that rank's local indices.  Not in the fixed-point
+ * bank or the drop-in mode; deferred items and pattern steps carry host records only. */
+enum { SKRED_CTL_PHASE_INC = 1u<<0,  /* voice_phase_inc = phase_inc */
+       SKRED_CTL_INC_SCALE = 1u<<1,  /* voice_phase_inc = voice_phase_inc * inc_scale: ONE float multiply, unfused; a product that is
+                                        not finite is not stored (the voice keeps its increment; counted in d_result[1]) */
+       SKRED_CTL_AMP       = 1u<<2,  /* voice_amp = amp on voices whose voice_amp != 0.0f ON THE DEVICE; others keep 0 (counted) */
+       SKRED_CTL_PAN       = 1u<<3,  /* voice_pan_left / _right */
+       SKRED_CTL_FILTER    = 1u<<4,  /* voice_filter.b0 b1 b2 a1 a2 (coefficients as mmf_set_params made them; memory untouched) */
+       SKRED_CTL_ENV_TIMES = 1u<<5,  /* attack_time, decay_time, sustain_level, release_time */
+       SKRED_CTL_VELOCITY  = 1u<<6,
+       SKRED_CTL_SMOOTHING = 1u<<7,  /* voice_smoother_smoothing */
+       SKRED_CTL_FM_DEPTH  = 1u<<8, SKRED_CTL_FREQ_SCALE = 1u<<9, SKRED_CTL_AM_DEPTH = 1u<<10, SKRED_CTL_PAN_DEPTH = 1u<<11,
+       SKRED_CTL_CZ_DEPTH  = 1u<<12, SKRED_CTL_CZ_DIST = 1u<<13 };
+typedef struct skred_ctl { uint32_t set; float phase_inc, inc_scale, amp, pan_left, pan_right, b0, b1, b2, a1, a2,
+                           attack_time, decay_time, sustain_level, release_time, velocity, smoothing,
+                           fm_depth, freq_scale, am_depth, pan_depth, cz_depth, cz_dist; uint32_t reserved; } skred_ctl_t;  /* 96 bytes */
+
+/* Pure host, no device: SKRED_OK, or what the two entry points refuse about the controller itself.  SKRED_E_RANGE: K not a power of
+ * two in 1 .. 64.  SKRED_E_BAD_ARG: NULL ctl; a voice_mask that is 0 or has bits at or above K; and, in a record whose mask bit is
+ * set: unknown bits in set, set == 0, reserved != 0, both PHASE_INC and INC_SCALE, a named value that is not finite, amp == 0 under
+ * SKRED_CTL_AMP (a controller never silences a voice for good: the planner would not know).  Values a field does not name are not
+ * looked at.  Negative amp, zero depths and zero times are accepted. */
+int  skred_ctl_check(const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask);
+/* The controller on every slot of [first, first + count): first and count multiples of K, inside the bank.  Asynchronous on `stream`:
+ * the K records travel through the staging ring of skred_bank_update (`ctl` is free again on return), one kernel stores them,
+ * nothing waits for the device.  d_result (device memory, uint32[2], may be NULL) is cleared on the stream ahead of the kernel:
+ * [0] = voices written (masked voices of the range), [1] = stores withheld by the two guards above (AMP on a zero-amp voice, a
+ * scaled increment that is not finite); both are sums, the same whatever the order of arrival.
+ * Refused before anything touches the device: what skred_ctl_check refuses; SKRED_E_BAD_ARG for a NULL bank; SKRED_E_RANGE for
+ * count < 0, a range outside the bank, first or count not a multiple of K.  count == 0: SKRED_OK, nothing is done. */
+int  skred_bank_ctl_range(skred_bank_t *bank, const skred_ctl_t *ctl, int first, int count, int slot_voices, uint64_t voice_mask,
+                          uint32_t *d_result, void *stream);
+/* The controller on the first min(n, *d_count_or_null) slots of a list in device memory (NULL: n).  Entries that are no slot of the
+ * bank -- negative, not a multiple of K, past the bank -- are skipped: skred_bank_stamp_slots' rules, so the d_assigned of a
+ * skred_bank_note_on_idle_slots serves, -1 holes and all, as the list for "this chord only".  A slot named twice gets the same
+ * absolute stores twice, which is the same as once and is counted twice in d_result; with SKRED_CTL_INC_SCALE its increment is
+ * UNSPECIFIED (scaled once or twice), nothing else is affected.  d_result and the rest as for skred_bank_ctl_range.
+ * Refused before anything touches the device: what skred_ctl_check refuses; SKRED_E_BAD_ARG for a NULL bank or list, n < 0 or
+ * n > INT32_MAX / 64.  n == 0: SKRED_OK, nothing is done. */
+int  skred_bank_ctl_slots(skred_bank_t *bank, const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask,
+                          const int32_t *d_slots, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+/* The words a controller can store, as the device holds them, into the host view -- what skred_bank_download leaves out:
+ * voice_phase_inc, voice_amp, the envelope's four times and velocity, voice_smoother_smoothing, the filter's five coefficients, the
+ * four modulation depths / scale, voice_cz_mod_depth, voice_cz_distortion (and the pans, which skred_bank_download returns too).
+ * Waits for the device, like skred_bank_download; windows as there. */
+int  skred_bank_download_ctl(skred_bank_t *bank, skred_voice_bank_t *host, int src_first, int dst_first, int count);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

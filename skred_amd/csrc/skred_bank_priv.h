@@ -265,6 +265,9 @@ void sk_notes_free(skred_bank_t *b);         /* skred_bank_notes.c: the list scr
 int sk_note_check_one(const skred_note_t *t, int k);
 int sk_note_list_room(skred_bank_t *b, int n);
 #define SK_NOTE_LIST_WORDS 4       /* in front of d_note_list's entries: a query's two counts, the joined list's length (note_on_steal), padded to 16 bytes */
+/* skred_bank_ctl.c: the K records of a checked controller as they travel (masked ones word for word, the others zeroed); returns the
+ * mask of the voices whose record puts them on the motion list.  Pure host */
+uint64_t sk_ctl_pack(const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask, sk_ctl_t *out);
 /* skred_bank_idle.c, for skred_bank_slots.c: the scratch both list queries share (allocated on first use), the kernels' view of a
  * query on this bank, and room for `need` entries in d_idle_out / h_idle_out */
 int sk_idle_scratch(skred_bank_t *b, hipStream_t s);

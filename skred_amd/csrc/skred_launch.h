@@ -16,10 +16,11 @@
  *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_steal_select, sk_launch_list_append
  *   skred_slot_kernels.hip    sk_launch_slots, sk_launch_slot_notes, sk_launch_slot_stamps
  *   skred_slot_steal_kernels.hip  sk_launch_slot_steal
+ *   skred_ctl_kernels.hip     sk_launch_ctl_range, sk_launch_ctl_slots
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
- * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c and skred_recorder.c.
+ * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c, skred_bank_ctl.c and skred_recorder.c.
  */
 #ifndef SKRED_LAUNCH_H
 #define SKRED_LAUNCH_H
@@ -224,6 +225,44 @@ int sk_launch_slot_stamps(const int32_t *d_slots, int n, const uint32_t *d_count
  * is.  `args` as for sk_launch_steal (first and end multiples of slot_voices, never SK_STEAL_UNNAMED / SK_IDLE_UNNAMED); d_voices
  * receives first voices of slots.  max_out == 0: the key pass alone, which writes d_count */
 int sk_launch_slot_steal(const sk_steal_args_t *args, uint64_t member_mask, int slot_voices, hipStream_t stream);
+
+/* ---- patch controllers (skred_bank_ctl.c -> skred_ctl_kernels.hip; include/skred_amd.h: skred_bank_ctl_range / _ctl_slots) ----
+ * A controller record is skred_ctl_t word for word (layout and bits checked at compile time in skred_bank_ctl.c): word 0 names the
+ * fields to store, the values follow.  The bits equal SKRED_CTL_*. */
+#define SK_CTL_PHASE_INC  (1u << 0)
+#define SK_CTL_INC_SCALE  (1u << 1)
+#define SK_CTL_AMP        (1u << 2)
+#define SK_CTL_PAN        (1u << 3)
+#define SK_CTL_FILTER     (1u << 4)
+#define SK_CTL_ENV_TIMES  (1u << 5)
+#define SK_CTL_VELOCITY   (1u << 6)
+#define SK_CTL_SMOOTHING  (1u << 7)
+#define SK_CTL_FM_DEPTH   (1u << 8)
+#define SK_CTL_FREQ_SCALE (1u << 9)
+#define SK_CTL_AM_DEPTH   (1u << 10)
+#define SK_CTL_PAN_DEPTH  (1u << 11)
+#define SK_CTL_CZ_DEPTH   (1u << 12)
+#define SK_CTL_CZ_DIST    (1u << 13)
+#define SK_CTL_ALL        ((1u << 14) - 1u)
+/* the words sk_env_motion (skred_kernel_common.hpp) reads: a voice whose record names one goes on the motion list */
+#define SK_CTL_LISTS      (SK_CTL_AMP | SK_CTL_ENV_TIMES | SK_CTL_VELOCITY | SK_CTL_SMOOTHING)
+enum { SK_CTL_SET = 0, SK_CTL_W_PHASE_INC, SK_CTL_W_INC_SCALE, SK_CTL_W_AMP, SK_CTL_W_PAN_LEFT, SK_CTL_W_PAN_RIGHT, SK_CTL_W_B0, SK_CTL_W_B1,
+       SK_CTL_W_B2, SK_CTL_W_A1, SK_CTL_W_A2, SK_CTL_W_ATTACK, SK_CTL_W_DECAY, SK_CTL_W_SUSTAIN, SK_CTL_W_RELEASE, SK_CTL_W_VELOCITY,
+       SK_CTL_W_SMOOTHING, SK_CTL_W_FM_DEPTH, SK_CTL_W_FREQ_SCALE, SK_CTL_W_AM_DEPTH, SK_CTL_W_PAN_DEPTH, SK_CTL_W_CZ_DEPTH,
+       SK_CTL_W_CZ_DIST, SK_CTL_W_RESERVED, SK_CTL_WORDS };
+typedef struct {
+  uint32_t w[SK_CTL_WORDS];
+} sk_ctl_t;
+/* d_recs: slot_voices records (record l: voice l of a slot; records without a bit in voice_mask hold set == 0), possibly the pinned
+ * staging buffer; cnt / done / seq and `mask` as for sk_launch_update.  d_result[2] (or NULL) is zeroed on `stream` ahead of the
+ * kernel and receives voices written, stores withheld.  Range: every slot of [first, first + count), both multiples of slot_voices
+ * inside the bank.  Slots: the first min(n, d_count[0]) entries (d_count NULL: n); entries that are no slot of the bank are skipped */
+int sk_launch_ctl_range(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_mask, int first, int count,
+                        sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t *mask, uint32_t *d_result,
+                        uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+int sk_launch_ctl_slots(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_mask, const int32_t *d_slots, int n,
+                        const uint32_t *d_count, int n_voices, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
+                        uint64_t *mask, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

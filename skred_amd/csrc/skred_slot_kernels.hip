@@ -31,7 +31,7 @@
 #include "skred_idle_common.hpp"   // sk_idle_pred: the predicate of one voice
 #include "skred_idle_scan.hpp"     // counts, offsets, rank of `from`, scatter
 #include "skred_launch.h"
-#include "skred_update_common.hpp" // sk_note_store, sk_stamp_store, sk_batch_done
+#include "skred_update_common.hpp" // sk_note_store, sk_stamp_store, sk_slot_valid, sk_batch_done
 
 // this lane is the first voice of an idle slot (v: its voice; a slot never straddles a wavefront: spans start at a multiple of 64)
 __device__ __forceinline__ bool sk_slot_listed(const sk_slot_args_t &s, int v, bool in_range) {
@@ -54,11 +54,6 @@ __global__ __launch_bounds__(SK_IDLE_SPAN) void sk_slot_scatter_kernel(sk_slot_a
   bool in_range;
   const int v = sk_idle_voice(s.idle, in_range);
   sk_idle_scatter_tail(s.idle, v, sk_slot_listed(s, v, in_range), lds);
-}
-
-// entry e names a slot of the bank
-__device__ __forceinline__ bool sk_slot_valid(int e, int slot_voices, int n_voices) {
-  return e >= 0 && (e & (slot_voices - 1)) == 0 && e <= n_voices - slot_voices;
 }
 
 __global__ __launch_bounds__(SK_NOTE_SPAN) void sk_slot_notes_kernel(const sk_note_t *__restrict__ notes, int n, int k_shift,

@@ -1,6 +1,6 @@
 // skred_update_common.hpp -- what the kernels that apply control actions share (skred_update_kernels.hip: updates and stamps
 // named by the host; skred_note_kernels.hip: note-ons and stamps on voices named by a list in device memory; skred_slot_kernels.hip:
-// the same on the voices of slots named by a list in device memory).
+// the same on the voices of slots named by a list in device memory; skred_ctl_kernels.hip: patch controllers).
 #ifndef SKRED_UPDATE_COMMON_HPP
 #define SKRED_UPDATE_COMMON_HPP
 
@@ -58,6 +58,11 @@ __device__ __forceinline__ void sk_stamp_store(const sk_plane_ptrs_t &p, uint64_
   }
   *reinterpret_cast<uint4 *>(&p.ro[SKP_ENV_S][v]) = es;
   *rwflags = f;
+}
+
+// entry e of a slot list names a slot of the bank (skred_slot_kernels.hip: notes and stamps; skred_ctl_kernels.hip: controllers)
+__device__ __forceinline__ bool sk_slot_valid(int e, int slot_voices, int n_voices) {
+  return e >= 0 && (e & (slot_voices - 1)) == 0 && e <= n_voices - slot_voices;
 }
 
 // The batch was read (straight from the host's pinned staging buffer, for small batches): the workgroup that finishes last tells

@@ -41,9 +41,11 @@ ABI_SYMBOLS = [
     "skred_bank_find_idle_slots", "skred_bank_find_idle_slots_host", "skred_bank_notes_on_slots", "skred_bank_note_on_idle_slots",
     "skred_bank_stamp_slots",
     "skred_bank_find_steal_slots", "skred_bank_find_steal_slots_host", "skred_bank_note_on_steal_slots",
+    "skred_bank_ctl_range", "skred_bank_ctl_slots", "skred_bank_download_ctl",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
-HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check"]
+HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
+                    "skred_ctl_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -92,6 +94,37 @@ def note_array(notes):
         return notes
     notes = list(notes)
     return (NoteC * len(notes))(*notes)
+
+
+# SKRED_CTL_* (skred_bank_ctl_range / _ctl_slots)
+CTL_PHASE_INC, CTL_INC_SCALE, CTL_AMP, CTL_PAN, CTL_FILTER, CTL_ENV_TIMES, CTL_VELOCITY, CTL_SMOOTHING = (1 << i for i in range(8))
+CTL_FM_DEPTH, CTL_FREQ_SCALE, CTL_AM_DEPTH, CTL_PAN_DEPTH, CTL_CZ_DEPTH, CTL_CZ_DIST = (1 << i for i in range(8, 14))
+CTL_ALL = (1 << 14) - 1
+
+
+class CtlC(C.Structure):
+    """ctypes image of ``skred_ctl_t`` (96 bytes): `set` names the fields the record stores."""
+    _fields_ = [("set", C.c_uint32)] + [(name, C.c_float) for name in (
+        "phase_inc", "inc_scale", "amp", "pan_left", "pan_right", "b0", "b1", "b2", "a1", "a2",
+        "attack_time", "decay_time", "sustain_level", "release_time", "velocity", "smoothing",
+        "fm_depth", "freq_scale", "am_depth", "pan_depth", "cz_depth", "cz_dist")] + [("reserved", C.c_uint32)]
+
+
+def ctl(set: int = 0, **values) -> CtlC:
+    """A controller record: ``ctl(CTL_AMP | CTL_PAN, amp=0.5, pan_left=0.2, pan_right=0.8)``."""
+    c = CtlC()
+    c.set = int(set)
+    for k, v in values.items():
+        setattr(c, k, v)
+    return c
+
+
+def ctl_array(ctls):
+    """A contiguous ``CtlC`` array from a sequence of CtlC (a ctypes array of CtlC passes through)."""
+    if isinstance(ctls, C.Array) and ctls._type_ is CtlC:
+        return ctls
+    ctls = list(ctls)
+    return (CtlC * len(ctls))(*ctls)
 
 
 _lib: Optional[C.CDLL] = None
@@ -196,6 +229,10 @@ def load() -> C.CDLL:
     L.skred_bank_find_steal_slots.argtypes = [vp, C.POINTER(SlotStealQueryC), vp, vp, vp]
     L.skred_bank_find_steal_slots_host.argtypes = [vp, C.POINTER(SlotStealQueryC), vp, C.POINTER(i32), vp]
     L.skred_bank_note_on_steal_slots.argtypes = [vp, C.POINTER(SlotQueryC), C.POINTER(SlotStealQueryC), vp, i32, C.c_uint64, vp, vp, vp]
+    L.skred_ctl_check.argtypes = [vp, i32, C.c_uint64]
+    L.skred_bank_ctl_range.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, vp, vp]
+    L.skred_bank_ctl_slots.argtypes = [vp, vp, i32, C.c_uint64, vp, i32, vp, vp, vp]
+    L.skred_bank_download_ctl.argtypes = [vp, C.POINTER(VoiceBankC), i32, i32, i32]
     _lib = L
     return L
 
@@ -232,6 +269,13 @@ def slot_notes_check(notes, slot_voices: int, voice_mask: int) -> int:
     arr = note_array(notes)
     return int(load().skred_slot_notes_check(C.cast(arr, C.c_void_p), len(arr) // max(int(slot_voices), 1), int(slot_voices),
                                              int(voice_mask)))
+
+
+def ctl_check(ctls, voice_mask: int, slot_voices: Optional[int] = None) -> int:
+    """skred_ctl_check on the K = len(ctls) records of a controller (record l: voice l of a slot): 0, SKRED_E_BAD_ARG (-2) or
+    SKRED_E_RANGE (-4) for one the bank entry points would refuse.  Pure host."""
+    arr = ctl_array(ctls)
+    return int(load().skred_ctl_check(C.cast(arr, C.c_void_p), len(arr) if slot_voices is None else int(slot_voices), int(voice_mask)))
 
 
 class DeviceBank:
@@ -464,6 +508,27 @@ class DeviceBank:
         entries that are no slot of the bank -- the -1 of a dropped note -- are skipped."""
         _check(self.L.skred_bank_stamp_slots(self.h, d_slots or None, int(n), d_count or None, int(slot_voices), int(voice_mask),
                                              int(stamps), stream or None), "skred_bank_stamp_slots")
+
+    # ---- patch controllers (include/skred_amd.h: skred_bank_ctl_range / _ctl_slots / _download_ctl) ----
+    def ctl_range(self, ctls, first: int, count: int, voice_mask: int, d_result: int = 0, stream: int = 0):
+        """Asynchronous on `stream`: the controller (K = len(ctls) records, record l for voice l of a slot) on the masked voices of
+        every slot of [first, first + count).  d_result (uint32[2], may be 0): voices written, stores withheld by the two guards."""
+        arr = ctl_array(ctls)
+        _check(self.L.skred_bank_ctl_range(self.h, C.cast(arr, C.c_void_p), int(first), int(count), len(arr), int(voice_mask),
+                                           d_result or None, stream or None), "skred_bank_ctl_range")
+
+    def ctl_slots(self, ctls, voice_mask: int, d_slots: int, n: int, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """The same on the first min(n, d_count[0]) listed slots (d_count 0: n entries); entries that are no slot of the bank -- the
+        -1 of a dropped note -- are skipped, so an earlier d_assigned is the list for "this chord only"."""
+        arr = ctl_array(ctls)
+        _check(self.L.skred_bank_ctl_slots(self.h, C.cast(arr, C.c_void_p), len(arr), int(voice_mask), d_slots or None, int(n),
+                                           d_count or None, d_result or None, stream or None), "skred_bank_ctl_slots")
+
+    def download_ctl(self, bank: VoiceBank, src_first: int = 0, dst_first: int = 0, count: Optional[int] = None):
+        """The words a controller can store, as the device holds them, into `bank` (download() returns the state fields only)."""
+        count = bank.n - dst_first if count is None else count
+        cb = bank.as_c()
+        _check(self.L.skred_bank_download_ctl(self.h, C.byref(cb), src_first, dst_first, count), "skred_bank_download_ctl")
 
     # ---- slot stealing (include/skred_amd.h: skred_bank_find_steal_slots / _find_steal_slots_host / _note_on_steal_slots) ----
     def find_steal_slots(self, q: SlotStealQueryC, d_slots: int = 0, d_count: int = 0, stream: int = 0):

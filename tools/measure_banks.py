@@ -859,8 +859,111 @@ def slotsteal():
     db.close()
 
 
+def ctl():
+    """A cutoff change on every copy of bank_patch("3sk", 2**20) -- the three carriers of every copy filtered and enveloped -- through
+    skred_bank_ctl_range, against the only route before it (host-view writes + skred_bank_update of those voices); ctl_slots on a
+    256-slot list; the 64-frame block after the sweep beside the steady block of the same run; the blocks after a bank-wide AMP
+    controller (every voice listed) until the block time is back at the steady one.  Medians of 12."""
+    D = device
+    n, K, REPS, F, LIST = 1 << 20, 4, 12, 64, 256
+    CARRIERS = 0x7
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    sel = (np.arange(n) % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel], e["sample_start"][sel] = 1.0, 1, np.uint64(now - 40000)
+    co = banks.biquad_coeffs(np.array([1]), np.array([1200.0], np.float32), np.array([1.0], np.float32), 44100)
+    bank["voice_filter_mode"][sel] = 1
+    for k, v in co.items():
+        bank["voice_filter"][k][sel] = v[0]
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.upload(bank); db.set_globals(g)
+    out = torch.zeros(F, 2, device="cuda")
+    dres = torch.zeros(2, dtype=torch.int32, device="cuda")
+    dlist = torch.from_numpy((np.random.default_rng(5).choice(n // K, LIST, replace=False) * K).astype(np.int32)).cuda()
+    mirror = bank.copy()
+    carriers = np.flatnonzero(sel).astype(np.int32)
+
+    def coeffs(i):
+        c = banks.biquad_coeffs(np.array([1]), np.array([600.0 + 150.0 * i], np.float32), np.array([1.0], np.float32), 44100)
+        return {k: float(v[0]) for k, v in c.items()}
+
+    def sweep(i):
+        c = coeffs(i)
+        return D.ctl_array([D.ctl(D.CTL_FILTER if l < 3 else 0, **c) for l in range(K)])
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        t0 = time.perf_counter()
+        fn()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+
+    def host_route(i):
+        c = coeffs(i)
+        for k, v in c.items():
+            mirror["voice_filter"][k][carriers] = np.float32(v)
+        db.update(mirror, carriers, D.DIRTY_PARAMS)
+
+    def show(label, host, stream, extra=""):
+        print(f"  {label}: host time median {np.median(host):.4f} ms (min {np.min(host):.4f}, max {np.max(host):.4f}); stream time between "
+              f"events median {np.median(stream):.4f} ms (min {np.min(stream):.4f}, max {np.max(stream):.4f}){extra}")
+
+    print(f"3sk {n} voices = {n // K} copies of {K}, carriers filtered and enveloped, {F}-frame blocks, medians of {REPS}")
+    for _ in range(8):
+        block()
+    steady, after, host, stream = [], [], [], []
+    for i in range(2 + REPS):
+        b0 = block()
+        arr = sweep(i)
+        h, s_ms = timed(lambda: db.ctl_range(arr, 0, n, CARRIERS, dres.data_ptr()))
+        b1 = block()
+        if i >= 2:
+            steady.append(b0); after.append(b1); host.append(h); stream.append(s_ms)
+    show("1. ctl_range, FILTER on the carriers of every copy", host, stream, f"; d_result = {dres.cpu().numpy().tolist()}")
+    print(f"  4. the block after it: median {np.median(after):.4f} ms (min {np.min(after):.4f}, max {np.max(after):.4f}); the steady block in front of it: "
+          f"median {np.median(steady):.4f} ms (min {np.min(steady):.4f}, max {np.max(steady):.4f})")
+    host, stream = [], []
+    for i in range(2 + REPS):
+        arr = sweep(i)
+        h, s_ms = timed(lambda: db.ctl_slots(arr, CARRIERS, dlist.data_ptr(), LIST, 0, dres.data_ptr()))
+        if i >= 2:
+            host.append(h); stream.append(s_ms)
+    show(f"3. ctl_slots, the same on a list of {LIST} slots", host, stream, f"; d_result = {dres.cpu().numpy().tolist()}")
+    host, stream = [], []
+    for i in range(1 + 3):
+        h, s_ms = timed(lambda: host_route(i))
+        if i >= 1:
+            host.append(h); stream.append(s_ms)
+        for _ in range(6):
+            block()
+    show(f"2. host-view writes + skred_bank_update of the {len(carriers)} carriers (3 runs)", host, stream)
+    for _ in range(8):
+        block()
+    base = float(np.median([block() for _ in range(REPS)]))
+    firsts, back = [], []
+    for i in range(REPS):
+        arr = D.ctl_array([D.ctl(D.CTL_AMP if l < 3 else 0, amp=0.5 + 0.01 * i) for l in range(K)])
+        db.ctl_range(arr, 0, n, CARRIERS, dres.data_ptr())
+        times = [block() for _ in range(24)]
+        firsts.append(times[0])
+        back.append(next((k for k, t in enumerate(times) if t <= 1.1 * base), len(times)))
+    print(f"  5. the block after a bank-wide AMP controller: median {np.median(firsts):.4f} ms (min {np.min(firsts):.4f}, max {np.max(firsts):.4f}), steady "
+          f"{base:.4f} ms; blocks until within 10 % of the steady time: median {np.median(back):.0f} (min {np.min(back)}, max {np.max(back)}; 24: not within 24)")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
