@@ -823,6 +823,78 @@ int  skred_bank_ctl_slots(skred_bank_t *bank, const skred_ctl_t *ctl, int slot_v
  * Waits for the device, like skred_bank_download; windows as there. */
 int  skred_bank_download_ctl(skred_bank_t *bank, skred_voice_bank_t *host, int src_first, int dst_first, int count);
 
+/* ---- note owners: note-offs and controllers that cannot hit a stolen slot --------------------------------------------------
+ *
+ * A note-off is skred_bank_stamp_slots on an earlier d_assigned, "this chord only" is skred_bank_ctl_slots on one: both act on a
+ * slot INDEX, and since the stealing calls exist that index may hold somebody else's note by the time the call arrives (chord A is
+ * placed, the bank fills up, chord B steals A's slots, A's key is lifted: B is released).  A host that kept its own key -> slot map
+ * would have to read every d_assigned back, one stream wait per burst.  These calls keep the answer on the device instead.
+ *
+ * owner[n_voices] is a uint32 array in device memory that only the calls of this section read or write.  The OWNER of a slot is the
+ * word at the slot's FIRST voice (K = 1: the voice's own word; ranges of different K can live in one bank); 0 means "nobody".  The
+ * bank allocates the array (4 bytes per voice) on the first call of this section other than _owner_clear and _download_owners and
+ * zero-fills it; that first call waits for the device once, like the first query.  skred_bank_upload, _update, the renders, notes,
+ * stamps, steals and controllers above never touch it, and no render kernel, probe, tap or report reads it: state, mix, reports
+ * and form counters of every block are bit-identical to the same blocks without owner calls.
+ *
+ * The sequence of a MIDI-style host: draw a non-zero tag per note, place the burst with any of the six note-on calls, then
+ * skred_bank_tag_slots(d_assigned, tags) on the same stream -- a thief's tags overwrite its victims'.  Note-off by id:
+ * skred_bank_release_tags(tags); note-off or "this chord only" on a kept d_assigned: skred_bank_stamp_owned / _ctl_owned with the
+ * tags the entries are expected to carry.  Tagged and untagged note-ons should not share a range: an untagged note that steals a
+ * tagged slot leaves the victim's tag in place, and the victim's note-off would release it.
+ * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring, so the
+ * caller's array is free on return and nothing waits for the device.  A slot, K = slot_voices and voice_mask mean what they mean for
+ * skred_bank_notes_on_slots.  n == 0: SKRED_OK, nothing is done.  On a shard: through skred_shard_bank(), with that rank's local
+ * indices.  Not in the fixed-point bank or the drop-in mode; deferred items and pattern steps carry no tags. */
+#define SKRED_OWNER_MAX_TAGS 1024
+enum { SKRED_OWNER_ALLOW_ZERO = 1u << 0,   /* tag 0 is accepted (skred_bank_tag_slots: it clears the owner) */
+       SKRED_OWNER_UNIQUE     = 1u << 1 }; /* no tag twice and n <= SKRED_OWNER_MAX_TAGS (skred_bank_find_owned, _release_tags) */
+/* Pure host, no device: SKRED_OK, or SKRED_E_BAD_ARG for NULL tags, n < 0, unknown flags, a zero tag without ALLOW_ZERO, and with
+ * UNIQUE a tag that appears twice or n > SKRED_OWNER_MAX_TAGS.  Every entry point below calls it before anything touches the device. */
+int  skred_owner_tags_check(const uint32_t *tags, int n, uint32_t flags);
+/* owner[d_slots[k]] = tags[k] (host uint32[n]; 0 clears) for the first min(n, *d_count_or_null) entries (NULL: n) that are slots of
+ * the bank -- skred_bank_stamp_slots' rule, so a d_assigned with its -1 holes is the natural argument right after a note-on call.
+ * A slot named twice with different tags ends up with one of them, unspecified which.  d_result (device, uint32[2], may be NULL) is
+ * cleared on the stream ahead of the kernel: [0] slots tagged, [1] entries of those first min(n, count) that are no slot.
+ * SKRED_E_BAD_ARG: NULL bank, list or tags, n < 0 or n > INT32_MAX / 64; SKRED_E_RANGE: a bad K. */
+int  skred_bank_tag_slots(skred_bank_t *bank, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                          int slot_voices, uint32_t *d_result, void *stream);
+/* d_slots_out[k] (device, int32[n]) = the LOWEST first voice of a slot of [first, first + count) whose owner equals tags[k], or -1.
+ * tags: host uint32[n], 1 <= n <= SKRED_OWNER_MAX_TAGS, none zero, none twice.  The same state gives the same bytes, whatever order
+ * the workgroups arrive in (an unsigned minimum); no workgroup waits for another.  SKRED_E_BAD_ARG: NULL bank, tags or d_slots_out,
+ * what skred_owner_tags_check(UNIQUE) refuses; SKRED_E_RANGE: a bad K, first or count not a multiple of K, count <= 0, a range
+ * outside the bank. */
+int  skred_bank_find_owned(skred_bank_t *bank, int first, int count, int slot_voices, const uint32_t *tags, int n,
+                           int32_t *d_slots_out, void *stream);
+/* skred_bank_stamp_slots with a guard: entry k (of the first min(n, *d_count_or_null)) is stamped only if it is a slot of the bank
+ * AND owner[slot] == tags[k]; tags are non-zero, so an untagged slot never matches.  The stores are skred_bank_stamp_slots'.
+ * d_result (device, uint32[3], required) is cleared on the stream ahead of the kernel: [0] slots stamped, [1] slots whose owner
+ * differs (the note was stolen or re-tagged), [2] entries that are no slot; sums, the same whatever the order of arrival.
+ * SKRED_E_BAD_ARG: NULL bank, list, tags or result, n < 0 or n > INT32_MAX / 64, a zero tag, bad stamp bits, a bad voice_mask;
+ * SKRED_E_RANGE: a bad K. */
+int  skred_bank_stamp_owned(skred_bank_t *bank, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                            int slot_voices, uint64_t voice_mask, uint32_t stamps, uint32_t *d_result, void *stream);
+/* Note-off by note id: skred_bank_find_owned into scratch the bank owns, then skred_bank_stamp_owned on that list with the same
+ * tags.  Each tag stamps at most ONE slot, the lowest that carries it, so the call lists at most n * popcount(voice_mask) voices
+ * whatever the caller tagged.  d_result as for skred_bank_stamp_owned; [2] counts the tags nobody in the range carries, [1] is 0.
+ * One stream at a time per bank, as for the queries.  Refusals of both calls. */
+int  skred_bank_release_tags(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t voice_mask, const uint32_t *tags,
+                             int n, uint32_t stamps, uint32_t *d_result, void *stream);
+/* skred_bank_ctl_slots under the same guard: the same stores, the same two withheld-store rules, the same motion-list rule, and a
+ * controller that lists nobody leaves the planner's reports alone.  d_result (device, uint32[3], may be NULL): [0] voices written,
+ * [1] stores withheld, [2] slots whose owner differs.  Refused: what skred_bank_ctl_slots refuses, NULL tags, a zero tag. */
+int  skred_bank_ctl_owned(skred_bank_t *bank, const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
+                          const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+/* owner[first .. first + count) = 0 on `stream` (nothing to do on a bank that was never tagged).  SKRED_E_RANGE: count < 0 or a
+ * range outside the bank. */
+int  skred_bank_owner_clear(skred_bank_t *bank, int first, int count, void *stream);
+/* The owner words of [first, first + count) into host_u32; waits for the device, like skred_bank_download; zeros on a bank that
+ * was never tagged. */
+int  skred_bank_download_owners(skred_bank_t *bank, uint32_t *host_u32, int first, int count);
+/* The envelope clocks of [first, first + count) as the device holds them -- what skred_bank_download leaves out, and what a stamp
+ * stores: sample_start and sample_release (either may be NULL).  Waits for the device, like skred_bank_download. */
+int  skred_bank_download_env_clocks(skred_bank_t *bank, uint64_t *sample_start, uint64_t *sample_release, int first, int count);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

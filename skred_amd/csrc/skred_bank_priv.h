@@ -3,7 +3,7 @@
  * (skred_bank.c: lifecycle, tables, upload / download, options, class and tape plan; skred_bank_render.c:
  * one block from request to kernels, as skred_bank_plan.c picks them; skred_bank_update.c: block-granular
  * updates and the deferred queue; skred_bank_idle.c: the free-voice query; skred_bank_steal.c: the victim query; skred_bank_notes.c: note-ons and stamps on voices a
- * device-resident list names; skred_bank_slots.c: the same for the slots of a tiled patch).  Not installed.
+ * device-resident list names; skred_bank_slots.c: the same for the slots of a tiled patch; skred_bank_ctl.c: patch controllers; skred_bank_owner.c: note owners).  Not installed.
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -188,6 +188,9 @@ struct skred_bank {
   int steal_wgs;
   int32_t *d_steal_out;             /* [2] counts, then SK_STEAL_MAX victims: skred_bank_find_steal_host's list and skred_bank_note_on_steal's */
   int32_t *h_steal_out;             /* ... its pinned twin */
+  /* note owners (skred_bank_owner.c), allocated and zeroed by the first call that needs them */
+  uint32_t *d_owner;                /* [n_voices] a slot's tag at its first voice, 0: nobody; no render kernel reads it */
+  int32_t *d_owner_slots;           /* [SKRED_OWNER_MAX_TAGS] skred_bank_release_tags: the list its find pass leaves for its stamps (behind d_owner) */
 };
 
 /* per-voice classification (host shadow) */
@@ -268,6 +271,10 @@ int sk_note_list_room(skred_bank_t *b, int n);
 /* skred_bank_ctl.c: the K records of a checked controller as they travel (masked ones word for word, the others zeroed); returns the
  * mask of the voices whose record puts them on the motion list.  Pure host */
 uint64_t sk_ctl_pack(const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask, sk_ctl_t *out);
+/* skred_bank_owner.c: the owner array (skred_bank_destroy); n <= SKRED_OWNER_MAX_TAGS tags as the find pass reads them -- sorted[j]
+ * ascending as unsigned numbers, perm[j] the index that tag has in `tags`; returns 0, or 1 + the index of a repeated tag.  Pure host */
+void sk_owner_free(skred_bank_t *b);
+int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
 /* skred_bank_idle.c, for skred_bank_slots.c: the scratch both list queries share (allocated on first use), the kernels' view of a
  * query on this bank, and room for `need` entries in d_idle_out / h_idle_out */
 int sk_idle_scratch(skred_bank_t *b, hipStream_t s);

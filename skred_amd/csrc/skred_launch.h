@@ -16,7 +16,8 @@
  *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_steal_select, sk_launch_list_append
  *   skred_slot_kernels.hip    sk_launch_slots, sk_launch_slot_notes, sk_launch_slot_stamps
  *   skred_slot_steal_kernels.hip  sk_launch_slot_steal
- *   skred_ctl_kernels.hip     sk_launch_ctl_range, sk_launch_ctl_slots
+ *   skred_ctl_kernels.hip     sk_launch_ctl_range, sk_launch_ctl_slots, sk_launch_ctl_owned
+ *   skred_owner_kernels.hip   sk_launch_owner_tag, sk_launch_owner_find, sk_launch_owner_stamps
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
@@ -263,6 +264,34 @@ int sk_launch_ctl_range(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_
 int sk_launch_ctl_slots(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_mask, const int32_t *d_slots, int n,
                         const uint32_t *d_count, int n_voices, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
                         uint64_t *mask, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+
+/* ---- note owners (skred_bank_owner.c -> skred_owner_kernels.hip, the guarded controller in skred_ctl_kernels.hip;
+ * include/skred_amd.h: skred_bank_tag_slots / _find_owned / _stamp_owned / _release_tags / _ctl_owned) ----
+ * owner[n_voices]: one word per voice, a slot's owner at its first voice, 0 nobody.  Only these launches read or write it.
+ * d_tags and the other staged arrays may be the pinned staging buffer; cnt / done / seq as for sk_launch_update. */
+#define SK_OWNER_MAX_TAGS 1024
+#define SK_OWNER_SPAN 256          /* threads per workgroup of the owner kernels */
+/* owner[d_slots[k]] = d_tags[k] for the first min(n, d_count[0]) entries (d_count NULL: n) that are slots of the bank; d_result[2]
+ * (or NULL; zeroed on `stream` ahead of the kernel) += slots tagged, entries that are no slot */
+int sk_launch_owner_tag(uint32_t *owner, const int32_t *d_slots, const uint32_t *d_tags, int n, const uint32_t *d_count, int slot_voices,
+                        int n_voices, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* d_out[d_perm[j]] = min over the slots of [first, first + count) whose owner is d_sorted[j] of the slot's first voice, as an
+ * unsigned minimum onto d_out[0 .. n) preset to all-ones on `stream` (-1: nobody).  d_sorted: the n tags ascending as unsigned
+ * numbers, none zero, none twice; d_perm: where each stood in the caller's array.  One lane per slot */
+int sk_launch_owner_find(const uint32_t *owner, int first, int count, int slot_voices, const uint32_t *d_sorted, const uint32_t *d_perm,
+                         int n, int32_t *d_out, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* sk_launch_slot_stamps on the entries whose owner word equals d_tags[k]; d_result[3] (zeroed on `stream` ahead of the kernel) +=
+ * slots stamped, slots whose owner differs, entries that are no slot */
+int sk_launch_owner_stamps(const uint32_t *owner, const int32_t *d_slots, const uint32_t *d_tags, int n, const uint32_t *d_count,
+                           int slot_voices, uint64_t voice_mask, int n_voices, uint32_t dirty, sk_plane_t *const ro[SKP_COUNT],
+                           sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask, uint32_t *d_result, uint32_t *cnt,
+                           uint32_t *done, uint32_t seq, hipStream_t stream);
+/* sk_launch_ctl_slots on the entries whose owner word equals d_tags[k]; d_result[3] (or NULL): voices written, stores withheld,
+ * slots whose owner differs */
+int sk_launch_ctl_owned(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_mask, const int32_t *d_slots, const uint32_t *d_tags,
+                        const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, sk_plane_t *const ro[SKP_COUNT],
+                        sk_plane_t *const rw[SKS_COUNT], uint64_t *mask, uint32_t *d_result, uint32_t *cnt, uint32_t *done,
+                        uint32_t seq, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

@@ -42,10 +42,12 @@ ABI_SYMBOLS = [
     "skred_bank_stamp_slots",
     "skred_bank_find_steal_slots", "skred_bank_find_steal_slots_host", "skred_bank_note_on_steal_slots",
     "skred_bank_ctl_range", "skred_bank_ctl_slots", "skred_bank_download_ctl",
+    "skred_bank_tag_slots", "skred_bank_find_owned", "skred_bank_stamp_owned", "skred_bank_release_tags", "skred_bank_ctl_owned",
+    "skred_bank_owner_clear", "skred_bank_download_owners", "skred_bank_download_env_clocks",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
-                    "skred_ctl_check"]
+                    "skred_ctl_check", "skred_owner_tags_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -125,6 +127,16 @@ def ctl_array(ctls):
         return ctls
     ctls = list(ctls)
     return (CtlC * len(ctls))(*ctls)
+
+
+# SKRED_OWNER_* (skred_bank_tag_slots / _find_owned / _stamp_owned / _release_tags / _ctl_owned)
+OWNER_MAX_TAGS = 1024
+OWNER_ALLOW_ZERO, OWNER_UNIQUE = 1, 2
+
+
+def tag_array(tags) -> np.ndarray:
+    """A contiguous uint32 array of note tags."""
+    return np.ascontiguousarray(tags, dtype=np.uint32)
 
 
 _lib: Optional[C.CDLL] = None
@@ -233,6 +245,15 @@ def load() -> C.CDLL:
     L.skred_bank_ctl_range.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, vp, vp]
     L.skred_bank_ctl_slots.argtypes = [vp, vp, i32, C.c_uint64, vp, i32, vp, vp, vp]
     L.skred_bank_download_ctl.argtypes = [vp, C.POINTER(VoiceBankC), i32, i32, i32]
+    L.skred_owner_tags_check.argtypes = [vp, i32, C.c_uint32]
+    L.skred_bank_tag_slots.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
+    L.skred_bank_find_owned.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp]
+    L.skred_bank_stamp_owned.argtypes = [vp, vp, vp, i32, vp, i32, C.c_uint64, C.c_uint32, vp, vp]
+    L.skred_bank_release_tags.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, i32, C.c_uint32, vp, vp]
+    L.skred_bank_ctl_owned.argtypes = [vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_owner_clear.argtypes = [vp, i32, i32, vp]
+    L.skred_bank_download_owners.argtypes = [vp, vp, i32, i32]
+    L.skred_bank_download_env_clocks.argtypes = [vp, vp, vp, i32, i32]
     _lib = L
     return L
 
@@ -276,6 +297,12 @@ def ctl_check(ctls, voice_mask: int, slot_voices: Optional[int] = None) -> int:
     SKRED_E_RANGE (-4) for one the bank entry points would refuse.  Pure host."""
     arr = ctl_array(ctls)
     return int(load().skred_ctl_check(C.cast(arr, C.c_void_p), len(arr) if slot_voices is None else int(slot_voices), int(voice_mask)))
+
+
+def owner_tags_check(tags, flags: int = 0) -> int:
+    """skred_owner_tags_check: 0, or SKRED_E_BAD_ARG (-2) for tags the owner entry points would refuse.  Pure host."""
+    arr = tag_array(tags)
+    return int(load().skred_owner_tags_check(arr.ctypes.data, len(arr), int(flags)))
 
 
 class DeviceBank:
@@ -529,6 +556,61 @@ class DeviceBank:
         count = bank.n - dst_first if count is None else count
         cb = bank.as_c()
         _check(self.L.skred_bank_download_ctl(self.h, C.byref(cb), src_first, dst_first, count), "skred_bank_download_ctl")
+
+    # ---- note owners (include/skred_amd.h: skred_bank_tag_slots / _find_owned / _stamp_owned / _release_tags / _ctl_owned) ----
+    def tag_slots(self, d_slots: int, tags, slot_voices: int, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """Asynchronous on `stream`: owner[d_slots[k]] = tags[k] (0 clears) for the first min(len(tags), d_count[0]) entries that are
+        slots of the bank -- a d_assigned, -1 holes and all.  d_result (uint32[2], may be 0): slots tagged, entries that are no slot."""
+        arr = tag_array(tags)
+        _check(self.L.skred_bank_tag_slots(self.h, d_slots or None, arr.ctypes.data, len(arr), d_count or None, int(slot_voices),
+                                           d_result or None, stream or None), "skred_bank_tag_slots")
+
+    def find_owned(self, first: int, count: int, slot_voices: int, tags, d_slots_out: int, stream: int = 0):
+        """d_slots_out[k] (int32, device memory) = the lowest slot of [first, first + count) whose owner is tags[k], or -1."""
+        arr = tag_array(tags)
+        _check(self.L.skred_bank_find_owned(self.h, int(first), int(count), int(slot_voices), arr.ctypes.data, len(arr),
+                                            d_slots_out or None, stream or None), "skred_bank_find_owned")
+
+    def stamp_owned(self, d_slots: int, tags, slot_voices: int, voice_mask: int, stamps: int, d_result: int, d_count: int = 0,
+                    stream: int = 0):
+        """stamp_slots on the entries whose owner is tags[k].  d_result (uint32[3]): slots stamped, slots whose owner differs, entries
+        that are no slot."""
+        arr = tag_array(tags)
+        _check(self.L.skred_bank_stamp_owned(self.h, d_slots or None, arr.ctypes.data, len(arr), d_count or None, int(slot_voices),
+                                             int(voice_mask), int(stamps), d_result or None, stream or None), "skred_bank_stamp_owned")
+
+    def release_tags(self, first: int, count: int, slot_voices: int, voice_mask: int, tags, stamps: int, d_result: int, stream: int = 0):
+        """Note-off by note id: every tag stamps the lowest slot of the range that carries it.  d_result as for stamp_owned; [2] counts
+        the tags nobody carries."""
+        arr = tag_array(tags)
+        _check(self.L.skred_bank_release_tags(self.h, int(first), int(count), int(slot_voices), int(voice_mask), arr.ctypes.data, len(arr),
+                                              int(stamps), d_result or None, stream or None), "skred_bank_release_tags")
+
+    def ctl_owned(self, ctls, voice_mask: int, d_slots: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """ctl_slots on the entries whose owner is tags[k].  d_result (uint32[3], may be 0): voices written, stores withheld, slots
+        whose owner differs."""
+        arr, t = ctl_array(ctls), tag_array(tags)
+        _check(self.L.skred_bank_ctl_owned(self.h, C.cast(arr, C.c_void_p), len(arr), int(voice_mask), d_slots or None, t.ctypes.data,
+                                           len(t), d_count or None, d_result or None, stream or None), "skred_bank_ctl_owned")
+
+    def owner_clear(self, first: int = 0, count: Optional[int] = None, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_bank_owner_clear(self.h, int(first), int(count), stream or None), "skred_bank_owner_clear")
+
+    def download_owners(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The owner words of [first, first + count) (uint32); waits for the device.  Zeros on a bank that was never tagged."""
+        count = self.n - first if count is None else count
+        out = np.full(max(count, 0), 0xDEADBEEF, np.uint32)
+        _check(self.L.skred_bank_download_owners(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_owners")
+        return out
+
+    def download_env_clocks(self, first: int = 0, count: Optional[int] = None):
+        """(sample_start, sample_release) of [first, first + count) as the device holds them (uint64); waits for the device."""
+        count = self.n - first if count is None else count
+        start, release = np.zeros(max(count, 0), np.uint64), np.zeros(max(count, 0), np.uint64)
+        _check(self.L.skred_bank_download_env_clocks(self.h, start.ctypes.data, release.ctypes.data, int(first), int(count)),
+               "skred_bank_download_env_clocks")
+        return start, release
 
     # ---- slot stealing (include/skred_amd.h: skred_bank_find_steal_slots / _find_steal_slots_host / _note_on_steal_slots) ----
     def find_steal_slots(self, q: SlotStealQueryC, d_slots: int = 0, d_count: int = 0, stream: int = 0):

@@ -962,8 +962,108 @@ def ctl():
     db.close()
 
 
+def owners():
+    """Note-off by note id on bank_patch("3sk", 2**20), every copy sounding: a burst of 256 patch notes through
+    skred_bank_note_on_steal_slots (all of them stolen) is tagged from its own d_assigned, two blocks of 64 frames pass, and the chord is
+    released.  (a) skred_bank_release_tags of the 256 tags; (b) the only correct route before it: the burst's d_assigned copied to the
+    host behind a stream wait, a key -> slot map kept in Python (a stolen slot's earlier key evicted), the note-off list uploaded and
+    skred_bank_stamp_slots; (c) the 64-frame block after (a) beside the block after stamp_slots of the same slots.  Every repetition
+    uploads the bank and renders a block first.  Medians of 12 with minimum and maximum, stream events around the device calls."""
+    D = device
+    n, K, NOTES, REPS, F = 1 << 20, 4, 256, 12, 64
+    MEMBERS, VOICES = 0x7, 0xF
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = (now - 40000 - ((v[sel] // K) * 7919) % 30000 - (v[sel] % K)).astype(np.uint64)   # every copy its own age
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g)
+    which = D.IDLE_ENV_DONE
+    iq = D.slot_query(0, n, K, MEMBERS, which, 1e-3, 0, NOTES)
+    sq = D.slot_steal_query(0, n, K, MEMBERS, D.STEAL_OLDEST, 0, 0, which, 1e-3, NOTES)
+    notes = D.note_array([D.NoteC(0.4 + 0.001 * i, 0.8, 0.0, 0.5, 0.5, D.NOTE_SET_PHASE) for i in range(NOTES * K)])
+    tags = (0x80000000 + 17 * np.arange(NOTES)).astype(np.uint32)
+    da = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+    res = torch.zeros(3, dtype=torch.int32, device="cuda")
+    out = torch.zeros(F, 2, device="cuda")
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+
+    def by_tags():
+        db.note_on_steal_slots(notes, iq, sq, VOICES, da.data_ptr(), dr.data_ptr())
+        db.tag_slots(da.data_ptr(), tags, K)                       # (nothing waited for: the host never sees d_assigned)
+        block(); block()
+        torch.cuda.synchronize()
+        h, s_ms = timed(lambda: db.release_tags(0, n, K, VOICES, tags, D.STAMP_RELEASE, res.data_ptr()))
+        return h, s_ms, block(), res.cpu().numpy().tolist()
+
+    key_of, slot_of = {}, {}
+
+    def by_map():
+        db.note_on_steal_slots(notes, iq, sq, VOICES, da.data_ptr(), dr.data_ptr())
+        t0 = time.perf_counter()
+        got = da.cpu().numpy()                                     # the stream wait a device-side note-on was built to remove
+        for k, slot in enumerate(got.tolist()):
+            if slot < 0:
+                continue
+            old = key_of.pop(slot, None)                           # a theft: the slot's earlier key no longer names it
+            if old is not None:
+                slot_of.pop(old, None)
+            key_of[slot], slot_of[int(tags[k])] = int(tags[k]), slot
+        h_map = (time.perf_counter() - t0) * 1e3
+        block(); block()
+        torch.cuda.synchronize()
+
+        def off():
+            lst = np.array([slot_of[int(t)] for t in tags if int(t) in slot_of], np.int32)
+            dl = torch.from_numpy(lst).cuda()
+            db.stamp_slots(dl.data_ptr(), len(lst), K, VOICES, D.STAMP_RELEASE)
+        h, s_ms = timed(off)
+        return h_map + h, s_ms, block(), [h_map, h]
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, every copy sounding; a block, a burst of {NOTES} stolen patch notes, two blocks of {F} frames, the note-off; medians of {REPS}")
+    blocks = {}
+    for label, route in (("(a) release_tags of 256 tags (find pass over the whole bank + guarded stamps, on the device)", by_tags),
+                         ("(b) d_assigned read back behind a stream wait + key -> slot map in Python + list upload + stamp_slots", by_map)):
+        host, stream, after, extra = [], [], [], None
+        for it in range(2 + REPS):
+            db.upload(bank)
+            db.render_mix(F, out.data_ptr(), 2, 0, 0)
+            torch.cuda.synchronize()
+            key_of.clear(); slot_of.clear()
+            h, s_ms, b, extra = route()
+            torch.cuda.synchronize()
+            if it >= 2:
+                host.append(h); stream.append(s_ms); after.append(b)
+        blocks[label[:3]] = after
+        tail = f"d_result = {extra}" if label.startswith("(a)") else f"last run: readback and map {extra[0]:.4f} ms + note-off {extra[1]:.4f} ms"
+        print(f"  {label}: host time held median {np.median(host):.4f} ms (min {np.min(host):.4f}, max {np.max(host):.4f}); stream time of the note-off "
+              f"between events median {np.median(stream):.4f} ms (min {np.min(stream):.4f}, max {np.max(stream):.4f}); {tail}")
+    for key, what in (("(a)", "release_tags"), ("(b)", "stamp_slots of the same slots")):
+        t = blocks[key]
+        print(f"  (c) the {F}-frame block after {what}: median {np.median(t):.4f} ms (min {np.min(t):.4f}, max {np.max(t):.4f})")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
