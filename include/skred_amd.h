@@ -776,8 +776,9 @@ int  skred_bank_note_on_steal_slots(skred_bank_t *bank, const skred_slot_query_t
  * or a smoother moving); the other controllers do not, so a bank-wide filter sweep costs the next block nothing.
  * LIMIT, as for notes: the host view goes stale.  Before a later skred_bank_update with SKRED_DIRTY_PARAMS (or SKRED_DIRTY_PAN) of
  * such a voice, mirror the values into the host view; skred_bank_download_ctl reads them back where the host cannot know them (a
- * scaled increment, a withheld amp).  On a shard: through skred_shard_bank(), with that rank's local indices.  Not in the fixed-point
- * bank or the drop-in mode; deferred items and pattern steps carry host records only. */
+ * scaled increment, a withheld amp).  On a shard: through skred_shard_bank(), with that rank's local indices.  The fixed-point bank
+ * has per-voice controllers of its own (include/skred_amd_fxpt.h: skred_fxbank_ctl_range / _ctl_list / _ctl_owned, without slots and
+ * without the depth, scale and CZ fields).  Not in the drop-in mode; deferred items and pattern steps carry host records only. */
 enum { SKRED_CTL_PHASE_INC = 1u<<0,  /* voice_phase_inc = phase_inc */
        SKRED_CTL_INC_SCALE = 1u<<1,  /* voice_phase_inc = voice_phase_inc * inc_scale: ONE float multiply, unfused; a product that is
                                         not finite is not stored (the voice keeps its increment; counted in d_result[1]) */
@@ -845,7 +846,9 @@ int  skred_bank_download_ctl(skred_bank_t *bank, skred_voice_bank_t *host, int s
  * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring, so the
  * caller's array is free on return and nothing waits for the device.  A slot, K = slot_voices and voice_mask mean what they mean for
  * skred_bank_notes_on_slots.  n == 0: SKRED_OK, nothing is done.  On a shard: through skred_shard_bank(), with that rank's local
- * indices.  Not in the fixed-point bank or the drop-in mode; deferred items and pattern steps carry no tags. */
+ * indices.  The fixed-point bank has the same calls per voice (include/skred_amd_fxpt.h: skred_fxbank_tag_list / _find_owned /
+ * _stamp_owned / _release_tags / _ctl_owned / _owner_clear / _download_owners), which share skred_owner_tags_check and the tag and
+ * find kernels with these.  Not in the drop-in mode; deferred items and pattern steps carry no tags. */
 #define SKRED_OWNER_MAX_TAGS 1024
 enum { SKRED_OWNER_ALLOW_ZERO = 1u << 0,   /* tag 0 is accepted (skred_bank_tag_slots: it clears the owner) */
        SKRED_OWNER_UNIQUE     = 1u << 1 }; /* no tag twice and n <= SKRED_OWNER_MAX_TAGS (skred_bank_find_owned, _release_tags) */

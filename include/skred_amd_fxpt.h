@@ -120,7 +120,8 @@ int  skred_fxbank_stamp(skred_fxbank_t *fx, const int32_t *voices, int n_voices,
  * and their kin) on the fixed-point planes, with the same vocabulary: SKRED_DIRTY_* / SKRED_STAMP_*, SKRED_IDLE_*, SKRED_NOTE_*
  * keep their bit values.  Everything is asynchronous on the caller's stream, ordered like the renders queued on it; nothing here
  * waits for the device.  The calls work on a shard through skred_fxshard_bank(), with that rank's LOCAL voice indices.
- * Not here (yet): the deferred queue and the step clock, taps.
+ * Note owners and controllers have a section of their own below.  Not here (yet): the deferred queue and the step clock, taps,
+ * slots of more than one voice.
  *
  * Transport.  Records travel through a ring of SKRED_FX_RING_SLOTS pinned staging slots: one hipMemcpyAsync per batch into the
  * slot's device twin on `stream`, then the kernels, then an event of the slot's own.  The caller's arrays are free again when a
@@ -245,6 +246,113 @@ int  skred_fxbank_find_steal_host(skred_fxbank_t *fx, const skred_fx_steal_query
  * (SKRED_IDLE_AMP_ZERO among it), what skred_fx_steal_check refuses, what skred_fx_notes_check refuses. */
 int  skred_fxbank_note_on_steal(skred_fxbank_t *fx, const skred_fx_idle_query_t *idle_q, const skred_fx_steal_query_t *steal_q,
                                 const skred_fx_note_t *notes, int n, int32_t *d_assigned, uint32_t *d_result, void *stream);
+
+/* ---- note owners and controllers: note-offs and control changes that cannot hit a stolen voice ------------------------------
+ *
+ * The float bank's two sections of the same names (include/skred_amd.h: skred_bank_tag_slots .. skred_bank_download_owners,
+ * skred_bank_ctl_range / _ctl_slots / _ctl_owned) on the fixed-point planes.  This bank has NO SLOTS: every call is per voice,
+ * which is the float call at K = slot_voices = 1 and voice_mask = 1; slots (K > 1) are out of scope here.  Everything is
+ * asynchronous on the caller's stream and ordered like skred_fxbank_update; host arrays (tags, the controller record) travel through
+ * the ring of SKRED_FX_RING_SLOTS staging slots, so the caller's array is free on return and nothing waits for the device.  The
+ * calls work on a shard through skred_fxshard_bank(), with that rank's LOCAL voice indices.  n == 0 (count == 0 for _ctl_range and
+ * _owner_clear): SKRED_OK, nothing is done.  Every refusal comes before anything touches the device and leaves the bank usable.
+ *
+ * Owner words.  owner[n_voices] is a uint32 array in device memory that only the calls of this section read or write; 0 means
+ * "nobody".  The first call of this section other than _owner_clear and _download_owners allocates it (4 bytes per voice, plus the
+ * scratch of _release_tags) and zero-fills it; that one call may wait for the device.  skred_fxbank_upload, _update, the renders,
+ * notes, stamps and steals never touch it and sk_fx_render_kernel never reads it: a bank that makes owner calls renders the blocks
+ * of a bank that makes none, bit for bit.  The host's sequence is the float bank's: draw a non-zero tag per note, place the burst
+ * (skred_fxbank_note_on_idle / _note_on_steal), then skred_fxbank_tag_list(d_assigned, tags) on the same stream -- a thief's tags
+ * overwrite its victims'.  Note-off by id: skred_fxbank_release_tags; note-off or "this chord only" on a kept d_assigned:
+ * skred_fxbank_stamp_owned / _ctl_owned with the tags the entries are expected to carry.  Tags are checked with
+ * skred_owner_tags_check (include/skred_amd.h; SKRED_OWNER_MAX_TAGS, SKRED_OWNER_ALLOW_ZERO, SKRED_OWNER_UNIQUE as they are).
+ *
+ * skred_fxbank_tag_list      owner[d_voices[k]] = tags[k] (host uint32[n]; 0 clears) for the first min(n, *d_count_or_null) entries
+ *                            (NULL: n) that lie in [0, n_voices): a d_assigned with its -1 holes is the natural argument.  A voice
+ *                            named twice with different tags ends up with one of them.  d_result (device uint32[2], may be NULL),
+ *                            cleared on the stream ahead of the kernel: [0] voices tagged, [1] entries that are no voice.
+ *                            SKRED_E_BAD_ARG: NULL bank, list or tags, n < 0 or n > INT32_MAX / 64.
+ * skred_fxbank_find_owned    d_voices_out[k] (device int32[n]) = the LOWEST voice of [first, first + count) whose owner equals
+ *                            tags[k], or -1.  1 <= n <= SKRED_OWNER_MAX_TAGS, no zero tag, no tag twice.  An unsigned minimum: the
+ *                            same state gives the same bytes, and no workgroup waits for another.  SKRED_E_BAD_ARG: NULL bank, tags
+ *                            or d_voices_out, what skred_owner_tags_check(SKRED_OWNER_UNIQUE) refuses; SKRED_E_RANGE: count <= 0 or
+ *                            a range outside the bank.
+ * skred_fxbank_stamp_owned   skred_fxbank_stamp_list with the guard owner[voice] == tags[k] (tags non-zero: an untagged voice never
+ *                            matches).  The stores are exactly that call's, `now` the bank's sample count at the call.  d_result
+ *                            (device uint32[3], required), cleared on the stream ahead of the kernel: [0] voices stamped, [1] voices
+ *                            whose owner differs, [2] entries that are no voice.  SKRED_E_BAD_ARG: NULL bank, list, tags or result,
+ *                            n < 0 or n > INT32_MAX / 64, a zero tag, no or unknown stamp bits.
+ * skred_fxbank_release_tags  note-off by id: skred_fxbank_find_owned into scratch the bank owns, then skred_fxbank_stamp_owned on
+ *                            that list with the same tags.  Each tag stamps at most one voice, the lowest that carries it.
+ *                            d_result as there: [2] counts the tags nobody in the range carries, [1] is 0.  One stream at a time
+ *                            per bank.  Refusals of both calls.
+ * skred_fxbank_owner_clear   owner[first .. first + count) = 0 on `stream` (nothing to do on a bank that was never tagged).
+ *                            SKRED_E_RANGE: count < 0 or a range outside the bank.
+ * skred_fxbank_download_owners  the owner words of a range into host_u32; synchronous (waits for the device); zeros on a bank that
+ *                            was never tagged.
+ *
+ * Controllers.  skred_fx_ctl_t is ONE record (this bank has no slots): `which` names the fields it stores with the float bank's
+ * SKRED_CTL_* bits, reserved words are 0.  Each field stores exactly the words named here and nothing else -- the running phase, the
+ * delay line, the smoother's gain, the envelope clock, every flag, the table window and filter_mode keep what the device holds:
+ *   SKRED_CTL_PHASE_INC   phase_inc
+ *   SKRED_CTL_INC_SCALE   phase_inc = ((uint64)phase_inc * inc_scale_q16) >> 16, the product in 64 bits, 65536 = 1.0.  A result
+ *                         above 0xFFFFFFFF is NOT stored (the voice keeps its increment) and is counted in d_result[1].  Together
+ *                         with PHASE_INC the scale applies to the new value; when that product is withheld the new value stays.
+ *   SKRED_CTL_AMP         amp_q15, 1..65535, stored only on voices whose amp_q15 != 0 ON THE DEVICE; the others keep 0 and are
+ *                         counted in d_result[1] (the float bank's rule: one host drives both banks)
+ *   SKRED_CTL_PAN         pan_left_q15, pan_right_q15, each 0..65535
+ *   SKRED_CTL_FILTER      b0_q30 b1_q30 b2_q30 a1_q30 a2_q30 (Q2.30, any int32).  filter_mode and the delay line are untouched, so
+ *                         the choice of the render instantiation stays right; on a voice without a filter the coefficients are
+ *                         stored and inert
+ *   SKRED_CTL_ENV_TIMES   attack_frames, decay_frames, release_frames, their reciprocals floor(2^32 / X) (0 for X == 0) as
+ *                         skred_fxbank_upload makes them, and sustain_q15 (0..32768)
+ *   SKRED_CTL_VELOCITY    velocity_q15, 0..65535
+ *   SKRED_CTL_SMOOTHING   smoother_k_q15, 0..32768
+ * SKRED_CTL_FM_DEPTH .. SKRED_CTL_CZ_DIST are refused: the definition has no modulators.  skred_fx_ctl_check is pure host:
+ * SKRED_E_BAD_ARG for a NULL record, which == 0, unknown or refused bits, a non-zero reserved word, a named value outside its range.
+ * Values a field does not name are not looked at.
+ *
+ * skred_fxbank_ctl_range  the record on every voice of [first, first + count).  d_result (device uint32[2], may be NULL), cleared on
+ *                         the stream ahead of the kernel: [0] voices written, [1] stores withheld by the two guards.  Refused: what
+ *                         skred_fx_ctl_check refuses, a NULL bank; SKRED_E_RANGE: count < 0 or a range outside the bank.
+ * skred_fxbank_ctl_list   the record on the first min(n, *d_count_or_null) entries of a list in device memory that lie in
+ *                         [0, n_voices); -1 holes are skipped.  A voice listed twice gets the absolute stores twice, which is the same
+ *                         as once, and is counted twice; with SKRED_CTL_INC_SCALE its increment is UNSPECIFIED (scaled once or twice).
+ *                         d_result as for _ctl_range.  SKRED_E_BAD_ARG: NULL bank or list, n < 0 or n > INT32_MAX / 64.
+ * skred_fxbank_ctl_owned  skred_fxbank_ctl_list under the guard owner[voice] == tags[k].  d_result (device uint32[3], may be NULL):
+ *                         [0] voices written, [1] stores withheld, [2] voices whose owner differs.  Refused: what _ctl_list refuses,
+ *                         NULL tags, a zero tag.
+ * LIMIT, as for notes: the host view goes stale; mirror the values before a later skred_fxbank_update with SKRED_DIRTY_PARAMS or
+ * SKRED_DIRTY_PAN of such a voice.  skred_fxbank_download_params reads them back where the host cannot know them (a scaled
+ * increment, a withheld amp): every parameter field of the host view that skred_fxbank_download leaves out -- phase_inc,
+ * table_offset, log2_size, amp_q15, the pans, the five flags (as 0 / 1), the envelope's frame counts, sustain_q15, velocity_q15,
+ * smoother_k_q15, sample_start, sample_release, the five coefficients -- as the device holds it; recip_out (may be NULL) receives
+ * the three reciprocals of each voice, uint32[count][3].  Synchronous; windows as skred_fxbank_download. */
+typedef struct skred_fx_ctl {             /* 80 bytes */
+  uint32_t which;                         /* SKRED_CTL_* of the fields below */
+  uint32_t phase_inc, inc_scale_q16;
+  int32_t  amp_q15, pan_left_q15, pan_right_q15;
+  int32_t  b0_q30, b1_q30, b2_q30, a1_q30, a2_q30;
+  uint32_t attack_frames, decay_frames, release_frames;
+  int32_t  sustain_q15, velocity_q15, smoother_k_q15;
+  uint32_t reserved[3];                   /* 0 */
+} skred_fx_ctl_t;
+int  skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                           uint32_t *d_result, void *stream);
+int  skred_fxbank_find_owned(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int32_t *d_voices_out, void *stream);
+int  skred_fxbank_stamp_owned(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                              uint32_t stamps, uint32_t *d_result, void *stream);
+int  skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, uint32_t stamps,
+                               uint32_t *d_result, void *stream);
+int  skred_fxbank_owner_clear(skred_fxbank_t *fx, int first, int count, void *stream);
+int  skred_fxbank_download_owners(skred_fxbank_t *fx, uint32_t *host_u32, int first, int count);
+int  skred_fx_ctl_check(const skred_fx_ctl_t *ctl);
+int  skred_fxbank_ctl_range(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int first, int count, uint32_t *d_result, void *stream);
+int  skred_fxbank_ctl_list(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const int32_t *d_voices, int n, const uint32_t *d_count_or_null,
+                           uint32_t *d_result, void *stream);
+int  skred_fxbank_ctl_owned(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const int32_t *d_voices, const uint32_t *tags, int n,
+                            const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+int  skred_fxbank_download_params(skred_fxbank_t *fx, skred_fxpt_bank_t *host, uint32_t *recip_out, int src_first, int dst_first, int count);
 
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);

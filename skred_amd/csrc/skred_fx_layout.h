@@ -100,4 +100,12 @@ typedef struct {
   int32_t settle_q15;
   int32_t base, from_wg;           /* filled in by the launcher: `first` rounded down to 64; the workgroup that holds `from` */
 } skx_idle_args_t;
+
+/* ---- controllers (skred_fx_ctl_kernels.hip; include/skred_amd_fxpt.h: skred_fxbank_ctl_range / _ctl_list / _ctl_owned) ----
+ * the device's image of skred_fx_ctl_t, word for word; the three reserved words carry the reciprocals of the frame counts */
+enum { SKX_CTL_WHICH = 0, SKX_CTL_PHASE_INC, SKX_CTL_INC_SCALE, SKX_CTL_AMP, SKX_CTL_PAN_LEFT, SKX_CTL_PAN_RIGHT,
+       SKX_CTL_B0, SKX_CTL_B1, SKX_CTL_B2, SKX_CTL_A1, SKX_CTL_A2, SKX_CTL_ATTACK, SKX_CTL_DECAY, SKX_CTL_RELEASE,
+       SKX_CTL_SUSTAIN, SKX_CTL_VELOCITY, SKX_CTL_SMOOTHING, SKX_CTL_RECIP_A, SKX_CTL_RECIP_D, SKX_CTL_RECIP_R, SKX_CTL_WORDS };
+typedef struct { uint32_t w[SKX_CTL_WORDS]; } skx_ctl_t;     /* 80 bytes */
+#define SKX_CTL_SPAN 256           /* voices or entries (and threads) per workgroup of the controller and guarded-stamp kernels */
 #endif

@@ -49,12 +49,13 @@ void skx_live_free(skred_fxbank_t *fx) {
   fx->d_idle = NULL; fx->d_idle_out = NULL; fx->h_idle_out = NULL; fx->d_note_list = NULL;
   fx->idle_wgs = 0; fx->idle_out_cap = 0; fx->note_list_cap = 0;
   skx_steal_free(fx);
+  skx_owner_free(fx);
 }
 
 /* ------------------------------------------------------------------ the staging ring */
 
 /* the next slot, with room for `bytes`, not in flight */
-static int ring_take(skred_fxbank_t *fx, size_t bytes, skx_slot_t **out) {
+int skx_ring_take(skred_fxbank_t *fx, size_t bytes, skx_slot_t **out) {
   skx_slot_t *sl = &fx->ring[fx->ring_head++ % SKX_RING];
   if (!sl->ev) HIP_TRY(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
   if (sl->in_flight) {
@@ -76,13 +77,13 @@ static int ring_take(skred_fxbank_t *fx, size_t bytes, skx_slot_t **out) {
 }
 
 /* the slot's pinned bytes -> its device twin, on `s` */
-static int ring_send(skx_slot_t *sl, size_t bytes, hipStream_t s) {
+int skx_ring_send(skx_slot_t *sl, size_t bytes, hipStream_t s) {
   HIP_TRY(hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, s));
   return SKRED_OK;
 }
 
 /* behind the copy and the kernels that read the twin.  A failure to record leaves nothing to wait for later: wait now. */
-static int ring_guard(skx_slot_t *sl, hipStream_t s) {
+int skx_ring_guard(skx_slot_t *sl, hipStream_t s) {
   if (hipEventRecord(sl->ev, s) != hipSuccess) {
     (void)hipStreamSynchronize(s);
     return fail(SKRED_E_NO_DEVICE, "fx staging: hipEventRecord failed");
@@ -95,12 +96,12 @@ static int ring_guard(skx_slot_t *sl, hipStream_t s) {
 int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, hipStream_t s) {
   const size_t bytes = (size_t)n * sizeof(int32_t);
   skx_slot_t *sl;
-  int rc = ring_take(fx, bytes, &sl);
+  int rc = skx_ring_take(fx, bytes, &sl);
   if (rc) return rc;
   memcpy(sl->h, voices, bytes);
-  if ((rc = ring_send(sl, bytes, s))) return rc;
+  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
   const hipError_t e = (hipError_t)skx_launch_stamp((const int32_t *)sl->d, n, which, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, s);
-  rc = ring_guard(sl, s);
+  rc = skx_ring_guard(sl, s);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx stamp launch -> %s", hipGetErrorString(e));
   return rc;
 }
@@ -139,10 +140,10 @@ int skred_fxbank_update(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, const in
   const size_t bytes = (size_t)n * sizeof(skx_update_t);
   skx_slot_t *sl;
   int rc = hipSetDevice(fx->device) == hipSuccess ? SKRED_OK : fail(SKRED_E_NO_DEVICE, "fx update: hipSetDevice");
-  if (!rc) rc = ring_take(fx, bytes, &sl);
+  if (!rc) rc = skx_ring_take(fx, bytes, &sl);
   if (rc) { free(rec); return rc; }
   memcpy(sl->h, rec, bytes);
-  if ((rc = ring_send(sl, bytes, s))) { free(rec); return rc; }
+  if ((rc = skx_ring_send(sl, bytes, s))) { free(rec); return rc; }
   if (fx->n_filter < (1 << 30)) fx->n_filter += n_filter;   /* as a partial upload grows it: the next block must run the biquad */
   /* a voice named twice is applied in order: one launch per run of distinct voices, found with a per-voice epoch mark */
   const skx_update_t *src = (const skx_update_t *)sl->d;
@@ -160,7 +161,7 @@ int skred_fxbank_update(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, const in
     start = end;
   }
   free(rec);
-  rc = ring_guard(sl, s);                               /* (launches already queued still read the slot) */
+  rc = skx_ring_guard(sl, s);                               /* (launches already queued still read the slot) */
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx update launch -> %s", hipGetErrorString(e));
   return rc;
 }
@@ -275,13 +276,13 @@ int skx_notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, co
                      int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s) {
   const size_t bytes = (size_t)n * sizeof(skred_fx_note_t);
   skx_slot_t *sl;
-  int rc = ring_take(fx, bytes, &sl);
+  int rc = skx_ring_take(fx, bytes, &sl);
   if (rc) return rc;
   memcpy(sl->h, notes, bytes);
-  if ((rc = ring_send(sl, bytes, s))) return rc;
+  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
   const hipError_t e = (hipError_t)skx_launch_notes((const skx_note_t *)sl->d, n, d_voices, d_count, first_entry, fx->n_voices, fx->d_ro,
                                                     fx->d_rw, fx->count, d_assigned, d_result, s);
-  rc = ring_guard(sl, s);
+  rc = skx_ring_guard(sl, s);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx notes launch -> %s", hipGetErrorString(e));
   return rc;
 }

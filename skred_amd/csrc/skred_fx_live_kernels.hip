@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "skred_fx_ctl_common.hpp"  // skx_stamp_store: shared with skred_fx_owner_kernels.hip
 #include "skred_fx_idle_common.hpp" // skx_idle_pred, SKXI_*: shared with skred_fx_steal_kernels.hip
 #include "skred_fx_layout.h"
 #include "skred_kernel_common.hpp"   // sk_arrive_last, sk_gu32
@@ -243,13 +244,7 @@ __global__ __launch_bounds__(256) void sk_fx_stamp_list_kernel(const int32_t *d_
   if (d_count && (uint32_t)i >= d_count[0]) return;
   const int v = d_voices[i];
   if (v < 0 || v >= n_voices) return;
-  uint4 t = *reinterpret_cast<const uint4 *>(&time_plane[v]);
-  uint32_t *flags = &rw0[v].w[3];
-  uint32_t f = *flags;
-  if (stamps & SKXU_STAMP_TRIGGER) { t.x = (uint32_t)now; t.y = (uint32_t)(now >> 32); t.z = 0; t.w = 0; f |= SKXR_ACTIVE; }
-  if ((stamps & SKXU_STAMP_RELEASE) && (f & SKXR_ACTIVE)) { t.z = (uint32_t)now; t.w = (uint32_t)(now >> 32); }
-  *reinterpret_cast<uint4 *>(&time_plane[v]) = t;
-  *flags = f;
+  skx_stamp_store(time_plane, rw0, v, stamps, now);
 }
 
 // more than SKX_NOTE_SPAN notes: d_result is zeroed on `stream` ahead of the launch, the workgroups add their counts onto it

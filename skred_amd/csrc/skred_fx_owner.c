@@ -1,0 +1,233 @@
+/*
+ * skred_fx_owner.c -- note owners of the fixed-point bank: one 32-bit tag per voice on the device, and note-offs that carry the tag
+ * they expect to find (include/skred_amd_fxpt.h: skred_fxbank_tag_list / _find_owned / _stamp_owned / _release_tags / _owner_clear /
+ * _download_owners, and skred_fxbank_download_params).
+ *
+ * The host side, built like skred_fx_live.c: the checks (made before anything touches the device; the tags' own through the float
+ * bank's skred_owner_tags_check), the tags' way through the staging ring, the launches.  The tag and the find pass are the float
+ * bank's kernels, entered through their launchers at slot_voices = 1 without a batch-done word (skred_launch.h: this ring guards a
+ * slot with an event); the guarded stamp is skred_fx_owner_kernels.hip.  Nothing here waits for the device except the two downloads
+ * and the allocation of the array by the first call that needs it.  The bank has no slots: every call is per voice.
+ */
+#include <stdlib.h>
+#include <string.h>
+
+#include "skred_launch.h"
+#include "skred_fxbank_priv.h"
+
+#define fail skred_amd_set_error
+
+_Static_assert(SK_OWNER_MAX_TAGS == SKRED_OWNER_MAX_TAGS, "the find kernel's LDS holds SKRED_OWNER_MAX_TAGS tags");
+
+#define SKX_STAMPS (SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)
+
+/* the float bank's check, as it is (its message names skred_owner_tags_check; `who` made the call) */
+static int tags_check(const uint32_t *tags, int n, uint32_t flags, const char *who) {
+  (void)who;
+  return skred_owner_tags_check(tags, n, flags);
+}
+
+static int list_n_check(int n, const char *who) {
+  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);
+  return SKRED_OK;
+}
+
+static int stamps_check(uint32_t stamps, const char *who) {
+  if (!stamps || (stamps & ~(uint32_t)SKX_STAMPS))
+    return fail(SKRED_E_BAD_ARG, "%s: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", who, stamps);
+  return SKRED_OK;
+}
+
+/* at least one voice, inside the bank */
+static int range_check(const skred_fxbank_t *fx, int first, int count, const char *who) {
+  if (count <= 0 || first < 0 || first >= fx->n_voices || count > fx->n_voices - first)
+    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, first, count, fx->n_voices);
+  return SKRED_OK;
+}
+
+int skx_owner_ensure(skred_fxbank_t *fx) {
+  if (fx->d_owner) return SKRED_OK;
+  uint32_t *p = NULL;
+  const size_t words = (size_t)fx->n_voices + SKRED_OWNER_MAX_TAGS;
+  HIP_TRY(hipMalloc((void **)&p, words * sizeof(uint32_t)));
+  hipError_t e = hipMemset(p, 0, words * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
+  if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "fx owner array -> %s", hipGetErrorString(e)); }
+  fx->d_owner = p;
+  fx->d_owner_found = (int32_t *)(p + fx->n_voices);
+  return SKRED_OK;
+}
+
+void skx_owner_free(skred_fxbank_t *fx) {
+  if (fx->d_owner) (void)hipFree(fx->d_owner);
+  fx->d_owner = NULL;
+  fx->d_owner_found = NULL;
+}
+
+/* what a staged launch ends in: the slot's event behind everything that reads its twin, then the launch's own verdict */
+static int launched(skx_slot_t *sl, hipError_t e, const char *what, hipStream_t s) {
+  const int rc = skx_ring_guard(sl, s);
+  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "%s launch -> %s", what, hipGetErrorString(e));
+  return rc;
+}
+
+int skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                          uint32_t *d_result, void *stream) {
+  if (!fx || !d_voices) return fail(SKRED_E_BAD_ARG, "fx tag_list: no bank or no list");
+  int rc = tags_check(tags, n, SKRED_OWNER_ALLOW_ZERO, "fx tag_list");
+  if (rc) return rc;
+  if ((rc = list_n_check(n, "fx tag_list"))) return rc;
+  if (n == 0) return SKRED_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(fx->device));
+  if ((rc = skx_owner_ensure(fx))) return rc;
+  const size_t bytes = (size_t)n * sizeof(uint32_t);
+  skx_slot_t *sl;
+  if ((rc = skx_ring_take(fx, bytes, &sl))) return rc;
+  memcpy(sl->h, tags, bytes);
+  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
+  const hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, (const uint32_t *)sl->d, n, d_count_or_null, 1, fx->n_voices,
+                                                       d_result, NULL, NULL, 0, s);
+  return launched(sl, e, "fx tag_list", s);
+}
+
+/* Stages sorted | perm (| the tags as given, with_tags) of n checked tags and runs the find pass over a checked range into d_out.
+ * The slot is handed back unguarded: the caller queues what else reads it, then guards it. */
+static int find_launch(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int with_tags, int32_t *d_out, hipStream_t s,
+                       skx_slot_t **slot, hipError_t *err) {
+  const size_t words = (size_t)(with_tags ? 3 : 2) * (size_t)n, bytes = words * sizeof(uint32_t);
+  skx_slot_t *sl;
+  int rc = skx_ring_take(fx, bytes, &sl);
+  if (rc) return rc;
+  uint32_t *sorted = (uint32_t *)sl->h, *perm = sorted + n;
+  (void)sk_owner_pack(tags, n, sorted, perm);
+  if (with_tags) memcpy(perm + n, tags, (size_t)n * sizeof(uint32_t));
+  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
+  const uint32_t *src = (const uint32_t *)sl->d;
+  *err = (hipError_t)sk_launch_owner_find(fx->d_owner, first, count, 1, src, src + n, n, d_out, NULL, NULL, 0, s);
+  *slot = sl;
+  return SKRED_OK;
+}
+
+static int find_check(const skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, const char *who) {
+  const int rc = tags_check(tags, n, SKRED_OWNER_UNIQUE, who);
+  if (rc) return rc;
+  return range_check(fx, first, count, who);
+}
+
+int skred_fxbank_find_owned(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int32_t *d_voices_out, void *stream) {
+  if (!fx || !d_voices_out) return fail(SKRED_E_BAD_ARG, "fx find_owned: no bank or nowhere to put the voices");
+  int rc = find_check(fx, first, count, tags, n, "fx find_owned");
+  if (rc) return rc;
+  if (n == 0) return SKRED_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(fx->device));
+  if ((rc = skx_owner_ensure(fx))) return rc;
+  skx_slot_t *sl;
+  hipError_t e = hipSuccess;
+  if ((rc = find_launch(fx, first, count, tags, n, 0, d_voices_out, s, &sl, &e))) return rc;
+  return launched(sl, e, "fx find_owned", s);
+}
+
+int skred_fxbank_stamp_owned(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                             uint32_t stamps, uint32_t *d_result, void *stream) {
+  if (!fx || !d_voices || !d_result) return fail(SKRED_E_BAD_ARG, "fx stamp_owned: no bank, list or result");
+  int rc = tags_check(tags, n, 0, "fx stamp_owned");
+  if (rc) return rc;
+  if ((rc = list_n_check(n, "fx stamp_owned"))) return rc;
+  if ((rc = stamps_check(stamps, "fx stamp_owned"))) return rc;
+  if (n == 0) return SKRED_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(fx->device));
+  if ((rc = skx_owner_ensure(fx))) return rc;
+  const size_t bytes = (size_t)n * sizeof(uint32_t);
+  skx_slot_t *sl;
+  if ((rc = skx_ring_take(fx, bytes, &sl))) return rc;
+  memcpy(sl->h, tags, bytes);
+  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
+  const hipError_t e = (hipError_t)skx_launch_stamp_owned(fx->d_owner, d_voices, (const uint32_t *)sl->d, n, d_count_or_null, fx->n_voices,
+                                                          stamps, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, d_result, s);
+  return launched(sl, e, "fx stamp_owned", s);
+}
+
+int skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, uint32_t stamps, uint32_t *d_result,
+                              void *stream) {
+  if (!fx || !d_result) return fail(SKRED_E_BAD_ARG, "fx release_tags: no bank or no result");
+  int rc = find_check(fx, first, count, tags, n, "fx release_tags");
+  if (rc) return rc;
+  if ((rc = stamps_check(stamps, "fx release_tags"))) return rc;
+  if (n == 0) return SKRED_OK;
+  hipStream_t s = (hipStream_t)stream;
+  HIP_TRY(hipSetDevice(fx->device));
+  if ((rc = skx_owner_ensure(fx))) return rc;
+  skx_slot_t *sl;
+  hipError_t e = hipSuccess;
+  if ((rc = find_launch(fx, first, count, tags, n, 1, fx->d_owner_found, s, &sl, &e))) return rc;
+  /* entry k is the lowest voice that carries tags[k], or -1: the guard holds on every entry that is a voice */
+  if (e == hipSuccess)
+    e = (hipError_t)skx_launch_stamp_owned(fx->d_owner, fx->d_owner_found, (const uint32_t *)sl->d + 2 * (size_t)n, n, NULL, fx->n_voices,
+                                           stamps, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, d_result, s);
+  return launched(sl, e, "fx release_tags", s);
+}
+
+int skred_fxbank_owner_clear(skred_fxbank_t *fx, int first, int count, void *stream) {
+  if (!fx) return fail(SKRED_E_BAD_ARG, "fx owner_clear: no bank");
+  if (count < 0 || first < 0 || first > fx->n_voices || count > fx->n_voices - first)
+    return fail(SKRED_E_RANGE, "fx owner_clear: range [%d,+%d) outside the bank of %d voices", first, count, fx->n_voices);
+  if (count == 0 || !fx->d_owner) return SKRED_OK;      /* (never tagged: every word is 0 already) */
+  HIP_TRY(hipSetDevice(fx->device));
+  HIP_TRY(hipMemsetAsync(fx->d_owner + first, 0, (size_t)count * sizeof(uint32_t), (hipStream_t)stream));
+  return SKRED_OK;
+}
+
+int skred_fxbank_download_owners(skred_fxbank_t *fx, uint32_t *host_u32, int first, int count) {
+  if (!fx || !host_u32 || count < 0) return fail(SKRED_E_BAD_ARG, "fx download_owners: bad arguments");
+  if (first < 0 || first > fx->n_voices || count > fx->n_voices - first) return fail(SKRED_E_RANGE, "fx download_owners window outside bank");
+  if (count == 0) return SKRED_OK;
+  if (!fx->d_owner) { memset(host_u32, 0, (size_t)count * sizeof(uint32_t)); return SKRED_OK; }
+  HIP_TRY(hipSetDevice(fx->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(host_u32, fx->d_owner + first, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return SKRED_OK;
+}
+
+int skred_fxbank_download_params(skred_fxbank_t *fx, skred_fxpt_bank_t *h, uint32_t *recip_out, int src_first, int dst_first, int count) {
+  if (!fx || !h || count < 0) return fail(SKRED_E_BAD_ARG, "fx download_params: bad arguments");
+  if (src_first < 0 || src_first > fx->n_voices || count > fx->n_voices - src_first || dst_first < 0 || dst_first > h->n_voices ||
+      count > h->n_voices - dst_first)
+    return fail(SKRED_E_RANGE, "fx download_params window outside bank");
+  if (count == 0) return SKRED_OK;
+  HIP_TRY(hipSetDevice(fx->device));
+  skx_plane_t *st = (skx_plane_t *)malloc((size_t)SKX_COUNT * (size_t)count * sizeof(skx_plane_t));
+  if (!st) return fail(SKRED_E_NO_MEM, "fx download_params staging");
+  hipError_t e = hipDeviceSynchronize();
+  for (int p = 0; p < SKX_COUNT && e == hipSuccess; p++)
+    e = hipMemcpy(st + (size_t)p * count, fx->d_ro[p] + src_first, (size_t)count * sizeof(skx_plane_t), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) { free(st); HIP_TRY(e); }
+  for (int i = 0; i < count; i++) {
+    const int v = dst_first + i;
+    const skx_plane_t *osc = &st[(size_t)SKX_OSC * count + i], *gn = &st[(size_t)SKX_GAIN * count + i], *env = &st[(size_t)SKX_ENV * count + i];
+    const skx_plane_t *rc = &st[(size_t)SKX_RECIP * count + i], *tm = &st[(size_t)SKX_TIME * count + i];
+    const skx_plane_t *f = &st[(size_t)SKX_FILT * count + i], *f2 = &st[(size_t)SKX_FILT2 * count + i];
+    const uint32_t flags = osc->w[2] >> 8;
+    h->phase_inc[v] = osc->w[0]; h->table_offset[v] = (int32_t)osc->w[1]; h->log2_size[v] = (int32_t)(osc->w[2] & 0xFFu);
+    h->amp_q15[v] = (int32_t)osc->w[3];
+    h->use_envelope[v] = (flags & SKXF_USE_ENV) != 0; h->smoother_enable[v] = (flags & SKXF_SMOOTH) != 0;
+    h->disconnect[v] = (flags & SKXF_MUTED) != 0;
+    if (h->filter_mode) h->filter_mode[v] = (flags & SKXF_FILTER) != 0;
+    if (h->one_shot) h->one_shot[v] = (flags & SKXF_ONE_SHOT) != 0;
+    h->pan_left_q15[v] = (int32_t)gn->w[0]; h->pan_right_q15[v] = (int32_t)gn->w[1];
+    h->smoother_k_q15[v] = (int32_t)gn->w[2]; h->velocity_q15[v] = (int32_t)gn->w[3];
+    h->attack_frames[v] = env->w[0]; h->decay_frames[v] = env->w[1]; h->release_frames[v] = env->w[2]; h->sustain_q15[v] = (int32_t)env->w[3];
+    h->sample_start[v] = (uint64_t)tm->w[0] | (uint64_t)tm->w[1] << 32;
+    h->sample_release[v] = (uint64_t)tm->w[2] | (uint64_t)tm->w[3] << 32;
+    if (h->b0_q30) h->b0_q30[v] = (int32_t)f->w[0];
+    if (h->b1_q30) h->b1_q30[v] = (int32_t)f->w[1];
+    if (h->b2_q30) h->b2_q30[v] = (int32_t)f->w[2];
+    if (h->a1_q30) h->a1_q30[v] = (int32_t)f->w[3];
+    if (h->a2_q30) h->a2_q30[v] = (int32_t)f2->w[0];
+    if (recip_out) { recip_out[3 * (size_t)i] = rc->w[0]; recip_out[3 * (size_t)i + 1] = rc->w[1]; recip_out[3 * (size_t)i + 2] = rc->w[2]; }
+  }
+  free(st);
+  return SKRED_OK;
+}

@@ -1,5 +1,6 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
- * skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c: voice stealing). */
+ * skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c: voice stealing; skred_fx_owner.c: note owners;
+ * skred_fx_ctl.c: controllers). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -48,6 +49,8 @@ struct skred_fxbank {
                                                             * query's two counts, the joined list's length), then the list */
   uint32_t *d_steal; int steal_wgs;          /* skred_fxbank_find_steal's scratch, laid out as the float bank's (skred_bank_steal.c) */
   int32_t *d_steal_out, *h_steal_out;        /* [2] counts, then SK_STEAL_MAX victims: _find_steal_host's list and _note_on_steal's */
+  uint32_t *d_owner;                         /* note owners (skred_fx_owner.c): one word per voice, 0 nobody; NULL until the first call that needs it */
+  int32_t *d_owner_found;                    /* ... and behind it skred_fxbank_release_tags' list, SKRED_OWNER_MAX_TAGS entries */
   long long *d_mix; size_t mix_cap;
   int32_t *d_stems; size_t stems_cap;
   uint64_t count;
@@ -83,8 +86,22 @@ int skx_note_list_room(skred_fxbank_t *fx, int n);
 int skx_notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
                      int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s);
 
+/* ... the staging ring, for the other host files: the next slot with room for `bytes`, not in flight; the slot's pinned bytes ->
+ * its device twin on `s`; the slot's event behind the copy and the kernels that read the twin */
+int skx_ring_take(skred_fxbank_t *fx, size_t bytes, skx_slot_t **out);
+int skx_ring_send(skx_slot_t *sl, size_t bytes, hipStream_t s);
+int skx_ring_guard(skx_slot_t *sl, hipStream_t s);
+
 /* skred_fx_steal.c */
 void skx_steal_free(skred_fxbank_t *fx);
+
+/* skred_fx_owner.c: the owner array (allocated and zero-filled by the first call that needs it), for the guarded controller too */
+void skx_owner_free(skred_fxbank_t *fx);
+int skx_owner_ensure(skred_fxbank_t *fx);
+/* skred_fx_ctl.c: the checked record as it travels (the reserved words carry the reciprocals).  Pure host */
+void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
+/* skred_bank_owner.c: the find pass's view of n <= SKRED_OWNER_MAX_TAGS tags (sorted ascending as unsigned numbers, and where each stood) */
+int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
 
 /* skred_fx_kernels.hip, skred_fx_live_kernels.hip */
 int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);
@@ -97,5 +114,15 @@ int skx_launch_notes(const skx_note_t *d_notes, int n, const int32_t *d_voices, 
                      uint32_t *d_result, hipStream_t stream);
 int skx_launch_stamp_list(const int32_t *d_voices, int n, const uint32_t *d_count, int n_voices, uint32_t stamps,
                           skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);
+
+
+/* skred_fx_owner_kernels.hip, skred_fx_ctl_kernels.hip */
+int skx_launch_stamp_owned(const uint32_t *owner, const int32_t *d_voices, const uint32_t *d_tags, int n, const uint32_t *d_count,
+                           int n_voices, uint32_t stamps, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, uint32_t *d_result,
+                           hipStream_t stream);
+int skx_launch_ctl_range(const skx_ctl_t *d_rec, int first, int count, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result,
+                         hipStream_t stream);
+int skx_launch_ctl_list(const skx_ctl_t *d_rec, const int32_t *d_voices, const uint32_t *d_tags, const uint32_t *owner, int n,
+                        const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
 
 #endif

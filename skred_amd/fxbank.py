@@ -36,8 +36,11 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_update", "skred_fxbank_find_idle", "skred_fxbank_find_idle_host",
                   "skred_fxbank_notes_on_list", "skred_fxbank_note_on_idle", "skred_fxbank_stamp_list",
                   "skred_fxbank_find_steal", "skred_fxbank_find_steal_host", "skred_fxbank_note_on_steal",
+                  "skred_fxbank_tag_list", "skred_fxbank_find_owned", "skred_fxbank_stamp_owned", "skred_fxbank_release_tags",
+                  "skred_fxbank_owner_clear", "skred_fxbank_download_owners", "skred_fxbank_ctl_range", "skred_fxbank_ctl_list",
+                  "skred_fxbank_ctl_owned", "skred_fxbank_download_params",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
-FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check"]      # pure host: no bank, no device
+FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check"]      # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -47,6 +50,12 @@ NOTE_SET_PHASE, NOTE_SET_PAN = 1, 2
 STEAL_OLDEST, STEAL_QUIETEST = 0, 1               # SKRED_STEAL_*: policy; flags; the longest list
 STEAL_RELEASED_FIRST, STEAL_RELEASED_ONLY, STEAL_UNNAMED = 1, 2, 256
 STEAL_MAX = 1024
+# note owners and controllers: SKRED_OWNER_* and the SKRED_CTL_* bits this path has (FM_DEPTH .. CZ_DIST, 1 << 8 .. 1 << 13, are refused)
+OWNER_MAX_TAGS, OWNER_ALLOW_ZERO, OWNER_UNIQUE = 1024, 1, 2
+CTL_PHASE_INC, CTL_INC_SCALE, CTL_AMP, CTL_PAN, CTL_FILTER, CTL_ENV_TIMES, CTL_VELOCITY, CTL_SMOOTHING = 1, 2, 4, 8, 16, 32, 64, 128
+CTL_ALL = 255
+CTL_REFUSED = 0x3F00
+FX_CTL_SPAN = 256                                 # voices or entries per workgroup of the controller and guarded-stamp kernels
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
 MASTER_TARGET_Q31 = int(0.025 * 2147483648.0)     # the library's default: volume_user 1 x AMY_FACTOR
@@ -76,6 +85,33 @@ def fx_steal_query(first, count, policy=STEAL_OLDEST, flags=0, min_age=0, exclud
 def fx_steal_check(q: "FxStealQueryC", n_voices: int) -> int:
     """skred_fx_steal_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host, no device."""
     return int(_bind(load()).skred_fx_steal_check(C.byref(q) if q is not None else None, int(n_voices)))
+
+
+class FxCtlC(C.Structure):
+    """ctypes image of ``skred_fx_ctl_t`` (80 bytes)."""
+    _fields_ = [("which", C.c_uint32), ("phase_inc", C.c_uint32), ("inc_scale_q16", C.c_uint32), ("amp_q15", C.c_int32),
+                ("pan_left_q15", C.c_int32), ("pan_right_q15", C.c_int32), ("b0_q30", C.c_int32), ("b1_q30", C.c_int32),
+                ("b2_q30", C.c_int32), ("a1_q30", C.c_int32), ("a2_q30", C.c_int32), ("attack_frames", C.c_uint32),
+                ("decay_frames", C.c_uint32), ("release_frames", C.c_uint32), ("sustain_q15", C.c_int32), ("velocity_q15", C.c_int32),
+                ("smoother_k_q15", C.c_int32), ("reserved", C.c_uint32 * 3)]
+
+
+def fx_ctl(which: int, **values) -> FxCtlC:
+    """One controller record: ``which`` (CTL_*) and the named fields; everything else 0."""
+    c = FxCtlC()
+    c.which = int(which)
+    for k, v in values.items():
+        setattr(c, k, int(v))
+    return c
+
+
+def fx_ctl_check(ctl: Optional[FxCtlC]) -> int:
+    """skred_fx_ctl_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device."""
+    return int(_bind(load()).skred_fx_ctl_check(C.byref(ctl) if ctl is not None else None))
+
+
+def _tags(tags) -> np.ndarray:
+    return np.ascontiguousarray(tags, np.uint32)
 
 
 class FxNoteC(C.Structure):
@@ -176,6 +212,17 @@ def _bind(L):
     L.skred_fxbank_find_steal.argtypes = [vp, vp, vp, vp, vp]
     L.skred_fxbank_find_steal_host.argtypes = [vp, vp, vp, C.POINTER(C.c_int), vp]
     L.skred_fxbank_note_on_steal.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_tag_list.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_find_owned.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    L.skred_fxbank_stamp_owned.argtypes = [vp, vp, vp, i32, vp, C.c_uint32, vp, vp]
+    L.skred_fxbank_release_tags.argtypes = [vp, i32, i32, vp, i32, C.c_uint32, vp, vp]
+    L.skred_fxbank_owner_clear.argtypes = [vp, i32, i32, vp]
+    L.skred_fxbank_download_owners.argtypes = [vp, vp, i32, i32]
+    L.skred_fx_ctl_check.argtypes = [vp]
+    L.skred_fxbank_ctl_range.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.skred_fxbank_ctl_list.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_ctl_owned.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_download_params.argtypes = [vp, C.POINTER(FxBankC), vp, i32, i32, i32]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -339,6 +386,66 @@ class DeviceFxBank:
         arr = fx_note_array(notes)
         _check(self.L.skred_fxbank_note_on_steal(self.h, C.byref(idle_q), C.byref(steal_q), C.cast(arr, C.c_void_p), len(arr),
                                                  d_assigned or None, d_result or None, stream or None), "skred_fxbank_note_on_steal")
+
+    # ---- note owners (include/skred_amd_fxpt.h): one uint32 tag per voice on the device, 0 nobody ----
+    def tag_list(self, d_voices: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """owner[d_voices[k]] = tags[k] for the first min(len(tags), d_count[0]) entries that are voices; d_result[0..1] = tagged,
+        entries that are no voice (uint32, may be 0)."""
+        t = _tags(tags)
+        _check(self.L.skred_fxbank_tag_list(self.h, d_voices or None, t.ctypes.data, len(t), d_count or None, d_result or None,
+                                            stream or None), "skred_fxbank_tag_list")
+
+    def find_owned(self, first: int, count: int, tags, d_voices_out: int, stream: int = 0):
+        """d_voices_out[k] (int32) = the lowest voice of the range whose owner is tags[k], or -1."""
+        t = _tags(tags)
+        _check(self.L.skred_fxbank_find_owned(self.h, int(first), int(count), t.ctypes.data, len(t), d_voices_out or None,
+                                              stream or None), "skred_fxbank_find_owned")
+
+    def stamp_owned(self, d_voices: int, tags, stamps: int, d_result: int, d_count: int = 0, stream: int = 0):
+        """stamp_list under the guard owner[voice] == tags[k]; d_result[0..2] = stamped, owner differs, no voice (uint32)."""
+        t = _tags(tags)
+        _check(self.L.skred_fxbank_stamp_owned(self.h, d_voices or None, t.ctypes.data, len(t), d_count or None, int(stamps),
+                                               d_result or None, stream or None), "skred_fxbank_stamp_owned")
+
+    def release_tags(self, first: int, count: int, tags, stamps: int, d_result: int, stream: int = 0):
+        """Note-off by id: each tag stamps the lowest voice of the range that carries it; d_result as stamp_owned's, [1] is 0."""
+        t = _tags(tags)
+        _check(self.L.skred_fxbank_release_tags(self.h, int(first), int(count), t.ctypes.data, len(t), int(stamps), d_result or None,
+                                                stream or None), "skred_fxbank_release_tags")
+
+    def owner_clear(self, first: int, count: int, stream: int = 0):
+        _check(self.L.skred_fxbank_owner_clear(self.h, int(first), int(count), stream or None), "skred_fxbank_owner_clear")
+
+    def download_owners(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        count = self.n - first if count is None else count
+        out = np.full(max(count, 0), 0xABABABAB, np.uint32)
+        _check(self.L.skred_fxbank_download_owners(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_owners")
+        return out
+
+    # ---- controllers: a few parameter words of resident voices, stored by a kernel ----
+    def ctl_range(self, ctl: FxCtlC, first: int, count: int, d_result: int = 0, stream: int = 0):
+        """The record on every voice of [first, first + count); d_result[0..1] = voices written, stores withheld (uint32, may be 0)."""
+        _check(self.L.skred_fxbank_ctl_range(self.h, C.byref(ctl), int(first), int(count), d_result or None, stream or None),
+               "skred_fxbank_ctl_range")
+
+    def ctl_list(self, ctl: FxCtlC, d_voices: int, n: int, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """The record on the first min(n, d_count[0]) entries of a device list that are voices of the bank."""
+        _check(self.L.skred_fxbank_ctl_list(self.h, C.byref(ctl), d_voices or None, int(n), d_count or None, d_result or None,
+                                            stream or None), "skred_fxbank_ctl_list")
+
+    def ctl_owned(self, ctl: FxCtlC, d_voices: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """ctl_list under the guard owner[voice] == tags[k]; d_result[0..2] = written, withheld, owner differs."""
+        t = _tags(tags)
+        _check(self.L.skred_fxbank_ctl_owned(self.h, C.byref(ctl), d_voices or None, t.ctypes.data, len(t), d_count or None,
+                                             d_result or None, stream or None), "skred_fxbank_ctl_owned")
+
+    def download_params(self, bank: FxVoiceBank) -> np.ndarray:
+        """Every parameter field skred_fxbank_download leaves out, as the device holds it, into `bank` (the flags as 0 / 1);
+        returns the reciprocals of the three frame counts, uint32 [n][3]."""
+        cb = bank.as_c()
+        recip = np.zeros((bank.n, 3), np.uint32)
+        _check(self.L.skred_fxbank_download_params(self.h, C.byref(cb), recip.ctypes.data, 0, 0, bank.n), "skred_fxbank_download_params")
+        return recip
 
 
 # ------------------------------------------------------------------ synthetic fixed-point bank

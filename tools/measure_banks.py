@@ -32,6 +32,8 @@
              (medians of 12): (a) skred_fxbank_note_on_idle between an event pair -- stream time, and the time the call held the host;
              (b) the only route without it: skred_fxbank_download of the bank, picking on the CPU, skred_fxbank_upload of those voices,
              skred_fxbank_stamp -- host-held time and the stream time of upload + stamp; beside one 512-frame block of the bank
+  fxowners   note-off by tag on the FIXED-POINT bank (release_tags) beside the read-back-and-map route; fxctl: a bank-wide cutoff
+             change through ctl_range beside host-view writes + skred_fxbank_update, and ctl_list on 256 entries
   fxsteal    voice stealing on the FIXED-POINT bank: 2^20 voices of fxbank.bank_fx whose polyphony is used up but for 64 idle voices,
              a burst of 256 notes (medians of 12 with minimum and maximum): (a) skred_fxbank_note_on_steal between an event pair --
              stream time, and the time the call held the host; nothing is waited for; (b) the only route without it:
@@ -1062,8 +1064,116 @@ def owners():
     db.close()
 
 
+def _fx_timed(call, before=None, runs=12, warm=3):
+    """(stream ms between events, host ms held) of `call`, `runs` times after `warm`; `before` runs untimed ahead of each"""
+    ms, held = [], []
+    for it in range(warm + runs):
+        if before:
+            before()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        dt = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        if it >= warm:
+            ms.append(e0.elapsed_time(e1))
+            held.append(dt * 1e3)
+    return ms, held
+
+
+def _fx_stats(x):
+    return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f}) of {len(x)}"
+
+
+def _fx_block_after(db, out, F, call=None, runs=12):
+    t = []
+    for _ in range(runs):
+        if call:
+            call()
+        db.render_mix(F, out.data_ptr(), 1)
+        torch.cuda.synchronize()
+        t.append(db.last_render_ms())
+    return t
+
+
+def fxowners():
+    from skred_amd import fxbank as X
+    n, F, K = 1 << 20, 64, 256
+    bank, pool, c0 = X.bank_fx(n)                                         # every voice sounding: a burst can only steal
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    notes = X.fx_note_array([X.FxNoteC(3000017 + 40009 * k, 26000, 0, 16384, 16384, X.NOTE_SET_PHASE) for k in range(K)])
+    da = torch.full((K,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+    iq = X.FxIdleQueryC(0, n, X.IDLE_FINISHED | X.IDLE_ENV_DONE, 0, 0, 0)
+    sq = X.fx_steal_query(0, n, X.STEAL_OLDEST, 0, 64)
+    burst = [0]
+
+    def tags():
+        return (1 + burst[0] * K + np.arange(K)).astype(np.uint32)
+
+    def steal_and_tag():                                                  # 256 stolen notes tagged from their own d_assigned, two blocks
+        burst[0] += 1
+        db.note_on_steal(notes, iq, sq, da.data_ptr(), dr.data_ptr())
+        db.tag_list(da.data_ptr(), tags())
+        for _ in range(2):
+            db.render_mix(F, out.data_ptr(), 1)
+
+    def by_tag():
+        db.release_tags(0, n, tags(), X.STAMP_RELEASE, dr.data_ptr())
+
+    def by_host_map():                                                    # the parent's only correct route
+        held = da.cpu().numpy()                                           # d_assigned read back behind a stream wait
+        key_to_voice = {int(t): int(v) for t, v in zip(tags(), held)}     # the map a host would keep
+        db.stamp(np.array([key_to_voice[int(t)] for t in tags()], np.int32), X.FX_STAMP_RELEASE)
+
+    steady = _fx_block_after(db, out, F)
+    print(f"fx {n} voices all sounding, bursts of {K} stolen notes tagged from their own d_assigned, two {F}-frame blocks, then the note-off")
+    for label, call in (("(a) release_tags", by_tag), ("(b) d_assigned read back + a map in Python + skred_fxbank_stamp", by_host_map)):
+        ms, held = _fx_timed(call, steal_and_tag)
+        after = _fx_block_after(db, out, F, lambda: (steal_and_tag(), call()))
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {dr.cpu().numpy().tolist()}")
+        print(f"      the {F}-frame block after it: {_fx_stats(after)}; a steady block: {_fx_stats(steady)}")
+    db.close()
+
+
+def fxctl():
+    from skred_amd import fxbank as X
+    n, F, K = 1 << 20, 64, 256
+    bank, pool, c0 = X.bank_fx(n)                                         # every voice filtered
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    co = X.q30_coeffs(np.array([1]), np.array([1200.0], np.float32), np.array([1.5], np.float32), 48000)
+    c = X.fx_ctl(X.CTL_FILTER, **{k: int(v[0]) for k, v in co.items()})
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+    lst = torch.tensor(((np.arange(K, dtype=np.int64) * 4093 + 7) % n).astype(np.int32), dtype=torch.int32, device="cuda")
+    everyone = np.arange(n, dtype=np.int32)
+    h = bank.copy()
+
+    def by_update():                                                      # the parent's only route: host-view writes + update of those voices
+        for k, v in co.items():
+            h[k][...] = v[0]
+        db.update(h, everyone, X.DIRTY_PARAMS)
+
+    steady = _fx_block_after(db, out, F)
+    print(f"fx {n} voices, all filtered: a cutoff change on every voice")
+    for label, call, runs in (("(a) ctl_range", lambda: db.ctl_range(c, 0, n, dr.data_ptr()), 12),
+                              ("(b) host-view writes + skred_fxbank_update of every voice", by_update, 3),
+                              (f"(c) ctl_list on a {K}-entry list", lambda: db.ctl_list(c, lst.data_ptr(), K, 0, dr.data_ptr()), 12)):
+        ms, held = _fx_timed(call, None, runs, 1 if runs == 3 else 3)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {dr.cpu().numpy().tolist()[:2]}")
+    after = _fx_block_after(db, out, F, lambda: db.ctl_range(c, 0, n, dr.data_ptr()))
+    print(f"  (d) the {F}-frame block after ctl_range: {_fx_stats(after)}; a steady block: {_fx_stats(steady)}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
