@@ -898,6 +898,99 @@ int  skred_bank_download_owners(skred_bank_t *bank, uint32_t *host_u32, int firs
  * stores: sample_start and sample_release (either may be NULL).  Waits for the device, like skred_bank_download. */
 int  skred_bank_download_env_clocks(skred_bank_t *bank, uint64_t *sample_start, uint64_t *sample_release, int first, int count);
 
+/* ---- channels and per-note expression: masked owner matches, per-entry controller values -----------------------------------
+ *
+ * The owner word is 32 bits the host draws freely, so a part of it can name a CHANNEL: tag = channel << 24 | note id.  Parts that
+ * share one stolen-from range then still have "all notes off on channel 3", "mod wheel on channel 3" and "how many notes does
+ * channel 3 hold" -- without a list of every live tag on the host, which stealing would make wrong.  And a host that plays MPE,
+ * polyphonic aftertouch or per-note bend gives n sounding notes n DIFFERENT values in one call instead of n calls.
+ *
+ * A slot, K = slot_voices and voice_mask mean what they mean for skred_bank_notes_on_slots; the owner array is the one of the
+ * section above, allocated by the first call that needs it exactly as there.  All device calls are asynchronous on `stream` and
+ * ordered like skred_bank_update; host arrays travel through its staging ring, so the caller's memory is free on return and nothing
+ * waits for the device (skred_bank_find_match_host waits for its stream, and says so).  Results are pure functions of the state:
+ * the same state gives the same bytes whatever order the workgroups arrive in.  One stream at a time per bank, as for the queries.
+ * No render kernel, probe, tap or report reads anything these calls add; what the writing calls tell the planner is what their
+ * unguarded twins tell it (below).
+ * Out of scope: the fixed-point bank, the drop-in mode, deferred items and pattern steps (they carry no tags), per-entry filter
+ * coefficients.  On a shard: through skred_shard_bank(), with that rank's local indices, and nothing beyond that.
+ *
+ * A. Masked owner matches.  A slot MATCHES m when owner != 0 && (owner & m->mask) == m->value: mask 0 with value 0 is every tagged
+ * slot, mask 0xFF000000 a channel byte, mask 0xFFFFFFFF one note.  An untagged slot matches nothing. */
+typedef struct { uint32_t value, mask; } skred_owner_match_t;
+/* Pure host: SKRED_OK, or SKRED_E_BAD_ARG for NULL and for value & ~mask != 0 (a value no owner word can give). */
+int  skred_owner_match_check(const skred_owner_match_t *m);
+/* The first voices of the matching slots of [first, first + count), ascending, into d_slots[0 .. min(total, max_out)) (device,
+ * int32); d_count[0] (device, uint32[1]) = the TOTAL number of matching slots, whether or not the list was cut short -- the count
+ * word a later skred_bank_ctl_slots / _stamp_slots with n = max_out takes as it is.  max_out == 0: the count alone (d_slots may
+ * be NULL).  Entries past min(total, max_out) are not written.  The compaction is the idle queries' (ordered by index, no
+ * workgroup waits for another) and uses the same scratch.
+ * SKRED_E_BAD_ARG: NULL bank, match or d_count, what skred_owner_match_check refuses, max_out < 0, NULL d_slots with max_out > 0;
+ * SKRED_E_RANGE: a bad K, first or count not a multiple of K, count <= 0, a range outside the bank. */
+int  skred_bank_find_match(skred_bank_t *bank, int first, int count, int slot_voices, const skred_owner_match_t *m, int max_out,
+                           int32_t *d_slots, uint32_t *d_count, void *stream);
+/* The same into host memory, waiting for `stream` ONLY (as skred_bank_find_idle_slots_host): returns the number of slots written
+ * to slots[0 .. max_out) or a negative error; *total_out (may be NULL) = the total. */
+int  skred_bank_find_match_host(skred_bank_t *bank, int first, int count, int slot_voices, const skred_owner_match_t *m, int max_out,
+                                int32_t *slots, int *total_out, void *stream);
+/* skred_bank_stamp_slots' stores on the voice_mask voices of EVERY matching slot of the range -- all notes off on a channel -- in one
+ * pass over the range, with no list in between.  d_result (device, uint32[2], required) is cleared on the stream ahead of the
+ * kernel: [0] slots stamped, [1] slots of the range that did not match.  The planner is told what skred_bank_stamp_slots on every
+ * slot of the range would tell it: (count / K) * popcount(voice_mask) more voices may be on the motion list (the host cannot know
+ * how many slots match; the bound only has to hold).
+ * Refusals of skred_bank_find_match about bank, match and range; SKRED_E_BAD_ARG for a NULL d_result, bad stamp bits, a bad
+ * voice_mask. */
+int  skred_bank_stamp_match(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t voice_mask, const skred_owner_match_t *m,
+                            uint32_t stamps, uint32_t *d_result, void *stream);
+/* skred_bank_ctl_range under the match guard: the same stores, the same two withheld-store rules, the same rule for which words put
+ * a voice on the motion list -- on the matching slots only.  d_result (device, uint32[3], may be NULL): [0] voices written,
+ * [1] stores withheld, [2] slots of the range that did not match.  The motion-list bound grows as for skred_bank_ctl_range on the
+ * same range, and only when a record names AMP, ENV_TIMES, VELOCITY or SMOOTHING: a filter or pan sweep of a channel leaves the
+ * planner's reports alone, and the block behind it stays the steady block.
+ * Refused: what skred_ctl_check and skred_owner_match_check refuse, a NULL bank; SKRED_E_RANGE as for skred_bank_find_match. */
+int  skred_bank_ctl_match(skred_bank_t *bank, const skred_ctl_t *ctl, int first, int count, int slot_voices, uint64_t voice_mask,
+                          const skred_owner_match_t *m, uint32_t *d_result, void *stream);
+
+/* B. Per-entry controller values.  skred_bank_ctl_owned stores ONE set of K records on all n listed notes; here entry k of the list
+ * brings a small record of its own, whose named values replace or scale the records' for that entry alone:
+ *   SKRED_EACH_INC_SCALE  voice_phase_inc = voice_phase_inc * inc_scale on every masked voice of the slot: the device's value, ONE
+ *                         fp32 multiply, never fused; a product that is not finite is withheld and counted (SKRED_CTL_INC_SCALE's
+ *                         rule).  Per-note pitch bend.
+ *   SKRED_EACH_AMP_SCALE  needs record l of `ctl` to name SKRED_CTL_AMP: the amp stored on voice l is ctl[l].amp * amp_scale, ONE
+ *                         fp32 multiply, never fused, under SKRED_CTL_AMP's device-side guard (a voice with amp 0 keeps it).  A
+ *                         product that is zero or not finite is withheld and counted, and the voice's amp is left alone.
+ *                         Polyphonic aftertouch on a patch whose voices differ in level.
+ *   SKRED_EACH_VELOCITY   the entry's velocity replaces record l's, or supplies it where the record does not name the field.
+ *   SKRED_EACH_PAN        the same for the pan pair.
+ * Everything else a record names is stored as skred_bank_ctl_owned stores it.  `ctl` may be NULL: no base records, the entries
+ * supply everything (AMP_SCALE is then refused). */
+enum { SKRED_EACH_INC_SCALE = 1u << 0, SKRED_EACH_AMP_SCALE = 1u << 1, SKRED_EACH_VELOCITY = 1u << 2, SKRED_EACH_PAN = 1u << 3 };
+typedef struct skred_ctl_each { uint32_t set; float inc_scale, amp_scale, velocity, pan_left, pan_right;
+                                uint32_t reserved[2]; } skred_ctl_each_t;   /* 32 bytes */
+/* Pure host: SKRED_OK, or what the two entry points refuse about the entries.  SKRED_E_RANGE: a bad K.  SKRED_E_BAD_ARG: NULL each,
+ * n < 0, a bad voice_mask; with ctl != NULL what skred_ctl_check refuses; in an entry: unknown bits in set, set == 0, a reserved word
+ * that is not 0, a named value that is not finite, amp_scale == 0 under AMP_SCALE; AMP_SCALE where ctl is NULL or a masked record
+ * lacks SKRED_CTL_AMP; INC_SCALE where a masked record names SKRED_CTL_PHASE_INC or SKRED_CTL_INC_SCALE.  Values an entry does not
+ * name are not looked at (and never shipped). */
+int  skred_ctl_each_check(const skred_ctl_each_t *each, int n, const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask);
+/* Entry k (of the first min(n, *d_count_or_null)) acts on d_slots[k] only if that is a slot of the bank AND owner[slot] == tags[k]
+ * (non-zero); on that slot it performs skred_bank_ctl_owned's stores with each[k]'s replacements.  d_result (device, uint32[3], may
+ * be NULL): [0] voices written, [1] stores withheld (the two guards and the products above), [2] slots whose owner differs.  A slot
+ * named twice behaves as skred_bank_ctl_slots documents: absolute stores twice, a scaled increment UNSPECIFIED.  When an entry or a
+ * record names a listing word (AMP_SCALE, VELOCITY; AMP, ENV_TIMES, VELOCITY, SMOOTHING) the motion-list bound grows by
+ * n * popcount(voice_mask); otherwise the planner's reports are left alone.
+ * Refused: what skred_ctl_each_check refuses, NULL bank, list or tags, a zero tag, n > INT32_MAX / 64.  n == 0: SKRED_OK. */
+int  skred_bank_ctl_owned_each(skred_bank_t *bank, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int slot_voices,
+                               uint64_t voice_mask, const int32_t *d_slots, const uint32_t *tags, int n,
+                               const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+/* Expression by note id: skred_bank_find_owned of the tags over [first, first + count) into scratch the bank owns, then the call
+ * above on that list -- built as skred_bank_release_tags is.  each[k] goes with tags[k]: the tags travel sorted, and the entries
+ * are permuted with them on the host.  Tags unique, none zero, n <= SKRED_OWNER_MAX_TAGS; each tag reaches at most ONE slot, the
+ * lowest that carries it.  d_result as above; [2] is 0 (a tag nobody carries is a -1 entry and is not counted).
+ * Refusals of both calls. */
+int  skred_bank_ctl_tags_each(skred_bank_t *bank, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int first, int count,
+                              int slot_voices, uint64_t voice_mask, const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

@@ -65,13 +65,13 @@ static int tags_check(const uint32_t *tags, int n, uint32_t flags, const char *w
 
 int skred_owner_tags_check(const uint32_t *tags, int n, uint32_t flags) { return tags_check(tags, n, flags, "owner_tags_check"); }
 
-static int owner_k_check(int slot_voices, const char *who) {
+int sk_owner_k_check(int slot_voices, const char *who) {
   if (slot_voices < 1 || slot_voices > 64 || (slot_voices & (slot_voices - 1)))
     return fail(SKRED_E_RANGE, "%s: slot_voices = %d (a power of two, 1 .. 64)", who, slot_voices);
   return SKRED_OK;
 }
 
-static int owner_mask_check(int slot_voices, uint64_t mask, const char *who) {
+int sk_owner_mask_check(int slot_voices, uint64_t mask, const char *who) {
   if (!mask) return fail(SKRED_E_BAD_ARG, "%s: voice_mask is 0", who);
   if (slot_voices < 64 && (mask >> slot_voices))
     return fail(SKRED_E_BAD_ARG, "%s: voice_mask = 0x%llx has bits at or above slot_voices = %d", who, (unsigned long long)mask, slot_voices);
@@ -85,7 +85,7 @@ static int owner_stamps_check(uint32_t stamps, const char *who) {
 }
 
 /* a range of whole slots inside the bank, at least one */
-static int owner_range_check(const skred_bank_t *b, int first, int count, int K, const char *who) {
+int sk_owner_range_check(const skred_bank_t *b, int first, int count, int K, const char *who) {
   if (count <= 0 || first < 0 || first >= b->n_voices || count > b->n_voices - first)
     return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, first, count, b->n_voices);
   if ((first & (K - 1)) || (count & (K - 1)))
@@ -93,17 +93,19 @@ static int owner_range_check(const skred_bank_t *b, int first, int count, int K,
   return SKRED_OK;
 }
 
-/* the array and the scratch of skred_bank_release_tags, allocated and zeroed by the first call that needs them */
-static int owner_ensure(skred_bank_t *b) {
+/* the array, the scratch of skred_bank_release_tags and the two words of skred_bank_find_match (skred_bank_expr.c), allocated and
+ * zeroed by the first call that needs them */
+int sk_owner_ensure(skred_bank_t *b) {
   if (b->d_owner) return SKRED_OK;
   uint32_t *p = NULL;
-  const size_t words = (size_t)b->n_voices + SKRED_OWNER_MAX_TAGS;
+  const size_t words = (size_t)b->n_voices + SKRED_OWNER_MAX_TAGS + 2;
   HIP_TRY(hipMalloc((void **)&p, words * sizeof(uint32_t)));
   hipError_t e = hipMemset(p, 0, words * sizeof(uint32_t));
   if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
   if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "owner array -> %s", hipGetErrorString(e)); }
   b->d_owner = p;
   b->d_owner_slots = (int32_t *)(p + b->n_voices);
+  b->d_match_pair = p + b->n_voices + SKRED_OWNER_MAX_TAGS;
   return SKRED_OK;
 }
 
@@ -111,11 +113,12 @@ void sk_owner_free(skred_bank_t *b) {
   if (b->d_owner) (void)hipFree(b->d_owner);
   b->d_owner = NULL;
   b->d_owner_slots = NULL;
+  b->d_match_pair = NULL;
 }
 
 /* where the kernel reads a staged batch from: the pinned buffer itself (sk_stage), or -- `wide`: many workgroups read every byte --
  * the slot's device twin behind a copy */
-static const void *owner_staged(sk_upd_slot_t *sl, size_t bytes, int wide, hipStream_t s) {
+const void *sk_owner_staged(sk_upd_slot_t *sl, size_t bytes, int wide, hipStream_t s) {
   if (!wide) return sk_stage(sl, bytes, s);
   const hipError_t e = hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) { (void)fail(SKRED_E_NO_DEVICE, "owner copy -> %s", hipGetErrorString(e)); return NULL; }
@@ -128,7 +131,7 @@ static const void *owner_staged(sk_upd_slot_t *sl, size_t bytes, int wide, hipSt
   if (++(b)->upd_seq == 0) (b)->upd_seq = 1
 #define OWNER_CNT(b, idx) (b)->d_upd_cnt + (idx), (uint32_t *)(b)->h_upd_done + (idx), (b)->upd_seq
 
-static int owner_launched(skred_bank_t *b, sk_upd_slot_t *sl, hipError_t e, const char *what, hipStream_t s) {
+int sk_owner_launched(skred_bank_t *b, sk_upd_slot_t *sl, hipError_t e, const char *what, hipStream_t s) {
   if (e != hipSuccess) {
     (void)hipStreamSynchronize(s);                      /* (a copy into the slot's device twin may be queued: it reads the slot) */
     return fail(SKRED_E_NO_DEVICE, "%s launch -> %s", what, hipGetErrorString(e));
@@ -143,22 +146,22 @@ int skred_bank_tag_slots(skred_bank_t *b, const int32_t *d_slots, const uint32_t
   int rc = tags_check(tags, n, SKRED_OWNER_ALLOW_ZERO, "tag_slots");
   if (rc) return rc;
   if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "tag_slots: n = %d", n);
-  if ((rc = owner_k_check(slot_voices, "tag_slots"))) return rc;
+  if ((rc = sk_owner_k_check(slot_voices, "tag_slots"))) return rc;
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = owner_ensure(b))) return rc;
+  if ((rc = sk_owner_ensure(b))) return rc;
   const size_t bytes = (size_t)n * sizeof(uint32_t);
   sk_upd_slot_t *sl;
   if ((rc = sk_staging_slot(b, bytes, s, &sl))) return rc;
   void *h = sl->h;
   memcpy(h, tags, bytes);
-  const uint32_t *src = (const uint32_t *)owner_staged(sl, bytes, 0, s);
+  const uint32_t *src = (const uint32_t *)sk_owner_staged(sl, bytes, 0, s);
   if (!src) return SKRED_E_NO_DEVICE;
   OWNER_BATCH(b, sl, idx);
   const hipError_t e = (hipError_t)sk_launch_owner_tag(b->d_owner, d_slots, src, n, d_count_or_null, slot_voices, b->n_voices, d_result,
                                                        OWNER_CNT(b, idx), s);
-  return owner_launched(b, sl, e, "tag_slots", s);
+  return sk_owner_launched(b, sl, e, "tag_slots", s);
 }
 
 /* the find pass of n checked tags over a checked range into d_out (on the device) */
@@ -172,18 +175,18 @@ static int find_launch(skred_bank_t *b, int first, int count, int slot_voices, c
   void *h = sl->h;
   uint32_t *sorted = (uint32_t *)h, *perm = sorted + n;
   (void)sk_owner_pack(tags, n, sorted, perm);
-  const uint32_t *src = (const uint32_t *)owner_staged(sl, bytes, wide, s);
+  const uint32_t *src = (const uint32_t *)sk_owner_staged(sl, bytes, wide, s);
   if (!src) return SKRED_E_NO_DEVICE;
   OWNER_BATCH(b, sl, idx);
   const hipError_t e = (hipError_t)sk_launch_owner_find(b->d_owner, first, count, slot_voices, src, src + n, n, d_out, OWNER_CNT(b, idx), s);
-  return owner_launched(b, sl, e, "find_owned", s);
+  return sk_owner_launched(b, sl, e, "find_owned", s);
 }
 
 static int find_check(const skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, const char *who) {
   int rc = tags_check(tags, n, SKRED_OWNER_UNIQUE, who);
   if (rc) return rc;
-  if ((rc = owner_k_check(slot_voices, who))) return rc;
-  return owner_range_check(b, first, count, slot_voices, who);
+  if ((rc = sk_owner_k_check(slot_voices, who))) return rc;
+  return sk_owner_range_check(b, first, count, slot_voices, who);
 }
 
 int skred_bank_find_owned(skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, int32_t *d_slots_out,
@@ -193,7 +196,7 @@ int skred_bank_find_owned(skred_bank_t *b, int first, int count, int slot_voices
   if (rc) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = owner_ensure(b))) return rc;
+  if ((rc = sk_owner_ensure(b))) return rc;
   return find_launch(b, first, count, slot_voices, tags, n, d_slots_out, (hipStream_t)stream);
 }
 
@@ -206,13 +209,13 @@ static int stamp_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t 
   if (rc) return rc;
   void *h = sl->h;
   memcpy(h, tags, bytes);
-  const uint32_t *src = (const uint32_t *)owner_staged(sl, bytes, 0, s);
+  const uint32_t *src = (const uint32_t *)sk_owner_staged(sl, bytes, 0, s);
   if (!src) return SKRED_E_NO_DEVICE;
   OWNER_BATCH(b, sl, idx);
   const hipError_t e = (hipError_t)sk_launch_owner_stamps(b->d_owner, d_slots, src, n, d_count, slot_voices, voice_mask, b->n_voices, stamps,
                                                           b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], d_result,
                                                           OWNER_CNT(b, idx), s);
-  const int rc1 = owner_launched(b, sl, e, "stamp_owned", s);
+  const int rc1 = sk_owner_launched(b, sl, e, "stamp_owned", s);
   if (rc1) return rc1;
   b->touched_total += (uint64_t)n * (uint64_t)__builtin_popcountll(voice_mask);
   sk_control_changed(b);
@@ -226,11 +229,11 @@ int skred_bank_stamp_owned(skred_bank_t *b, const int32_t *d_slots, const uint32
   if (rc) return rc;
   if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "stamp_owned: n = %d", n);
   if ((rc = owner_stamps_check(stamps, "stamp_owned"))) return rc;
-  if ((rc = owner_k_check(slot_voices, "stamp_owned"))) return rc;
-  if ((rc = owner_mask_check(slot_voices, voice_mask, "stamp_owned"))) return rc;
+  if ((rc = sk_owner_k_check(slot_voices, "stamp_owned"))) return rc;
+  if ((rc = sk_owner_mask_check(slot_voices, voice_mask, "stamp_owned"))) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = owner_ensure(b))) return rc;
+  if ((rc = sk_owner_ensure(b))) return rc;
   return stamp_launch(b, d_slots, tags, n, d_count_or_null, slot_voices, voice_mask, stamps, d_result, (hipStream_t)stream);
 }
 
@@ -240,11 +243,11 @@ int skred_bank_release_tags(skred_bank_t *b, int first, int count, int slot_voic
   int rc = find_check(b, first, count, slot_voices, tags, n, "release_tags");
   if (rc) return rc;
   if ((rc = owner_stamps_check(stamps, "release_tags"))) return rc;
-  if ((rc = owner_mask_check(slot_voices, voice_mask, "release_tags"))) return rc;
+  if ((rc = sk_owner_mask_check(slot_voices, voice_mask, "release_tags"))) return rc;
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = owner_ensure(b))) return rc;
+  if ((rc = sk_owner_ensure(b))) return rc;
   if ((rc = find_launch(b, first, count, slot_voices, tags, n, b->d_owner_slots, s))) return rc;
   /* entry k is the lowest slot that carries tags[k], or -1: the guard holds on every entry that is a slot */
   return stamp_launch(b, b->d_owner_slots, tags, n, NULL, slot_voices, voice_mask, stamps, d_result, s);
@@ -260,7 +263,7 @@ int skred_bank_ctl_owned(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voice
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = owner_ensure(b))) return rc;
+  if ((rc = sk_owner_ensure(b))) return rc;
   /* the K records, then the n tags, in one staging slot: one kernel reads both */
   const size_t rec_bytes = (size_t)slot_voices * sizeof(sk_ctl_t), bytes = rec_bytes + (size_t)n * sizeof(uint32_t);
   const int wide = (int64_t)n * slot_voices > 64 * 256;    /* (skred_bank_ctl.c: beyond 64 workgroups the records are read from the device) */
@@ -269,13 +272,13 @@ int skred_bank_ctl_owned(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voice
   void *h = sl->h;
   const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)h);
   memcpy((char *)h + rec_bytes, tags, (size_t)n * sizeof(uint32_t));
-  const char *src = (const char *)owner_staged(sl, bytes, wide, s);
+  const char *src = (const char *)sk_owner_staged(sl, bytes, wide, s);
   if (!src) return SKRED_E_NO_DEVICE;
   OWNER_BATCH(b, sl, idx);
   const hipError_t e = (hipError_t)sk_launch_ctl_owned((const sk_ctl_t *)src, slot_voices, voice_mask, d_slots, (const uint32_t *)(src + rec_bytes),
                                                        b->d_owner, n, d_count_or_null, b->n_voices, b->d_ro, b->d_rw, b->d_mask[b->mask_p],
                                                        d_result, OWNER_CNT(b, idx), s);
-  if ((rc = owner_launched(b, sl, e, "ctl_owned", s))) return rc;
+  if ((rc = sk_owner_launched(b, sl, e, "ctl_owned", s))) return rc;
   if (lists) {                                          /* (skred_bank_ctl.c: a controller that lists nobody leaves the reports alone) */
     b->touched_total += (uint64_t)n * (uint64_t)__builtin_popcountll(lists);
     sk_control_changed(b);

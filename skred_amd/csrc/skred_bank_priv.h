@@ -191,6 +191,7 @@ struct skred_bank {
   /* note owners (skred_bank_owner.c), allocated and zeroed by the first call that needs them */
   uint32_t *d_owner;                /* [n_voices] a slot's tag at its first voice, 0: nobody; no render kernel reads it */
   int32_t *d_owner_slots;           /* [SKRED_OWNER_MAX_TAGS] skred_bank_release_tags: the list its find pass leaves for its stamps (behind d_owner) */
+  uint32_t *d_match_pair;           /* [2] skred_bank_find_match: where the shared count pass leaves (written, total) (behind d_owner_slots) */
 };
 
 /* per-voice classification (host shadow) */
@@ -275,6 +276,19 @@ uint64_t sk_ctl_pack(const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mas
  * ascending as unsigned numbers, perm[j] the index that tag has in `tags`; returns 0, or 1 + the index of a repeated tag.  Pure host */
 void sk_owner_free(skred_bank_t *b);
 int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
+/* ... and the array itself with the scratch behind it, allocated and zeroed by the first call that needs them (skred_bank_expr.c too) */
+int sk_owner_ensure(skred_bank_t *b);
+/* ... its checks of K, of a mask over the K voices and of a range of whole slots inside the bank (`who`: for the error text), where
+ * a kernel reads a staged batch from (the pinned buffer, or -- `wide` -- the slot's device twin behind a copy on `s`), and what every
+ * staged launch ends in (the slot is the batch's until its kernel has run) */
+int sk_owner_k_check(int slot_voices, const char *who);
+int sk_owner_mask_check(int slot_voices, uint64_t mask, const char *who);
+int sk_owner_range_check(const skred_bank_t *b, int first, int count, int K, const char *who);
+const void *sk_owner_staged(sk_upd_slot_t *sl, size_t bytes, int wide, hipStream_t s);
+int sk_owner_launched(skred_bank_t *b, sk_upd_slot_t *sl, hipError_t e, const char *what, hipStream_t s);
+/* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
+ * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
+uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);
 /* skred_bank_idle.c, for skred_bank_slots.c: the scratch both list queries share (allocated on first use), the kernels' view of a
  * query on this bank, and room for `need` entries in d_idle_out / h_idle_out */
 int sk_idle_scratch(skred_bank_t *b, hipStream_t s);

@@ -18,6 +18,7 @@
  *   skred_slot_steal_kernels.hip  sk_launch_slot_steal
  *   skred_ctl_kernels.hip     sk_launch_ctl_range, sk_launch_ctl_slots, sk_launch_ctl_owned
  *   skred_owner_kernels.hip   sk_launch_owner_tag, sk_launch_owner_find, sk_launch_owner_stamps
+ *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
@@ -292,6 +293,49 @@ int sk_launch_ctl_owned(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_
                         const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, sk_plane_t *const ro[SKP_COUNT],
                         sk_plane_t *const rw[SKS_COUNT], uint64_t *mask, uint32_t *d_result, uint32_t *cnt, uint32_t *done,
                         uint32_t seq, hipStream_t stream);
+
+/* ---- channels and per-note expression (skred_bank_expr.c -> skred_expr_kernels.hip; include/skred_amd.h: skred_bank_find_match /
+ * _stamp_match / _ctl_match / _ctl_owned_each / _ctl_tags_each) ----
+ * A slot matches when owner != 0 && (owner & mask) == value.  The ranges are whole slots inside the bank (checked on the host). */
+#define SK_EXPR_SPAN 256           /* threads per workgroup of the expression kernels */
+/* the ordered list of the matching slots: one lane per SLOT, skred_idle_scan.hpp's count and scatter.  `idle` holds the bank's idle
+ * scratch (words, counts, offsets), d_voices (the list), max_out, and d_count = two scratch words the count pass fills as it does
+ * for an idle query; first / end / from / base / from_wg are set by the launcher.  d_total[0] = the total, written by the second
+ * launch, which runs with max_out == 0 too */
+typedef struct {
+  sk_idle_args_t idle;
+  const uint32_t *owner;
+  uint32_t *d_total;
+  uint32_t value, mask;
+  int32_t first, n_slots, k_shift;
+} sk_match_args_t;
+int sk_launch_match_find(const sk_match_args_t *args, int first, int count, int slot_voices, hipStream_t stream);
+/* sk_launch_slot_stamps on every matching slot of the range; d_result[2] (zeroed on `stream` ahead of the kernel) += slots stamped,
+ * slots that did not match */
+int sk_launch_match_stamps(const uint32_t *owner, uint32_t value, uint32_t mask, int first, int count, int slot_voices,
+                           uint64_t voice_mask, uint32_t dirty, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
+                           uint64_t now, uint64_t *mask_list, uint32_t *d_result, hipStream_t stream);
+/* sk_launch_ctl_range on the matching slots; d_result[3] (or NULL): voices written, stores withheld, slots that did not match */
+int sk_launch_ctl_match(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_mask, int first, int count, const uint32_t *owner,
+                        uint32_t value, uint32_t mask, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
+                        uint64_t *mask_list, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* A per-entry record is skred_ctl_each_t word for word (layout and bits checked at compile time in skred_bank_expr.c); the bits
+ * equal SKRED_EACH_*.  Values an entry does not name arrive zeroed. */
+#define SK_EACH_INC_SCALE (1u << 0)
+#define SK_EACH_AMP_SCALE (1u << 1)
+#define SK_EACH_VELOCITY  (1u << 2)
+#define SK_EACH_PAN       (1u << 3)
+#define SK_EACH_ALL       ((1u << 4) - 1u)
+enum { SK_EACH_SET = 0, SK_EACH_W_INC_SCALE, SK_EACH_W_AMP_SCALE, SK_EACH_W_VELOCITY, SK_EACH_W_PAN_LEFT, SK_EACH_W_PAN_RIGHT, SK_EACH_WORDS = 8 };
+typedef struct {
+  uint32_t w[SK_EACH_WORDS];
+} sk_each_t;
+/* sk_launch_ctl_owned with entry k's record d_each[k] laid over the K records (d_recs: records without a mask bit, and all of them
+ * when the caller gave none, hold set == 0); d_result[3] as there, the withheld products counted in [1] */
+int sk_launch_ctl_owned_each(const sk_ctl_t *d_recs, const sk_each_t *d_each, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
+                             const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
+                             sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t *mask_list, uint32_t *d_result,
+                             uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

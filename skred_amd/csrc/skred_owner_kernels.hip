@@ -23,22 +23,7 @@
 #include <stdint.h>
 
 #include "skred_launch.h"
-#include "skred_update_common.hpp"   // sk_plane_ptrs_t, sk_stamp_store, sk_slot_valid, sk_batch_done
-
-// d_result[k] += the workgroup's number of threads with flag k set, k < N (every thread arrives: __syncthreads inside)
-template <int N>
-__device__ __forceinline__ void sk_owner_count(uint32_t *sums, uint32_t *d_result, const bool (&flag)[N]) {
-  const int tid = threadIdx.x;
-  if (tid < N) sums[tid] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    const uint32_t c = (uint32_t)__popcll(__ballot(flag[k]));
-    if ((tid & 63) == 0 && c) atomicAdd(&sums[k], c);
-  }
-  __syncthreads();
-  if (d_result && tid < N && sums[tid]) atomicAdd(d_result + tid, sums[tid]);
-}
+#include "skred_update_common.hpp"   // sk_plane_ptrs_t, sk_stamp_store, sk_slot_valid, sk_owner_count, sk_batch_done
 
 __global__ __launch_bounds__(SK_OWNER_SPAN) void sk_owner_tag_kernel(uint32_t *owner, const int32_t *d_slots,
                                                                      const uint32_t *__restrict__ tags, int n, const uint32_t *d_count,

@@ -65,6 +65,22 @@ __device__ __forceinline__ bool sk_slot_valid(int e, int slot_voices, int n_voic
   return e >= 0 && (e & (slot_voices - 1)) == 0 && e <= n_voices - slot_voices;
 }
 
+// d_result[k] += the workgroup's number of threads with flag k set, k < N (every thread arrives: __syncthreads inside).  Integer
+// sums: the same whatever the order of arrival (skred_owner_kernels.hip, skred_expr_kernels.hip)
+template <int N>
+__device__ __forceinline__ void sk_owner_count(uint32_t *sums, uint32_t *d_result, const bool (&flag)[N]) {
+  const int tid = threadIdx.x;
+  if (tid < N) sums[tid] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const uint32_t c = (uint32_t)__popcll(__ballot(flag[k]));
+    if ((tid & 63) == 0 && c) atomicAdd(&sums[k], c);
+  }
+  __syncthreads();
+  if (d_result && tid < N && sums[tid]) atomicAdd(d_result + tid, sums[tid]);
+}
+
 // The batch was read (straight from the host's pinned staging buffer, for small batches): the workgroup that finishes last tells
 // the host, which then reuses the buffer -- a word in pinned memory the host polls, instead of an event behind every batch
 // (an event record costs the stream ~5 us of gap in front of the next kernel: four per block under note traffic).

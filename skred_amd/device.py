@@ -44,10 +44,12 @@ ABI_SYMBOLS = [
     "skred_bank_ctl_range", "skred_bank_ctl_slots", "skred_bank_download_ctl",
     "skred_bank_tag_slots", "skred_bank_find_owned", "skred_bank_stamp_owned", "skred_bank_release_tags", "skred_bank_ctl_owned",
     "skred_bank_owner_clear", "skred_bank_download_owners", "skred_bank_download_env_clocks",
+    "skred_bank_find_match", "skred_bank_find_match_host", "skred_bank_stamp_match", "skred_bank_ctl_match",
+    "skred_bank_ctl_owned_each", "skred_bank_ctl_tags_each",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
-                    "skred_ctl_check", "skred_owner_tags_check"]
+                    "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -137,6 +139,43 @@ OWNER_ALLOW_ZERO, OWNER_UNIQUE = 1, 2
 def tag_array(tags) -> np.ndarray:
     """A contiguous uint32 array of note tags."""
     return np.ascontiguousarray(tags, dtype=np.uint32)
+
+
+# SKRED_EACH_* (skred_bank_ctl_owned_each / _ctl_tags_each)
+EACH_INC_SCALE, EACH_AMP_SCALE, EACH_VELOCITY, EACH_PAN = 1, 2, 4, 8
+EACH_ALL = 15
+
+
+class OwnerMatchC(C.Structure):
+    """ctypes image of ``skred_owner_match_t``: a slot matches when owner != 0 and (owner & mask) == value."""
+    _fields_ = [("value", C.c_uint32), ("mask", C.c_uint32)]
+
+
+def owner_match(value: int = 0, mask: int = 0) -> OwnerMatchC:
+    return OwnerMatchC(int(value) & 0xFFFFFFFF, int(mask) & 0xFFFFFFFF)
+
+
+class CtlEachC(C.Structure):
+    """ctypes image of ``skred_ctl_each_t`` (32 bytes): `set` names the values entry k brings."""
+    _fields_ = [("set", C.c_uint32), ("inc_scale", C.c_float), ("amp_scale", C.c_float), ("velocity", C.c_float),
+                ("pan_left", C.c_float), ("pan_right", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+def ctl_each(set: int = 0, **values) -> CtlEachC:
+    """A per-entry record: ``ctl_each(EACH_INC_SCALE | EACH_PAN, inc_scale=1.01, pan_left=0.2, pan_right=0.8)``."""
+    e = CtlEachC()
+    e.set = int(set)
+    for k, v in values.items():
+        setattr(e, k, v)
+    return e
+
+
+def ctl_each_array(each):
+    """A contiguous ``CtlEachC`` array from a sequence of CtlEachC (a ctypes array of CtlEachC passes through)."""
+    if isinstance(each, C.Array) and each._type_ is CtlEachC:
+        return each
+    each = list(each)
+    return (CtlEachC * len(each))(*each)
 
 
 _lib: Optional[C.CDLL] = None
@@ -254,6 +293,14 @@ def load() -> C.CDLL:
     L.skred_bank_owner_clear.argtypes = [vp, i32, i32, vp]
     L.skred_bank_download_owners.argtypes = [vp, vp, i32, i32]
     L.skred_bank_download_env_clocks.argtypes = [vp, vp, vp, i32, i32]
+    L.skred_owner_match_check.argtypes = [C.POINTER(OwnerMatchC)]
+    L.skred_ctl_each_check.argtypes = [vp, i32, vp, i32, C.c_uint64]
+    L.skred_bank_find_match.argtypes = [vp, i32, i32, i32, C.POINTER(OwnerMatchC), i32, vp, vp, vp]
+    L.skred_bank_find_match_host.argtypes = [vp, i32, i32, i32, C.POINTER(OwnerMatchC), i32, vp, C.POINTER(i32), vp]
+    L.skred_bank_stamp_match.argtypes = [vp, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), C.c_uint32, vp, vp]
+    L.skred_bank_ctl_match.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), vp, vp]
+    L.skred_bank_ctl_owned_each.argtypes = [vp, vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_ctl_tags_each.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
     _lib = L
     return L
 
@@ -303,6 +350,21 @@ def owner_tags_check(tags, flags: int = 0) -> int:
     """skred_owner_tags_check: 0, or SKRED_E_BAD_ARG (-2) for tags the owner entry points would refuse.  Pure host."""
     arr = tag_array(tags)
     return int(load().skred_owner_tags_check(arr.ctypes.data, len(arr), int(flags)))
+
+
+def owner_match_check(m: Optional[OwnerMatchC]) -> int:
+    """skred_owner_match_check: 0, or SKRED_E_BAD_ARG (-2) for None or a value with bits outside the mask.  Pure host."""
+    return int(load().skred_owner_match_check(C.byref(m) if m is not None else None))
+
+
+def ctl_each_check(each, ctls, voice_mask: int, slot_voices: Optional[int] = None) -> int:
+    """skred_ctl_each_check on the entries `each` over the K records `ctls` (None: no base records, then slot_voices is required):
+    0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host."""
+    e = ctl_each_array(each)
+    arr = ctl_array(ctls) if ctls is not None else None
+    K = len(arr) if slot_voices is None else int(slot_voices)
+    return int(load().skred_ctl_each_check(C.cast(e, C.c_void_p), len(e), C.cast(arr, C.c_void_p) if arr is not None else None, K,
+                                           int(voice_mask)))
 
 
 class DeviceBank:
@@ -611,6 +673,62 @@ class DeviceBank:
         _check(self.L.skred_bank_download_env_clocks(self.h, start.ctypes.data, release.ctypes.data, int(first), int(count)),
                "skred_bank_download_env_clocks")
         return start, release
+
+    # ---- channels and per-note expression (include/skred_amd.h: skred_bank_find_match / _stamp_match / _ctl_match /
+    # _ctl_owned_each / _ctl_tags_each) ----
+    def find_match(self, first: int, count: int, slot_voices: int, m: OwnerMatchC, max_out: int = 0, d_slots: int = 0, d_count: int = 0,
+                   stream: int = 0):
+        """Asynchronous on `stream`: the first voices of the slots of [first, first + count) whose owner matches m, ascending, into
+        d_slots[0 .. min(total, max_out)) (int32, device memory); d_count[0] = the TOTAL (uint32)."""
+        _check(self.L.skred_bank_find_match(self.h, int(first), int(count), int(slot_voices), C.byref(m), int(max_out), d_slots or None,
+                                            d_count or None, stream or None), "skred_bank_find_match")
+
+    def find_match_host(self, first: int, count: int, slot_voices: int, m: OwnerMatchC, max_out: int = 0, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the listed slots, total)."""
+        out = np.empty(max(int(max_out), 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_bank_find_match_host(self.h, int(first), int(count), int(slot_voices), C.byref(m), int(max_out),
+                                              out.ctypes.data if max_out > 0 else None, C.byref(total), stream or None)
+        if n < 0:
+            _check(n, "skred_bank_find_match_host")
+        return out[:n].copy(), int(total.value)
+
+    def stamp_match(self, first: int, count: int, slot_voices: int, voice_mask: int, m: OwnerMatchC, stamps: int, d_result: int,
+                    stream: int = 0):
+        """stamp_slots' stores on every matching slot of the range, in one pass.  d_result (uint32[2]): slots stamped, slots that did
+        not match."""
+        _check(self.L.skred_bank_stamp_match(self.h, int(first), int(count), int(slot_voices), int(voice_mask), C.byref(m), int(stamps),
+                                             d_result or None, stream or None), "skred_bank_stamp_match")
+
+    def ctl_match(self, ctls, first: int, count: int, voice_mask: int, m: OwnerMatchC, d_result: int = 0, stream: int = 0):
+        """ctl_range on the matching slots of the range.  d_result (uint32[3], may be 0): voices written, stores withheld, slots that
+        did not match."""
+        arr = ctl_array(ctls)
+        _check(self.L.skred_bank_ctl_match(self.h, C.cast(arr, C.c_void_p), int(first), int(count), len(arr), int(voice_mask), C.byref(m),
+                                           d_result or None, stream or None), "skred_bank_ctl_match")
+
+    def ctl_owned_each(self, ctls, each, voice_mask: int, d_slots: int, tags, slot_voices: Optional[int] = None, d_count: int = 0,
+                       d_result: int = 0, stream: int = 0):
+        """ctl_owned with entry k's record each[k] laid over the K records (ctls None: no base records, slot_voices required).
+        d_result (uint32[3], may be 0): voices written, stores withheld, slots whose owner differs."""
+        e, t = ctl_each_array(each), tag_array(tags)
+        assert len(e) == len(t), "one entry per tag"
+        arr = ctl_array(ctls) if ctls is not None else None
+        K = len(arr) if slot_voices is None else int(slot_voices)
+        _check(self.L.skred_bank_ctl_owned_each(self.h, C.cast(arr, C.c_void_p) if arr is not None else None, C.cast(e, C.c_void_p), K,
+                                                int(voice_mask), d_slots or None, t.ctypes.data, len(t), d_count or None,
+                                                d_result or None, stream or None), "skred_bank_ctl_owned_each")
+
+    def ctl_tags_each(self, ctls, each, first: int, count: int, voice_mask: int, tags, slot_voices: Optional[int] = None,
+                      d_result: int = 0, stream: int = 0):
+        """Expression by note id: each[k] on the lowest slot of [first, first + count) that carries tags[k]."""
+        e, t = ctl_each_array(each), tag_array(tags)
+        assert len(e) == len(t), "one entry per tag"
+        arr = ctl_array(ctls) if ctls is not None else None
+        K = len(arr) if slot_voices is None else int(slot_voices)
+        _check(self.L.skred_bank_ctl_tags_each(self.h, C.cast(arr, C.c_void_p) if arr is not None else None, C.cast(e, C.c_void_p),
+                                               int(first), int(count), K, int(voice_mask), t.ctypes.data, len(t), d_result or None,
+                                               stream or None), "skred_bank_ctl_tags_each")
 
     # ---- slot stealing (include/skred_amd.h: skred_bank_find_steal_slots / _find_steal_slots_host / _note_on_steal_slots) ----
     def find_steal_slots(self, q: SlotStealQueryC, d_slots: int = 0, d_count: int = 0, stream: int = 0):

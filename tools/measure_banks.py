@@ -34,6 +34,10 @@
              skred_fxbank_stamp -- host-held time and the stream time of upload + stamp; beside one 512-frame block of the bank
   fxowners   note-off by tag on the FIXED-POINT bank (release_tags) beside the read-back-and-map route; fxctl: a bank-wide cutoff
              change through ctl_range beside host-view writes + skred_fxbank_update, and ctl_list on 256 entries
+  expr       channels and per-note expression on bank_patch("3sk", 2^20) tagged over 16 channels (medians of 12): ctl_match of one
+             channel beside ctl_range of the range and beside download_owners + numpy pick + list upload + ctl_slots; stamp_match
+             beside that route ending in stamp_slots; 256 bends through one ctl_tags_each beside 256 ctl_owned calls; the 64-frame
+             block after a filter-only ctl_match beside the steady block
   fxsteal    voice stealing on the FIXED-POINT bank: 2^20 voices of fxbank.bank_fx whose polyphony is used up but for 64 idle voices,
              a burst of 256 notes (medians of 12 with minimum and maximum): (a) skred_fxbank_note_on_steal between an event pair --
              stream time, and the time the call held the host; nothing is waited for; (b) the only route without it:
@@ -1172,8 +1176,113 @@ def fxctl():
     db.close()
 
 
+def expr():
+    """Channels and per-note expression on bank_patch("3sk", 2**20), every copy sounding and tagged over 16 channels (tag = channel << 24
+    | slot + 1).  (a) a cutoff change on ONE channel: skred_bank_ctl_match, beside skred_bank_ctl_range over the whole range and beside
+    the only per-channel route before it -- skred_bank_download_owners (a device wait), a pick in numpy, the list uploaded,
+    skred_bank_ctl_slots; (b) all notes off on one channel: skred_bank_stamp_match beside that route ending in skred_bank_stamp_slots;
+    (c) 256 notes, 256 different bends: one skred_bank_ctl_tags_each beside 256 skred_bank_ctl_owned calls; (d) the 64-frame block after
+    a filter-only ctl_match beside the steady block.  Medians of 12 with minimum and maximum; host time held, and stream time between
+    events."""
+    D = device
+    n, K, REPS, F, CHANNELS, NOTES = 1 << 20, 4, 12, 64, 16, 256
+    MEMBERS, VOICES = 0x7, 0xF
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = np.uint64(now - 40000)
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g); db.upload(bank)
+    slots = np.arange(0, n, K, dtype=np.int32)
+    idx = np.arange(len(slots), dtype=np.uint32)
+    tags = (((idx % CHANNELS) + 1) << 24 | (idx // CHANNELS + 1)).astype(np.uint32)
+    dl_all = torch.from_numpy(slots).cuda()
+    db.tag_slots(dl_all.data_ptr(), tags, K)
+    res = torch.zeros(3, dtype=torch.int32, device="cuda")
+    out = torch.zeros(F, 2, device="cuda")
+    m = D.owner_match(3 << 24, 0xFF000000)
+    co = banks.biquad_coeffs(np.array([1]), np.array([900.0], np.float32), np.array([1.2], np.float32), 48000)
+    cut = [D.ctl(D.CTL_FILTER, b0=float(co["b0"][0]), b1=float(co["b1"][0]), b2=float(co["b2"][0]), a1=float(co["a1"][0]), a2=float(co["a2"][0]))
+           for _ in range(K)]
+    torch.cuda.synchronize()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def stats(x):
+        return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f})"
+
+    def series(call, before=None):
+        host, stream = [], []
+        for it in range(2 + REPS):
+            if before is not None:
+                before()
+            torch.cuda.synchronize()
+            h, s_ms = timed(call)
+            if it >= 2:
+                host.append(h); stream.append(s_ms)
+        return f"host time held {stats(host)}; stream time between events {stats(stream)}"
+
+    def parent_route(last):
+        own = db.download_owners()[::K]                            # the device wait the channel calls were built to remove
+        lst = slots[(own != 0) & ((own & np.uint32(0xFF000000)) == np.uint32(3 << 24))]
+        dl = torch.from_numpy(lst).cuda()
+        last(dl, len(lst))
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, every copy sounding, tagged over {CHANNELS} channels ({n // K // CHANNELS} notes each); medians of {REPS}")
+    print(f"  (a) cutoff of one channel, ctl_match: {series(lambda: db.ctl_match(cut, 0, n, MEMBERS, m, res.data_ptr()))}; d_result = {res.cpu().numpy().tolist()}")
+    print(f"  (a) cutoff of the whole range, ctl_range: {series(lambda: db.ctl_range(cut, 0, n, MEMBERS, res.data_ptr()))}")
+    print(f"  (a) cutoff of one channel, download_owners + numpy pick + list upload + ctl_slots: "
+          f"{series(lambda: parent_route(lambda dl, k: db.ctl_slots(cut, MEMBERS, dl.data_ptr(), k, 0, res.data_ptr())))}")
+    retrig = lambda: db.stamp_slots(dl_all.data_ptr(), len(slots), K, VOICES, D.STAMP_TRIGGER)   # noqa: E731
+    print(f"  (b) all notes off on one channel, stamp_match: {series(lambda: db.stamp_match(0, n, K, VOICES, m, D.STAMP_RELEASE, res.data_ptr()), retrig)}; "
+          f"d_result = {res.cpu().numpy()[:2].tolist()}")
+    print(f"  (b) the same, download_owners + numpy pick + list upload + stamp_slots: "
+          f"{series(lambda: parent_route(lambda dl, k: db.stamp_slots(dl.data_ptr(), k, K, VOICES, D.STAMP_RELEASE)), retrig)}")
+    note_tags = tags[3::CHANNELS * 7][:NOTES].copy()
+    bends = [D.ctl_each(D.EACH_INC_SCALE, inc_scale=float(np.float32(2.0 ** ((k % 25 - 12) / 1200.0)))) for k in range(NOTES)]
+    found = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    db.find_owned(0, n, K, note_tags, found.data_ptr())
+    torch.cuda.synchronize()
+    print(f"  (c) {NOTES} notes, {NOTES} bends, one ctl_tags_each: {series(lambda: db.ctl_tags_each(None, bends, 0, n, MEMBERS, note_tags, K, res.data_ptr()))}; "
+          f"d_result = {res.cpu().numpy().tolist()}")
+
+    def one_by_one():
+        for k in range(NOTES):
+            c = [D.ctl(D.CTL_INC_SCALE, inc_scale=bends[k].inc_scale)] * K
+            db.ctl_owned(c, MEMBERS, found.data_ptr() + 4 * k, note_tags[k:k + 1])
+    print(f"  (c) the same, {NOTES} ctl_owned calls on a list that is already on the device: {series(one_by_one)}")
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+    db.upload(bank)
+    for _ in range(8):
+        block()
+    steady = [block() for _ in range(REPS)]
+    after = []
+    for _ in range(REPS):
+        db.ctl_match(cut, 0, n, MEMBERS, m, 0)
+        after.append(block())
+        block()
+    print(f"  (d) the {F}-frame block after a filter-only ctl_match: {stats(after)}; a steady block: {stats(steady)}; kernel {db.last_kernel()}, "
+          f"list violations {db.list_violations()}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
