@@ -2,8 +2,8 @@
  * skred_bank_ctl.c -- patch controllers: a few parameter words of every copy of a tiled patch, changed on the device
  * (include/skred_amd.h: skred_ctl_check, skred_bank_ctl_range / _ctl_slots / _download_ctl).
  *
- * The host side of skred_ctl_kernels.hip, built like skred_bank_notes.c and skred_bank_slots.c: the checks (made before anything
- * touches the device), the K records' way through the staging ring of the update path, the launches.  Nothing here waits for the
+ * The host side of skred_ctl_kernels.hip, on the pieces of skred_bank_checks.c and skred_bank_stage.c: the checks (made before anything
+ * touches the device), the K records' way through the batch path, the launches.  Nothing here waits for the
  * device except the download.  The host's shadow of the bank (h_class, the counters, the lane words, the named set, the tape plan)
  * reads three things about the words a controller stores: whether voice_amp == 0 (SKC_LIVE), whether the increment is finite
  * (SKC_EXOTIC), and the routing.  The checks admit finite values only, the kernel keeps an amp of 0 at 0 and a scaled increment
@@ -51,16 +51,6 @@ static const struct { uint32_t bit; int first, count; const char *name; } ctl_fi
 };
 #define CTL_FIELDS ((int)(sizeof(ctl_fields) / sizeof(ctl_fields[0])))
 
-/* K and the mask over its voices: the rules of skred_slot_query_t */
-static int ctl_shape_check(int slot_voices, uint64_t mask, const char *who) {
-  if (slot_voices < 1 || slot_voices > 64 || (slot_voices & (slot_voices - 1)))
-    return fail(SKRED_E_RANGE, "%s: slot_voices = %d (a power of two, 1 .. 64)", who, slot_voices);
-  if (!mask) return fail(SKRED_E_BAD_ARG, "%s: voice_mask is 0", who);
-  if (slot_voices < 64 && (mask >> slot_voices))
-    return fail(SKRED_E_BAD_ARG, "%s: voice_mask = 0x%llx has bits at or above slot_voices = %d", who, (unsigned long long)mask, slot_voices);
-  return SKRED_OK;
-}
-
 static int ctl_check_one(const skred_ctl_t *c, int l, const char *who) {
   if (c->set & ~(uint32_t)SK_CTL_ALL) return fail(SKRED_E_BAD_ARG, "%s: record %d: unknown bits in set = 0x%x", who, l, c->set);
   if (!c->set) return fail(SKRED_E_BAD_ARG, "%s: record %d: set is 0 and the voice's mask bit is set", who, l);
@@ -82,7 +72,7 @@ static int ctl_check_one(const skred_ctl_t *c, int l, const char *who) {
 
 static int ctl_check(const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask, const char *who) {
   if (!ctl) return fail(SKRED_E_BAD_ARG, "%s: no controller", who);
-  const int rc = ctl_shape_check(slot_voices, voice_mask, who);
+  const int rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", who);   /* (the rules of skred_slot_query_t) */
   if (rc) return rc;
   for (int l = 0; l < slot_voices; l++) {
     if (!((voice_mask >> l) & 1)) continue;                /* a record no voice receives is not looked at */
@@ -107,50 +97,30 @@ uint64_t sk_ctl_pack(const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mas
   return lists;
 }
 
-#define SK_CTL_ZERO_COPY_LANES (64 * 256)   /* up to 64 workgroups read the records from the pinned staging buffer itself */
-
 /* the packed records -> a staging slot -> one of the two kernels (d_slots NULL: the range) */
 static int ctl_launch(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask, int first, int count,
                       const int32_t *d_slots, int n, const uint32_t *d_count, uint32_t *d_result, hipStream_t s) {
   HIP_TRY(hipSetDevice(b->device));
   const size_t bytes = (size_t)slot_voices * sizeof(sk_ctl_t);
-  sk_upd_slot_t *sl;
-  const int rc = sk_staging_slot(b, bytes, s, &sl);
+  sk_batch_t bt;
+  int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;
-  const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)sl->h);
-  /* sk_stage would hand these few KB to the kernel in the pinned buffer itself, which suits a handful of workgroups; a bank-wide
-   * range is thousands of them, each staging the records into its LDS -- over the bus that cost the stream 0.3 ms at 2^20 voices.
-   * Such a launch reads the slot's device twin behind one small copy */
+  const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)bt.h);
+  /* up to 64 workgroups read these few KB from the pinned buffer itself; a bank-wide range is thousands of them, each staging the
+   * records into its LDS: wide (skred_bank_stage.c has the measurement) */
   const int64_t lanes = d_slots ? (int64_t)n * slot_voices : (int64_t)count;
-  const sk_ctl_t *src;
-  if (lanes > SK_CTL_ZERO_COPY_LANES) {
-    const hipError_t ec = hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, s);
-    if (ec != hipSuccess) return fail(SKRED_E_NO_DEVICE, "controller copy -> %s", hipGetErrorString(ec));
-    src = (const sk_ctl_t *)sl->d;
-  } else {
-    src = (const sk_ctl_t *)sk_stage(sl, bytes, s);
-    if (!src) return SKRED_E_NO_DEVICE;
-  }
-  const int idx = (int)(sl - b->upd);
-  if (++b->upd_seq == 0) b->upd_seq = 1;
-  uint32_t *cnt = b->d_upd_cnt + idx, *done = (uint32_t *)b->h_upd_done + idx;
+  const sk_ctl_t *src = (const sk_ctl_t *)sk_batch_send(b, &bt, bytes, lanes > 64 * 256, s);
+  if (!src) return SKRED_E_NO_DEVICE;
   const hipError_t e = d_slots
     ? (hipError_t)sk_launch_ctl_slots(src, slot_voices, voice_mask, d_slots, n, d_count, b->n_voices, b->d_ro, b->d_rw,
-                                      b->d_mask[b->mask_p], d_result, cnt, done, b->upd_seq, s)
+                                      b->d_mask[b->mask_p], d_result, bt.cnt, bt.done, bt.seq, s)
     : (hipError_t)sk_launch_ctl_range(src, slot_voices, voice_mask, first, count, b->d_ro, b->d_rw, b->d_mask[b->mask_p], d_result,
-                                      cnt, done, b->upd_seq, s);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);                      /* (a copy into the slot's device twin may be queued: it reads the slot) */
-    return fail(SKRED_E_NO_DEVICE, "controller launch -> %s", hipGetErrorString(e));
-  }
-  sl->seq = b->upd_seq;
+                                      bt.cnt, bt.done, bt.seq, s);
+  if ((rc = sk_batch_end(&bt, e, "controller", s))) return rc;
   /* every voice the call MAY have listed: the slots of the range (or the entries, whether or not each is a slot) times the voices
    * of a slot whose record names a listing word.  FILTER, PAN, the increments and the depths list nobody */
   const uint64_t slots = d_slots ? (uint64_t)n : (uint64_t)(count / slot_voices);
-  if (lists) {
-    b->touched_total += slots * (uint64_t)__builtin_popcountll(lists);
-    sk_control_changed(b);
-  }
+  if (lists) sk_touched(b, slots * (uint64_t)__builtin_popcountll(lists));
   /* (a controller that lists nobody leaves what earlier launches reported about envelope activity true: an empty motion list is
    * still empty, and the block behind a bank-wide filter sweep stays the steady block -- with sk_control_changed here it ran the
    * list's path on an empty list, 0.150 ms instead of 0.139 ms at 2^20 voices) */
@@ -160,12 +130,9 @@ static int ctl_launch(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voices, 
 int skred_bank_ctl_range(skred_bank_t *b, const skred_ctl_t *ctl, int first, int count, int slot_voices, uint64_t voice_mask,
                          uint32_t *d_result, void *stream) {
   if (!b) return fail(SKRED_E_BAD_ARG, "ctl_range: no bank");
-  const int rc = ctl_check(ctl, slot_voices, voice_mask, "ctl_range");
+  int rc = ctl_check(ctl, slot_voices, voice_mask, "ctl_range");
   if (rc) return rc;
-  if (count < 0 || first < 0 || first > b->n_voices || count > b->n_voices - first)
-    return fail(SKRED_E_RANGE, "ctl_range: range [%d,+%d) outside the bank of %d voices", first, count, b->n_voices);
-  if ((first & (slot_voices - 1)) || (count & (slot_voices - 1)))
-    return fail(SKRED_E_RANGE, "ctl_range: range [%d,+%d) is not made of whole slots of %d voices", first, count, slot_voices);
+  if ((rc = sk_check_slot_range(b->n_voices, first, count, slot_voices, 1, "ctl_range"))) return rc;
   if (count == 0) return SKRED_OK;
   return ctl_launch(b, ctl, slot_voices, voice_mask, first, count, NULL, 0, NULL, d_result, (hipStream_t)stream);
 }
@@ -173,9 +140,9 @@ int skred_bank_ctl_range(skred_bank_t *b, const skred_ctl_t *ctl, int first, int
 int skred_bank_ctl_slots(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask, const int32_t *d_slots, int n,
                          const uint32_t *d_count_or_null, uint32_t *d_result, void *stream) {
   if (!b || !d_slots) return fail(SKRED_E_BAD_ARG, "ctl_slots: no bank or no list");
-  if (n < 0 || n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "ctl_slots: n = %d", n);   /* (n * K stays an int) */
-  const int rc = ctl_check(ctl, slot_voices, voice_mask, "ctl_slots");
+  int rc = sk_check_list_n(n, "ctl_slots");
   if (rc) return rc;
+  if ((rc = ctl_check(ctl, slot_voices, voice_mask, "ctl_slots"))) return rc;
   if (n == 0) return SKRED_OK;
   return ctl_launch(b, ctl, slot_voices, voice_mask, 0, 0, d_slots, n, d_count_or_null, d_result, (hipStream_t)stream);
 }
@@ -184,9 +151,8 @@ static inline float u2f(uint32_t u) { float f; memcpy(&f, &u, 4); return f; }
 
 int skred_bank_download_ctl(skred_bank_t *b, skred_voice_bank_t *h, int src_first, int dst_first, int count) {
   if (!b || !h || count < 0) return fail(SKRED_E_BAD_ARG, "download_ctl: bad arguments");
-  if (src_first < 0 || src_first > b->n_voices || count > b->n_voices - src_first || dst_first < 0 || dst_first > h->n_voices ||
-      count > h->n_voices - dst_first)
-    return fail(SKRED_E_RANGE, "download_ctl window outside bank");
+  int rc = sk_check_window(b->n_voices, src_first, count, "download_ctl");
+  if (rc || (rc = sk_check_window(h->n_voices, dst_first, count, "download_ctl into the host view"))) return rc;
   if (count == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
   static const int planes[] = { SKP_OSC, SKP_ENV_T, SKP_GAIN, SKP_FILT, SKP_MODF, SKP_MODX };

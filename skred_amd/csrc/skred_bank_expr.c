@@ -3,9 +3,9 @@
  * (include/skred_amd.h: skred_owner_match_check, skred_ctl_each_check, skred_bank_find_match / _find_match_host / _stamp_match /
  * _ctl_match / _ctl_owned_each / _ctl_tags_each).
  *
- * The host side of skred_expr_kernels.hip, built like skred_bank_owner.c and skred_bank_ctl.c and on their pieces: the checks (made
- * before anything touches the device), the records', entries' and tags' way through the staging ring of the update path, the
- * launches.  Nothing here waits for the device except _find_match_host, which waits for its stream, and the allocation of the
+ * The host side of skred_expr_kernels.hip, on the pieces of skred_bank_checks.c and skred_bank_stage.c (and the owner array of
+ * skred_bank_owner.c): the checks (made before anything touches the device), the records', entries' and tags' way through the batch
+ * path, the launches.  Nothing here waits for the device except _find_match_host, which waits for its stream, and the allocation of the
  * owner array by the first call that needs it.  What the two range calls tell the bank is what their unguarded twins tell it about
  * the same range -- the host cannot know how many slots match, and the bound behind the in-place rule only has to hold: stamp_match
  * always grows it, ctl_match only when a record names a listing word, and a controller that lists nobody leaves the reports alone
@@ -45,10 +45,7 @@ static int each_check(const skred_ctl_each_t *each, int n, const skred_ctl_t *ct
   if (n < 0) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);
   int rc;
   if (ctl) { if ((rc = skred_ctl_check(ctl, slot_voices, voice_mask))) return rc; }
-  else {
-    if ((rc = sk_owner_k_check(slot_voices, who))) return rc;
-    if ((rc = sk_owner_mask_check(slot_voices, voice_mask, who))) return rc;
-  }
+  else if ((rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", who))) return rc;
   /* what the masked records name: every one (AMP_SCALE needs AMP on all of them), any one (INC_SCALE needs no increment on any) */
   uint32_t all = ctl ? ~0u : 0u, any = 0;
   for (int l = 0; ctl && l < slot_voices; l++)
@@ -106,8 +103,8 @@ static int find_match_check(const skred_bank_t *b, int first, int count, int K, 
   if (!total) return fail(SKRED_E_BAD_ARG, "%s: nowhere to put the count", who);
   if (max_out < 0) return fail(SKRED_E_BAD_ARG, "%s: max_out %d", who, max_out);
   if (max_out > 0 && !slots) return fail(SKRED_E_BAD_ARG, "%s: max_out %d and no list to fill", who, max_out);
-  if ((rc = sk_owner_k_check(K, who))) return rc;
-  return sk_owner_range_check(b, first, count, K, who);
+  if ((rc = sk_check_slot_shape(K, 0, NULL, who))) return rc;
+  return sk_check_slot_range(b->n_voices, first, count, K, 0, who);
 }
 
 /* count and scatter of the matching slots of a checked range; the count pass's (written, total) pair goes to the words behind the
@@ -144,17 +141,11 @@ int skred_bank_find_match_host(skred_bank_t *b, int first, int count, int slot_v
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  const size_t need = (size_t)max_out;
-  if ((rc = sk_idle_out_room(b, need))) return rc;
+  if ((rc = sk_idle_out_room(b, (size_t)max_out))) return rc;
   /* word 0: the total; the list from word 2, as the idle queries lay their answer out */
   if ((rc = find_match_launch(b, first, count, slot_voices, m, max_out, b->d_idle_out + 2, (uint32_t *)b->d_idle_out, s))) return rc;
-  HIP_TRY(hipMemcpyAsync(b->h_idle_out, b->d_idle_out, (2 + need) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int total = b->h_idle_out[0];
-  if (total < 0 || total > count / slot_voices) return fail(SKRED_E_NO_DEVICE, "find_match_host: the device reported %d matches in %d slots", total, count / slot_voices);
-  const int written = total < max_out ? total : max_out;
-  if (written > 0) memcpy(slots, b->h_idle_out + 2, (size_t)written * sizeof(int32_t));
-  if (total_out) *total_out = total;
+  const int written = sk_read_back(b->d_idle_out, b->h_idle_out, max_out, count / slot_voices, slots, s, "find_match_host");
+  if (written >= 0 && total_out) *total_out = b->h_idle_out[0];
   return written;
 }
 
@@ -163,19 +154,16 @@ int skred_bank_stamp_match(skred_bank_t *b, int first, int count, int slot_voice
   if (!b || !d_result) return fail(SKRED_E_BAD_ARG, "stamp_match: no bank or no result");
   int rc = match_check(m, "stamp_match");
   if (rc) return rc;
-  if (!stamps || (stamps & ~(uint32_t)(SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)))
-    return fail(SKRED_E_BAD_ARG, "stamp_match: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", stamps);
-  if ((rc = sk_owner_k_check(slot_voices, "stamp_match"))) return rc;
-  if ((rc = sk_owner_mask_check(slot_voices, voice_mask, "stamp_match"))) return rc;
-  if ((rc = sk_owner_range_check(b, first, count, slot_voices, "stamp_match"))) return rc;
+  if ((rc = sk_check_stamps(stamps, "stamp_match"))) return rc;
+  if ((rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", "stamp_match"))) return rc;
+  if ((rc = sk_check_slot_range(b->n_voices, first, count, slot_voices, 0, "stamp_match"))) return rc;
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
   const hipError_t e = (hipError_t)sk_launch_match_stamps(b->d_owner, m->value, m->mask, first, count, slot_voices, voice_mask, stamps, b->d_ro,
                                                           b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], d_result, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "stamp_match launch -> %s", hipGetErrorString(e));
   /* every slot of the range may match: what skred_bank_stamp_slots on all of them would add */
-  b->touched_total += (uint64_t)(count / slot_voices) * (uint64_t)__builtin_popcountll(voice_mask);
-  sk_control_changed(b);
+  sk_touched(b, (uint64_t)(count / slot_voices) * (uint64_t)__builtin_popcountll(voice_mask));
   return SKRED_OK;
 }
 
@@ -185,27 +173,22 @@ int skred_bank_ctl_match(skred_bank_t *b, const skred_ctl_t *ctl, int first, int
   int rc = skred_ctl_check(ctl, slot_voices, voice_mask);
   if (rc) return rc;
   if ((rc = match_check(m, "ctl_match"))) return rc;
-  if ((rc = sk_owner_range_check(b, first, count, slot_voices, "ctl_match"))) return rc;
+  if ((rc = sk_check_slot_range(b->n_voices, first, count, slot_voices, 0, "ctl_match"))) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
   const size_t bytes = (size_t)slot_voices * sizeof(sk_ctl_t);
-  sk_upd_slot_t *sl;
-  if ((rc = sk_staging_slot(b, bytes, s, &sl))) return rc;
-  const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)sl->h);
+  sk_batch_t bt;
+  if ((rc = sk_batch_begin(b, bytes, s, &bt))) return rc;
+  const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)bt.h);
   /* (skred_bank_ctl.c: beyond 64 workgroups the records are read from the device, not over the bus) */
-  const sk_ctl_t *src = (const sk_ctl_t *)sk_owner_staged(sl, bytes, count > 64 * SK_EXPR_SPAN, s);
+  const sk_ctl_t *src = (const sk_ctl_t *)sk_batch_send(b, &bt, bytes, count > 64 * SK_EXPR_SPAN, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const int idx = (int)(sl - b->upd);
-  if (++b->upd_seq == 0) b->upd_seq = 1;
   const hipError_t e = (hipError_t)sk_launch_ctl_match(src, slot_voices, voice_mask, first, count, b->d_owner, m->value, m->mask, b->d_ro, b->d_rw,
-                                                       b->d_mask[b->mask_p], d_result, b->d_upd_cnt + idx, (uint32_t *)b->h_upd_done + idx,
-                                                       b->upd_seq, s);
-  if ((rc = sk_owner_launched(b, sl, e, "ctl_match", s))) return rc;
-  if (lists) {                                          /* (a controller that lists nobody leaves the reports alone: skred_bank_ctl.c) */
-    b->touched_total += (uint64_t)(count / slot_voices) * (uint64_t)__builtin_popcountll(lists);
-    sk_control_changed(b);
-  }
+                                                       b->d_mask[b->mask_p], d_result, bt.cnt, bt.done, bt.seq, s);
+  if ((rc = sk_batch_end(&bt, e, "ctl_match", s))) return rc;
+  /* (a controller that lists nobody leaves the reports alone: skred_bank_ctl.c) */
+  if (lists) sk_touched(b, (uint64_t)(count / slot_voices) * (uint64_t)__builtin_popcountll(lists));
   return SKRED_OK;
 }
 
@@ -216,7 +199,7 @@ static int owned_each_check(const skred_bank_t *b, const skred_ctl_t *ctl, const
   if (!b) return fail(SKRED_E_BAD_ARG, "%s: no bank", who);
   int rc = skred_owner_tags_check(tags, n, tag_flags);
   if (rc) return rc;
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);   /* (n * K stays an int) */
+  if ((rc = sk_check_list_n(n, who))) return rc;
   return each_check(each, n, ctl, slot_voices, voice_mask, who);
 }
 
@@ -228,28 +211,22 @@ static int owned_each_launch(skred_bank_t *b, const skred_ctl_t *ctl, const skre
   const size_t rec_bytes = (size_t)slot_voices * sizeof(sk_ctl_t), each_bytes = (size_t)n * sizeof(sk_each_t);
   const size_t bytes = rec_bytes + each_bytes + (size_t)n * sizeof(uint32_t);
   const int wide = (int64_t)n * slot_voices > 64 * SK_EXPR_SPAN;
-  sk_upd_slot_t *sl;
-  int rc = sk_staging_slot(b, bytes, s, &sl);
+  sk_batch_t bt;
+  int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;
-  char *h = (char *)sl->h;
+  char *h = (char *)bt.h;
   uint64_t lists = 0;
   if (ctl) lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)h);
   else memset(h, 0, rec_bytes);
   const uint32_t bits = sk_each_pack(each, n, perm, (sk_each_t *)(h + rec_bytes));
   memcpy(h + rec_bytes + each_bytes, tags, (size_t)n * sizeof(uint32_t));
-  const char *src = (const char *)sk_owner_staged(sl, bytes, wide, s);
+  const char *src = (const char *)sk_batch_send(b, &bt, bytes, wide, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const int idx = (int)(sl - b->upd);
-  if (++b->upd_seq == 0) b->upd_seq = 1;
   const hipError_t e = (hipError_t)sk_launch_ctl_owned_each((const sk_ctl_t *)src, (const sk_each_t *)(src + rec_bytes), slot_voices, voice_mask,
                                                             d_slots, (const uint32_t *)(src + rec_bytes + each_bytes), b->d_owner, n, d_count,
-                                                            b->n_voices, b->d_ro, b->d_rw, b->d_mask[b->mask_p], d_result, b->d_upd_cnt + idx,
-                                                            (uint32_t *)b->h_upd_done + idx, b->upd_seq, s);
-  if ((rc = sk_owner_launched(b, sl, e, what, s))) return rc;
-  if (lists || (bits & SK_EACH_LISTS)) {
-    b->touched_total += (uint64_t)n * (uint64_t)__builtin_popcountll(voice_mask);
-    sk_control_changed(b);
-  }
+                                                            b->n_voices, b->d_ro, b->d_rw, b->d_mask[b->mask_p], d_result, bt.cnt, bt.done, bt.seq, s);
+  if ((rc = sk_batch_end(&bt, e, what, s))) return rc;
+  if (lists || (bits & SK_EACH_LISTS)) sk_touched(b, (uint64_t)n * (uint64_t)__builtin_popcountll(voice_mask));
   return SKRED_OK;
 }
 
@@ -270,7 +247,7 @@ int skred_bank_ctl_tags_each(skred_bank_t *b, const skred_ctl_t *ctl, const skre
                              uint64_t voice_mask, const uint32_t *tags, int n, uint32_t *d_result, void *stream) {
   int rc = owned_each_check(b, ctl, each, slot_voices, voice_mask, tags, n, SKRED_OWNER_UNIQUE, "ctl_tags_each");
   if (rc) return rc;
-  if ((rc = sk_owner_range_check(b, first, count, slot_voices, "ctl_tags_each"))) return rc;
+  if ((rc = sk_check_slot_range(b->n_voices, first, count, slot_voices, 0, "ctl_tags_each"))) return rc;
   if (n == 0) return SKRED_OK;
   /* the tags travel sorted (the find pass searches them), and each[k] stays with tags[k]: entry j of the list is the slot of the
    * j-th smallest tag, and receives each[perm[j]] */

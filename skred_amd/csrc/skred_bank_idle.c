@@ -33,8 +33,8 @@ int sk_idle_check(const skred_bank_t *b, const skred_idle_query_t *q, const void
   if (q->which & ~(uint32_t)(SK_IDLE_CRITERIA | SKRED_IDLE_UNNAMED)) return fail(SKRED_E_BAD_ARG, "%s: unknown bits in which = 0x%x", who, q->which);
   if (!(q->which & SK_IDLE_CRITERIA)) return fail(SKRED_E_BAD_ARG, "%s: which = 0x%x selects no criterion", who, q->which);
   if (!(q->settle_level >= 0.0f) || isinf(q->settle_level)) return fail(SKRED_E_BAD_ARG, "%s: settle_level %g", who, (double)q->settle_level);
-  if (q->count <= 0 || q->first < 0 || q->first >= b->n_voices || q->count > b->n_voices - q->first)
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, q->first, q->count, b->n_voices);
+  const int rc = sk_check_slot_range(b->n_voices, q->first, q->count, 1, 0, who);
+  if (rc) return rc;
   if (q->from < q->first || q->from - q->first >= q->count)
     return fail(SKRED_E_RANGE, "%s: from = %d outside the range [%d,+%d)", who, q->from, q->first, q->count);
   return SKRED_OK;
@@ -130,15 +130,10 @@ int skred_bank_find_idle_host(skred_bank_t *b, const skred_idle_query_t *q, int3
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  const size_t need = (size_t)q->max_out;
-  if ((rc = sk_idle_out_room(b, need))) return rc;
+  if ((rc = sk_idle_out_room(b, (size_t)q->max_out))) return rc;
   rc = idle_launch(b, q, b->d_idle_out + 2, (uint32_t *)b->d_idle_out, s);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(b->h_idle_out, b->d_idle_out, (2 + need) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int written = b->h_idle_out[0];
-  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "find_idle_host: the device reported %d voices written of %d", written, q->max_out);
-  if (written > 0) memcpy(voices, b->h_idle_out + 2, (size_t)written * sizeof(int32_t));
-  if (total_out) *total_out = b->h_idle_out[1];
+  const int written = sk_read_back(b->d_idle_out, b->h_idle_out, q->max_out, q->max_out, voices, s, "find_idle_host");
+  if (written >= 0 && total_out) *total_out = b->h_idle_out[1];
   return written;
 }

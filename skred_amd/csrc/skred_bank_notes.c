@@ -3,7 +3,7 @@
  * skred_notes_check, skred_bank_notes_on_list / _note_on_idle / _note_on_steal / _stamp_list).
  *
  * The host side of skred_note_kernels.hip: the checks (made before anything touches the device), the notes' way through the
- * staging ring of the update path, the launches, and the list skred_bank_note_on_idle's query leaves for its placement.
+ * batch path (skred_bank_stage.c), the launches, and the list skred_bank_note_on_idle's query leaves for its placement.
  * Nothing here waits for the device, and nothing here learns which voice took which note: the host's shadow of the bank
  * (h_class, the counters, the lane words) does not depend on what a note stores -- see the header -- so it stays as it is;
  * what the calls do tell the bank is what every control action tells it: `n` more voices may be on the motion list
@@ -56,24 +56,17 @@ static int notes_launch(skred_bank_t *b, const skred_note_t *notes, int n, const
                         int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s) {
   HIP_TRY(hipSetDevice(b->device));
   const size_t bytes = (size_t)n * sizeof(skred_note_t);
-  sk_upd_slot_t *sl;
-  const int rc = sk_staging_slot(b, bytes, s, &sl);
+  sk_batch_t bt;
+  int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;
-  memcpy(sl->h, notes, bytes);
-  const sk_note_t *src = (const sk_note_t *)sk_stage(sl, bytes, s);
+  memcpy(bt.h, notes, bytes);
+  const sk_note_t *src = (const sk_note_t *)sk_batch_send(b, &bt, bytes, 0, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const int idx = (int)(sl - b->upd);
-  if (++b->upd_seq == 0) b->upd_seq = 1;
   const hipError_t e = (hipError_t)sk_launch_notes(src, n, d_voices, d_count, first_entry, b->n_voices, b->d_ro, b->d_rw,
                                                    b->g.synth_sample_count, b->d_mask[b->mask_p], d_assigned, d_result,
-                                                   b->d_upd_cnt + idx, (uint32_t *)b->h_upd_done + idx, b->upd_seq, s);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);                      /* (a copy into the slot's device twin may be queued: it reads the slot) */
-    return fail(SKRED_E_NO_DEVICE, "notes launch -> %s", hipGetErrorString(e));
-  }
-  sl->seq = b->upd_seq;
-  b->touched_total += (uint64_t)n;
-  sk_control_changed(b);
+                                                   bt.cnt, bt.done, bt.seq, s);
+  if ((rc = sk_batch_end(&bt, e, "notes", s))) return rc;
+  sk_touched(b, (uint64_t)n);
   return SKRED_OK;
 }
 
@@ -155,14 +148,13 @@ int skred_bank_note_on_steal(skred_bank_t *b, const skred_idle_query_t *idle_q, 
 int skred_bank_stamp_list(skred_bank_t *b, const int32_t *d_voices, int n, const uint32_t *d_count_or_null, uint32_t stamps,
                           void *stream) {
   if (!b || !d_voices || n < 0) return fail(SKRED_E_BAD_ARG, "stamp_list: no bank, no list or n = %d", n);
-  if (!stamps || (stamps & ~(uint32_t)(SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)))
-    return fail(SKRED_E_BAD_ARG, "stamp_list: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", stamps);
+  const int rc = sk_check_stamps(stamps, "stamp_list");
+  if (rc) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
   const hipError_t e = (hipError_t)sk_launch_stamp_list(d_voices, n, d_count_or_null, b->n_voices, stamps, b->d_ro, b->d_rw,
                                                         b->g.synth_sample_count, b->d_mask[b->mask_p], (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "stamp_list launch -> %s", hipGetErrorString(e));
-  b->touched_total += (uint64_t)n;
-  sk_control_changed(b);
+  sk_touched(b, (uint64_t)n);
   return SKRED_OK;
 }

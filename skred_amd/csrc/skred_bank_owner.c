@@ -3,8 +3,8 @@
  * expect to find (include/skred_amd.h: skred_owner_tags_check, skred_bank_tag_slots / _find_owned / _stamp_owned / _release_tags /
  * _ctl_owned / _owner_clear / _download_owners / _download_env_clocks).
  *
- * The host side of skred_owner_kernels.hip and of sk_ctl_owned_kernel, built like skred_bank_slots.c and skred_bank_ctl.c: the
- * checks (made before anything touches the device), the tags' way through the staging ring of the update path, the launches.
+ * The host side of skred_owner_kernels.hip and of sk_ctl_owned_kernel, on the pieces of skred_bank_checks.c and skred_bank_stage.c:
+ * the checks (made before anything touches the device), the tags' way through the batch path, the launches.
  * Nothing here waits for the device except the two downloads and the allocation of the array by the first call that needs it.  The
  * owner array is no part of the bank the planner knows: no class, counter, lane word or report depends on it.  What a guarded stamp
  * or controller tells the bank is what its unguarded twin tells it -- n * popcount(mask) more voices may be on the motion list (an
@@ -65,34 +65,6 @@ static int tags_check(const uint32_t *tags, int n, uint32_t flags, const char *w
 
 int skred_owner_tags_check(const uint32_t *tags, int n, uint32_t flags) { return tags_check(tags, n, flags, "owner_tags_check"); }
 
-int sk_owner_k_check(int slot_voices, const char *who) {
-  if (slot_voices < 1 || slot_voices > 64 || (slot_voices & (slot_voices - 1)))
-    return fail(SKRED_E_RANGE, "%s: slot_voices = %d (a power of two, 1 .. 64)", who, slot_voices);
-  return SKRED_OK;
-}
-
-int sk_owner_mask_check(int slot_voices, uint64_t mask, const char *who) {
-  if (!mask) return fail(SKRED_E_BAD_ARG, "%s: voice_mask is 0", who);
-  if (slot_voices < 64 && (mask >> slot_voices))
-    return fail(SKRED_E_BAD_ARG, "%s: voice_mask = 0x%llx has bits at or above slot_voices = %d", who, (unsigned long long)mask, slot_voices);
-  return SKRED_OK;
-}
-
-static int owner_stamps_check(uint32_t stamps, const char *who) {
-  if (!stamps || (stamps & ~(uint32_t)(SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)))
-    return fail(SKRED_E_BAD_ARG, "%s: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", who, stamps);
-  return SKRED_OK;
-}
-
-/* a range of whole slots inside the bank, at least one */
-int sk_owner_range_check(const skred_bank_t *b, int first, int count, int K, const char *who) {
-  if (count <= 0 || first < 0 || first >= b->n_voices || count > b->n_voices - first)
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, first, count, b->n_voices);
-  if ((first & (K - 1)) || (count & (K - 1)))
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) is not made of whole slots of %d voices", who, first, count, K);
-  return SKRED_OK;
-}
-
 /* the array, the scratch of skred_bank_release_tags and the two words of skred_bank_find_match (skred_bank_expr.c), allocated and
  * zeroed by the first call that needs them */
 int sk_owner_ensure(skred_bank_t *b) {
@@ -116,52 +88,26 @@ void sk_owner_free(skred_bank_t *b) {
   b->d_match_pair = NULL;
 }
 
-/* where the kernel reads a staged batch from: the pinned buffer itself (sk_stage), or -- `wide`: many workgroups read every byte --
- * the slot's device twin behind a copy */
-const void *sk_owner_staged(sk_upd_slot_t *sl, size_t bytes, int wide, hipStream_t s) {
-  if (!wide) return sk_stage(sl, bytes, s);
-  const hipError_t e = hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) { (void)fail(SKRED_E_NO_DEVICE, "owner copy -> %s", hipGetErrorString(e)); return NULL; }
-  return sl->d;
-}
-
-/* what every launch below ends in: the slot is the batch's until its kernel has run (sk_batch_done) */
-#define OWNER_BATCH(b, sl, idx)                         \
-  const int idx = (int)((sl) - (b)->upd);               \
-  if (++(b)->upd_seq == 0) (b)->upd_seq = 1
-#define OWNER_CNT(b, idx) (b)->d_upd_cnt + (idx), (uint32_t *)(b)->h_upd_done + (idx), (b)->upd_seq
-
-int sk_owner_launched(skred_bank_t *b, sk_upd_slot_t *sl, hipError_t e, const char *what, hipStream_t s) {
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);                      /* (a copy into the slot's device twin may be queued: it reads the slot) */
-    return fail(SKRED_E_NO_DEVICE, "%s launch -> %s", what, hipGetErrorString(e));
-  }
-  sl->seq = b->upd_seq;
-  return SKRED_OK;
-}
-
 int skred_bank_tag_slots(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
                          int slot_voices, uint32_t *d_result, void *stream) {
   if (!b || !d_slots) return fail(SKRED_E_BAD_ARG, "tag_slots: no bank or no list");
   int rc = tags_check(tags, n, SKRED_OWNER_ALLOW_ZERO, "tag_slots");
   if (rc) return rc;
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "tag_slots: n = %d", n);
-  if ((rc = sk_owner_k_check(slot_voices, "tag_slots"))) return rc;
+  if ((rc = sk_check_list_n(n, "tag_slots"))) return rc;
+  if ((rc = sk_check_slot_shape(slot_voices, 0, NULL, "tag_slots"))) return rc;
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
   const size_t bytes = (size_t)n * sizeof(uint32_t);
-  sk_upd_slot_t *sl;
-  if ((rc = sk_staging_slot(b, bytes, s, &sl))) return rc;
-  void *h = sl->h;
-  memcpy(h, tags, bytes);
-  const uint32_t *src = (const uint32_t *)sk_owner_staged(sl, bytes, 0, s);
+  sk_batch_t bt;
+  if ((rc = sk_batch_begin(b, bytes, s, &bt))) return rc;
+  memcpy(bt.h, tags, bytes);
+  const uint32_t *src = (const uint32_t *)sk_batch_send(b, &bt, bytes, 0, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  OWNER_BATCH(b, sl, idx);
   const hipError_t e = (hipError_t)sk_launch_owner_tag(b->d_owner, d_slots, src, n, d_count_or_null, slot_voices, b->n_voices, d_result,
-                                                       OWNER_CNT(b, idx), s);
-  return sk_owner_launched(b, sl, e, "tag_slots", s);
+                                                       bt.cnt, bt.done, bt.seq, s);
+  return sk_batch_end(&bt, e, "tag_slots", s);
 }
 
 /* the find pass of n checked tags over a checked range into d_out (on the device) */
@@ -169,24 +115,22 @@ static int find_launch(skred_bank_t *b, int first, int count, int slot_voices, c
   const size_t bytes = 2 * (size_t)n * sizeof(uint32_t);
   /* one workgroup per 256 slots stages the tags: beyond a handful of workgroups they read the slot's device twin, not the bus */
   const int wide = (count / slot_voices) > 64 * SK_OWNER_SPAN;
-  sk_upd_slot_t *sl;
-  const int rc = sk_staging_slot(b, bytes, s, &sl);
+  sk_batch_t bt;
+  const int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;
-  void *h = sl->h;
-  uint32_t *sorted = (uint32_t *)h, *perm = sorted + n;
+  uint32_t *sorted = (uint32_t *)bt.h, *perm = sorted + n;
   (void)sk_owner_pack(tags, n, sorted, perm);
-  const uint32_t *src = (const uint32_t *)sk_owner_staged(sl, bytes, wide, s);
+  const uint32_t *src = (const uint32_t *)sk_batch_send(b, &bt, bytes, wide, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  OWNER_BATCH(b, sl, idx);
-  const hipError_t e = (hipError_t)sk_launch_owner_find(b->d_owner, first, count, slot_voices, src, src + n, n, d_out, OWNER_CNT(b, idx), s);
-  return sk_owner_launched(b, sl, e, "find_owned", s);
+  const hipError_t e = (hipError_t)sk_launch_owner_find(b->d_owner, first, count, slot_voices, src, src + n, n, d_out, bt.cnt, bt.done, bt.seq, s);
+  return sk_batch_end(&bt, e, "find_owned", s);
 }
 
 static int find_check(const skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, const char *who) {
   int rc = tags_check(tags, n, SKRED_OWNER_UNIQUE, who);
   if (rc) return rc;
-  if ((rc = sk_owner_k_check(slot_voices, who))) return rc;
-  return sk_owner_range_check(b, first, count, slot_voices, who);
+  if ((rc = sk_check_slot_shape(slot_voices, 0, NULL, who))) return rc;
+  return sk_check_slot_range(b->n_voices, first, count, slot_voices, 0, who);
 }
 
 int skred_bank_find_owned(skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, int32_t *d_slots_out,
@@ -204,21 +148,17 @@ int skred_bank_find_owned(skred_bank_t *b, int first, int count, int slot_voices
 static int stamp_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count, int slot_voices,
                         uint64_t voice_mask, uint32_t stamps, uint32_t *d_result, hipStream_t s) {
   const size_t bytes = (size_t)n * sizeof(uint32_t);
-  sk_upd_slot_t *sl;
-  const int rc = sk_staging_slot(b, bytes, s, &sl);
+  sk_batch_t bt;
+  int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;
-  void *h = sl->h;
-  memcpy(h, tags, bytes);
-  const uint32_t *src = (const uint32_t *)sk_owner_staged(sl, bytes, 0, s);
+  memcpy(bt.h, tags, bytes);
+  const uint32_t *src = (const uint32_t *)sk_batch_send(b, &bt, bytes, 0, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  OWNER_BATCH(b, sl, idx);
   const hipError_t e = (hipError_t)sk_launch_owner_stamps(b->d_owner, d_slots, src, n, d_count, slot_voices, voice_mask, b->n_voices, stamps,
                                                           b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], d_result,
-                                                          OWNER_CNT(b, idx), s);
-  const int rc1 = sk_owner_launched(b, sl, e, "stamp_owned", s);
-  if (rc1) return rc1;
-  b->touched_total += (uint64_t)n * (uint64_t)__builtin_popcountll(voice_mask);
-  sk_control_changed(b);
+                                                          bt.cnt, bt.done, bt.seq, s);
+  if ((rc = sk_batch_end(&bt, e, "stamp_owned", s))) return rc;
+  sk_touched(b, (uint64_t)n * (uint64_t)__builtin_popcountll(voice_mask));
   return SKRED_OK;
 }
 
@@ -227,10 +167,9 @@ int skred_bank_stamp_owned(skred_bank_t *b, const int32_t *d_slots, const uint32
   if (!b || !d_slots || !d_result) return fail(SKRED_E_BAD_ARG, "stamp_owned: no bank, list or result");
   int rc = tags_check(tags, n, 0, "stamp_owned");
   if (rc) return rc;
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "stamp_owned: n = %d", n);
-  if ((rc = owner_stamps_check(stamps, "stamp_owned"))) return rc;
-  if ((rc = sk_owner_k_check(slot_voices, "stamp_owned"))) return rc;
-  if ((rc = sk_owner_mask_check(slot_voices, voice_mask, "stamp_owned"))) return rc;
+  if ((rc = sk_check_list_n(n, "stamp_owned"))) return rc;
+  if ((rc = sk_check_stamps(stamps, "stamp_owned"))) return rc;
+  if ((rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", "stamp_owned"))) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
@@ -242,8 +181,8 @@ int skred_bank_release_tags(skred_bank_t *b, int first, int count, int slot_voic
   if (!b || !d_result) return fail(SKRED_E_BAD_ARG, "release_tags: no bank or no result");
   int rc = find_check(b, first, count, slot_voices, tags, n, "release_tags");
   if (rc) return rc;
-  if ((rc = owner_stamps_check(stamps, "release_tags"))) return rc;
-  if ((rc = sk_owner_mask_check(slot_voices, voice_mask, "release_tags"))) return rc;
+  if ((rc = sk_check_stamps(stamps, "release_tags"))) return rc;
+  if ((rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", "release_tags"))) return rc;   /* (K passed find_check: the mask) */
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
@@ -258,7 +197,7 @@ int skred_bank_ctl_owned(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voice
   if (!b || !d_slots) return fail(SKRED_E_BAD_ARG, "ctl_owned: no bank or no list");
   int rc = tags_check(tags, n, 0, "ctl_owned");
   if (rc) return rc;
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "ctl_owned: n = %d", n);   /* (n * K stays an int) */
+  if ((rc = sk_check_list_n(n, "ctl_owned"))) return rc;
   if ((rc = skred_ctl_check(ctl, slot_voices, voice_mask))) return rc;
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -267,29 +206,24 @@ int skred_bank_ctl_owned(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voice
   /* the K records, then the n tags, in one staging slot: one kernel reads both */
   const size_t rec_bytes = (size_t)slot_voices * sizeof(sk_ctl_t), bytes = rec_bytes + (size_t)n * sizeof(uint32_t);
   const int wide = (int64_t)n * slot_voices > 64 * 256;    /* (skred_bank_ctl.c: beyond 64 workgroups the records are read from the device) */
-  sk_upd_slot_t *sl;
-  if ((rc = sk_staging_slot(b, bytes, s, &sl))) return rc;
-  void *h = sl->h;
-  const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)h);
-  memcpy((char *)h + rec_bytes, tags, (size_t)n * sizeof(uint32_t));
-  const char *src = (const char *)sk_owner_staged(sl, bytes, wide, s);
+  sk_batch_t bt;
+  if ((rc = sk_batch_begin(b, bytes, s, &bt))) return rc;
+  const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)bt.h);
+  memcpy((char *)bt.h + rec_bytes, tags, (size_t)n * sizeof(uint32_t));
+  const char *src = (const char *)sk_batch_send(b, &bt, bytes, wide, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  OWNER_BATCH(b, sl, idx);
   const hipError_t e = (hipError_t)sk_launch_ctl_owned((const sk_ctl_t *)src, slot_voices, voice_mask, d_slots, (const uint32_t *)(src + rec_bytes),
                                                        b->d_owner, n, d_count_or_null, b->n_voices, b->d_ro, b->d_rw, b->d_mask[b->mask_p],
-                                                       d_result, OWNER_CNT(b, idx), s);
-  if ((rc = sk_owner_launched(b, sl, e, "ctl_owned", s))) return rc;
-  if (lists) {                                          /* (skred_bank_ctl.c: a controller that lists nobody leaves the reports alone) */
-    b->touched_total += (uint64_t)n * (uint64_t)__builtin_popcountll(lists);
-    sk_control_changed(b);
-  }
+                                                       d_result, bt.cnt, bt.done, bt.seq, s);
+  if ((rc = sk_batch_end(&bt, e, "ctl_owned", s))) return rc;
+  if (lists) sk_touched(b, (uint64_t)n * (uint64_t)__builtin_popcountll(lists));   /* (skred_bank_ctl.c: a controller that lists nobody leaves the reports alone) */
   return SKRED_OK;
 }
 
 int skred_bank_owner_clear(skred_bank_t *b, int first, int count, void *stream) {
   if (!b) return fail(SKRED_E_BAD_ARG, "owner_clear: no bank");
-  if (count < 0 || first < 0 || first > b->n_voices || count > b->n_voices - first)
-    return fail(SKRED_E_RANGE, "owner_clear: range [%d,+%d) outside the bank of %d voices", first, count, b->n_voices);
+  const int rc = sk_check_window(b->n_voices, first, count, "owner_clear");
+  if (rc) return rc;
   if (count == 0 || !b->d_owner) return SKRED_OK;       /* (never tagged: every word is 0 already) */
   HIP_TRY(hipSetDevice(b->device));
   HIP_TRY(hipMemsetAsync(b->d_owner + first, 0, (size_t)count * sizeof(uint32_t), (hipStream_t)stream));
@@ -298,7 +232,8 @@ int skred_bank_owner_clear(skred_bank_t *b, int first, int count, void *stream) 
 
 int skred_bank_download_owners(skred_bank_t *b, uint32_t *host_u32, int first, int count) {
   if (!b || !host_u32 || count < 0) return fail(SKRED_E_BAD_ARG, "download_owners: bad arguments");
-  if (first < 0 || first > b->n_voices || count > b->n_voices - first) return fail(SKRED_E_RANGE, "download_owners window outside bank");
+  const int rc = sk_check_window(b->n_voices, first, count, "download_owners");
+  if (rc) return rc;
   if (count == 0) return SKRED_OK;
   if (!b->d_owner) { memset(host_u32, 0, (size_t)count * sizeof(uint32_t)); return SKRED_OK; }
   HIP_TRY(hipSetDevice(b->device));
@@ -309,7 +244,8 @@ int skred_bank_download_owners(skred_bank_t *b, uint32_t *host_u32, int first, i
 
 int skred_bank_download_env_clocks(skred_bank_t *b, uint64_t *sample_start, uint64_t *sample_release, int first, int count) {
   if (!b || count < 0) return fail(SKRED_E_BAD_ARG, "download_env_clocks: bad arguments");
-  if (first < 0 || first > b->n_voices || count > b->n_voices - first) return fail(SKRED_E_RANGE, "download_env_clocks window outside bank");
+  const int rc = sk_check_window(b->n_voices, first, count, "download_env_clocks");
+  if (rc) return rc;
   if (count == 0 || (!sample_start && !sample_release)) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
   sk_plane_t *st = (sk_plane_t *)malloc((size_t)count * sizeof(sk_plane_t));

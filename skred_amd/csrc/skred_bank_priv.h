@@ -1,9 +1,15 @@
 /*
- * skred_bank_priv.h -- internals shared by the translation units behind include/skred_amd.h
- * (skred_bank.c: lifecycle, tables, upload / download, options, class and tape plan; skred_bank_render.c:
- * one block from request to kernels, as skred_bank_plan.c picks them; skred_bank_update.c: block-granular
- * updates and the deferred queue; skred_bank_idle.c: the free-voice query; skred_bank_steal.c: the victim query; skred_bank_notes.c: note-ons and stamps on voices a
- * device-resident list names; skred_bank_slots.c: the same for the slots of a tiled patch; skred_bank_ctl.c: patch controllers; skred_bank_owner.c: note owners).  Not installed.
+ * skred_bank_priv.h -- internals shared by the translation units behind include/skred_amd.h.  Not installed.
+ *   skred_bank.c         lifecycle, tables, upload / download, options, class and tape plan
+ *   skred_bank_render.c  one block from request to kernels, as skred_bank_plan.c picks them
+ *   skred_bank_stage.c   the staging ring and the batch path: the one way a host-written batch reaches a kernel; the _host queries' read-back
+ *   skred_bank_checks.c  the argument checks the control calls share (pure host; the fixed-point bank uses them too)
+ *   skred_bank_update.c  block-granular updates and the deferred queue
+ *   skred_bank_idle.c    the free-voice query                  skred_bank_steal.c  the victim query
+ *   skred_bank_notes.c   note-ons and stamps on voices a device-resident list names
+ *   skred_bank_slots.c   the same for the slots of a tiled patch, and slot stealing
+ *   skred_bank_ctl.c     patch controllers                     skred_bank_owner.c  note owners
+ *   skred_bank_expr.c    channels and per-note expression: masked owner matches, per-entry controller values
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -165,7 +171,7 @@ struct skred_bank {
   struct sk_queue_item *queue;  /* deferred updates (skred_bank_update.c), singly linked in arrival order */
   struct sk_queue_item *queue_tail;
   int queue_len;
-  sk_upd_slot_t upd[SK_UPD_RING];   /* staging ring of the update path (skred_bank_update.c) */
+  sk_upd_slot_t upd[SK_UPD_RING];   /* staging ring of host-written batches (skred_bank_stage.c) */
   uint32_t upd_head;
   volatile uint32_t *h_upd_done;    /* pinned [SK_UPD_RING]: the sequence number of the last batch each slot's kernels have finished with */
   uint32_t *d_upd_cnt;              /* device [SK_UPD_RING]: arrival counters of those kernels' workgroups */
@@ -278,14 +284,6 @@ void sk_owner_free(skred_bank_t *b);
 int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
 /* ... and the array itself with the scratch behind it, allocated and zeroed by the first call that needs them (skred_bank_expr.c too) */
 int sk_owner_ensure(skred_bank_t *b);
-/* ... its checks of K, of a mask over the K voices and of a range of whole slots inside the bank (`who`: for the error text), where
- * a kernel reads a staged batch from (the pinned buffer, or -- `wide` -- the slot's device twin behind a copy on `s`), and what every
- * staged launch ends in (the slot is the batch's until its kernel has run) */
-int sk_owner_k_check(int slot_voices, const char *who);
-int sk_owner_mask_check(int slot_voices, uint64_t mask, const char *who);
-int sk_owner_range_check(const skred_bank_t *b, int first, int count, int K, const char *who);
-const void *sk_owner_staged(sk_upd_slot_t *sl, size_t bytes, int wide, hipStream_t s);
-int sk_owner_launched(skred_bank_t *b, sk_upd_slot_t *sl, hipError_t e, const char *what, hipStream_t s);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);
@@ -298,12 +296,36 @@ int sk_idle_out_room(skred_bank_t *b, size_t need);
 /* skred_bank_idle.c: everything skred_bank_find_idle refuses, without the device (`voices` / `count`: where the list and the
  * counts would go; `who` names the caller in the error text) */
 int sk_idle_check(const skred_bank_t *b, const skred_idle_query_t *q, const void *voices, const void *count, const char *who);
-/* skred_bank_update.c, the staging ring of host-written batches: a free slot of at least `bytes` (waits for the batch that last
+/* skred_bank_stage.c, the staging ring of host-written batches: a free slot of at least `bytes` (waits for the batch that last
  * used it); where the kernel reads the staged bytes from (the pinned buffer itself, or its device twin behind a copy on `s`) */
 int sk_staging_slot(skred_bank_t *b, size_t bytes, hipStream_t s, sk_upd_slot_t **out);
 const void *sk_stage(sk_upd_slot_t *sl, size_t bytes, hipStream_t s);
+/* ... and the batch path every staged launch takes.  begin: a slot with room for `bytes`, filled through bt->h.  send: where the
+ * kernel reads from -- sk_stage's rule, or, `wide` (many workgroups read every byte), the device twin behind a copy -- and the
+ * batch's number; NULL when the copy failed.  end: the launch's verdict -- failed: the stream is waited for (what is queued still
+ * reads the slot) and the call fails under `who`; else the slot is the batch's until its kernel has run */
+typedef struct {
+  sk_upd_slot_t *sl;
+  void *h;                      /* the slot's pinned buffer */
+  uint32_t *cnt, *done, seq;    /* what a launcher takes as cnt, done, seq */
+} sk_batch_t;
+int sk_batch_begin(skred_bank_t *b, size_t bytes, hipStream_t s, sk_batch_t *bt);
+const void *sk_batch_send(skred_bank_t *b, sk_batch_t *bt, size_t bytes, int wide, hipStream_t s);
+int sk_batch_end(sk_batch_t *bt, hipError_t e, const char *who, hipStream_t s);
+/* ... the ending of a _host query (plain pointers: the fixed-point bank's too): returns the entries copied to `out`, or an error */
+int sk_read_back(const int32_t *d_out, int32_t *h_out, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
+/* skred_bank_checks.c (`who`: the entry point, for the error text): K and -- `what` != NULL, its name -- a mask over the K voices;
+ * the stamp bits; a list's length (n * K stays an int); a range of whole slots of K voices inside the bank, empty only where
+ * allowed; a plain window for the clears and downloads */
+int sk_check_slot_shape(int slot_voices, uint64_t mask, const char *what, const char *who);
+int sk_check_stamps(uint32_t stamps, const char *who);
+int sk_check_list_n(int n, const char *who);
+int sk_check_slot_range(int n_voices, int first, int count, int K, int allow_empty, const char *who);
+int sk_check_window(int n_voices, int first, int count, const char *who);
 /* a control action reached the bank: what earlier launches reported about envelope activity no longer holds (the voices it
  * touched went on the motion list on the device: skred_update_kernels.hip) */
 static inline void sk_control_changed(skred_bank_t *b) { b->control_epoch++; b->env_quiet = 0; b->list_empty = 0; }
+/* ... and may have put this many more voices on the motion list (an upper bound: touched_total is what the in-place rule rests on) */
+static inline void sk_touched(skred_bank_t *b, uint64_t voices) { b->touched_total += voices; sk_control_changed(b); }
 
 #endif

@@ -4,9 +4,8 @@
  * _note_on_idle_slots / _stamp_slots), and slot stealing (skred_slot_steal_check, skred_bank_find_steal_slots / _find_steal_slots_host /
  * _note_on_steal_slots): the victim query of skred_bank_steal.c behind the key pass of skred_slot_steal_kernels.hip.
  *
- * The host side of skred_slot_kernels.hip, built like skred_bank_idle.c and skred_bank_notes.c and on their pieces: the checks (made
- * before anything touches the device), the bank's idle scratch, the notes' way through the staging ring of the update path, the
- * launches.  Nothing here waits for the device except the _host query, which waits for its stream.  What a call tells the bank is
+ * The host side of skred_slot_kernels.hip, on the pieces of skred_bank_checks.c and skred_bank_stage.c: the checks (made before
+ * anything touches the device), the bank's idle scratch, the notes' way through the batch path, the launches.  Nothing here waits for the device except the _host query, which waits for its stream.  What a call tells the bank is
  * what every control action tells it -- with n * popcount(voice_mask) voices, not n: that many more voices may be on the motion
  * list (touched_total, the bound behind the in-place rule), and earlier launches' reports are out of date.
  */
@@ -22,15 +21,6 @@ _Static_assert(sizeof(skred_slot_steal_query_t) == 56 && offsetof(skred_slot_ste
 
 #define SK_SLOT_CRITERIA (SKRED_IDLE_FINISHED | SKRED_IDLE_ENV_DONE | SKRED_IDLE_AMP_ZERO)
 
-/* K and a mask over its voices (`what`: which mask, for the error text) */
-static int slot_shape_check(int slot_voices, uint64_t mask, const char *who, const char *what) {
-  if (slot_voices < 1 || slot_voices > 64 || (slot_voices & (slot_voices - 1)))
-    return fail(SKRED_E_RANGE, "%s: slot_voices = %d (a power of two, 1 .. 64)", who, slot_voices);
-  if (!mask) return fail(SKRED_E_BAD_ARG, "%s: %s is 0", who, what);
-  if (slot_voices < 64 && (mask >> slot_voices)) return fail(SKRED_E_BAD_ARG, "%s: %s = 0x%llx has bits at or above slot_voices = %d", who, what, (unsigned long long)mask, slot_voices);
-  return SKRED_OK;
-}
-
 static int slot_query_check(const skred_slot_query_t *q, int n_voices, const char *who) {
   if (!q) return fail(SKRED_E_BAD_ARG, "%s: no query", who);
   if (q->max_out < 0) return fail(SKRED_E_BAD_ARG, "%s: max_out %d", who, q->max_out);
@@ -38,13 +28,10 @@ static int slot_query_check(const skred_slot_query_t *q, int n_voices, const cha
   if (q->which & ~(uint32_t)SK_SLOT_CRITERIA) return fail(SKRED_E_BAD_ARG, "%s: unknown bits in which = 0x%x", who, q->which);
   if (!(q->which & SK_SLOT_CRITERIA)) return fail(SKRED_E_BAD_ARG, "%s: which = 0x%x selects no criterion", who, q->which);
   if (!(q->settle_level >= 0.0f) || isinf(q->settle_level)) return fail(SKRED_E_BAD_ARG, "%s: settle_level %g", who, (double)q->settle_level);
-  const int rc = slot_shape_check(q->slot_voices, q->member_mask, who, "member_mask");
+  int rc = sk_check_slot_shape(q->slot_voices, q->member_mask, "member_mask", who);
   if (rc) return rc;
   const int K = q->slot_voices;
-  if (q->count <= 0 || q->first < 0 || q->first >= n_voices || q->count > n_voices - q->first)
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, q->first, q->count, n_voices);
-  if ((q->first & (K - 1)) || (q->count & (K - 1)))
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) is not made of whole slots of %d voices", who, q->first, q->count, K);
+  if ((rc = sk_check_slot_range(n_voices, q->first, q->count, K, 0, who))) return rc;
   if (q->from < q->first || q->from - q->first >= q->count)
     return fail(SKRED_E_RANGE, "%s: from = %d outside the range [%d,+%d)", who, q->from, q->first, q->count);
   if (q->from & (K - 1)) return fail(SKRED_E_RANGE, "%s: from = %d is not the first voice of a slot of %d voices", who, q->from, K);
@@ -55,9 +42,9 @@ int skred_slot_query_check(const skred_slot_query_t *q, int n_voices) { return s
 
 static int slot_notes_check(const skred_note_t *notes, int n, int slot_voices, uint64_t voice_mask, const char *who) {
   if (!notes || n < 0) return fail(SKRED_E_BAD_ARG, "%s: no notes or n = %d", who, n);
-  const int rc = slot_shape_check(slot_voices, voice_mask, who, "voice_mask");
+  int rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", who);
   if (rc) return rc;
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);   /* (n * K stays an int) */
+  if ((rc = sk_check_list_n(n, who))) return rc;
   for (int k = 0; k < n; k++)
     for (int l = 0; l < slot_voices; l++) {
       if (!((voice_mask >> l) & 1)) continue;              /* a record no voice receives is not looked at */
@@ -105,16 +92,11 @@ int skred_bank_find_idle_slots_host(skred_bank_t *b, const skred_slot_query_t *q
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  const size_t need = (size_t)q->max_out;
-  if ((rc = sk_idle_out_room(b, need))) return rc;
+  if ((rc = sk_idle_out_room(b, (size_t)q->max_out))) return rc;
   rc = slots_launch(b, q, b->d_idle_out + 2, (uint32_t *)b->d_idle_out, s);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(b->h_idle_out, b->d_idle_out, (2 + need) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int written = b->h_idle_out[0];
-  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "find_idle_slots_host: the device reported %d slots written of %d", written, q->max_out);
-  if (written > 0) memcpy(slots, b->h_idle_out + 2, (size_t)written * sizeof(int32_t));
-  if (total_out) *total_out = b->h_idle_out[1];
+  const int written = sk_read_back(b->d_idle_out, b->h_idle_out, q->max_out, q->max_out, slots, s, "find_idle_slots_host");
+  if (written >= 0 && total_out) *total_out = b->h_idle_out[1];
   return written;
 }
 
@@ -128,24 +110,17 @@ static int slot_notes_launch(skred_bank_t *b, const skred_note_t *notes, int n, 
                              uint32_t *d_result, hipStream_t s) {
   HIP_TRY(hipSetDevice(b->device));
   const size_t bytes = (size_t)n * (size_t)slot_voices * sizeof(skred_note_t);
-  sk_upd_slot_t *sl;
-  const int rc = sk_staging_slot(b, bytes, s, &sl);
+  sk_batch_t bt;
+  int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;
-  memcpy(sl->h, notes, bytes);
-  const sk_note_t *src = (const sk_note_t *)sk_stage(sl, bytes, s);
+  memcpy(bt.h, notes, bytes);
+  const sk_note_t *src = (const sk_note_t *)sk_batch_send(b, &bt, bytes, 0, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const int idx = (int)(sl - b->upd);
-  if (++b->upd_seq == 0) b->upd_seq = 1;
   const hipError_t e = (hipError_t)sk_launch_slot_notes(src, n, slot_voices, voice_mask, d_slots, d_count, first_entry, b->n_voices,
                                                         b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], d_assigned,
-                                                        d_result, b->d_upd_cnt + idx, (uint32_t *)b->h_upd_done + idx, b->upd_seq, s);
-  if (e != hipSuccess) {
-    (void)hipStreamSynchronize(s);                      /* (a copy into the slot's device twin may be queued: it reads the slot) */
-    return fail(SKRED_E_NO_DEVICE, "slot notes launch -> %s", hipGetErrorString(e));
-  }
-  sl->seq = b->upd_seq;
-  b->touched_total += slot_touched(n, voice_mask);
-  sk_control_changed(b);
+                                                        d_result, bt.cnt, bt.done, bt.seq, s);
+  if ((rc = sk_batch_end(&bt, e, "slot notes", s))) return rc;
+  sk_touched(b, slot_touched(n, voice_mask));
   return SKRED_OK;
 }
 
@@ -184,18 +159,16 @@ int skred_bank_note_on_idle_slots(skred_bank_t *b, const skred_slot_query_t *q, 
 int skred_bank_stamp_slots(skred_bank_t *b, const int32_t *d_slots, int n, const uint32_t *d_count_or_null, int slot_voices,
                            uint64_t voice_mask, uint32_t stamps, void *stream) {
   if (!b || !d_slots || n < 0) return fail(SKRED_E_BAD_ARG, "stamp_slots: no bank, no list or n = %d", n);
-  if (!stamps || (stamps & ~(uint32_t)(SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)))
-    return fail(SKRED_E_BAD_ARG, "stamp_slots: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", stamps);
-  const int rc = slot_shape_check(slot_voices, voice_mask, "stamp_slots", "voice_mask");
+  int rc = sk_check_stamps(stamps, "stamp_slots");
   if (rc) return rc;
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "stamp_slots: n = %d", n);
+  if ((rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", "stamp_slots"))) return rc;
+  if ((rc = sk_check_list_n(n, "stamp_slots"))) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
   const hipError_t e = (hipError_t)sk_launch_slot_stamps(d_slots, n, d_count_or_null, slot_voices, voice_mask, b->n_voices, stamps,
                                                          b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "stamp_slots launch -> %s", hipGetErrorString(e));
-  b->touched_total += slot_touched(n, voice_mask);
-  sk_control_changed(b);
+  sk_touched(b, slot_touched(n, voice_mask));
   return SKRED_OK;
 }
 
@@ -213,15 +186,10 @@ static int slot_steal_check(const skred_slot_steal_query_t *q, int n_voices, con
   if (q->reserved[0] || q->reserved[1]) return fail(SKRED_E_BAD_ARG, "%s: reserved words must be 0", who);
   if (q->max_out < 0 || q->max_out > SKRED_STEAL_MAX) return fail(SKRED_E_BAD_ARG, "%s: max_out %d outside [0, %d]", who, q->max_out, SKRED_STEAL_MAX);
   if (!(q->settle_level >= 0.0f) || isinf(q->settle_level)) return fail(SKRED_E_BAD_ARG, "%s: settle_level %g", who, (double)q->settle_level);
-  const int rc = slot_shape_check(q->slot_voices, q->member_mask, who, "member_mask");
+  const int rc = sk_check_slot_shape(q->slot_voices, q->member_mask, "member_mask", who);
   if (rc) return rc;
-  const int K = q->slot_voices;
   if (n_voices <= 0) return fail(SKRED_E_BAD_ARG, "%s: a bank of %d voices", who, n_voices);
-  if (q->count <= 0 || q->first < 0 || q->first >= n_voices || q->count > n_voices - q->first)
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, q->first, q->count, n_voices);
-  if ((q->first & (K - 1)) || (q->count & (K - 1)))
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) is not made of whole slots of %d voices", who, q->first, q->count, K);
-  return SKRED_OK;
+  return sk_check_slot_range(n_voices, q->first, q->count, q->slot_voices, 0, who);
 }
 
 int skred_slot_steal_check(const skred_slot_steal_query_t *q, int n_voices) { return slot_steal_check(q, n_voices, "slot_steal_check"); }
@@ -265,12 +233,8 @@ int skred_bank_find_steal_slots_host(skred_bank_t *b, const skred_slot_steal_que
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = slot_steal_into_scratch(b, q, s))) return rc;
-  HIP_TRY(hipMemcpyAsync(b->h_steal_out, b->d_steal_out, (2 + (size_t)q->max_out) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int written = b->h_steal_out[0];
-  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "find_steal_slots_host: the device reported %d slots written of %d", written, q->max_out);
-  if (written > 0) memcpy(slots, b->h_steal_out + 2, (size_t)written * sizeof(int32_t));
-  if (total_out) *total_out = b->h_steal_out[1];
+  const int written = sk_read_back(b->d_steal_out, b->h_steal_out, q->max_out, q->max_out, slots, s, "find_steal_slots_host");
+  if (written >= 0 && total_out) *total_out = b->h_steal_out[1];
   return written;
 }
 

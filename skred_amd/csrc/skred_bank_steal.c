@@ -36,9 +36,7 @@ static int steal_check(const skred_steal_query_t *q, int n_voices, const char *w
   if (q->max_out < 0 || q->max_out > SKRED_STEAL_MAX) return fail(SKRED_E_BAD_ARG, "%s: max_out %d outside [0, %d]", who, q->max_out, SKRED_STEAL_MAX);
   if (!(q->settle_level >= 0.0f) || isinf(q->settle_level)) return fail(SKRED_E_BAD_ARG, "%s: settle_level %g", who, (double)q->settle_level);
   if (n_voices <= 0) return fail(SKRED_E_BAD_ARG, "%s: a bank of %d voices", who, n_voices);
-  if (q->count <= 0 || q->first < 0 || q->first >= n_voices || q->count > n_voices - q->first)
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, q->first, q->count, n_voices);
-  return SKRED_OK;
+  return sk_check_slot_range(n_voices, q->first, q->count, 1, 0, who);
 }
 
 int skred_steal_check(const skred_steal_query_t *q, int n_voices) { return steal_check(q, n_voices, "steal_check"); }
@@ -138,11 +136,7 @@ int skred_bank_find_steal_host(skred_bank_t *b, const skred_steal_query_t *q, in
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = sk_steal_into_scratch(b, q, s))) return rc;
-  HIP_TRY(hipMemcpyAsync(b->h_steal_out, b->d_steal_out, (2 + (size_t)q->max_out) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int written = b->h_steal_out[0];
-  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "find_steal_host: the device reported %d voices written of %d", written, q->max_out);
-  if (written > 0) memcpy(voices, b->h_steal_out + 2, (size_t)written * sizeof(int32_t));
-  if (total_out) *total_out = b->h_steal_out[1];
+  const int written = sk_read_back(b->d_steal_out, b->h_steal_out, q->max_out, q->max_out, voices, s, "find_steal_host");
+  if (written >= 0 && total_out) *total_out = b->h_steal_out[1];
   return written;
 }

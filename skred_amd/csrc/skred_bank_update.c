@@ -13,8 +13,6 @@
  */
 #include <stdlib.h>
 #include <pthread.h>
-#include <sched.h>
-#include <time.h>
 #include <string.h>
 
 #include "skred_bank_priv.h"
@@ -302,123 +300,42 @@ static int build_batch(const skred_bank_t *b, const skred_voice_bank_t *h, const
   return SKRED_OK;
 }
 
-/* One staging slot of the ring: pinned host buffer, device buffer, and the number of the batch after which both may be
- * reused -- the batch's last kernel stores it into pinned memory (sk_batch_done), the host looks there.  With a ring the
- * host only ever waits for a batch issued SK_UPD_RING batches ago (a host that queues blocks far ahead of the device is
- * held back here, as an event would hold it); a single slot would stall every update behind the render that precedes it in
- * the stream. */
-int sk_staging_slot(skred_bank_t *b, size_t bytes, hipStream_t s, sk_upd_slot_t **out) {
-  const int idx = (int)(b->upd_head++ % SK_UPD_RING);
-  sk_upd_slot_t *sl = &b->upd[idx];
-  if (!b->h_upd_done) {
-    HIP_TRY(hipHostMalloc((void **)&b->h_upd_done, SK_UPD_RING * sizeof(uint32_t), hipHostMallocCoherent));   /* (the host polls words the device stores while kernels run) */
-    for (int i = 0; i < SK_UPD_RING; i++) b->h_upd_done[i] = 0;
-    HIP_TRY(hipMalloc((void **)&b->d_upd_cnt, SK_UPD_RING * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(b->d_upd_cnt, 0, SK_UPD_RING * sizeof(uint32_t)));
-  }
-  if (sl->seq) {
-    struct timespec t0, t1;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (unsigned spins = 0; __atomic_load_n(&b->h_upd_done[idx], __ATOMIC_ACQUIRE) != sl->seq; spins++) {
-      if ((spins & 63) == 63) {
-        sched_yield();
-        clock_gettime(CLOCK_MONOTONIC, &t1);
-        /* Five seconds without the batch's kernel having run: its stream is blocked -- e.g. behind an event the caller means to record
-         * only after this call returns.  Waiting for the device here would turn that into a deadlock, so the call fails instead; the
-         * slot stays marked in flight (its buffers are still the batch's), and the ring moves on to the next slot. */
-        if (t1.tv_sec - t0.tv_sec > 5)
-          return fail(SKRED_E_NO_DEVICE, "update: staging slot %d is still in flight after 5 s (batch %u of a stream that has not run): "
-                                         "the bank is %d update batches ahead of the device", idx, sl->seq, SK_UPD_RING);
-      }
-    }
-    sl->seq = 0;
-  }
-  if (bytes > sl->cap) {
-    if (sl->d) { (void)hipFree(sl->d); sl->d = NULL; }
-    if (sl->h) { (void)hipHostFree(sl->h); sl->h = NULL; }
-    sl->cap = 0;
-    size_t cap = 64 * 1024;
-    while (cap < bytes) cap *= 2;
-    HIP_TRY(hipMalloc(&sl->d, cap));
-    HIP_TRY(hipHostMalloc(&sl->h, cap, hipHostMallocDefault));
-    sl->cap = cap;
-  }
-  (void)s;
-  *out = sl;
-  return SKRED_OK;
-}
-
-/* Where the scatter kernel reads a staged batch from.  A small batch -- the notes of one audio block -- is read straight out
- * of the pinned host buffer (it is mapped into the device's address space): a copy engine transfer in front of a 5 us kernel
- * cost the stream ~12 us each (the copy and the gap behind it), four times per block under note traffic.  A large batch goes
- * through the copy engine into the slot's device twin: bandwidth matters there, not latency. */
-#define SK_UPD_ZERO_COPY_MAX (256 * 1024)
-const void *sk_stage(sk_upd_slot_t *sl, size_t bytes, hipStream_t s) {
-  if (bytes <= SK_UPD_ZERO_COPY_MAX) return sl->h;
-  const hipError_t e = hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) { (void)fail(SKRED_E_NO_DEVICE, "update copy -> %s", hipGetErrorString(e)); return NULL; }
-  return sl->d;
-}
-
 /* push records to the device and scatter them; a voice named twice is applied in order (one launch per run
  * of distinct voices, found with a per-voice epoch mark: linear in the batch) */
 static int apply_batch(skred_bank_t *b, const sk_update_t *rec, const sk_voice_meta_t *meta, int n, hipStream_t s) {
   HIP_TRY(hipSetDevice(b->device));
   const uint32_t dirty = rec[0].dirty;                 /* a batch has one mask */
-  sk_upd_slot_t *sl;
-  if (SK_STAMP_ONLY(dirty)) {
-    /* note-ons / note-offs: voice ids only (stamping the same voice twice with the same clock is idempotent) */
-    int rc = sk_staging_slot(b, (size_t)n * sizeof(int32_t), s, &sl);
-    if (rc) return rc;
-    int32_t *ids = (int32_t *)sl->h;
-    for (int i = 0; i < n; i++) ids[i] = rec[i].voice;
-    const void *src = sk_stage(sl, (size_t)n * sizeof(int32_t), s);
-    if (!src) return SKRED_E_NO_DEVICE;
-    const int idx = (int)(sl - b->upd);
-    if (++b->upd_seq == 0) b->upd_seq = 1;
-    const hipError_t e = (hipError_t)sk_launch_stamp((const int32_t *)src, n, dirty, b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p],
-                                                     b->d_upd_cnt + idx, (uint32_t *)b->h_upd_done + idx, b->upd_seq, s);
-    if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "stamp launch -> %s", hipGetErrorString(e));
-    sl->seq = b->upd_seq;
-    b->touched_total += (uint64_t)n;
-    sk_control_changed(b);
-    return SKRED_OK;
-  }
-  int rc = sk_staging_slot(b, (size_t)n * sizeof(sk_update_t), s, &sl);
-  if (rc) return rc;
-  memcpy(sl->h, rec, (size_t)n * sizeof(sk_update_t));
-  const sk_update_t *src = (const sk_update_t *)sk_stage(sl, (size_t)n * sizeof(sk_update_t), s);
-  if (!src) return SKRED_E_NO_DEVICE;
-  const int idx = (int)(sl - b->upd);
-  if (!b->upd_mark) {
+  const int stamp_only = SK_STAMP_ONLY(dirty);         /* note-ons / note-offs: voice ids only (stamping the same voice twice with the same clock is idempotent) */
+  if (!stamp_only && !b->upd_mark) {
     b->upd_mark = (uint32_t *)calloc((size_t)b->n_voices, sizeof(uint32_t));
     if (!b->upd_mark) return fail(SKRED_E_NO_MEM, "update marks");
   }
-  int start = 0;
-  while (start < n) {
+  const size_t bytes = (size_t)n * (stamp_only ? sizeof(int32_t) : sizeof(sk_update_t));
+  sk_batch_t bt;
+  int rc = sk_batch_begin(b, bytes, s, &bt);
+  if (rc) return rc;
+  if (!stamp_only) memcpy(bt.h, rec, bytes);
+  else for (int i = 0; i < n; i++) ((int32_t *)bt.h)[i] = rec[i].voice;
+  const void *src = sk_batch_send(b, &bt, bytes, 0, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  hipError_t e = hipSuccess;
+  if (stamp_only)
+    e = (hipError_t)sk_launch_stamp((const int32_t *)src, n, dirty, b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p], bt.cnt, bt.done, bt.seq, s);
+  else for (int start = 0, end; start < n && e == hipSuccess; start = end) {   /* one launch per run of distinct voices */
     if (++b->upd_epoch == 0) { memset(b->upd_mark, 0, (size_t)b->n_voices * sizeof(uint32_t)); b->upd_epoch = 1; }
-    int end = start;
-    for (; end < n; end++) {
+    for (end = start; end < n; end++) {
       uint32_t *m = &b->upd_mark[rec[end].voice];
       if (*m == b->upd_epoch) break;                    /* named before in this run: the next launch takes it */
       *m = b->upd_epoch;
     }
     const int last = end == n;                          /* the batch's last launch reports the slot free */
-    if (last && ++b->upd_seq == 0) b->upd_seq = 1;
-    const hipError_t e = (hipError_t)sk_launch_update(src + start, end - start, b->d_ro, b->d_rw,
-                                                      b->g.synth_sample_count, b->d_mask[b->mask_p],
-                                                      last ? b->d_upd_cnt + idx : NULL, last ? (uint32_t *)b->h_upd_done + idx : NULL, b->upd_seq, s);
-    if (e != hipSuccess) {                              /* (launches of this batch already queued still read the slot) */
-      (void)hipStreamSynchronize(s);
-      return fail(SKRED_E_NO_DEVICE, "update launch -> %s", hipGetErrorString(e));
-    }
-    if (last) sl->seq = b->upd_seq;
-    start = end;
+    e = (hipError_t)sk_launch_update((const sk_update_t *)src + start, end - start, b->d_ro, b->d_rw, b->g.synth_sample_count, b->d_mask[b->mask_p],
+                                     last ? bt.cnt : NULL, last ? bt.done : NULL, bt.seq, s);
   }
+  if ((rc = sk_batch_end(&bt, e, stamp_only ? "stamp" : "update", s))) return rc;
   if (meta && (dirty & SKRED_DIRTY_PARAMS)) for (int i = 0; i < n; i++) sk_apply_meta(b, rec[i].voice, &meta[i], 1);
   if (dirty & SKRED_DIRTY_SAMPLE) b->pack_zero = 1;    /* (a voice_sample written onto a skipped voice: cleared again before a packed block) */
-  b->touched_total += (uint64_t)n;
-  sk_control_changed(b);
+  sk_touched(b, (uint64_t)n);
   return SKRED_OK;
 }
 

@@ -106,10 +106,9 @@ static int ctl_launch(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int first, 
 
 int skred_fxbank_ctl_range(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int first, int count, uint32_t *d_result, void *stream) {
   if (!fx) return fail(SKRED_E_BAD_ARG, "fx ctl_range: no bank");
-  const int rc = ctl_check(ctl, "fx ctl_range");
+  int rc = ctl_check(ctl, "fx ctl_range");
   if (rc) return rc;
-  if (count < 0 || first < 0 || first > fx->n_voices || count > fx->n_voices - first)
-    return fail(SKRED_E_RANGE, "fx ctl_range: range [%d,+%d) outside the bank of %d voices", first, count, fx->n_voices);
+  if ((rc = sk_check_slot_range(fx->n_voices, first, count, 1, 1, "fx ctl_range"))) return rc;
   if (count == 0) return SKRED_OK;
   return ctl_launch(fx, ctl, first, count, NULL, NULL, 0, NULL, d_result, (hipStream_t)stream);
 }
@@ -117,9 +116,8 @@ int skred_fxbank_ctl_range(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int fi
 int skred_fxbank_ctl_list(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const int32_t *d_voices, int n, const uint32_t *d_count_or_null,
                           uint32_t *d_result, void *stream) {
   if (!fx || !d_voices) return fail(SKRED_E_BAD_ARG, "fx ctl_list: no bank or no list");
-  if (n < 0 || n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "fx ctl_list: n = %d", n);
-  const int rc = ctl_check(ctl, "fx ctl_list");
-  if (rc) return rc;
+  int rc = sk_check_list_n(n, "fx ctl_list");
+  if (rc || (rc = ctl_check(ctl, "fx ctl_list"))) return rc;
   if (n == 0) return SKRED_OK;
   return ctl_launch(fx, ctl, 0, 0, d_voices, NULL, n, d_count_or_null, d_result, (hipStream_t)stream);
 }
@@ -129,7 +127,7 @@ int skred_fxbank_ctl_owned(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const 
   if (!fx || !d_voices) return fail(SKRED_E_BAD_ARG, "fx ctl_owned: no bank or no list");
   int rc = skred_owner_tags_check(tags, n, 0);
   if (rc) return rc;
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "fx ctl_owned: n = %d", n);
+  if ((rc = sk_check_list_n(n, "fx ctl_owned"))) return rc;
   if ((rc = ctl_check(ctl, "fx ctl_owned"))) return rc;
   if (n == 0) return SKRED_OK;
   return ctl_launch(fx, ctl, 0, 0, d_voices, tags, n, d_count_or_null, d_result, (hipStream_t)stream);

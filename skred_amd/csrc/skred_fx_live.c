@@ -175,8 +175,8 @@ int skred_fx_idle_check(const skred_fx_idle_query_t *q, int n_voices) {
   if (q->which & ~(uint32_t)SKX_IDLE_CRITERIA) return fail(SKRED_E_BAD_ARG, "fx find_idle: unknown bits in which = 0x%x", q->which);
   if (!(q->which & SKX_IDLE_CRITERIA)) return fail(SKRED_E_BAD_ARG, "fx find_idle: which = 0x%x selects no criterion", q->which);
   if (q->settle_q15 < 0) return fail(SKRED_E_BAD_ARG, "fx find_idle: settle_q15 %d", q->settle_q15);
-  if (q->count <= 0 || q->first < 0 || q->first >= n_voices || q->count > n_voices - q->first)
-    return fail(SKRED_E_RANGE, "fx find_idle: range [%d,+%d) outside the bank of %d voices", q->first, q->count, n_voices);
+  const int rc = sk_check_slot_range(n_voices, q->first, q->count, 1, 0, "fx find_idle");
+  if (rc) return rc;
   if (q->from < q->first || q->from - q->first >= q->count)
     return fail(SKRED_E_RANGE, "fx find_idle: from = %d outside the range [%d,+%d)", q->from, q->first, q->count);
   return SKRED_OK;
@@ -247,12 +247,8 @@ int skred_fxbank_find_idle_host(skred_fxbank_t *fx, const skred_fx_idle_query_t 
   }
   rc = skx_idle_launch(fx, q, fx->d_idle_out + 2, (uint32_t *)fx->d_idle_out, s);
   if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(fx->h_idle_out, fx->d_idle_out, (2 + need) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int written = fx->h_idle_out[0];
-  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "fx find_idle_host: the device reported %d voices written of %d", written, q->max_out);
-  if (written > 0) memcpy(voices, fx->h_idle_out + 2, (size_t)written * sizeof(int32_t));
-  if (total_out) *total_out = fx->h_idle_out[1];
+  const int written = sk_read_back(fx->d_idle_out, fx->h_idle_out, q->max_out, q->max_out, voices, s, "fx find_idle_host");
+  if (written >= 0 && total_out) *total_out = fx->h_idle_out[1];
   return written;
 }
 
@@ -335,8 +331,8 @@ int skred_fxbank_note_on_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q
 int skred_fxbank_stamp_list(skred_fxbank_t *fx, const int32_t *d_voices, int n, const uint32_t *d_count_or_null, uint32_t stamps,
                             void *stream) {
   if (!fx || !d_voices || n < 0) return fail(SKRED_E_BAD_ARG, "fx stamp_list: no bank, no list or n = %d", n);
-  if (!stamps || (stamps & ~(uint32_t)SKX_STAMPS))
-    return fail(SKRED_E_BAD_ARG, "fx stamp_list: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", stamps);
+  const int rc = sk_check_stamps(stamps, "fx stamp_list");
+  if (rc) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(fx->device));
   const hipError_t e = (hipError_t)skx_launch_stamp_list(d_voices, n, d_count_or_null, fx->n_voices, stamps, fx->d_ro[SKX_TIME], fx->d_rw[0],

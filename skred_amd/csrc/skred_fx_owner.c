@@ -4,7 +4,7 @@
  * _download_owners, and skred_fxbank_download_params).
  *
  * The host side, built like skred_fx_live.c: the checks (made before anything touches the device; the tags' own through the float
- * bank's skred_owner_tags_check), the tags' way through the staging ring, the launches.  The tag and the find pass are the float
+ * bank's skred_owner_tags_check, the shared ones of skred_bank_checks.c), the tags' way through the staging ring, the launches.  The tag and the find pass are the float
  * bank's kernels, entered through their launchers at slot_voices = 1 without a batch-done word (skred_launch.h: this ring guards a
  * slot with an event); the guarded stamp is skred_fx_owner_kernels.hip.  Nothing here waits for the device except the two downloads
  * and the allocation of the array by the first call that needs it.  The bank has no slots: every call is per voice.
@@ -19,30 +19,10 @@
 
 _Static_assert(SK_OWNER_MAX_TAGS == SKRED_OWNER_MAX_TAGS, "the find kernel's LDS holds SKRED_OWNER_MAX_TAGS tags");
 
-#define SKX_STAMPS (SKRED_STAMP_TRIGGER | SKRED_STAMP_RELEASE)
-
 /* the float bank's check, as it is (its message names skred_owner_tags_check; `who` made the call) */
 static int tags_check(const uint32_t *tags, int n, uint32_t flags, const char *who) {
   (void)who;
   return skred_owner_tags_check(tags, n, flags);
-}
-
-static int list_n_check(int n, const char *who) {
-  if (n > INT32_MAX / 64) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);
-  return SKRED_OK;
-}
-
-static int stamps_check(uint32_t stamps, const char *who) {
-  if (!stamps || (stamps & ~(uint32_t)SKX_STAMPS))
-    return fail(SKRED_E_BAD_ARG, "%s: stamps = 0x%x (SKRED_STAMP_TRIGGER and / or SKRED_STAMP_RELEASE)", who, stamps);
-  return SKRED_OK;
-}
-
-/* at least one voice, inside the bank */
-static int range_check(const skred_fxbank_t *fx, int first, int count, const char *who) {
-  if (count <= 0 || first < 0 || first >= fx->n_voices || count > fx->n_voices - first)
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, first, count, fx->n_voices);
-  return SKRED_OK;
 }
 
 int skx_owner_ensure(skred_fxbank_t *fx) {
@@ -76,7 +56,7 @@ int skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uin
   if (!fx || !d_voices) return fail(SKRED_E_BAD_ARG, "fx tag_list: no bank or no list");
   int rc = tags_check(tags, n, SKRED_OWNER_ALLOW_ZERO, "fx tag_list");
   if (rc) return rc;
-  if ((rc = list_n_check(n, "fx tag_list"))) return rc;
+  if ((rc = sk_check_list_n(n, "fx tag_list"))) return rc;
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
@@ -112,7 +92,7 @@ static int find_launch(skred_fxbank_t *fx, int first, int count, const uint32_t 
 static int find_check(const skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, const char *who) {
   const int rc = tags_check(tags, n, SKRED_OWNER_UNIQUE, who);
   if (rc) return rc;
-  return range_check(fx, first, count, who);
+  return sk_check_slot_range(fx->n_voices, first, count, 1, 0, who);   /* at least one voice, inside the bank */
 }
 
 int skred_fxbank_find_owned(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int32_t *d_voices_out, void *stream) {
@@ -134,8 +114,8 @@ int skred_fxbank_stamp_owned(skred_fxbank_t *fx, const int32_t *d_voices, const 
   if (!fx || !d_voices || !d_result) return fail(SKRED_E_BAD_ARG, "fx stamp_owned: no bank, list or result");
   int rc = tags_check(tags, n, 0, "fx stamp_owned");
   if (rc) return rc;
-  if ((rc = list_n_check(n, "fx stamp_owned"))) return rc;
-  if ((rc = stamps_check(stamps, "fx stamp_owned"))) return rc;
+  if ((rc = sk_check_list_n(n, "fx stamp_owned"))) return rc;
+  if ((rc = sk_check_stamps(stamps, "fx stamp_owned"))) return rc;
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
@@ -155,7 +135,7 @@ int skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const ui
   if (!fx || !d_result) return fail(SKRED_E_BAD_ARG, "fx release_tags: no bank or no result");
   int rc = find_check(fx, first, count, tags, n, "fx release_tags");
   if (rc) return rc;
-  if ((rc = stamps_check(stamps, "fx release_tags"))) return rc;
+  if ((rc = sk_check_stamps(stamps, "fx release_tags"))) return rc;
   if (n == 0) return SKRED_OK;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
@@ -172,8 +152,8 @@ int skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const ui
 
 int skred_fxbank_owner_clear(skred_fxbank_t *fx, int first, int count, void *stream) {
   if (!fx) return fail(SKRED_E_BAD_ARG, "fx owner_clear: no bank");
-  if (count < 0 || first < 0 || first > fx->n_voices || count > fx->n_voices - first)
-    return fail(SKRED_E_RANGE, "fx owner_clear: range [%d,+%d) outside the bank of %d voices", first, count, fx->n_voices);
+  const int rc = sk_check_window(fx->n_voices, first, count, "fx owner_clear");
+  if (rc) return rc;
   if (count == 0 || !fx->d_owner) return SKRED_OK;      /* (never tagged: every word is 0 already) */
   HIP_TRY(hipSetDevice(fx->device));
   HIP_TRY(hipMemsetAsync(fx->d_owner + first, 0, (size_t)count * sizeof(uint32_t), (hipStream_t)stream));
@@ -182,7 +162,8 @@ int skred_fxbank_owner_clear(skred_fxbank_t *fx, int first, int count, void *str
 
 int skred_fxbank_download_owners(skred_fxbank_t *fx, uint32_t *host_u32, int first, int count) {
   if (!fx || !host_u32 || count < 0) return fail(SKRED_E_BAD_ARG, "fx download_owners: bad arguments");
-  if (first < 0 || first > fx->n_voices || count > fx->n_voices - first) return fail(SKRED_E_RANGE, "fx download_owners window outside bank");
+  const int rc = sk_check_window(fx->n_voices, first, count, "fx download_owners");
+  if (rc) return rc;
   if (count == 0) return SKRED_OK;
   if (!fx->d_owner) { memset(host_u32, 0, (size_t)count * sizeof(uint32_t)); return SKRED_OK; }
   HIP_TRY(hipSetDevice(fx->device));
@@ -193,9 +174,8 @@ int skred_fxbank_download_owners(skred_fxbank_t *fx, uint32_t *host_u32, int fir
 
 int skred_fxbank_download_params(skred_fxbank_t *fx, skred_fxpt_bank_t *h, uint32_t *recip_out, int src_first, int dst_first, int count) {
   if (!fx || !h || count < 0) return fail(SKRED_E_BAD_ARG, "fx download_params: bad arguments");
-  if (src_first < 0 || src_first > fx->n_voices || count > fx->n_voices - src_first || dst_first < 0 || dst_first > h->n_voices ||
-      count > h->n_voices - dst_first)
-    return fail(SKRED_E_RANGE, "fx download_params window outside bank");
+  int bad = sk_check_window(fx->n_voices, src_first, count, "fx download_params");
+  if (bad || (bad = sk_check_window(h->n_voices, dst_first, count, "fx download_params into the host view"))) return bad;
   if (count == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(fx->device));
   skx_plane_t *st = (skx_plane_t *)malloc((size_t)SKX_COUNT * (size_t)count * sizeof(skx_plane_t));

@@ -41,9 +41,7 @@ static int steal_check(const skred_fx_steal_query_t *q, int n_voices, const char
   if (q->max_out < 0 || q->max_out > SKRED_STEAL_MAX) return fail(SKRED_E_BAD_ARG, "%s: max_out %d outside [0, %d]", who, q->max_out, SKRED_STEAL_MAX);
   if (q->settle_q15 < 0) return fail(SKRED_E_BAD_ARG, "%s: settle_q15 %d", who, q->settle_q15);
   if (n_voices <= 0) return fail(SKRED_E_BAD_ARG, "%s: a bank of %d voices", who, n_voices);
-  if (q->count <= 0 || q->first < 0 || q->first >= n_voices || q->count > n_voices - q->first)
-    return fail(SKRED_E_RANGE, "%s: range [%d,+%d) outside the bank of %d voices", who, q->first, q->count, n_voices);
-  return SKRED_OK;
+  return sk_check_slot_range(n_voices, q->first, q->count, 1, 0, who);
 }
 
 int skred_fx_steal_check(const skred_fx_steal_query_t *q, int n_voices) { return steal_check(q, n_voices, "fx steal_check"); }
@@ -122,12 +120,8 @@ int skred_fxbank_find_steal_host(skred_fxbank_t *fx, const skred_fx_steal_query_
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = steal_into_scratch(fx, q, s))) return rc;
-  HIP_TRY(hipMemcpyAsync(fx->h_steal_out, fx->d_steal_out, (2 + (size_t)q->max_out) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  const int written = fx->h_steal_out[0];
-  if (written < 0 || written > q->max_out) return fail(SKRED_E_NO_DEVICE, "fx find_steal_host: the device reported %d voices written of %d", written, q->max_out);
-  if (written > 0) memcpy(voices, fx->h_steal_out + 2, (size_t)written * sizeof(int32_t));
-  if (total_out) *total_out = fx->h_steal_out[1];
+  const int written = sk_read_back(fx->d_steal_out, fx->h_steal_out, q->max_out, q->max_out, voices, s, "fx find_steal_host");
+  if (written >= 0 && total_out) *total_out = fx->h_steal_out[1];
   return written;
 }
 

@@ -102,6 +102,14 @@ int skx_owner_ensure(skred_fxbank_t *fx);
 void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
 /* skred_bank_owner.c: the find pass's view of n <= SKRED_OWNER_MAX_TAGS tags (sorted ascending as unsigned numbers, and where each stood) */
 int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
+/* skred_bank_checks.c, the float bank's argument checks this bank shares (`who`: the entry point, with its "fx " in front): the stamp
+ * bits, a list's length, a range of voices (K = 1) inside the bank, empty only where allowed, a plain window */
+int sk_check_stamps(uint32_t stamps, const char *who);
+int sk_check_list_n(int n, const char *who);
+int sk_check_slot_range(int n_voices, int first, int count, int K, int allow_empty, const char *who);
+int sk_check_window(int n_voices, int first, int count, const char *who);
+/* skred_bank_stage.c: the ending of a _host query -- returns the entries copied to `out`, or an error */
+int sk_read_back(const int32_t *d_out, int32_t *h_out, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
 
 /* skred_fx_kernels.hip, skred_fx_live_kernels.hip */
 int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);

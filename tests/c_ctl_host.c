@@ -1,7 +1,14 @@
 /* The host side of the patch controllers without a device: skred_ctl_check, the record packing (sk_ctl_pack) and every refusal the
  * entry points make before anything touches the device, on a skred_bank_t that is nothing but its voice count (a refused call reads
  * no other member).  One line per case, "OK" last.  tests/test_ctl_cpu.py builds and runs it; built together with
- * skred_amd/csrc/skred_bank_ctl.c and -fsanitize=address,undefined it is the sanitizer run of that file's host code. */
+ * skred_amd/csrc/skred_bank_ctl.c, the shared checks and the batch path it reaches, and -fsanitize=address,undefined
+ * it is the sanitizer run of those files' host code -- from the repository root, after the library is built (the program's own copy of
+ * skred_bank_ctl.c, skred_bank_checks.c and skred_bank_stage.c takes the place of the library's; everything else it calls comes from the library):
+ *   gcc -O1 -g -Wall -Werror -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iskred_amd/csrc \
+ *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_ctl_host.c skred_amd/csrc/skred_bank_ctl.c skred_amd/csrc/skred_bank_checks.c \
+ *       skred_amd/csrc/skred_bank_stage.c -o /tmp/c_ctl_host_san \
+ *       -Lskred_amd -lskred_amd -L${ROCM_PATH:-/opt/rocm}/lib -lamdhip64 -lm -lpthread \
+ *       -Wl,-rpath,$PWD/skred_amd -Wl,-rpath,${ROCM_PATH:-/opt/rocm}/lib && /tmp/c_ctl_host_san */
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -95,6 +102,15 @@ int main(void) {
   k8[7].b2 = 0.1f;
   CASE("slots/empty", skred_bank_ctl_slots(b, k8, 8, 0xFF, dummy_list, 0, NULL, NULL, NULL) == SKRED_OK);
   CASE("download/null", skred_bank_download_ctl(NULL, NULL, 0, 0, 0) == SKRED_E_BAD_ARG);
+  /* the checks the entry points share (skred_bank_checks.c): an empty range at the very end is a controller's alone, and a call that
+   * is wrong in several ways gets the code of its first check -- stamp_slots looks at the stamps before K and the mask */
+  CASE("range/empty_at_the_end_k1", skred_bank_ctl_range(b, k8, 200, 0, 1, 1, NULL, NULL) == SKRED_OK);
+  CASE("range/empty_past_the_end", skred_bank_ctl_range(b, k8, 201, 0, 1, 1, NULL, NULL) == SKRED_E_RANGE);
+  CASE("slots/n_at_the_limit", skred_bank_ctl_slots(b, k8, 8, 0xFF, dummy_list, INT32_MAX / 64 + 1, NULL, NULL, NULL) == SKRED_E_BAD_ARG);
+  CASE("slots/stamp_slots_k3_mask_at_k_stamps0", skred_bank_stamp_slots(b, dummy_list, 4, NULL, 3, 0x8, 0, NULL) == SKRED_E_BAD_ARG);
+  CASE("slots/stamp_slots_k3_mask_at_k_stamps4", skred_bank_stamp_slots(b, dummy_list, 4, NULL, 3, 0x8, 4, NULL) == SKRED_E_BAD_ARG);
+  CASE("slots/stamp_slots_k3_mask_at_k", skred_bank_stamp_slots(b, dummy_list, 4, NULL, 3, 0x8, SKRED_STAMP_RELEASE, NULL) == SKRED_E_RANGE);
+  CASE("slots/stamp_slots_mask_at_k", skred_bank_stamp_slots(b, dummy_list, 4, NULL, 4, 0x10, SKRED_STAMP_RELEASE, NULL) == SKRED_E_BAD_ARG);
   CASE("bank/untouched", b->touched_total == 0 && b->control_epoch == 0 && b->upd_seq == 0 && b->upd_head == 0);
   free(b);
   puts(failures ? "FAILED" : "OK");

@@ -2,11 +2,13 @@
  * the per-entry records (sk_each_pack: named values word for word, the others zeroed), the permutation that keeps each[k] beside
  * tags[k] through the sort of the tags, and every refusal the entry points make before anything touches the device, on a skred_bank_t
  * that is nothing but its voice count (a refused call reads no other member).  One line per case, "OK" last.
- * tests/test_expr_cpu.py builds and runs it; built together with skred_amd/csrc/skred_bank_expr.c and -fsanitize=address,undefined
- * it is the sanitizer run of that file's host code -- from the repository root, after the library is built (the program's own copy of
- * the file takes the place of the library's; everything else it calls comes from the library):
+ * tests/test_expr_cpu.py builds and runs it; built together with skred_amd/csrc/skred_bank_expr.c, the shared checks and the batch
+ * path it reaches, and -fsanitize=address,undefined it is the sanitizer run of those files' host code -- from the repository root,
+ * after the library is built (the program's own copy of skred_bank_expr.c, skred_bank_checks.c and skred_bank_stage.c takes the place
+ * of the library's; everything else it calls comes from the library):
  *   gcc -O1 -g -Wall -Werror -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iskred_amd/csrc \
- *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_expr_host.c skred_amd/csrc/skred_bank_expr.c -o /tmp/c_expr_host_san \
+ *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_expr_host.c skred_amd/csrc/skred_bank_expr.c skred_amd/csrc/skred_bank_checks.c \
+ *       skred_amd/csrc/skred_bank_stage.c -o /tmp/c_expr_host_san \
  *       -Lskred_amd -lskred_amd -L${ROCM_PATH:-/opt/rocm}/lib -lamdhip64 -lm -lpthread \
  *       -Wl,-rpath,$PWD/skred_amd -Wl,-rpath,${ROCM_PATH:-/opt/rocm}/lib && /tmp/c_expr_host_san */
 #include <math.h>
@@ -181,9 +183,19 @@ int main(void) {
   CASE("stamp/count_zero", skred_bank_stamp_match(b, 8, 0, 8, 0xFF, &chan, REL, res, NULL) == SKRED_E_RANGE);
   CASE("stamp/past_the_bank", skred_bank_stamp_match(b, 0, 208, 8, 0xFF, &chan, REL, res, NULL) == SKRED_E_RANGE);
 
+  /* the checks the entry points share (skred_bank_checks.c): a call that is wrong in several ways gets the code of its first check
+   * (stamp_match looks at the stamps before K and the mask), and the matches refuse the empty range a controller accepts */
+  CASE("stamp/k3_mask_at_k_stamps0", skred_bank_stamp_match(b, 0, 200, 3, 0x8, &chan, 0, res, NULL) == SKRED_E_BAD_ARG);
+  CASE("stamp/k3_mask_at_k_stamps4", skred_bank_stamp_match(b, 0, 200, 3, 0x8, &chan, 4, res, NULL) == SKRED_E_BAD_ARG);
+  CASE("stamp/k3_mask_at_k", skred_bank_stamp_match(b, 0, 200, 3, 0x8, &chan, REL, res, NULL) == SKRED_E_RANGE);
+  CASE("stamp/count_zero_at_the_end", skred_bank_stamp_match(b, 200, 0, 8, 0xFF, &chan, REL, res, NULL) == SKRED_E_RANGE);
+  CASE("find/count_zero_at_the_end", skred_bank_find_match(b, 200, 0, 8, &chan, 4, list, res, NULL) == SKRED_E_RANGE);
+
   skred_ctl_t k8[8];
   memset(k8, 0, sizeof(k8));
   for (int l = 0; l < 8; l++) { k8[l].set = SKRED_CTL_PAN; k8[l].pan_left = 0.25f; k8[l].pan_right = 0.75f; }
+  CASE("ctl/count_zero_at_the_end", skred_bank_ctl_match(b, k8, 200, 0, 8, 0xFF, &chan, NULL, NULL) == SKRED_E_RANGE);
+  CASE("ctl/range_empty_at_the_end", skred_bank_ctl_range(b, k8, 200, 0, 8, 0xFF, NULL, NULL) == SKRED_OK);
   CASE("ctl/null_bank", skred_bank_ctl_match(NULL, k8, 0, 200, 8, 0xFF, &chan, NULL, NULL) == SKRED_E_BAD_ARG);
   CASE("ctl/null_ctl", skred_bank_ctl_match(b, NULL, 0, 200, 8, 0xFF, &chan, NULL, NULL) == SKRED_E_BAD_ARG);
   CASE("ctl/null_match", skred_bank_ctl_match(b, k8, 0, 200, 8, 0xFF, NULL, NULL, NULL) == SKRED_E_BAD_ARG);

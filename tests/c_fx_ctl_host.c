@@ -2,8 +2,14 @@
  * (skx_ctl_pack), the sort-plus-permutation of the tags as the find pass gets them (sk_owner_pack) and every refusal the entry points
  * make before anything touches the device, on a skred_fxbank_t that is nothing but its voice count (a refused call reads no other
  * member).  One line per case, "OK" last.  tests/test_fx_ctl_cpu.py and tests/test_fx_owner_cpu.py build and run it; built together
- * with skred_amd/csrc/skred_fx_owner.c and skred_fx_ctl.c under -fsanitize=address,undefined it is the sanitizer run of those files'
- * host code. */
+ * with skred_amd/csrc/skred_fx_owner.c, skred_fx_ctl.c and the checks they share with the float bank under -fsanitize=address,undefined
+ * it is the sanitizer run of those files' host code -- from the repository root, after the library is built (the program's own copy of
+ * skred_fx_owner.c, skred_fx_ctl.c and skred_bank_checks.c takes the place of the library's; everything else it calls comes from the library):
+ *   gcc -O1 -g -Wall -Werror -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iskred_amd/csrc \
+ *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_fx_ctl_host.c skred_amd/csrc/skred_fx_owner.c skred_amd/csrc/skred_fx_ctl.c \
+ *       skred_amd/csrc/skred_bank_checks.c -o /tmp/c_fx_ctl_host_san \
+ *       -Lskred_amd -lskred_amd -L${ROCM_PATH:-/opt/rocm}/lib -lamdhip64 -lm -lpthread \
+ *       -Wl,-rpath,$PWD/skred_amd -Wl,-rpath,${ROCM_PATH:-/opt/rocm}/lib && /tmp/c_fx_ctl_host_san */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -183,6 +189,12 @@ int main(void) {
   CASE("release/count_zero", skred_fxbank_release_tags(fx, 0, 0, t4, 4, REL, res, NULL) == RNG);
   CASE("release/past_the_bank", skred_fxbank_release_tags(fx, 0, 301, t4, 4, REL, res, NULL) == RNG);
   CASE("release/empty", skred_fxbank_release_tags(fx, 0, 300, t4, 0, REL, res, NULL) == SKRED_OK);
+
+  /* the checks shared with the float bank (skred_bank_checks.c): the same codes, in the same order */
+  CASE("stamp/stamps4", skred_fxbank_stamp_owned(fx, list, t4, 4, NULL, 4, res, NULL) == BAD);
+  CASE("release/stamps4_count_zero", skred_fxbank_release_tags(fx, 300, 0, t4, 4, 4, res, NULL) == RNG);
+  CASE("release/stamps0", skred_fxbank_release_tags(fx, 0, 300, t4, 4, 0, res, NULL) == BAD);
+  CASE("find/count_zero_at_the_end", skred_fxbank_find_owned(fx, 300, 0, t4, 4, list, NULL) == RNG);
 
   CASE("clear/null_bank", skred_fxbank_owner_clear(NULL, 0, 8, NULL) == BAD);
   CASE("clear/negative", skred_fxbank_owner_clear(fx, 0, -1, NULL) == RNG);

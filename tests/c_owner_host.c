@@ -1,8 +1,14 @@
 /* The host side of the note owners without a device: skred_owner_tags_check, the sort-plus-permutation packing of the find pass
  * (sk_owner_pack) and every refusal the entry points make before anything touches the device, on a skred_bank_t that is nothing but
  * its voice count (a refused call reads no other member).  One line per case, "OK" last.  tests/test_owner_cpu.py builds and runs
- * it; built together with skred_amd/csrc/skred_bank_owner.c and -fsanitize=address,undefined it is the sanitizer run of that file's
- * host code. */
+ * it; built together with skred_amd/csrc/skred_bank_owner.c, the shared checks and the batch path it reaches, and -fsanitize=address,undefined
+ * it is the sanitizer run of those files' host code -- from the repository root, after the library is built (the program's own copy of
+ * skred_bank_owner.c, skred_bank_checks.c and skred_bank_stage.c takes the place of the library's; everything else it calls comes from the library):
+ *   gcc -O1 -g -Wall -Werror -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iskred_amd/csrc \
+ *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_owner_host.c skred_amd/csrc/skred_bank_owner.c skred_amd/csrc/skred_bank_checks.c \
+ *       skred_amd/csrc/skred_bank_stage.c -o /tmp/c_owner_host_san \
+ *       -Lskred_amd -lskred_amd -L${ROCM_PATH:-/opt/rocm}/lib -lamdhip64 -lm -lpthread \
+ *       -Wl,-rpath,$PWD/skred_amd -Wl,-rpath,${ROCM_PATH:-/opt/rocm}/lib && /tmp/c_owner_host_san */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -146,6 +152,18 @@ int main(void) {
   k8[2].set = 0;
   CASE("ctl/set0_masked", skred_bank_ctl_owned(b, k8, 8, 0xFF, list, t4, 4, NULL, NULL, NULL) == SKRED_E_BAD_ARG);
   CASE("ctl/set0_unmasked_empty", skred_bank_ctl_owned(b, k8, 8, 0xFB, list, t4, 0, NULL, NULL, NULL) == SKRED_OK);
+
+  /* the checks the entry points share (skred_bank_checks.c): a find refuses the empty range a controller accepts, and a call that is
+   * wrong in several ways gets the code of its first check -- stamp_owned looks at the stamps before K, release_tags at K first */
+  CASE("find/count_zero_at_the_end", skred_bank_find_owned(b, 200, 0, 8, t4, 4, list, NULL) == SKRED_E_RANGE);
+  CASE("ctl/range_empty_at_the_end", skred_bank_ctl_range(b, k8, 200, 0, 8, 0xFB, NULL, NULL) == SKRED_OK);
+  CASE("stamp/k3_mask_at_k_stamps0", skred_bank_stamp_owned(b, list, t4, 4, NULL, 3, 0x8, 0, res, NULL) == SKRED_E_BAD_ARG);
+  CASE("stamp/k3_mask_at_k_stamps4", skred_bank_stamp_owned(b, list, t4, 4, NULL, 3, 0x8, 4, res, NULL) == SKRED_E_BAD_ARG);
+  CASE("stamp/k3_mask_at_k", skred_bank_stamp_owned(b, list, t4, 4, NULL, 3, 0x8, REL, res, NULL) == SKRED_E_RANGE);
+  CASE("release/k3_mask_at_k_stamps0", skred_bank_release_tags(b, 0, 200, 3, 0x8, t4, 4, 0, res, NULL) == SKRED_E_RANGE);
+  CASE("release/k3_mask_at_k_stamps4", skred_bank_release_tags(b, 0, 200, 3, 0x8, t4, 4, 4, res, NULL) == SKRED_E_RANGE);
+  CASE("release/mask_at_k_stamps0", skred_bank_release_tags(b, 0, 200, 4, 0x10, t4, 4, 0, res, NULL) == SKRED_E_BAD_ARG);
+  CASE("release/count_zero_bad_mask", skred_bank_release_tags(b, 200, 0, 8, 0, t4, 4, REL, res, NULL) == SKRED_E_RANGE);
 
   CASE("clear/null_bank", skred_bank_owner_clear(NULL, 0, 8, NULL) == SKRED_E_BAD_ARG);
   CASE("clear/negative", skred_bank_owner_clear(b, 0, -1, NULL) == SKRED_E_RANGE);

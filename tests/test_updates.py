@@ -414,7 +414,7 @@ def test_million_voice_bank_takes_small_updates(dev):
 def test_staging_ring_reused_across_two_streams_under_host_polling(dev):
     """The update path's staging ring: a batch is read by its scatter kernel straight from one of eight pinned slots, the kernel's
     last workgroup re-arms the slot's arrival counter and then stores the batch's number into pinned memory, and the host -- which
-    polls that word instead of waiting for an event -- reuses the slot (skred_bank_update.c: staging_slot;
+    polls that word instead of waiting for an event -- reuses the slot (skred_bank_stage.c: sk_staging_slot;
     skred_update_kernels.hip: sk_batch_done).  Batches issued on ONE stream are ordered by the stream whatever the kernel does;
     here 400 small batches alternate between TWO streams, so the batch that reuses a slot is not ordered behind the one that used
     it before except by that protocol: the counter must be back at zero (and visible) before the host can see the slot free --
@@ -461,3 +461,96 @@ def test_staging_ring_reused_across_two_streams_under_host_polling(dev):
     assert rel_rms(mix, ref_mix) <= 1e-5
     bad = got.rw_equal(ref_bank)
     assert not bad, bad
+
+
+def test_staging_ring_serves_every_call_family_back_to_back(dev):
+    """The batch path (skred_bank_stage.c) is the one way a host-written batch reaches a kernel, whatever the call: 3 x SK_UPD_RING
+    = 24 staged calls of eleven kinds go to bank A back to back on one stream -- every slot of the ring is reused twice, by a call
+    of another family, under nothing but the completion-word protocol -- and to bank B with a device synchronise after each.
+    Everything the calls write must be the same, byte for byte.  32768 voices with K = 1 slots: the smallest bank at which the
+    bank-wide ctl_range (32768 lanes > 64 * 256) and find_owned (32768 slots > 64 * 256) read the slot's device twin behind a copy,
+    while the eight-entry calls read the pinned buffer itself.  Voice i carries the tag i + 1 for i < 1024."""
+    import time
+    import torch
+    n, ring, E = 32768, 8, 8
+    bank, tables, g = banks.bank_c2(n)
+    REL = dev.STAMP_RELEASE
+
+    def i32(values):
+        return torch.tensor(np.asarray(values, np.int64).astype(np.int32), dtype=torch.int32, device="cuda")
+
+    def run(sync_each):
+        db = dev.DeviceBank(n)
+        db.set_tables(tables)
+        host = bank.copy()
+        db.upload(host)
+        db.set_globals(g)
+        db.render_host(64, 2, 0)                                  # synth_sample_count = 64: what the stamps and the notes store
+        keep, results, found = [i32(np.arange(1024))], [], []
+        db.tag_slots(keep[0].data_ptr(), np.arange(1, 1025), 1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for k in range(3 * ring):
+            ids = np.arange(E) * 97 + 13 * k                      # eight voices below 1024: voice v carries the tag v + 1
+            lst, cnt, res = i32(ids), i32([E]), torch.zeros(3, dtype=torch.int32, device="cuda")
+            val = float(np.float32(0.001 * (k + 1)))
+            notes = [dev.NoteC(val, 0.5 + val, 0.25, val, 1.0 - val, dev.NOTE_SET_PHASE | dev.NOTE_SET_PAN) for _ in range(E)]
+            pan = [dev.ctl(dev.CTL_PAN, pan_left=val, pan_right=2 * val)]
+            kind = k % 11
+            if kind == 0:
+                vs = (2048 + ids).astype(np.int32)
+                host["voice_phase_inc"][vs] = np.float32(val)
+                db.update(host, vs, dev.DIRTY_PARAMS)
+            elif kind == 1:
+                db.notes_on_list(notes, lst.data_ptr(), cnt.data_ptr(), 0, 0, res.data_ptr())
+            elif kind == 2:
+                db.notes_on_slots(notes, 1, 1, lst.data_ptr(), cnt.data_ptr(), 0, 0, res.data_ptr())
+            elif kind == 3:
+                db.ctl_slots(pan, 1, lst.data_ptr(), E, 0, res.data_ptr())
+            elif kind == 4:
+                db.ctl_range([dev.ctl(dev.CTL_PAN_DEPTH, pan_depth=val)], 0, n, 1, res.data_ptr())
+            elif kind == 5:
+                keep.append(i32(4096 + ids))
+                db.tag_slots(keep[-1].data_ptr(), 5000 + ids, 1, 0, res.data_ptr())
+            elif kind == 6:
+                out = torch.full((E,), -7, dtype=torch.int32, device="cuda")
+                db.find_owned(0, n, 1, np.concatenate([ids[:6] + 1, [5000 + 13 * 5, 77777]]), out.data_ptr())
+                found.append(out)
+            elif kind == 7:
+                db.stamp_owned(lst.data_ptr(), ids + 1, 1, 1, REL, res.data_ptr())
+            elif kind == 8:
+                db.ctl_owned(pan, 1, lst.data_ptr(), ids + 1, 0, res.data_ptr())
+            elif kind == 9:
+                db.ctl_match([dev.ctl(dev.CTL_AM_DEPTH, am_depth=val)], 0, n, 1, dev.owner_match(k & 3, 3), res.data_ptr())
+            else:
+                each = [dev.ctl_each(dev.EACH_VELOCITY, velocity=val + 0.01 * j) for j in range(E)]
+                db.ctl_owned_each(pan, each, 1, lst.data_ptr(), ids + 1, 1, 0, res.data_ptr())
+            keep.append((lst, cnt))
+            results.append(res)
+            if sync_each:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        took = time.perf_counter() - t0
+        got = bank.copy()
+        db.download(got)
+        db.download_ctl(got)
+        owners, clocks = db.download_owners(), db.download_env_clocks()
+        mix, _ = db.render_host(64, 2, 0)
+        db.close()
+        return dict(took=took, bank=got, owners=owners, clocks=clocks, mix=mix, results=[r.cpu().numpy() for r in results],
+                    found=[f.cpu().numpy() for f in found])
+
+    a, b = run(False), run(True)
+    assert a["took"] < 4.0, "a call sat out the staging ring's time limit"
+    differ = [name for name in a["bank"].a if a["bank"].a[name].tobytes() != b["bank"].a[name].tobytes()]
+    assert not differ, differ
+    assert a["owners"].tobytes() == b["owners"].tobytes()
+    assert a["clocks"][0].tobytes() == b["clocks"][0].tobytes() and a["clocks"][1].tobytes() == b["clocks"][1].tobytes()
+    for k, (ra, rb) in enumerate(zip(a["results"], b["results"])):
+        assert ra.tobytes() == rb.tobytes(), (k, ra, rb)
+    assert len(a["found"]) == 2 and all(fa.tobytes() == fb.tobytes() for fa, fb in zip(a["found"], b["found"]))
+    assert a["mix"].tobytes() == b["mix"].tobytes()
+    # the calls did what they say: nothing above compares two banks that both stood still
+    assert int(a["owners"][4096 + 13 * 5]) == 5000 + 13 * 5 and a["found"][0].tolist()[:6] == (np.arange(6) * 97 + 13 * 6).tolist()
+    assert a["found"][0].tolist()[6:] == [4096 + 13 * 5, -1] and a["results"][1].tolist()[:2] == [E, 0]
+    assert float(a["bank"]["voice_pan_mod_depth"][n - 1]) == float(np.float32(0.001 * 16)) and a["results"][4].tolist()[0] == n
