@@ -912,8 +912,9 @@ int  skred_bank_download_env_clocks(skred_bank_t *bank, uint64_t *sample_start, 
  * the same state gives the same bytes whatever order the workgroups arrive in.  One stream at a time per bank, as for the queries.
  * No render kernel, probe, tap or report reads anything these calls add; what the writing calls tell the planner is what their
  * unguarded twins tell it (below).
- * Out of scope: the fixed-point bank, the drop-in mode, deferred items and pattern steps (they carry no tags), per-entry filter
- * coefficients.  On a shard: through skred_shard_bank(), with that rank's local indices, and nothing beyond that.
+ * The fixed-point bank has the same calls per voice (include/skred_amd_fxpt.h: skred_fxbank_find_match / _stamp_match / _ctl_match /
+ * _ctl_owned_each / _ctl_tags_each, with this section's skred_owner_match_t and SKRED_EACH_* bits).
+ * Out of scope: the drop-in mode, deferred items and pattern steps (they carry no tags), per-entry filter coefficients.  On a shard: through skred_shard_bank(), with that rank's local indices, and nothing beyond that.
  *
  * A. Masked owner matches.  A slot MATCHES m when owner != 0 && (owner & m->mask) == m->value: mask 0 with value 0 is every tagged
  * slot, mask 0xFF000000 a channel byte, mask 0xFFFFFFFF one note.  An untagged slot matches nothing. */

@@ -59,6 +59,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include "skred_amd.h"   /* skred_owner_match_t and the SKRED_EACH_* bits, shared with the float bank */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -353,6 +355,105 @@ int  skred_fxbank_ctl_list(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const 
 int  skred_fxbank_ctl_owned(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const int32_t *d_voices, const uint32_t *tags, int n,
                             const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
 int  skred_fxbank_download_params(skred_fxbank_t *fx, skred_fxpt_bank_t *host, uint32_t *recip_out, int src_first, int dst_first, int count);
+
+/* ---- channels and per-note expression: masked owner matches, per-entry controller values -----------------------------------
+ *
+ * The fixed-point twin of the float bank's section of the same name (include/skred_amd.h: skred_bank_find_match .. _ctl_tags_each),
+ * with the same vocabulary: a host that tags notes as channel << 24 | note id has "all notes off on channel 3", "mod wheel on
+ * channel 3", "how many notes does channel 3 hold" and n different bends on n notes as ONE device call each, instead of
+ * skred_fxbank_download_owners behind a device wait, a pick on the host and an uploaded list, or n skred_fxbank_ctl_owned calls.
+ * This bank has no slots: everything is per voice (the float calls at K = 1, voice_mask = 1).
+ *
+ * Every call is asynchronous on the caller's stream and ordered like skred_fxbank_update; host arrays travel through the ring of
+ * SKRED_FX_RING_SLOTS staging slots, so the caller's memory is free on return and nothing waits for the device -- except
+ * skred_fxbank_find_match_host, which waits for its stream ONLY.  The owner array is the one of the section above, allocated by the
+ * first call that needs it exactly as there; these calls read it and never write it.  No render kernel reads anything these calls
+ * add: a bank that makes match queries renders the blocks of a bank that makes none, bit for bit.  Every refusal comes before
+ * anything touches the device.  One stream at a time per bank, as for the queries (the list shares their scratch).  On a shard:
+ * through skred_fxshard_bank(), with that rank's local indices.
+ * Out of scope: slots (K > 1), the deferred queue and pattern steps, the drop-in mode, per-entry filter coefficients.
+ *
+ * A. Masked matches.  skred_owner_match_t and skred_owner_match_check are the float bank's, as they are.  A voice MATCHES m when
+ * owner != 0 && (owner & m->mask) == m->value: mask 0 with value 0 is every tagged voice, mask 0xFF000000 a channel byte, mask
+ * 0xFFFFFFFF one note.  An untagged voice matches nothing.
+ *
+ * skred_fxbank_find_match       the matching voices of [first, first + count), ascending, into d_voices[0 .. min(total, max_out))
+ *                               (device int32); d_count[0] (device uint32[1]) = the TOTAL, whether or not the list was cut short.
+ *                               max_out == 0: the count alone (d_voices may be NULL).  Entries past min(total, max_out) are not
+ *                               written.  The same state gives the same bytes: the compaction is ordered by index, no workgroup
+ *                               waits for another, and it is the float bank's (sk_match_count_kernel / _scatter_kernel) on the
+ *                               scratch of skred_fxbank_find_idle.  SKRED_E_BAD_ARG: NULL bank, match or d_count, what
+ *                               skred_owner_match_check refuses, max_out < 0, NULL d_voices with max_out > 0; SKRED_E_RANGE:
+ *                               count <= 0 or a range outside the bank.
+ * skred_fxbank_find_match_host  the same into host memory, waiting for `stream` only: returns the number of voices written to
+ *                               voices[0 .. max_out) or a negative SKRED_E_* code; *total_out (may be NULL) = the total.
+ * skred_fxbank_stamp_match      skred_fxbank_stamp_list's stores on EVERY matching voice of the range -- all notes off on a channel
+ *                               -- in one pass, with no list in between; `now` is the bank's sample count at the call.  d_result
+ *                               (device uint32[2], required), cleared on the stream ahead of the kernel: [0] voices stamped,
+ *                               [1] voices of the range that did not match.  Refusals of _find_match about bank, match and range;
+ *                               SKRED_E_BAD_ARG for a NULL d_result, no or unknown stamp bits.
+ * skred_fxbank_ctl_match        skred_fxbank_ctl_range under the match guard: the same stores, the same two withheld-store rules,
+ *                               on the matching voices only.  d_result (device uint32[3], may be NULL): [0] voices written,
+ *                               [1] stores withheld, [2] voices of the range that did not match.  Refused: what skred_fx_ctl_check
+ *                               and skred_owner_match_check refuse, a NULL bank; SKRED_E_RANGE as for _find_match.
+ *
+ * B. Per-entry controller values.  skred_fxbank_ctl_owned stores ONE record on all n listed notes; here entry k of the list brings a
+ * small record of its own (skred_fx_ctl_each_t, `set` made of the float bank's SKRED_EACH_* bits, reserved words 0), whose named
+ * values replace or scale the record's for that entry alone.  Exact integer arithmetic, field by field:
+ *   SKRED_EACH_INC_SCALE  phase_inc = ((uint64)phase_inc * inc_scale_q16) >> 16 on the DEVICE's value, the product in 64 bits,
+ *                         65536 = 1.0 -- SKRED_CTL_INC_SCALE's rule: a result above 0xFFFFFFFF is NOT stored (the voice keeps its
+ *                         increment) and is counted in d_result[1]; exactly 0xFFFFFFFF is stored.  Per-note pitch bend.
+ *   SKRED_EACH_AMP_SCALE  needs the record to name SKRED_CTL_AMP: the amp stored is ((uint64)ctl->amp_q15 * amp_scale_q16) >> 16,
+ *                         under SKRED_CTL_AMP's device-side guard (a voice whose amp_q15 is 0 keeps it and is counted).  A result
+ *                         of 0 or above 65535 is withheld and counted in d_result[1], and the voice's amp is left alone -- the amp
+ *                         guard then does not look at the voice, so it cannot count it a second time; exactly 1 and exactly 65535
+ *                         are stored.  amp_scale_q16 == 0 is refused.  Polyphonic aftertouch.
+ *   SKRED_EACH_VELOCITY   the entry's velocity_q15 (0..65535) replaces the record's, or supplies it where the record does not
+ *                         name the field.
+ *   SKRED_EACH_PAN        the same for pan_left_q15, pan_right_q15, each 0..65535.
+ * The withheld stores add up to at most 2 per voice (one for the increment, one for the amp).  Everything else the record names is
+ * stored as skred_fxbank_ctl_owned stores it.  `ctl` may be NULL: no base record, the entries supply everything (AMP_SCALE is then
+ * refused).
+ *
+ * skred_fx_ctl_each_check       pure host: SKRED_OK, or SKRED_E_BAD_ARG for NULL each, n < 0; with ctl != NULL what
+ *                               skred_fx_ctl_check refuses; in an entry: unknown bits in set, set == 0, a non-zero reserved word, a
+ *                               named value outside its range, amp_scale_q16 == 0 under AMP_SCALE; AMP_SCALE where ctl is NULL or
+ *                               does not name SKRED_CTL_AMP; INC_SCALE where ctl names SKRED_CTL_PHASE_INC or SKRED_CTL_INC_SCALE.
+ *                               Values an entry does not name are not looked at (and never shipped).
+ * skred_fxbank_ctl_owned_each   entry k (of the first min(n, *d_count_or_null)) acts only if d_voices[k] lies in [0, n_voices) AND
+ *                               owner[voice] == tags[k] (non-zero); -1 holes and entries outside the bank are skipped.  On that
+ *                               voice it performs skred_fxbank_ctl_owned's stores with each[k] laid over the record.  d_result
+ *                               (device uint32[3], may be NULL): [0] voices written, [1] stores withheld (the two guards and the
+ *                               amp products), [2] voices whose owner differs.  A voice listed twice gets the absolute stores twice;
+ *                               a scaled increment on such a voice is UNSPECIFIED, as for skred_fxbank_ctl_list.  Refused: what
+ *                               skred_fx_ctl_each_check refuses, NULL bank, list or tags, a zero tag, n > INT32_MAX / 64.
+ *                               n == 0: SKRED_OK, nothing is done.
+ * skred_fxbank_ctl_tags_each    expression by note id: skred_fxbank_find_owned of the tags over [first, first + count) into the
+ *                               scratch of skred_fxbank_release_tags, then the call above on that list -- built as _release_tags
+ *                               is.  each[k] goes with tags[k]: the tags travel sorted, and the entries are permuted with them on
+ *                               the host.  Tags unique, none zero, n <= SKRED_OWNER_MAX_TAGS; each tag reaches at most ONE voice,
+ *                               the lowest that carries it.  d_result as above; [2] is 0 (a tag nobody carries is a -1 entry and
+ *                               is not counted).  Refusals of both calls.
+ * LIMIT, as for the controllers: the host view goes stale; skred_fxbank_download_params reads the values back. */
+typedef struct skred_fx_ctl_each {        /* 32 bytes */
+  uint32_t set;                           /* SKRED_EACH_* of the values below */
+  uint32_t inc_scale_q16, amp_scale_q16;
+  int32_t  velocity_q15, pan_left_q15, pan_right_q15;
+  uint32_t reserved[2];                   /* 0 */
+} skred_fx_ctl_each_t;
+int  skred_fxbank_find_match(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, int max_out, int32_t *d_voices,
+                             uint32_t *d_count, void *stream);
+int  skred_fxbank_find_match_host(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, int max_out, int32_t *voices,
+                                  int *total_out, void *stream);
+int  skred_fxbank_stamp_match(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, uint32_t stamps, uint32_t *d_result,
+                              void *stream);
+int  skred_fxbank_ctl_match(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int first, int count, const skred_owner_match_t *m,
+                            uint32_t *d_result, void *stream);
+int  skred_fx_ctl_each_check(const skred_fx_ctl_each_t *each, int n, const skred_fx_ctl_t *ctl);
+int  skred_fxbank_ctl_owned_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const int32_t *d_voices,
+                                 const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+int  skred_fxbank_ctl_tags_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, int first, int count,
+                                const uint32_t *tags, int n, uint32_t *d_result, void *stream);
 
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);

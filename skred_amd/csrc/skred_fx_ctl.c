@@ -26,7 +26,7 @@ _Static_assert(sizeof(skred_fx_ctl_t) == sizeof(skx_ctl_t) && sizeof(skred_fx_ct
                offsetof(skred_fx_ctl_t, velocity_q15) == 4 * SKX_CTL_VELOCITY && offsetof(skred_fx_ctl_t, smoother_k_q15) == 4 * SKX_CTL_SMOOTHING &&
                offsetof(skred_fx_ctl_t, reserved) == 4 * SKX_CTL_RECIP_A,
                "the device's controller record must be skred_fx_ctl_t word for word");
-/* the kernels spell the public bits out (skred_fx_ctl_kernels.hip: SKX_C_*) */
+/* the kernels spell the public bits out (skred_fx_ctl_common.hpp: SKX_C_*) */
 _Static_assert(SKRED_CTL_PHASE_INC == 1u << 0 && SKRED_CTL_INC_SCALE == 1u << 1 && SKRED_CTL_AMP == 1u << 2 && SKRED_CTL_PAN == 1u << 3 &&
                SKRED_CTL_FILTER == 1u << 4 && SKRED_CTL_ENV_TIMES == 1u << 5 && SKRED_CTL_VELOCITY == 1u << 6 && SKRED_CTL_SMOOTHING == 1u << 7,
                "device controller bits must equal the public SKRED_CTL_* values");

@@ -22,51 +22,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "skred_fx_ctl_common.hpp"   // skx_list_looked, skx_count
+#include "skred_fx_ctl_common.hpp"   // skx_ctl_store, skx_ctl_planes_t, skx_list_looked, skx_count
 #include "skred_fx_layout.h"
-
-// the public bit values (include/skred_amd.h: SKRED_CTL_*; checked against the header in skred_fx_ctl.c)
-enum { SKX_C_PHASE_INC = 1u << 0, SKX_C_INC_SCALE = 1u << 1, SKX_C_AMP = 1u << 2, SKX_C_PAN = 1u << 3, SKX_C_FILTER = 1u << 4,
-       SKX_C_ENV_TIMES = 1u << 5, SKX_C_VELOCITY = 1u << 6, SKX_C_SMOOTHING = 1u << 7 };
-
-struct skx_ctl_planes_t {
-  skx_plane_t *osc, *gain, *env, *recip, *filt, *filt2;
-};
-
-// The stores of record r on voice v.  Returns the stores withheld by the two guards (0, 1 or 2).
-__device__ __forceinline__ uint32_t skx_ctl_store(const skx_ctl_planes_t &p, int v, const uint32_t *__restrict__ r) {
-  const uint32_t which = r[SKX_CTL_WHICH];
-  uint32_t withheld = 0;
-  if (which & (SKX_C_PHASE_INC | SKX_C_INC_SCALE | SKX_C_AMP)) {
-    uint4 o = *reinterpret_cast<const uint4 *>(&p.osc[v]);          // w[1] the table offset, w[2] log2_size and the flags: kept
-    if (which & SKX_C_PHASE_INC) o.x = r[SKX_CTL_PHASE_INC];
-    if (which & SKX_C_INC_SCALE) {
-      const uint64_t prod = ((uint64_t)o.x * (uint64_t)r[SKX_CTL_INC_SCALE]) >> 16;
-      if (prod <= 0xFFFFFFFFull) o.x = (uint32_t)prod; else ++withheld;
-    }
-    if (which & SKX_C_AMP) {
-      if (o.w != 0u) o.w = r[SKX_CTL_AMP]; else ++withheld;
-    }
-    *reinterpret_cast<uint4 *>(&p.osc[v]) = o;
-  }
-  if (which & (SKX_C_PAN | SKX_C_VELOCITY | SKX_C_SMOOTHING)) {
-    uint4 g = *reinterpret_cast<const uint4 *>(&p.gain[v]);
-    if (which & SKX_C_PAN) { g.x = r[SKX_CTL_PAN_LEFT]; g.y = r[SKX_CTL_PAN_RIGHT]; }
-    if (which & SKX_C_SMOOTHING) g.z = r[SKX_CTL_SMOOTHING];
-    if (which & SKX_C_VELOCITY) g.w = r[SKX_CTL_VELOCITY];
-    *reinterpret_cast<uint4 *>(&p.gain[v]) = g;
-  }
-  if (which & SKX_C_FILTER) {                                          // (all four words of SKX_FILT are named: nothing to read)
-    *reinterpret_cast<uint4 *>(&p.filt[v]) = make_uint4(r[SKX_CTL_B0], r[SKX_CTL_B1], r[SKX_CTL_B2], r[SKX_CTL_A1]);
-    p.filt2[v].w[0] = r[SKX_CTL_A2];
-  }
-  if (which & SKX_C_ENV_TIMES) {
-    *reinterpret_cast<uint4 *>(&p.env[v]) = make_uint4(r[SKX_CTL_ATTACK], r[SKX_CTL_DECAY], r[SKX_CTL_RELEASE], r[SKX_CTL_SUSTAIN]);
-    *reinterpret_cast<uint2 *>(&p.recip[v].w[0]) = make_uint2(r[SKX_CTL_RECIP_A], r[SKX_CTL_RECIP_D]);
-    p.recip[v].w[2] = r[SKX_CTL_RECIP_R];
-  }
-  return withheld;
-}
 
 __global__ __launch_bounds__(SKX_CTL_SPAN) void sk_fx_ctl_range_kernel(const skx_ctl_t *__restrict__ rec, int first, int count,
                                                                        skx_ctl_planes_t p, uint32_t *d_result) {
@@ -100,10 +57,6 @@ __global__ __launch_bounds__(SKX_CTL_SPAN) void sk_fx_ctl_list_kernel(const skx_
     const uint32_t val[2] = { mine ? 1u : 0u, withheld };
     skx_count<2>(sums, d_result, val);
   }
-}
-
-static void skx_ctl_planes(skx_ctl_planes_t &p, skx_plane_t *const ro[SKX_COUNT]) {
-  p.osc = ro[SKX_OSC]; p.gain = ro[SKX_GAIN]; p.env = ro[SKX_ENV]; p.recip = ro[SKX_RECIP]; p.filt = ro[SKX_FILT]; p.filt2 = ro[SKX_FILT2];
 }
 
 extern "C" int skx_launch_ctl_range(const skx_ctl_t *d_rec, int first, int count, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result,

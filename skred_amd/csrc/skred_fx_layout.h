@@ -108,4 +108,18 @@ enum { SKX_CTL_WHICH = 0, SKX_CTL_PHASE_INC, SKX_CTL_INC_SCALE, SKX_CTL_AMP, SKX
        SKX_CTL_SUSTAIN, SKX_CTL_VELOCITY, SKX_CTL_SMOOTHING, SKX_CTL_RECIP_A, SKX_CTL_RECIP_D, SKX_CTL_RECIP_R, SKX_CTL_WORDS };
 typedef struct { uint32_t w[SKX_CTL_WORDS]; } skx_ctl_t;     /* 80 bytes */
 #define SKX_CTL_SPAN 256           /* voices or entries (and threads) per workgroup of the controller and guarded-stamp kernels */
+
+/* ---- channels and per-note expression (skred_fx_expr_kernels.hip; include/skred_amd_fxpt.h: skred_fxbank_find_match / _stamp_match /
+ * _ctl_match / _ctl_owned_each / _ctl_tags_each) ----
+ * the device's image of skred_fx_ctl_each_t, word for word; the bits equal SKRED_EACH_* (checked in skred_fx_expr.c).  Values an
+ * entry does not name arrive zeroed */
+#define SKX_EACH_INC_SCALE (1u << 0)
+#define SKX_EACH_AMP_SCALE (1u << 1)
+#define SKX_EACH_VELOCITY  (1u << 2)
+#define SKX_EACH_PAN       (1u << 3)
+#define SKX_EACH_ALL       ((1u << 4) - 1u)
+enum { SKX_EACH_SET = 0, SKX_EACH_W_INC_SCALE, SKX_EACH_W_AMP_SCALE, SKX_EACH_W_VELOCITY, SKX_EACH_W_PAN_LEFT, SKX_EACH_W_PAN_RIGHT,
+       SKX_EACH_WORDS = 8 };
+typedef struct { uint32_t w[SKX_EACH_WORDS]; } skx_each_t;   /* 32 bytes */
+#define SKX_EXPR_SPAN 256          /* voices or entries (and threads) per workgroup of the expression kernels */
 #endif

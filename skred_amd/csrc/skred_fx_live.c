@@ -191,15 +191,20 @@ static int idle_check_bank(const skred_fxbank_t *fx, const skred_fx_idle_query_t
   return SKRED_OK;
 }
 
+int skx_idle_scratch(skred_fxbank_t *fx, hipStream_t s) {
+  if (fx->d_idle) return SKRED_OK;
+  /* sized once, for the whole bank from any `first` (a range's spans start at `first` rounded down to 64) */
+  const int wgs = skx_idle_workgroups(63, fx->n_padded);
+  HIP_TRY(hipMalloc((void **)&fx->d_idle, ((size_t)SKX_IDLE_W_COUNT + 2 * (size_t)wgs) * sizeof(uint32_t)));
+  fx->idle_wgs = wgs;
+  HIP_TRY(hipMemsetAsync(fx->d_idle, 0, (size_t)SKX_IDLE_W_COUNT * sizeof(uint32_t), s));   /* the ticket: zero once, re-armed by every last arriver */
+  return SKRED_OK;
+}
+
 int skx_idle_launch(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
   HIP_TRY(hipSetDevice(fx->device));
-  if (!fx->d_idle) {
-    /* sized once, for the whole bank from any `first` (a range's spans start at `first` rounded down to 64) */
-    const int wgs = skx_idle_workgroups(63, fx->n_padded);
-    HIP_TRY(hipMalloc((void **)&fx->d_idle, ((size_t)SKX_IDLE_W_COUNT + 2 * (size_t)wgs) * sizeof(uint32_t)));
-    fx->idle_wgs = wgs;
-    HIP_TRY(hipMemsetAsync(fx->d_idle, 0, (size_t)SKX_IDLE_W_COUNT * sizeof(uint32_t), s));   /* the ticket: zero once, re-armed by every last arriver */
-  }
+  const int rc = skx_idle_scratch(fx, s);
+  if (rc) return rc;
   if (skx_idle_workgroups(q->first, q->count) > fx->idle_wgs) return fail(SKRED_E_RANGE, "fx find_idle: scratch too small");   /* (unreachable: sized above) */
   skx_idle_args_t a;
   memset(&a, 0, sizeof(a));
@@ -227,24 +232,27 @@ int skred_fxbank_find_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, i
   return skx_idle_launch(fx, q, d_voices, d_count, (hipStream_t)stream);
 }
 
+int skx_idle_out_room(skred_fxbank_t *fx, size_t need) {
+  if (fx->d_idle_out && need <= fx->idle_out_cap) return SKRED_OK;
+  /* (the previous call waited for its copy: nothing reads the old buffers) */
+  if (fx->d_idle_out) { (void)hipFree(fx->d_idle_out); fx->d_idle_out = NULL; }
+  if (fx->h_idle_out) { (void)hipHostFree(fx->h_idle_out); fx->h_idle_out = NULL; }
+  fx->idle_out_cap = 0;
+  size_t cap = 1024;
+  while (cap < need) cap *= 2;
+  HIP_TRY(hipMalloc((void **)&fx->d_idle_out, (2 + cap) * sizeof(int32_t)));
+  HIP_TRY(hipHostMalloc((void **)&fx->h_idle_out, (2 + cap) * sizeof(int32_t), hipHostMallocDefault));
+  fx->idle_out_cap = cap;
+  return SKRED_OK;
+}
+
 int skred_fxbank_find_idle_host(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *voices, int *total_out, void *stream) {
   int dummy = 0;
   int rc = idle_check_bank(fx, q, voices, &dummy, "fx find_idle_host");
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
-  const size_t need = (size_t)q->max_out;
-  if (!fx->d_idle_out || need > fx->idle_out_cap) {
-    /* (the previous call waited for its copy: nothing reads the old buffers) */
-    if (fx->d_idle_out) { (void)hipFree(fx->d_idle_out); fx->d_idle_out = NULL; }
-    if (fx->h_idle_out) { (void)hipHostFree(fx->h_idle_out); fx->h_idle_out = NULL; }
-    fx->idle_out_cap = 0;
-    size_t cap = 1024;
-    while (cap < need) cap *= 2;
-    HIP_TRY(hipMalloc((void **)&fx->d_idle_out, (2 + cap) * sizeof(int32_t)));
-    HIP_TRY(hipHostMalloc((void **)&fx->h_idle_out, (2 + cap) * sizeof(int32_t), hipHostMallocDefault));
-    fx->idle_out_cap = cap;
-  }
+  if ((rc = skx_idle_out_room(fx, (size_t)q->max_out))) return rc;
   rc = skx_idle_launch(fx, q, fx->d_idle_out + 2, (uint32_t *)fx->d_idle_out, s);
   if (rc) return rc;
   const int written = sk_read_back(fx->d_idle_out, fx->h_idle_out, q->max_out, q->max_out, voices, s, "fx find_idle_host");

@@ -28,13 +28,14 @@ static int tags_check(const uint32_t *tags, int n, uint32_t flags, const char *w
 int skx_owner_ensure(skred_fxbank_t *fx) {
   if (fx->d_owner) return SKRED_OK;
   uint32_t *p = NULL;
-  const size_t words = (size_t)fx->n_voices + SKRED_OWNER_MAX_TAGS;
+  const size_t words = (size_t)fx->n_voices + SKRED_OWNER_MAX_TAGS + 2;   /* the owners, _release_tags' list, _find_match's pair */
   HIP_TRY(hipMalloc((void **)&p, words * sizeof(uint32_t)));
   hipError_t e = hipMemset(p, 0, words * sizeof(uint32_t));
   if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
   if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "fx owner array -> %s", hipGetErrorString(e)); }
   fx->d_owner = p;
   fx->d_owner_found = (int32_t *)(p + fx->n_voices);
+  fx->d_match_pair = p + fx->n_voices + SKRED_OWNER_MAX_TAGS;
   return SKRED_OK;
 }
 
@@ -42,6 +43,7 @@ void skx_owner_free(skred_fxbank_t *fx) {
   if (fx->d_owner) (void)hipFree(fx->d_owner);
   fx->d_owner = NULL;
   fx->d_owner_found = NULL;
+  fx->d_match_pair = NULL;
 }
 
 /* what a staged launch ends in: the slot's event behind everything that reads its twin, then the launch's own verdict */

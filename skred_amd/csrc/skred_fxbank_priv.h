@@ -1,6 +1,6 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
  * skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c: voice stealing; skred_fx_owner.c: note owners;
- * skred_fx_ctl.c: controllers). */
+ * skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -51,6 +51,7 @@ struct skred_fxbank {
   int32_t *d_steal_out, *h_steal_out;        /* [2] counts, then SK_STEAL_MAX victims: _find_steal_host's list and _note_on_steal's */
   uint32_t *d_owner;                         /* note owners (skred_fx_owner.c): one word per voice, 0 nobody; NULL until the first call that needs it */
   int32_t *d_owner_found;                    /* ... and behind it skred_fxbank_release_tags' list, SKRED_OWNER_MAX_TAGS entries */
+  uint32_t *d_match_pair;                    /* ... and behind that the two words the count pass of skred_fxbank_find_match fills */
   long long *d_mix; size_t mix_cap;
   int32_t *d_stems; size_t stems_cap;
   uint64_t count;
@@ -82,6 +83,10 @@ int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, h
 /* ... for skred_fxbank_note_on_steal: the idle query's launches (q checked by the caller), room for n entries in d_note_list, and
  * the checked notes through a staging slot into the placement kernel */
 int skx_idle_launch(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s);
+/* ... for skred_fxbank_find_match too: the query scratch (SKX_IDLE_W_COUNT words, idle_wgs counts, idle_wgs offsets; allocated once,
+ * for the whole bank, the words zeroed on `s`), and room for 2 + need entries in d_idle_out / h_idle_out */
+int skx_idle_scratch(skred_fxbank_t *fx, hipStream_t s);
+int skx_idle_out_room(skred_fxbank_t *fx, size_t need);
 int skx_note_list_room(skred_fxbank_t *fx, int n);
 int skx_notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
                      int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s);
@@ -100,6 +105,9 @@ void skx_owner_free(skred_fxbank_t *fx);
 int skx_owner_ensure(skred_fxbank_t *fx);
 /* skred_fx_ctl.c: the checked record as it travels (the reserved words carry the reciprocals).  Pure host */
 void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
+/* skred_fx_expr.c: the checked entries as they travel -- out[j] = each[perm[j]] (perm NULL: j), the named values word for word, the
+ * others zeroed.  Pure host */
+void skx_each_pack(const skred_fx_ctl_each_t *each, int n, const uint32_t *perm, skx_each_t *out);
 /* skred_bank_owner.c: the find pass's view of n <= SKRED_OWNER_MAX_TAGS tags (sorted ascending as unsigned numbers, and where each stood) */
 int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
 /* skred_bank_checks.c, the float bank's argument checks this bank shares (`who`: the entry point, with its "fx " in front): the stamp
@@ -132,5 +140,13 @@ int skx_launch_ctl_range(const skx_ctl_t *d_rec, int first, int count, skx_plane
                          hipStream_t stream);
 int skx_launch_ctl_list(const skx_ctl_t *d_rec, const int32_t *d_voices, const uint32_t *d_tags, const uint32_t *owner, int n,
                         const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
+/* skred_fx_expr_kernels.hip (the ordered list of the matches is the float bank's sk_launch_match_find, skred_launch.h) */
+int skx_launch_match_stamps(const uint32_t *owner, uint32_t value, uint32_t mask, int first, int count, uint32_t stamps,
+                            skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, uint32_t *d_result, hipStream_t stream);
+int skx_launch_ctl_match(const skx_ctl_t *d_rec, int first, int count, const uint32_t *owner, uint32_t value, uint32_t mask,
+                         skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
+int skx_launch_ctl_owned_each(const skx_ctl_t *d_rec, const skx_each_t *d_each, const int32_t *d_voices, const uint32_t *d_tags,
+                              const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT],
+                              uint32_t *d_result, hipStream_t stream);
 
 #endif

@@ -23,8 +23,8 @@
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
  * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c, skred_bank_ctl.c, skred_bank_owner.c, skred_bank_expr.c and
- * skred_recorder.c (sk_launch_owner_tag, sk_launch_owner_find and sk_launch_list_append by the fixed-point bank's skred_fx_owner.c and
- * skred_fx_steal.c too).  A launcher that takes `cnt, done, seq` gets them from the batch path (skred_bank_stage.c: sk_batch_send).
+ * skred_recorder.c (sk_launch_owner_tag, sk_launch_owner_find, sk_launch_match_find and sk_launch_list_append by the fixed-point
+ * bank's skred_fx_owner.c, skred_fx_expr.c and skred_fx_steal.c too).  A launcher that takes `cnt, done, seq` gets them from the batch path (skred_bank_stage.c: sk_batch_send).
  */
 #ifndef SKRED_LAUNCH_H
 #define SKRED_LAUNCH_H

@@ -11,7 +11,7 @@ from typing import Dict, Optional, Tuple
 import numpy as np
 
 from . import banks
-from .device import SkredAmdError, _check, load
+from .device import OwnerMatchC, SkredAmdError, _check, load
 
 U32, I32, U64 = np.dtype("<u4"), np.dtype("<i4"), np.dtype("<u8")
 FX_FIELDS = [
@@ -39,8 +39,11 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_tag_list", "skred_fxbank_find_owned", "skred_fxbank_stamp_owned", "skred_fxbank_release_tags",
                   "skred_fxbank_owner_clear", "skred_fxbank_download_owners", "skred_fxbank_ctl_range", "skred_fxbank_ctl_list",
                   "skred_fxbank_ctl_owned", "skred_fxbank_download_params",
+                  "skred_fxbank_find_match", "skred_fxbank_find_match_host", "skred_fxbank_stamp_match", "skred_fxbank_ctl_match",
+                  "skred_fxbank_ctl_owned_each", "skred_fxbank_ctl_tags_each",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
-FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check"]      # pure host: no bank, no device
+FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
+                       "skred_fx_ctl_each_check"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -55,6 +58,9 @@ OWNER_MAX_TAGS, OWNER_ALLOW_ZERO, OWNER_UNIQUE = 1024, 1, 2
 CTL_PHASE_INC, CTL_INC_SCALE, CTL_AMP, CTL_PAN, CTL_FILTER, CTL_ENV_TIMES, CTL_VELOCITY, CTL_SMOOTHING = 1, 2, 4, 8, 16, 32, 64, 128
 CTL_ALL = 255
 CTL_REFUSED = 0x3F00
+# channels and per-note expression: the float bank's SKRED_EACH_* bits
+EACH_INC_SCALE, EACH_AMP_SCALE, EACH_VELOCITY, EACH_PAN = 1, 2, 4, 8
+EACH_ALL = 15
 FX_CTL_SPAN = 256                                 # voices or entries per workgroup of the controller and guarded-stamp kernels
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
@@ -108,6 +114,37 @@ def fx_ctl(which: int, **values) -> FxCtlC:
 def fx_ctl_check(ctl: Optional[FxCtlC]) -> int:
     """skred_fx_ctl_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device."""
     return int(_bind(load()).skred_fx_ctl_check(C.byref(ctl) if ctl is not None else None))
+
+
+class FxCtlEachC(C.Structure):
+    """ctypes image of ``skred_fx_ctl_each_t`` (32 bytes)."""
+    _fields_ = [("set", C.c_uint32), ("inc_scale_q16", C.c_uint32), ("amp_scale_q16", C.c_uint32), ("velocity_q15", C.c_int32),
+                ("pan_left_q15", C.c_int32), ("pan_right_q15", C.c_int32), ("reserved", C.c_uint32 * 2)]
+
+
+def fx_each(set: int, **values) -> FxCtlEachC:
+    """One per-entry record: ``set`` (EACH_*) and the named values; everything else 0."""
+    e = FxCtlEachC()
+    e.set = int(set)
+    for k, v in values.items():
+        setattr(e, k, int(v))
+    return e
+
+
+def fx_each_array(entries):
+    """A contiguous ``FxCtlEachC`` array from a sequence of FxCtlEachC (a ctypes array of FxCtlEachC passes through)."""
+    if isinstance(entries, C.Array) and entries._type_ is FxCtlEachC:
+        return entries
+    entries = list(entries)
+    return (FxCtlEachC * len(entries))(*entries)
+
+
+def fx_ctl_each_check(entries, ctl: Optional[FxCtlC] = None, n: Optional[int] = None) -> int:
+    """skred_fx_ctl_each_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device.  ``entries`` None: a NULL array."""
+    arr = fx_each_array(entries) if entries is not None else None
+    n = (len(arr) if arr is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_ctl_each_check(C.cast(arr, C.c_void_p) if arr is not None else None, int(n),
+                                                      C.byref(ctl) if ctl is not None else None))
 
 
 def _tags(tags) -> np.ndarray:
@@ -223,6 +260,13 @@ def _bind(L):
     L.skred_fxbank_ctl_list.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     L.skred_fxbank_ctl_owned.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
     L.skred_fxbank_download_params.argtypes = [vp, C.POINTER(FxBankC), vp, i32, i32, i32]
+    L.skred_fxbank_find_match.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp]
+    L.skred_fxbank_find_match_host.argtypes = [vp, i32, i32, vp, i32, vp, C.POINTER(C.c_int), vp]
+    L.skred_fxbank_stamp_match.argtypes = [vp, i32, i32, vp, C.c_uint32, vp, vp]
+    L.skred_fxbank_ctl_match.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.skred_fx_ctl_each_check.argtypes = [vp, i32, vp]
+    L.skred_fxbank_ctl_owned_each.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_ctl_tags_each.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -446,6 +490,53 @@ class DeviceFxBank:
         recip = np.zeros((bank.n, 3), np.uint32)
         _check(self.L.skred_fxbank_download_params(self.h, C.byref(cb), recip.ctypes.data, 0, 0, bank.n), "skred_fxbank_download_params")
         return recip
+
+    # ---- channels and per-note expression: masked owner matches, per-entry controller values ----
+    def find_match(self, first: int, count: int, value: int, mask: int, max_out: int = 0, d_voices: int = 0, d_count: int = 0,
+                   stream: int = 0):
+        """The voices of the range with owner != 0 and (owner & mask) == value, ascending, into d_voices[0 .. min(total, max_out))
+        (int32, device memory); d_count[0] = the total (uint32)."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_find_match(self.h, int(first), int(count), C.byref(m), int(max_out), d_voices or None,
+                                              d_count or None, stream or None), "skred_fxbank_find_match")
+
+    def find_match_host(self, first: int, count: int, value: int, mask: int, max_out: Optional[int] = None, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the listed voices, total)."""
+        max_out = count if max_out is None else max_out
+        m = OwnerMatchC(int(value), int(mask))
+        out = np.empty(max(max_out, 0), np.int32)
+        total = C.c_int(0)
+        n = self.L.skred_fxbank_find_match_host(self.h, int(first), int(count), C.byref(m), int(max_out),
+                                                out.ctypes.data if max_out > 0 else None, C.byref(total), stream or None)
+        if n < 0:
+            _check(n, "skred_fxbank_find_match_host")
+        return out[:n].copy(), int(total.value)
+
+    def stamp_match(self, first: int, count: int, value: int, mask: int, stamps: int, d_result: int, stream: int = 0):
+        """stamp_list's stores on every matching voice of the range; d_result[0..1] = stamped, did not match (uint32)."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_stamp_match(self.h, int(first), int(count), C.byref(m), int(stamps), d_result or None,
+                                               stream or None), "skred_fxbank_stamp_match")
+
+    def ctl_match(self, ctl: FxCtlC, first: int, count: int, value: int, mask: int, d_result: int = 0, stream: int = 0):
+        """ctl_range under the match guard; d_result[0..2] = written, withheld, did not match (uint32, may be 0)."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_ctl_match(self.h, C.byref(ctl), int(first), int(count), C.byref(m), d_result or None,
+                                             stream or None), "skred_fxbank_ctl_match")
+
+    def ctl_owned_each(self, ctl: Optional[FxCtlC], entries, d_voices: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """ctl_owned with entry k's record laid over `ctl` (may be None); d_result[0..2] = written, withheld, owner differs."""
+        t, arr = _tags(tags), fx_each_array(entries)
+        _check(self.L.skred_fxbank_ctl_owned_each(self.h, C.byref(ctl) if ctl is not None else None, C.cast(arr, C.c_void_p),
+                                                  d_voices or None, t.ctypes.data, len(t), d_count or None, d_result or None,
+                                                  stream or None), "skred_fxbank_ctl_owned_each")
+
+    def ctl_tags_each(self, ctl: Optional[FxCtlC], entries, first: int, count: int, tags, d_result: int = 0, stream: int = 0):
+        """Expression by note id: entries[k] on the lowest voice of the range that carries tags[k]; d_result as ctl_owned_each's."""
+        t, arr = _tags(tags), fx_each_array(entries)
+        _check(self.L.skred_fxbank_ctl_tags_each(self.h, C.byref(ctl) if ctl is not None else None, C.cast(arr, C.c_void_p),
+                                                 int(first), int(count), t.ctypes.data, len(t), d_result or None, stream or None),
+               "skred_fxbank_ctl_tags_each")
 
 
 # ------------------------------------------------------------------ synthetic fixed-point bank

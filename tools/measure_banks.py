@@ -38,6 +38,10 @@
              channel beside ctl_range of the range and beside download_owners + numpy pick + list upload + ctl_slots; stamp_match
              beside that route ending in stamp_slots; 256 bends through one ctl_tags_each beside 256 ctl_owned calls; the 64-frame
              block after a filter-only ctl_match beside the steady block
+  fxexpr     the same on the FIXED-POINT bank: fxbank.bank_fx, 2^20 voices all sounding, tagged over 16 channels (medians of 12 with
+             minimum and maximum): ctl_match of one channel beside download_owners + numpy pick + list upload + ctl_list; stamp_match
+             beside that route ending in stamp_list; 256 bends through one ctl_tags_each beside 256 ctl_owned calls; the 64-frame
+             block after the ctl_match beside the steady block
   fxsteal    voice stealing on the FIXED-POINT bank: 2^20 voices of fxbank.bank_fx whose polyphony is used up but for 64 idle voices,
              a burst of 256 notes (medians of 12 with minimum and maximum): (a) skred_fxbank_note_on_steal between an event pair --
              stream time, and the time the call held the host; nothing is waited for; (b) the only route without it:
@@ -1281,8 +1285,68 @@ def expr():
     db.close()
 
 
+def fxexpr():
+    """Channels and per-note expression on bank_fx(2**20), every voice sounding and tagged over 16 channels (tag = channel << 24 |
+    voice + 1).  (a) a cutoff change on ONE channel: skred_fxbank_ctl_match beside the only per-channel route before it --
+    skred_fxbank_download_owners (a device wait), a pick in numpy, the list uploaded, skred_fxbank_ctl_list; (b) all notes off on one
+    channel: skred_fxbank_stamp_match beside that route ending in skred_fxbank_stamp_list; (c) 256 notes, 256 different bends: one
+    skred_fxbank_ctl_tags_each beside 256 skred_fxbank_ctl_owned calls; (d) the 64-frame block after (a) beside the steady block.
+    Medians of 12 with minimum and maximum; host time held, and stream time between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES = 1 << 20, 64, 16, 256
+    bank, pool, c0 = X.bank_fx(n)
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    everyone = torch.arange(n, dtype=torch.int32, device="cuda")
+    db.tag_list(everyone.data_ptr(), tags)
+    value, mask = 3 << 24, 0xFF000000
+    co = X.q30_coeffs(np.array([1]), np.array([900.0], np.float32), np.array([1.2], np.float32), 48000)
+    cut = X.fx_ctl(X.CTL_FILTER, **{k: int(x[0]) for k, x in co.items()})
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def parent_route(last):
+        own = db.download_owners()                                        # the device wait the channel calls were built to remove
+        lst = np.flatnonzero((own != 0) & ((own & np.uint32(mask)) == np.uint32(value))).astype(np.int32)
+        dl = torch.from_numpy(lst).cuda()
+        last(dl, len(lst))
+
+    def line(label, call, before=None, words=3):
+        ms, held = _fx_timed(call, before)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {dr.cpu().numpy().tolist()[:words]}")
+
+    retrig = lambda: db.stamp_list(everyone.data_ptr(), n, X.STAMP_TRIGGER)   # noqa: E731
+    print(f"fx {n} voices all sounding, tagged over {CHANNELS} channels ({n // CHANNELS} notes each)")
+    line("(a) cutoff of one channel, ctl_match", lambda: db.ctl_match(cut, 0, n, value, mask, dr.data_ptr()))
+    line("(a) the same, download_owners + numpy pick + list upload + ctl_list",
+         lambda: parent_route(lambda dl, k: db.ctl_list(cut, dl.data_ptr(), k, 0, dr.data_ptr())), None, 2)
+    line("(b) all notes off on one channel, stamp_match", lambda: db.stamp_match(0, n, value, mask, X.STAMP_RELEASE, dr.data_ptr()), retrig, 2)
+    line("(b) the same, download_owners + numpy pick + list upload + stamp_list",
+         lambda: parent_route(lambda dl, k: db.stamp_list(dl.data_ptr(), k, X.STAMP_RELEASE)), retrig, 0)
+    note_tags = tags[2::CHANNELS * 7][:NOTES].copy()
+    bends = [X.fx_each(X.EACH_INC_SCALE, inc_scale_q16=int(round(65536 * 2.0 ** ((k % 25 - 12) / 1200.0)))) for k in range(NOTES)]
+    found = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    db.find_owned(0, n, note_tags, found.data_ptr())
+    torch.cuda.synchronize()
+    line(f"(c) {NOTES} notes, {NOTES} bends, one ctl_tags_each", lambda: db.ctl_tags_each(None, bends, 0, n, note_tags, dr.data_ptr()))
+
+    def one_by_one():
+        for k in range(NOTES):
+            db.ctl_owned(X.fx_ctl(X.CTL_INC_SCALE, inc_scale_q16=bends[k].inc_scale_q16), found.data_ptr() + 4 * k, note_tags[k:k + 1])
+    line(f"(c) the same, {NOTES} ctl_owned calls on a list that is already on the device", one_by_one, None, 0)
+    db.upload(bank)
+    _fx_block_after(db, out, F, None, 4)
+    steady = _fx_block_after(db, out, F)
+    after = _fx_block_after(db, out, F, lambda: db.ctl_match(cut, 0, n, value, mask))
+    print(f"  (d) the {F}-frame block after ctl_match of one channel: {_fx_stats(after)}; a steady block: {_fx_stats(steady)}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
