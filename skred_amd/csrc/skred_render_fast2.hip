@@ -265,9 +265,9 @@ __device__ __forceinline__ v2f fast2_osc(Fast2Regs &r, const char *lds_tab, cons
 // this frame's gain from r.gt (in-place instantiation); 7: as 3 with gain and pan folded into one constant per lane and
 // channel (fast2_fold_pan; sk_render_fast2_kernel's tame waves).  TAME: see fast_frame.
 template <bool FILTER, int EM, bool TAME, bool MIXED = false, bool MUTESEL = false, int FMP = 0>
-__device__ __forceinline__ void fast2_post(Fast2Regs &r, Env2Regs &e, v2f s, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
-                                           const bool rel0, const bool rel1, const bool silent0,
-                                           const bool silent1, float &out_l, float &out_r) {
+__device__ __forceinline__ void fast2_post_lr(Fast2Regs &r, Env2Regs &e, v2f s, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
+                                              const bool rel0, const bool rel1, const bool silent0,
+                                              const bool silent1, v2f &out_lr) {
   // ---- biquad, packed ----
   if (FILTER) {
     v2f y = r.b0 * s;
@@ -307,9 +307,7 @@ __device__ __forceinline__ void fast2_post(Fast2Regs &r, Env2Regs &e, v2f s, v2f
       if (r.probe[1]) { *r.probe[1] = make_float2(sg.y * r.pan0[1].x, sg.y * r.pan0[1].y); r.probe[1] += r.probe_stride; }
     }
 #endif
-    const v2f lr = __builtin_elementwise_fma(r.pan_lr[1], (v2f){so.y, so.y}, r.pan_lr[0] * (v2f){so.x, so.x});
-    out_l = lr.x;
-    out_r = lr.y;
+    out_lr = __builtin_elementwise_fma(r.pan_lr[1], (v2f){so.y, so.y}, r.pan_lr[0] * (v2f){so.x, so.x});
     return;
   }
   // ---- gain ----
@@ -384,7 +382,15 @@ __device__ __forceinline__ void fast2_post(Fast2Regs &r, Env2Regs &e, v2f s, v2f
     if (r.probe[1]) { *r.probe[1] = make_float2(s.y * r.pan_lr[1].x, s.y * r.pan_lr[1].y); r.probe[1] += r.probe_stride; }
   }
 #endif
-  const v2f lr = r.pan_lr[0] * (v2f){so.x, so.x} + r.pan_lr[1] * (v2f){so.y, so.y};
+  out_lr = r.pan_lr[0] * (v2f){so.x, so.x} + r.pan_lr[1] * (v2f){so.y, so.y};
+}
+// the same with the lane's (L, R) split into two floats (every form but the packed pair tile, SK_FAST2_LDS_BLOCK_P)
+template <bool FILTER, int EM, bool TAME, bool MIXED = false, bool MUTESEL = false, int FMP = 0>
+__device__ __forceinline__ void fast2_post(Fast2Regs &r, Env2Regs &e, v2f s, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
+                                           const bool rel0, const bool rel1, const bool silent0,
+                                           const bool silent1, float &out_l, float &out_r) {
+  v2f lr;
+  fast2_post_lr<FILTER, EM, TAME, MIXED, MUTESEL, FMP>(r, e, s, xn, xo, yn, yo, rel0, rel1, silent0, silent1, lr);
   out_l = lr.x;
   out_r = lr.y;
 }
@@ -569,6 +575,65 @@ __device__ __forceinline__ v2f fast2_osc_win(Fast2Regs &r, const WinRegs &w, con
     }                                                                                                    \
     SK_WAVE_SYNC()                                                                                       \
   }
+// The packed pair tile (`pairt`, a bool in scope: Fast2Shape::pair_tile): the same eight frames with the lane's (L, R) parked
+// as the v2f fast2_post_lr formed it -- one ds_write_b64, no split, no fold_lr -- in a tile of 8 rows of 64 float2.  Row f
+// starts at float2 SK_XP2_OFF(f) = (f & 3) * 130 + (f >> 2) * 64: rows f and f + 4 lie back to back and the next such couple
+// starts 2 float2 (16 B) further than 128 would put it.  Banks: a ds_write_b64 is served in four groups of 16 contiguous lanes,
+// 32 contiguous dwords each, one per bank (of 32); a ds_read_b128 in four groups of 16 lanes that hold rows 0..3 of two segments
+// and rows 4..7 of two others (e.g. lanes 0-3, 12-15, 20-27: rows 0..3 of segments 0 and 3, rows 4..7 of 1 and 2), and with
+// 16-byte slot (f & 3) + 4 seg (mod 16) those sixteen lanes hit sixteen different slots of the 64 banks.
+// Order of the 128-term sum of a frame (fixed: the mix is bit-reproducible): lane (f = lane & 7, seg = lane >> 3) adds the
+// pairs of lanes 8 seg .. 8 seg + 7 in ascending lane order, both channels at once (seven v_pk_add_f32); the eight segment
+// sums s0..s7 are then added as ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7)) per channel: row_ror:8 on both halves,
+// one v_permlane16_swap + add (rows 0 | 1 then hold L | R of segments 0..3, rows 2 | 3 of segments 4..7), one
+// v_permlane32_swap + add.  Six plain VALU for that last step; the alternative, a second LDS stage like xq of
+// skred_render_fast.hip, takes a store, four reads and seven more packed adds on eight lanes.
+#define SK_XP2_OFF(F_) (((F_) & 3) * 130 + ((F_) >> 2) * 64)   /* float2 */
+#define SK_XP2_FLOATS (2 * (4 * 130))                          /* the whole tile, in floats */
+__host__ __device__ constexpr int sk_fast2_tile_floats(bool pair) { return pair ? SK_XP2_FLOATS : 8 * SK_XT2; }   /* per wave */
+__host__ __device__ constexpr int sk_fast2_win_floats() { return 2 * SK_WIN * 64; }   /* per wave, global-table banks: the table windows in the tile's place */
+__device__ __forceinline__ void row_ror8_add2(float &x0, float &x1) {
+  asm volatile("s_nop 1\n\t"
+               "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+               "v_add_f32_dpp %1, %1, %1 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+               "s_nop 1"
+               : "+v"(x0), "+v"(x1));
+}
+#define SK_FAST2_LDS_BLOCK_P(J, EM_, LOZ_, MUTE_)                                                        \
+  {                                                                                                      \
+    /* software pipeline and source order as in SK_FAST2_LDS_BLOCK_Z: the gather of the NEXT frame ahead of the current     \
+       frame's chain, both tile stores of a frame pair behind it */                                      \
+    v2f s0_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                               \
+    _Pragma("unroll") for (int q_ = 0; q_ < 8; q_ += 2) {                                                \
+      v2f lr0_, lr1_;                                                                                    \
+      const v2f s1_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                       \
+      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_>(r, e, s0_, r.x1, r.x2, r.y1, r.y2, released[0], released[1], silent[0], silent[1], lr0_); \
+      if (q_ < 6) s0_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                     \
+      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_>(r, e, s1_, r.x2, r.x1, r.y2, r.y1, released[0], released[1], silent[0], silent[1], lr1_); \
+      xp[SK_XP2_OFF(q_) + lane] = make_float2(lr0_.x, lr0_.y);                                           \
+      xp[SK_XP2_OFF(q_ + 1) + lane] = make_float2(lr1_.x, lr1_.y);                                       \
+    }                                                                                                    \
+    if ((EM_) == 7) { SK_FAST2_FOLD_SAMPLE() }   /* one packed multiply per eight frames */              \
+    SK_WAVE_SYNC()                                                                                       \
+    {                                                                                                    \
+      const float4 *src_ = reinterpret_cast<const float4 *>(xp + SK_XP2_OFF(lane & 7) + (lane >> 3) * 8); \
+      const float4 a_ = src_[0], b_ = src_[1];                                                           \
+      v2f t_ = (v2f){a_.x, a_.y} + (v2f){a_.z, a_.w};                                                    \
+      t_ = t_ + (v2f){b_.x, b_.y}; t_ = t_ + (v2f){b_.z, b_.w};                                          \
+      __builtin_amdgcn_sched_barrier(0);         /* two reads in flight, as in the folded form: the kernel sits at its register budget */ \
+      const float4 c_ = src_[2], d_ = src_[3];                                                           \
+      t_ = t_ + (v2f){c_.x, c_.y}; t_ = t_ + (v2f){c_.z, c_.w};                                          \
+      t_ = t_ + (v2f){d_.x, d_.y}; t_ = t_ + (v2f){d_.z, d_.w};                                          \
+      float tl_ = t_.x, tr_ = t_.y;                                                                      \
+      row_ror8_add2(tl_, tr_);                   /* lanes 0..7 of row k: segments 2k + (2k + 1), L and R */ \
+      const auto p16_ = __builtin_amdgcn_permlane16_swap(__float_as_uint(tl_), __float_as_uint(tr_), false, false); \
+      const float z_ = __uint_as_float(p16_[0]) + __uint_as_float(p16_[1]);   /* rows 0 | 1 | 2 | 3: L 0..3 | R 0..3 | L 4..7 | R 4..7 */ \
+      const auto p32_ = __builtin_amdgcn_permlane32_swap(__float_as_uint(z_), __float_as_uint(z_), false, false); \
+      const float w_ = __uint_as_float(p32_[0]) + __uint_as_float(p32_[1]);   /* lanes 0..7: L of frames 0..7, lanes 16..23: R */ \
+      if ((lane & 40) == 0) reinterpret_cast<float *>(&wsum[wave * SK_CHUNK + (J) + (lane & 7)])[(lane >> 4) & 1] = w_; \
+    }                                                                                                    \
+    SK_WAVE_SYNC()                                                                                       \
+  }
 // The same eight frames for a wave that is not tame (frequency-modulated carriers of an FMP bank, loops out of range ...):
 // general frames, no gather ahead (a carrier's increment needs the modulator's sample of the frame before), same tile.
 #define SK_FAST2_LDS_BLOCK_U(J, EM_)                                                                     \
@@ -591,12 +656,15 @@ __device__ __forceinline__ v2f fast2_osc_win(Fast2Regs &r, const WinRegs &w, con
     }                                                                                                    \
     SK_WAVE_SYNC()                                                                                       \
   }
-// `loz` (wave-uniform, set once per pass): see fast2_osc
+// `loz` (wave-uniform, set once per pass): see fast2_osc; `pairt` (a constexpr in scope: the kernel's PAIR): the packed pair
+// tile, see SK_FAST2_LDS_BLOCK_P
 #define SK_FAST2_LDS_BLOCK(J, EM_)                                                                       \
-  { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, false) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, false) }
+  { if constexpr (pairt) { if (loz) SK_FAST2_LDS_BLOCK_P(J, EM_, true, false) else SK_FAST2_LDS_BLOCK_P(J, EM_, false, false) } \
+    else { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, false) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, false) } }
 // the same for a tame wave with muted live lanes (tame_m): their contribution is selected away, synth.c:596
 #define SK_FAST2_LDS_BLOCK_M(J, EM_)                                                                     \
-  { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, true) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, true) }
+  { if constexpr (pairt) { if (loz) SK_FAST2_LDS_BLOCK_P(J, EM_, true, true) else SK_FAST2_LDS_BLOCK_P(J, EM_, false, true) } \
+    else { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, true) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, true) } }
 // Eight frames of a tame wave that holds listed voices (in-place instantiation): SK_FAST2_LDS_BLOCK_Z with the listed voices'
 // gains of the block's frames in gtile[8][SK_GT_RANKS] (rank: the listed voice's number within the wave), parked there by
 // the block before.  This block fetches the NEXT eight frames at its start -- lane (frame = lane & 7, rank = (lane >> 3) +
@@ -876,12 +944,11 @@ __device__ __forceinline__ void fast2_store(const sk_render_args_t &a, const Fas
   const char *lds_tab = reinterpret_cast<const char *>(lds);                                         \
   const char *glb_tab = reinterpret_cast<const char *>(a.tables);                                    \
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;                                     \
-  /* wave-private: the reduction tile [8 frames][SK_XT2] of folded (L | R) pair sums (it used to be a float2 tile [8][65] and a \
-     second stage xq[64]: 4.7 KB per wave, of which 2.2 are in use since the fold -- 20 KB per workgroup that kept banks with \
-     more than 31 KB of tables at one workgroup per CU) */                                            \
-  float2 *xp = reinterpret_cast<float2 *>(reinterpret_cast<float *>(wsum0 + 2 * NW * SK_CHUNK) + wave * (8 * SK_XT2)); \
+  /* wave-private: the reduction tile, [8 frames][SK_XT2] of folded (L | R) pair sums or, with `pairt` (a constexpr in scope), the \
+     packed pair tile of SK_FAST2_LDS_BLOCK_P: sk_fast2_tile_floats */                                 \
+  float2 *xp = reinterpret_cast<float2 *>(reinterpret_cast<float *>(wsum0 + 2 * NW * SK_CHUNK) + wave * sk_fast2_tile_floats(pairt)); \
   /* global-table banks: the same LDS holds the wave's table windows instead (2 voices x SK_WIN x 64 lanes) */ \
-  float *win = reinterpret_cast<float *>(wsum0 + 2 * NW * SK_CHUNK) + wave * (2 * SK_WIN * 64);      \
+  float *win = reinterpret_cast<float *>(wsum0 + 2 * NW * SK_CHUNK) + wave * sk_fast2_win_floats();  \
   (void)xp; (void)win;                                                                               \
   const int bid = (int)blockIdx.x - ((GAIN_WG) ? a.wg_shift : 0);   /* row of the partial mix; -1: the gain workgroup */ \
   if ((GAIN_WG) && bid < 0) { sk_finish_block(a, bid, tid, NW * 64, reinterpret_cast<int *>(lds)); return; } \
@@ -912,7 +979,29 @@ __device__ __forceinline__ void fast2_store(const sk_render_args_t &a, const Fas
     const bool skip_[2] = {(bool)((m0 >> lane) & 1), (bool)((m1 >> lane) & 1)};                      \
     fast2_store<MIXED>(a, r, dead, vidx, skip_);                                                     \
   }
-template <bool TAB_LDS> struct Fast2Shape { static constexpr int NW = TAB_LDS ? SK_FAST2_NW_LDS : 4; };
+// The reduction tile: the packed pair tile (SK_FAST2_LDS_BLOCK_P, 4 160 B per wave) where two workgroups of NW waves -- tables,
+// wsum and tiles each -- still share a CU's 160 KB of LDS, i.e. for table pools up to 81 920 - 8 * (1 024 + 4 160) = 40 448 B
+// (the 25 KB pool of the C2 / C3 recipes: 67 072 B per workgroup); larger pools keep the folded tile (2 176 B per wave), with
+// which every pool that is staged in LDS at all (SK_LDS_TABLE_MAX_FLOATS) runs two workgroups per CU.  The tile is a template
+// argument of the kernel (PAIR): the launcher applies the rule and picks the instantiation.  The truncating (INTERP == 0) plain
+// and probe instantiations of sk_render_fast2_kernel only.  The linear ones keep the folded tile: their two taps per voice and
+// frame make their LDS pipe the busier one, the wider stores and two more reads per block cost more there than the VALU saves
+// (c3_linear measured 1.7 % SLOWER with the pair tile, profiles/pairsum_NOTE.md), and they spilled two more registers.  So do
+// the in-place (GT) and two-operator (FMP) instantiations and the envelope kernel, whatever the pool.
+#define SK_FAST2_LDS_SHARE ((size_t)80 * 1024)   /* half a CU's LDS */
+template <bool TAB_LDS> struct Fast2Shape {
+  static constexpr int NW = TAB_LDS ? SK_FAST2_NW_LDS : 4;
+  // LDS of a workgroup of nw waves: [tables] + wsum[2][nw][SK_CHUNK] + per wave the reduction tile (LDS-table banks) or the table
+  // windows (global-table banks) + (in-place instantiation) per wave gtile and srank
+  __host__ __device__ static constexpr size_t lds_bytes(int table_floats, int nw, bool pair, bool gt) {
+    return (size_t)(TAB_LDS ? table_floats : 0) * sizeof(float) +
+           (size_t)nw * (2 * SK_CHUNK * sizeof(float2) + (size_t)(TAB_LDS ? sk_fast2_tile_floats(pair) : sk_fast2_win_floats()) * sizeof(float) +
+                         (gt ? (size_t)SK_GT_LDS_FLOATS * sizeof(float) : 0));
+  }
+  __host__ __device__ static constexpr bool pair_tile(int table_floats) {
+    return TAB_LDS && lds_bytes(table_floats, NW, true, false) <= SK_FAST2_LDS_SHARE;
+  }
+};
 
 // FMP: a two-operator FM bank (SKM_FM_PAIR) -- a lane holds voices 2i and 2i+1 of its slice, carrier and modulator.
 // FMP == 2 (SKM_PAIR_AP): some carrier's amplitude or pan is modulated too (by the voice after it or by itself).
@@ -922,15 +1011,18 @@ template <bool TAB_LDS> struct Fast2Shape { static constexpr int NW = TAB_LDS ? 
 // pass outside the chunk and frame loops: profiles/fold_usage_*.txt).
 // PROBE: the same kernel compiled in a translation unit with -DSK_PROBE_TU (fast2_post then also writes the probe rows of
 // skred_bank_set_probe): a template parameter only so that its instantiations are symbols of their own.
-template <bool TAB_LDS, bool FILTER, bool ENV, int INTERP, bool MIXED, int FMP = 0, bool GT = false, bool PROBE = false>
+// PAIR: the packed pair tile (Fast2Shape::pair_tile, decided by the launcher).
+template <bool TAB_LDS, bool FILTER, bool ENV, int INTERP, bool MIXED, int FMP = 0, bool GT = false, bool PROBE = false, bool PAIR = false>
 __global__ __launch_bounds__(Fast2Shape<TAB_LDS>::NW * 64, SK_FAST2_MIN_WAVES) void sk_render_fast2_kernel(const sk_render_args_t a) {
+  static_assert(!PAIR || (TAB_LDS && !GT && FMP == 0 && INTERP == 0), "the packed pair tile: truncating plain and probe instantiations of LDS-table banks");
   constexpr int NW = Fast2Shape<TAB_LDS>::NW;
   constexpr bool fold_on = !GT;      // the in-place instantiation keeps its frames as they are
+  constexpr bool pairt = PAIR;
   SK_FAST2_PROLOGUE()
   (void)n_flags;
   // GT: per wave, behind the tiles: gtile[8][SK_GT_RANKS] (the listed voices' gains of one 8-frame block) and
   // srank[SK_GT_RANKS] (rank -> where that voice's row starts in a.env_gain)
-  float *const gtile = reinterpret_cast<float *>(wsum0 + 2 * NW * SK_CHUNK) + NW * (8 * SK_XT2) + wave * SK_GT_LDS_FLOATS;
+  float *const gtile = reinterpret_cast<float *>(wsum0 + 2 * NW * SK_CHUNK) + NW * sk_fast2_tile_floats(pairt) + wave * SK_GT_LDS_FLOATS;
   int *const srank = reinterpret_cast<int *>(gtile + 8 * SK_GT_RANKS);
   (void)gtile; (void)srank;
   bool first_pass = true;
@@ -1075,6 +1167,7 @@ template <bool TAB_LDS, bool FILTER, int INTERP, bool MIXED, int FMP = 0, bool P
 __global__ __launch_bounds__(SK_GROUP, SK_ENV2_MIN_WAVES) void sk_render_env2_kernel(const sk_render_args_t a) {
   constexpr int NW = 4;              // always 512 voices per pass: its register budget allows 3 waves per SIMD anyway
   constexpr bool fold_on = false;    // (SK_FAST2_CHUNK: the folded frames are sk_render_fast2_kernel's)
+  constexpr bool pairt = false;      // (... and so is the packed pair tile)
   bool folded = false;
   (void)folded;
   // the listed voices in ascending order (sk_collect_scan_kernel + sk_collect_expand_kernel, just before on this stream):
@@ -1413,13 +1506,10 @@ extern "C" int sk_launch_render_fast2p(const sk_render_args_t *args, int n_workg
 extern "C" int sk_launch_env_fast2p(const sk_render_args_t *args, hipStream_t stream);
 #endif
 
-static inline size_t sk_fast2_lds(const sk_render_args_t *args, int nw, bool gt = false) {
-  // LDS: [tables] + wsum[2][NW][SK_CHUNK] + per wave the transposition tile and row sums (LDS-table banks) or the table
-  // windows (global-table banks)
-  const bool tab_lds = args->lds_table_floats > 0;
-  const size_t tab_bytes = (size_t)(tab_lds ? args->lds_table_floats : 0) * sizeof(float);
-  const size_t per_wave = tab_lds ? (size_t)(8 * SK_XT2) * sizeof(float) : (size_t)(2 * SK_WIN * 64) * sizeof(float);
-  return tab_bytes + (size_t)nw * (2 * SK_CHUNK * sizeof(float2) + per_wave + (gt ? (size_t)SK_GT_LDS_FLOATS * sizeof(float) : 0));
+// `pair`: the launch is of a PAIR instantiation of sk_render_fast2_kernel
+static inline size_t sk_fast2_lds(const sk_render_args_t *args, int nw, bool gt = false, bool pair = false) {
+  if (args->lds_table_floats <= 0) return Fast2Shape<false>::lds_bytes(0, nw, false, gt);
+  return Fast2Shape<true>::lds_bytes(args->lds_table_floats, nw, pair, gt);
 }
 static inline int sk_fast2_key(const sk_render_args_t *args) {
   return (args->lds_table_floats > 0 ? 8 : 0) | ((args->fast_mode & SKM_FILTER_ALL) ? 4 : 0) |
@@ -1480,20 +1570,34 @@ extern "C" int SK_FAST2_LAUNCHER(const sk_render_args_t *args, int n_workgroups,
   (void)lds_bytes;
   const int nw = tab_lds ? Fast2Shape<true>::NW : Fast2Shape<false>::NW;
 #ifdef SK_FAST2_GT_TU
-  const size_t lds_fast2 = sk_fast2_lds(args, nw, true);
+  const bool pair = false;
+  const size_t lds_fast2 = sk_fast2_lds(args, nw, true, false);
+#elif defined(SK_FAST2_FMP_TU)
+  const bool pair = false;
+  const size_t lds_fast2 = sk_fast2_lds(args, nw, false, false);
 #else
-  const size_t lds_fast2 = sk_fast2_lds(args, nw);
+  const bool pair = tab_lds && args->interp == 0 && Fast2Shape<true>::pair_tile(args->lds_table_floats);   // (truncating lookup only: see Fast2Shape)
+  const size_t lds_fast2 = sk_fast2_lds(args, nw, false, pair);
 #endif
+  (void)pair;
   dim3 grid((unsigned)(n_workgroups + args->wg_shift)), block((unsigned)nw * 64);
   const bool mixed = (args->fast_mode & SKM_MIXED) != 0;     // filter / envelope on some voices only: per-lane flags
   const int key = sk_fast2_key(args);
 #ifdef SK_FAST2_GT_TU
 #define SK_FAST2_LAUNCH(T, F, E, I, M, P) { hipLaunchKernelGGL((sk_render_fast2_kernel<T, F, E, I, M, P, true, SK_PROBE_FLAG>), grid, block, lds_fast2, stream, *args); }
 #else
-#define SK_FAST2_LAUNCH(T, F, E, I, M, P) { hipLaunchKernelGGL((sk_render_fast2_kernel<T, F, E, I, M, P, false, SK_PROBE_FLAG>), grid, block, lds_fast2, stream, *args); }
+/* (with the packed pair tile the C2 / C3 recipes' workgroup holds 67 072 B: beyond 64 KB the kernel is told so, per launch as in
+   skred_render_fast.hip -- the attribute belongs to the device the calling thread is on) */
+#define SK_FAST2_LAUNCH_(T, F, E, I, M, P, PR) {                                                                             \
+    if (lds_fast2 > 65536 && hipFuncSetAttribute(reinterpret_cast<const void *>(&sk_render_fast2_kernel<T, F, E, I, M, P, false, SK_PROBE_FLAG, PR>), \
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)SK_FAST2_LDS_SHARE) != hipSuccess) return (int)hipGetLastError(); \
+    hipLaunchKernelGGL((sk_render_fast2_kernel<T, F, E, I, M, P, false, SK_PROBE_FLAG, PR>), grid, block, lds_fast2, stream, *args); }
+/* (`pair` is only ever true for T && P == 0 && I == 0: the first branch names the same instantiation as the second otherwise) */
+#define SK_FAST2_LAUNCH(T, F, E, I, M, P) { if (pair) SK_FAST2_LAUNCH_(T, F, E, I, M, P, ((T) && (P) == 0 && (I) == 0)) else SK_FAST2_LAUNCH_(T, F, E, I, M, P, false) }
 #endif
   SK_FAST2_SWITCH()
 #undef SK_FAST2_LAUNCH
+#undef SK_FAST2_LAUNCH_
   return (int)hipGetLastError();
 }
 
