@@ -992,6 +992,66 @@ int  skred_bank_ctl_owned_each(skred_bank_t *bank, const skred_ctl_t *ctl, const
 int  skred_bank_ctl_tags_each(skred_bank_t *bank, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int first, int count,
                               int slot_voices, uint64_t voice_mask, const uint32_t *tags, int n, uint32_t *d_result, void *stream);
 
+/* ---- channel polyphony: stealing inside one channel, note-ons under a cap ---------------------------------------------------
+ *
+ * A channel can be swept, bent and silenced (the section above); these calls let it ALLOCATE.  skred_bank_find_steal_slots ranks
+ * every sounding slot of a range, whoever owns it -- a burst on the pad channel takes the bass line's notes -- and nothing limits
+ * how many slots a channel holds.  The host cannot enforce a limit: the number of sounding slots of a channel is device state.
+ *
+ * Slots, K, member_mask, live, released, age, idle, class, primary and key mean what skred_slot_steal_query_t defines;
+ * match(o) := o != 0 && (o & m.mask) == m.value is skred_owner_match_t's rule; a slot's owner is the word at its first voice.  On
+ * the fields AS THE DEVICE HOLDS THEM at that point of the stream, every comparison exact:
+ *   sounding(slot)  := slot inside the range && match(owner[slot]) && some member is live
+ *                      && NOT (exclude_idle != 0 && every member is idle)
+ *   candidate(slot) := sounding(slot) && every live member has age >= min_age
+ *                      && (with RELEASED_ONLY: every live member is released)
+ * Victim order as before: ascending key, ties by ascending first voice.  An untagged slot (owner 0) is never sounding in this sense:
+ * it is neither counted nor stolen.  A slot that does not match costs one owner word and no plane read.
+ *
+ * skred_bank_find_steal_slots under its contract (asynchronous, reads the bank and the owner array only, the same state gives the
+ * same bytes, the bank's steal scratch -- one stream at a time --, no workgroup ever waits for another), restricted to the match:
+ * d_slots[0 .. written) = the first min(total, max_out) victims, d_count (device, uint32[3]): [0] written, [1] total candidates,
+ * [2] the sounding slots of the match in the range -- the channel's current polyphony.  max_out == 0: a census of the channel in
+ * one launch.  With mask == 0 and every sounding slot tagged the list and d_count[0..1] are skred_bank_find_steal_slots' bytes.
+ * Refused before anything touches the device: what skred_slot_steal_check and skred_owner_match_check refuse, and SKRED_E_BAD_ARG
+ * for a NULL bank, query or d_count, or a NULL d_slots with max_out > 0. */
+int  skred_bank_find_steal_slots_match(skred_bank_t *bank, const skred_slot_steal_query_t *q, const skred_owner_match_t *m,
+                                       int32_t *d_slots, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only.  Returns `written` (>= 0) or a SKRED_E_* code; *total_out and *sounding_out
+ * may be NULL. */
+int  skred_bank_find_steal_slots_match_host(skred_bank_t *bank, const skred_slot_steal_query_t *q, const skred_owner_match_t *m,
+                                            int32_t *slots, int *total_out, int *sounding_out, void *stream);
+/* A burst of n patch notes of ONE channel under a polyphony cap: skred_bank_note_on_steal_slots with three differences, all decided
+ * on the device.  With I = idle slots listed by idle_q (at most n), S = the channel's sounding count (d_count[2] of the matched
+ * query above, run with steal_q and m) and V = the victims that query wrote:
+ *   a = min(n, I, cap > S ? cap - S : 0)   notes take the first a idle slots            (idle slots are limited by the cap),
+ *   b = min(n - a, V)                      notes take the channel's victims, in victim order (stealing stays inside the channel),
+ *   the remaining n - a - b notes are dropped whole,
+ * and note k's slot gets owner = tags[k], as skred_bank_tag_slots on d_assigned would write it (every placed note is tagged; a
+ * thief's tag overwrites its victim's).  d_result (device, uint32[4], required): [0] placed, [1] dropped, [2] stolen (b), [3] S as
+ * seen before the burst.  d_assigned as for skred_bank_notes_on_slots.
+ * Consequences: a channel at or below its cap never exceeds it; a channel above a lowered cap does not grow (a = 0: every note
+ * steals one of its own); a burst cannot steal from itself (both lists are made before a note is placed, and they are disjoint);
+ * cap = 1 with min_age = 0 is mono mode -- the new note takes the old one's slot; SKRED_CHAN_NO_CAP never limits.  Victims come from
+ * the channel only: there is no bank-wide fallback here -- a host that wants one calls skred_bank_note_on_steal_slots.
+ * The library overrides steal_q's exclude_idle, settle_level and max_out as skred_bank_note_on_steal_slots does.  Five steps on
+ * `stream`: the idle query, the matched key pass and its select, one one-workgroup join kernel, the slot-note launch, the owner-tag
+ * launch.  The motion-list bound grows by n * popcount(voice_mask); the host never learns the counts and waits for nothing.
+ * skred_chan_check is the pure-host statement of what is refused before anything touches the device: what
+ * skred_slot_query_check (with max_out = n), skred_slot_steal_check (with the overrides) and skred_owner_match_check refuse;
+ * SKRED_E_BAD_ARG for a NULL query, n < 0, SKRED_IDLE_AMP_ZERO in idle_q->which, queries that differ in slot_voices or
+ * member_mask, NULL tags, n > INT32_MAX / 64, a tag that is 0 or does not satisfy m (such a note would not count towards its own
+ * channel).  Every cap is accepted.  The entry point also refuses a NULL bank, notes or d_result and what skred_slot_notes_check
+ * refuses.  n == 0: SKRED_OK, nothing is done.  On a shard: through skred_shard_bank(), with that rank's local indices.
+ * Not built here (out of scope): a twin on the fixed-point bank, shards beyond skred_shard_bank(), the drop-in mode, deferred items
+ * and pattern steps. */
+#define SKRED_CHAN_NO_CAP 0xFFFFFFFFu
+int  skred_chan_check(const skred_slot_query_t *idle_q, const skred_slot_steal_query_t *steal_q, const skred_owner_match_t *m,
+                      uint32_t cap, const uint32_t *tags, int n, int n_voices);
+int  skred_bank_note_on_channel(skred_bank_t *bank, const skred_slot_query_t *idle_q, const skred_slot_steal_query_t *steal_q,
+                                const skred_owner_match_t *m, uint32_t cap, const skred_note_t *notes, const uint32_t *tags, int n,
+                                uint64_t voice_mask, int32_t *d_assigned, uint32_t *d_result, void *stream);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

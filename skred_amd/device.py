@@ -46,10 +46,12 @@ ABI_SYMBOLS = [
     "skred_bank_owner_clear", "skred_bank_download_owners", "skred_bank_download_env_clocks",
     "skred_bank_find_match", "skred_bank_find_match_host", "skred_bank_stamp_match", "skred_bank_ctl_match",
     "skred_bank_ctl_owned_each", "skred_bank_ctl_tags_each",
+    "skred_bank_find_steal_slots_match", "skred_bank_find_steal_slots_match_host", "skred_bank_note_on_channel",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
-                    "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check"]
+                    "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check",
+                    "skred_chan_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -301,6 +303,12 @@ def load() -> C.CDLL:
     L.skred_bank_ctl_match.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), vp, vp]
     L.skred_bank_ctl_owned_each.argtypes = [vp, vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
     L.skred_bank_ctl_tags_each.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
+    L.skred_chan_check.argtypes = [C.POINTER(SlotQueryC), C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), C.c_uint32, vp, i32, i32]
+    L.skred_bank_find_steal_slots_match.argtypes = [vp, C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), vp, vp, vp]
+    L.skred_bank_find_steal_slots_match_host.argtypes = [vp, C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), vp, C.POINTER(i32),
+                                                         C.POINTER(i32), vp]
+    L.skred_bank_note_on_channel.argtypes = [vp, C.POINTER(SlotQueryC), C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), C.c_uint32,
+                                             vp, vp, i32, C.c_uint64, vp, vp, vp]
     _lib = L
     return L
 
@@ -355,6 +363,18 @@ def owner_tags_check(tags, flags: int = 0) -> int:
 def owner_match_check(m: Optional[OwnerMatchC]) -> int:
     """skred_owner_match_check: 0, or SKRED_E_BAD_ARG (-2) for None or a value with bits outside the mask.  Pure host."""
     return int(load().skred_owner_match_check(C.byref(m) if m is not None else None))
+
+
+CHAN_NO_CAP = 0xFFFFFFFF          # SKRED_CHAN_NO_CAP
+
+
+def chan_check(idle_q, steal_q, m, cap: int, tags, n_voices: int) -> int:
+    """skred_chan_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for a burst note_on_channel would refuse (queries, match, cap
+    and the len(tags) tags; None stands for a NULL pointer).  Pure host."""
+    arr = tag_array(tags) if tags is not None else None
+    ref = lambda x: C.byref(x) if x is not None else None   # noqa: E731
+    return int(load().skred_chan_check(ref(idle_q), ref(steal_q), ref(m), int(cap) & 0xFFFFFFFF, arr.ctypes.data if arr is not None else None,
+                                       len(arr) if arr is not None else 0, int(n_voices)))
 
 
 def ctl_each_check(each, ctls, voice_mask: int, slot_voices: Optional[int] = None) -> int:
@@ -755,6 +775,34 @@ class DeviceBank:
         _check(self.L.skred_bank_note_on_steal_slots(self.h, C.byref(idle_q), C.byref(steal_q), C.cast(arr, C.c_void_p),
                                                      len(arr) // int(idle_q.slot_voices), int(voice_mask), d_assigned or None,
                                                      d_result or None, stream or None), "skred_bank_note_on_steal_slots")
+
+    # ---- channel polyphony (include/skred_amd.h: skred_bank_find_steal_slots_match / _match_host / _note_on_channel) ----
+    def find_steal_slots_match(self, q: SlotStealQueryC, m: OwnerMatchC, d_slots: int = 0, d_count: int = 0, stream: int = 0):
+        """find_steal_slots restricted to the slots whose owner word matches `m`; d_count (uint32[3], device memory) = written, total
+        candidates, sounding slots of the match in the range."""
+        _check(self.L.skred_bank_find_steal_slots_match(self.h, C.byref(q), C.byref(m), d_slots or None, d_count or None, stream or None),
+               "skred_bank_find_steal_slots_match")
+
+    def find_steal_slots_match_host(self, q: SlotStealQueryC, m: OwnerMatchC, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the victim slots, total, sounding)."""
+        out = np.empty(max(int(q.max_out), 0), np.int32)
+        total, sounding = C.c_int(0), C.c_int(0)
+        n = self.L.skred_bank_find_steal_slots_match_host(self.h, C.byref(q), C.byref(m), out.ctypes.data if q.max_out > 0 else None,
+                                                          C.byref(total), C.byref(sounding), stream or None)
+        if n < 0:
+            _check(n, "skred_bank_find_steal_slots_match_host")
+        return out[:n].copy(), int(total.value), int(sounding.value)
+
+    def note_on_channel(self, notes, tags, idle_q: SlotQueryC, steal_q: SlotStealQueryC, m: OwnerMatchC, cap: int, voice_mask: int,
+                        d_assigned: int = 0, d_result: int = 0, stream: int = 0):
+        """A burst of len(tags) patch notes of one channel under a polyphony cap: idle slots while the channel's sounding count stays
+        below `cap`, then victims of the channel itself, every placed note tagged with its tags[k];
+        d_result[0..4) = placed, dropped, stolen, the channel's sounding count before the burst."""
+        arr = note_array(notes)
+        t = tag_array(tags)
+        _check(self.L.skred_bank_note_on_channel(self.h, C.byref(idle_q), C.byref(steal_q), C.byref(m), int(cap) & 0xFFFFFFFF,
+                                                 C.cast(arr, C.c_void_p), t.ctypes.data, len(t), int(voice_mask), d_assigned or None,
+                                                 d_result or None, stream or None), "skred_bank_note_on_channel")
 
     def force_generic(self, on: bool = True):
         _check(self.L.skred_bank_set_option(self.h, 1, int(on)), "skred_bank_set_option")

@@ -1345,8 +1345,120 @@ def fxexpr():
     db.close()
 
 
+def chan():
+    """Channel polyphony on bank_patch("3sk", 2**20), every copy sounding and tagged over 16 channels (tag = channel << 24 | slot + 1).
+    (a) a burst of 256 patch notes on ONE channel with the cap at the channel's current count, so that all 256 steal inside the
+    channel: skred_bank_note_on_channel, beside the only route before it -- skred_bank_download_owners and skred_bank_download behind a
+    device wait, the channel pick and the victim order in numpy, skred_bank_update, skred_bank_tag_slots; (b) the key pass:
+    skred_bank_find_steal_slots_match beside skred_bank_find_steal_slots on the same range at max_out 0 and 16; (c) the 64-frame block
+    after the burst beside the block after the equivalent skred_bank_note_on_steal_slots.  Medians of 12 with minimum and maximum;
+    host time held, and stream time between events."""
+    D = device
+    from skred_amd.bank import slot_query, slot_steal_query
+    n, K, REPS, F, CHANNELS, NOTES = 1 << 20, 4, 12, 64, 16, 256
+    MEMBERS, VOICES = 0x7, 0xF
+    WHICH = D.IDLE_FINISHED | D.IDLE_ENV_DONE
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = (now - 40000 - ((v[sel] // K) * 37) % 1000).astype(np.uint64)
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g); db.upload(bank)
+    slots = np.arange(0, n, K, dtype=np.int32)
+    idx = np.arange(len(slots), dtype=np.uint32)
+    tags = (((idx % CHANNELS) + 1) << 24 | (idx // CHANNELS + 1)).astype(np.uint32)
+    dl_all = torch.from_numpy(slots).cuda()
+    db.tag_slots(dl_all.data_ptr(), tags, K)
+    out = torch.zeros(F, 2, device="cuda")
+    m = D.owner_match(3 << 24, 0xFF000000)
+    per_channel = n // K // CHANNELS
+    iq = slot_query(0, n, K, MEMBERS, WHICH, 1e-3, 0, 0)
+    sq = slot_steal_query(0, n, K, MEMBERS)
+    notes = D.note_array([D.NoteC(0.01 + 1e-5 * (k % 97), 0.8, 0.0, 0.5, 0.5, 1) for k in range(NOTES * K)])   # (built once: a ctypes array passes through)
+    note_tags = ((3 << 24) | (0x800000 + np.arange(NOTES))).astype(np.uint32)
+    da = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(4, dtype=torch.int32, device="cuda")
+    dv = torch.full((16,), -1, dtype=torch.int32, device="cuda")
+    dc = torch.zeros(3, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def stats(x):
+        return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f})"
+
+    def series(call):
+        host, stream = [], []
+        for it in range(2 + REPS):
+            torch.cuda.synchronize()
+            h, s_ms = timed(call)
+            if it >= 2:
+                host.append(h); stream.append(s_ms)
+        return f"host time held {stats(host)}; stream time between events {stats(stream)}"
+
+    mirror, state = bank.copy(), bank.copy()
+    starts = e["sample_start"].astype(np.int64).copy()
+
+    def parent_route():
+        own = db.download_owners()[::K]                            # the device waits the channel call was built to remove
+        db.download(state)
+        mine = (own != 0) & ((own & np.uint32(0xFF000000)) == np.uint32(3 << 24))
+        live = (state["voice_amp_envelope"]["is_active"].reshape(-1, K)[:, :3] != 0).any(1)
+        heads = slots[mine & live]
+        key = starts.reshape(-1, K)[:, :3].max(1)[heads // K]
+        picks = heads[np.lexsort((heads, key))][:NOTES]
+        touched = (picks[:, None] + np.arange(K)[None, :]).reshape(-1).astype(np.int32)
+        db.update(mirror, touched, D.DIRTY_PARAMS | D.DIRTY_PHASE | D.STAMP_TRIGGER)
+        dl = torch.from_numpy(picks).cuda()
+        db.tag_slots(dl.data_ptr(), note_tags[:len(picks)], K)
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, every copy sounding, tagged over {CHANNELS} channels ({per_channel} notes each); medians of {REPS}")
+    burst = lambda: db.note_on_channel(notes, note_tags, iq, sq, m, per_channel, VOICES, da.data_ptr(), dr.data_ptr())   # noqa: E731
+    print(f"  (a) {NOTES} notes on one channel at its cap, note_on_channel: {series(burst)}; d_result = {dr.cpu().numpy().tolist()}")
+    print(f"  (a) the same, download_owners + download + numpy pick and order + update + tag_slots: {series(parent_route)}")
+    for mo in (0, 16):
+        q = slot_steal_query(0, n, K, MEMBERS, max_out=mo)
+        print(f"  (b) max_out {mo}, find_steal_slots_match on one channel: {series(lambda: db.find_steal_slots_match(q, m, dv.data_ptr(), dc.data_ptr()))}; "
+              f"d_count = {dc.cpu().numpy().tolist()}")
+        print(f"  (b) max_out {mo}, find_steal_slots on the whole range: {series(lambda: db.find_steal_slots(q, dv.data_ptr(), dc.data_ptr()))}; "
+              f"d_count = {dc.cpu().numpy()[:2].tolist()}")
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+
+    def block_after(call):
+        db.upload(bank)
+        db.tag_slots(dl_all.data_ptr(), tags, K)
+        for _ in range(8):
+            block()
+        after = []
+        for _ in range(REPS):
+            call()
+            after.append(block())
+            block()
+        return after
+    after_chan = block_after(burst)
+    after_steal = block_after(lambda: db.note_on_steal_slots(notes, iq, sq, VOICES, da.data_ptr(), dr.data_ptr()))
+    print(f"  (c) the {F}-frame block after the channel burst: {stats(after_chan)}; after note_on_steal_slots of {NOTES} notes: {stats(after_steal)}; "
+          f"kernel {db.last_kernel()}, list violations {db.list_violations()}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
