@@ -1043,8 +1043,9 @@ int  skred_bank_find_steal_slots_match_host(skred_bank_t *bank, const skred_slot
  * member_mask, NULL tags, n > INT32_MAX / 64, a tag that is 0 or does not satisfy m (such a note would not count towards its own
  * channel).  Every cap is accepted.  The entry point also refuses a NULL bank, notes or d_result and what skred_slot_notes_check
  * refuses.  n == 0: SKRED_OK, nothing is done.  On a shard: through skred_shard_bank(), with that rank's local indices.
- * Not built here (out of scope): a twin on the fixed-point bank, shards beyond skred_shard_bank(), the drop-in mode, deferred items
- * and pattern steps. */
+ * The fixed-point bank has the same calls per voice (include/skred_amd_fxpt.h: skred_fxbank_find_steal_match / _find_steal_match_host /
+ * _note_on_channel, skred_fx_chan_check).  Not built here (out of scope): shards beyond skred_shard_bank(), the drop-in mode, deferred
+ * items and pattern steps. */
 #define SKRED_CHAN_NO_CAP 0xFFFFFFFFu
 int  skred_chan_check(const skred_slot_query_t *idle_q, const skred_slot_steal_query_t *steal_q, const skred_owner_match_t *m,
                       uint32_t cap, const uint32_t *tags, int n, int n_voices);

@@ -455,6 +455,74 @@ int  skred_fxbank_ctl_owned_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, 
 int  skred_fxbank_ctl_tags_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, int first, int count,
                                 const uint32_t *tags, int n, uint32_t *d_result, void *stream);
 
+/* ---- channel polyphony: stealing inside one channel, note-ons under a cap ---------------------------------------------------
+ *
+ * The fixed-point twin of the float bank's section of the same name (include/skred_amd.h: skred_bank_find_steal_slots_match ..
+ * skred_bank_note_on_channel).  A channel can be swept, bent and silenced (the section above); these calls let it ALLOCATE.
+ * skred_fxbank_find_steal ranks every sounding voice of a range, whoever owns it -- a burst on the pad channel takes the bass line's
+ * notes -- and nothing limits how many voices a channel holds.  The host cannot enforce a limit: the number of sounding voices of a
+ * channel is device state, and the only correct host route is skred_fxbank_download_owners plus skred_fxbank_download behind a device
+ * wait.  This bank has no slots: every call is per voice (the float call at K = 1, voice_mask = 1).  skred_owner_match_t,
+ * skred_owner_match_check, SKRED_CHAN_NO_CAP and the SKRED_STEAL_* / SKRED_IDLE_* bits keep their meaning and values.
+ *
+ * On the words AS THE DEVICE HOLDS THEM at that point of the stream, every comparison exact (q: the skred_fx_steal_query_t, m: the
+ * match; released, age, class, primary, key and order are exactly those of skred_fxbank_find_steal):
+ *   match(o)      o != 0  &&  (o & m.mask) == m.value                          (skred_owner_match_t's rule)
+ *   sounding(v)   v lies in [first, first + count)  &&  match(owner[v])  &&  use_envelope != 0  &&  is_active != 0
+ *                 &&  NOT (exclude_idle != 0  &&  v satisfies skred_fxbank_find_idle's predicate for (exclude_idle, settle_q15))
+ *   candidate(v)  sounding(v)  &&  age >= min_age  &&  (released, under SKRED_STEAL_RELEASED_ONLY)
+ *   order         ascending key, ties by ascending voice index
+ * An untagged voice (owner 0) is never sounding in this sense: it is neither counted nor stolen.  A voice that does not match costs
+ * one owner word and no plane read.
+ *
+ * skred_fxbank_find_steal_match is skred_fxbank_find_steal under its contract (asynchronous, reads the bank and the owner array only,
+ * the same state gives the same bytes, the bank's steal scratch -- one stream at a time --, no workgroup ever waits for another),
+ * restricted to the match: d_voices[0 .. written) = the first min(total, max_out) victims; d_count (device, uint32[3]):
+ *   [0]  written = min(total, max_out)
+ *   [1]  total candidates
+ *   [2]  the sounding voices of the match in the range -- the channel's current polyphony
+ * Entries past `written` are not touched.  max_out == 0: a census of the channel in one launch.  With mask == 0 and every sounding
+ * voice tagged the list and d_count[0..1] are skred_fxbank_find_steal's bytes.  The first call allocates the owner array as the note
+ * owners' section says.  Refused before anything touches the device: what skred_fx_steal_check and skred_owner_match_check refuse, and
+ * SKRED_E_BAD_ARG for a NULL bank, query or d_count, or a NULL d_voices with max_out > 0. */
+int  skred_fxbank_find_steal_match(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, const skred_owner_match_t *m,
+                                   int32_t *d_voices, uint32_t *d_count, void *stream);
+/* The same into host memory; waits for `stream` only.  Returns `written` (>= 0) or a SKRED_E_* code; *total_out and *sounding_out
+ * may be NULL. */
+int  skred_fxbank_find_steal_match_host(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, const skred_owner_match_t *m,
+                                        int32_t *voices, int *total_out, int *sounding_out, void *stream);
+/* A burst of n notes of ONE channel under a polyphony cap: skred_fxbank_note_on_steal with three differences, all decided on the
+ * device.  With
+ *   I = the idle voices idle_q lists, at most n,
+ *   S = the channel's sounding count: d_count[2] of the matched query above, run with steal_q and m,
+ *   V = the victims that query wrote,
+ * the burst is split as
+ *   a = min(n, I, cap > S ? cap - S : 0)   notes take the first a idle voices            (idle voices are limited by the cap),
+ *   b = min(n - a, V)                      notes take the channel's own victims, in victim order (stealing stays inside the channel),
+ *   the remaining n - a - b notes are dropped,
+ * and every placed note k's voice gets owner = tags[k], as skred_fxbank_tag_list on d_assigned would write it (a thief's tag
+ * overwrites its victim's).  d_result (device, uint32[4], required): [0] placed, [1] dropped, [2] stolen (b), [3] S as seen before the
+ * burst.  d_assigned as for skred_fxbank_notes_on_list.
+ * Consequences: a channel at or below its cap never exceeds it; a channel above a lowered cap does not grow (a = 0: every note
+ * steals one of its own); a burst cannot steal from itself (both lists are made before a note is placed, and they are disjoint: a
+ * victim is never a voice the idle list offers) or from another channel (only voices that match are ranked); cap = 1 with
+ * min_age = 0 is mono mode -- the new note takes the old one's voice; SKRED_CHAN_NO_CAP never limits.  There is no bank-wide fallback:
+ * victims come from the channel only -- a host that wants one calls skred_fxbank_note_on_steal.
+ * The library overrides steal_q's exclude_idle, settle_q15 and max_out exactly as skred_fxbank_note_on_steal does.  Five steps on
+ * `stream`: the idle query, the matched key pass and its select, one one-workgroup join kernel, the note launch, the owner-tag launch.
+ * The notes and the tags travel through the staging ring (two slots); the host never learns the counts and waits for nothing.
+ * skred_fx_chan_check is the pure-host statement of what is refused before anything touches the device: what skred_fx_idle_check
+ * (with max_out = n), skred_fx_steal_check (with the overrides) and skred_owner_match_check refuse; SKRED_E_BAD_ARG for a NULL query,
+ * n < 0, SKRED_IDLE_AMP_ZERO in idle_q->which, NULL tags, n > INT32_MAX / 64 (skred_fxbank_tag_list's bound), a tag that is 0 or does
+ * not satisfy m (such a note would not count towards its own channel).  Every cap is accepted.  The entry point also refuses a NULL
+ * bank, notes or d_result and what skred_fx_notes_check refuses.  n == 0: SKRED_OK, nothing is done.  On a shard: through
+ * skred_fxshard_bank(), with that rank's local indices. */
+int  skred_fx_chan_check(const skred_fx_idle_query_t *idle_q, const skred_fx_steal_query_t *steal_q, const skred_owner_match_t *m,
+                         uint32_t cap, const uint32_t *tags, int n, int n_voices);
+int  skred_fxbank_note_on_channel(skred_fxbank_t *fx, const skred_fx_idle_query_t *idle_q, const skred_fx_steal_query_t *steal_q,
+                                  const skred_owner_match_t *m, uint32_t cap, const skred_fx_note_t *notes, const uint32_t *tags,
+                                  int n, int32_t *d_assigned, uint32_t *d_result, void *stream);
+
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);
 float skred_fxbank_last_render_ms(skred_fxbank_t *fx);

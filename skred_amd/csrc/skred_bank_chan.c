@@ -11,7 +11,8 @@
  * be on the motion list (an upper bound: the cap and the channel can only take notes away), and earlier launches' reports are out
  * of date.  The tags change no class, counter, lane word or report: the owner array is no part of the bank the planner knows.
  *
- * Out of scope: the fixed-point bank, shards beyond skred_shard_bank(), the drop-in mode, deferred items and pattern steps.
+ * The fixed-point bank's twin is skred_fx_chan.c.  Out of scope: shards beyond skred_shard_bank(), the drop-in mode, deferred items and
+ * pattern steps.
  */
 #include <stddef.h>
 #include <string.h>

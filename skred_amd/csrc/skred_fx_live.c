@@ -49,6 +49,7 @@ void skx_live_free(skred_fxbank_t *fx) {
   fx->d_idle = NULL; fx->d_idle_out = NULL; fx->h_idle_out = NULL; fx->d_note_list = NULL;
   fx->idle_wgs = 0; fx->idle_out_cap = 0; fx->note_list_cap = 0;
   skx_steal_free(fx);
+  skx_chan_free(fx);
   skx_owner_free(fx);
 }
 

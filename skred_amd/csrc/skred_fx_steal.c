@@ -55,7 +55,8 @@ static int steal_check_bank(const skred_fxbank_t *fx, const skred_fx_steal_query
   return SKRED_OK;
 }
 
-static int steal_launch(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
+int skx_steal_prepare(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s,
+                      skx_steal_args_t *out) {
   HIP_TRY(hipSetDevice(fx->device));
   /* the scratch, sized once for the whole bank from any `first` (as the idle query's): words and histogram | four words per
    * workgroup | the winners' keys, then their voices | one key per voice of the spans */
@@ -95,6 +96,14 @@ static int steal_launch(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, int
   a.s.policy = q->policy;
   a.s.flags = q->flags;
   if (sk_idle_workgroups(a.s.first, q->count) > wgs) return fail(SKRED_E_RANGE, "fx find_steal: scratch too small");   /* (unreachable: sized above) */
+  *out = a;
+  return SKRED_OK;
+}
+
+static int steal_launch(skred_fxbank_t *fx, const skred_fx_steal_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s) {
+  skx_steal_args_t a;
+  const int rc = skx_steal_prepare(fx, q, d_voices, d_count, s, &a);
+  if (rc) return rc;
   const hipError_t e = (hipError_t)skx_launch_steal(&a, s);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx find_steal launch -> %s", hipGetErrorString(e));
   return SKRED_OK;

@@ -22,6 +22,12 @@ extern "C" {
 #endif
 /* the key pass, then sk_launch_steal_select: SK_STEAL_DIGITS + 3 launches whatever the data, the key pass alone with max_out == 0 */
 int skx_launch_steal(const skx_steal_args_t *args, hipStream_t stream);
+/* skred_fx_steal.c, for skred_fx_chan.c too: the bank's scratch (allocated by the first query, its words zeroed on `s`) and a checked
+ * query as the key passes take it -- everything but base, digit and the idle range, which the launchers fill */
+struct skred_fxbank;
+struct skred_fx_steal_query;
+int skx_steal_prepare(struct skred_fxbank *fx, const struct skred_fx_steal_query *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s,
+                      skx_steal_args_t *a);
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
  * skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c: voice stealing; skred_fx_owner.c: note owners;
- * skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression). */
+ * skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression; skred_fx_chan.c: channel polyphony). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -49,6 +49,7 @@ struct skred_fxbank {
                                                             * query's two counts, the joined list's length), then the list */
   uint32_t *d_steal; int steal_wgs;          /* skred_fxbank_find_steal's scratch, laid out as the float bank's (skred_bank_steal.c) */
   int32_t *d_steal_out, *h_steal_out;        /* [2] counts, then SK_STEAL_MAX victims: _find_steal_host's list and _note_on_steal's */
+  int32_t *d_chan_out, *h_chan_out;          /* skred_fx_chan.c: [3] counts, then SK_STEAL_MAX victims, device and pinned; NULL until the first call that needs them */
   uint32_t *d_owner;                         /* note owners (skred_fx_owner.c): one word per voice, 0 nobody; NULL until the first call that needs it */
   int32_t *d_owner_found;                    /* ... and behind it skred_fxbank_release_tags' list, SKRED_OWNER_MAX_TAGS entries */
   uint32_t *d_match_pair;                    /* ... and behind that the two words the count pass of skred_fxbank_find_match fills */
@@ -99,6 +100,9 @@ int skx_ring_guard(skx_slot_t *sl, hipStream_t s);
 
 /* skred_fx_steal.c */
 void skx_steal_free(skred_fxbank_t *fx);
+
+/* skred_fx_chan.c */
+void skx_chan_free(skred_fxbank_t *fx);
 
 /* skred_fx_owner.c: the owner array (allocated and zero-filled by the first call that needs it), for the guarded controller too */
 void skx_owner_free(skred_fxbank_t *fx);

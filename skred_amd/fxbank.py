@@ -41,9 +41,10 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_ctl_owned", "skred_fxbank_download_params",
                   "skred_fxbank_find_match", "skred_fxbank_find_match_host", "skred_fxbank_stamp_match", "skred_fxbank_ctl_match",
                   "skred_fxbank_ctl_owned_each", "skred_fxbank_ctl_tags_each",
+                  "skred_fxbank_find_steal_match", "skred_fxbank_find_steal_match_host", "skred_fxbank_note_on_channel",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
 FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
-                       "skred_fx_ctl_each_check"]                                                                     # pure host: no bank, no device
+                       "skred_fx_ctl_each_check", "skred_fx_chan_check"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -61,6 +62,7 @@ CTL_REFUSED = 0x3F00
 # channels and per-note expression: the float bank's SKRED_EACH_* bits
 EACH_INC_SCALE, EACH_AMP_SCALE, EACH_VELOCITY, EACH_PAN = 1, 2, 4, 8
 EACH_ALL = 15
+CHAN_NO_CAP = 0xFFFFFFFF                          # SKRED_CHAN_NO_CAP: a cap that never limits
 FX_CTL_SPAN = 256                                 # voices or entries per workgroup of the controller and guarded-stamp kernels
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
@@ -149,6 +151,17 @@ def fx_ctl_each_check(entries, ctl: Optional[FxCtlC] = None, n: Optional[int] = 
 
 def _tags(tags) -> np.ndarray:
     return np.ascontiguousarray(tags, np.uint32)
+
+
+def fx_chan_check(idle_q: Optional[FxIdleQueryC], steal_q: Optional[FxStealQueryC], m: Optional[OwnerMatchC], cap: int, tags,
+                  n_voices: int, n: Optional[int] = None) -> int:
+    """skred_fx_chan_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host, no device.  ``tags`` None: a NULL array."""
+    t = _tags(tags) if tags is not None else None
+    n = (len(t) if t is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_chan_check(C.byref(idle_q) if idle_q is not None else None,
+                                                 C.byref(steal_q) if steal_q is not None else None,
+                                                 C.byref(m) if m is not None else None, int(cap),
+                                                 t.ctypes.data if t is not None else None, int(n), int(n_voices)))
 
 
 class FxNoteC(C.Structure):
@@ -267,6 +280,10 @@ def _bind(L):
     L.skred_fx_ctl_each_check.argtypes = [vp, i32, vp]
     L.skred_fxbank_ctl_owned_each.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.skred_fxbank_ctl_tags_each.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+    L.skred_fxbank_find_steal_match.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.skred_fxbank_find_steal_match_host.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
+    L.skred_fx_chan_check.argtypes = [vp, vp, vp, C.c_uint32, vp, i32, i32]
+    L.skred_fxbank_note_on_channel.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, i32, vp, vp, vp]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -537,6 +554,34 @@ class DeviceFxBank:
         _check(self.L.skred_fxbank_ctl_tags_each(self.h, C.byref(ctl) if ctl is not None else None, C.cast(arr, C.c_void_p),
                                                  int(first), int(count), t.ctypes.data, len(t), d_result or None, stream or None),
                "skred_fxbank_ctl_tags_each")
+
+    # ---- channel polyphony (include/skred_amd_fxpt.h: skred_fxbank_find_steal_match / _find_steal_match_host / _note_on_channel) ----
+    def find_steal_match(self, q: FxStealQueryC, value: int, mask: int, d_voices: int = 0, d_count: int = 0, stream: int = 0):
+        """find_steal among the voices with owner != 0 and (owner & mask) == value; d_count[0..2] = written, total candidates, the
+        sounding voices of the match in the range (uint32)."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_find_steal_match(self.h, C.byref(q), C.byref(m), d_voices or None, d_count or None, stream or None),
+               "skred_fxbank_find_steal_match")
+
+    def find_steal_match_host(self, q: FxStealQueryC, value: int, mask: int, stream: int = 0):
+        """The same into host memory, waiting for `stream` only.  Returns (np.int32 array of the victims, total, sounding)."""
+        m = OwnerMatchC(int(value), int(mask))
+        out = np.empty(max(q.max_out, 0), np.int32)
+        total, sounding = C.c_int(0), C.c_int(0)
+        n = self.L.skred_fxbank_find_steal_match_host(self.h, C.byref(q), C.byref(m), out.ctypes.data if q.max_out > 0 else None,
+                                                      C.byref(total), C.byref(sounding), stream or None)
+        if n < 0:
+            _check(n, "skred_fxbank_find_steal_match_host")
+        return out[:n].copy(), int(total.value), int(sounding.value)
+
+    def note_on_channel(self, notes, idle_q: FxIdleQueryC, steal_q: FxStealQueryC, value: int, mask: int, cap: int, tags,
+                        d_assigned: int = 0, d_result: int = 0, stream: int = 0):
+        """A burst of one channel under a polyphony cap: idle voices as far as the cap allows, then the channel's own victims; every
+        placed note k is tagged tags[k]; d_result[0..3] = placed, dropped, stolen, the channel's sounding count before (uint32)."""
+        arr, t, m = fx_note_array(notes), _tags(tags), OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_note_on_channel(self.h, C.byref(idle_q), C.byref(steal_q), C.byref(m), int(cap),
+                                                   C.cast(arr, C.c_void_p), t.ctypes.data, len(arr), d_assigned or None,
+                                                   d_result or None, stream or None), "skred_fxbank_note_on_channel")
 
 
 # ------------------------------------------------------------------ synthetic fixed-point bank

@@ -1457,8 +1457,82 @@ def chan():
     db.close()
 
 
+def fxchan():
+    """Channel polyphony on bank_fx(2**20), every voice sounding and tagged over 16 channels (tag = channel << 24 | voice // 16 + 1).
+    (a) a burst of 256 notes on ONE channel with the cap at the channel's current count, so that all 256 steal inside the channel:
+    skred_fxbank_note_on_channel, beside the only route before it -- skred_fxbank_download_owners and skred_fxbank_download behind a
+    device wait, the channel pick and the victim order in numpy, skred_fxbank_update, skred_fxbank_tag_list; (b) the key pass:
+    skred_fxbank_find_steal_match beside skred_fxbank_find_steal on the same range at max_out 0 and 16; (c) the 64-frame block after
+    the burst beside the block after the equivalent skred_fxbank_note_on_steal.  Medians of 12 with minimum and maximum; host time
+    held, and stream time between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES = 1 << 20, 64, 16, 256
+    bank, pool, c0 = X.bank_fx(n)                                         # every voice sounding: a burst can only steal
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    everyone = torch.arange(n, dtype=torch.int32, device="cuda")
+    db.tag_list(everyone.data_ptr(), tags)
+    value, mask = 3 << 24, 0xFF000000
+    per_channel = n // CHANNELS
+    iq = X.FxIdleQueryC(0, n, X.IDLE_FINISHED | X.IDLE_ENV_DONE, 0, 0, 0)
+    sq = X.fx_steal_query(0, n, X.STEAL_OLDEST, 0, 64)
+    notes = X.fx_note_array([X.FxNoteC(3000017 + 40009 * k, 26000, 0, 16384, 16384, X.NOTE_SET_PHASE) for k in range(NOTES)])
+    note_tags = ((3 << 24) | (0x800000 + np.arange(NOTES))).astype(np.uint32)
+    da = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    dr = torch.zeros(4, dtype=torch.int32, device="cuda")
+    dv = torch.full((16,), -1, dtype=torch.int32, device="cuda")
+    dc = torch.zeros(3, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    mirror, state = bank.copy(), bank.copy()
+    starts = bank["sample_start"].astype(np.int64).copy()
+
+    def parent_route():
+        own = db.download_owners()                                        # the device waits the channel call was built to remove
+        db.download(state)
+        mine = (own != 0) & ((own & np.uint32(mask)) == np.uint32(value)) & (state["is_active"] != 0)
+        voices = np.flatnonzero(mine)
+        picks = voices[np.lexsort((voices, starts[voices]))][:NOTES].astype(np.int32)
+        db.update(mirror, picks, X.DIRTY_PARAMS | X.DIRTY_PHASE | X.STAMP_TRIGGER)
+        dl = torch.from_numpy(picks).cuda()
+        db.tag_list(dl.data_ptr(), note_tags[:len(picks)])
+
+    def line(label, call, words, res=None):
+        ms, held = _fx_timed(call)
+        res = dr if res is None else res
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; result words = {res.cpu().numpy().tolist()[:words]}")
+
+    print(f"fx {n} voices all sounding, tagged over {CHANNELS} channels ({per_channel} notes each)")
+    burst = lambda: db.note_on_channel(notes, iq, sq, value, mask, per_channel, note_tags, da.data_ptr(), dr.data_ptr())   # noqa: E731
+    line(f"(a) {NOTES} notes on one channel at its cap, note_on_channel", burst, 4)
+    line("(a) the same, download_owners + download + numpy pick and order + update + tag_list", parent_route, 0)
+    for mo in (0, 16):
+        q = X.fx_steal_query(0, n, X.STEAL_OLDEST, 0, 64, 0, 0, mo)
+        line(f"(b) max_out {mo}, find_steal_match on one channel", lambda: db.find_steal_match(q, value, mask, dv.data_ptr(), dc.data_ptr()), 3, dc)
+        line(f"(b) max_out {mo}, find_steal on the whole range", lambda: db.find_steal(q, dv.data_ptr(), dc.data_ptr()), 2, dc)
+
+    def block_after(call):
+        db.upload(bank); db.set_sample_count(c0)
+        db.tag_list(everyone.data_ptr(), tags)
+        _fx_block_after(db, out, F, None, 8)
+        after = []
+        for _ in range(12):
+            call()
+            after += _fx_block_after(db, out, F, None, 1)
+            _fx_block_after(db, out, F, None, 1)
+        return after
+    steady = _fx_block_after(db, out, F)
+    after_chan = block_after(burst)
+    after_steal = block_after(lambda: db.note_on_steal(notes, iq, sq, da.data_ptr(), dr.data_ptr()))
+    print(f"  (c) the {F}-frame block after the channel burst: {_fx_stats(after_chan)}; after note_on_steal of {NOTES} notes: {_fx_stats(after_steal)}; "
+          f"a steady block: {_fx_stats(steady)}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan, "fxchan": fxchan}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
