@@ -144,7 +144,7 @@ int skred_bank_find_match_host(skred_bank_t *b, int first, int count, int slot_v
   if ((rc = sk_idle_out_room(b, (size_t)max_out))) return rc;
   /* word 0: the total; the list from word 2, as the idle queries lay their answer out */
   if ((rc = find_match_launch(b, first, count, slot_voices, m, max_out, b->d_idle_out + 2, (uint32_t *)b->d_idle_out, s))) return rc;
-  const int written = sk_read_back(b->d_idle_out, b->h_idle_out, max_out, count / slot_voices, slots, s, "find_match_host");
+  const int written = sk_read_back(b->d_idle_out, b->h_idle_out, 2, max_out, count / slot_voices, slots, s, "find_match_host");
   if (written >= 0 && total_out) *total_out = b->h_idle_out[0];
   return written;
 }

@@ -133,7 +133,7 @@ int skred_bank_find_idle_host(skred_bank_t *b, const skred_idle_query_t *q, int3
   if ((rc = sk_idle_out_room(b, (size_t)q->max_out))) return rc;
   rc = idle_launch(b, q, b->d_idle_out + 2, (uint32_t *)b->d_idle_out, s);
   if (rc) return rc;
-  const int written = sk_read_back(b->d_idle_out, b->h_idle_out, q->max_out, q->max_out, voices, s, "find_idle_host");
+  const int written = sk_read_back(b->d_idle_out, b->h_idle_out, 2, q->max_out, q->max_out, voices, s, "find_idle_host");
   if (written >= 0 && total_out) *total_out = b->h_idle_out[1];
   return written;
 }

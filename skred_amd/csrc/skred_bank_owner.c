@@ -88,6 +88,22 @@ void sk_owner_free(skred_bank_t *b) {
   b->d_match_pair = NULL;
 }
 
+/* n >= 1 checked tags -> a staging slot -> the tag kernel: entry k of the list gets tags[k] (the bank's device is current) */
+int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count, int slot_voices,
+                        uint32_t *d_result, const char *who, hipStream_t s) {
+  int rc = sk_owner_ensure(b);
+  if (rc) return rc;
+  const size_t bytes = (size_t)n * sizeof(uint32_t);
+  sk_batch_t bt;
+  if ((rc = sk_batch_begin(b, bytes, s, &bt))) return rc;
+  memcpy(bt.h, tags, bytes);
+  const uint32_t *src = (const uint32_t *)sk_batch_send(b, &bt, bytes, 0, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  const hipError_t e = (hipError_t)sk_launch_owner_tag(b->d_owner, d_slots, src, n, d_count, slot_voices, b->n_voices, d_result, bt.cnt,
+                                                       bt.done, bt.seq, s);
+  return sk_batch_end(&bt, e, who, s);
+}
+
 int skred_bank_tag_slots(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
                          int slot_voices, uint32_t *d_result, void *stream) {
   if (!b || !d_slots) return fail(SKRED_E_BAD_ARG, "tag_slots: no bank or no list");
@@ -96,18 +112,8 @@ int skred_bank_tag_slots(skred_bank_t *b, const int32_t *d_slots, const uint32_t
   if ((rc = sk_check_list_n(n, "tag_slots"))) return rc;
   if ((rc = sk_check_slot_shape(slot_voices, 0, NULL, "tag_slots"))) return rc;
   if (n == 0) return SKRED_OK;
-  hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = sk_owner_ensure(b))) return rc;
-  const size_t bytes = (size_t)n * sizeof(uint32_t);
-  sk_batch_t bt;
-  if ((rc = sk_batch_begin(b, bytes, s, &bt))) return rc;
-  memcpy(bt.h, tags, bytes);
-  const uint32_t *src = (const uint32_t *)sk_batch_send(b, &bt, bytes, 0, s);
-  if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)sk_launch_owner_tag(b->d_owner, d_slots, src, n, d_count_or_null, slot_voices, b->n_voices, d_result,
-                                                       bt.cnt, bt.done, bt.seq, s);
-  return sk_batch_end(&bt, e, "tag_slots", s);
+  return sk_owner_tag_launch(b, d_slots, tags, n, d_count_or_null, slot_voices, d_result, "tag_slots", (hipStream_t)stream);
 }
 
 /* the find pass of n checked tags over a checked range into d_out (on the device) */

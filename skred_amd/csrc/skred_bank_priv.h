@@ -7,7 +7,7 @@
  *   skred_bank_update.c  block-granular updates and the deferred queue
  *   skred_bank_idle.c    the free-voice query                  skred_bank_steal.c  the victim query
  *   skred_bank_notes.c   note-ons and stamps on voices a device-resident list names
- *   skred_bank_slots.c   the same for the slots of a tiled patch, and slot stealing
+ *   skred_bank_slots.c   the same for the slots of a tiled patch, slot stealing, and channel polyphony (matched stealing, capped note-ons)
  *   skred_bank_ctl.c     patch controllers                     skred_bank_owner.c  note owners
  *   skred_bank_expr.c    channels and per-note expression: masked owner matches, per-entry controller values
  */
@@ -192,7 +192,7 @@ struct skred_bank {
   /* voice stealing (skred_bank_steal.c), everything allocated on first use */
   uint32_t *d_steal;                /* the radix select's scratch (skred_launch.h: SK_STEAL_W_*, histogram, counts, offsets, winners, keys) */
   int steal_wgs;
-  int32_t *d_steal_out;             /* [2] counts, then SK_STEAL_MAX victims: skred_bank_find_steal_host's list and skred_bank_note_on_steal's */
+  int32_t *d_steal_out;             /* [2] counts (a matched query: [3]), then SK_STEAL_MAX victims: the _host queries' list and the note-on bursts' */
   int32_t *h_steal_out;             /* ... its pinned twin */
   /* note owners (skred_bank_owner.c), allocated and zeroed by the first call that needs them */
   uint32_t *d_owner;                /* [n_voices] a slot's tag at its first voice, 0: nobody; no render kernel reads it */
@@ -284,6 +284,10 @@ void sk_owner_free(skred_bank_t *b);
 int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
 /* ... and the array itself with the scratch behind it, allocated and zeroed by the first call that needs them (skred_bank_expr.c too) */
 int sk_owner_ensure(skred_bank_t *b);
+/* ... and skred_bank_tag_slots behind its checks, for the channel burst of skred_bank_slots.c: n >= 1 tags through the batch path
+ * into the tag kernel (`who`: the caller, for the error text) */
+int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count, int slot_voices,
+                        uint32_t *d_result, const char *who, hipStream_t s);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);
@@ -313,7 +317,7 @@ int sk_batch_begin(skred_bank_t *b, size_t bytes, hipStream_t s, sk_batch_t *bt)
 const void *sk_batch_send(skred_bank_t *b, sk_batch_t *bt, size_t bytes, int wide, hipStream_t s);
 int sk_batch_end(sk_batch_t *bt, hipError_t e, const char *who, hipStream_t s);
 /* ... the ending of a _host query (plain pointers: the fixed-point bank's too): returns the entries copied to `out`, or an error */
-int sk_read_back(const int32_t *d_out, int32_t *h_out, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
+int sk_read_back(const int32_t *d_out, int32_t *h_out, int counts, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
 /* skred_bank_checks.c (`who`: the entry point, for the error text): K and -- `what` != NULL, its name -- a mask over the K voices;
  * the stamp bits; a list's length (n * K stays an int); a range of whole slots of K voices inside the bank, empty only where
  * allowed; a plain window for the clears and downloads */

@@ -109,14 +109,15 @@ int sk_batch_end(sk_batch_t *bt, hipError_t e, const char *who, hipStream_t s) {
   return SKRED_OK;
 }
 
-/* What a _host query ends in: the device's two report words and max_out entries behind them -> the pinned twin, the stream waited
- * for, the entries handed to the caller.  `bound`: the most report word 0 can honestly say -- max_out where it counts the entries
- * written, the slots of the range where it is a total (skred_bank_find_match_host).  Returns the entries copied to `out`, or an error */
-int sk_read_back(const int32_t *d_out, int32_t *h_out, int max_out, int bound, int32_t *out, hipStream_t s, const char *who) {
-  HIP_TRY(hipMemcpyAsync(h_out, d_out, (2 + (size_t)max_out) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+/* What a _host query ends in: the device's `counts` report words (2; a matched victim query's 3) and max_out entries behind them ->
+ * the pinned twin, the stream waited for, the entries handed to the caller.  `bound`: the most report word 0 can honestly say --
+ * max_out where it counts the entries written, the slots of the range where it is a total (skred_bank_find_match_host).  Returns the
+ * entries copied to `out`, or an error */
+int sk_read_back(const int32_t *d_out, int32_t *h_out, int counts, int max_out, int bound, int32_t *out, hipStream_t s, const char *who) {
+  HIP_TRY(hipMemcpyAsync(h_out, d_out, ((size_t)counts + (size_t)max_out) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (h_out[0] < 0 || h_out[0] > bound) return fail(SKRED_E_NO_DEVICE, "%s: the device reported %d of at most %d", who, h_out[0], bound);
   const int written = h_out[0] < max_out ? h_out[0] : max_out;
-  if (written > 0) memcpy(out, h_out + 2, (size_t)written * sizeof(int32_t));
+  if (written > 0) memcpy(out, h_out + counts, (size_t)written * sizeof(int32_t));
   return written;
 }

@@ -118,8 +118,8 @@ int skred_bank_find_steal(skred_bank_t *b, const skred_steal_query_t *q, int32_t
 }
 
 int sk_steal_out_buffers(skred_bank_t *b) {
-  if (!b->d_steal_out) HIP_TRY(hipMalloc((void **)&b->d_steal_out, (2 + SK_STEAL_MAX) * sizeof(int32_t)));
-  if (!b->h_steal_out) HIP_TRY(hipHostMalloc((void **)&b->h_steal_out, (2 + SK_STEAL_MAX) * sizeof(int32_t), hipHostMallocDefault));
+  if (!b->d_steal_out) HIP_TRY(hipMalloc((void **)&b->d_steal_out, (3 + SK_STEAL_MAX) * sizeof(int32_t)));
+  if (!b->h_steal_out) HIP_TRY(hipHostMalloc((void **)&b->h_steal_out, (3 + SK_STEAL_MAX) * sizeof(int32_t), hipHostMallocDefault));
   return SKRED_OK;
 }
 
@@ -136,7 +136,7 @@ int skred_bank_find_steal_host(skred_bank_t *b, const skred_steal_query_t *q, in
   if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   if ((rc = sk_steal_into_scratch(b, q, s))) return rc;
-  const int written = sk_read_back(b->d_steal_out, b->h_steal_out, q->max_out, q->max_out, voices, s, "find_steal_host");
+  const int written = sk_read_back(b->d_steal_out, b->h_steal_out, 2, q->max_out, q->max_out, voices, s, "find_steal_host");
   if (written >= 0 && total_out) *total_out = b->h_steal_out[1];
   return written;
 }

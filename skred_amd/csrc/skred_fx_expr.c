@@ -138,7 +138,7 @@ int skred_fxbank_find_match_host(skred_fxbank_t *fx, int first, int count, const
   if ((rc = skx_idle_out_room(fx, (size_t)max_out))) return rc;
   /* word 0: the total; the list from word 2, as the idle query lays its answer out */
   if ((rc = find_match_launch(fx, first, count, m, max_out, fx->d_idle_out + 2, (uint32_t *)fx->d_idle_out, s))) return rc;
-  const int written = sk_read_back(fx->d_idle_out, fx->h_idle_out, max_out, count, voices, s, "fx find_match_host");
+  const int written = sk_read_back(fx->d_idle_out, fx->h_idle_out, 2, max_out, count, voices, s, "fx find_match_host");
   if (written >= 0 && total_out) *total_out = fx->h_idle_out[0];
   return written;
 }

@@ -1,5 +1,5 @@
 // skred_fx_idle_common.hpp -- the fixed-point bank's idle predicate, shared by the kernels that ask "is this voice free"
-// (skred_fx_live_kernels.hip: the free-voice list; skred_fx_steal_kernels.hip, skred_fx_chan_kernels.hip: a voice the idle query would list is no candidate
+// (skred_fx_live_kernels.hip: the free-voice list; skred_fx_steal_kernels.hip: a voice the idle query would list is no candidate
 // for stealing).
 #ifndef SKRED_FX_IDLE_COMMON_HPP
 #define SKRED_FX_IDLE_COMMON_HPP

@@ -49,7 +49,6 @@ void skx_live_free(skred_fxbank_t *fx) {
   fx->d_idle = NULL; fx->d_idle_out = NULL; fx->h_idle_out = NULL; fx->d_note_list = NULL;
   fx->idle_wgs = 0; fx->idle_out_cap = 0; fx->note_list_cap = 0;
   skx_steal_free(fx);
-  skx_chan_free(fx);
   skx_owner_free(fx);
 }
 
@@ -256,7 +255,7 @@ int skred_fxbank_find_idle_host(skred_fxbank_t *fx, const skred_fx_idle_query_t 
   if ((rc = skx_idle_out_room(fx, (size_t)q->max_out))) return rc;
   rc = skx_idle_launch(fx, q, fx->d_idle_out + 2, (uint32_t *)fx->d_idle_out, s);
   if (rc) return rc;
-  const int written = sk_read_back(fx->d_idle_out, fx->h_idle_out, q->max_out, q->max_out, voices, s, "fx find_idle_host");
+  const int written = sk_read_back(fx->d_idle_out, fx->h_idle_out, 2, q->max_out, q->max_out, voices, s, "fx find_idle_host");
   if (written >= 0 && total_out) *total_out = fx->h_idle_out[1];
   return written;
 }

@@ -53,6 +53,22 @@ static int launched(skx_slot_t *sl, hipError_t e, const char *what, hipStream_t 
   return rc;
 }
 
+/* n >= 1 checked tags -> a staging slot -> the float bank's tag kernel at K = 1: entry k of the list gets tags[k] (the bank's device
+ * is current) */
+int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count,
+                         uint32_t *d_result, const char *who, hipStream_t s) {
+  int rc = skx_owner_ensure(fx);
+  if (rc) return rc;
+  const size_t bytes = (size_t)n * sizeof(uint32_t);
+  skx_slot_t *sl;
+  if ((rc = skx_ring_take(fx, bytes, &sl))) return rc;
+  memcpy(sl->h, tags, bytes);
+  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
+  const hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, (const uint32_t *)sl->d, n, d_count, 1, fx->n_voices,
+                                                       d_result, NULL, NULL, 0, s);
+  return launched(sl, e, who, s);
+}
+
 int skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
                           uint32_t *d_result, void *stream) {
   if (!fx || !d_voices) return fail(SKRED_E_BAD_ARG, "fx tag_list: no bank or no list");
@@ -60,17 +76,8 @@ int skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uin
   if (rc) return rc;
   if ((rc = sk_check_list_n(n, "fx tag_list"))) return rc;
   if (n == 0) return SKRED_OK;
-  hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
-  if ((rc = skx_owner_ensure(fx))) return rc;
-  const size_t bytes = (size_t)n * sizeof(uint32_t);
-  skx_slot_t *sl;
-  if ((rc = skx_ring_take(fx, bytes, &sl))) return rc;
-  memcpy(sl->h, tags, bytes);
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, (const uint32_t *)sl->d, n, d_count_or_null, 1, fx->n_voices,
-                                                       d_result, NULL, NULL, 0, s);
-  return launched(sl, e, "fx tag_list", s);
+  return skx_owner_tag_launch(fx, d_voices, tags, n, d_count_or_null, d_result, "fx tag_list", (hipStream_t)stream);
 }
 
 /* Stages sorted | perm (| the tags as given, with_tags) of n checked tags and runs the find pass over a checked range into d_out.

@@ -20,14 +20,11 @@ typedef struct {
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* the key pass, then sk_launch_steal_select: SK_STEAL_DIGITS + 3 launches whatever the data, the key pass alone with max_out == 0 */
-int skx_launch_steal(const skx_steal_args_t *args, hipStream_t stream);
-/* skred_fx_steal.c, for skred_fx_chan.c too: the bank's scratch (allocated by the first query, its words zeroed on `s`) and a checked
- * query as the key passes take it -- everything but base, digit and the idle range, which the launchers fill */
-struct skred_fxbank;
-struct skred_fx_steal_query;
-int skx_steal_prepare(struct skred_fxbank *fx, const struct skred_fx_steal_query *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s,
-                      skx_steal_args_t *a);
+/* the key pass, then sk_launch_steal_select: SK_STEAL_DIGITS + 3 launches whatever the data, the key pass alone with max_out == 0.
+ * `owner` != NULL (one word per voice of the bank): the MATCHED query of channel polyphony -- a voice takes part when owner[v] != 0
+ * and (owner[v] & mask) == value, and d_count is uint32[3]: written, total candidates, sounding voices of the match in the range
+ * (the key pass writes all three with max_out == 0).  NULL: value and mask are not looked at, d_count is uint32[2] */
+int skx_launch_steal(const skx_steal_args_t *args, const uint32_t *owner, uint32_t value, uint32_t mask, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
-// skred_fx_steal_common.hpp -- the fixed-point bank's per-voice steal terms, shared by its two key passes
-// (skred_fx_steal_kernels.hip: sk_fx_steal_keys_kernel, every voice of the range; skred_fx_chan_kernels.hip:
-// sk_fx_chan_steal_keys_kernel, the voices of one owner match).  include/skred_amd_fxpt.h states the definition field by field.
+// skred_fx_steal_common.hpp -- the fixed-point bank's per-voice steal terms, for the two instantiations of its key pass
+// (skred_fx_steal_kernels.hip: sk_fx_steal_keys_kernel -- every voice of the range, or the voices of one owner match).
+// include/skred_amd_fxpt.h states the definition field by field.
 #ifndef SKRED_FX_STEAL_COMMON_HPP
 #define SKRED_FX_STEAL_COMMON_HPP
 

@@ -1,6 +1,6 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
  * skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c: voice stealing; skred_fx_owner.c: note owners;
- * skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression; skred_fx_chan.c: channel polyphony). */
+ * skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression; channel polyphony lives in skred_fx_steal.c). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -48,8 +48,7 @@ struct skred_fxbank {
   uint32_t *d_note_list; size_t note_list_cap;             /* skred_fxbank_note_on_idle / _note_on_steal: SKX_NOTE_LIST_WORDS words (the idle
                                                             * query's two counts, the joined list's length), then the list */
   uint32_t *d_steal; int steal_wgs;          /* skred_fxbank_find_steal's scratch, laid out as the float bank's (skred_bank_steal.c) */
-  int32_t *d_steal_out, *h_steal_out;        /* [2] counts, then SK_STEAL_MAX victims: _find_steal_host's list and _note_on_steal's */
-  int32_t *d_chan_out, *h_chan_out;          /* skred_fx_chan.c: [3] counts, then SK_STEAL_MAX victims, device and pinned; NULL until the first call that needs them */
+  int32_t *d_steal_out, *h_steal_out;        /* [2] counts (a matched query: [3]), then SK_STEAL_MAX victims: the _host queries' list and the note-on bursts' */
   uint32_t *d_owner;                         /* note owners (skred_fx_owner.c): one word per voice, 0 nobody; NULL until the first call that needs it */
   int32_t *d_owner_found;                    /* ... and behind it skred_fxbank_release_tags' list, SKRED_OWNER_MAX_TAGS entries */
   uint32_t *d_match_pair;                    /* ... and behind that the two words the count pass of skred_fxbank_find_match fills */
@@ -101,12 +100,13 @@ int skx_ring_guard(skx_slot_t *sl, hipStream_t s);
 /* skred_fx_steal.c */
 void skx_steal_free(skred_fxbank_t *fx);
 
-/* skred_fx_chan.c */
-void skx_chan_free(skred_fxbank_t *fx);
-
 /* skred_fx_owner.c: the owner array (allocated and zero-filled by the first call that needs it), for the guarded controller too */
 void skx_owner_free(skred_fxbank_t *fx);
 int skx_owner_ensure(skred_fxbank_t *fx);
+/* ... and skred_fxbank_tag_list behind its checks, for the channel burst of skred_fx_steal.c: n >= 1 tags through the staging ring
+ * into the tag kernel (`who`: the caller, for the error text) */
+int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count,
+                         uint32_t *d_result, const char *who, hipStream_t s);
 /* skred_fx_ctl.c: the checked record as it travels (the reserved words carry the reciprocals).  Pure host */
 void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
 /* skred_fx_expr.c: the checked entries as they travel -- out[j] = each[perm[j]] (perm NULL: j), the named values word for word, the
@@ -121,7 +121,7 @@ int sk_check_list_n(int n, const char *who);
 int sk_check_slot_range(int n_voices, int first, int count, int K, int allow_empty, const char *who);
 int sk_check_window(int n_voices, int first, int count, const char *who);
 /* skred_bank_stage.c: the ending of a _host query -- returns the entries copied to `out`, or an error */
-int sk_read_back(const int32_t *d_out, int32_t *h_out, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
+int sk_read_back(const int32_t *d_out, int32_t *h_out, int counts, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
 
 /* skred_fx_kernels.hip, skred_fx_live_kernels.hip */
 int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);

@@ -13,9 +13,9 @@
  *   skred_rec_kernels.hip     sk_launch_rec_minmax, sk_rec_partial_floats, sk_launch_rec_convert
  *   skred_idle_kernels.hip    sk_launch_idle, sk_idle_workgroups, sk_launch_named
  *   skred_note_kernels.hip    sk_launch_notes, sk_launch_stamp_list
- *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_steal_select, sk_launch_list_append
+ *   skred_steal_kernels.hip   sk_launch_steal, sk_launch_steal_select, sk_launch_list_append, sk_launch_chan_join
  *   skred_slot_kernels.hip    sk_launch_slots, sk_launch_slot_notes, sk_launch_slot_stamps
- *   skred_slot_steal_kernels.hip  sk_launch_slot_steal
+ *   skred_slot_steal_kernels.hip  sk_launch_slot_steal (plain and matched)
  *   skred_ctl_kernels.hip     sk_launch_ctl_range, sk_launch_ctl_slots, sk_launch_ctl_owned
  *   skred_owner_kernels.hip   sk_launch_owner_tag, sk_launch_owner_find, sk_launch_owner_stamps
  *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each
@@ -23,7 +23,7 @@
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
  * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c, skred_bank_ctl.c, skred_bank_owner.c, skred_bank_expr.c and
- * skred_recorder.c (sk_launch_owner_tag, sk_launch_owner_find, sk_launch_match_find and sk_launch_list_append by the fixed-point
+ * skred_recorder.c (sk_launch_owner_tag, sk_launch_owner_find, sk_launch_match_find, sk_launch_list_append and sk_launch_chan_join by the fixed-point
  * bank's skred_fx_owner.c, skred_fx_expr.c and skred_fx_steal.c too).  A launcher that takes `cnt, done, seq` gets them from the batch path (skred_bank_stage.c: sk_batch_send).
  */
 #ifndef SKRED_LAUNCH_H
@@ -169,6 +169,8 @@ enum { SK_STEAL_W_TICKET = 0,     /* arrival ticket, shared by the launches of a
        SK_STEAL_W_REMAIN,         /* ... of them, how many lie in the histogram bin the digits so far select */
        SK_STEAL_W_PREFIX_LO,      /* the digits fixed so far (after the last digit pass: the threshold key) */
        SK_STEAL_W_PREFIX_HI,
+       SK_CHAN_W_SOUNDING,        /* a matched key pass only (both banks): its workgroups add up the sounding slots of the match here;
+                                     its last arriver stores the sum to d_count[2] and re-arms the word.  The select never touches it */
        SK_STEAL_W_COUNT = 8 };
 typedef struct {
   sk_idle_args_t idle;             /* the exclusion: planes, named set, which = exclude_idle, settle_level (first / end as below) */
@@ -197,6 +199,11 @@ int sk_launch_steal_select(const sk_steal_args_t *args, hipStream_t stream);
  * stolen[0] = copied.  One workgroup: room - at is at most SK_STEAL_MAX entries (src holds no more) */
 int sk_launch_list_append(int32_t *dst, const uint32_t *dst_count, const int32_t *src, const uint32_t *src_count, int room,
                           uint32_t *out_count, uint32_t *stolen, hipStream_t stream);
+/* The join of a capped burst (channel polyphony, both banks).  One workgroup.  I = min(idle_count[0], n), S = victim_count[2],
+ * V = min(victim_count[0], SK_STEAL_MAX): a = min(n, I, cap > S ? cap - S : 0), b = min(n - a, V); list[a + t] = victims[t] for
+ * t < b; out_count[0] = a + b; d_result[2] = b, d_result[3] = S.  `list` has room for n entries */
+int sk_launch_chan_join(int32_t *list, const uint32_t *idle_count, const int32_t *victims, const uint32_t *victim_count, int n,
+                        uint32_t cap, uint32_t *out_count, uint32_t *d_result, hipStream_t stream);
 
 /* ---- patch notes: idle slots, and notes and stamps on the voices of listed slots (skred_bank_slots.c -> skred_slot_kernels.hip;
  * include/skred_amd.h: skred_bank_find_idle_slots / _notes_on_slots / _stamp_slots) ----
@@ -227,8 +234,13 @@ int sk_launch_slot_stamps(const int32_t *d_slots, int n, const uint32_t *d_count
  * sk_launch_steal with another key pass: one key per SLOT of slot_voices voices, stored at the slot's first voice (every other voice
  * of the spans holds SK_STEAL_NOKEY), made of the terms of the voices with a bit in member_mask; then sk_launch_steal_select as it
  * is.  `args` as for sk_launch_steal (first and end multiples of slot_voices, never SK_STEAL_UNNAMED / SK_IDLE_UNNAMED); d_voices
- * receives first voices of slots.  max_out == 0: the key pass alone, which writes d_count */
-int sk_launch_slot_steal(const sk_steal_args_t *args, uint64_t member_mask, int slot_voices, hipStream_t stream);
+ * receives first voices of slots.  max_out == 0: the key pass alone, which writes d_count.
+ * `owner` != NULL (one word per voice of the bank): the MATCHED query of channel polyphony (include/skred_amd.h: "channel
+ * polyphony") -- a slot takes part when owner[first voice] != 0 and (owner & mask) == value, and d_count is uint32[3]: written, total
+ * candidates, sounding slots of the match in the range (the key pass writes all three with max_out == 0).  NULL: value and mask are
+ * not looked at, d_count is uint32[2] */
+int sk_launch_slot_steal(const sk_steal_args_t *args, uint64_t member_mask, int slot_voices, const uint32_t *owner, uint32_t value,
+                         uint32_t mask, hipStream_t stream);
 
 /* ---- patch controllers (skred_bank_ctl.c -> skred_ctl_kernels.hip; include/skred_amd.h: skred_bank_ctl_range / _ctl_slots) ----
  * A controller record is skred_ctl_t word for word (layout and bits checked at compile time in skred_bank_ctl.c): word 0 names the

@@ -4,6 +4,8 @@
 // and lets its last arriver pick the first bin with sk_steal_pick; nothing behind it reads a plane.
 // The float bank has two key passes -- one key per voice (sk_steal_keys_kernel) and one per slot of a tiled patch
 // (skred_slot_steal_kernels.hip: sk_slot_steal_keys_kernel); the per-voice terms both are made of are stated once, below.
+// The slot key pass and the fixed-point one have a MATCHED instantiation each (one channel's victims: an owner guard in front, and a
+// count of the match's sounding slots beside the keys); the count is stated once, at the end.
 #ifndef SKRED_STEAL_COMMON_HPP
 #define SKRED_STEAL_COMMON_HPP
 
@@ -140,6 +142,36 @@ __device__ __forceinline__ void sk_steal_pick(const sk_steal_args_t &a, int digi
     a.words[SK_STEAL_W_REMAIN] = remain - run;
     a.words[SK_STEAL_W_PREFIX_LO] = (uint32_t)longer;
     a.words[SK_STEAL_W_PREFIX_HI] = (uint32_t)(longer >> 32);
+  }
+}
+
+// ---- the sounding count of a matched key pass: how many slots (voices) of the match sound in the range, candidates or not.  Each
+// wave counts with one ballot, the SK_STEAL_WAVES counts meet in LDS, and ONE lane per workgroup adds the sum to word
+// SK_CHAN_W_SOUNDING of the steal scratch (workgroups without a sounding slot add nothing).  The last arriver -- sk_arrive_last,
+// after the adds of every workgroup have left their CUs -- stores the sum to d_count[2] and re-arms the word.
+#define SK_STEAL_WAVES (SK_IDLE_SPAN / 64)
+
+// sk_steal_histogram with one workgroup's share of the count around it: `snd` is the wave's ballot of its sounding lanes (taken with
+// the whole wavefront active), `row` SK_STEAL_WAVES words of LDS.  The histogram's barriers stand between the waves' stores to the
+// row and the sum, which is why the two travel together
+__device__ __forceinline__ void sk_steal_histogram_sounding(const sk_steal_args_t &a, bool counted, uint32_t digit, uint32_t *hist,
+                                                            uint32_t *row, unsigned long long snd, int tid) {
+  if ((tid & 63) == 0) row[tid >> 6] = (uint32_t)__popcll(snd);
+  sk_steal_histogram(a, counted, digit, hist, tid);
+  if (tid == 0) {
+    uint32_t sum = 0;
+#pragma unroll
+    for (int w = 0; w < SK_STEAL_WAVES; ++w) sum += row[w];
+    if (sum) __hip_atomic_fetch_add((sk_gu32 *)(a.words + SK_CHAN_W_SOUNDING), sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// the last arriver's publish-and-re-arm (every thread of the workgroup that sk_arrive_last let through calls it)
+__device__ __forceinline__ void sk_steal_sounding_publish(const sk_steal_args_t &a, int tid) {
+  if (tid == 0) {
+    sk_gu32 *w = (sk_gu32 *)(a.words + SK_CHAN_W_SOUNDING);
+    a.d_count[2] = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(w, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // re-armed for the next query (stream-ordered)
   }
 }
 

@@ -30,6 +30,9 @@
 //
 //   sk_list_append_kernel    skred_bank_note_on_steal: the victims copied behind the idle list's entries, at the offset the idle
 //                            query's count word holds on the device.
+//   sk_chan_join_kernel      skred_bank_note_on_channel (and the fixed-point bank's): one workgroup -- how many notes of a burst take
+//                            idle slots (the cap minus the channel's sounding count), how many steal, the victims copied behind the
+//                            idle slots that are used.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -207,6 +210,21 @@ __global__ __launch_bounds__(SK_STEAL_MAX) void sk_list_append_kernel(int32_t *d
   if (t == 0) { out_count[0] = at + n; stolen[0] = n; }
 }
 
+__global__ __launch_bounds__(SK_STEAL_MAX) void sk_chan_join_kernel(int32_t *list, const uint32_t *idle_count, const int32_t *victims,
+                                                                    const uint32_t *victim_count, int n, uint32_t cap,
+                                                                    uint32_t *out_count, uint32_t *d_result) {
+  const uint32_t un = (uint32_t)n;
+  const uint32_t idle = idle_count[0] < un ? idle_count[0] : un;
+  const uint32_t snd = victim_count[2];
+  const uint32_t room = cap > snd ? cap - snd : 0u;
+  uint32_t a = idle < room ? idle : room;                      // (<= n: `idle` is)
+  uint32_t b = victim_count[0] < (uint32_t)SK_STEAL_MAX ? victim_count[0] : (uint32_t)SK_STEAL_MAX;
+  if (b > un - a) b = un - a;
+  const uint32_t t = threadIdx.x;
+  if (t < b) list[a + t] = victims[t];                         // (a + t < a + b <= n: inside the list)
+  if (t == 0) { out_count[0] = a + b; d_result[2] = b; d_result[3] = snd; }
+}
+
 // everything behind a key pass: it reads a.keys and the words the key pass's last arriver left, never a plane
 extern "C" int sk_launch_steal_select(const sk_steal_args_t *args, hipStream_t stream) {
   sk_steal_args_t a = *args;
@@ -243,5 +261,12 @@ extern "C" int sk_launch_steal(const sk_steal_args_t *args, hipStream_t stream) 
 extern "C" int sk_launch_list_append(int32_t *dst, const uint32_t *dst_count, const int32_t *src, const uint32_t *src_count, int room,
                                      uint32_t *out_count, uint32_t *stolen, hipStream_t stream) {
   hipLaunchKernelGGL(sk_list_append_kernel, dim3(1), dim3(SK_STEAL_MAX), 0, stream, dst, dst_count, src, src_count, room, out_count, stolen);
+  return (int)hipGetLastError();
+}
+
+extern "C" int sk_launch_chan_join(int32_t *list, const uint32_t *idle_count, const int32_t *victims, const uint32_t *victim_count,
+                                   int n, uint32_t cap, uint32_t *out_count, uint32_t *d_result, hipStream_t stream) {
+  hipLaunchKernelGGL(sk_chan_join_kernel, dim3(1), dim3(SK_STEAL_MAX), 0, stream, list, idle_count, victims, victim_count, n, cap,
+                     out_count, d_result);
   return (int)hipGetLastError();
 }

@@ -2,11 +2,11 @@
  * touches the device, on a skred_bank_t that is nothing but its voice count (a refused call reads no other member), and the way the
  * burst's two queries are packed (the library's overrides: a steal query that would be refused in the fields the library overrides
  * passes, one that is wrong elsewhere does not).  One line per case, "OK" last.
- * tests/test_chan_cpu.py builds and runs it; built together with skred_amd/csrc/skred_bank_chan.c and -fsanitize=address,undefined it
+ * tests/test_chan_cpu.py builds and runs it; built together with skred_amd/csrc/skred_bank_slots.c and -fsanitize=address,undefined it
  * is the sanitizer run of that file's host code -- from the repository root, after the library is built (the program's own copy of
- * skred_bank_chan.c takes the place of the library's; everything else it calls comes from the library):
+ * skred_bank_slots.c takes the place of the library's; everything else it calls comes from the library):
  *   gcc -O1 -g -Wall -Werror -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iskred_amd/csrc \
- *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_chan_host.c skred_amd/csrc/skred_bank_chan.c -o /tmp/c_chan_host_san \
+ *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_chan_host.c skred_amd/csrc/skred_bank_slots.c -o /tmp/c_chan_host_san \
  *       -Lskred_amd -lskred_amd -L${ROCM_PATH:-/opt/rocm}/lib -lamdhip64 -lm -lpthread \
  *       -Wl,-rpath,$PWD/skred_amd -Wl,-rpath,${ROCM_PATH:-/opt/rocm}/lib && /tmp/c_chan_host_san */
 #include <math.h>

@@ -2,11 +2,11 @@
  * points make before anything touches the device, on a skred_fxbank_t that is nothing but its voice count (a refused call reads no
  * other member), and the way the burst's two queries are packed (the library's overrides: a steal query that would be refused in the
  * fields the library overrides passes, one that is wrong elsewhere does not).  One line per case, "OK" last.
- * tests/test_fx_chan_cpu.py builds and runs it; built together with skred_amd/csrc/skred_fx_chan.c and -fsanitize=address,undefined it
+ * tests/test_fx_chan_cpu.py builds and runs it; built together with skred_amd/csrc/skred_fx_steal.c and -fsanitize=address,undefined it
  * is the sanitizer run of that file's host code -- from the repository root, after the library is built (the program's own copy of
- * skred_fx_chan.c takes the place of the library's; everything else it calls comes from the library):
+ * skred_fx_steal.c takes the place of the library's; everything else it calls comes from the library):
  *   gcc -O1 -g -Wall -Werror -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iskred_amd/csrc \
- *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_fx_chan_host.c skred_amd/csrc/skred_fx_chan.c -o /tmp/c_fx_chan_host_san \
+ *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_fx_chan_host.c skred_amd/csrc/skred_fx_steal.c -o /tmp/c_fx_chan_host_san \
  *       -Lskred_amd -lskred_amd -L${ROCM_PATH:-/opt/rocm}/lib -lamdhip64 -lm -lpthread \
  *       -Wl,-rpath,$PWD/skred_amd -Wl,-rpath,${ROCM_PATH:-/opt/rocm}/lib && /tmp/c_fx_chan_host_san */
 #include <stdio.h>
@@ -169,8 +169,8 @@ int main(void) {
 
   CASE("untouched/outputs", cnt[0] == 7 && cnt[1] == 7 && cnt[2] == 7 && res[0] == 7 && res[1] == 7 && res[2] == 7 && res[3] == 7 && total == 7 &&
                             sounding == 7 && list[0] == -1 && list[15] == -1 && assigned[0] == -1 && assigned[3] == -1);
-  CASE("untouched/bank", fx->ring_head == 0 && !fx->d_owner && !fx->d_steal && !fx->d_idle && !fx->d_chan_out && !fx->h_chan_out &&
-                         !fx->d_note_list && !fx->d_steal_out && fx->count == 0);
+  CASE("untouched/bank", fx->ring_head == 0 && !fx->d_owner && !fx->d_steal && !fx->d_idle && !fx->d_steal_out && !fx->h_steal_out &&
+                         !fx->d_note_list && fx->count == 0);
   free(notes);
   free(fx);
   puts(failures ? "FAILED" : "OK");

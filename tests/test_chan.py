@@ -132,6 +132,50 @@ def test_query_scenes(dev, K):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("K", [1, 4, 64])
+def test_matched_key_pass_with_mask_zero_is_the_plain_one(dev, K):
+    """The two instantiations of the slot key pass on one bank of 600 voices, every slot tagged, match (0, 0): the list and the first
+    two count words are find_steal_slots's bytes.  The range starts off a 64-voice boundary (K = 64, whose slots are 64-aligned:
+    at voice 64, which moves the span edge to 320) and crosses a 256-voice workgroup span with sounding slots on both sides, so two workgroups add to
+    the sounding word and the last arriver publishes it; each matched query runs twice in a row on one stream with no host wait
+    between the two: the second starts from a re-armed word."""
+    import torch
+    n, mask = 600, (1 << K) - 1
+    first = {1: 37, 4: 36, 64: 64}[K]
+    count = (n - n % K) - first
+    edge = (first & ~63) + 256                                                   # where the second workgroup's span begins
+    db, truth, now = reach(dev, n, K, mask)
+    try:
+        own = np.full(n, 5, np.uint32)
+        set_owners(db, own, K)
+        for policy, flags in ((OLDEST, 0), (QUIETEST, RELEASED_ONLY)):           # (RELEASED_ONLY: fewer candidates than sounding slots)
+            for max_out in (0, 5):
+                q = M.SlotQuery(first, count, K, mask, policy=policy, flags=flags, max_out=max_out, exclude_idle=S.EXCLUDE,
+                                settle_level=float(S.SETTLE))
+                want, counts = CM.query(truth, now, q, own, (0, 0))
+                left = CM.query(truth, now, q.but(count=edge - first), own, (0, 0))[1][2]
+                assert 0 < left < counts[2], "both workgroups must have sounding slots to add"
+                pv = torch.full((max_out + 8,), -1, dtype=torch.int32, device="cuda")
+                pc = torch.full((4,), -1, dtype=torch.int32, device="cuda")
+                dv = [torch.full((max_out + 8,), -1, dtype=torch.int32, device="cuda") for _ in range(2)]
+                dc = [torch.full((4,), -1, dtype=torch.int32, device="cuda") for _ in range(2)]
+                torch.cuda.synchronize()
+                db.find_steal_slots(q.c(), pv.data_ptr(), pc.data_ptr())
+                for i in range(2):
+                    db.find_steal_slots_match(q.c(), device.owner_match(0, 0), dv[i].data_ptr(), dc[i].data_ptr())
+                torch.cuda.synchronize()
+                pv, pc = pv.cpu().numpy(), pc.cpu().numpy()
+                assert pc[:2].tolist() == counts[:2] and (pc[2:] == -1).all() and np.array_equal(pv[:counts[0]], want), (q, pc)
+                for i in range(2):
+                    gv, gc = dv[i].cpu().numpy(), dc[i].cpu().numpy()
+                    print(f"K {K} policy {policy} max_out {max_out} run {i}: plain {pc[:2].tolist()} matched {gc.tolist()}")
+                    assert gv.tobytes() == pv.tobytes() and gc[:2].tobytes() == pc[:2].tobytes(), (q, i)
+                    assert gc[2] == counts[2] and gc[3] == -1, (q, i, gc.tolist(), counts)
+    finally:
+        db.close()
+
+
+@pytest.mark.gpu
 def test_ties_at_the_threshold_inside_one_channel(dev):
     """70 000 voices, every slot with the same key, the two channels interleaved: the list is the channel's first voices in index
     order, however short; the other channel's slots lie between them."""

@@ -138,7 +138,7 @@ def host_lines(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("chan") / "c_chan_host")
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     cmd = ["gcc", "-O1", "-Wall", "-Werror", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + os.path.join(rocm, "include"),
-           os.path.join(HERE, "c_chan_host.c"), os.path.join(CSRC, "skred_bank_chan.c"), "-o", exe, "-L" + os.path.join(ROOT, "skred_amd"),
+           os.path.join(HERE, "c_chan_host.c"), os.path.join(CSRC, "skred_bank_slots.c"), "-o", exe, "-L" + os.path.join(ROOT, "skred_amd"),
            "-lskred_amd", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-lm", "-lpthread", "-Wl,-rpath," + os.path.join(ROOT, "skred_amd"),
            "-Wl,-rpath," + os.path.join(rocm, "lib")]
     out = subprocess.run(cmd, capture_output=True, text=True)

@@ -131,6 +131,41 @@ def test_fx_chan_mask_zero_with_everything_tagged_is_find_steal():
         twin.close()
 
 
+def test_fx_matched_key_pass_with_mask_zero_is_the_plain_one():
+    """The two instantiations of the fixed-point key pass on one bank of 600 voices, every voice tagged, match (0, 0): the list and
+    the first two count words are find_steal's bytes.  The range starts off a 64-voice boundary and crosses a 256-voice workgroup
+    span with sounding voices on both sides, so two workgroups add to the sounding word and the last arriver publishes it; each
+    matched query runs twice in a row on one stream with no host wait between the two: the second starts from a re-armed word."""
+    import torch
+    n, first = 600, 37
+    count, edge = n - first, 256
+    own = np.full(n, 5, np.uint32)
+    db, ref, pool, cnt = reach(n, "plain", own)
+    try:
+        for policy, flags in ((OLDEST, 0), (QUIETEST, RELEASED_ONLY)):           # (RELEASED_ONLY: fewer candidates than sounding voices)
+            for max_out in (0, 5):
+                q = Query(first, count, policy, flags, 0, FIN | ENV, 3, max_out)
+                want, counts = CM.query(ref, cnt, q, own, (0, 0))
+                left = CM.query(ref, cnt, q.but(count=edge - first), own, (0, 0))[1][2]
+                assert 0 < left < counts[2], "both workgroups must have sounding voices to add"
+                pv, pc = dev_i32(max_out + 8), dev_i32(5)
+                dv, dc = [dev_i32(max_out + 8) for _ in range(2)], [dev_i32(5) for _ in range(2)]
+                torch.cuda.synchronize()
+                db.find_steal(q.c(), pv.data_ptr() if max_out > 0 else 0, pc.data_ptr())
+                for i in range(2):
+                    db.find_steal_match(q.c(), 0, 0, dv[i].data_ptr() if max_out > 0 else 0, dc[i].data_ptr())
+                torch.cuda.synchronize()
+                pv, pc = host_of(pv), host_of(pc)
+                assert pc[:2].tolist() == counts[:2] and (pc[2:] == -7).all() and np.array_equal(pv[:counts[0]], want), (q, pc)
+                for i in range(2):
+                    gv, gc = host_of(dv[i]), host_of(dc[i])
+                    print(f"policy {policy} flags {flags} max_out {max_out} run {i}: plain {pc[:2].tolist()} matched {gc.tolist()}")
+                    assert gv.tobytes() == pv.tobytes() and gc[:2].tobytes() == pc[:2].tobytes(), (q, i)
+                    assert gc[2] == counts[2] and (gc[3:] == -7).all(), (q, i, gc.tolist(), counts)
+    finally:
+        db.close()
+
+
 def test_fx_chan_query_reads_the_bank_only():
     """A bank queried between its blocks against a twin that is never queried (and never tagged): state, parameters, mix and master
     gain bit for bit.  Two queries in a row give the same counts (the count word was re-armed), and skred_fxbank_find_steal behind a

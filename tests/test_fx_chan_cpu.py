@@ -31,7 +31,7 @@ def test_symbols_match_the_header():
         assert s in fxb.FX_ABI_SYMBOLS + fxb.FX_HOST_ABI_SYMBOLS
     assert "skred_fx_chan_check" in fxb.FX_HOST_ABI_SYMBOLS
     assert fxb.CHAN_NO_CAP == CM.NO_CAP == 0xFFFFFFFF
-    for hdr in ("include/skred_amd.h", "skred_amd/csrc/skred_bank_chan.c", "DESIGN.md"):       # the twin is no longer out of scope
+    for hdr in ("include/skred_amd.h", "skred_amd/csrc/skred_bank_slots.c", "DESIGN.md"):       # the twin is no longer out of scope
         assert "a twin on the fixed-point bank" not in open(os.path.join(ROOT, hdr)).read(), hdr
 
 
@@ -146,7 +146,7 @@ def host_lines(tmp_path_factory):
     exe = str(tmp_path_factory.mktemp("fxchan") / "c_fx_chan_host")
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     cmd = ["gcc", "-O1", "-Wall", "-Werror", "-std=gnu11", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-I" + os.path.join(rocm, "include"),
-           os.path.join(HERE, "c_fx_chan_host.c"), os.path.join(CSRC, "skred_fx_chan.c"), "-o", exe, "-L" + os.path.join(ROOT, "skred_amd"),
+           os.path.join(HERE, "c_fx_chan_host.c"), os.path.join(CSRC, "skred_fx_steal.c"), "-o", exe, "-L" + os.path.join(ROOT, "skred_amd"),
            "-lskred_amd", "-L" + os.path.join(rocm, "lib"), "-lamdhip64", "-lm", "-lpthread", "-Wl,-rpath," + os.path.join(ROOT, "skred_amd"),
            "-Wl,-rpath," + os.path.join(rocm, "lib")]
     out = subprocess.run(cmd, capture_output=True, text=True)
