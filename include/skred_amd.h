@@ -1053,6 +1053,95 @@ int  skred_bank_note_on_channel(skred_bank_t *bank, const skred_slot_query_t *id
                                 const skred_owner_match_t *m, uint32_t cap, const skred_note_t *notes, const uint32_t *tags, int n,
                                 uint64_t voice_mask, int32_t *d_assigned, uint32_t *d_result, void *stream);
 
+/* ---- pedals: sustain and sostenuto hold note-offs back on the device --------------------------------------------------------
+ *
+ * Under a sustain pedal (MIDI CC 64) a note-off is remembered per sounding note and executed when the pedal goes up; the sostenuto
+ * pedal (CC 66) does the same for the notes that were held down when IT went down.  Which slot holds a note is device state (notes
+ * land on idle slots and steal slots there), so a host that kept its own list of pending note-offs would release the wrong note
+ * after a theft, and would need a read-back behind a stream wait on every pedal-up.  These calls keep the pedal state beside the
+ * owner word instead.
+ *
+ * pedal[n_voices] is a uint32 array in device memory that only the calls of this section read or write; a slot's word is the word at
+ * its FIRST voice.  SKRED_PEDAL_PENDING: a note-off arrived and was held back.  SKRED_PEDAL_LATCHED: sostenuto caught this note.
+ * The bank allocates the array (4 bytes per voice) behind the owner array on the first call of this section other than _pedal_clear
+ * and _download_pedals and zero-fills it; that call waits for the device once, as the first owner call does.  No render kernel, probe,
+ * tap, report or planner rule reads the word: blocks rendered with and without pedal calls that hold nothing are bit-identical.
+ *
+ * A NEW NOTE CLEARS THE WORD.  The natural tag is channel << 24 | key, and keys are struck again: once the array exists, every tag
+ * launch of the bank (skred_bank_tag_slots, the tags of skred_bank_note_on_channel) is followed on its stream by a launch that stores
+ * 0 into the pedal word of every slot it tagged -- the same list, the same min(n, *d_count) rule, the same "is a slot" rule.  So a
+ * thief's tag call clears its victim's bits, and a key struck again under the pedal (the same slot in the same block in mono mode)
+ * starts clean: the pedal-up releases the old note-off's slot only if the old note is still the one that sounds there.  A bank that
+ * never made a pedal call launches nothing more.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring; nothing
+ * waits for the device; results are pure functions of the state, whatever the order of arrival; one stream at a time per bank.  A
+ * slot, K = slot_voices, voice_mask, tags and matches mean what they mean in the three sections above.
+ *
+ * Stated behaviour: a pending note ranks in the steal queries as the held note it is (its envelope has no release clock).
+ * skred_bank_stamp_match / _release_tags / _stamp_owned on a pending slot stamp at once and LEAVE the bit: a later pedal_up stamps
+ * again, as a second amp_envelope_release of the reference would -- "all notes off" under a pedal is therefore skred_bank_pedal_up or
+ * _pedal_clear first.  Tagged and untagged note-ons still must not share a range.
+ * Not built here: the fixed-point bank's twin of these calls, the drop-in mode, deferred items and pattern steps, shards beyond
+ * skred_shard_bank(). */
+enum { SKRED_PEDAL_PENDING = 1u << 0, SKRED_PEDAL_LATCHED = 1u << 1 };
+enum { SKRED_PEDAL_LIFT_SUSTAIN = 1u << 0,     /* the sustain pedal goes up */
+       SKRED_PEDAL_LIFT_SOSTENUTO = 1u << 1,   /* the sostenuto pedal goes up */
+       SKRED_PEDAL_SUSTAIN_DOWN = 1u << 2 };   /* sostenuto lifts while sustain stays down: pending notes stay pending */
+enum { SKRED_PEDAL_CALL_STAMP_OWNED = 0, SKRED_PEDAL_CALL_RELEASE_TAGS, SKRED_PEDAL_CALL_LATCH, SKRED_PEDAL_CALL_UP };
+/* Pure host, no device: what the entry point named by `call` refuses about everything but its pointers to the bank, the list and the
+ * result, in the order it checks.  Arguments a call does not take are not looked at (STAMP_OWNED: first, count, m, flags;
+ * RELEASE_TAGS: m, flags; LATCH: tags, n, flags; UP: tags, n).
+ *   STAMP_OWNED   SKRED_E_BAD_ARG: NULL tags, n < 0, a zero tag, n > INT32_MAX / 64, a bad voice_mask; SKRED_E_RANGE: a bad K.
+ *   RELEASE_TAGS  SKRED_E_BAD_ARG: what skred_owner_tags_check(UNIQUE) refuses, a zero tag, a bad voice_mask; SKRED_E_RANGE: a bad K,
+ *                 first or count not a multiple of K, count <= 0, a range outside the bank of n_voices voices.
+ *   LATCH         SKRED_E_BAD_ARG: what skred_owner_match_check refuses, a bad voice_mask; SKRED_E_RANGE as above.
+ *   UP            the same, and SKRED_E_BAD_ARG for flags with unknown bits, without a LIFT bit, or with SUSTAIN_DOWN and LIFT_SUSTAIN.
+ * An unknown `call`: SKRED_E_BAD_ARG.  Every entry point below calls it before anything touches the device; a refused call writes
+ * nothing. */
+int  skred_pedal_check(int call, int n_voices, int first, int count, int slot_voices, uint64_t voice_mask, const skred_owner_match_t *m,
+                       uint32_t flags, const uint32_t *tags, int n);
+/* skred_bank_stamp_owned with the stamp fixed to SKRED_STAMP_RELEASE and one more decision per entry whose owner equals its tag:
+ * hold_all != 0 (the host knows the channel's sustain pedal is down) or a LATCHED slot -> pedal[slot] |= PENDING and nothing is
+ * stamped; otherwise the slot is stamped exactly as skred_bank_stamp_owned stamps it.  d_result (device, uint32[4], required) is
+ * cleared on the stream ahead of the kernel: [0] slots stamped, [1] slots whose owner differs, [2] entries that are no slot,
+ * [3] slots held back.  A slot named twice ends with the same word and the same clocks as named once; it is counted twice.  With
+ * hold_all == 0 on a bank where nothing is latched, the bank's bytes and words 0..2 are skred_bank_stamp_owned's.  The motion-list
+ * bound grows by n * popcount(voice_mask).  n == 0: SKRED_OK, nothing is done.
+ * Refused: NULL bank, list or result, what skred_pedal_check(STAMP_OWNED) refuses. */
+int  skred_bank_stamp_owned_pedal(skred_bank_t *bank, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                                  int slot_voices, uint64_t voice_mask, int hold_all, uint32_t *d_result, void *stream);
+/* Note-off by note id under the pedals: skred_bank_release_tags' find pass into the same scratch -- each tag reaches at most ONE
+ * slot, the lowest of [first, first + count) that carries it -- then the call above on that list.  d_result as above; [2] counts the
+ * tags nobody in the range carries, [1] is 0.  Refused: NULL bank or result, what skred_pedal_check(RELEASE_TAGS) refuses. */
+int  skred_bank_release_tags_pedal(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t voice_mask, const uint32_t *tags,
+                                   int n, int hold_all, uint32_t *d_result, void *stream);
+/* Sostenuto down, in one pass over the range, no list: a slot that matches m gets LATCHED when its PENDING bit is clear AND at least
+ * one voice_mask voice is HELD -- voice_use_amp_envelope != 0 && is_active != 0 && sample_release == 0, the terms live and released of
+ * skred_slot_steal_query_t, on the fields as the device holds them at that point of the stream.  Notes struck later are not caught
+ * (their tag launch clears the word), nor notes whose note-off is already pending.  d_result (device, uint32[2], required) is
+ * cleared on the stream ahead of the kernel: [0] slots that satisfy the rule (latched now or before), [1] slots of the range that
+ * did not match.  Reads the planes and writes the pedal array only: the planner is told nothing.
+ * Refused: NULL bank or result, what skred_pedal_check(LATCH) refuses. */
+int  skred_bank_pedal_latch(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t voice_mask, const skred_owner_match_t *m,
+                            uint32_t *d_result, void *stream);
+/* A pedal goes up, in one pass over the matching slots of the range.  flags: at least one of LIFT_SUSTAIN and LIFT_SOSTENUTO;
+ * SUSTAIN_DOWN (the host says sustain stays down while sostenuto lifts) is refused together with LIFT_SUSTAIN.  With LIFT_SOSTENUTO
+ * the slot's LATCHED bit is cleared.  A slot that is then PENDING, not LATCHED and not kept by SUSTAIN_DOWN gets skred_bank_stamp_slots'
+ * SKRED_STAMP_RELEASE on its voice_mask voices, and its PENDING bit is cleared: the release clock is this call's, not the note-off's.
+ * d_result (device, uint32[3], required) is cleared on the stream ahead of the kernel: [0] slots released, [1] slots still pending
+ * after the call, [2] slots of the range that did not match.  The planner is told what skred_bank_stamp_match on the same range
+ * tells it: (count / K) * popcount(voice_mask) more voices may be on the motion list.
+ * Refused: NULL bank or result, what skred_pedal_check(UP) refuses. */
+int  skred_bank_pedal_up(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t voice_mask, const skred_owner_match_t *m,
+                         uint32_t flags, uint32_t *d_result, void *stream);
+/* pedal[first .. first + count) = 0 on `stream` (nothing to do on a bank without a pedal array).  SKRED_E_RANGE: count < 0 or a
+ * range outside the bank. */
+int  skred_bank_pedal_clear(skred_bank_t *bank, int first, int count, void *stream);
+/* The pedal words of [first, first + count) into host_u32; waits for the device, like skred_bank_download; zeros on a bank without
+ * a pedal array. */
+int  skred_bank_download_pedals(skred_bank_t *bank, uint32_t *host_u32, int first, int count);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

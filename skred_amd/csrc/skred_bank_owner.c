@@ -88,7 +88,9 @@ void sk_owner_free(skred_bank_t *b) {
   b->d_match_pair = NULL;
 }
 
-/* n >= 1 checked tags -> a staging slot -> the tag kernel: entry k of the list gets tags[k] (the bank's device is current) */
+/* n >= 1 checked tags -> a staging slot -> the tag kernel: entry k of the list gets tags[k] (the bank's device is current).  A bank
+ * that has a pedal array (skred_bank_pedal.c) clears the tagged slots' pedal words right behind it: a new note starts with no bit
+ * of the note it replaces */
 int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count, int slot_voices,
                         uint32_t *d_result, const char *who, hipStream_t s) {
   int rc = sk_owner_ensure(b);
@@ -99,8 +101,9 @@ int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t 
   memcpy(bt.h, tags, bytes);
   const uint32_t *src = (const uint32_t *)sk_batch_send(b, &bt, bytes, 0, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)sk_launch_owner_tag(b->d_owner, d_slots, src, n, d_count, slot_voices, b->n_voices, d_result, bt.cnt,
-                                                       bt.done, bt.seq, s);
+  hipError_t e = (hipError_t)sk_launch_owner_tag(b->d_owner, d_slots, src, n, d_count, slot_voices, b->n_voices, d_result, bt.cnt, bt.done,
+                                                 bt.seq, s);
+  if (e == hipSuccess && b->d_pedal) e = (hipError_t)sk_launch_pedal_clear(b->d_pedal, d_slots, n, d_count, slot_voices, b->n_voices, s);
   return sk_batch_end(&bt, e, who, s);
 }
 
@@ -116,8 +119,8 @@ int skred_bank_tag_slots(skred_bank_t *b, const int32_t *d_slots, const uint32_t
   return sk_owner_tag_launch(b, d_slots, tags, n, d_count_or_null, slot_voices, d_result, "tag_slots", (hipStream_t)stream);
 }
 
-/* the find pass of n checked tags over a checked range into d_out (on the device) */
-static int find_launch(skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, int32_t *d_out, hipStream_t s) {
+/* the find pass of n checked tags over a checked range into d_out (on the device); skred_bank_pedal.c runs it too */
+int sk_owner_find_launch(skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, int32_t *d_out, hipStream_t s) {
   const size_t bytes = 2 * (size_t)n * sizeof(uint32_t);
   /* one workgroup per 256 slots stages the tags: beyond a handful of workgroups they read the slot's device twin, not the bus */
   const int wide = (count / slot_voices) > 64 * SK_OWNER_SPAN;
@@ -147,7 +150,7 @@ int skred_bank_find_owned(skred_bank_t *b, int first, int count, int slot_voices
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
-  return find_launch(b, first, count, slot_voices, tags, n, d_slots_out, (hipStream_t)stream);
+  return sk_owner_find_launch(b, first, count, slot_voices, tags, n, d_slots_out, (hipStream_t)stream);
 }
 
 /* the guarded stamps of n checked tags on a list in device memory */
@@ -193,7 +196,7 @@ int skred_bank_release_tags(skred_bank_t *b, int first, int count, int slot_voic
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
-  if ((rc = find_launch(b, first, count, slot_voices, tags, n, b->d_owner_slots, s))) return rc;
+  if ((rc = sk_owner_find_launch(b, first, count, slot_voices, tags, n, b->d_owner_slots, s))) return rc;
   /* entry k is the lowest slot that carries tags[k], or -1: the guard holds on every entry that is a slot */
   return stamp_launch(b, b->d_owner_slots, tags, n, NULL, slot_voices, voice_mask, stamps, d_result, s);
 }

@@ -10,6 +10,7 @@
  *   skred_bank_slots.c   the same for the slots of a tiled patch, slot stealing, and channel polyphony (matched stealing, capped note-ons)
  *   skred_bank_ctl.c     patch controllers                     skred_bank_owner.c  note owners
  *   skred_bank_expr.c    channels and per-note expression: masked owner matches, per-entry controller values
+ *   skred_bank_pedal.c   pedals: note-offs held back per slot, sostenuto's latch, the pedal-up
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -198,6 +199,9 @@ struct skred_bank {
   uint32_t *d_owner;                /* [n_voices] a slot's tag at its first voice, 0: nobody; no render kernel reads it */
   int32_t *d_owner_slots;           /* [SKRED_OWNER_MAX_TAGS] skred_bank_release_tags: the list its find pass leaves for its stamps (behind d_owner) */
   uint32_t *d_match_pair;           /* [2] skred_bank_find_match: where the shared count pass leaves (written, total) (behind d_owner_slots) */
+  /* pedals (skred_bank_pedal.c), allocated and zeroed by the first pedal call */
+  uint32_t *d_pedal;                /* [n_voices] a slot's SKRED_PEDAL_* bits at its first voice; NULL: no pedal call yet, and the tag
+                                       launches clear nothing; no render kernel reads it */
 };
 
 /* per-voice classification (host shadow) */
@@ -284,10 +288,15 @@ void sk_owner_free(skred_bank_t *b);
 int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
 /* ... and the array itself with the scratch behind it, allocated and zeroed by the first call that needs them (skred_bank_expr.c too) */
 int sk_owner_ensure(skred_bank_t *b);
+/* ... the find pass of n checked tags (1 .. SKRED_OWNER_MAX_TAGS, none zero, none twice) over a checked range into d_out on the
+ * device (skred_bank_pedal.c: into d_owner_slots, as skred_bank_release_tags does) */
+int sk_owner_find_launch(skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, int32_t *d_out, hipStream_t s);
 /* ... and skred_bank_tag_slots behind its checks, for the channel burst of skred_bank_slots.c: n >= 1 tags through the batch path
  * into the tag kernel (`who`: the caller, for the error text) */
 int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count, int slot_voices,
                         uint32_t *d_result, const char *who, hipStream_t s);
+/* skred_bank_pedal.c: the pedal array (skred_bank_destroy) */
+void sk_pedal_free(skred_bank_t *b);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);

@@ -19,10 +19,11 @@
  *   skred_ctl_kernels.hip     sk_launch_ctl_range, sk_launch_ctl_slots, sk_launch_ctl_owned
  *   skred_owner_kernels.hip   sk_launch_owner_tag, sk_launch_owner_find, sk_launch_owner_stamps
  *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each
+ *   skred_pedal_kernels.hip   sk_launch_pedal_clear, sk_launch_pedal_stamps, sk_launch_pedal_latch, sk_launch_pedal_up
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
- * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c, skred_bank_ctl.c, skred_bank_owner.c, skred_bank_expr.c and
+ * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c, skred_bank_ctl.c, skred_bank_owner.c, skred_bank_expr.c, skred_bank_pedal.c and
  * skred_recorder.c (sk_launch_owner_tag, sk_launch_owner_find, sk_launch_match_find, sk_launch_list_append and sk_launch_chan_join by the fixed-point
  * bank's skred_fx_owner.c, skred_fx_expr.c and skred_fx_steal.c too).  A launcher that takes `cnt, done, seq` gets them from the batch path (skred_bank_stage.c: sk_batch_send).
  */
@@ -350,6 +351,38 @@ int sk_launch_ctl_owned_each(const sk_ctl_t *d_recs, const sk_each_t *d_each, in
                              const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
                              sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t *mask_list, uint32_t *d_result,
                              uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+
+/* ---- pedals (skred_bank_pedal.c -> skred_pedal_kernels.hip; include/skred_amd.h: skred_bank_stamp_owned_pedal /
+ * _release_tags_pedal / _pedal_latch / _pedal_up) ----
+ * pedal[n_voices]: one word per voice beside the owner array, a slot's word at its first voice.  Only these launches read or write
+ * it.  The bits equal SKRED_PEDAL_* (checked at compile time in skred_bank_pedal.c). */
+#define SK_PEDAL_PENDING        (1u << 0)
+#define SK_PEDAL_LATCHED        (1u << 1)
+#define SK_PEDAL_LIFT_SUSTAIN   (1u << 0)
+#define SK_PEDAL_LIFT_SOSTENUTO (1u << 1)
+#define SK_PEDAL_SUSTAIN_DOWN   (1u << 2)
+#define SK_PEDAL_SPAN 256          /* threads per workgroup of the pedal kernels */
+/* pedal[d_slots[k]] = 0 under sk_launch_owner_tag's list rule: launched behind it by a bank that has a pedal array */
+int sk_launch_pedal_clear(uint32_t *pedal, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
+                          hipStream_t stream);
+/* sk_launch_owner_stamps with the stamp fixed to a release, except where hold_all != 0 or the slot is LATCHED: there PENDING is set
+ * and nothing stamped.  d_result[4] (zeroed on `stream` ahead of the kernel) += slots stamped, slots whose owner differs, entries
+ * that are no slot, slots held back */
+int sk_launch_pedal_stamps(const uint32_t *owner, uint32_t *pedal, const int32_t *d_slots, const uint32_t *d_tags, int n,
+                           const uint32_t *d_count, int slot_voices, uint64_t voice_mask, int n_voices, int hold_all,
+                           sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask,
+                           uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* LATCHED on every matching slot of the range that is not PENDING and has a held voice_mask voice (live, not released);
+ * d_result[2] (zeroed on `stream` ahead of the kernel) += slots latched, slots that did not match */
+int sk_launch_pedal_latch(const uint32_t *owner, uint32_t *pedal, uint32_t value, uint32_t mask, int first, int count, int slot_voices,
+                          uint64_t voice_mask, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint32_t *d_result,
+                          hipStream_t stream);
+/* flags: SK_PEDAL_LIFT_* / SK_PEDAL_SUSTAIN_DOWN.  On the matching slots: LIFT_SOSTENUTO clears LATCHED; a slot then PENDING, not
+ * LATCHED and not kept by SUSTAIN_DOWN is released on its voice_mask voices and loses PENDING.  d_result[3] (zeroed on `stream`
+ * ahead of the kernel) += slots released, slots still pending, slots that did not match */
+int sk_launch_pedal_up(const uint32_t *owner, uint32_t *pedal, uint32_t value, uint32_t mask, int first, int count, int slot_voices,
+                       uint64_t voice_mask, uint32_t flags, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
+                       uint64_t now, uint64_t *mask_list, uint32_t *d_result, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

@@ -47,11 +47,13 @@ ABI_SYMBOLS = [
     "skred_bank_find_match", "skred_bank_find_match_host", "skred_bank_stamp_match", "skred_bank_ctl_match",
     "skred_bank_ctl_owned_each", "skred_bank_ctl_tags_each",
     "skred_bank_find_steal_slots_match", "skred_bank_find_steal_slots_match_host", "skred_bank_note_on_channel",
+    "skred_bank_stamp_owned_pedal", "skred_bank_release_tags_pedal", "skred_bank_pedal_latch", "skred_bank_pedal_up",
+    "skred_bank_pedal_clear", "skred_bank_download_pedals",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
                     "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check",
-                    "skred_chan_check"]
+                    "skred_chan_check", "skred_pedal_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -178,6 +180,12 @@ def ctl_each_array(each):
         return each
     each = list(each)
     return (CtlEachC * len(each))(*each)
+
+
+# SKRED_PEDAL_* (skred_bank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up)
+PEDAL_PENDING, PEDAL_LATCHED = 1, 2
+PEDAL_LIFT_SUSTAIN, PEDAL_LIFT_SOSTENUTO, PEDAL_SUSTAIN_DOWN = 1, 2, 4
+PEDAL_CALL_STAMP_OWNED, PEDAL_CALL_RELEASE_TAGS, PEDAL_CALL_LATCH, PEDAL_CALL_UP = 0, 1, 2, 3
 
 
 _lib: Optional[C.CDLL] = None
@@ -309,6 +317,13 @@ def load() -> C.CDLL:
                                                          C.POINTER(i32), vp]
     L.skred_bank_note_on_channel.argtypes = [vp, C.POINTER(SlotQueryC), C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), C.c_uint32,
                                              vp, vp, i32, C.c_uint64, vp, vp, vp]
+    L.skred_pedal_check.argtypes = [i32, i32, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), C.c_uint32, vp, i32]
+    L.skred_bank_stamp_owned_pedal.argtypes = [vp, vp, vp, i32, vp, i32, C.c_uint64, i32, vp, vp]
+    L.skred_bank_release_tags_pedal.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, i32, i32, vp, vp]
+    L.skred_bank_pedal_latch.argtypes = [vp, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), vp, vp]
+    L.skred_bank_pedal_up.argtypes = [vp, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), C.c_uint32, vp, vp]
+    L.skred_bank_pedal_clear.argtypes = [vp, i32, i32, vp]
+    L.skred_bank_download_pedals.argtypes = [vp, vp, i32, i32]
     _lib = L
     return L
 
@@ -375,6 +390,16 @@ def chan_check(idle_q, steal_q, m, cap: int, tags, n_voices: int) -> int:
     ref = lambda x: C.byref(x) if x is not None else None   # noqa: E731
     return int(load().skred_chan_check(ref(idle_q), ref(steal_q), ref(m), int(cap) & 0xFFFFFFFF, arr.ctypes.data if arr is not None else None,
                                        len(arr) if arr is not None else 0, int(n_voices)))
+
+
+def pedal_check(call: int, n_voices: int, first: int = 0, count: int = 0, slot_voices: int = 1, voice_mask: int = 1, m=None, flags: int = 0,
+                tags=None) -> int:
+    """skred_pedal_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for what the pedal entry point PEDAL_CALL_* would refuse (None
+    stands for a NULL pointer).  Pure host."""
+    arr = tag_array(tags) if tags is not None else None
+    return int(load().skred_pedal_check(int(call), int(n_voices), int(first), int(count), int(slot_voices), int(voice_mask),
+                                        C.byref(m) if m is not None else None, int(flags) & 0xFFFFFFFF,
+                                        arr.ctypes.data if arr is not None else None, len(arr) if arr is not None else 0))
 
 
 def ctl_each_check(each, ctls, voice_mask: int, slot_voices: Optional[int] = None) -> int:
@@ -803,6 +828,49 @@ class DeviceBank:
         _check(self.L.skred_bank_note_on_channel(self.h, C.byref(idle_q), C.byref(steal_q), C.byref(m), int(cap) & 0xFFFFFFFF,
                                                  C.cast(arr, C.c_void_p), t.ctypes.data, len(t), int(voice_mask), d_assigned or None,
                                                  d_result or None, stream or None), "skred_bank_note_on_channel")
+
+    # ---- pedals (include/skred_amd.h: skred_bank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up) ----
+    def stamp_owned_pedal(self, d_slots: int, tags, slot_voices: int, voice_mask: int, hold_all: bool, d_result: int, d_count: int = 0,
+                          stream: int = 0):
+        """stamp_owned's release, except where `hold_all` or the slot is latched: there the note-off is held back (PENDING).
+        d_result (uint32[4]): slots stamped, slots whose owner differs, entries that are no slot, slots held back."""
+        arr = tag_array(tags)
+        _check(self.L.skred_bank_stamp_owned_pedal(self.h, d_slots or None, arr.ctypes.data, len(arr), d_count or None, int(slot_voices),
+                                                   int(voice_mask), int(bool(hold_all)), d_result or None, stream or None),
+               "skred_bank_stamp_owned_pedal")
+
+    def release_tags_pedal(self, first: int, count: int, slot_voices: int, voice_mask: int, tags, hold_all: bool, d_result: int,
+                           stream: int = 0):
+        """Note-off by note id under the pedals: every tag reaches the lowest slot of the range that carries it.  d_result as for
+        stamp_owned_pedal; [2] counts the tags nobody carries."""
+        arr = tag_array(tags)
+        _check(self.L.skred_bank_release_tags_pedal(self.h, int(first), int(count), int(slot_voices), int(voice_mask), arr.ctypes.data,
+                                                    len(arr), int(bool(hold_all)), d_result or None, stream or None),
+               "skred_bank_release_tags_pedal")
+
+    def pedal_latch(self, first: int, count: int, slot_voices: int, voice_mask: int, m: OwnerMatchC, d_result: int, stream: int = 0):
+        """Sostenuto down: LATCHED on the matching slots with a held voice and no pending note-off.  d_result (uint32[2]): slots
+        latched, slots that did not match."""
+        _check(self.L.skred_bank_pedal_latch(self.h, int(first), int(count), int(slot_voices), int(voice_mask), C.byref(m), d_result or None,
+                                             stream or None), "skred_bank_pedal_latch")
+
+    def pedal_up(self, first: int, count: int, slot_voices: int, voice_mask: int, m: OwnerMatchC, flags: int, d_result: int,
+                 stream: int = 0):
+        """A pedal goes up (PEDAL_LIFT_* / PEDAL_SUSTAIN_DOWN): the held-back note-offs of the matching slots are stamped now.
+        d_result (uint32[3]): slots released, slots still pending, slots that did not match."""
+        _check(self.L.skred_bank_pedal_up(self.h, int(first), int(count), int(slot_voices), int(voice_mask), C.byref(m), int(flags),
+                                          d_result or None, stream or None), "skred_bank_pedal_up")
+
+    def pedal_clear(self, first: int = 0, count: Optional[int] = None, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_bank_pedal_clear(self.h, int(first), int(count), stream or None), "skred_bank_pedal_clear")
+
+    def download_pedals(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The pedal words of [first, first + count) (uint32); waits for the device.  Zeros on a bank without a pedal array."""
+        count = self.n - first if count is None else count
+        out = np.full(max(count, 0), 0xDEADBEEF, np.uint32)
+        _check(self.L.skred_bank_download_pedals(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_pedals")
+        return out
 
     def force_generic(self, on: bool = True):
         _check(self.L.skred_bank_set_option(self.h, 1, int(on)), "skred_bank_set_option")

@@ -1531,8 +1531,120 @@ def fxchan():
     db.close()
 
 
+def pedal():
+    """Pedals on bank_patch("3sk", 2**20), every copy sounding and tagged over 16 channels (tag = channel << 24 | slot + 1), 256
+    note-offs of one channel held back, then the pedal goes up.  (a) skred_bank_release_tags_pedal beside skred_bank_release_tags of
+    the same tags; (b) skred_bank_pedal_up beside skred_bank_stamp_match of the same channel, and beside the only correct route without
+    the pedal array -- skred_bank_download_owners and skred_bank_download_env_clocks behind a device wait, the host's pending tags
+    mapped to the slots that still carry them, the list uploaded, skred_bank_stamp_slots; (c) the 64-frame block after the pedal-up
+    beside the block after stamp_slots of the same slots; (d) skred_bank_tag_slots of 256 slots before the bank has a pedal array and
+    after (the clear launch behind the tag kernel).  Medians of 12 with minimum and maximum; host time held, and stream time between
+    events."""
+    D = device
+    n, K, REPS, F, CHANNELS, NOTES = 1 << 20, 4, 12, 64, 16, 256
+    VOICES = 0xF
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = np.uint64(now - 40000)
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g); db.upload(bank)
+    slots = np.arange(0, n, K, dtype=np.int32)
+    idx = np.arange(len(slots), dtype=np.uint32)
+    tags = (((idx % CHANNELS) + 1) << 24 | (idx // CHANNELS + 1)).astype(np.uint32)
+    dl_all = torch.from_numpy(slots).cuda()
+    db.tag_slots(dl_all.data_ptr(), tags, K)
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    out = torch.zeros(F, 2, device="cuda")
+    m = D.owner_match(3 << 24, 0xFF000000)
+    held_at = np.flatnonzero(idx % CHANNELS == 2)[::7][:NOTES]                  # 256 notes of channel 3
+    note_tags, note_slots = tags[held_at].copy(), slots[held_at].copy()
+    dl_notes = torch.from_numpy(note_slots).cuda()
+    torch.cuda.synchronize()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def stats(x):
+        return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f})"
+
+    def series(call, before=None):
+        host, stream = [], []
+        for it in range(2 + REPS):
+            if before is not None:
+                before()
+            torch.cuda.synchronize()
+            h, s_ms = timed(call)
+            if it >= 2:
+                host.append(h); stream.append(s_ms)
+        return f"host time held {stats(host)}; stream time between events {stats(stream)}"
+
+    retrig = lambda: db.stamp_slots(dl_notes.data_ptr(), NOTES, K, VOICES, D.STAMP_TRIGGER)   # noqa: E731
+    hold = lambda: db.release_tags_pedal(0, n, K, VOICES, note_tags, True, res.data_ptr())    # noqa: E731
+
+    def parent_route():
+        own = db.download_owners()[::K]                            # the device wait the pedal calls were built to remove
+        _, rel = db.download_env_clocks()
+        at = {int(t): i for i, t in enumerate(own) if t}           # the host's map: which slot carries which tag now
+        lst = np.array([slots[at[int(t)]] for t in note_tags if int(t) in at and rel[slots[at[int(t)]]] == 0], np.int32)
+        dl = torch.from_numpy(lst).cuda()
+        db.stamp_slots(dl.data_ptr(), len(lst), K, VOICES, D.STAMP_RELEASE)
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, every copy sounding, tagged over {CHANNELS} channels ({n // K // CHANNELS} notes each); "
+          f"{NOTES} note-offs of one channel; medians of {REPS}")
+    print(f"  (d) tag_slots of {NOTES} slots, no pedal array yet: {series(lambda: db.tag_slots(dl_notes.data_ptr(), note_tags, K))}")
+    print(f"  (a) release_tags of {NOTES} tags: {series(lambda: db.release_tags(0, n, K, VOICES, note_tags, D.STAMP_RELEASE, res.data_ptr()), retrig)}; "
+          f"d_result = {res.cpu().numpy()[:3].tolist()}")
+    print(f"  (a) release_tags_pedal of the same tags, held back: {series(hold, lambda: (retrig(), db.pedal_clear()))}; d_result = {res.cpu().numpy().tolist()}")
+    print(f"  (a) release_tags_pedal of the same tags, hold_all 0: {series(lambda: db.release_tags_pedal(0, n, K, VOICES, note_tags, False, res.data_ptr()), lambda: (retrig(), db.pedal_clear()))}; "
+          f"d_result = {res.cpu().numpy().tolist()}")
+    print(f"  (d) tag_slots of {NOTES} slots with the clear launch behind it: {series(lambda: db.tag_slots(dl_notes.data_ptr(), note_tags, K))}")
+    print(f"  (b) pedal_up of the channel: {series(lambda: db.pedal_up(0, n, K, VOICES, m, D.PEDAL_LIFT_SUSTAIN, res.data_ptr()), lambda: (retrig(), hold()))}; "
+          f"d_result = {res.cpu().numpy()[:3].tolist()}")
+    print(f"  (b) stamp_match of the channel: {series(lambda: db.stamp_match(0, n, K, VOICES, m, D.STAMP_RELEASE, res.data_ptr()), retrig)}; "
+          f"d_result = {res.cpu().numpy()[:2].tolist()}")
+    print(f"  (b) pedal_latch of the channel: {series(lambda: db.pedal_latch(0, n, K, VOICES, m, res.data_ptr()), lambda: (retrig(), db.pedal_clear()))}; "
+          f"d_result = {res.cpu().numpy()[:2].tolist()}")
+    db.pedal_clear()
+    print(f"  (b) the pedal-up without the array, download_owners + download_env_clocks + host map + list upload + stamp_slots: {series(parent_route, retrig)}")
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+
+    def block_after(call, before):
+        after = []
+        for _ in range(REPS):
+            before()
+            block()
+            call()
+            after.append(block())
+            block()
+        return after
+    db.upload(bank)
+    for _ in range(8):
+        block()
+    steady = [block() for _ in range(REPS)]
+    after_up = block_after(lambda: db.pedal_up(0, n, K, VOICES, m, D.PEDAL_LIFT_SUSTAIN, res.data_ptr()), lambda: (retrig(), hold()))
+    after_slots = block_after(lambda: db.stamp_slots(dl_notes.data_ptr(), NOTES, K, VOICES, D.STAMP_RELEASE), retrig)
+    print(f"  (c) the {F}-frame block after pedal_up: {stats(after_up)}; after stamp_slots of the same {NOTES} slots: {stats(after_slots)}; "
+          f"a steady block: {stats(steady)}; kernel {db.last_kernel()}, list violations {db.list_violations()}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan, "fxchan": fxchan}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan, "fxchan": fxchan, "pedal": pedal}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
