@@ -105,17 +105,7 @@ static int idle_launch(skred_bank_t *b, const skred_idle_query_t *q, int32_t *d_
 
 /* room for `need` entries behind the two counts in d_idle_out and its pinned twin (the _host forms of both list queries) */
 int sk_idle_out_room(skred_bank_t *b, size_t need) {
-  if (b->d_idle_out && need <= b->idle_out_cap) return SKRED_OK;
-  /* (the previous call waited for its copy: nothing reads the old buffers) */
-  if (b->d_idle_out) { (void)hipFree(b->d_idle_out); b->d_idle_out = NULL; }
-  if (b->h_idle_out) { (void)hipHostFree(b->h_idle_out); b->h_idle_out = NULL; }
-  b->idle_out_cap = 0;
-  size_t cap = 1024;
-  while (cap < need) cap *= 2;
-  HIP_TRY(hipMalloc((void **)&b->d_idle_out, (2 + cap) * sizeof(int32_t)));
-  HIP_TRY(hipHostMalloc((void **)&b->h_idle_out, (2 + cap) * sizeof(int32_t), hipHostMallocDefault));
-  b->idle_out_cap = cap;
-  return SKRED_OK;
+  return sk_answer_room((void **)&b->d_idle_out, (void **)&b->h_idle_out, &b->idle_out_cap, 2, need);
 }
 
 int skred_bank_find_idle(skred_bank_t *b, const skred_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, void *stream) {

@@ -82,14 +82,7 @@ int skred_bank_notes_on_list(skred_bank_t *b, const skred_note_t *notes, int n, 
 
 /* room for n entries in the bank's own list (skred_bank_slots.c: the slot list of skred_bank_note_on_idle_slots) */
 int sk_note_list_room(skred_bank_t *b, int n) {
-  if ((size_t)n <= b->note_list_cap) return SKRED_OK;
-  /* (hipFree waits for the device: no earlier placement still reads the old list) */
-  sk_notes_free(b);
-  size_t cap = 1024;
-  while (cap < (size_t)n) cap *= 2;
-  HIP_TRY(hipMalloc((void **)&b->d_note_list, (SK_NOTE_LIST_WORDS + cap) * sizeof(uint32_t)));
-  b->note_list_cap = cap;
-  return SKRED_OK;
+  return sk_answer_room((void **)&b->d_note_list, NULL, &b->note_list_cap, SK_NOTE_LIST_WORDS, (size_t)n);
 }
 
 int skred_bank_note_on_idle(skred_bank_t *b, const skred_idle_query_t *q, const skred_note_t *notes, int n, int32_t *d_assigned,

@@ -325,8 +325,10 @@ typedef struct {
 int sk_batch_begin(skred_bank_t *b, size_t bytes, hipStream_t s, sk_batch_t *bt);
 const void *sk_batch_send(skred_bank_t *b, sk_batch_t *bt, size_t bytes, int wide, hipStream_t s);
 int sk_batch_end(sk_batch_t *bt, hipError_t e, const char *who, hipStream_t s);
-/* ... the ending of a _host query (plain pointers: the fixed-point bank's too): returns the entries copied to `out`, or an error */
+/* ... the ending of a _host query (plain pointers: the fixed-point bank's too): returns the entries copied to `out`, or an error; and
+ * room for `need` entries behind `head` words in a grow-on-demand answer buffer (h_buf NULL: no pinned twin), both banks' */
 int sk_read_back(const int32_t *d_out, int32_t *h_out, int counts, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
+int sk_answer_room(void **d_buf, void **h_buf, size_t *cap, size_t head, size_t need);
 /* skred_bank_checks.c (`who`: the entry point, for the error text): K and -- `what` != NULL, its name -- a mask over the K voices;
  * the stamp bits; a list's length (n * K stays an int); a range of whole slots of K voices inside the bank, empty only where
  * allowed; a plain window for the clears and downloads */

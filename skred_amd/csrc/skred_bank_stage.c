@@ -8,8 +8,9 @@
  *   end     takes the launch's verdict: the slot is the batch's until its kernel has run; after a failed launch the stream is
  *           waited for, because a copy into the slot's device twin, or an earlier launch of the batch, may still read the slot
  *
- * Also the read-back ending of the _host queries (sk_read_back).  The fixed-point bank guards its ring with events instead
- * (skred_fxbank_priv.h says why); nothing here serves it but sk_read_back, which takes plain pointers.
+ * Also the read-back ending of the _host queries (sk_read_back) and the room of the grow-on-demand answer buffers (sk_answer_room).
+ * The fixed-point bank guards its ring with events instead (skred_fxbank_priv.h says why); nothing here serves it but those two, which
+ * take plain pointers.  Its own ring and batch path, shaped like this one: skred_fx_stage.c.
  */
 #include <sched.h>
 #include <string.h>
@@ -106,6 +107,23 @@ int sk_batch_end(sk_batch_t *bt, hipError_t e, const char *who, hipStream_t s) {
     return fail(SKRED_E_NO_DEVICE, "%s launch -> %s", who, hipGetErrorString(e));
   }
   bt->sl->seq = bt->seq;
+  return SKRED_OK;
+}
+
+/* Room for `need` entries behind `head` words in an answer buffer on the device and -- h_buf != NULL -- its pinned twin, all 32-bit
+ * words: *cap entries, the next power of two >= need, from 1024.  The old buffers are freed first, and nothing reads them any more: a
+ * _host query waited for its copy before it returned, and hipFree waits for the device (a list an earlier placement still reads).
+ * *cap stays 0 when an allocation fails */
+int sk_answer_room(void **d_buf, void **h_buf, size_t *cap, size_t head, size_t need) {
+  if (*d_buf && need <= *cap) return SKRED_OK;
+  if (*d_buf) { (void)hipFree(*d_buf); *d_buf = NULL; }
+  if (h_buf && *h_buf) { (void)hipHostFree(*h_buf); *h_buf = NULL; }
+  *cap = 0;
+  size_t entries = 1024;
+  while (entries < need) entries *= 2;
+  HIP_TRY(hipMalloc(d_buf, (head + entries) * sizeof(uint32_t)));
+  if (h_buf) HIP_TRY(hipHostMalloc(h_buf, (head + entries) * sizeof(uint32_t), hipHostMallocDefault));
+  *cap = entries;
   return SKRED_OK;
 }
 

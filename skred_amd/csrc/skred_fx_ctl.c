@@ -3,7 +3,7 @@
  * (include/skred_amd_fxpt.h: skred_fx_ctl_check, skred_fxbank_ctl_range / _ctl_list / _ctl_owned).
  *
  * The host side of skred_fx_ctl_kernels.hip, built like skred_fx_live.c: the checks (made before anything touches the device), the
- * record's -- and for the guarded form the tags' -- way through the staging ring, one launch.  Nothing here waits for the device.
+ * record's -- and for the guarded form the tags' -- way through the batch path (skred_fx_stage.c), one launch.  Nothing here waits for the device.
  * The bank keeps no shadow of the voices; the one thing the host knows about them, n_filter (which selects the biquad
  * instantiation), counts voices with filter_mode != 0, and no controller can name filter_mode: it stays right by construction.
  * The bank has no slots: one record, every call per voice.
@@ -84,24 +84,22 @@ void skx_ctl_pack(const skred_fx_ctl_t *c, skx_ctl_t *out) {
 
 /* the packed record (and, guarded, the n tags behind it) -> a staging slot -> one of the two kernels (d_voices NULL: the range) */
 static int ctl_launch(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int first, int count, const int32_t *d_voices, const uint32_t *tags, int n,
-                      const uint32_t *d_count, uint32_t *d_result, hipStream_t s) {
+                      const uint32_t *d_count, uint32_t *d_result, const char *who, hipStream_t s) {
   HIP_TRY(hipSetDevice(fx->device));
   int rc;
   if (tags && (rc = skx_owner_ensure(fx))) return rc;
   const size_t bytes = sizeof(skx_ctl_t) + (tags ? (size_t)n * sizeof(uint32_t) : 0);
-  skx_slot_t *sl;
-  if ((rc = skx_ring_take(fx, bytes, &sl))) return rc;
-  skx_ctl_pack(ctl, (skx_ctl_t *)sl->h);
-  if (tags) memcpy((char *)sl->h + sizeof(skx_ctl_t), tags, (size_t)n * sizeof(uint32_t));
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const skx_ctl_t *src = (const skx_ctl_t *)sl->d;     /* the device twin: a bank-wide range is thousands of workgroups reading it */
+  skx_batch_t bt;
+  if ((rc = skx_batch_begin(fx, bytes, &bt))) return rc;
+  skx_ctl_pack(ctl, (skx_ctl_t *)bt.h);
+  if (tags) memcpy((char *)bt.h + sizeof(skx_ctl_t), tags, (size_t)n * sizeof(uint32_t));
+  const skx_ctl_t *src = (const skx_ctl_t *)skx_batch_send(&bt, bytes, s);   /* the device twin: a bank-wide range is thousands of workgroups reading it */
+  if (!src) return SKRED_E_NO_DEVICE;
   const hipError_t e = d_voices
     ? (hipError_t)skx_launch_ctl_list(src, d_voices, tags ? (const uint32_t *)(src + 1) : NULL, tags ? fx->d_owner : NULL, n, d_count,
                                       fx->n_voices, fx->d_ro, d_result, s)
     : (hipError_t)skx_launch_ctl_range(src, first, count, fx->d_ro, d_result, s);
-  rc = skx_ring_guard(sl, s);
-  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx controller launch -> %s", hipGetErrorString(e));
-  return rc;
+  return skx_batch_end(&bt, e, who, s);
 }
 
 int skred_fxbank_ctl_range(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int first, int count, uint32_t *d_result, void *stream) {
@@ -110,7 +108,7 @@ int skred_fxbank_ctl_range(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int fi
   if (rc) return rc;
   if ((rc = sk_check_slot_range(fx->n_voices, first, count, 1, 1, "fx ctl_range"))) return rc;
   if (count == 0) return SKRED_OK;
-  return ctl_launch(fx, ctl, first, count, NULL, NULL, 0, NULL, d_result, (hipStream_t)stream);
+  return ctl_launch(fx, ctl, first, count, NULL, NULL, 0, NULL, d_result, "fx ctl_range", (hipStream_t)stream);
 }
 
 int skred_fxbank_ctl_list(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const int32_t *d_voices, int n, const uint32_t *d_count_or_null,
@@ -119,7 +117,7 @@ int skred_fxbank_ctl_list(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const i
   int rc = sk_check_list_n(n, "fx ctl_list");
   if (rc || (rc = ctl_check(ctl, "fx ctl_list"))) return rc;
   if (n == 0) return SKRED_OK;
-  return ctl_launch(fx, ctl, 0, 0, d_voices, NULL, n, d_count_or_null, d_result, (hipStream_t)stream);
+  return ctl_launch(fx, ctl, 0, 0, d_voices, NULL, n, d_count_or_null, d_result, "fx ctl_list", (hipStream_t)stream);
 }
 
 int skred_fxbank_ctl_owned(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const int32_t *d_voices, const uint32_t *tags, int n,
@@ -130,5 +128,5 @@ int skred_fxbank_ctl_owned(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const 
   if ((rc = sk_check_list_n(n, "fx ctl_owned"))) return rc;
   if ((rc = ctl_check(ctl, "fx ctl_owned"))) return rc;
   if (n == 0) return SKRED_OK;
-  return ctl_launch(fx, ctl, 0, 0, d_voices, tags, n, d_count_or_null, d_result, (hipStream_t)stream);
+  return ctl_launch(fx, ctl, 0, 0, d_voices, tags, n, d_count_or_null, d_result, "fx ctl_owned", (hipStream_t)stream);
 }

@@ -5,7 +5,7 @@
  *
  * The host side of skred_fx_expr_kernels.hip, built like skred_fx_ctl.c and skred_fx_owner.c: the checks (made before anything
  * touches the device; the match's own through the float bank's skred_owner_match_check, the record's through skred_fx_ctl_check, the
- * shared ones of skred_bank_checks.c), the record's, entries' and tags' way through the staging ring, the launches.  The ordered list
+ * shared ones of skred_bank_checks.c), the record's, entries' and tags' way through the batch path (skred_fx_stage.c), the launches.  The ordered list
  * of the matches is the float bank's count and scatter, entered through sk_launch_match_find at slot_voices = 1 on this bank's query
  * scratch, which has the shape they need (skred_fx_live.c: skx_idle_scratch).  Nothing here waits for the device except
  * _find_match_host, which waits for its stream, and the allocation of the owner array by the first call that needs it.  The bank
@@ -158,13 +158,6 @@ int skred_fxbank_stamp_match(skred_fxbank_t *fx, int first, int count, const skr
   return SKRED_OK;
 }
 
-/* what a staged launch ends in: the slot's event behind everything that reads its twin, then the launch's own verdict */
-static int launched(skx_slot_t *sl, hipError_t e, const char *what, hipStream_t s) {
-  const int rc = skx_ring_guard(sl, s);
-  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "%s launch -> %s", what, hipGetErrorString(e));
-  return rc;
-}
-
 int skred_fxbank_ctl_match(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int first, int count, const skred_owner_match_t *m,
                            uint32_t *d_result, void *stream) {
   if (!fx) return fail(SKRED_E_BAD_ARG, "fx ctl_match: no bank");
@@ -175,14 +168,14 @@ int skred_fxbank_ctl_match(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int fi
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
   if ((rc = skx_owner_ensure(fx))) return rc;
-  skx_slot_t *sl;
-  if ((rc = skx_ring_take(fx, sizeof(skx_ctl_t), &sl))) return rc;
-  skx_ctl_pack(ctl, (skx_ctl_t *)sl->h);
-  if ((rc = skx_ring_send(sl, sizeof(skx_ctl_t), s))) return rc;
+  skx_batch_t bt;
+  if ((rc = skx_batch_begin(fx, sizeof(skx_ctl_t), &bt))) return rc;
+  skx_ctl_pack(ctl, (skx_ctl_t *)bt.h);
   /* the device twin: a bank-wide range is thousands of workgroups reading the record */
-  const hipError_t e = (hipError_t)skx_launch_ctl_match((const skx_ctl_t *)sl->d, first, count, fx->d_owner, m->value, m->mask, fx->d_ro,
-                                                        d_result, s);
-  return launched(sl, e, "fx ctl_match", s);
+  const skx_ctl_t *src = (const skx_ctl_t *)skx_batch_send(&bt, sizeof(skx_ctl_t), s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  const hipError_t e = (hipError_t)skx_launch_ctl_match(src, first, count, fx->d_owner, m->value, m->mask, fx->d_ro, d_result, s);
+  return skx_batch_end(&bt, e, "fx ctl_match", s);
 }
 
 /* ---- B. per-entry controller values ---- */
@@ -199,23 +192,23 @@ static int owned_each_check(const skred_fxbank_t *fx, const skred_fx_ctl_t *ctl,
 /* the record (zeros without `ctl`), the n entries (each[perm[j]]; perm NULL: as they stand) and the n tags in one staging slot: one
  * kernel reads all three, from the slot's device twin */
 static int owned_each_launch(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const uint32_t *perm,
-                             const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count, uint32_t *d_result, const char *what,
+                             const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count, uint32_t *d_result, const char *who,
                              hipStream_t s) {
   const size_t each_bytes = (size_t)n * sizeof(skx_each_t), bytes = sizeof(skx_ctl_t) + each_bytes + (size_t)n * sizeof(uint32_t);
-  skx_slot_t *sl;
-  int rc = skx_ring_take(fx, bytes, &sl);
+  skx_batch_t bt;
+  const int rc = skx_batch_begin(fx, bytes, &bt);
   if (rc) return rc;
-  char *h = (char *)sl->h;
+  char *h = (char *)bt.h;
   if (ctl) skx_ctl_pack(ctl, (skx_ctl_t *)h);
   else memset(h, 0, sizeof(skx_ctl_t));
   skx_each_pack(each, n, perm, (skx_each_t *)(h + sizeof(skx_ctl_t)));
   memcpy(h + sizeof(skx_ctl_t) + each_bytes, tags, (size_t)n * sizeof(uint32_t));
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const char *src = (const char *)sl->d;
+  const char *src = (const char *)skx_batch_send(&bt, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
   const hipError_t e = (hipError_t)skx_launch_ctl_owned_each((const skx_ctl_t *)src, (const skx_each_t *)(src + sizeof(skx_ctl_t)), d_voices,
                                                              (const uint32_t *)(src + sizeof(skx_ctl_t) + each_bytes), fx->d_owner, n, d_count,
                                                              fx->n_voices, fx->d_ro, d_result, s);
-  return launched(sl, e, what, s);
+  return skx_batch_end(&bt, e, who, s);
 }
 
 int skred_fxbank_ctl_owned_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const int32_t *d_voices,

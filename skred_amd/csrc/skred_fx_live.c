@@ -2,10 +2,10 @@
  * skred_fx_live.c -- live control of the fixed-point bank (include/skred_amd_fxpt.h: skred_fxbank_update, _find_idle /
  * _find_idle_host, _notes_on_list / _note_on_idle / _stamp_list; skred_fxbank_stamp's transport).
  *
- * The host side of skred_fx_live_kernels.hip: the checks (made before anything touches the device), the staging ring, the
- * launches.  Everything is queued on the caller's stream; the only waits are for a staging slot's own event, when the ring has
- * gone round, and -- in skred_fxbank_find_idle_host -- for the caller's stream.  The bank keeps no shadow of the voices: all state
- * the render kernel reads lives in the planes, except n_filter, which selects the biquad instantiation and is grown here.
+ * The host side of skred_fx_live_kernels.hip: the checks (made before anything touches the device), the batch path
+ * (skred_fx_stage.c), the launches.  Everything is queued on the caller's stream; the only waits are for a staging slot's own event,
+ * when the ring has gone round, and -- in skred_fxbank_find_idle_host -- for the caller's stream.  The bank keeps no shadow of the
+ * voices: all state the render kernel reads lives in the planes, except n_filter, which selects the biquad instantiation and is grown here.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -52,61 +52,48 @@ void skx_live_free(skred_fxbank_t *fx) {
   skx_owner_free(fx);
 }
 
-/* ------------------------------------------------------------------ the staging ring */
-
-/* the next slot, with room for `bytes`, not in flight */
-int skx_ring_take(skred_fxbank_t *fx, size_t bytes, skx_slot_t **out) {
-  skx_slot_t *sl = &fx->ring[fx->ring_head++ % SKX_RING];
-  if (!sl->ev) HIP_TRY(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
-  if (sl->in_flight) {
-    HIP_TRY(hipEventSynchronize(sl->ev));      /* this slot's batch alone: not the stream, not the device */
-    sl->in_flight = 0;
-  }
-  if (bytes > sl->cap) {
-    if (sl->d) { (void)hipFree(sl->d); sl->d = NULL; }
-    if (sl->h) { (void)hipHostFree(sl->h); sl->h = NULL; }
-    sl->cap = 0;
-    size_t cap = 64 * 1024;
-    while (cap < bytes) cap *= 2;
-    HIP_TRY(hipMalloc(&sl->d, cap));
-    HIP_TRY(hipHostMalloc(&sl->h, cap, hipHostMallocDefault));
-    sl->cap = cap;
-  }
-  *out = sl;
-  return SKRED_OK;
-}
-
-/* the slot's pinned bytes -> its device twin, on `s` */
-int skx_ring_send(skx_slot_t *sl, size_t bytes, hipStream_t s) {
-  HIP_TRY(hipMemcpyAsync(sl->d, sl->h, bytes, hipMemcpyHostToDevice, s));
-  return SKRED_OK;
-}
-
-/* behind the copy and the kernels that read the twin.  A failure to record leaves nothing to wait for later: wait now. */
-int skx_ring_guard(skx_slot_t *sl, hipStream_t s) {
-  if (hipEventRecord(sl->ev, s) != hipSuccess) {
-    (void)hipStreamSynchronize(s);
-    return fail(SKRED_E_NO_DEVICE, "fx staging: hipEventRecord failed");
-  }
-  sl->in_flight = 1;
-  return SKRED_OK;
-}
-
 /* note-ons / note-offs of voices the host names: ids only (stamping a voice twice with the same clock is idempotent) */
-int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, hipStream_t s) {
+int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, const char *who, hipStream_t s) {
   const size_t bytes = (size_t)n * sizeof(int32_t);
-  skx_slot_t *sl;
-  int rc = skx_ring_take(fx, bytes, &sl);
+  skx_batch_t bt;
+  const int rc = skx_batch_begin(fx, bytes, &bt);
   if (rc) return rc;
-  memcpy(sl->h, voices, bytes);
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const hipError_t e = (hipError_t)skx_launch_stamp((const int32_t *)sl->d, n, which, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, s);
-  rc = skx_ring_guard(sl, s);
-  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx stamp launch -> %s", hipGetErrorString(e));
-  return rc;
+  memcpy(bt.h, voices, bytes);
+  const int32_t *src = (const int32_t *)skx_batch_send(&bt, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  const hipError_t e = (hipError_t)skx_launch_stamp(src, n, which, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, s);
+  return skx_batch_end(&bt, e, who, s);
 }
 
 /* ------------------------------------------------------------------ updates */
+
+/* n packed, checked records (n_filter of them bring a biquad; upd_mark allocated) -> a staging slot -> the update kernel */
+static int update_launch(skred_fxbank_t *fx, const skx_update_t *rec, int n, int n_filter, hipStream_t s) {
+  HIP_TRY(hipSetDevice(fx->device));
+  const size_t bytes = (size_t)n * sizeof(skx_update_t);
+  skx_batch_t bt;
+  const int rc = skx_batch_begin(fx, bytes, &bt);
+  if (rc) return rc;
+  memcpy(bt.h, rec, bytes);
+  const skx_update_t *src = (const skx_update_t *)skx_batch_send(&bt, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  if (fx->n_filter < (1 << 30)) fx->n_filter += n_filter;   /* as a partial upload grows it: the next block must run the biquad */
+  /* a voice named twice is applied in order: one launch per run of distinct voices, found with a per-voice epoch mark */
+  hipError_t e = hipSuccess;
+  int start = 0;
+  while (start < n && e == hipSuccess) {
+    if (++fx->upd_epoch == 0) { memset(fx->upd_mark, 0, (size_t)fx->n_voices * sizeof(uint32_t)); fx->upd_epoch = 1; }
+    int end = start;
+    for (; end < n; end++) {
+      uint32_t *m = &fx->upd_mark[rec[end].voice];
+      if (*m == fx->upd_epoch) break;                   /* named before in this run: the next launch takes it */
+      *m = fx->upd_epoch;
+    }
+    e = (hipError_t)skx_launch_update(src + start, end - start, fx->d_ro, fx->d_rw, fx->count, s);
+    start = end;
+  }
+  return skx_batch_end(&bt, e, "fx update", s);
+}
 
 int skred_fxbank_update(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, const int32_t *voices, int n, uint32_t dirty, void *stream) {
   if (!fx || !h || n < 0 || (n > 0 && !voices)) return fail(SKRED_E_BAD_ARG, "fx update: bad arguments");
@@ -119,7 +106,7 @@ int skred_fxbank_update(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, const in
   hipStream_t s = (hipStream_t)stream;
   if (!(dirty & ~(uint32_t)SKX_STAMPS)) {               /* stamps carry no values: nothing to pack */
     HIP_TRY(hipSetDevice(fx->device));
-    return skx_stamp_ids(fx, voices, n, (int)(dirty >> 8), s);
+    return skx_stamp_ids(fx, voices, n, (int)(dirty >> 8), "fx update", s);
   }
   /* pack and check every record before anything touches the device */
   skx_update_t *rec = (skx_update_t *)calloc((size_t)n, sizeof(skx_update_t));
@@ -137,32 +124,8 @@ int skred_fxbank_update(skred_fxbank_t *fx, const skred_fxpt_bank_t *h, const in
     fx->upd_mark = (uint32_t *)calloc((size_t)fx->n_voices, sizeof(uint32_t));
     if (!fx->upd_mark) { free(rec); return fail(SKRED_E_NO_MEM, "fx update marks"); }
   }
-  const size_t bytes = (size_t)n * sizeof(skx_update_t);
-  skx_slot_t *sl;
-  int rc = hipSetDevice(fx->device) == hipSuccess ? SKRED_OK : fail(SKRED_E_NO_DEVICE, "fx update: hipSetDevice");
-  if (!rc) rc = skx_ring_take(fx, bytes, &sl);
-  if (rc) { free(rec); return rc; }
-  memcpy(sl->h, rec, bytes);
-  if ((rc = skx_ring_send(sl, bytes, s))) { free(rec); return rc; }
-  if (fx->n_filter < (1 << 30)) fx->n_filter += n_filter;   /* as a partial upload grows it: the next block must run the biquad */
-  /* a voice named twice is applied in order: one launch per run of distinct voices, found with a per-voice epoch mark */
-  const skx_update_t *src = (const skx_update_t *)sl->d;
-  hipError_t e = hipSuccess;
-  int start = 0;
-  while (start < n && e == hipSuccess) {
-    if (++fx->upd_epoch == 0) { memset(fx->upd_mark, 0, (size_t)fx->n_voices * sizeof(uint32_t)); fx->upd_epoch = 1; }
-    int end = start;
-    for (; end < n; end++) {
-      uint32_t *m = &fx->upd_mark[rec[end].voice];
-      if (*m == fx->upd_epoch) break;                   /* named before in this run: the next launch takes it */
-      *m = fx->upd_epoch;
-    }
-    e = (hipError_t)skx_launch_update(src + start, end - start, fx->d_ro, fx->d_rw, fx->count, s);
-    start = end;
-  }
+  const int rc = update_launch(fx, rec, n, n_filter, s);
   free(rec);
-  rc = skx_ring_guard(sl, s);                               /* (launches already queued still read the slot) */
-  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx update launch -> %s", hipGetErrorString(e));
   return rc;
 }
 
@@ -233,17 +196,7 @@ int skred_fxbank_find_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, i
 }
 
 int skx_idle_out_room(skred_fxbank_t *fx, size_t need) {
-  if (fx->d_idle_out && need <= fx->idle_out_cap) return SKRED_OK;
-  /* (the previous call waited for its copy: nothing reads the old buffers) */
-  if (fx->d_idle_out) { (void)hipFree(fx->d_idle_out); fx->d_idle_out = NULL; }
-  if (fx->h_idle_out) { (void)hipHostFree(fx->h_idle_out); fx->h_idle_out = NULL; }
-  fx->idle_out_cap = 0;
-  size_t cap = 1024;
-  while (cap < need) cap *= 2;
-  HIP_TRY(hipMalloc((void **)&fx->d_idle_out, (2 + cap) * sizeof(int32_t)));
-  HIP_TRY(hipHostMalloc((void **)&fx->h_idle_out, (2 + cap) * sizeof(int32_t), hipHostMallocDefault));
-  fx->idle_out_cap = cap;
-  return SKRED_OK;
+  return sk_answer_room((void **)&fx->d_idle_out, (void **)&fx->h_idle_out, &fx->idle_out_cap, 2, need);
 }
 
 int skred_fxbank_find_idle_host(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *voices, int *total_out, void *stream) {
@@ -277,18 +230,17 @@ int skred_fx_notes_check(const skred_fx_note_t *notes, int n) {
 
 /* the checked notes -> a staging slot -> the placement kernel */
 int skx_notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
-                     int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s) {
+                     int first_entry, int32_t *d_assigned, uint32_t *d_result, const char *who, hipStream_t s) {
   const size_t bytes = (size_t)n * sizeof(skred_fx_note_t);
-  skx_slot_t *sl;
-  int rc = skx_ring_take(fx, bytes, &sl);
+  skx_batch_t bt;
+  const int rc = skx_batch_begin(fx, bytes, &bt);
   if (rc) return rc;
-  memcpy(sl->h, notes, bytes);
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const hipError_t e = (hipError_t)skx_launch_notes((const skx_note_t *)sl->d, n, d_voices, d_count, first_entry, fx->n_voices, fx->d_ro,
-                                                    fx->d_rw, fx->count, d_assigned, d_result, s);
-  rc = skx_ring_guard(sl, s);
-  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx notes launch -> %s", hipGetErrorString(e));
-  return rc;
+  memcpy(bt.h, notes, bytes);
+  const skx_note_t *src = (const skx_note_t *)skx_batch_send(&bt, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  const hipError_t e = (hipError_t)skx_launch_notes(src, n, d_voices, d_count, first_entry, fx->n_voices, fx->d_ro, fx->d_rw, fx->count,
+                                                    d_assigned, d_result, s);
+  return skx_batch_end(&bt, e, who, s);
 }
 
 int skred_fxbank_notes_on_list(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
@@ -299,20 +251,12 @@ int skred_fxbank_notes_on_list(skred_fxbank_t *fx, const skred_fx_note_t *notes,
   const int rc = skred_fx_notes_check(notes, n);
   if (rc) return rc;
   HIP_TRY(hipSetDevice(fx->device));
-  return skx_notes_launch(fx, notes, n, d_voices, d_count, first_entry, d_assigned, d_result, (hipStream_t)stream);
+  return skx_notes_launch(fx, notes, n, d_voices, d_count, first_entry, d_assigned, d_result, "fx notes_on_list", (hipStream_t)stream);
 }
 
 /* room for n entries in the bank's own list */
 int skx_note_list_room(skred_fxbank_t *fx, int n) {
-  if ((size_t)n <= fx->note_list_cap) return SKRED_OK;
-  /* (hipFree waits for the device: no earlier placement still reads the old list) */
-  if (fx->d_note_list) { (void)hipFree(fx->d_note_list); fx->d_note_list = NULL; }
-  fx->note_list_cap = 0;
-  size_t cap = 1024;
-  while (cap < (size_t)n) cap *= 2;
-  HIP_TRY(hipMalloc((void **)&fx->d_note_list, (SKX_NOTE_LIST_WORDS + cap) * sizeof(uint32_t)));
-  fx->note_list_cap = cap;
-  return SKRED_OK;
+  return sk_answer_room((void **)&fx->d_note_list, NULL, &fx->note_list_cap, SKX_NOTE_LIST_WORDS, (size_t)n);
 }
 
 int skred_fxbank_note_on_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, const skred_fx_note_t *notes, int n, int32_t *d_assigned,
@@ -333,7 +277,7 @@ int skred_fxbank_note_on_idle(skred_fxbank_t *fx, const skred_fx_idle_query_t *q
   uint32_t *d_count = fx->d_note_list;
   int32_t *d_list = (int32_t *)(fx->d_note_list + SKX_NOTE_LIST_WORDS);
   if ((rc = skx_idle_launch(fx, &qq, d_list, d_count, s))) return rc;
-  return skx_notes_launch(fx, notes, n, d_list, d_count, 0, d_assigned, d_result, s);
+  return skx_notes_launch(fx, notes, n, d_list, d_count, 0, d_assigned, d_result, "fx note_on_idle", s);
 }
 
 int skred_fxbank_stamp_list(skred_fxbank_t *fx, const int32_t *d_voices, int n, const uint32_t *d_count_or_null, uint32_t stamps,

@@ -4,9 +4,9 @@
  * _download_owners, and skred_fxbank_download_params).
  *
  * The host side, built like skred_fx_live.c: the checks (made before anything touches the device; the tags' own through the float
- * bank's skred_owner_tags_check, the shared ones of skred_bank_checks.c), the tags' way through the staging ring, the launches.  The tag and the find pass are the float
- * bank's kernels, entered through their launchers at slot_voices = 1 without a batch-done word (skred_launch.h: this ring guards a
- * slot with an event); the guarded stamp is skred_fx_owner_kernels.hip.  Nothing here waits for the device except the two downloads
+ * bank's skred_owner_tags_check, the shared ones of skred_bank_checks.c), the tags' way through the batch path (skred_fx_stage.c),
+ * the launches.  The tag and the find pass are the float bank's kernels, entered through their launchers at slot_voices = 1 without a
+ * batch-done word (skred_launch.h: this ring guards a slot with an event); the guarded stamp is skred_fx_owner_kernels.hip.  Nothing here waits for the device except the two downloads
  * and the allocation of the array by the first call that needs it.  The bank has no slots: every call is per voice.
  */
 #include <stdlib.h>
@@ -18,12 +18,6 @@
 #define fail skred_amd_set_error
 
 _Static_assert(SK_OWNER_MAX_TAGS == SKRED_OWNER_MAX_TAGS, "the find kernel's LDS holds SKRED_OWNER_MAX_TAGS tags");
-
-/* the float bank's check, as it is (its message names skred_owner_tags_check; `who` made the call) */
-static int tags_check(const uint32_t *tags, int n, uint32_t flags, const char *who) {
-  (void)who;
-  return skred_owner_tags_check(tags, n, flags);
-}
 
 int skx_owner_ensure(skred_fxbank_t *fx) {
   if (fx->d_owner) return SKRED_OK;
@@ -46,13 +40,6 @@ void skx_owner_free(skred_fxbank_t *fx) {
   fx->d_match_pair = NULL;
 }
 
-/* what a staged launch ends in: the slot's event behind everything that reads its twin, then the launch's own verdict */
-static int launched(skx_slot_t *sl, hipError_t e, const char *what, hipStream_t s) {
-  const int rc = skx_ring_guard(sl, s);
-  if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "%s launch -> %s", what, hipGetErrorString(e));
-  return rc;
-}
-
 /* n >= 1 checked tags -> a staging slot -> the float bank's tag kernel at K = 1: entry k of the list gets tags[k] (the bank's device
  * is current) */
 int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count,
@@ -60,19 +47,19 @@ int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint
   int rc = skx_owner_ensure(fx);
   if (rc) return rc;
   const size_t bytes = (size_t)n * sizeof(uint32_t);
-  skx_slot_t *sl;
-  if ((rc = skx_ring_take(fx, bytes, &sl))) return rc;
-  memcpy(sl->h, tags, bytes);
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, (const uint32_t *)sl->d, n, d_count, 1, fx->n_voices,
-                                                       d_result, NULL, NULL, 0, s);
-  return launched(sl, e, who, s);
+  skx_batch_t bt;
+  if ((rc = skx_batch_begin(fx, bytes, &bt))) return rc;
+  memcpy(bt.h, tags, bytes);
+  const uint32_t *src = (const uint32_t *)skx_batch_send(&bt, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  const hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, src, n, d_count, 1, fx->n_voices, d_result, NULL, NULL, 0, s);
+  return skx_batch_end(&bt, e, who, s);
 }
 
 int skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
                           uint32_t *d_result, void *stream) {
   if (!fx || !d_voices) return fail(SKRED_E_BAD_ARG, "fx tag_list: no bank or no list");
-  int rc = tags_check(tags, n, SKRED_OWNER_ALLOW_ZERO, "fx tag_list");
+  int rc = skred_owner_tags_check(tags, n, SKRED_OWNER_ALLOW_ZERO);
   if (rc) return rc;
   if ((rc = sk_check_list_n(n, "fx tag_list"))) return rc;
   if (n == 0) return SKRED_OK;
@@ -80,26 +67,24 @@ int skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uin
   return skx_owner_tag_launch(fx, d_voices, tags, n, d_count_or_null, d_result, "fx tag_list", (hipStream_t)stream);
 }
 
-/* Stages sorted | perm (| the tags as given, with_tags) of n checked tags and runs the find pass over a checked range into d_out.
- * The slot is handed back unguarded: the caller queues what else reads it, then guards it. */
+/* Begins the batch `bt` with sorted | perm (| the tags as given, with_tags) of n checked tags and queues the find pass over a checked
+ * range into d_out: *err is that launch's verdict.  The caller queues what else reads the slot (bt->sl->d), then ends the batch. */
 static int find_launch(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int with_tags, int32_t *d_out, hipStream_t s,
-                       skx_slot_t **slot, hipError_t *err) {
+                       skx_batch_t *bt, hipError_t *err) {
   const size_t words = (size_t)(with_tags ? 3 : 2) * (size_t)n, bytes = words * sizeof(uint32_t);
-  skx_slot_t *sl;
-  int rc = skx_ring_take(fx, bytes, &sl);
+  const int rc = skx_batch_begin(fx, bytes, bt);
   if (rc) return rc;
-  uint32_t *sorted = (uint32_t *)sl->h, *perm = sorted + n;
+  uint32_t *sorted = (uint32_t *)bt->h, *perm = sorted + n;
   (void)sk_owner_pack(tags, n, sorted, perm);
   if (with_tags) memcpy(perm + n, tags, (size_t)n * sizeof(uint32_t));
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const uint32_t *src = (const uint32_t *)sl->d;
+  const uint32_t *src = (const uint32_t *)skx_batch_send(bt, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
   *err = (hipError_t)sk_launch_owner_find(fx->d_owner, first, count, 1, src, src + n, n, d_out, NULL, NULL, 0, s);
-  *slot = sl;
   return SKRED_OK;
 }
 
 static int find_check(const skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, const char *who) {
-  const int rc = tags_check(tags, n, SKRED_OWNER_UNIQUE, who);
+  const int rc = skred_owner_tags_check(tags, n, SKRED_OWNER_UNIQUE);
   if (rc) return rc;
   return sk_check_slot_range(fx->n_voices, first, count, 1, 0, who);   /* at least one voice, inside the bank */
 }
@@ -112,16 +97,16 @@ int skred_fxbank_find_owned(skred_fxbank_t *fx, int first, int count, const uint
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
   if ((rc = skx_owner_ensure(fx))) return rc;
-  skx_slot_t *sl;
+  skx_batch_t bt;
   hipError_t e = hipSuccess;
-  if ((rc = find_launch(fx, first, count, tags, n, 0, d_voices_out, s, &sl, &e))) return rc;
-  return launched(sl, e, "fx find_owned", s);
+  if ((rc = find_launch(fx, first, count, tags, n, 0, d_voices_out, s, &bt, &e))) return rc;
+  return skx_batch_end(&bt, e, "fx find_owned", s);
 }
 
 int skred_fxbank_stamp_owned(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
                              uint32_t stamps, uint32_t *d_result, void *stream) {
   if (!fx || !d_voices || !d_result) return fail(SKRED_E_BAD_ARG, "fx stamp_owned: no bank, list or result");
-  int rc = tags_check(tags, n, 0, "fx stamp_owned");
+  int rc = skred_owner_tags_check(tags, n, 0);
   if (rc) return rc;
   if ((rc = sk_check_list_n(n, "fx stamp_owned"))) return rc;
   if ((rc = sk_check_stamps(stamps, "fx stamp_owned"))) return rc;
@@ -130,13 +115,14 @@ int skred_fxbank_stamp_owned(skred_fxbank_t *fx, const int32_t *d_voices, const 
   HIP_TRY(hipSetDevice(fx->device));
   if ((rc = skx_owner_ensure(fx))) return rc;
   const size_t bytes = (size_t)n * sizeof(uint32_t);
-  skx_slot_t *sl;
-  if ((rc = skx_ring_take(fx, bytes, &sl))) return rc;
-  memcpy(sl->h, tags, bytes);
-  if ((rc = skx_ring_send(sl, bytes, s))) return rc;
-  const hipError_t e = (hipError_t)skx_launch_stamp_owned(fx->d_owner, d_voices, (const uint32_t *)sl->d, n, d_count_or_null, fx->n_voices,
-                                                          stamps, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, d_result, s);
-  return launched(sl, e, "fx stamp_owned", s);
+  skx_batch_t bt;
+  if ((rc = skx_batch_begin(fx, bytes, &bt))) return rc;
+  memcpy(bt.h, tags, bytes);
+  const uint32_t *src = (const uint32_t *)skx_batch_send(&bt, bytes, s);
+  if (!src) return SKRED_E_NO_DEVICE;
+  const hipError_t e = (hipError_t)skx_launch_stamp_owned(fx->d_owner, d_voices, src, n, d_count_or_null, fx->n_voices, stamps,
+                                                          fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, d_result, s);
+  return skx_batch_end(&bt, e, "fx stamp_owned", s);
 }
 
 int skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, uint32_t stamps, uint32_t *d_result,
@@ -149,14 +135,14 @@ int skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const ui
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(fx->device));
   if ((rc = skx_owner_ensure(fx))) return rc;
-  skx_slot_t *sl;
+  skx_batch_t bt;
   hipError_t e = hipSuccess;
-  if ((rc = find_launch(fx, first, count, tags, n, 1, fx->d_owner_found, s, &sl, &e))) return rc;
+  if ((rc = find_launch(fx, first, count, tags, n, 1, fx->d_owner_found, s, &bt, &e))) return rc;
   /* entry k is the lowest voice that carries tags[k], or -1: the guard holds on every entry that is a voice */
   if (e == hipSuccess)
-    e = (hipError_t)skx_launch_stamp_owned(fx->d_owner, fx->d_owner_found, (const uint32_t *)sl->d + 2 * (size_t)n, n, NULL, fx->n_voices,
+    e = (hipError_t)skx_launch_stamp_owned(fx->d_owner, fx->d_owner_found, (const uint32_t *)bt.sl->d + 2 * (size_t)n, n, NULL, fx->n_voices,
                                            stamps, fx->d_ro[SKX_TIME], fx->d_rw[0], fx->count, d_result, s);
-  return launched(sl, e, "fx release_tags", s);
+  return skx_batch_end(&bt, e, "fx release_tags", s);
 }
 
 int skred_fxbank_owner_clear(skred_fxbank_t *fx, int first, int count, void *stream) {

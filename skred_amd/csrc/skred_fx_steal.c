@@ -6,7 +6,7 @@
  *
  * Argument checks (made before anything touches the device), the bank's scratch -- laid out as the float bank's
  * (skred_bank_steal.c), because everything behind the key pass is the float bank's select -- and the launches.  The query travels
- * in the launch arguments: it takes no staging slot.  skred_fxbank_note_on_steal stages its notes through the ring exactly as
+ * in the launch arguments: it takes no staging slot.  skred_fxbank_note_on_steal stages its notes through the batch path exactly as
  * skred_fxbank_notes_on_list does.  Everything is queued on the caller's stream; only the host variant waits, for that stream alone.
  */
 #include <string.h>
@@ -214,7 +214,7 @@ int skred_fxbank_note_on_steal(skred_fxbank_t *fx, const skred_fx_idle_query_t *
   const hipError_t e = (hipError_t)sk_launch_list_append(d_list, d_idle_count, fx->d_steal_out + 2, (const uint32_t *)fx->d_steal_out, n,
                                                          d_joined, d_result + 2, s);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx list append launch -> %s", hipGetErrorString(e));
-  return skx_notes_launch(fx, notes, n, d_list, d_joined, 0, d_assigned, d_result, s);
+  return skx_notes_launch(fx, notes, n, d_list, d_joined, 0, d_assigned, d_result, "fx note_on_steal", s);
 }
 
 /* ---- channel polyphony: the capped, tagged burst ---- */
@@ -273,6 +273,6 @@ int skred_fxbank_note_on_channel(skred_fxbank_t *fx, const skred_fx_idle_query_t
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx note_on_channel: join launch -> %s", hipGetErrorString(e));
   /* 4. the notes on the joined list: d_assigned, d_result[0..1];  5. their tags: entry k of the joined list gets tags[k] (every entry
    * is a voice of the bank) */
-  if ((rc = skx_notes_launch(fx, notes, n, d_list, d_joined, 0, d_assigned, d_result, s))) return rc;
+  if ((rc = skx_notes_launch(fx, notes, n, d_list, d_joined, 0, d_assigned, d_result, "fx note_on_channel", s))) return rc;
   return skx_owner_tag_launch(fx, d_list, tags, n, d_joined, NULL, "fx note_on_channel: tags", s);
 }

@@ -281,7 +281,7 @@ int skred_fxbank_stamp(skred_fxbank_t *fx, const int32_t *voices, int n, int whi
   for (int i = 0; i < n; i++)
     if (voices[i] < 0 || voices[i] >= fx->n_voices) return skred_amd_set_error(SKRED_E_RANGE, "fx stamp: voice %d outside the bank", voices[i]);
   HIP_TRY(hipSetDevice(fx->device));
-  return skx_stamp_ids(fx, voices, n, which, (hipStream_t)stream);   /* through the staging ring: no wait for the stream */
+  return skx_stamp_ids(fx, voices, n, which, "fx stamp", (hipStream_t)stream);   /* through the staging ring: no wait for the stream */
 }
 
 int skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems) {

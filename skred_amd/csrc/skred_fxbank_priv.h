@@ -1,6 +1,7 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
- * skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c: voice stealing; skred_fx_owner.c: note owners;
- * skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression; channel polyphony lives in skred_fx_steal.c). */
+ * skred_fx_stage.c: the staging ring and the batch path; skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c:
+ * voice stealing; skred_fx_owner.c: note owners; skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression;
+ * channel polyphony lives in skred_fx_steal.c). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -40,7 +41,7 @@ struct skred_fxbank {
   int32_t master_k_q15;         /* default: 0.002 in Q15 */
   int gains_frames;             /* > 0: the latest sum-only render left the gains of a block of this many frames */
   size_t gains_offset;          /* ... at this int64 offset into d_partial */
-  skx_slot_t ring[SKX_RING];    /* staging of updates, stamps and notes (skred_fx_live.c) */
+  skx_slot_t ring[SKX_RING];    /* staging of every host-written batch (skred_fx_stage.c) */
   unsigned ring_head;
   uint32_t *upd_mark; uint32_t upd_epoch;    /* per-voice epoch marks: a batch that names a voice twice is split into launches */
   uint32_t *d_idle; int idle_wgs;            /* the query's scratch: SKX_IDLE_W_COUNT words, idle_wgs counts, idle_wgs offsets */
@@ -79,9 +80,9 @@ int skx_pack_voice(const skred_fxbank_t *fx, const skred_fxpt_bank_t *h, int v, 
 /* skred_fx_live.c */
 #define SKX_NOTE_LIST_WORDS 4      /* in front of the bank's note list: the idle query's two counts, the joined list's length, padding */
 void skx_live_free(skred_fxbank_t *fx);
-int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, hipStream_t s);
+int skx_stamp_ids(skred_fxbank_t *fx, const int32_t *voices, int n, int which, const char *who, hipStream_t s);
 /* ... for skred_fxbank_note_on_steal: the idle query's launches (q checked by the caller), room for n entries in d_note_list, and
- * the checked notes through a staging slot into the placement kernel */
+ * the checked notes through the batch path into the placement kernel (`who`, here and below: the entry point, for the error text) */
 int skx_idle_launch(skred_fxbank_t *fx, const skred_fx_idle_query_t *q, int32_t *d_voices, uint32_t *d_count, hipStream_t s);
 /* ... for skred_fxbank_find_match too: the query scratch (SKX_IDLE_W_COUNT words, idle_wgs counts, idle_wgs offsets; allocated once,
  * for the whole bank, the words zeroed on `s`), and room for 2 + need entries in d_idle_out / h_idle_out */
@@ -89,13 +90,15 @@ int skx_idle_scratch(skred_fxbank_t *fx, hipStream_t s);
 int skx_idle_out_room(skred_fxbank_t *fx, size_t need);
 int skx_note_list_room(skred_fxbank_t *fx, int n);
 int skx_notes_launch(skred_fxbank_t *fx, const skred_fx_note_t *notes, int n, const int32_t *d_voices, const uint32_t *d_count,
-                     int first_entry, int32_t *d_assigned, uint32_t *d_result, hipStream_t s);
+                     int first_entry, int32_t *d_assigned, uint32_t *d_result, const char *who, hipStream_t s);
 
-/* ... the staging ring, for the other host files: the next slot with room for `bytes`, not in flight; the slot's pinned bytes ->
- * its device twin on `s`; the slot's event behind the copy and the kernels that read the twin */
-int skx_ring_take(skred_fxbank_t *fx, size_t bytes, skx_slot_t **out);
-int skx_ring_send(skx_slot_t *sl, size_t bytes, hipStream_t s);
-int skx_ring_guard(skx_slot_t *sl, hipStream_t s);
+/* skred_fx_stage.c, the batch path every staged launch takes.  begin: a slot of the ring with room for `bytes`, not in flight, filled
+ * through bt->h.  send: the copy on `s`; returns the slot's device twin, or NULL with the error set.  end: the slot's event behind
+ * everything queued, failed launch or not, then the verdict: `e`, the first launch that failed, fails the call under `who` */
+typedef struct { skx_slot_t *sl; void *h; } skx_batch_t;
+int skx_batch_begin(skred_fxbank_t *fx, size_t bytes, skx_batch_t *bt);
+const void *skx_batch_send(skx_batch_t *bt, size_t bytes, hipStream_t s);
+int skx_batch_end(skx_batch_t *bt, hipError_t e, const char *who, hipStream_t s);
 
 /* skred_fx_steal.c */
 void skx_steal_free(skred_fxbank_t *fx);
@@ -103,8 +106,8 @@ void skx_steal_free(skred_fxbank_t *fx);
 /* skred_fx_owner.c: the owner array (allocated and zero-filled by the first call that needs it), for the guarded controller too */
 void skx_owner_free(skred_fxbank_t *fx);
 int skx_owner_ensure(skred_fxbank_t *fx);
-/* ... and skred_fxbank_tag_list behind its checks, for the channel burst of skred_fx_steal.c: n >= 1 tags through the staging ring
- * into the tag kernel (`who`: the caller, for the error text) */
+/* ... and skred_fxbank_tag_list behind its checks, for the channel burst of skred_fx_steal.c: n >= 1 tags through the batch path
+ * into the tag kernel */
 int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count,
                          uint32_t *d_result, const char *who, hipStream_t s);
 /* skred_fx_ctl.c: the checked record as it travels (the reserved words carry the reciprocals).  Pure host */
@@ -120,8 +123,10 @@ int sk_check_stamps(uint32_t stamps, const char *who);
 int sk_check_list_n(int n, const char *who);
 int sk_check_slot_range(int n_voices, int first, int count, int K, int allow_empty, const char *who);
 int sk_check_window(int n_voices, int first, int count, const char *who);
-/* skred_bank_stage.c: the ending of a _host query -- returns the entries copied to `out`, or an error */
+/* skred_bank_stage.c: the ending of a _host query -- returns the entries copied to `out`, or an error; and room for `need` entries
+ * behind `head` words in a grow-on-demand answer buffer (h_buf NULL: no pinned twin) */
 int sk_read_back(const int32_t *d_out, int32_t *h_out, int counts, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
+int sk_answer_room(void **d_buf, void **h_buf, size_t *cap, size_t head, size_t need);
 
 /* skred_fx_kernels.hip, skred_fx_live_kernels.hip */
 int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);

@@ -1,13 +1,15 @@
 /* The host side of the fixed-point bank's note owners and controllers without a device: skred_fx_ctl_check, the record's packing
  * (skx_ctl_pack), the sort-plus-permutation of the tags as the find pass gets them (sk_owner_pack) and every refusal the entry points
  * make before anything touches the device, on a skred_fxbank_t that is nothing but its voice count (a refused call reads no other
- * member).  One line per case, "OK" last.  tests/test_fx_ctl_cpu.py and tests/test_fx_owner_cpu.py build and run it; built together
- * with skred_amd/csrc/skred_fx_owner.c, skred_fx_ctl.c and the checks they share with the float bank under -fsanitize=address,undefined
- * it is the sanitizer run of those files' host code -- from the repository root, after the library is built (the program's own copy of
- * skred_fx_owner.c, skred_fx_ctl.c and skred_bank_checks.c takes the place of the library's; everything else it calls comes from the library):
+ * member), those of the live calls that share the batch path with them included (skred_fxbank_update, _stamp, _notes_on_list,
+ * _note_on_idle, _find_idle_host).  One line per case, "OK" last.  tests/test_fx_ctl_cpu.py and tests/test_fx_owner_cpu.py build and
+ * run it; built together with skred_amd/csrc/skred_fx_owner.c, skred_fx_ctl.c, skred_fx_live.c, skred_fx_stage.c and the checks they
+ * share with the float bank under -fsanitize=address,undefined it is the sanitizer run of those files' host code -- from the
+ * repository root, after the library is built (the program's own copy of those files takes the place of the library's; everything
+ * else it calls comes from the library):
  *   gcc -O1 -g -Wall -Werror -std=gnu11 -fsanitize=address,undefined -fno-sanitize-recover=undefined -Iinclude -Iskred_amd/csrc \
  *       -I${ROCM_PATH:-/opt/rocm}/include tests/c_fx_ctl_host.c skred_amd/csrc/skred_fx_owner.c skred_amd/csrc/skred_fx_ctl.c \
- *       skred_amd/csrc/skred_bank_checks.c -o /tmp/c_fx_ctl_host_san \
+ *       skred_amd/csrc/skred_fx_live.c skred_amd/csrc/skred_fx_stage.c skred_amd/csrc/skred_bank_checks.c -o /tmp/c_fx_ctl_host_san \
  *       -Lskred_amd -lskred_amd -L${ROCM_PATH:-/opt/rocm}/lib -lamdhip64 -lm -lpthread \
  *       -Wl,-rpath,$PWD/skred_amd -Wl,-rpath,${ROCM_PATH:-/opt/rocm}/lib && /tmp/c_fx_ctl_host_san */
 #include <stdio.h>
@@ -247,7 +249,109 @@ int main(void) {
   CASE("owned/negative_n", skred_fxbank_ctl_owned(fx, &pan, list, t4, -1, NULL, NULL, NULL) == BAD);
   CASE("owned/empty", skred_fxbank_ctl_owned(fx, &pan, list, d4, 0, NULL, NULL, NULL) == SKRED_OK);
 
-  int untouched = !fx->d_owner && !fx->d_owner_found && fx->ring_head == 0 && fx->n_filter == 0 && fx->count == 0;
+  /* the order of the checks, where two of them would answer differently */
+  CASE("tag/null_tags_empty", skred_fxbank_tag_list(fx, list, NULL, 0, NULL, NULL, NULL) == BAD);
+  CASE("tag/huge_n", skred_fxbank_tag_list(fx, list, t4, INT32_MAX / 64 + 1, NULL, NULL, NULL) == BAD);
+  CASE("find/dup_tag_past_the_bank", skred_fxbank_find_owned(fx, 299, 2, d4, 4, list, NULL) == BAD);
+  CASE("stamp/no_stamp_bit_empty", skred_fxbank_stamp_owned(fx, list, t4, 0, NULL, 0, res, NULL) == BAD);
+  CASE("release/zero_tag_count_zero", skred_fxbank_release_tags(fx, 0, 0, z4, 4, REL, res, NULL) == BAD);
+  CASE("release/bad_stamps_empty", skred_fxbank_release_tags(fx, 0, 300, t4, 0, 1024, res, NULL) == BAD);
+
+  /* ---- the live calls that go through the same batch path (skred_fx_live.c, skred_fxbank_stamp): refused before the device */
+  int32_t log2s[8] = { 3, 3, 3, 3, 3, 3, 3, 3 }, offs[8] = { 0 }, amps[8] = { 0 };
+  const int32_t v01[2] = { 0, 1 }, v8[1] = { 8 }, v300[2] = { 0, 300 }, vneg[1] = { -1 };
+  memset(&view, 0, sizeof(view));
+  view.n_voices = 8; view.log2_size = log2s; view.table_offset = offs; view.amp_q15 = amps;
+  const uint32_t PARAMS = SKRED_DIRTY_PARAMS;
+  CASE("update/null_bank", skred_fxbank_update(NULL, &view, v01, 2, PARAMS, NULL) == BAD);
+  CASE("update/null_view", skred_fxbank_update(fx, NULL, v01, 2, PARAMS, NULL) == BAD);
+  CASE("update/null_voices", skred_fxbank_update(fx, &view, NULL, 2, PARAMS, NULL) == BAD);
+  CASE("update/negative_n", skred_fxbank_update(fx, &view, v01, -1, PARAMS, NULL) == BAD);
+  CASE("update/empty_before_the_mask", skred_fxbank_update(fx, &view, NULL, 0, 0, NULL) == SKRED_OK);
+  CASE("update/dirty0", skred_fxbank_update(fx, &view, v01, 2, 0, NULL) == BAD);
+  CASE("update/unknown_bit", skred_fxbank_update(fx, &view, v01, 2, 1u << 11, NULL) == BAD);
+  CASE("update/hold", skred_fxbank_update(fx, &view, v01, 2, PARAMS | SKRED_DIRTY_HOLD, NULL) == BAD);
+  CASE("update/mask_before_the_voices", skred_fxbank_update(fx, &view, v300, 2, 0, NULL) == BAD);
+  CASE("update/voice_past_the_bank", skred_fxbank_update(fx, &view, v300, 2, PARAMS, NULL) == RNG);
+  CASE("update/voice_past_the_view", skred_fxbank_update(fx, &view, v8, 1, PARAMS, NULL) == RNG);
+  CASE("update/voice_negative", skred_fxbank_update(fx, &view, vneg, 1, PARAMS, NULL) == RNG);
+  CASE("update/stamp_voice_past_the_bank", skred_fxbank_update(fx, &view, v300, 2, SKRED_STAMP_TRIGGER, NULL) == RNG);
+  CASE("update/table_outside_the_pool", skred_fxbank_update(fx, &view, v01, 2, PARAMS, NULL) == RNG);      /* (a pool of 0 entries) */
+  fx->table_entries = 64;
+  amps[0] = 65536;
+  CASE("update/amp_high", skred_fxbank_update(fx, &view, v01, 2, PARAMS, NULL) == RNG);
+  log2s[0] = 16; amps[0] = 0;
+  CASE("update/log2_size_high", skred_fxbank_update(fx, &view, v01, 2, PARAMS, NULL) == RNG);
+  fx->table_entries = 0;
+  CASE("ids/null_bank", skred_fxbank_stamp(NULL, v01, 2, 1, NULL) == BAD);
+  CASE("ids/null_voices", skred_fxbank_stamp(fx, NULL, 2, 1, NULL) == BAD);
+  CASE("ids/negative_n", skred_fxbank_stamp(fx, v01, -1, 1, NULL) == BAD);
+  CASE("ids/which0", skred_fxbank_stamp(fx, v01, 2, 0, NULL) == BAD);
+  CASE("ids/which4", skred_fxbank_stamp(fx, v01, 2, 4, NULL) == BAD);
+  CASE("ids/which0_empty", skred_fxbank_stamp(fx, v01, 0, 0, NULL) == BAD);
+  CASE("ids/voice_past_the_bank", skred_fxbank_stamp(fx, v300, 2, 3, NULL) == RNG);
+  CASE("ids/empty", skred_fxbank_stamp(fx, NULL, 0, 3, NULL) == SKRED_OK);
+
+  skred_fx_note_t note[2];
+  memset(note, 0, sizeof(note));
+  note[0].phase_inc = note[1].phase_inc = 3000017u; note[0].velocity_q15 = note[1].velocity_q15 = 9000;
+  int32_t out4[4] = { -7, -7, -7, -7 };
+#define NOTES(bank, nt, n, l, c, fe, r) skred_fxbank_notes_on_list(bank, nt, n, l, c, fe, out4, r, NULL)
+  CASE("notes/null_bank", NOTES(NULL, note, 2, list, res, 0, res) == BAD);
+  CASE("notes/null_notes", NOTES(fx, NULL, 2, list, res, 0, res) == BAD);
+  CASE("notes/null_list", NOTES(fx, note, 2, NULL, res, 0, res) == BAD);
+  CASE("notes/null_count", NOTES(fx, note, 2, list, NULL, 0, res) == BAD);
+  CASE("notes/null_result", NOTES(fx, note, 2, list, res, 0, NULL) == BAD);
+  CASE("notes/negative_n", NOTES(fx, note, -1, list, res, 0, res) == BAD);
+  CASE("notes/negative_first_entry", NOTES(fx, note, 2, list, res, -1, res) == BAD);
+  note[1].flags = 4;
+  CASE("notes/unknown_flag", NOTES(fx, note, 2, list, res, 0, res) == BAD);
+  CASE("notes/empty_before_the_notes", NOTES(fx, note, 0, list, res, 0, res) == SKRED_OK);
+  note[1].flags = 0; note[1].reserved[0] = 1;
+  CASE("notes/reserved", NOTES(fx, note, 2, list, res, 0, res) == BAD);
+  note[1].reserved[0] = 0; note[0].velocity_q15 = 65536;
+  CASE("notes/velocity_high", NOTES(fx, note, 2, list, res, 0, res) == BAD);
+  note[0].velocity_q15 = 9000;
+
+  skred_fx_idle_query_t q;
+  memset(&q, 0, sizeof(q));
+  q.first = 0; q.count = 300; q.which = SKRED_IDLE_ENV_DONE; q.from = 0; q.max_out = 4;
+  skred_fx_idle_query_t qb;
+  CASE("on_idle/null_bank", skred_fxbank_note_on_idle(NULL, &q, note, 2, out4, res, NULL) == BAD);
+  CASE("on_idle/null_query", skred_fxbank_note_on_idle(fx, NULL, note, 2, out4, res, NULL) == BAD);
+  CASE("on_idle/null_notes", skred_fxbank_note_on_idle(fx, &q, NULL, 2, out4, res, NULL) == BAD);
+  CASE("on_idle/null_result", skred_fxbank_note_on_idle(fx, &q, note, 2, out4, NULL, NULL) == BAD);
+  CASE("on_idle/negative_n", skred_fxbank_note_on_idle(fx, &q, note, -1, out4, res, NULL) == BAD);
+  qb = q; qb.which |= SKRED_IDLE_AMP_ZERO;
+  CASE("on_idle/amp_zero", skred_fxbank_note_on_idle(fx, &qb, note, 2, out4, res, NULL) == BAD);
+  qb = q; qb.count = 301;
+  CASE("on_idle/past_the_bank", skred_fxbank_note_on_idle(fx, &qb, note, 2, out4, res, NULL) == RNG);
+  CASE("on_idle/past_the_bank_empty", skred_fxbank_note_on_idle(fx, &qb, note, 0, out4, res, NULL) == RNG);
+  qb = q; qb.from = 300;
+  CASE("on_idle/from_outside", skred_fxbank_note_on_idle(fx, &qb, note, 2, out4, res, NULL) == RNG);
+  CASE("on_idle/empty", skred_fxbank_note_on_idle(fx, &q, note, 0, out4, res, NULL) == SKRED_OK);
+  note[1].flags = 8;
+  CASE("on_idle/unknown_flag", skred_fxbank_note_on_idle(fx, &q, note, 2, out4, res, NULL) == BAD);
+  note[1].flags = 0;
+
+  int idle_total = -5;
+  CASE("idle_host/null_bank", skred_fxbank_find_idle_host(NULL, &q, out4, &idle_total, NULL) == BAD);
+  CASE("idle_host/null_query", skred_fxbank_find_idle_host(fx, NULL, out4, &idle_total, NULL) == BAD);
+  CASE("idle_host/null_list", skred_fxbank_find_idle_host(fx, &q, NULL, &idle_total, NULL) == BAD);
+  qb = q; qb.max_out = -1;
+  CASE("idle_host/negative_max_out", skred_fxbank_find_idle_host(fx, &qb, out4, &idle_total, NULL) == BAD);
+  qb = q; qb.which = SKRED_IDLE_ENV_DONE | SKRED_IDLE_UNNAMED;
+  CASE("idle_host/unnamed", skred_fxbank_find_idle_host(fx, &qb, out4, &idle_total, NULL) == BAD);
+  qb = q; qb.which = 0;
+  CASE("idle_host/no_criterion", skred_fxbank_find_idle_host(fx, &qb, out4, &idle_total, NULL) == BAD);
+  qb = q; qb.count = 0;
+  CASE("idle_host/empty_range", skred_fxbank_find_idle_host(fx, &qb, out4, &idle_total, NULL) == RNG);
+  qb = q; qb.first = 299; qb.from = 299; qb.count = 2;
+  CASE("idle_host/past_the_bank", skred_fxbank_find_idle_host(fx, &qb, out4, &idle_total, NULL) == RNG);
+  CASE("idle_host/outputs_untouched", idle_total == -5 && out4[0] == -7 && out4[3] == -7 && res[0] == 0 && res[1] == 0 && res[2] == 0);
+
+  int untouched = !fx->d_owner && !fx->d_owner_found && fx->ring_head == 0 && fx->n_filter == 0 && fx->count == 0 && !fx->upd_mark &&
+                  !fx->d_idle && !fx->d_idle_out && !fx->h_idle_out && !fx->d_note_list;
   for (int i = 0; i < SKX_RING; i++) untouched = untouched && !fx->ring[i].h && !fx->ring[i].d && !fx->ring[i].ev && !fx->ring[i].in_flight;
   CASE("bank/untouched", untouched);
   free(many);

@@ -213,6 +213,99 @@ def test_fx_stamp_goes_through_the_ring(base):
     db.close()
 
 
+def test_fx_staging_ring_serves_every_call_family_back_to_back():
+    """The batch path (skred_fx_stage.c) is the one way a host-written batch reaches a kernel of this bank, whatever the call: 3 x
+    FX_RING_SLOTS = 24 staged calls of twelve kinds go to bank A back to back on one stream -- every slot of the ring is reused twice,
+    by a call of another family, under nothing but its event -- and to bank B with a device synchronise after each.  Everything the
+    calls write must be the same, byte for byte.  This ring always reads the slot's device twin behind a copy: there is no size
+    threshold to cross, so 4096 voices do.  Voice i carries the tag i + 1 for i < 1024.  Every device buffer exists before the first
+    call, so nothing but the calls themselves is issued in between."""
+    import torch
+    n, E, calls = 4096, 8, 3 * fxb.FX_RING_SLOTS
+    bank, pool, c0 = fxb.bank_fx(n)
+    REL = fxb.STAMP_RELEASE
+
+    def i32(values):
+        return torch.tensor(np.asarray(values, np.int64).astype(np.int32), dtype=torch.int32, device="cuda")
+
+    def ids_of(k):
+        return np.arange(E) * 97 + 13 * k                     # eight voices below 1024: voice v carries the tag v + 1
+
+    def run(sync_each):
+        db = open_fx(bank, pool, c0)
+        host = bank.copy()
+        db.render_host(64, 1)                                 # the voices are sounding, the clock has moved
+        first = i32(np.arange(1024))
+        db.tag_list(first.data_ptr(), np.arange(1, 1025))
+        lists = [i32(ids_of(k)) for k in range(calls)]
+        high = [i32(3100 + ids_of(k)) for k in range(calls)]
+        cnt = i32([E])
+        results = [torch.zeros(3, dtype=torch.int32, device="cuda") for _ in range(calls)]
+        found = [torch.full((E,), -7, dtype=torch.int32, device="cuda") for _ in range(calls)]
+        torch.cuda.synchronize()
+        for k in range(calls):
+            ids, lst, res, val = ids_of(k), lists[k].data_ptr(), results[k].data_ptr(), 100 + 7 * k
+            pan = fxb.fx_ctl(fxb.CTL_PAN, pan_left_q15=val, pan_right_q15=2 * val)
+            kind = k % 12
+            if kind == 0:
+                vs = (2048 + ids).astype(np.int32)
+                host["phase_inc"][vs] = 1000003 * (k + 1)
+                db.update(host, vs, fxb.DIRTY_PARAMS)
+            elif kind == 1:
+                if k < 12:
+                    db.update(host, (2048 + ids).astype(np.int32), REL)
+                else:
+                    db.stamp(2048 + ids, fxb.FX_STAMP_TRIGGER)
+            elif kind == 2:
+                notes = [fxb.FxNoteC(3000017 + val, 9000 + val, 77 * val, val, 32000 - val, fxb.NOTE_SET_PHASE | fxb.NOTE_SET_PAN)
+                         for _ in range(E)]
+                db.notes_on_list(notes, lst, cnt.data_ptr(), 0, 0, res)
+            elif kind == 3:
+                db.tag_list(high[k].data_ptr(), 5000 + ids, 0, res)
+            elif kind == 4:
+                db.find_owned(0, n, np.concatenate([ids[:6] + 1, [5000 + 13 * 3, 77777]]), found[k].data_ptr())
+            elif kind == 5:
+                db.stamp_owned(lst, ids + 1, REL, res)
+            elif kind == 6:
+                db.release_tags(0, n, ids + 1, REL, res)
+            elif kind == 7:
+                db.ctl_range(pan, 0, n, res)
+            elif kind == 8:
+                db.ctl_list(pan, lst, E, 0, res)
+            elif kind == 9:
+                db.ctl_owned(pan, lst, ids + 1, 0, res)
+            elif kind == 10:
+                db.ctl_match(fxb.fx_ctl(fxb.CTL_VELOCITY, velocity_q15=val), 0, n, k & 3, 3, res)
+            else:
+                each = [fxb.fx_each(fxb.EACH_VELOCITY, velocity_q15=val + j) for j in range(E)]
+                db.ctl_owned_each(pan, each, lst, ids + 1, 0, res)
+            if sync_each:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        got, params = bank.copy(), bank.copy()
+        db.download(got)
+        owners, recips = db.download_owners(), db.download_params(params)
+        mix, _ = db.render_host(64, 1)
+        db.close()
+        return dict(bank=got, params=params, owners=owners, recips=recips, mix=mix, results=[host_of(r) for r in results],
+                    found=[host_of(found[k]) for k in range(calls) if k % 12 == 4])
+
+    a, b = run(False), run(True)
+    for view in ("bank", "params"):
+        differ = [name for name in a[view].a if a[view].a[name].tobytes() != b[view].a[name].tobytes()]
+        assert not differ, (view, differ)
+    assert a["owners"].tobytes() == b["owners"].tobytes() and a["recips"].tobytes() == b["recips"].tobytes()
+    for k, (ra, rb) in enumerate(zip(a["results"], b["results"])):
+        assert ra.tobytes() == rb.tobytes(), (k, ra, rb)
+    assert len(a["found"]) == 2 and all(fa.tobytes() == fb.tobytes() for fa, fb in zip(a["found"], b["found"]))
+    assert a["mix"].tobytes() == b["mix"].tobytes()
+    # the calls did what they say: nothing above compares two banks that both stood still
+    assert int(a["owners"][3100 + 13 * 3]) == 5000 + 13 * 3 and a["found"][0].tolist()[:6] == ids_of(4)[:6].tolist()
+    assert a["found"][0].tolist()[6:] == [3100 + 13 * 3, -1] and a["results"][2].tolist()[:2] == [E, 0]
+    assert int(a["params"]["pan_left_q15"][n - 1]) == 100 + 7 * 19 and a["results"][7].tolist()[:2] == [n, 0]
+    assert int(a["params"]["phase_inc"][2048 + 13 * 12]) == 1000003 * 13 and a["results"][5].tolist() == [E, 0, 0]
+
+
 # ---------------------------------------------------------------------------------------------- 2. the idle list
 
 def idle_state(n, seed):
