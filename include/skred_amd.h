@@ -1082,8 +1082,9 @@ int  skred_bank_note_on_channel(skred_bank_t *bank, const skred_slot_query_t *id
  * skred_bank_stamp_match / _release_tags / _stamp_owned on a pending slot stamp at once and LEAVE the bit: a later pedal_up stamps
  * again, as a second amp_envelope_release of the reference would -- "all notes off" under a pedal is therefore skred_bank_pedal_up or
  * _pedal_clear first.  Tagged and untagged note-ons still must not share a range.
- * Not built here: the fixed-point bank's twin of these calls, the drop-in mode, deferred items and pattern steps, shards beyond
- * skred_shard_bank(). */
+ * The fixed-point bank's twin of these calls is include/skred_amd_fxpt.h's section of the same name (skred_fxbank_stamp_owned_pedal ..
+ * skred_fxbank_download_pedals), on these constants.  Not built here: the drop-in mode, deferred items and pattern steps, shards
+ * beyond skred_shard_bank(). */
 enum { SKRED_PEDAL_PENDING = 1u << 0, SKRED_PEDAL_LATCHED = 1u << 1 };
 enum { SKRED_PEDAL_LIFT_SUSTAIN = 1u << 0,     /* the sustain pedal goes up */
        SKRED_PEDAL_LIFT_SOSTENUTO = 1u << 1,   /* the sostenuto pedal goes up */

@@ -523,6 +523,90 @@ int  skred_fxbank_note_on_channel(skred_fxbank_t *fx, const skred_fx_idle_query_
                                   const skred_owner_match_t *m, uint32_t cap, const skred_fx_note_t *notes, const uint32_t *tags,
                                   int n, int32_t *d_assigned, uint32_t *d_result, void *stream);
 
+/* ---- pedals: sustain and sostenuto hold note-offs back on the device --------------------------------------------------------
+ *
+ * The fixed-point, per-voice twin of the float bank's section "pedals" (include/skred_amd.h: skred_pedal_check ..
+ * skred_bank_download_pedals): that section read at slot_voices = 1, voice_mask = 1 -- this bank has no slots.  SKRED_PEDAL_PENDING /
+ * _LATCHED, SKRED_PEDAL_LIFT_SUSTAIN / _LIFT_SOSTENUTO / _SUSTAIN_DOWN, SKRED_PEDAL_CALL_*, skred_owner_match_t,
+ * skred_owner_match_check and skred_owner_tags_check are that header's, values and meaning unchanged.  A host that plays this bank
+ * through skred_fxbank_note_on_channel steals on the device, so a pending note-off kept on the host would release the wrong note
+ * after a theft; the only other correct route is skred_fxbank_download_owners plus skred_fxbank_download behind a device wait on
+ * every pedal-up.
+ *
+ * pedal[n_voices] is a uint32 array in device memory, one word per voice, that only the calls of this section read or write.
+ * SKRED_PEDAL_PENDING: a note-off arrived and was held back.  SKRED_PEDAL_LATCHED: sostenuto caught this note.  The first call of
+ * this section other than _pedal_clear and _download_pedals allocates it (4 bytes per voice) and zero-fills it, and ensures the owner
+ * array too; that call waits for the device once, as the first owner call does.  It is freed with the bank.  No render kernel reads
+ * the word: blocks rendered with and without pedal calls that hold nothing are bit-identical, and a bank that never makes a pedal
+ * call launches nothing more than it did before this section existed.
+ *
+ * A NEW NOTE CLEARS THE WORD.  Once the array exists, every tag launch of the bank (skred_fxbank_tag_list, the tags of
+ * skred_fxbank_note_on_channel) is followed on its stream by a launch that stores 0 into the pedal word of every voice it tagged --
+ * the same list, the same min(n, *d_count) rule, the same "is a voice" rule.  So a thief's tags clear its victim's bits, and a key
+ * struck again under the pedal (the same voice in mono mode) starts clean: the pedal-up releases the old note-off's voice only if the
+ * old note is still the one that sounds there.
+ *
+ * HELD(v):  use_envelope != 0  &&  is_active != 0  &&  sample_release == 0  -- the terms candidate and released of
+ * skred_fxbank_find_steal, on the words as the device holds them at that point of the stream.
+ *
+ * PARTICULAR TO THIS BANK: SKRED_STAMP_RELEASE writes the release clock only while is_active is set (skred_fxbank_stamp_list's rule).
+ * skred_fxbank_pedal_up and skred_fxbank_stamp_owned_pedal count a voice whose envelope is not active as released or stamped all the
+ * same, exactly as skred_fxbank_stamp_owned counts it today; its clock stays as it was, and PENDING is cleared.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_fxbank_update; host arrays travel through the staging ring; nothing
+ * waits for the device; results are pure functions of the state, whatever the order of arrival; one stream at a time per bank.  On a
+ * shard: through skred_fxshard_bank(), with that rank's local indices.
+ *
+ * Stated behaviour: a pending note ranks in the steal queries as the held note it is (its envelope has no release clock).
+ * skred_fxbank_stamp_match / _release_tags / _stamp_owned on a pending voice stamp at once and LEAVE the bit: a later pedal_up stamps
+ * again -- "all notes off" under a pedal is therefore skred_fxbank_pedal_up or _pedal_clear first.
+ * Out of scope: the drop-in mode, deferred items, pattern steps.
+ *
+ * skred_fx_pedal_check            pure host, no device: what the entry point named by `call` refuses about everything but its
+ *                                 pointers to the bank, the list and the result, in the order it checks -- the return codes and the
+ *                                 order of skred_pedal_check(call, n_voices, first, count, 1, 1, m, flags, tags, n).  Every entry
+ *                                 point below calls it before anything touches the device; a refused call writes nothing.
+ * skred_fxbank_stamp_owned_pedal  looks at the entries below min(n, *d_count_or_null).  An entry that is no voice of the bank: [2].
+ *                                 owner[v] != tags[k]: [1].  Otherwise, hold_all != 0 or a LATCHED word: pedal[v] |= PENDING,
+ *                                 nothing is stamped, [3].  Otherwise skred_fxbank_stamp_owned's SKRED_STAMP_RELEASE with the bank's
+ *                                 sample count as the clock, [0].  d_result (device, uint32[4], required) is cleared on the stream
+ *                                 ahead of the kernel.  An entry named twice stores the same words twice and is counted twice.  With
+ *                                 hold_all == 0 and nothing latched, the bank's bytes and words 0..2 are those of
+ *                                 skred_fxbank_stamp_owned(..., SKRED_STAMP_RELEASE, ...).  n == 0: SKRED_OK, nothing is done.
+ *                                 Refused: NULL bank, list or result, what skred_fx_pedal_check(STAMP_OWNED) refuses.
+ * skred_fxbank_release_tags_pedal note-off by note id: skred_fxbank_release_tags' find pass into the same scratch -- the lowest voice
+ *                                 of [first, first + count) per tag, or -1 -- then the call above on that list, in one staged batch.
+ *                                 [1] is 0; [2] counts the tags nobody in the range carries.  Refused: NULL bank or result, what
+ *                                 skred_fx_pedal_check(RELEASE_TAGS) refuses.
+ * skred_fxbank_pedal_latch        sostenuto down, one pass over the range, no list: a voice that matches m gets LATCHED when its
+ *                                 PENDING bit is clear and it is HELD.  Notes struck later are not caught (their tags clear the
+ *                                 word), nor notes whose note-off is already pending.  d_result (device, uint32[2], required),
+ *                                 cleared ahead of the kernel: [0] voices that satisfy the rule (latched now or before), [1] voices
+ *                                 of the range that did not match.  Only matching voices read a plane; no plane is written.
+ *                                 Refused: NULL bank or result, what skred_fx_pedal_check(LATCH) refuses.
+ * skred_fxbank_pedal_up           a pedal goes up, one pass over the matching voices of the range.  flags: at least one of
+ *                                 LIFT_SUSTAIN and LIFT_SOSTENUTO; SUSTAIN_DOWN is refused together with LIFT_SUSTAIN.
+ *                                 LIFT_SOSTENUTO clears LATCHED.  A voice that is then PENDING, not LATCHED and not kept by
+ *                                 SUSTAIN_DOWN gets the release stamp with THIS call's clock and loses PENDING.  d_result (device,
+ *                                 uint32[3], required), cleared ahead of the kernel: [0] voices released, [1] voices still pending,
+ *                                 [2] voices of the range that did not match.  The word is stored only when it changed.
+ *                                 Refused: NULL bank or result, what skred_fx_pedal_check(UP) refuses.
+ * skred_fxbank_pedal_clear        pedal[first .. first + count) = 0 on `stream`; nothing to do on a bank without the array.
+ *                                 SKRED_E_RANGE: count < 0 or a range outside the bank.
+ * skred_fxbank_download_pedals    the words of [first, first + count) into host_u32; waits for the device, like
+ *                                 skred_fxbank_download_owners; zeros on a bank without the array. */
+int  skred_fx_pedal_check(int call, int n_voices, int first, int count, const skred_owner_match_t *m, uint32_t flags,
+                          const uint32_t *tags, int n);
+int  skred_fxbank_stamp_owned_pedal(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n,
+                                    const uint32_t *d_count_or_null, int hold_all, uint32_t *d_result, void *stream);
+int  skred_fxbank_release_tags_pedal(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int hold_all,
+                                     uint32_t *d_result, void *stream);
+int  skred_fxbank_pedal_latch(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, uint32_t *d_result, void *stream);
+int  skred_fxbank_pedal_up(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, uint32_t flags, uint32_t *d_result,
+                           void *stream);
+int  skred_fxbank_pedal_clear(skred_fxbank_t *fx, int first, int count, void *stream);
+int  skred_fxbank_download_pedals(skred_fxbank_t *fx, uint32_t *host_u32, int first, int count);
+
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);
 float skred_fxbank_last_render_ms(skred_fxbank_t *fx);

@@ -50,6 +50,7 @@ void skx_live_free(skred_fxbank_t *fx) {
   fx->idle_wgs = 0; fx->idle_out_cap = 0; fx->note_list_cap = 0;
   skx_steal_free(fx);
   skx_owner_free(fx);
+  skx_pedal_free(fx);
 }
 
 /* note-ons / note-offs of voices the host names: ids only (stamping a voice twice with the same clock is idempotent) */

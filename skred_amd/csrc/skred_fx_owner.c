@@ -52,7 +52,9 @@ int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint
   memcpy(bt.h, tags, bytes);
   const uint32_t *src = (const uint32_t *)skx_batch_send(&bt, bytes, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, src, n, d_count, 1, fx->n_voices, d_result, NULL, NULL, 0, s);
+  hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, src, n, d_count, 1, fx->n_voices, d_result, NULL, NULL, 0, s);
+  /* a new note clears its voice's pedal word (skred_fx_pedal.c): the same list under the same rule, once the bank has the array */
+  if (e == hipSuccess && fx->d_pedal) e = (hipError_t)sk_launch_pedal_clear(fx->d_pedal, d_voices, n, d_count, 1, fx->n_voices, s);
   return skx_batch_end(&bt, e, who, s);
 }
 
@@ -68,9 +70,10 @@ int skred_fxbank_tag_list(skred_fxbank_t *fx, const int32_t *d_voices, const uin
 }
 
 /* Begins the batch `bt` with sorted | perm (| the tags as given, with_tags) of n checked tags and queues the find pass over a checked
- * range into d_out: *err is that launch's verdict.  The caller queues what else reads the slot (bt->sl->d), then ends the batch. */
-static int find_launch(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int with_tags, int32_t *d_out, hipStream_t s,
-                       skx_batch_t *bt, hipError_t *err) {
+ * range into d_out: *err is that launch's verdict.  The caller queues what else reads the slot (bt->sl->d), then ends the batch.
+ * (skred_fx_pedal.c enters it too.) */
+int skx_owner_find_launch(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int with_tags, int32_t *d_out, hipStream_t s,
+                          skx_batch_t *bt, hipError_t *err) {
   const size_t words = (size_t)(with_tags ? 3 : 2) * (size_t)n, bytes = words * sizeof(uint32_t);
   const int rc = skx_batch_begin(fx, bytes, bt);
   if (rc) return rc;
@@ -99,7 +102,7 @@ int skred_fxbank_find_owned(skred_fxbank_t *fx, int first, int count, const uint
   if ((rc = skx_owner_ensure(fx))) return rc;
   skx_batch_t bt;
   hipError_t e = hipSuccess;
-  if ((rc = find_launch(fx, first, count, tags, n, 0, d_voices_out, s, &bt, &e))) return rc;
+  if ((rc = skx_owner_find_launch(fx, first, count, tags, n, 0, d_voices_out, s, &bt, &e))) return rc;
   return skx_batch_end(&bt, e, "fx find_owned", s);
 }
 
@@ -137,7 +140,7 @@ int skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const ui
   if ((rc = skx_owner_ensure(fx))) return rc;
   skx_batch_t bt;
   hipError_t e = hipSuccess;
-  if ((rc = find_launch(fx, first, count, tags, n, 1, fx->d_owner_found, s, &bt, &e))) return rc;
+  if ((rc = skx_owner_find_launch(fx, first, count, tags, n, 1, fx->d_owner_found, s, &bt, &e))) return rc;
   /* entry k is the lowest voice that carries tags[k], or -1: the guard holds on every entry that is a voice */
   if (e == hipSuccess)
     e = (hipError_t)skx_launch_stamp_owned(fx->d_owner, fx->d_owner_found, (const uint32_t *)bt.sl->d + 2 * (size_t)n, n, NULL, fx->n_voices,

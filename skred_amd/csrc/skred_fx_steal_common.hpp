@@ -57,4 +57,14 @@ __device__ __forceinline__ bool skx_steal_sounding(const skx_steal_args_t &a, in
   return snd;
 }
 
+// HELD, for the sostenuto latch (skred_fx_pedal_kernels.hip): the candidate's first two terms -- an envelope that runs -- on a voice
+// that is not released (no release clock).  The same words of the same planes skx_steal_key reads
+__device__ __forceinline__ bool skx_steal_held(const skx_plane_t *osc, const skx_plane_t *rw0, const skx_plane_t *time, int v) {
+  const uint32_t flags = osc[v].w[2] >> 8;
+  const uint32_t rwf = rw0[v].w[3];
+  if (!((flags & SKXF_USE_ENV) && (rwf & SKXR_ACTIVE))) return false;
+  const uint2 r = *reinterpret_cast<const uint2 *>(&time[v].w[2]);     // sample_release lo, hi
+  return (r.x | r.y) == 0u;
+}
+
 #endif

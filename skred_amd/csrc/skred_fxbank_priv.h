@@ -1,7 +1,7 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
  * skred_fx_stage.c: the staging ring and the batch path; skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c:
  * voice stealing; skred_fx_owner.c: note owners; skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression;
- * channel polyphony lives in skred_fx_steal.c). */
+ * skred_fx_pedal.c: pedals; channel polyphony lives in skred_fx_steal.c). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -53,6 +53,7 @@ struct skred_fxbank {
   uint32_t *d_owner;                         /* note owners (skred_fx_owner.c): one word per voice, 0 nobody; NULL until the first call that needs it */
   int32_t *d_owner_found;                    /* ... and behind it skred_fxbank_release_tags' list, SKRED_OWNER_MAX_TAGS entries */
   uint32_t *d_match_pair;                    /* ... and behind that the two words the count pass of skred_fxbank_find_match fills */
+  uint32_t *d_pedal;                         /* pedals (skred_fx_pedal.c): one word per voice, SKRED_PEDAL_*; NULL until the first call that needs it */
   long long *d_mix; size_t mix_cap;
   int32_t *d_stems; size_t stems_cap;
   uint64_t count;
@@ -110,6 +111,13 @@ int skx_owner_ensure(skred_fxbank_t *fx);
  * into the tag kernel */
 int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count,
                          uint32_t *d_result, const char *who, hipStream_t s);
+/* ... and the find pass of skred_fxbank_release_tags, for the pedals: begins the batch `bt` with sorted | perm (| the tags as given,
+ * with_tags) of n checked tags and queues the find pass over a checked range into d_out; *err is that launch's verdict.  The caller
+ * queues what else reads the slot (bt->sl->d), then ends the batch */
+int skx_owner_find_launch(skred_fxbank_t *fx, int first, int count, const uint32_t *tags, int n, int with_tags, int32_t *d_out, hipStream_t s,
+                          skx_batch_t *bt, hipError_t *err);
+/* skred_fx_pedal.c: the pedal array, freed with the bank */
+void skx_pedal_free(skred_fxbank_t *fx);
 /* skred_fx_ctl.c: the checked record as it travels (the reserved words carry the reciprocals).  Pure host */
 void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
 /* skred_fx_expr.c: the checked entries as they travel -- out[j] = each[perm[j]] (perm NULL: j), the named values word for word, the

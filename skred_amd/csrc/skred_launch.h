@@ -20,6 +20,8 @@
  *   skred_owner_kernels.hip   sk_launch_owner_tag, sk_launch_owner_find, sk_launch_owner_stamps
  *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each
  *   skred_pedal_kernels.hip   sk_launch_pedal_clear, sk_launch_pedal_stamps, sk_launch_pedal_latch, sk_launch_pedal_up
+ *   skred_fx_pedal_kernels.hip  skx_launch_pedal_stamps, skx_launch_pedal_latch, skx_launch_pedal_up (sk_launch_pedal_clear by
+ *                             skred_fx_owner.c too)
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
@@ -38,6 +40,7 @@
 #include <stdint.h>
 
 #include "skred_device_layout.h"
+#include "skred_fx_layout.h"      /* skx_plane_t, for the fixed-point pedal launchers */
 
 #ifdef __cplusplus
 extern "C" {
@@ -383,6 +386,22 @@ int sk_launch_pedal_latch(const uint32_t *owner, uint32_t *pedal, uint32_t value
 int sk_launch_pedal_up(const uint32_t *owner, uint32_t *pedal, uint32_t value, uint32_t mask, int first, int count, int slot_voices,
                        uint64_t voice_mask, uint32_t flags, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
                        uint64_t now, uint64_t *mask_list, uint32_t *d_result, hipStream_t stream);
+
+/* ---- pedals on the fixed-point bank (skred_fx_pedal.c -> skred_fx_pedal_kernels.hip; include/skred_amd_fxpt.h:
+ * skred_fxbank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up) ----
+ * The three launchers above at one voice per slot, on the fixed-point planes (time_plane: SKX_TIME, rw0: read-write plane 0, osc:
+ * SKX_OSC); the bits are SK_PEDAL_*; each d_result is zeroed on `stream` ahead of its kernel.  The clear behind a tag launch is
+ * sk_launch_pedal_clear itself, at slot_voices = 1. */
+/* d_result[4] += voices stamped, voices whose owner differs, entries that are no voice, voices held back */
+int skx_launch_pedal_stamps(const uint32_t *owner, uint32_t *pedal, const int32_t *d_voices, const uint32_t *d_tags, int n,
+                            const uint32_t *d_count, int n_voices, int hold_all, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now,
+                            uint32_t *d_result, hipStream_t stream);
+/* d_result[2] += voices that satisfy the latch rule, voices of the range that did not match */
+int skx_launch_pedal_latch(const uint32_t *owner, uint32_t *pedal, uint32_t value, uint32_t mask, int first, int count,
+                           const skx_plane_t *osc, skx_plane_t *time_plane, skx_plane_t *rw0, uint32_t *d_result, hipStream_t stream);
+/* d_result[3] += voices released, voices still pending, voices of the range that did not match */
+int skx_launch_pedal_up(const uint32_t *owner, uint32_t *pedal, uint32_t value, uint32_t mask, int first, int count, uint32_t flags,
+                        skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, uint32_t *d_result, hipStream_t stream);
 
 /* stem recorder (skred_recorder.c): min/max partials of rec[n_floats]; selected voices -> int16 pairs */
 int sk_rec_partial_floats(void);

@@ -12,6 +12,8 @@ import numpy as np
 
 from . import banks
 from .device import OwnerMatchC, SkredAmdError, _check, load
+from .device import (PEDAL_PENDING, PEDAL_LATCHED, PEDAL_LIFT_SUSTAIN, PEDAL_LIFT_SOSTENUTO, PEDAL_SUSTAIN_DOWN,   # noqa: F401
+                     PEDAL_CALL_STAMP_OWNED, PEDAL_CALL_RELEASE_TAGS, PEDAL_CALL_LATCH, PEDAL_CALL_UP)             # (SKRED_PEDAL_*: the float bank's, as they are)
 
 U32, I32, U64 = np.dtype("<u4"), np.dtype("<i4"), np.dtype("<u8")
 FX_FIELDS = [
@@ -42,9 +44,11 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_find_match", "skred_fxbank_find_match_host", "skred_fxbank_stamp_match", "skred_fxbank_ctl_match",
                   "skred_fxbank_ctl_owned_each", "skred_fxbank_ctl_tags_each",
                   "skred_fxbank_find_steal_match", "skred_fxbank_find_steal_match_host", "skred_fxbank_note_on_channel",
+                  "skred_fxbank_stamp_owned_pedal", "skred_fxbank_release_tags_pedal", "skred_fxbank_pedal_latch",
+                  "skred_fxbank_pedal_up", "skred_fxbank_pedal_clear", "skred_fxbank_download_pedals",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
 FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
-                       "skred_fx_ctl_each_check", "skred_fx_chan_check"]                                                                     # pure host: no bank, no device
+                       "skred_fx_ctl_each_check", "skred_fx_chan_check", "skred_fx_pedal_check"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -162,6 +166,16 @@ def fx_chan_check(idle_q: Optional[FxIdleQueryC], steal_q: Optional[FxStealQuery
                                                  C.byref(steal_q) if steal_q is not None else None,
                                                  C.byref(m) if m is not None else None, int(cap),
                                                  t.ctypes.data if t is not None else None, int(n), int(n_voices)))
+
+
+def fx_pedal_check(call: int, n_voices: int, first: int = 0, count: int = 0, m: Optional[OwnerMatchC] = None, flags: int = 0, tags=None,
+                   n: Optional[int] = None) -> int:
+    """skred_fx_pedal_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for what the pedal entry point PEDAL_CALL_* would refuse.
+    Pure host, no device.  ``tags`` None: a NULL array."""
+    t = _tags(tags) if tags is not None else None
+    n = (len(t) if t is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_pedal_check(int(call), int(n_voices), int(first), int(count), C.byref(m) if m is not None else None,
+                                                  int(flags), t.ctypes.data if t is not None else None, int(n)))
 
 
 class FxNoteC(C.Structure):
@@ -284,6 +298,13 @@ def _bind(L):
     L.skred_fxbank_find_steal_match_host.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
     L.skred_fx_chan_check.argtypes = [vp, vp, vp, C.c_uint32, vp, i32, i32]
     L.skred_fxbank_note_on_channel.argtypes = [vp, vp, vp, vp, C.c_uint32, vp, vp, i32, vp, vp, vp]
+    L.skred_fx_pedal_check.argtypes = [i32, i32, i32, i32, vp, C.c_uint32, vp, i32]
+    L.skred_fxbank_stamp_owned_pedal.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
+    L.skred_fxbank_release_tags_pedal.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp]
+    L.skred_fxbank_pedal_latch.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.skred_fxbank_pedal_up.argtypes = [vp, i32, i32, vp, C.c_uint32, vp, vp]
+    L.skred_fxbank_pedal_clear.argtypes = [vp, i32, i32, vp]
+    L.skred_fxbank_download_pedals.argtypes = [vp, vp, i32, i32]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -582,6 +603,46 @@ class DeviceFxBank:
         _check(self.L.skred_fxbank_note_on_channel(self.h, C.byref(idle_q), C.byref(steal_q), C.byref(m), int(cap),
                                                    C.cast(arr, C.c_void_p), t.ctypes.data, len(arr), d_assigned or None,
                                                    d_result or None, stream or None), "skred_fxbank_note_on_channel")
+
+    # ---- pedals (include/skred_amd_fxpt.h: skred_fxbank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up) ----
+    def stamp_owned_pedal(self, d_voices: int, tags, hold_all: bool, d_result: int, d_count: int = 0, stream: int = 0):
+        """stamp_owned's release, held back (PEDAL_PENDING) where hold_all is set or the voice is PEDAL_LATCHED; d_result[0..3] =
+        stamped, owner differs, no voice, held back (uint32)."""
+        t = _tags(tags)
+        _check(self.L.skred_fxbank_stamp_owned_pedal(self.h, d_voices or None, t.ctypes.data, len(t), d_count or None, int(bool(hold_all)),
+                                                     d_result or None, stream or None), "skred_fxbank_stamp_owned_pedal")
+
+    def release_tags_pedal(self, first: int, count: int, tags, hold_all: bool, d_result: int, stream: int = 0):
+        """Note-off by note id under the pedals: every tag reaches the lowest voice of the range that carries it.  d_result as for
+        stamp_owned_pedal; [2] counts the tags nobody carries."""
+        t = _tags(tags)
+        _check(self.L.skred_fxbank_release_tags_pedal(self.h, int(first), int(count), t.ctypes.data, len(t), int(bool(hold_all)),
+                                                      d_result or None, stream or None), "skred_fxbank_release_tags_pedal")
+
+    def pedal_latch(self, first: int, count: int, value: int, mask: int, d_result: int, stream: int = 0):
+        """Sostenuto down: PEDAL_LATCHED on the matching voices that are held and not pending; d_result[0..1] = voices that satisfy
+        the rule, voices that did not match (uint32)."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_pedal_latch(self.h, int(first), int(count), C.byref(m), d_result or None, stream or None),
+               "skred_fxbank_pedal_latch")
+
+    def pedal_up(self, first: int, count: int, value: int, mask: int, flags: int, d_result: int, stream: int = 0):
+        """A pedal goes up (PEDAL_LIFT_* / PEDAL_SUSTAIN_DOWN): the held-back note-offs of the matching voices are stamped now.
+        d_result[0..2] = released, still pending, did not match (uint32)."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_pedal_up(self.h, int(first), int(count), C.byref(m), int(flags), d_result or None, stream or None),
+               "skred_fxbank_pedal_up")
+
+    def pedal_clear(self, first: int = 0, count: Optional[int] = None, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_fxbank_pedal_clear(self.h, int(first), int(count), stream or None), "skred_fxbank_pedal_clear")
+
+    def download_pedals(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The pedal words of [first, first + count) (uint32); waits for the device.  Zeros on a bank without a pedal array."""
+        count = self.n - first if count is None else count
+        out = np.full(max(count, 0), 0xABABABAB, np.uint32)
+        _check(self.L.skred_fxbank_download_pedals(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_pedals")
+        return out
 
 
 # ------------------------------------------------------------------ synthetic fixed-point bank

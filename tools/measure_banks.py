@@ -1643,8 +1643,87 @@ def pedal():
     db.close()
 
 
+def fxpedal():
+    """Pedals on bank_fx(2**20), every voice sounding and tagged over 16 channels (tag = channel << 24 | voice // 16 + 1), 256
+    note-offs of one channel held back, then the pedal goes up: the `pedal` mode on the fixed-point bank.  (a) each new call beside
+    the only correct route without the pedal array -- skred_fxbank_download_owners and skred_fxbank_download behind a device wait, the
+    host's pending tags mapped (numpy: one sort, one search) to the voices that still carry them, the list uploaded,
+    skred_fxbank_stamp; (b) skred_fxbank_release_tags_pedal with hold_all 1 and 0 beside skred_fxbank_release_tags of the same tags,
+    skred_fxbank_pedal_up and _pedal_latch beside skred_fxbank_stamp_match of the same channel; (c) the 64-frame block after the
+    pedal-up beside the block after skred_fxbank_stamp_list of the same voices; (d) skred_fxbank_tag_list of 256 voices before the
+    bank has a pedal array and after (the clear launch behind the tag kernel).  Medians of 12 with minimum and maximum; host time
+    held, and stream time between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES = 1 << 20, 64, 16, 256
+    bank, pool, c0 = X.bank_fx(n)
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    everyone = torch.arange(n, dtype=torch.int32, device="cuda")
+    db.tag_list(everyone.data_ptr(), tags)
+    value, mask = 3 << 24, 0xFF000000
+    held_at = np.flatnonzero(v % CHANNELS == 2)[::7][:NOTES]                     # 256 notes of channel 3
+    note_tags, note_voices = tags[held_at].copy(), held_at.astype(np.int32)
+    dl_notes = torch.from_numpy(note_voices).cuda()
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    state = bank.copy()
+    torch.cuda.synchronize()
+
+    retrig = lambda: db.stamp_list(dl_notes.data_ptr(), NOTES, X.STAMP_TRIGGER)   # noqa: E731
+    hold = lambda: db.release_tags_pedal(0, n, note_tags, True, res.data_ptr())   # noqa: E731
+    reset = lambda: (retrig(), db.pedal_clear())                                  # noqa: E731
+    pend = lambda: (retrig(), hold())                                             # noqa: E731
+
+    def parent_route():
+        own = db.download_owners()                                                # the device waits the pedal calls were built to remove
+        db.download(state)
+        order = np.argsort(own, kind="stable")                                    # the host's map: which voice carries which tag now
+        at = np.minimum(np.searchsorted(own[order], note_tags), n - 1)
+        voices = order[at]
+        lst = voices[(own[voices] == note_tags) & (state["is_active"][voices] != 0)].astype(np.int32)
+        db.stamp(lst, X.FX_STAMP_RELEASE)
+
+    def line(label, call, words, before=None):
+        ms, held = _fx_timed(call, before)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {res.cpu().numpy().tolist()[:words]}")
+
+    print(f"fx {n} voices all sounding, tagged over {CHANNELS} channels ({n // CHANNELS} notes each); {NOTES} note-offs of one channel")
+    line(f"(d) tag_list of {NOTES} voices, no pedal array yet", lambda: db.tag_list(dl_notes.data_ptr(), note_tags), 0)
+    line(f"(b) release_tags of {NOTES} tags", lambda: db.release_tags(0, n, note_tags, X.STAMP_RELEASE, res.data_ptr()), 3, retrig)
+    line("(b) release_tags_pedal of the same tags, held back (hold_all 1)", hold, 4, reset)
+    line("(b) release_tags_pedal of the same tags, hold_all 0", lambda: db.release_tags_pedal(0, n, note_tags, False, res.data_ptr()), 4, reset)
+    line(f"(a) stamp_owned_pedal of the same {NOTES} voices, held back",
+         lambda: db.stamp_owned_pedal(dl_notes.data_ptr(), note_tags, True, res.data_ptr()), 4, reset)
+    line(f"(d) tag_list of {NOTES} voices with the clear launch behind it", lambda: db.tag_list(dl_notes.data_ptr(), note_tags), 0)
+    line("(a) pedal_up of the channel", lambda: db.pedal_up(0, n, value, mask, X.PEDAL_LIFT_SUSTAIN, res.data_ptr()), 3, pend)
+    line("(b) stamp_match of the channel", lambda: db.stamp_match(0, n, value, mask, X.STAMP_RELEASE, res.data_ptr()), 2, retrig)
+    line("(a) pedal_latch of the channel", lambda: db.pedal_latch(0, n, value, mask, res.data_ptr()), 2, reset)
+    db.pedal_clear()
+    line("(a) the pedal-up without the array, download_owners + download + host map + list upload + stamp", parent_route, 0, retrig)
+
+    def block_after(call, before):
+        after = []
+        for _ in range(12):
+            before()
+            _fx_block_after(db, out, F, None, 1)
+            call()
+            after += _fx_block_after(db, out, F, None, 1)
+            _fx_block_after(db, out, F, None, 1)
+        return after
+    db.upload(bank); db.set_sample_count(c0)
+    _fx_block_after(db, out, F, None, 8)
+    steady = _fx_block_after(db, out, F)
+    after_up = block_after(lambda: db.pedal_up(0, n, value, mask, X.PEDAL_LIFT_SUSTAIN, res.data_ptr()), pend)
+    after_list = block_after(lambda: db.stamp_list(dl_notes.data_ptr(), NOTES, X.STAMP_RELEASE), retrig)
+    print(f"  (c) the {F}-frame block after pedal_up: {_fx_stats(after_up)}; after stamp_list of the same {NOTES} voices: {_fx_stats(after_list)}; "
+          f"a steady block: {_fx_stats(steady)}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan, "fxchan": fxchan, "pedal": pedal}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
