@@ -914,7 +914,7 @@ int  skred_bank_download_env_clocks(skred_bank_t *bank, uint64_t *sample_start, 
  * unguarded twins tell it (below).
  * The fixed-point bank has the same calls per voice (include/skred_amd_fxpt.h: skred_fxbank_find_match / _stamp_match / _ctl_match /
  * _ctl_owned_each / _ctl_tags_each, with this section's skred_owner_match_t and SKRED_EACH_* bits).
- * Out of scope: the drop-in mode, deferred items and pattern steps (they carry no tags), per-entry filter coefficients.  On a shard: through skred_shard_bank(), with that rank's local indices, and nothing beyond that.
+ * Out of scope: the drop-in mode, deferred items and pattern steps (they carry no tags).  On a shard: through skred_shard_bank(), with that rank's local indices, and nothing beyond that.
  *
  * A. Masked owner matches.  A slot MATCHES m when owner != 0 && (owner & m->mask) == m->value: mask 0 with value 0 is every tagged
  * slot, mask 0xFF000000 a channel byte, mask 0xFFFFFFFF one note.  An untagged slot matches nothing. */
@@ -991,6 +991,47 @@ int  skred_bank_ctl_owned_each(skred_bank_t *bank, const skred_ctl_t *ctl, const
  * Refusals of both calls. */
 int  skred_bank_ctl_tags_each(skred_bank_t *bank, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int first, int count,
                               int slot_voices, uint64_t voice_mask, const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+
+/* C. Per-note timbre: per-entry filter coefficients.  The two calls of B with one more array: entry k also brings ONE set of biquad
+ * coefficients, stored on every voice l of its slot that has bit l of filter_mask set -- key tracking, velocity-to-cutoff, MPE
+ * timbre (CC 74) on a patch whose voices are filtered, n notes with n cutoffs in one call.  The words are SKRED_CTL_FILTER's:
+ * voice_filter.b0 b1 b2 a1 a2 = filt[k]; the filter memory (x1 x2 y1 y2) is untouched, and a voice whose filter is bypassed keeps
+ * the words without reading them.  Entry k acts exactly as it does in B (a valid slot whose owner is tags[k]); the records of `ctl`
+ * and the values of each[k] are stored as there, under the same two withheld-store rules and the same listing rule.  `each` may be
+ * NULL here: the coefficients only; `ctl` may be NULL as in B.  d_result keeps its three words; a voice written only through
+ * filter_mask counts in [0] once, like any written voice (filter_mask is a subset of voice_mask, and [0] counts the voices of
+ * voice_mask).  FILTER is not a listing word: a call whose records and entries name none leaves the planner's reports alone, and
+ * the block behind it is the steady block.  One set per entry: voices of one slot that need different coefficients take a record
+ * of `ctl` each (SKRED_CTL_FILTER) on the lanes outside filter_mask.
+ * Out of scope: the drop-in mode, deferred items and pattern steps, coefficients computed on the device.  On a shard: through
+ * skred_shard_bank(), with that rank's local indices.  The fixed-point bank has the twin (include/skred_amd_fxpt.h:
+ * skred_fxbank_ctl_owned_each_filter / _ctl_tags_each_filter). */
+typedef struct skred_filter_each { float b0, b1, b2, a1, a2; uint32_t reserved[3]; } skred_filter_each_t;   /* 32 bytes, reserved 0 */
+/* Pure host: SKRED_OK, or what the two entry points refuse about the coefficients.  SKRED_E_RANGE: a bad K.  SKRED_E_BAD_ARG: NULL
+ * filt, n < 0, a bad voice_mask, filter_mask == 0 or with a bit outside voice_mask; with ctl != NULL what skred_ctl_check refuses,
+ * and a record l with bit l in filter_mask that itself names SKRED_CTL_FILTER (two sets of coefficients for one voice: ambiguous,
+ * as INC_SCALE against PHASE_INC is); in an entry: a reserved word that is not 0, a coefficient that is not finite. */
+int  skred_filter_each_check(const skred_filter_each_t *filt, int n, const skred_ctl_t *ctl_or_null, int slot_voices,
+                             uint64_t voice_mask, uint64_t filter_mask);
+/* skred_bank_ctl_owned_each with filt[k] beside each[k].  The three arrays and the tags travel through the staging ring in one
+ * batch; one kernel reads them.  Refused: what skred_bank_ctl_owned_each refuses (a NULL `each` excepted) and what
+ * skred_filter_each_check refuses.  n == 0: SKRED_OK. */
+int  skred_bank_ctl_owned_each_filter(skred_bank_t *bank, const skred_ctl_t *ctl_or_null, const skred_ctl_each_t *each_or_null,
+                                      const skred_filter_each_t *filt, int slot_voices, uint64_t voice_mask, uint64_t filter_mask,
+                                      const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                                      uint32_t *d_result, void *stream);
+/* skred_bank_ctl_tags_each with filt[k] beside tags[k]: the tags travel sorted, and filt is permuted on the host with each by the
+ * same permutation.  Refusals of skred_bank_ctl_tags_each (a NULL `each` excepted) and of skred_filter_each_check. */
+int  skred_bank_ctl_tags_each_filter(skred_bank_t *bank, const skred_ctl_t *ctl_or_null, const skred_ctl_each_t *each_or_null,
+                                     const skred_filter_each_t *filt, int first, int count, int slot_voices, uint64_t voice_mask,
+                                     uint64_t filter_mask, const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+/* The coefficients of one filter setting, pure host: the arithmetic of the drop-in mode's mmf_set_params (RBJ cookbook, fp32, the
+ * operations in its order; skred_synth_dropin.c calls this function) with the sample rate as an argument, so that a host computes
+ * key-tracked coefficients without a voice array.  mode: 1 low-pass, 2 high-pass, 3 band-pass, 4 notch, 5 all-pass; any other
+ * non-zero mode is low-pass, as there.  out5 = b0 b1 b2 a1 a2.  Returns SKRED_OK; 1 for mode 0 (bypass: nothing is computed and out5
+ * is left as it is, as mmf_set_params leaves the voice's words); SKRED_E_BAD_ARG for a NULL out5.  The arguments are not judged: a
+ * resonance of 0 gives coefficients that are not finite, which skred_filter_each_check refuses. */
+int  skred_filter_coeffs(int mode, float freq, float resonance, float sample_rate, float out5[5]);
 
 /* ---- channel polyphony: stealing inside one channel, note-ons under a cap ---------------------------------------------------
  *

@@ -371,7 +371,7 @@ int  skred_fxbank_download_params(skred_fxbank_t *fx, skred_fxpt_bank_t *host, u
  * add: a bank that makes match queries renders the blocks of a bank that makes none, bit for bit.  Every refusal comes before
  * anything touches the device.  One stream at a time per bank, as for the queries (the list shares their scratch).  On a shard:
  * through skred_fxshard_bank(), with that rank's local indices.
- * Out of scope: slots (K > 1), the deferred queue and pattern steps, the drop-in mode, per-entry filter coefficients.
+ * Out of scope: slots (K > 1), the deferred queue and pattern steps, the drop-in mode.
  *
  * A. Masked matches.  skred_owner_match_t and skred_owner_match_check are the float bank's, as they are.  A voice MATCHES m when
  * owner != 0 && (owner & m->mask) == m->value: mask 0 with value 0 is every tagged voice, mask 0xFF000000 a channel byte, mask
@@ -454,6 +454,38 @@ int  skred_fxbank_ctl_owned_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, 
                                  const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
 int  skred_fxbank_ctl_tags_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, int first, int count,
                                 const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+
+/* C. Per-note timbre: per-entry filter coefficients.  The per-voice twin of the float bank's section C (include/skred_amd.h:
+ * skred_bank_ctl_owned_each_filter / _ctl_tags_each_filter) at K = 1, without masks: the two calls of B with one more array, entry k
+ * also bringing the five Q2.30 coefficients of its voice -- key tracking, velocity-to-cutoff, MPE timbre (CC 74), n notes with n
+ * cutoffs in one call instead of n skred_fxbank_ctl_owned calls.  The five words are stored as SKRED_CTL_FILTER stores them on this
+ * bank: any int32; filter_mode and the delay line are untouched, and on a voice without a filter the words are inert.  Entry k
+ * acts exactly as it does in B (a voice of the bank whose owner is tags[k]); the record and each[k] are stored as there, under the
+ * same withheld-store rules.  `each` may be NULL here: the coefficients only; `ctl` may be NULL as in B.  d_result keeps its three
+ * words and their meaning.
+ *
+ * skred_fx_filter_each_check          pure host: SKRED_OK, or SKRED_E_BAD_ARG for NULL filt, n < 0, a non-zero reserved word; with
+ *                                     ctl != NULL what skred_fx_ctl_check refuses, and a ctl that itself names SKRED_CTL_FILTER
+ *                                     (two sets of coefficients for one voice: ambiguous).
+ * skred_fxbank_ctl_owned_each_filter  skred_fxbank_ctl_owned_each with filt[k] beside each[k]; the arrays and the tags travel in one
+ *                                     staged batch, one kernel reads them.  Refused: what _ctl_owned_each refuses (a NULL `each`
+ *                                     excepted) and what skred_fx_filter_each_check refuses.  n == 0: SKRED_OK.
+ * skred_fxbank_ctl_tags_each_filter   skred_fxbank_ctl_tags_each with filt[k] beside tags[k]: the tags travel sorted, and filt is
+ *                                     permuted on the host with each by the same permutation.  Refusals of both.
+ * Out of scope: the deferred queue and pattern steps, the drop-in mode, coefficients computed on the device (skred_filter_coeffs of
+ * include/skred_amd.h computes fp32 coefficients on the host; their conversion to Q2.30 is the host's, as for skred_fxbank_upload).
+ * LIMIT, as for the controllers: the host view goes stale; skred_fxbank_download_params reads the values back. */
+typedef struct skred_fx_filter_each {     /* 32 bytes */
+  int32_t  b0_q30, b1_q30, b2_q30, a1_q30, a2_q30;
+  uint32_t reserved[3];                   /* 0 */
+} skred_fx_filter_each_t;
+int  skred_fx_filter_each_check(const skred_fx_filter_each_t *filt, int n, const skred_fx_ctl_t *ctl_or_null);
+int  skred_fxbank_ctl_owned_each_filter(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl_or_null, const skred_fx_ctl_each_t *each_or_null,
+                                        const skred_fx_filter_each_t *filt, const int32_t *d_voices, const uint32_t *tags, int n,
+                                        const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+int  skred_fxbank_ctl_tags_each_filter(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl_or_null, const skred_fx_ctl_each_t *each_or_null,
+                                       const skred_fx_filter_each_t *filt, int first, int count, const uint32_t *tags, int n,
+                                       uint32_t *d_result, void *stream);
 
 /* ---- channel polyphony: stealing inside one channel, note-ons under a cap ---------------------------------------------------
  *

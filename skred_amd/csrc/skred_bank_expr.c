@@ -1,7 +1,8 @@
 /*
  * skred_bank_expr.c -- channels and per-note expression: masked owner matches and per-entry controller values
  * (include/skred_amd.h: skred_owner_match_check, skred_ctl_each_check, skred_bank_find_match / _find_match_host / _stamp_match /
- * _ctl_match / _ctl_owned_each / _ctl_tags_each).
+ * _ctl_match / _ctl_owned_each / _ctl_tags_each), and per-note timbre: the same two calls with per-entry filter coefficients
+ * (skred_filter_each_check, skred_bank_ctl_owned_each_filter / _ctl_tags_each_filter, skred_filter_coeffs).
  *
  * The host side of skred_expr_kernels.hip, on the pieces of skred_bank_checks.c and skred_bank_stage.c (and the owner array of
  * skred_bank_owner.c): the checks (made before anything touches the device), the records', entries' and tags' way through the batch
@@ -11,7 +12,7 @@
  * always grows it, ctl_match only when a record names a listing word, and a controller that lists nobody leaves the reports alone
  * (skred_bank_ctl.c has the measurement behind that).
  *
- * Out of scope: the fixed-point bank, the drop-in mode, deferred items and pattern steps, per-entry filter coefficients.
+ * Out of scope: the fixed-point bank, the drop-in mode, deferred items and pattern steps.
  */
 #include <math.h>
 #include <stddef.h>
@@ -28,6 +29,11 @@ _Static_assert(sizeof(skred_ctl_each_t) == sizeof(sk_each_t) && sizeof(skred_ctl
 _Static_assert(SK_EACH_INC_SCALE == SKRED_EACH_INC_SCALE && SK_EACH_AMP_SCALE == SKRED_EACH_AMP_SCALE && SK_EACH_VELOCITY == SKRED_EACH_VELOCITY &&
                SK_EACH_PAN == SKRED_EACH_PAN, "device per-entry bits must equal the public SKRED_EACH_* values");
 _Static_assert(sizeof(sk_ctl_t) % 32 == 0, "the entries behind the K records stay 16-byte aligned");
+
+_Static_assert(sizeof(skred_filter_each_t) == sizeof(sk_filt_each_t) && sizeof(skred_filter_each_t) == 32 && offsetof(skred_filter_each_t, b0) == 4 * SK_FILT_W_B0 &&
+               offsetof(skred_filter_each_t, b1) == 4 * SK_FILT_W_B1 && offsetof(skred_filter_each_t, b2) == 4 * SK_FILT_W_B2 &&
+               offsetof(skred_filter_each_t, a1) == 4 * SK_FILT_W_A1 && offsetof(skred_filter_each_t, a2) == 4 * SK_FILT_W_A2 &&
+               offsetof(skred_filter_each_t, reserved) == 20, "the device's per-entry filter record must be skred_filter_each_t word for word");
 
 /* the entry bits that put a voice on the motion list (AMP_SCALE stores voice_amp, VELOCITY the envelope's velocity) */
 #define SK_EACH_LISTS (SKRED_EACH_AMP_SCALE | SKRED_EACH_VELOCITY)
@@ -91,6 +97,64 @@ uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm,
     bits |= e->set;
   }
   return bits;
+}
+
+/* K, the two masks and the records first (what each_check looks at before its entries), then the coefficients */
+static int filter_check(const skred_filter_each_t *filt, int n, const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask, uint64_t filter_mask,
+                        const char *who) {
+  if (!filt) return fail(SKRED_E_BAD_ARG, "%s: no coefficients", who);
+  if (n < 0) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);
+  int rc;
+  if (ctl) { if ((rc = skred_ctl_check(ctl, slot_voices, voice_mask))) return rc; }
+  else if ((rc = sk_check_slot_shape(slot_voices, voice_mask, "voice_mask", who))) return rc;
+  if (!filter_mask) return fail(SKRED_E_BAD_ARG, "%s: filter_mask is 0", who);
+  if (filter_mask & ~voice_mask) return fail(SKRED_E_BAD_ARG, "%s: filter_mask = 0x%llx has bits outside voice_mask = 0x%llx", who,
+                                             (unsigned long long)filter_mask, (unsigned long long)voice_mask);
+  for (int l = 0; ctl && l < slot_voices; l++)
+    if (((filter_mask >> l) & 1) && (ctl[l].set & SKRED_CTL_FILTER))
+      return fail(SKRED_E_BAD_ARG, "%s: record %d names SKRED_CTL_FILTER and bit %d of filter_mask is set: two sets of coefficients", who, l, l);
+  for (int k = 0; k < n; k++) {
+    const skred_filter_each_t *f = &filt[k];
+    if (f->reserved[0] || f->reserved[1] || f->reserved[2]) return fail(SKRED_E_BAD_ARG, "%s: coefficients %d: the reserved words must be 0", who, k);
+    if (!isfinite(f->b0) || !isfinite(f->b1) || !isfinite(f->b2) || !isfinite(f->a1) || !isfinite(f->a2))
+      return fail(SKRED_E_BAD_ARG, "%s: coefficients %d hold %g %g %g %g %g", who, k, (double)f->b0, (double)f->b1, (double)f->b2, (double)f->a1,
+                  (double)f->a2);
+  }
+  return SKRED_OK;
+}
+
+int skred_filter_each_check(const skred_filter_each_t *filt, int n, const skred_ctl_t *ctl, int slot_voices, uint64_t voice_mask,
+                            uint64_t filter_mask) {
+  return filter_check(filt, n, ctl, slot_voices, voice_mask, filter_mask, "filter_each_check");
+}
+
+/* The checked coefficients as they travel: out[j] = filt[perm[j]] (perm NULL: j), the five words as they stand, the rest zero.  Pure host */
+void sk_filt_pack(const skred_filter_each_t *filt, int n, const uint32_t *perm, sk_filt_each_t *out) {
+  memset(out, 0, (size_t)n * sizeof(sk_filt_each_t));
+  for (int j = 0; j < n; j++) memcpy(out[j].w, &filt[perm ? perm[j] : (uint32_t)j], 5 * sizeof(uint32_t));
+}
+
+/* mmf_set_params' arithmetic (skred_synth_dropin.c calls this): fp32 throughout, every product, sum and quotient rounded on its own
+ * -- the Makefile builds this file with -ffp-contract=off, as it builds the drop-in's */
+int skred_filter_coeffs(int mode, float freq, float resonance, float sample_rate, float out5[5]) {
+  if (!out5) return fail(SKRED_E_BAD_ARG, "filter_coeffs: nowhere to put the coefficients");
+  if (mode == 0) return 1;                                    /* bypassed: nothing computed */
+  const float w = 2.0f * (float)M_PI * freq / sample_rate;
+  const float sn = sinf(w), cs = cosf(w);
+  const float alpha = sn / (2.0f * resonance);
+  const float a0 = 1.0f + alpha;
+  float b0, b1, b2;
+  switch (mode) {
+    case 2:  b0 = (1.0f + cs) / 2.0f; b1 = -(1.0f + cs); b2 = (1.0f + cs) / 2.0f; break;   /* high-pass */
+    case 3:  b0 = alpha; b1 = 0.0f; b2 = -alpha; break;                                    /* band-pass */
+    case 4:  b0 = 1.0f; b1 = -2.0f * cs; b2 = 1.0f; break;                                 /* notch */
+    case 5:  b0 = 1.0f - alpha; b1 = -2.0f * cs; b2 = 1.0f + alpha; break;                 /* all-pass */
+    default: b0 = (1.0f - cs) / 2.0f; b1 = 1.0f - cs; b2 = (1.0f - cs) / 2.0f; break;      /* low-pass; also any unknown mode */
+  }
+  out5[0] = b0 / a0; out5[1] = b1 / a0; out5[2] = b2 / a0;
+  out5[3] = (-2.0f * cs) / a0;
+  out5[4] = (1.0f - alpha) / a0;
+  return SKRED_OK;
 }
 
 /* ---- A. masked owner matches ---- */
@@ -194,22 +258,27 @@ int skred_bank_ctl_match(skred_bank_t *b, const skred_ctl_t *ctl, int first, int
 
 /* ---- B. per-entry controller values ---- */
 
-static int owned_each_check(const skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int slot_voices, uint64_t voice_mask,
-                            const uint32_t *tags, int n, uint32_t tag_flags, const char *who) {
+/* with_filter: a call of section C -- `each` may be NULL, `filt` may not, and the coefficients are checked behind the entries */
+static int owned_each_check(const skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, const skred_filter_each_t *filt,
+                            int with_filter, int slot_voices, uint64_t voice_mask, uint64_t filter_mask, const uint32_t *tags, int n,
+                            uint32_t tag_flags, const char *who) {
   if (!b) return fail(SKRED_E_BAD_ARG, "%s: no bank", who);
   int rc = skred_owner_tags_check(tags, n, tag_flags);
   if (rc) return rc;
   if ((rc = sk_check_list_n(n, who))) return rc;
-  return each_check(each, n, ctl, slot_voices, voice_mask, who);
+  if (!with_filter) return each_check(each, n, ctl, slot_voices, voice_mask, who);
+  if (each && (rc = each_check(each, n, ctl, slot_voices, voice_mask, who))) return rc;
+  return filter_check(filt, n, ctl, slot_voices, voice_mask, filter_mask, who);
 }
 
-/* the K records (zeros without `ctl`), the n entries (each[perm[j]]; perm NULL: as they stand) and the n tags in one staging slot:
- * one kernel reads all three */
-static int owned_each_launch(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, const uint32_t *perm, int slot_voices,
-                             uint64_t voice_mask, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count,
-                             uint32_t *d_result, const char *what, hipStream_t s) {
-  const size_t rec_bytes = (size_t)slot_voices * sizeof(sk_ctl_t), each_bytes = (size_t)n * sizeof(sk_each_t);
-  const size_t bytes = rec_bytes + each_bytes + (size_t)n * sizeof(uint32_t);
+/* the K records (zeros without `ctl`), the n entries (each[perm[j]]; perm NULL: as they stand), with `filt` the n sets of coefficients
+ * (permuted likewise; then `each` may be NULL and no entries travel) and the n tags in one staging slot: one kernel reads them all */
+static int owned_each_launch(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, const skred_filter_each_t *filt,
+                             const uint32_t *perm, int slot_voices, uint64_t voice_mask, uint64_t filter_mask, const int32_t *d_slots,
+                             const uint32_t *tags, int n, const uint32_t *d_count, uint32_t *d_result, const char *what, hipStream_t s) {
+  const size_t rec_bytes = (size_t)slot_voices * sizeof(sk_ctl_t), each_bytes = each ? (size_t)n * sizeof(sk_each_t) : 0;
+  const size_t filt_bytes = filt ? (size_t)n * sizeof(sk_filt_each_t) : 0;
+  const size_t bytes = rec_bytes + each_bytes + filt_bytes + (size_t)n * sizeof(uint32_t);
   const int wide = (int64_t)n * slot_voices > 64 * SK_EXPR_SPAN;
   sk_batch_t bt;
   int rc = sk_batch_begin(b, bytes, s, &bt);
@@ -218,45 +287,77 @@ static int owned_each_launch(skred_bank_t *b, const skred_ctl_t *ctl, const skre
   uint64_t lists = 0;
   if (ctl) lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)h);
   else memset(h, 0, rec_bytes);
-  const uint32_t bits = sk_each_pack(each, n, perm, (sk_each_t *)(h + rec_bytes));
-  memcpy(h + rec_bytes + each_bytes, tags, (size_t)n * sizeof(uint32_t));
+  const uint32_t bits = each ? sk_each_pack(each, n, perm, (sk_each_t *)(h + rec_bytes)) : 0u;
+  if (filt) sk_filt_pack(filt, n, perm, (sk_filt_each_t *)(h + rec_bytes + each_bytes));
+  memcpy(h + rec_bytes + each_bytes + filt_bytes, tags, (size_t)n * sizeof(uint32_t));
   const char *src = (const char *)sk_batch_send(b, &bt, bytes, wide, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)sk_launch_ctl_owned_each((const sk_ctl_t *)src, (const sk_each_t *)(src + rec_bytes), slot_voices, voice_mask,
-                                                            d_slots, (const uint32_t *)(src + rec_bytes + each_bytes), b->d_owner, n, d_count,
-                                                            b->n_voices, b->d_ro, b->d_rw, b->d_mask[b->mask_p], d_result, bt.cnt, bt.done, bt.seq, s);
+  const hipError_t e = (hipError_t)sk_launch_ctl_owned_each_filter((const sk_ctl_t *)src, each ? (const sk_each_t *)(src + rec_bytes) : NULL,
+                                                                   filt ? (const sk_filt_each_t *)(src + rec_bytes + each_bytes) : NULL,
+                                                                   slot_voices, voice_mask, filter_mask, d_slots,
+                                                                   (const uint32_t *)(src + rec_bytes + each_bytes + filt_bytes), b->d_owner, n,
+                                                                   d_count, b->n_voices, b->d_ro, b->d_rw, b->d_mask[b->mask_p], d_result,
+                                                                   bt.cnt, bt.done, bt.seq, s);
   if ((rc = sk_batch_end(&bt, e, what, s))) return rc;
   if (lists || (bits & SK_EACH_LISTS)) sk_touched(b, (uint64_t)n * (uint64_t)__builtin_popcountll(voice_mask));
   return SKRED_OK;
 }
 
-int skred_bank_ctl_owned_each(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int slot_voices, uint64_t voice_mask,
-                              const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result,
-                              void *stream) {
-  if (!d_slots) return fail(SKRED_E_BAD_ARG, "ctl_owned_each: no list");
-  int rc = owned_each_check(b, ctl, each, slot_voices, voice_mask, tags, n, 0, "ctl_owned_each");
+static int owned_each_call(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, const skred_filter_each_t *filt, int with_filter,
+                           int slot_voices, uint64_t voice_mask, uint64_t filter_mask, const int32_t *d_slots, const uint32_t *tags, int n,
+                           const uint32_t *d_count_or_null, uint32_t *d_result, const char *who, void *stream) {
+  if (!d_slots) return fail(SKRED_E_BAD_ARG, "%s: no list", who);
+  int rc = owned_each_check(b, ctl, each, filt, with_filter, slot_voices, voice_mask, filter_mask, tags, n, 0, who);
   if (rc) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
-  return owned_each_launch(b, ctl, each, NULL, slot_voices, voice_mask, d_slots, tags, n, d_count_or_null, d_result, "ctl_owned_each",
+  return owned_each_launch(b, ctl, each, filt, NULL, slot_voices, voice_mask, filter_mask, d_slots, tags, n, d_count_or_null, d_result, who,
                            (hipStream_t)stream);
 }
 
-int skred_bank_ctl_tags_each(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int first, int count, int slot_voices,
-                             uint64_t voice_mask, const uint32_t *tags, int n, uint32_t *d_result, void *stream) {
-  int rc = owned_each_check(b, ctl, each, slot_voices, voice_mask, tags, n, SKRED_OWNER_UNIQUE, "ctl_tags_each");
+static int tags_each_call(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, const skred_filter_each_t *filt, int with_filter,
+                          int first, int count, int slot_voices, uint64_t voice_mask, uint64_t filter_mask, const uint32_t *tags, int n,
+                          uint32_t *d_result, const char *who, void *stream) {
+  int rc = owned_each_check(b, ctl, each, filt, with_filter, slot_voices, voice_mask, filter_mask, tags, n, SKRED_OWNER_UNIQUE, who);
   if (rc) return rc;
-  if ((rc = sk_check_slot_range(b->n_voices, first, count, slot_voices, 0, "ctl_tags_each"))) return rc;
+  if ((rc = sk_check_slot_range(b->n_voices, first, count, slot_voices, 0, who))) return rc;
   if (n == 0) return SKRED_OK;
-  /* the tags travel sorted (the find pass searches them), and each[k] stays with tags[k]: entry j of the list is the slot of the
-   * j-th smallest tag, and receives each[perm[j]] */
+  /* the tags travel sorted (the find pass searches them), and each[k] and filt[k] stay with tags[k]: entry j of the list is the slot
+   * of the j-th smallest tag, and receives each[perm[j]] and filt[perm[j]] */
   uint32_t sorted[SKRED_OWNER_MAX_TAGS], perm[SKRED_OWNER_MAX_TAGS];
   (void)sk_owner_pack(tags, n, sorted, perm);
   HIP_TRY(hipSetDevice(b->device));
   if ((rc = sk_owner_ensure(b))) return rc;
   if ((rc = skred_bank_find_owned(b, first, count, slot_voices, sorted, n, b->d_owner_slots, stream))) return rc;
   /* entry j is the lowest slot that carries sorted[j], or -1: the guard holds on every entry that is a slot */
-  return owned_each_launch(b, ctl, each, perm, slot_voices, voice_mask, b->d_owner_slots, sorted, n, NULL, d_result, "ctl_tags_each",
+  return owned_each_launch(b, ctl, each, filt, perm, slot_voices, voice_mask, filter_mask, b->d_owner_slots, sorted, n, NULL, d_result, who,
                            (hipStream_t)stream);
+}
+
+int skred_bank_ctl_owned_each(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int slot_voices, uint64_t voice_mask,
+                              const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result,
+                              void *stream) {
+  return owned_each_call(b, ctl, each, NULL, 0, slot_voices, voice_mask, 0, d_slots, tags, n, d_count_or_null, d_result, "ctl_owned_each", stream);
+}
+
+int skred_bank_ctl_tags_each(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, int first, int count, int slot_voices,
+                             uint64_t voice_mask, const uint32_t *tags, int n, uint32_t *d_result, void *stream) {
+  return tags_each_call(b, ctl, each, NULL, 0, first, count, slot_voices, voice_mask, 0, tags, n, d_result, "ctl_tags_each", stream);
+}
+
+/* ---- C. per-entry filter coefficients ---- */
+
+int skred_bank_ctl_owned_each_filter(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, const skred_filter_each_t *filt,
+                                     int slot_voices, uint64_t voice_mask, uint64_t filter_mask, const int32_t *d_slots, const uint32_t *tags,
+                                     int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream) {
+  return owned_each_call(b, ctl, each, filt, 1, slot_voices, voice_mask, filter_mask, d_slots, tags, n, d_count_or_null, d_result,
+                         "ctl_owned_each_filter", stream);
+}
+
+int skred_bank_ctl_tags_each_filter(skred_bank_t *b, const skred_ctl_t *ctl, const skred_ctl_each_t *each, const skred_filter_each_t *filt,
+                                    int first, int count, int slot_voices, uint64_t voice_mask, uint64_t filter_mask, const uint32_t *tags,
+                                    int n, uint32_t *d_result, void *stream) {
+  return tags_each_call(b, ctl, each, filt, 1, first, count, slot_voices, voice_mask, filter_mask, tags, n, d_result, "ctl_tags_each_filter",
+                        stream);
 }

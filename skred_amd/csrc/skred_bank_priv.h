@@ -9,7 +9,7 @@
  *   skred_bank_notes.c   note-ons and stamps on voices a device-resident list names
  *   skred_bank_slots.c   the same for the slots of a tiled patch, slot stealing, and channel polyphony (matched stealing, capped note-ons)
  *   skred_bank_ctl.c     patch controllers                     skred_bank_owner.c  note owners
- *   skred_bank_expr.c    channels and per-note expression: masked owner matches, per-entry controller values
+ *   skred_bank_expr.c    channels and per-note expression: masked owner matches, per-entry controller values and filter coefficients
  *   skred_bank_pedal.c   pedals: note-offs held back per slot, sostenuto's latch, the pedal-up
  */
 #ifndef SKRED_BANK_PRIV_H
@@ -300,6 +300,8 @@ void sk_pedal_free(skred_bank_t *b);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);
+/* ... and n checked sets of per-entry filter coefficients the same way: out[j] = filt[perm[j]], five words, the rest zero.  Pure host */
+void sk_filt_pack(const skred_filter_each_t *filt, int n, const uint32_t *perm, sk_filt_each_t *out);
 /* skred_bank_idle.c, for skred_bank_slots.c: the scratch both list queries share (allocated on first use), the kernels' view of a
  * query on this bank, and room for `need` entries in d_idle_out / h_idle_out */
 int sk_idle_scratch(skred_bank_t *b, hipStream_t s);

@@ -1,7 +1,7 @@
 // skred_expr_kernels.hip -- channels and per-note expression: masked owner matches over a range, and a guarded controller whose
 // entries bring values of their own (gfx950 / CDNA4, wave64).
 //
-// skred_bank_find_match / _stamp_match / _ctl_match / _ctl_owned_each / _ctl_tags_each (include/skred_amd.h).  owner[n_voices] is
+// skred_bank_find_match / _stamp_match / _ctl_match / _ctl_owned_each / _ctl_tags_each and the two _each_filter calls (include/skred_amd.h).  owner[n_voices] is
 // the note-owner array (skred_owner_kernels.hip has its rules): a slot's tag at its first voice, 0 for nobody.  A slot MATCHES
 // (value, mask) when owner != 0 && (owner & mask) == value.  These kernels read the array and never write it.
 //
@@ -16,6 +16,10 @@
 //                            runs: INC_SCALE, VELOCITY and PAN add the field to the record's `set` and supply its value; AMP_SCALE
 //                            replaces the record's amp by ONE fp32 product (__fmul_rn: never contracted), and a product that is
 //                            zero or not finite takes SK_CTL_AMP out of `set` for that voice and counts as withheld.
+//                            template <bool FILT>: the second instantiation (skred_bank_ctl_owned_each_filter / _ctl_tags_each_filter)
+//                            also takes filt[n] and a filter_mask, and on the lanes of that mask lays entry k's five coefficients
+//                            over the record with SK_CTL_FILTER: one 16-byte and one 4-byte load more per such lane, sk_ctl_store's
+//                            stores as they are.  FILT = false is the kernel as it was (profiles/timbre_usage.txt).
 //
 // The stores are sk_stamp_store's and sk_ctl_store's (skred_update_common.hpp, skred_ctl_common.hpp): nothing here can drift from
 // the unguarded calls.  Plain vector stores and ordinary atomics only; every count is an integer sum.
@@ -105,12 +109,21 @@ __global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_match_kernel(const sk_ctl
   sk_batch_done(cnt, done, seq);
 }
 
+// what the FILT instantiation takes beside the rest: entry k's coefficients and the voices of a slot that receive them (FILT false:
+// an empty struct the kernel never reads)
+template <bool FILT> struct sk_each_filt_t {};
+template <> struct sk_each_filt_t<true> {
+  const sk_filt_each_t *filt;
+  uint64_t filter_mask;
+};
+
+template <bool FILT>
 __global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_owned_each_kernel(const sk_ctl_t *__restrict__ recs, const sk_each_t *__restrict__ each,
                                                                          int k_shift, uint64_t voice_mask, const int32_t *d_slots,
                                                                          const uint32_t *__restrict__ tags, const uint32_t *__restrict__ owner,
                                                                          int n, const uint32_t *d_count, int n_voices, sk_plane_ptrs_t p,
                                                                          uint64_t *mask, uint32_t *d_result, uint32_t *cnt, uint32_t *done,
-                                                                         uint32_t seq) {
+                                                                         uint32_t seq, sk_each_filt_t<FILT> fa) {
   __shared__ uint32_t lds[64 * SK_CTL_WORDS];
   __shared__ uint32_t sums[3];
   const int K = 1 << k_shift;
@@ -132,8 +145,12 @@ __global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_owned_each_kernel(const s
     uint32_t r[SK_CTL_WORDS];                                           // record l with entry i laid over it (registers: constant indices)
 #pragma unroll
     for (int k = 0; k < SK_CTL_WORDS; ++k) r[k] = lds[l * SK_CTL_WORDS + k];
-    const uint4 ea = *reinterpret_cast<const uint4 *>(&each[i].w[0]);   // set, inc_scale, amp_scale, velocity
-    const uint2 eb = *reinterpret_cast<const uint2 *>(&each[i].w[SK_EACH_W_PAN_LEFT]);
+    uint4 ea = make_uint4(0u, 0u, 0u, 0u);                              // set, inc_scale, amp_scale, velocity
+    uint2 eb = make_uint2(0u, 0u);
+    if (!FILT || each) {                                                // (FILT: no entries is "the coefficients only")
+      ea = *reinterpret_cast<const uint4 *>(&each[i].w[0]);
+      eb = *reinterpret_cast<const uint2 *>(&each[i].w[SK_EACH_W_PAN_LEFT]);
+    }
     const uint32_t es = ea.x;
     if (es & SK_EACH_INC_SCALE) { r[SK_CTL_SET] |= SK_CTL_INC_SCALE; r[SK_CTL_W_INC_SCALE] = ea.y; }   // (the record names no increment: checked on the host)
     if (es & SK_EACH_AMP_SCALE) {                                       // (the record names SK_CTL_AMP: checked on the host)
@@ -143,6 +160,14 @@ __global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_owned_each_kernel(const s
     }
     if (es & SK_EACH_VELOCITY) { r[SK_CTL_SET] |= SK_CTL_VELOCITY; r[SK_CTL_W_VELOCITY] = ea.w; }
     if (es & SK_EACH_PAN) { r[SK_CTL_SET] |= SK_CTL_PAN; r[SK_CTL_W_PAN_LEFT] = eb.x; r[SK_CTL_W_PAN_RIGHT] = eb.y; }
+    if constexpr (FILT) {
+      if ((fa.filter_mask >> l) & 1) {                                  // (record l names no SK_CTL_FILTER: checked on the host)
+        const uint4 fc = *reinterpret_cast<const uint4 *>(&fa.filt[i].w[SK_FILT_W_B0]);   // b0, b1, b2, a1
+        r[SK_CTL_SET] |= SK_CTL_FILTER;
+        r[SK_CTL_W_B0] = fc.x; r[SK_CTL_W_B1] = fc.y; r[SK_CTL_W_B2] = fc.z; r[SK_CTL_W_A1] = fc.w;
+        r[SK_CTL_W_A2] = fa.filt[i].w[SK_FILT_W_A2];
+      }
+    }
     withheld += sk_ctl_store(p, mask, e + l, r);                        // (at most 2: one for the increment, one for the amp)
   }
   sk_expr_ctl_count(sums, d_result, mine, withheld, valid && !owned && l == 0);
@@ -206,10 +231,12 @@ extern "C" int sk_launch_ctl_match(const sk_ctl_t *d_recs, int slot_voices, uint
   return (int)hipGetLastError();
 }
 
-extern "C" int sk_launch_ctl_owned_each(const sk_ctl_t *d_recs, const sk_each_t *d_each, int slot_voices, uint64_t voice_mask,
-                                        const int32_t *d_slots, const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count,
-                                        int n_voices, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t *mask_list,
-                                        uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream) {
+// d_filt == NULL: the FILT = false instantiation, the per-entry controller without coefficients; else FILT = true
+extern "C" int sk_launch_ctl_owned_each_filter(const sk_ctl_t *d_recs, const sk_each_t *d_each, const sk_filt_each_t *d_filt, int slot_voices,
+                                               uint64_t voice_mask, uint64_t filter_mask, const int32_t *d_slots, const uint32_t *d_tags,
+                                               const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
+                                               sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t *mask_list,
+                                               uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
   if (d_result) {
     const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
@@ -219,7 +246,15 @@ extern "C" int sk_launch_ctl_owned_each(const sk_ctl_t *d_recs, const sk_each_t 
   sk_expr_planes(p, ro, rw);
   const int sh = sk_expr_shift(slot_voices), per_wg = SK_EXPR_SPAN >> sh;
   const unsigned n_wg = (unsigned)(((long long)n + per_wg - 1) / per_wg);
-  hipLaunchKernelGGL(sk_ctl_owned_each_kernel, dim3(n_wg), dim3(SK_EXPR_SPAN), 0, stream, d_recs, d_each, sh, voice_mask, d_slots, d_tags,
-                     owner, n, d_count, n_voices, p, mask_list, d_result, cnt, done, seq);
+  if (d_filt) {
+    sk_each_filt_t<true> fa;
+    fa.filt = d_filt;
+    fa.filter_mask = filter_mask;
+    hipLaunchKernelGGL(sk_ctl_owned_each_kernel<true>, dim3(n_wg), dim3(SK_EXPR_SPAN), 0, stream, d_recs, d_each, sh, voice_mask, d_slots,
+                       d_tags, owner, n, d_count, n_voices, p, mask_list, d_result, cnt, done, seq, fa);
+  } else {
+    hipLaunchKernelGGL(sk_ctl_owned_each_kernel<false>, dim3(n_wg), dim3(SK_EXPR_SPAN), 0, stream, d_recs, d_each, sh, voice_mask, d_slots,
+                       d_tags, owner, n, d_count, n_voices, p, mask_list, d_result, cnt, done, seq, sk_each_filt_t<false>());
+  }
   return (int)hipGetLastError();
 }

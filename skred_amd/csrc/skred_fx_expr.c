@@ -1,7 +1,8 @@
 /*
  * skred_fx_expr.c -- channels and per-note expression on the fixed-point bank: masked owner matches and per-entry controller values
  * (include/skred_amd_fxpt.h: skred_fx_ctl_each_check, skred_fxbank_find_match / _find_match_host / _stamp_match / _ctl_match /
- * _ctl_owned_each / _ctl_tags_each).
+ * _ctl_owned_each / _ctl_tags_each), and per-note timbre: the same two calls with per-entry filter coefficients
+ * (skred_fx_filter_each_check, skred_fxbank_ctl_owned_each_filter / _ctl_tags_each_filter).
  *
  * The host side of skred_fx_expr_kernels.hip, built like skred_fx_ctl.c and skred_fx_owner.c: the checks (made before anything
  * touches the device; the match's own through the float bank's skred_owner_match_check, the record's through skred_fx_ctl_check, the
@@ -11,7 +12,7 @@
  * _find_match_host, which waits for its stream, and the allocation of the owner array by the first call that needs it.  The bank
  * keeps no shadow of the voices and its render path has no planner to tell: a call ends with its launch.
  *
- * Out of scope: slots (K > 1), the deferred queue and pattern steps, the drop-in mode, per-entry filter coefficients.
+ * Out of scope: slots (K > 1), the deferred queue and pattern steps, the drop-in mode.
  */
 #include <stddef.h>
 #include <string.h>
@@ -29,6 +30,11 @@ _Static_assert(sizeof(skred_fx_ctl_each_t) == sizeof(skx_each_t) && sizeof(skred
 _Static_assert(SKX_EACH_INC_SCALE == SKRED_EACH_INC_SCALE && SKX_EACH_AMP_SCALE == SKRED_EACH_AMP_SCALE && SKX_EACH_VELOCITY == SKRED_EACH_VELOCITY &&
                SKX_EACH_PAN == SKRED_EACH_PAN, "device per-entry bits must equal the public SKRED_EACH_* values");
 _Static_assert(sizeof(skx_ctl_t) % 16 == 0, "the entries behind the record stay 16-byte aligned");
+_Static_assert(sizeof(skred_fx_filter_each_t) == sizeof(skx_filt_each_t) && sizeof(skred_fx_filter_each_t) == 32 &&
+               offsetof(skred_fx_filter_each_t, b0_q30) == 4 * SKX_FILT_W_B0 && offsetof(skred_fx_filter_each_t, b1_q30) == 4 * SKX_FILT_W_B1 &&
+               offsetof(skred_fx_filter_each_t, b2_q30) == 4 * SKX_FILT_W_B2 && offsetof(skred_fx_filter_each_t, a1_q30) == 4 * SKX_FILT_W_A1 &&
+               offsetof(skred_fx_filter_each_t, a2_q30) == 4 * SKX_FILT_W_A2 && offsetof(skred_fx_filter_each_t, reserved) == 20,
+               "the device's per-entry filter record must be skred_fx_filter_each_t word for word");
 /* the float bank's count and scatter run on this bank's query scratch */
 _Static_assert((int)SKX_IDLE_W_TICKET == (int)SK_IDLE_W_TICKET && (int)SKX_IDLE_W_PART == (int)SK_IDLE_W_PART &&
                (int)SKX_IDLE_W_RANK == (int)SK_IDLE_W_RANK && (int)SKX_IDLE_W_TOTAL == (int)SK_IDLE_W_TOTAL &&
@@ -74,6 +80,28 @@ void skx_each_pack(const skred_fx_ctl_each_t *each, int n, const uint32_t *perm,
     if (e->set & SKRED_EACH_VELOCITY) w[SKX_EACH_W_VELOCITY] = (uint32_t)e->velocity_q15;
     if (e->set & SKRED_EACH_PAN) { w[SKX_EACH_W_PAN_LEFT] = (uint32_t)e->pan_left_q15; w[SKX_EACH_W_PAN_RIGHT] = (uint32_t)e->pan_right_q15; }
   }
+}
+
+/* the record first (what each_check looks at before its entries), then the coefficients: any int32 is a coefficient */
+static int filter_check(const skred_fx_filter_each_t *filt, int n, const skred_fx_ctl_t *ctl, const char *who) {
+  if (!filt) return fail(SKRED_E_BAD_ARG, "%s: no coefficients", who);
+  if (n < 0) return fail(SKRED_E_BAD_ARG, "%s: n = %d", who, n);
+  int rc;
+  if (ctl && (rc = skred_fx_ctl_check(ctl))) return rc;
+  if (ctl && (ctl->which & SKRED_CTL_FILTER)) return fail(SKRED_E_BAD_ARG, "%s: the record names SKRED_CTL_FILTER too: two sets of coefficients", who);
+  for (int k = 0; k < n; k++)
+    if (filt[k].reserved[0] || filt[k].reserved[1] || filt[k].reserved[2])
+      return fail(SKRED_E_BAD_ARG, "%s: coefficients %d: the reserved words must be 0", who, k);
+  return SKRED_OK;
+}
+
+int skred_fx_filter_each_check(const skred_fx_filter_each_t *filt, int n, const skred_fx_ctl_t *ctl) {
+  return filter_check(filt, n, ctl, "fx filter_each_check");
+}
+
+void skx_filt_pack(const skred_fx_filter_each_t *filt, int n, const uint32_t *perm, skx_filt_each_t *out) {
+  memset(out, 0, (size_t)n * sizeof(skx_filt_each_t));
+  for (int j = 0; j < n; j++) memcpy(out[j].w, &filt[perm ? perm[j] : (uint32_t)j], 5 * sizeof(uint32_t));
 }
 
 /* ---- A. masked matches ---- */
@@ -180,61 +208,93 @@ int skred_fxbank_ctl_match(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, int fi
 
 /* ---- B. per-entry controller values ---- */
 
-static int owned_each_check(const skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const uint32_t *tags, int n,
-                            uint32_t tag_flags, const char *who) {
+/* with_filter: a call of section C, where `each` may be NULL and the coefficients are checked behind the entries */
+static int owned_each_check(const skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const skred_fx_filter_each_t *filt,
+                            int with_filter, const uint32_t *tags, int n, uint32_t tag_flags, const char *who) {
   if (!fx) return fail(SKRED_E_BAD_ARG, "%s: no bank", who);
   int rc = skred_owner_tags_check(tags, n, tag_flags);
   if (rc) return rc;
   if ((rc = sk_check_list_n(n, who))) return rc;
-  return each_check(each, n, ctl, who);
+  if (!with_filter) return each_check(each, n, ctl, who);
+  if (each && (rc = each_check(each, n, ctl, who))) return rc;
+  return filter_check(filt, n, ctl, who);
 }
 
-/* the record (zeros without `ctl`), the n entries (each[perm[j]]; perm NULL: as they stand) and the n tags in one staging slot: one
- * kernel reads all three, from the slot's device twin */
-static int owned_each_launch(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const uint32_t *perm,
-                             const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count, uint32_t *d_result, const char *who,
-                             hipStream_t s) {
-  const size_t each_bytes = (size_t)n * sizeof(skx_each_t), bytes = sizeof(skx_ctl_t) + each_bytes + (size_t)n * sizeof(uint32_t);
+/* the record (zeros without `ctl`), the n entries (each[perm[j]]; perm NULL: as they stand), with `filt` the n sets of coefficients
+ * (permuted likewise; then `each` may be NULL and no entries travel) and the n tags in one staging slot: one kernel reads them all,
+ * from the slot's device twin */
+static int owned_each_launch(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const skred_fx_filter_each_t *filt,
+                             const uint32_t *perm, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count,
+                             uint32_t *d_result, const char *who, hipStream_t s) {
+  const size_t each_bytes = each ? (size_t)n * sizeof(skx_each_t) : 0, filt_bytes = filt ? (size_t)n * sizeof(skx_filt_each_t) : 0;
+  const size_t tags_at = sizeof(skx_ctl_t) + each_bytes + filt_bytes, bytes = tags_at + (size_t)n * sizeof(uint32_t);
   skx_batch_t bt;
   const int rc = skx_batch_begin(fx, bytes, &bt);
   if (rc) return rc;
   char *h = (char *)bt.h;
   if (ctl) skx_ctl_pack(ctl, (skx_ctl_t *)h);
   else memset(h, 0, sizeof(skx_ctl_t));
-  skx_each_pack(each, n, perm, (skx_each_t *)(h + sizeof(skx_ctl_t)));
-  memcpy(h + sizeof(skx_ctl_t) + each_bytes, tags, (size_t)n * sizeof(uint32_t));
+  if (each) skx_each_pack(each, n, perm, (skx_each_t *)(h + sizeof(skx_ctl_t)));
+  if (filt) skx_filt_pack(filt, n, perm, (skx_filt_each_t *)(h + sizeof(skx_ctl_t) + each_bytes));
+  memcpy(h + tags_at, tags, (size_t)n * sizeof(uint32_t));
   const char *src = (const char *)skx_batch_send(&bt, bytes, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)skx_launch_ctl_owned_each((const skx_ctl_t *)src, (const skx_each_t *)(src + sizeof(skx_ctl_t)), d_voices,
-                                                             (const uint32_t *)(src + sizeof(skx_ctl_t) + each_bytes), fx->d_owner, n, d_count,
-                                                             fx->n_voices, fx->d_ro, d_result, s);
+  const hipError_t e = (hipError_t)skx_launch_ctl_owned_each_filter((const skx_ctl_t *)src, each ? (const skx_each_t *)(src + sizeof(skx_ctl_t)) : NULL,
+                                                                    filt ? (const skx_filt_each_t *)(src + sizeof(skx_ctl_t) + each_bytes) : NULL,
+                                                                    d_voices, (const uint32_t *)(src + tags_at), fx->d_owner, n, d_count,
+                                                                    fx->n_voices, fx->d_ro, d_result, s);
   return skx_batch_end(&bt, e, who, s);
 }
 
-int skred_fxbank_ctl_owned_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const int32_t *d_voices,
-                                const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream) {
-  if (!d_voices) return fail(SKRED_E_BAD_ARG, "fx ctl_owned_each: no list");
-  int rc = owned_each_check(fx, ctl, each, tags, n, 0, "fx ctl_owned_each");
+static int owned_each_call(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const skred_fx_filter_each_t *filt,
+                           int with_filter, const int32_t *d_voices, const uint32_t *tags, int n, const uint32_t *d_count_or_null,
+                           uint32_t *d_result, const char *who, void *stream) {
+  if (!d_voices) return fail(SKRED_E_BAD_ARG, "%s: no list", who);
+  int rc = owned_each_check(fx, ctl, each, filt, with_filter, tags, n, 0, who);
   if (rc) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(fx->device));
   if ((rc = skx_owner_ensure(fx))) return rc;
-  return owned_each_launch(fx, ctl, each, NULL, d_voices, tags, n, d_count_or_null, d_result, "fx ctl_owned_each", (hipStream_t)stream);
+  return owned_each_launch(fx, ctl, each, filt, NULL, d_voices, tags, n, d_count_or_null, d_result, who, (hipStream_t)stream);
 }
 
-int skred_fxbank_ctl_tags_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, int first, int count,
-                               const uint32_t *tags, int n, uint32_t *d_result, void *stream) {
-  int rc = owned_each_check(fx, ctl, each, tags, n, SKRED_OWNER_UNIQUE, "fx ctl_tags_each");
+static int tags_each_call(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const skred_fx_filter_each_t *filt,
+                          int with_filter, int first, int count, const uint32_t *tags, int n, uint32_t *d_result, const char *who, void *stream) {
+  int rc = owned_each_check(fx, ctl, each, filt, with_filter, tags, n, SKRED_OWNER_UNIQUE, who);
   if (rc) return rc;
-  if ((rc = sk_check_slot_range(fx->n_voices, first, count, 1, 0, "fx ctl_tags_each"))) return rc;
+  if ((rc = sk_check_slot_range(fx->n_voices, first, count, 1, 0, who))) return rc;
   if (n == 0) return SKRED_OK;
-  /* the tags travel sorted (the find pass searches them), and each[k] stays with tags[k]: entry j of the list is the voice of the
-   * j-th smallest tag, and receives each[perm[j]] */
+  /* the tags travel sorted (the find pass searches them), and each[k] and filt[k] stay with tags[k]: entry j of the list is the voice
+   * of the j-th smallest tag, and receives each[perm[j]] and filt[perm[j]] */
   uint32_t sorted[SKRED_OWNER_MAX_TAGS], perm[SKRED_OWNER_MAX_TAGS];
   (void)sk_owner_pack(tags, n, sorted, perm);
   HIP_TRY(hipSetDevice(fx->device));
   if ((rc = skx_owner_ensure(fx))) return rc;
   if ((rc = skred_fxbank_find_owned(fx, first, count, sorted, n, fx->d_owner_found, stream))) return rc;
   /* entry j is the lowest voice that carries sorted[j], or -1: the guard holds on every entry that is a voice */
-  return owned_each_launch(fx, ctl, each, perm, fx->d_owner_found, sorted, n, NULL, d_result, "fx ctl_tags_each", (hipStream_t)stream);
+  return owned_each_launch(fx, ctl, each, filt, perm, fx->d_owner_found, sorted, n, NULL, d_result, who, (hipStream_t)stream);
+}
+
+int skred_fxbank_ctl_owned_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, const int32_t *d_voices,
+                                const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream) {
+  return owned_each_call(fx, ctl, each, NULL, 0, d_voices, tags, n, d_count_or_null, d_result, "fx ctl_owned_each", stream);
+}
+
+int skred_fxbank_ctl_tags_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each, int first, int count,
+                               const uint32_t *tags, int n, uint32_t *d_result, void *stream) {
+  return tags_each_call(fx, ctl, each, NULL, 0, first, count, tags, n, d_result, "fx ctl_tags_each", stream);
+}
+
+/* ---- C. per-entry filter coefficients ---- */
+
+int skred_fxbank_ctl_owned_each_filter(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each,
+                                       const skred_fx_filter_each_t *filt, const int32_t *d_voices, const uint32_t *tags, int n,
+                                       const uint32_t *d_count_or_null, uint32_t *d_result, void *stream) {
+  return owned_each_call(fx, ctl, each, filt, 1, d_voices, tags, n, d_count_or_null, d_result, "fx ctl_owned_each_filter", stream);
+}
+
+int skred_fxbank_ctl_tags_each_filter(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, const skred_fx_ctl_each_t *each,
+                                      const skred_fx_filter_each_t *filt, int first, int count, const uint32_t *tags, int n, uint32_t *d_result,
+                                      void *stream) {
+  return tags_each_call(fx, ctl, each, filt, 1, first, count, tags, n, d_result, "fx ctl_tags_each_filter", stream);
 }

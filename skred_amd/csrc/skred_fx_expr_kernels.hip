@@ -1,7 +1,7 @@
 // skred_fx_expr_kernels.hip -- channels and per-note expression on the fixed-point bank: masked owner matches over a range, and a
 // guarded controller whose entries bring values of their own (gfx950 / CDNA4, wave64).
 //
-// skred_fxbank_stamp_match / _ctl_match / _ctl_owned_each / _ctl_tags_each (include/skred_amd_fxpt.h).  owner[n_voices] is the
+// skred_fxbank_stamp_match / _ctl_match / _ctl_owned_each / _ctl_tags_each and the two _each_filter calls (include/skred_amd_fxpt.h).  owner[n_voices] is the
 // note-owner array of skred_fx_owner.c: one tag per voice, 0 for nobody.  A voice MATCHES (value, mask) when
 // owner != 0 && (owner & mask) == value.  These kernels read the array and never write it.  The ordered list of the matching voices
 // (skred_fxbank_find_match) needs no kernel of this bank's: it reads the owner array and the scan scratch alone, so the bank enters
@@ -17,6 +17,10 @@
 //                                 field to `which` and supply its value; AMP_SCALE replaces the record's amp by
 //                                 ((uint64)amp_q15 * amp_scale_q16) >> 16, and a product of 0 or above 65535 takes SKX_C_AMP out of
 //                                 `which` for that voice and counts as withheld -- the amp guard cannot count the voice again.
+//                                 template <bool FILT>: the second instantiation (skred_fxbank_ctl_owned_each_filter /
+//                                 _ctl_tags_each_filter) also takes filt[n] and lays entry k's five Q2.30 coefficients over the
+//                                 record with SKX_C_FILTER: one 16-byte and one 4-byte load more per lane, skx_ctl_store's stores as
+//                                 they are.  FILT = false is the kernel as it was (profiles/timbre_usage.txt).
 //
 // The stores are skx_stamp_store's and skx_ctl_store's (skred_fx_ctl_common.hpp): nothing here can drift from the unguarded calls.
 // Misses are the ordinary case under a match guard (fifteen voices of sixteen on a 16-channel range), so every count goes through
@@ -66,10 +70,18 @@ __global__ __launch_bounds__(SKX_EXPR_SPAN) void sk_fx_ctl_match_kernel(const sk
   skx_count<3>(sums, d_result, val);
 }
 
+// what the FILT instantiation takes beside the rest: entry k's coefficients (FILT false: an empty struct the kernel never reads)
+template <bool FILT> struct skx_each_filt_t {};
+template <> struct skx_each_filt_t<true> {
+  const skx_filt_each_t *filt;
+};
+
+template <bool FILT>
 __global__ __launch_bounds__(SKX_EXPR_SPAN) void sk_fx_ctl_owned_each_kernel(const skx_ctl_t *__restrict__ rec, const skx_each_t *__restrict__ each,
                                                                              const int32_t *d_voices, const uint32_t *__restrict__ tags,
                                                                              const uint32_t *__restrict__ owner, int n, const uint32_t *d_count,
-                                                                             int n_voices, skx_ctl_planes_t p, uint32_t *d_result) {
+                                                                             int n_voices, skx_ctl_planes_t p, uint32_t *d_result,
+                                                                             skx_each_filt_t<FILT> fa) {
   __shared__ uint32_t sums[3];
   const int64_t i = (int64_t)blockIdx.x * SKX_EXPR_SPAN + threadIdx.x;
   bool valid = false, mine = false;
@@ -82,8 +94,12 @@ __global__ __launch_bounds__(SKX_EXPR_SPAN) void sk_fx_ctl_owned_each_kernel(con
       uint32_t r[SKX_CTL_WORDS];                                        // the record with entry i laid over it (registers: constant indices)
 #pragma unroll
       for (int k = 0; k < SKX_CTL_WORDS; ++k) r[k] = rec->w[k];
-      const uint4 ea = *reinterpret_cast<const uint4 *>(&each[i].w[0]);  // set, inc_scale_q16, amp_scale_q16, velocity_q15
-      const uint2 eb = *reinterpret_cast<const uint2 *>(&each[i].w[SKX_EACH_W_PAN_LEFT]);
+      uint4 ea = make_uint4(0u, 0u, 0u, 0u);                            // set, inc_scale_q16, amp_scale_q16, velocity_q15
+      uint2 eb = make_uint2(0u, 0u);
+      if (!FILT || each) {                                              // (FILT: no entries is "the coefficients only")
+        ea = *reinterpret_cast<const uint4 *>(&each[i].w[0]);
+        eb = *reinterpret_cast<const uint2 *>(&each[i].w[SKX_EACH_W_PAN_LEFT]);
+      }
       const uint32_t es = ea.x;
       if (es & SKX_EACH_INC_SCALE) { r[SKX_CTL_WHICH] |= SKX_C_INC_SCALE; r[SKX_CTL_INC_SCALE] = ea.y; }   // (the record names no increment: checked on the host)
       if (es & SKX_EACH_AMP_SCALE) {                                    // (the record names SKX_C_AMP: checked on the host)
@@ -93,6 +109,12 @@ __global__ __launch_bounds__(SKX_EXPR_SPAN) void sk_fx_ctl_owned_each_kernel(con
       }
       if (es & SKX_EACH_VELOCITY) { r[SKX_CTL_WHICH] |= SKX_C_VELOCITY; r[SKX_CTL_VELOCITY] = ea.w; }
       if (es & SKX_EACH_PAN) { r[SKX_CTL_WHICH] |= SKX_C_PAN; r[SKX_CTL_PAN_LEFT] = eb.x; r[SKX_CTL_PAN_RIGHT] = eb.y; }
+      if constexpr (FILT) {                                             // (the record names no SKX_C_FILTER: checked on the host)
+        const uint4 fc = *reinterpret_cast<const uint4 *>(&fa.filt[i].w[SKX_FILT_W_B0]);   // b0, b1, b2, a1 (Q2.30)
+        r[SKX_CTL_WHICH] |= SKX_C_FILTER;
+        r[SKX_CTL_B0] = fc.x; r[SKX_CTL_B1] = fc.y; r[SKX_CTL_B2] = fc.z; r[SKX_CTL_A1] = fc.w;
+        r[SKX_CTL_A2] = fa.filt[i].w[SKX_FILT_W_A2];
+      }
       withheld += skx_ctl_store(p, v, r);                               // (at most 2: one for the increment, one for the amp)
     }
   }
@@ -130,9 +152,12 @@ extern "C" int skx_launch_ctl_match(const skx_ctl_t *d_rec, int first, int count
 
 // d_rec: the base record (which == 0 when the caller gave none); d_each: 16-byte aligned; d_result[3] (or NULL): voices written,
 // stores withheld (the two guards and the amp products), voices whose owner differs
-extern "C" int skx_launch_ctl_owned_each(const skx_ctl_t *d_rec, const skx_each_t *d_each, const int32_t *d_voices, const uint32_t *d_tags,
-                                         const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
-                                         skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream) {
+// d_filt == NULL: the FILT = false instantiation, the per-entry controller without coefficients.  Else FILT = true: entry k's five
+// coefficients d_filt[k] (16-byte aligned) laid over the record with SKX_C_FILTER; d_each may then be NULL (the coefficients alone)
+extern "C" int skx_launch_ctl_owned_each_filter(const skx_ctl_t *d_rec, const skx_each_t *d_each, const skx_filt_each_t *d_filt,
+                                                const int32_t *d_voices, const uint32_t *d_tags, const uint32_t *owner, int n,
+                                                const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result,
+                                                hipStream_t stream) {
   if (n <= 0) return 0;
   if (d_result) {
     const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
@@ -140,7 +165,14 @@ extern "C" int skx_launch_ctl_owned_each(const skx_ctl_t *d_rec, const skx_each_
   }
   skx_ctl_planes_t p;
   skx_ctl_planes(p, ro);
-  hipLaunchKernelGGL(sk_fx_ctl_owned_each_kernel, dim3(skx_expr_grid(n)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, d_each, d_voices, d_tags, owner,
-                     n, d_count, n_voices, p, d_result);
+  if (d_filt) {
+    skx_each_filt_t<true> fa;
+    fa.filt = d_filt;
+    hipLaunchKernelGGL(sk_fx_ctl_owned_each_kernel<true>, dim3(skx_expr_grid(n)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, d_each, d_voices,
+                       d_tags, owner, n, d_count, n_voices, p, d_result, fa);
+  } else {
+    hipLaunchKernelGGL(sk_fx_ctl_owned_each_kernel<false>, dim3(skx_expr_grid(n)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, d_each, d_voices,
+                       d_tags, owner, n, d_count, n_voices, p, d_result, skx_each_filt_t<false>());
+  }
   return (int)hipGetLastError();
 }

@@ -121,5 +121,9 @@ typedef struct { uint32_t w[SKX_CTL_WORDS]; } skx_ctl_t;     /* 80 bytes */
 enum { SKX_EACH_SET = 0, SKX_EACH_W_INC_SCALE, SKX_EACH_W_AMP_SCALE, SKX_EACH_W_VELOCITY, SKX_EACH_W_PAN_LEFT, SKX_EACH_W_PAN_RIGHT,
        SKX_EACH_WORDS = 8 };
 typedef struct { uint32_t w[SKX_EACH_WORDS]; } skx_each_t;   /* 32 bytes */
+/* a per-entry filter record is skred_fx_filter_each_t word for word (checked at compile time in skred_fx_expr.c): 32 bytes, so that
+ * b0 b1 b2 a1 are one aligned 16-byte load */
+enum { SKX_FILT_W_B0 = 0, SKX_FILT_W_B1, SKX_FILT_W_B2, SKX_FILT_W_A1, SKX_FILT_W_A2, SKX_FILT_WORDS = 8 };
+typedef struct { uint32_t w[SKX_FILT_WORDS]; } skx_filt_each_t;   /* 32 bytes */
 #define SKX_EXPR_SPAN 256          /* voices or entries (and threads) per workgroup of the expression kernels */
 #endif

@@ -123,6 +123,8 @@ void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
 /* skred_fx_expr.c: the checked entries as they travel -- out[j] = each[perm[j]] (perm NULL: j), the named values word for word, the
  * others zeroed.  Pure host */
 void skx_each_pack(const skred_fx_ctl_each_t *each, int n, const uint32_t *perm, skx_each_t *out);
+/* ... and n checked sets of per-entry filter coefficients the same way: out[j] = filt[perm[j]], five words, the rest zero.  Pure host */
+void skx_filt_pack(const skred_fx_filter_each_t *filt, int n, const uint32_t *perm, skx_filt_each_t *out);
 /* skred_bank_owner.c: the find pass's view of n <= SKRED_OWNER_MAX_TAGS tags (sorted ascending as unsigned numbers, and where each stood) */
 int sk_owner_pack(const uint32_t *tags, int n, uint32_t *sorted, uint32_t *perm);
 /* skred_bank_checks.c, the float bank's argument checks this bank shares (`who`: the entry point, with its "fx " in front): the stamp
@@ -162,8 +164,9 @@ int skx_launch_match_stamps(const uint32_t *owner, uint32_t value, uint32_t mask
                             skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, uint32_t *d_result, hipStream_t stream);
 int skx_launch_ctl_match(const skx_ctl_t *d_rec, int first, int count, const uint32_t *owner, uint32_t value, uint32_t mask,
                          skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
-int skx_launch_ctl_owned_each(const skx_ctl_t *d_rec, const skx_each_t *d_each, const int32_t *d_voices, const uint32_t *d_tags,
-                              const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT],
-                              uint32_t *d_result, hipStream_t stream);
+/* the per-entry controller: d_filt == NULL the FILT = false instantiation (d_each required), else FILT = true (d_each may be NULL) */
+int skx_launch_ctl_owned_each_filter(const skx_ctl_t *d_rec, const skx_each_t *d_each, const skx_filt_each_t *d_filt, const int32_t *d_voices,
+                                     const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
+                                     skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
 
 #endif

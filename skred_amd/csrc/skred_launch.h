@@ -18,7 +18,7 @@
  *   skred_slot_steal_kernels.hip  sk_launch_slot_steal (plain and matched)
  *   skred_ctl_kernels.hip     sk_launch_ctl_range, sk_launch_ctl_slots, sk_launch_ctl_owned
  *   skred_owner_kernels.hip   sk_launch_owner_tag, sk_launch_owner_find, sk_launch_owner_stamps
- *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each
+ *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each_filter
  *   skred_pedal_kernels.hip   sk_launch_pedal_clear, sk_launch_pedal_stamps, sk_launch_pedal_latch, sk_launch_pedal_up
  *   skred_fx_pedal_kernels.hip  skx_launch_pedal_stamps, skx_launch_pedal_latch, skx_launch_pedal_up (sk_launch_pedal_clear by
  *                             skred_fx_owner.c too)
@@ -348,12 +348,22 @@ enum { SK_EACH_SET = 0, SK_EACH_W_INC_SCALE, SK_EACH_W_AMP_SCALE, SK_EACH_W_VELO
 typedef struct {
   uint32_t w[SK_EACH_WORDS];
 } sk_each_t;
+/* A per-entry filter record is skred_filter_each_t word for word (checked at compile time in skred_bank_expr.c): 32 bytes, so that
+ * b0 b1 b2 a1 are one aligned 16-byte load. */
+enum { SK_FILT_W_B0 = 0, SK_FILT_W_B1, SK_FILT_W_B2, SK_FILT_W_A1, SK_FILT_W_A2, SK_FILT_WORDS = 8 };
+typedef struct {
+  uint32_t w[SK_FILT_WORDS];
+} sk_filt_each_t;
 /* sk_launch_ctl_owned with entry k's record d_each[k] laid over the K records (d_recs: records without a mask bit, and all of them
- * when the caller gave none, hold set == 0); d_result[3] as there, the withheld products counted in [1] */
-int sk_launch_ctl_owned_each(const sk_ctl_t *d_recs, const sk_each_t *d_each, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
-                             const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
-                             sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t *mask_list, uint32_t *d_result,
-                             uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+ * when the caller gave none, hold set == 0); d_result[3] as there, the withheld products counted in [1].  d_filt != NULL: also entry
+ * k's coefficients d_filt[k] (16-byte aligned) laid over record l, with SK_CTL_FILTER, on the voices l of filter_mask (a subset of
+ * voice_mask; no masked record of it names SK_CTL_FILTER); d_each may then be NULL: the coefficients alone.  d_filt == NULL:
+ * filter_mask is not looked at and d_each is required */
+int sk_launch_ctl_owned_each_filter(const sk_ctl_t *d_recs, const sk_each_t *d_each, const sk_filt_each_t *d_filt, int slot_voices,
+                                    uint64_t voice_mask, uint64_t filter_mask, const int32_t *d_slots, const uint32_t *d_tags,
+                                    const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, sk_plane_t *const ro[SKP_COUNT],
+                                    sk_plane_t *const rw[SKS_COUNT], uint64_t *mask_list, uint32_t *d_result, uint32_t *cnt,
+                                    uint32_t *done, uint32_t seq, hipStream_t stream);
 
 /* ---- pedals (skred_bank_pedal.c -> skred_pedal_kernels.hip; include/skred_amd.h: skred_bank_stamp_owned_pedal /
  * _release_tags_pedal / _pedal_latch / _pedal_up) ----

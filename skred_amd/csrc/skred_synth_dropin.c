@@ -150,34 +150,18 @@ void osc_trigger(int voice) {
   voice_finished[voice] = 0;
 }
 
-/* ---- biquad coefficients: RBJ cookbook, cached on (freq, resonance, mode) (synth.c:929-1008) ---- */
-
-typedef struct { float b0, b1, b2; } rbj_numerator_t;
-
-static rbj_numerator_t rbj_numerator(int mode, float cs, float alpha) {
-  switch (mode) {
-    case 2:  return (rbj_numerator_t){ (1.0f + cs) / 2.0f, -(1.0f + cs), (1.0f + cs) / 2.0f };   /* high-pass */
-    case 3:  return (rbj_numerator_t){ alpha, 0.0f, -alpha };                                    /* band-pass */
-    case 4:  return (rbj_numerator_t){ 1.0f, -2.0f * cs, 1.0f };                                 /* notch */
-    case 5:  return (rbj_numerator_t){ 1.0f - alpha, -2.0f * cs, 1.0f + alpha };                 /* all-pass */
-    default: return (rbj_numerator_t){ (1.0f - cs) / 2.0f, 1.0f - cs, (1.0f - cs) / 2.0f };      /* low-pass; also any unknown mode */
-  }
-}
+/* ---- biquad coefficients: RBJ cookbook, cached on (freq, resonance, mode) (synth.c:929-1008) ----
+ * The arithmetic itself is skred_filter_coeffs' (include/skred_amd.h, skred_bank_expr.c), at this library's rate: one statement of it,
+ * shared with the hosts that compute per-note coefficients for skred_bank_ctl_tags_each_filter. */
 
 void mmf_set_params(int n, float f, float resonance) {
   skred_mmf_t *q = &voice_filter[n];
   const int mode = voice_filter_mode[n];
   if (q->last_freq == f && q->last_resonance == resonance && q->last_mode == mode) return;
   q->last_freq = f; q->last_resonance = resonance; q->last_mode = mode;
-  if (mode == 0) return;                                      /* bypassed: keys remembered, nothing computed */
-  const float w = 2.0f * (float)M_PI * f / (float)RATE;
-  const float sn = sinf(w), cs = cosf(w);
-  const float alpha = sn / (2.0f * resonance);
-  const float a0 = 1.0f + alpha;
-  const rbj_numerator_t num = rbj_numerator(mode, cs, alpha);
-  q->b0 = num.b0 / a0; q->b1 = num.b1 / a0; q->b2 = num.b2 / a0;
-  q->a1 = (-2.0f * cs) / a0;
-  q->a2 = (1.0f - alpha) / a0;
+  float c[5];
+  if (skred_filter_coeffs(mode, f, resonance, (float)RATE, c) != SKRED_OK) return;   /* bypassed: keys remembered, nothing computed */
+  q->b0 = c[0]; q->b1 = c[1]; q->b2 = c[2]; q->a1 = c[3]; q->a2 = c[4];
   voice_filter_freq[n] = f;
   voice_filter_res[n] = resonance;
 }

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "skred_bank_owner_clear", "skred_bank_download_owners", "skred_bank_download_env_clocks",
     "skred_bank_find_match", "skred_bank_find_match_host", "skred_bank_stamp_match", "skred_bank_ctl_match",
     "skred_bank_ctl_owned_each", "skred_bank_ctl_tags_each",
+    "skred_bank_ctl_owned_each_filter", "skred_bank_ctl_tags_each_filter",
     "skred_bank_find_steal_slots_match", "skred_bank_find_steal_slots_match_host", "skred_bank_note_on_channel",
     "skred_bank_stamp_owned_pedal", "skred_bank_release_tags_pedal", "skred_bank_pedal_latch", "skred_bank_pedal_up",
     "skred_bank_pedal_clear", "skred_bank_download_pedals",
@@ -53,6 +54,7 @@ ABI_SYMBOLS = [
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
                     "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check",
+                    "skred_filter_each_check", "skred_filter_coeffs",
                     "skred_chan_check", "skred_pedal_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
@@ -180,6 +182,24 @@ def ctl_each_array(each):
         return each
     each = list(each)
     return (CtlEachC * len(each))(*each)
+
+
+class FilterEachC(C.Structure):
+    """ctypes image of ``skred_filter_each_t`` (32 bytes): the five biquad coefficients entry k brings."""
+    _fields_ = [("b0", C.c_float), ("b1", C.c_float), ("b2", C.c_float), ("a1", C.c_float), ("a2", C.c_float), ("reserved", C.c_uint32 * 3)]
+
+
+def filter_each(b0: float = 0.0, b1: float = 0.0, b2: float = 0.0, a1: float = 0.0, a2: float = 0.0) -> FilterEachC:
+    """One set of per-entry coefficients: ``filter_each(*filter_coeffs(1, 880.0, 0.9, 44100.0))``."""
+    return FilterEachC(b0, b1, b2, a1, a2)
+
+
+def filter_each_array(filt):
+    """A contiguous ``FilterEachC`` array from a sequence of FilterEachC (a ctypes array of FilterEachC passes through)."""
+    if isinstance(filt, C.Array) and filt._type_ is FilterEachC:
+        return filt
+    filt = list(filt)
+    return (FilterEachC * len(filt))(*filt)
 
 
 # SKRED_PEDAL_* (skred_bank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up)
@@ -311,6 +331,10 @@ def load() -> C.CDLL:
     L.skred_bank_ctl_match.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), vp, vp]
     L.skred_bank_ctl_owned_each.argtypes = [vp, vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
     L.skred_bank_ctl_tags_each.argtypes = [vp, vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
+    L.skred_filter_each_check.argtypes = [vp, i32, vp, i32, C.c_uint64, C.c_uint64]
+    L.skred_filter_coeffs.argtypes = [i32, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]
+    L.skred_bank_ctl_owned_each_filter.argtypes = [vp, vp, vp, vp, i32, C.c_uint64, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_ctl_tags_each_filter.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.c_uint64, C.c_uint64, vp, i32, vp, vp]
     L.skred_chan_check.argtypes = [C.POINTER(SlotQueryC), C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), C.c_uint32, vp, i32, i32]
     L.skred_bank_find_steal_slots_match.argtypes = [vp, C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), vp, vp, vp]
     L.skred_bank_find_steal_slots_match_host.argtypes = [vp, C.POINTER(SlotStealQueryC), C.POINTER(OwnerMatchC), vp, C.POINTER(i32),
@@ -410,6 +434,27 @@ def ctl_each_check(each, ctls, voice_mask: int, slot_voices: Optional[int] = Non
     K = len(arr) if slot_voices is None else int(slot_voices)
     return int(load().skred_ctl_each_check(C.cast(e, C.c_void_p), len(e), C.cast(arr, C.c_void_p) if arr is not None else None, K,
                                            int(voice_mask)))
+
+
+def filter_each_check(filt, ctls, voice_mask: int, filter_mask: int, slot_voices: Optional[int] = None) -> int:
+    """skred_filter_each_check on the coefficients `filt` over the K records `ctls` (None: no base records, then slot_voices is
+    required): 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host."""
+    f = filter_each_array(filt) if filt is not None else None
+    arr = ctl_array(ctls) if ctls is not None else None
+    K = len(arr) if slot_voices is None else int(slot_voices)
+    return int(load().skred_filter_each_check(C.cast(f, C.c_void_p) if f is not None else None, len(f) if f is not None else 0,
+                                              C.cast(arr, C.c_void_p) if arr is not None else None, K, int(voice_mask), int(filter_mask)))
+
+
+def filter_coeffs(mode: int, freq: float, resonance: float, sample_rate: float):
+    """skred_filter_coeffs: (b0, b1, b2, a1, a2) as np.float32 for one filter setting -- the drop-in mode's mmf_set_params arithmetic
+    with the rate as an argument.  None for mode 0 (bypass: nothing is computed).  Pure host."""
+    out = (C.c_float * 5)()
+    rc = int(load().skred_filter_coeffs(int(mode), float(freq), float(resonance), float(sample_rate), out))
+    if rc == 1:
+        return None
+    _check(rc, "skred_filter_coeffs")
+    return tuple(np.float32(x) for x in out)
 
 
 class DeviceBank:
@@ -774,6 +819,35 @@ class DeviceBank:
         _check(self.L.skred_bank_ctl_tags_each(self.h, C.cast(arr, C.c_void_p) if arr is not None else None, C.cast(e, C.c_void_p),
                                                int(first), int(count), K, int(voice_mask), t.ctypes.data, len(t), d_result or None,
                                                stream or None), "skred_bank_ctl_tags_each")
+
+    # ---- per-note timbre (include/skred_amd.h: skred_bank_ctl_owned_each_filter / _ctl_tags_each_filter) ----
+    def ctl_owned_each_filter(self, ctls, each, filt, voice_mask: int, filter_mask: int, d_slots: int, tags,
+                              slot_voices: Optional[int] = None, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """ctl_owned_each with entry k's coefficients filt[k] stored on the voices of filter_mask (each None: the coefficients only;
+        ctls None: no base records, slot_voices required).  d_result (uint32[3], may be 0) as for ctl_owned_each."""
+        f, t = filter_each_array(filt), tag_array(tags)
+        e = ctl_each_array(each) if each is not None else None
+        assert len(f) == len(t) and (e is None or len(e) == len(t)), "one entry per tag"
+        arr = ctl_array(ctls) if ctls is not None else None
+        K = len(arr) if slot_voices is None else int(slot_voices)
+        _check(self.L.skred_bank_ctl_owned_each_filter(self.h, C.cast(arr, C.c_void_p) if arr is not None else None,
+                                                       C.cast(e, C.c_void_p) if e is not None else None, C.cast(f, C.c_void_p), K,
+                                                       int(voice_mask), int(filter_mask), d_slots or None, t.ctypes.data, len(t),
+                                                       d_count or None, d_result or None, stream or None),
+               "skred_bank_ctl_owned_each_filter")
+
+    def ctl_tags_each_filter(self, ctls, each, filt, first: int, count: int, voice_mask: int, filter_mask: int, tags,
+                             slot_voices: Optional[int] = None, d_result: int = 0, stream: int = 0):
+        """Timbre by note id: filt[k] (and each[k]) on the lowest slot of [first, first + count) that carries tags[k]."""
+        f, t = filter_each_array(filt), tag_array(tags)
+        e = ctl_each_array(each) if each is not None else None
+        assert len(f) == len(t) and (e is None or len(e) == len(t)), "one entry per tag"
+        arr = ctl_array(ctls) if ctls is not None else None
+        K = len(arr) if slot_voices is None else int(slot_voices)
+        _check(self.L.skred_bank_ctl_tags_each_filter(self.h, C.cast(arr, C.c_void_p) if arr is not None else None,
+                                                      C.cast(e, C.c_void_p) if e is not None else None, C.cast(f, C.c_void_p),
+                                                      int(first), int(count), K, int(voice_mask), int(filter_mask), t.ctypes.data, len(t),
+                                                      d_result or None, stream or None), "skred_bank_ctl_tags_each_filter")
 
     # ---- slot stealing (include/skred_amd.h: skred_bank_find_steal_slots / _find_steal_slots_host / _note_on_steal_slots) ----
     def find_steal_slots(self, q: SlotStealQueryC, d_slots: int = 0, d_count: int = 0, stream: int = 0):

@@ -43,12 +43,13 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_ctl_owned", "skred_fxbank_download_params",
                   "skred_fxbank_find_match", "skred_fxbank_find_match_host", "skred_fxbank_stamp_match", "skred_fxbank_ctl_match",
                   "skred_fxbank_ctl_owned_each", "skred_fxbank_ctl_tags_each",
+                  "skred_fxbank_ctl_owned_each_filter", "skred_fxbank_ctl_tags_each_filter",
                   "skred_fxbank_find_steal_match", "skred_fxbank_find_steal_match_host", "skred_fxbank_note_on_channel",
                   "skred_fxbank_stamp_owned_pedal", "skred_fxbank_release_tags_pedal", "skred_fxbank_pedal_latch",
                   "skred_fxbank_pedal_up", "skred_fxbank_pedal_clear", "skred_fxbank_download_pedals",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
 FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
-                       "skred_fx_ctl_each_check", "skred_fx_chan_check", "skred_fx_pedal_check"]                                                                     # pure host: no bank, no device
+                       "skred_fx_ctl_each_check", "skred_fx_filter_each_check", "skred_fx_chan_check", "skred_fx_pedal_check"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -151,6 +152,33 @@ def fx_ctl_each_check(entries, ctl: Optional[FxCtlC] = None, n: Optional[int] = 
     n = (len(arr) if arr is not None else 0) if n is None else n
     return int(_bind(load()).skred_fx_ctl_each_check(C.cast(arr, C.c_void_p) if arr is not None else None, int(n),
                                                       C.byref(ctl) if ctl is not None else None))
+
+
+class FxFilterEachC(C.Structure):
+    """ctypes image of ``skred_fx_filter_each_t`` (32 bytes): the five Q2.30 coefficients entry k brings."""
+    _fields_ = [("b0_q30", C.c_int32), ("b1_q30", C.c_int32), ("b2_q30", C.c_int32), ("a1_q30", C.c_int32), ("a2_q30", C.c_int32),
+                ("reserved", C.c_uint32 * 3)]
+
+
+def fx_filter_each(b0_q30: int = 0, b1_q30: int = 0, b2_q30: int = 0, a1_q30: int = 0, a2_q30: int = 0) -> FxFilterEachC:
+    """One set of per-entry coefficients (Q2.30, any int32)."""
+    return FxFilterEachC(int(b0_q30), int(b1_q30), int(b2_q30), int(a1_q30), int(a2_q30))
+
+
+def fx_filter_each_array(filt):
+    """A contiguous ``FxFilterEachC`` array from a sequence of FxFilterEachC (a ctypes array of FxFilterEachC passes through)."""
+    if isinstance(filt, C.Array) and filt._type_ is FxFilterEachC:
+        return filt
+    filt = list(filt)
+    return (FxFilterEachC * len(filt))(*filt)
+
+
+def fx_filter_each_check(filt, ctl: Optional[FxCtlC] = None, n: Optional[int] = None) -> int:
+    """skred_fx_filter_each_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device.  ``filt`` None: a NULL array."""
+    arr = fx_filter_each_array(filt) if filt is not None else None
+    n = (len(arr) if arr is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_filter_each_check(C.cast(arr, C.c_void_p) if arr is not None else None, int(n),
+                                                         C.byref(ctl) if ctl is not None else None))
 
 
 def _tags(tags) -> np.ndarray:
@@ -294,6 +322,9 @@ def _bind(L):
     L.skred_fx_ctl_each_check.argtypes = [vp, i32, vp]
     L.skred_fxbank_ctl_owned_each.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp]
     L.skred_fxbank_ctl_tags_each.argtypes = [vp, vp, vp, i32, i32, vp, i32, vp, vp]
+    L.skred_fx_filter_each_check.argtypes = [vp, i32, vp]
+    L.skred_fxbank_ctl_owned_each_filter.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_ctl_tags_each_filter.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, vp]
     L.skred_fxbank_find_steal_match.argtypes = [vp, vp, vp, vp, vp, vp]
     L.skred_fxbank_find_steal_match_host.argtypes = [vp, vp, vp, vp, C.POINTER(C.c_int), C.POINTER(C.c_int), vp]
     L.skred_fx_chan_check.argtypes = [vp, vp, vp, C.c_uint32, vp, i32, i32]
@@ -575,6 +606,28 @@ class DeviceFxBank:
         _check(self.L.skred_fxbank_ctl_tags_each(self.h, C.byref(ctl) if ctl is not None else None, C.cast(arr, C.c_void_p),
                                                  int(first), int(count), t.ctypes.data, len(t), d_result or None, stream or None),
                "skred_fxbank_ctl_tags_each")
+
+    # ---- per-note timbre (include/skred_amd_fxpt.h: skred_fxbank_ctl_owned_each_filter / _ctl_tags_each_filter) ----
+    def ctl_owned_each_filter(self, ctl: Optional[FxCtlC], entries, filt, d_voices: int, tags, d_count: int = 0, d_result: int = 0,
+                              stream: int = 0):
+        """ctl_owned_each with entry k's five coefficients filt[k] (entries None: the coefficients only); d_result as there."""
+        t, f = _tags(tags), fx_filter_each_array(filt)
+        arr = fx_each_array(entries) if entries is not None else None
+        assert len(f) == len(t) and (arr is None or len(arr) == len(t)), "one entry per tag"
+        _check(self.L.skred_fxbank_ctl_owned_each_filter(self.h, C.byref(ctl) if ctl is not None else None,
+                                                         C.cast(arr, C.c_void_p) if arr is not None else None, C.cast(f, C.c_void_p),
+                                                         d_voices or None, t.ctypes.data, len(t), d_count or None, d_result or None,
+                                                         stream or None), "skred_fxbank_ctl_owned_each_filter")
+
+    def ctl_tags_each_filter(self, ctl: Optional[FxCtlC], entries, filt, first: int, count: int, tags, d_result: int = 0, stream: int = 0):
+        """Timbre by note id: filt[k] (and entries[k]) on the lowest voice of the range that carries tags[k]."""
+        t, f = _tags(tags), fx_filter_each_array(filt)
+        arr = fx_each_array(entries) if entries is not None else None
+        assert len(f) == len(t) and (arr is None or len(arr) == len(t)), "one entry per tag"
+        _check(self.L.skred_fxbank_ctl_tags_each_filter(self.h, C.byref(ctl) if ctl is not None else None,
+                                                        C.cast(arr, C.c_void_p) if arr is not None else None, C.cast(f, C.c_void_p),
+                                                        int(first), int(count), t.ctypes.data, len(t), d_result or None, stream or None),
+               "skred_fxbank_ctl_tags_each_filter")
 
     # ---- channel polyphony (include/skred_amd_fxpt.h: skred_fxbank_find_steal_match / _find_steal_match_host / _note_on_channel) ----
     def find_steal_match(self, q: FxStealQueryC, value: int, mask: int, d_voices: int = 0, d_count: int = 0, stream: int = 0):

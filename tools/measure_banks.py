@@ -1345,6 +1345,138 @@ def fxexpr():
     db.close()
 
 
+def timbre():
+    """Per-note timbre on bank_patch("3sk", 2**20), every copy sounding and tagged over 16 channels (tag = channel << 24 | slot + 1):
+    256 notes with 256 cutoffs.  (a) one skred_bank_ctl_tags_each_filter beside the only route before it, 256 skred_bank_ctl_owned calls
+    with SKRED_CTL_FILTER on a list that is already on the device; (b) the 64-frame block after the call beside the steady block.
+    Medians of 12 with minimum and maximum; host time held, and stream time between events."""
+    D = device
+    n, K, REPS, F, CHANNELS, NOTES = 1 << 20, 4, 12, 64, 16, 256
+    MEMBERS = 0x7
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    sel = (np.arange(n) % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = np.uint64(now - 40000)
+    bank["voice_filter_mode"][sel] = 1                             # the carriers filtered: the coefficients are heard
+    for name, x in zip(("b0", "b1", "b2", "a1", "a2"), D.filter_coeffs(1, 2000.0, 0.707, 44100.0)):
+        bank["voice_filter"][name][sel] = x
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g); db.upload(bank)
+    slots = np.arange(0, n, K, dtype=np.int32)
+    idx = np.arange(len(slots), dtype=np.uint32)
+    tags = (((idx % CHANNELS) + 1) << 24 | (idx // CHANNELS + 1)).astype(np.uint32)
+    db.tag_slots(torch.from_numpy(slots).cuda().data_ptr(), tags, K)
+    res = torch.zeros(3, dtype=torch.int32, device="cuda")
+    out = torch.zeros(F, 2, device="cuda")
+    note_tags = tags[3::CHANNELS * 7][:NOTES].copy()
+    coeffs = [D.filter_coeffs(1, 220.0 * 2.0 ** (k / 48.0), 0.9, 44100.0) for k in range(NOTES)]
+    filt = D.filter_each_array([D.filter_each(*c) for c in coeffs])
+    found = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    db.find_owned(0, n, K, note_tags, found.data_ptr())
+    torch.cuda.synchronize()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def stats(x):
+        return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f})"
+
+    def series(call):
+        host, stream = [], []
+        for it in range(2 + REPS):
+            torch.cuda.synchronize()
+            h, s_ms = timed(call)
+            if it >= 2:
+                host.append(h); stream.append(s_ms)
+        return f"host time held {stats(host)}; stream time between events {stats(stream)}"
+
+    one_call = lambda: db.ctl_tags_each_filter(None, None, filt, 0, n, MEMBERS, MEMBERS, note_tags, K, res.data_ptr())   # noqa: E731
+    print(f"3sk {n} voices = {n // K} slots of {K}, every copy sounding, tagged over {CHANNELS} channels; medians of {REPS}")
+    print(f"  (a) {NOTES} notes, {NOTES} cutoffs, one ctl_tags_each_filter: {series(one_call)}; d_result = {res.cpu().numpy().tolist()}")
+
+    # the records of the old route built ahead of the timed region, as the new call's array is
+    singles = [D.ctl_array([D.ctl(D.CTL_FILTER, **dict(zip(("b0", "b1", "b2", "a1", "a2"), (float(x) for x in coeffs[k]))))] * K) for k in range(NOTES)]
+    single_tags = [note_tags[k:k + 1].copy() for k in range(NOTES)]
+
+    def one_by_one():
+        for k in range(NOTES):
+            db.ctl_owned(singles[k], MEMBERS, found.data_ptr() + 4 * k, single_tags[k])
+    print(f"  (a) the same, {NOTES} ctl_owned calls on a list that is already on the device: {series(one_by_one)}")
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+    db.upload(bank)
+    for _ in range(8):
+        block()
+    steady = [block() for _ in range(REPS)]
+    after = []
+    for _ in range(REPS):
+        one_call()
+        after.append(block())
+        block()
+    print(f"  (b) the {F}-frame block after ctl_tags_each_filter: {stats(after)}; a steady block: {stats(steady)}; kernel {db.last_kernel()}, "
+          f"list violations {db.list_violations()}")
+    db.close()
+
+
+def fxtimbre():
+    """Per-note timbre on bank_fx(2**20), every voice sounding and tagged over 16 channels: 256 notes with 256 cutoffs.  (a) one
+    skred_fxbank_ctl_tags_each_filter beside 256 skred_fxbank_ctl_owned calls with SKRED_CTL_FILTER; (b) the 64-frame block after the
+    call beside the steady block.  Medians of 12 with minimum and maximum; host time held, and stream time between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES = 1 << 20, 64, 16, 256
+    bank, pool, c0 = X.bank_fx(n)
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    db.tag_list(torch.arange(n, dtype=torch.int32, device="cuda").data_ptr(), tags)
+    dr = torch.zeros(3, dtype=torch.int32, device="cuda")
+    note_tags = tags[2::CHANNELS * 7][:NOTES].copy()
+    names = ("b0_q30", "b1_q30", "b2_q30", "a1_q30", "a2_q30")
+    q30 = [[int(max(-(1 << 31), min((1 << 31) - 1, round(float(x) * (1 << 30))))) for x in device.filter_coeffs(1, 220.0 * 2.0 ** (k / 48.0), 0.9, 48000.0)]
+           for k in range(NOTES)]
+    filt = X.fx_filter_each_array([X.fx_filter_each(*c) for c in q30])
+    found = torch.full((NOTES,), -1, dtype=torch.int32, device="cuda")
+    db.find_owned(0, n, note_tags, found.data_ptr())
+    torch.cuda.synchronize()
+
+    def line(label, call, words=3):
+        ms, held = _fx_timed(call, None)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {dr.cpu().numpy().tolist()[:words]}")
+
+    one_call = lambda: db.ctl_tags_each_filter(None, None, filt, 0, n, note_tags, dr.data_ptr())   # noqa: E731
+    print(f"fx {n} voices all sounding, tagged over {CHANNELS} channels ({n // CHANNELS} notes each)")
+    line(f"(a) {NOTES} notes, {NOTES} cutoffs, one ctl_tags_each_filter", one_call)
+
+    # the records of the old route built ahead of the timed region, as the new call's array is
+    singles = [X.fx_ctl(X.CTL_FILTER, **dict(zip(names, q30[k]))) for k in range(NOTES)]
+    single_tags = [note_tags[k:k + 1].copy() for k in range(NOTES)]
+
+    def one_by_one():
+        for k in range(NOTES):
+            db.ctl_owned(singles[k], found.data_ptr() + 4 * k, single_tags[k])
+    line(f"(a) the same, {NOTES} ctl_owned calls on a list that is already on the device", one_by_one, 0)
+    db.upload(bank)
+    _fx_block_after(db, out, F, None, 4)
+    steady = _fx_block_after(db, out, F)
+    after = _fx_block_after(db, out, F, one_call)
+    print(f"  (b) the {F}-frame block after ctl_tags_each_filter: {_fx_stats(after)}; a steady block: {_fx_stats(steady)}")
+    db.close()
+
+
 def chan():
     """Channel polyphony on bank_patch("3sk", 2**20), every copy sounding and tagged over 16 channels (tag = channel << 24 | slot + 1).
     (a) a burst of 256 patch notes on ONE channel with the cap at the channel's current count, so that all 256 steal inside the
@@ -1723,7 +1855,7 @@ def fxpedal():
 
 
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
