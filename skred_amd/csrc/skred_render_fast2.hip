@@ -264,15 +264,26 @@ __device__ __forceinline__ v2f fast2_osc(Fast2Regs &r, const char *lds_tab, cons
 // (fast2_smoother_stalled: its update no longer changes it, so it is skipped); 6: as 0 with the lane's listed voices taking
 // this frame's gain from r.gt (in-place instantiation); 7: as 3 with gain and pan folded into one constant per lane and
 // channel (fast2_fold_pan; sk_render_fast2_kernel's tame waves).  TAME: see fast_frame.
-template <bool FILTER, int EM, bool TAME, bool MIXED = false, bool MUTESEL = false, int FMP = 0>
+// B2R (folded frames of a wave that passed fast2_b2_vote): every lane's b2 is +b0 or -b0 bit for bit, so b2 * s(n-2) is
+// sigma * fl(b0 * s(n-2)) -- sigma = +-1, and the product is P = b0 * s as this function formed it two frames earlier.  The
+// caller carries pn = P(n-1) and po = P(n-2) beside xn (handed over like the delay lines: po takes this frame's P and the roles
+// swap), r.b2 holds sigma (fast2_b2_sigma), and the b2 term is fma(sigma, po, y): sigma * po is exact, so the one rounding is
+// that of the add, and y is bit for bit what y + b2 * xo gives -- one packed multiply per frame less.  xo is not read; it
+// still takes s, so x1 / x2 hold s(n-1) / s(n-2) behind every frame as ever (tails, the store).  A NaN sample with sigma = -1
+// may come out with the other sign bit than -b0 * NaN had.
+template <bool FILTER, int EM, bool TAME, bool MIXED = false, bool MUTESEL = false, int FMP = 0, bool B2R = false>
 __device__ __forceinline__ void fast2_post_lr(Fast2Regs &r, Env2Regs &e, v2f s, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
-                                              const bool rel0, const bool rel1, const bool silent0,
+                                              v2f &pn, v2f &po, const bool rel0, const bool rel1, const bool silent0,
                                               const bool silent1, v2f &out_lr) {
+  static_assert(!B2R || (FILTER && EM == 7 && !MIXED && FMP == 0), "the b2-reusing frames: folded frames of plain filtered banks");
+  (void)pn;
   // ---- biquad, packed ----
   if (FILTER) {
     v2f y = r.b0 * s;
+    const v2f p = y;
     y = y + r.b1 * xn;
-    y = y + r.b2 * xo;
+    if (B2R) { y = __builtin_elementwise_fma(r.b2, po, y); po = p; }
+    else y = y + r.b2 * xo;
     y = y - r.a1 * yn;
     y = y - r.a2 * yo;
     if (MIXED) {                                       // filter_mode 0: the sample passes, the delay line rests (synth.c:577)
@@ -389,8 +400,8 @@ template <bool FILTER, int EM, bool TAME, bool MIXED = false, bool MUTESEL = fal
 __device__ __forceinline__ void fast2_post(Fast2Regs &r, Env2Regs &e, v2f s, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
                                            const bool rel0, const bool rel1, const bool silent0,
                                            const bool silent1, float &out_l, float &out_r) {
-  v2f lr;
-  fast2_post_lr<FILTER, EM, TAME, MIXED, MUTESEL, FMP>(r, e, s, xn, xo, yn, yo, rel0, rel1, silent0, silent1, lr);
+  v2f lr, p_unused;
+  fast2_post_lr<FILTER, EM, TAME, MIXED, MUTESEL, FMP>(r, e, s, xn, xo, yn, yo, p_unused, p_unused, rel0, rel1, silent0, silent1, lr);
   out_l = lr.x;
   out_r = lr.y;
 }
@@ -418,6 +429,28 @@ __device__ __forceinline__ void fast2_fold_pan(Fast2Regs &r) {
 }
 // behind the last folded frame of a block or a tail: voice_sample = y * sgain, the product every unfolded frame forms
 #define SK_FAST2_FOLD_SAMPLE() r.sample = r.sample * r.sgain;
+
+// The b2-reusing frames (fast2_post_lr<.., B2R>).  The vote, once per pass: in every lane and for both voices the bits of b2 are
+// the bits of b0, or those with the sign flipped -- the low-pass, high-pass, notch (b2 = b0) and band-pass (b2 = -b0) forms of
+// the reference's mmf_set_params, whose b0 and b2 go through the same division by a0 (tests/test_b2_identity.py); its all-pass
+// form (b0 = 1 - alpha, b2 = 1 + alpha) fails, and so does whatever else a host wrote.  Dead and absent lanes hold zeros and pass;
+// `listed` lanes (their voices are rendered by the envelope kernel: pan gains zero, nothing stored) pass whatever they hold --
+// their filter then runs with +-b0 for b2 and the same poles, into a product with zero.
+__device__ __forceinline__ bool fast2_b2_vote(const Fast2Regs &r, const bool listed0, const bool listed1) {
+  const uint32_t d0 = __float_as_uint(r.b2.x) ^ __float_as_uint(r.b0.x), d1 = __float_as_uint(r.b2.y) ^ __float_as_uint(r.b0.y);
+  return __all((listed0 || (d0 & 0x7fffffffu) == 0) && (listed1 || (d1 & 0x7fffffffu) == 0));
+}
+// From the wave's first folded chunk on r.b2 holds sigma = +-1.0f in b2's place (the steady instantiation has no two registers
+// to carry both; nothing stores b2 back) ...
+__device__ __forceinline__ void fast2_b2_sigma(Fast2Regs &r) {
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+    r.b2[c] = __uint_as_float(0x3f800000u | ((__float_as_uint(r.b2[c]) ^ __float_as_uint(r.b0[c])) & 0x80000000u));
+}
+// ... and a ragged tail, whose frames keep the plain form, takes b2 = sigma * b0 back first: the same bits (and -0 for -(+0)).
+__device__ __forceinline__ void fast2_b2_restore(Fast2Regs &r) { r.b2 = r.b2 * r.b0; }
+// entering the reusing frames (the block loop of every chunk): the two products the plain form would have made
+#define SK_FAST2_B2R_ENTER() { pn_ = r.b0 * r.x1; po_ = r.b0 * r.x2; }
 
 template <bool TAB_LDS, bool FILTER, int EM, bool TAME, int INTERP, bool MIXED = false, int FMP = 0, bool MUTESEL = false>
 __device__ __forceinline__ void fast2_frame(Fast2Regs &r, Env2Regs &e, v2f &xn, v2f &xo, v2f &yn, v2f &yo,
@@ -549,20 +582,21 @@ __device__ __forceinline__ v2f fast2_osc_win(Fast2Regs &r, const WinRegs &w, con
   __builtin_amdgcn_wave_barrier();                          \
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #define SK_XT2 68   /* floats per tile row (see SK_XT in skred_render_fast.hip) */
-#define SK_FAST2_LDS_BLOCK_Z(J, EM_, LOZ_, MUTE_)                                                                       \
+// B2R_: the b2-reusing frames (fast2_post_lr; pn_ / po_, two v2f in scope, carry the products from frame to frame)
+#define SK_FAST2_LDS_BLOCK_Z(J, EM_, LOZ_, MUTE_, B2R_)                                                  \
   {                                                                                                      \
     float *const xt_ = reinterpret_cast<float *>(xp);   /* the wave's tile: [8 frames][SK_XT2] folded (L | R) pair sums */ \
     /* software pipeline: the table gather of the NEXT frame is issued before the biquad/gain chain of the   \
        current one (the source order matters: the compiler may not move an LDS read above the tile write) */  \
     v2f s0_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                                      \
     _Pragma("unroll") for (int q_ = 0; q_ < 8; q_ += 2) {                                                \
-      float l0, r0, l1, r1;                                                                              \
+      v2f lr0_, lr1_;                                                                                    \
       const v2f s1_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                              \
-      fast2_post<FILTER, EM_, true, MIXED, MUTE_>(r, e, s0_, r.x1, r.x2, r.y1, r.y2, released[0], released[1], silent[0], silent[1], l0, r0); \
+      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_, 0, B2R_>(r, e, s0_, r.x1, r.x2, r.y1, r.y2, pn_, po_, released[0], released[1], silent[0], silent[1], lr0_); \
       if (q_ < 6) s0_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                            \
-      fast2_post<FILTER, EM_, true, MIXED, MUTE_>(r, e, s1_, r.x2, r.x1, r.y2, r.y1, released[0], released[1], silent[0], silent[1], l1, r1); \
-      xt_[q_ * SK_XT2 + lane] = fold_lr(l0, r0);                                                         \
-      xt_[(q_ + 1) * SK_XT2 + lane] = fold_lr(l1, r1);                                                   \
+      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_, 0, B2R_>(r, e, s1_, r.x2, r.x1, r.y2, r.y1, po_, pn_, released[0], released[1], silent[0], silent[1], lr1_); \
+      xt_[q_ * SK_XT2 + lane] = fold_lr(lr0_.x, lr0_.y);                                                 \
+      xt_[(q_ + 1) * SK_XT2 + lane] = fold_lr(lr1_.x, lr1_.y);                                           \
     }                                                                                                    \
     if ((EM_) == 7) { SK_FAST2_FOLD_SAMPLE() }   /* one packed multiply per eight frames */              \
     SK_WAVE_SYNC()                                                                                       \
@@ -599,7 +633,7 @@ __device__ __forceinline__ void row_ror8_add2(float &x0, float &x1) {
                "s_nop 1"
                : "+v"(x0), "+v"(x1));
 }
-#define SK_FAST2_LDS_BLOCK_P(J, EM_, LOZ_, MUTE_)                                                        \
+#define SK_FAST2_LDS_BLOCK_P(J, EM_, LOZ_, MUTE_, B2R_)                                                  \
   {                                                                                                      \
     /* software pipeline and source order as in SK_FAST2_LDS_BLOCK_Z: the gather of the NEXT frame ahead of the current     \
        frame's chain, both tile stores of a frame pair behind it */                                      \
@@ -607,9 +641,9 @@ __device__ __forceinline__ void row_ror8_add2(float &x0, float &x1) {
     _Pragma("unroll") for (int q_ = 0; q_ < 8; q_ += 2) {                                                \
       v2f lr0_, lr1_;                                                                                    \
       const v2f s1_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                       \
-      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_>(r, e, s0_, r.x1, r.x2, r.y1, r.y2, released[0], released[1], silent[0], silent[1], lr0_); \
+      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_, 0, B2R_>(r, e, s0_, r.x1, r.x2, r.y1, r.y2, pn_, po_, released[0], released[1], silent[0], silent[1], lr0_); \
       if (q_ < 6) s0_ = fast2_osc<TAB_LDS, true, INTERP, LOZ_>(r, lds_tab, glb_tab);                     \
-      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_>(r, e, s1_, r.x2, r.x1, r.y2, r.y1, released[0], released[1], silent[0], silent[1], lr1_); \
+      fast2_post_lr<FILTER, EM_, true, MIXED, MUTE_, 0, B2R_>(r, e, s1_, r.x2, r.x1, r.y2, r.y1, po_, pn_, released[0], released[1], silent[0], silent[1], lr1_); \
       xp[SK_XP2_OFF(q_) + lane] = make_float2(lr0_.x, lr0_.y);                                           \
       xp[SK_XP2_OFF(q_ + 1) + lane] = make_float2(lr1_.x, lr1_.y);                                       \
     }                                                                                                    \
@@ -659,12 +693,16 @@ __device__ __forceinline__ void row_ror8_add2(float &x0, float &x1) {
 // `loz` (wave-uniform, set once per pass): see fast2_osc; `pairt` (a constexpr in scope: the kernel's PAIR): the packed pair
 // tile, see SK_FAST2_LDS_BLOCK_P
 #define SK_FAST2_LDS_BLOCK(J, EM_)                                                                       \
-  { if constexpr (pairt) { if (loz) SK_FAST2_LDS_BLOCK_P(J, EM_, true, false) else SK_FAST2_LDS_BLOCK_P(J, EM_, false, false) } \
-    else { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, false) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, false) } }
+  { if constexpr (pairt) { if (loz) SK_FAST2_LDS_BLOCK_P(J, EM_, true, false, false) else SK_FAST2_LDS_BLOCK_P(J, EM_, false, false, false) } \
+    else { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, false, false) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, false, false) } }
 // the same for a tame wave with muted live lanes (tame_m): their contribution is selected away, synth.c:596
 #define SK_FAST2_LDS_BLOCK_M(J, EM_)                                                                     \
-  { if constexpr (pairt) { if (loz) SK_FAST2_LDS_BLOCK_P(J, EM_, true, true) else SK_FAST2_LDS_BLOCK_P(J, EM_, false, true) } \
-    else { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, true) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, true) } }
+  { if constexpr (pairt) { if (loz) SK_FAST2_LDS_BLOCK_P(J, EM_, true, true, false) else SK_FAST2_LDS_BLOCK_P(J, EM_, false, true, false) } \
+    else { if (loz) SK_FAST2_LDS_BLOCK_Z(J, EM_, true, true, false) else SK_FAST2_LDS_BLOCK_Z(J, EM_, false, true, false) } }
+// the folded block (EM 7) of a wave that passed the b2 vote, without / with muted live lanes (MUTE_): the b2-reusing frames
+#define SK_FAST2_LDS_BLOCK_R(J, MUTE_)                                                                   \
+  { if constexpr (pairt) { if (loz) SK_FAST2_LDS_BLOCK_P(J, 7, true, MUTE_, true) else SK_FAST2_LDS_BLOCK_P(J, 7, false, MUTE_, true) } \
+    else { if (loz) SK_FAST2_LDS_BLOCK_Z(J, 7, true, MUTE_, true) else SK_FAST2_LDS_BLOCK_Z(J, 7, false, MUTE_, true) } }
 // Eight frames of a tame wave that holds listed voices (in-place instantiation): SK_FAST2_LDS_BLOCK_Z with the listed voices'
 // gains of the block's frames in gtile[8][SK_GT_RANKS] (rank: the listed voice's number within the wave), parked there by
 // the block before.  This block fetches the NEXT eight frames at its start -- lane (frame = lane & 7, rank = (lane >> 3) +
@@ -765,14 +803,23 @@ __device__ __forceinline__ void row_ror8_add2(float &x0, float &x1) {
   {                                                                             \
     int j = 0;                                                                  \
     if constexpr (fold_on && TAB_LDS && (EM_) == 0) {                           \
-      if (!folded && (tame || tame_m) && fast2_smoother_stalled(r)) { fast2_fold_pan(r); folded = true; } \
+      if (!folded && (tame || tame_m) && fast2_smoother_stalled(r)) {           \
+        fast2_fold_pan(r); folded = true;                                       \
+        if constexpr (b2r_on) { if (b2r) fast2_b2_sigma(r); }                   \
+      }                                                                         \
       if (folded) {                                                             \
-        if (tame) { for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK(j, 7)        \
-                    if (j < cn) { for (; j + 1 < cn; j += 2) SK_FAST2_PAIR_F(j, false) \
+        /* b2r (wave-uniform, per pass; b2r_on: a constexpr in scope): the wave passed fast2_b2_vote, its folded 8-frame blocks \
+           reuse the b2 product; a ragged tail takes b2 back and ends that (a ragged chunk is the launch's last anyway) */ \
+        if (tame) { if constexpr (b2r_on) { if (b2r && cn >= 8) { SK_FAST2_B2R_ENTER() for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_R(j, false) } } \
+                    for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK(j, 7)        \
+                    if (j < cn) { if constexpr (b2r_on) { if (b2r) { fast2_b2_restore(r); b2r = false; } } \
+                                  for (; j + 1 < cn; j += 2) SK_FAST2_PAIR_F(j, false) \
                                   if (j < cn) SK_FAST2_ONE_F(j, false)          \
                                   SK_FAST2_FOLD_SAMPLE() } }                    \
-        else      { for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_M(j, 7)      \
-                    if (j < cn) { for (; j + 1 < cn; j += 2) SK_FAST2_PAIR_F(j, true) \
+        else      { if constexpr (b2r_on) { if (b2r && cn >= 8) { SK_FAST2_B2R_ENTER() for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_R(j, true) } } \
+                    for (; j + 8 <= cn; j += 8) SK_FAST2_LDS_BLOCK_M(j, 7)      \
+                    if (j < cn) { if constexpr (b2r_on) { if (b2r) { fast2_b2_restore(r); b2r = false; } } \
+                                  for (; j + 1 < cn; j += 2) SK_FAST2_PAIR_F(j, true) \
                                   if (j < cn) SK_FAST2_ONE_F(j, true)           \
                                   SK_FAST2_FOLD_SAMPLE() } }                    \
       } else { SK_FAST2_CHUNK_PLAIN(EM_, true) }                                \
@@ -1018,6 +1065,8 @@ __global__ __launch_bounds__(Fast2Shape<TAB_LDS>::NW * 64, SK_FAST2_MIN_WAVES) v
   constexpr int NW = Fast2Shape<TAB_LDS>::NW;
   constexpr bool fold_on = !GT;      // the in-place instantiation keeps its frames as they are
   constexpr bool pairt = PAIR;
+  // the b2-reusing frames (fast2_b2_vote): the folded blocks of the plain filtered instantiations and their probe twins
+  constexpr bool b2r_on = fold_on && TAB_LDS && FILTER && !MIXED && FMP == 0;
   SK_FAST2_PROLOGUE()
   (void)n_flags;
   // GT: per wave, behind the tiles: gtile[8][SK_GT_RANKS] (the listed voices' gains of one 8-frame block) and
@@ -1134,6 +1183,10 @@ __global__ __launch_bounds__(Fast2Shape<TAB_LDS>::NW * 64, SK_FAST2_MIN_WAVES) v
         continue;
       }
     }
+    bool b2r = false;                 // the wave's folded blocks reuse the b2 product (SK_FAST2_CHUNK)
+    v2f pn_, po_;                     // ... and carry b0 * s of the last two frames through a chunk's blocks
+    if constexpr (b2r_on) b2r = (tame || tame_m) && fast2_b2_vote(r, (m0 >> lane) & 1, (m1 >> lane) & 1);
+    (void)b2r; (void)pn_; (void)po_;
     for (int c0 = 0; c0 < a.num_frames; c0 += SK_CHUNK) {
       const int cn = min(SK_CHUNK, a.num_frames - c0);
       if (GT && (m0 | m1) != 0) {
@@ -1168,8 +1221,10 @@ __global__ __launch_bounds__(SK_GROUP, SK_ENV2_MIN_WAVES) void sk_render_env2_ke
   constexpr int NW = 4;              // always 512 voices per pass: its register budget allows 3 waves per SIMD anyway
   constexpr bool fold_on = false;    // (SK_FAST2_CHUNK: the folded frames are sk_render_fast2_kernel's)
   constexpr bool pairt = false;      // (... and so is the packed pair tile)
-  bool folded = false;
-  (void)folded;
+  constexpr bool b2r_on = false && FILTER;   // (... and so are the b2-reusing frames; value-dependent, so that SK_FAST2_CHUNK's branch is discarded uninstantiated)
+  bool folded = false, b2r = false;
+  v2f pn_, po_;                      // (named by the block macros, never touched)
+  (void)folded; (void)b2r; (void)pn_; (void)po_;
   // the listed voices in ascending order (sk_collect_scan_kernel + sk_collect_expand_kernel, just before on this stream):
   // every workgroup pass takes 512 of them, so the launch costs what those voices cost; the grid is what the device holds at
   // once (a grid of more rendering workgroups than fit runs in rounds, the last one mostly empty) and strides over the passes
