@@ -1184,6 +1184,89 @@ int  skred_bank_pedal_clear(skred_bank_t *bank, int first, int count, void *stre
  * a pedal array. */
 int  skred_bank_download_pedals(skred_bank_t *bank, uint32_t *host_u32, int first, int count);
 
+/* ---- portamento: pitch glides that advance and land on the device ---------------------------------------------------------
+ *
+ * A glide moves a voice's voice_phase_inc towards a TARGET increment by one fp32 multiply per 64 frames and stores the target's bits
+ * when it gets there: portamento between two keys of a mono lead (MIDI CC 5 / 65 / 84), a slide into a chord.  The reference stores
+ * voice_glissando_enable / _speed / _target and never reads them, so the behaviour is defined here.  The host-driven route -- one
+ * skred_bank_ctl_tags_each(SKRED_EACH_INC_SCALE) per block -- needs a host that counts blocks per note, and never lands: repeated
+ * multiplies do not arrive at the note-on's increment bit for bit.  For device-placed notes the host does not know the increment at
+ * all; the glide's state lies where the increment lives.
+ *
+ * glide[n_voices] is an array of four words PER VOICE (one uint4: target, rate_up, rate_down as fp32 bit patterns, carry as an
+ * integer) in device memory that only the calls of this section read or write.  target == 0 (all bits) means "not gliding".  The bank
+ * allocates the array (16 bytes per voice) behind the owner array on the first skred_bank_glide_owned / _glide_tags call and
+ * zero-fills it; that call waits for the device once, as the first owner call does.  No render kernel, report, probe, tap or planner
+ * rule reads the array, and a glide stores nothing but finite increments, which is all the planner looks at (SKRED_CTL_INC_SCALE's
+ * argument): blocks rendered with and without glide calls that move nothing are bit-identical, and a glide call leaves the planner's
+ * reports alone.  A bank that never starts a glide launches nothing more and allocates nothing.
+ *
+ * ADVANCE BY F FRAMES (skred_bank_glide_advance), for every gliding voice of a range, with inc = voice_phase_inc as the device holds
+ * it:
+ *   0. inc zero, not finite, or of the other sign than the target: the voice ARRIVES at once (a glide cannot cross zero).
+ *   1. c = carry + F, m = c >> 6, carry = c & 63.
+ *   2. m times, stopping at arrival:  |inc| < |target|: inc = inc * rate_up (ONE fp32 multiply, round to nearest, never fused); the
+ *      voice arrives if the product is not finite or |inc| >= |target|.  |inc| > |target|: inc = inc * rate_down; it arrives if the
+ *      product is not finite or |inc| <= |target|.  |inc| == |target|: it arrives.
+ *   3. on arrival inc = target (the bits) and the voice's four words are cleared.
+ * So the pass stores only finite products or the target; the rates are per 64 frames, and the increments at every multiple of 64
+ * frames do not depend on how the host cuts its blocks; the loop runs at most F / 64 + 1 times.  The glide moves ONCE PER BLOCK, as
+ * every control of the reference does: steps of 11.6 ms at 512 frames, 1.5 ms at 64.  Per-frame glides are not part of this.
+ *
+ * A NEW NOTE CLEARS THE WORDS.  Once the array exists, every tag launch of the bank (skred_bank_tag_slots, the tags of
+ * skred_bank_note_on_channel) is followed on its stream by a launch that zeroes the glide words of all K voices of every slot it
+ * tagged (the pedal word's rule): a thief or a key struck again does not inherit its victim's glide.  The order for mono legato is
+ * therefore skred_bank_note_on_channel, then skred_bank_glide_tags(SKRED_GLIDE_FROM_SCALE).
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring, so the
+ * caller's memory is free on return; nothing waits for the device but the download and the first allocation; one stream at a time per
+ * bank.  A slot, K = slot_voices, voice_mask and tags mean what they mean in the sections above.
+ *
+ * Limits: glides belong with tagged notes.  A SKRED_CTL_PHASE_INC / _INC_SCALE bend of a gliding voice is undone on arrival (the
+ * target's bits are stored): bend the target with SKRED_GLIDE_TO_SCALE.  The host view of voice_phase_inc goes stale, as for
+ * SKRED_CTL_INC_SCALE; skred_bank_download_ctl reads it back.  On a shard: through skred_shard_bank(), with that rank's local indices.
+ * This section is the float bank's alone: a fixed-point twin of these calls is a follow-up.  Also out of scope: the drop-in mode (it
+ * keeps voice_glissando_* as dead data), deferred items and pattern steps. */
+enum { SKRED_GLIDE_FROM_SCALE = 1u << 0,   /* target = inc (the pitch a note-on just stored), then inc = inc * scale: slide INTO the note
+                                              from the previous key; the host needs the ratio of two keys, never an increment */
+       SKRED_GLIDE_TO_SCALE = 1u << 1 };   /* target = (gliding ? the old target : inc) * scale, inc stays: legato onto a new key without
+                                              a retrigger; a chain of them composes on the intended notes */
+typedef struct skred_glide { uint32_t set; float rate_up, rate_down, scale; uint32_t reserved[4]; } skred_glide_t;   /* 32 bytes */
+/* Pure host: SKRED_OK, or what the two starting calls refuse about the entries, in this order.  SKRED_E_BAD_ARG: a NULL array, n < 0;
+ * SKRED_E_RANGE: a bad K (not a power of two in 1 .. 64); SKRED_E_BAD_ARG: a voice_mask that is 0 or has bits at or above K; in an
+ * entry: set that is not exactly one of the two bits, a reserved word that is not 0, a value that is not finite, rate_up <= 1,
+ * rate_down >= 1 or <= 0, scale <= 0. */
+int  skred_glide_check(const skred_glide_t *glide, int n, int slot_voices, uint64_t voice_mask);
+/* Entry k (of the first min(n, *d_count_or_null)) acts on d_slots[k] only if that is a slot of the bank AND owner[slot] == tags[k]
+ * (non-zero): it starts glide[k]'s glide on every voice_mask voice of the slot -- the words above, carry = 0.  Either product is ONE
+ * unfused fp32 multiply; where the product or inc is zero or not finite the start is withheld and counted, and the voice (its
+ * increment and its glide words) is left exactly as it was.  d_result (device, uint32[3], may be NULL; cleared on the stream ahead of
+ * the kernel): [0] voices set gliding, [1] starts withheld, [2] slots whose owner differs.  A slot named twice: UNSPECIFIED.  The
+ * planner is told nothing.
+ * Refused: NULL bank, list or tags, a zero tag, n > INT32_MAX / 64, what skred_glide_check refuses.  n == 0: SKRED_OK. */
+int  skred_bank_glide_owned(skred_bank_t *bank, const skred_glide_t *glide, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
+                            const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+/* Glides by note id: skred_bank_find_owned of the tags over [first, first + count) into scratch the bank owns, then the call above
+ * on that list -- built as skred_bank_ctl_tags_each is.  glide[k] goes with tags[k]: the tags travel sorted, the entries are permuted
+ * with them on the host.  Tags unique, none zero, n <= SKRED_OWNER_MAX_TAGS; each tag reaches at most ONE slot, the lowest that
+ * carries it.  d_result as above; [2] is 0.  Refusals of both calls; SKRED_E_RANGE: first or count not a multiple of K, count <= 0,
+ * a range outside the bank. */
+int  skred_bank_glide_tags(skred_bank_t *bank, const skred_glide_t *glide, int first, int count, int slot_voices, uint64_t voice_mask,
+                           const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+/* The advance pass above over the voices [first, first + count): purely per voice, no K.  d_result (device, uint32[2], may be NULL;
+ * cleared on the stream ahead of the kernel): [0] voices still gliding after the pass, [1] voices that arrived in it.  The host calls
+ * it ahead of each render on the ranges of the channels that have portamento on; a lazily read [0] == 0 tells it to stop.  A voice
+ * that does not glide costs one 16-byte load.  On a bank without a glide array: SKRED_OK, d_result (if given) is cleared on the
+ * stream, nothing is launched.
+ * SKRED_E_BAD_ARG: NULL bank, num_frames outside 1 .. 65536; SKRED_E_RANGE: count <= 0 or a range outside the bank. */
+int  skred_bank_glide_advance(skred_bank_t *bank, int first, int count, int num_frames, uint32_t *d_result, void *stream);
+/* The glide words of [first, first + count) are cleared on `stream`; with snap != 0 a gliding voice's increment is set to its target
+ * first.  Nothing to do on a bank without a glide array.  SKRED_E_RANGE: count < 0 or a range outside the bank. */
+int  skred_bank_glide_stop(skred_bank_t *bank, int first, int count, int snap, void *stream);
+/* The glide words of [first, first + count) into host_u32x4 (4 * count words: target, rate_up, rate_down, carry per voice); waits
+ * for the device, like skred_bank_download_owners; zeros on a bank that never started a glide. */
+int  skred_bank_download_glide(skred_bank_t *bank, uint32_t *host_u32x4, int first, int count);
+
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *
  * One process per GPU.  Rank r of `world` owns the contiguous block [lo, hi) of the bank's voices and renders its

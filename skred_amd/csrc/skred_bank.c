@@ -178,6 +178,7 @@ void skred_bank_destroy(skred_bank_t *b) {
   sk_notes_free(b);
   sk_owner_free(b);
   sk_pedal_free(b);
+  sk_glide_free(b);
   for (int i = 0; i < SK_UPD_RING; i++) {
     if (b->upd[i].d) hipFree(b->upd[i].d);
     if (b->upd[i].h) hipHostFree(b->upd[i].h);

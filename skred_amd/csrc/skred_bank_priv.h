@@ -11,6 +11,7 @@
  *   skred_bank_ctl.c     patch controllers                     skred_bank_owner.c  note owners
  *   skred_bank_expr.c    channels and per-note expression: masked owner matches, per-entry controller values and filter coefficients
  *   skred_bank_pedal.c   pedals: note-offs held back per slot, sostenuto's latch, the pedal-up
+ *   skred_bank_glide.c   portamento: per-voice glides, started under the owner guard, advanced and landed on the device
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -202,6 +203,9 @@ struct skred_bank {
   /* pedals (skred_bank_pedal.c), allocated and zeroed by the first pedal call */
   uint32_t *d_pedal;                /* [n_voices] a slot's SKRED_PEDAL_* bits at its first voice; NULL: no pedal call yet, and the tag
                                        launches clear nothing; no render kernel reads it */
+  /* portamento (skred_bank_glide.c), allocated and zeroed by the first call that starts a glide */
+  sk_glide_t *d_glide;              /* [n_voices] target, rate_up, rate_down, carry per voice; target 0: not gliding; NULL: no glide was
+                                       ever started, and the tag launches clear nothing; no render kernel reads it */
 };
 
 /* per-voice classification (host shadow) */
@@ -297,6 +301,10 @@ int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t 
                         uint32_t *d_result, const char *who, hipStream_t s);
 /* skred_bank_pedal.c: the pedal array (skred_bank_destroy) */
 void sk_pedal_free(skred_bank_t *b);
+/* skred_bank_glide.c: the glide array (skred_bank_destroy); n checked entries as they travel -- out[j] = glide[perm[j]] (perm NULL:
+ * glide[j]), the four named words as they stand, the reserved ones zero.  Pure host */
+void sk_glide_free(skred_bank_t *b);
+void sk_glide_pack(const skred_glide_t *glide, int n, const uint32_t *perm, sk_glide_each_t *out);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);

@@ -20,12 +20,13 @@
  *   skred_owner_kernels.hip   sk_launch_owner_tag, sk_launch_owner_find, sk_launch_owner_stamps
  *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each_filter
  *   skred_pedal_kernels.hip   sk_launch_pedal_clear, sk_launch_pedal_stamps, sk_launch_pedal_latch, sk_launch_pedal_up
+ *   skred_glide_kernels.hip   sk_launch_glide_clear, sk_launch_glide_start, sk_launch_glide_advance, sk_launch_glide_stop
  *   skred_fx_pedal_kernels.hip  skx_launch_pedal_stamps, skx_launch_pedal_latch, skx_launch_pedal_up (sk_launch_pedal_clear by
  *                             skred_fx_owner.c too)
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,
- * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c, skred_bank_ctl.c, skred_bank_owner.c, skred_bank_expr.c, skred_bank_pedal.c and
+ * skred_bank_steal.c, skred_bank_notes.c, skred_bank_slots.c, skred_bank_ctl.c, skred_bank_owner.c, skred_bank_expr.c, skred_bank_pedal.c, skred_bank_glide.c and
  * skred_recorder.c (sk_launch_owner_tag, sk_launch_owner_find, sk_launch_match_find, sk_launch_list_append and sk_launch_chan_join by the fixed-point
  * bank's skred_fx_owner.c, skred_fx_expr.c and skred_fx_steal.c too).  A launcher that takes `cnt, done, seq` gets them from the batch path (skred_bank_stage.c: sk_batch_send).
  */
@@ -396,6 +397,40 @@ int sk_launch_pedal_latch(const uint32_t *owner, uint32_t *pedal, uint32_t value
 int sk_launch_pedal_up(const uint32_t *owner, uint32_t *pedal, uint32_t value, uint32_t mask, int first, int count, int slot_voices,
                        uint64_t voice_mask, uint32_t flags, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
                        uint64_t now, uint64_t *mask_list, uint32_t *d_result, hipStream_t stream);
+
+/* ---- portamento (skred_bank_glide.c -> skred_glide_kernels.hip; include/skred_amd.h: skred_bank_glide_owned / _glide_tags /
+ * _glide_advance / _glide_stop) ----
+ * glide[n_voices]: four words per voice (one 16-byte load) beside the owner array.  Only these launches read or write it; the words
+ * they store into the planes are voice_phase_inc's (SKP_OSC word 0), finite products or a target's bits. */
+enum { SK_GLIDE_TARGET = 0, SK_GLIDE_RATE_UP, SK_GLIDE_RATE_DOWN, SK_GLIDE_CARRY, SK_GLIDE_WORDS = 4 };
+typedef struct {
+  uint32_t w[SK_GLIDE_WORDS];
+} sk_glide_t;
+/* A per-entry record is skred_glide_t word for word (layout and bits checked at compile time in skred_bank_glide.c): 32 bytes, so
+ * that set, rate_up, rate_down, scale are one aligned 16-byte load.  The bits equal SKRED_GLIDE_*. */
+#define SK_GLIDE_FROM_SCALE (1u << 0)
+#define SK_GLIDE_TO_SCALE   (1u << 1)
+enum { SK_GLIDE_E_SET = 0, SK_GLIDE_E_RATE_UP, SK_GLIDE_E_RATE_DOWN, SK_GLIDE_E_SCALE, SK_GLIDE_E_WORDS = 8 };
+typedef struct {
+  uint32_t w[SK_GLIDE_E_WORDS];
+} sk_glide_each_t;
+#define SK_GLIDE_SPAN 256          /* threads per workgroup of the glide kernels */
+/* glide[d_slots[k] + l] = 0, l < slot_voices, under sk_launch_owner_tag's list rule: launched behind it by a bank that has a glide
+ * array */
+int sk_launch_glide_clear(sk_glide_t *glide, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
+                          hipStream_t stream);
+/* entry k starts d_each[k]'s glide (16-byte aligned) on the voice_mask voices of d_slots[k] where that is a slot whose owner is
+ * d_tags[k]; d_result[3] (may be NULL; zeroed on `stream` ahead of the kernel) += voices set gliding, starts withheld, slots whose
+ * owner differs */
+int sk_launch_glide_start(sk_glide_t *glide, const sk_glide_each_t *d_each, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
+                          const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, sk_plane_t *osc,
+                          uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] (may be NULL; zeroed on `stream` ahead
+ * of the kernel) += voices still gliding, voices that arrived */
+int sk_launch_glide_advance(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int num_frames, uint32_t *d_result,
+                            hipStream_t stream);
+/* glide[first .. first + count) = 0; snap != 0: a gliding voice's increment = its target first */
+int sk_launch_glide_stop(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int snap, hipStream_t stream);
 
 /* ---- pedals on the fixed-point bank (skred_fx_pedal.c -> skred_fx_pedal_kernels.hip; include/skred_amd_fxpt.h:
  * skred_fxbank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up) ----

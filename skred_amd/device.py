@@ -50,12 +50,13 @@ ABI_SYMBOLS = [
     "skred_bank_find_steal_slots_match", "skred_bank_find_steal_slots_match_host", "skred_bank_note_on_channel",
     "skred_bank_stamp_owned_pedal", "skred_bank_release_tags_pedal", "skred_bank_pedal_latch", "skred_bank_pedal_up",
     "skred_bank_pedal_clear", "skred_bank_download_pedals",
+    "skred_bank_glide_owned", "skred_bank_glide_tags", "skred_bank_glide_advance", "skred_bank_glide_stop", "skred_bank_download_glide",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
                     "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check",
                     "skred_filter_each_check", "skred_filter_coeffs",
-                    "skred_chan_check", "skred_pedal_check"]
+                    "skred_chan_check", "skred_pedal_check", "skred_glide_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -208,6 +209,28 @@ PEDAL_LIFT_SUSTAIN, PEDAL_LIFT_SOSTENUTO, PEDAL_SUSTAIN_DOWN = 1, 2, 4
 PEDAL_CALL_STAMP_OWNED, PEDAL_CALL_RELEASE_TAGS, PEDAL_CALL_LATCH, PEDAL_CALL_UP = 0, 1, 2, 3
 
 
+# SKRED_GLIDE_* (skred_bank_glide_owned / _glide_tags)
+GLIDE_FROM_SCALE, GLIDE_TO_SCALE = 1, 2
+
+
+class GlideC(C.Structure):
+    """ctypes image of ``skred_glide_t`` (32 bytes): `set` is exactly one of GLIDE_FROM_SCALE and GLIDE_TO_SCALE."""
+    _fields_ = [("set", C.c_uint32), ("rate_up", C.c_float), ("rate_down", C.c_float), ("scale", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
+def glide(set: int, rate_up: float, rate_down: float, scale: float) -> GlideC:
+    """One glide: ``glide(GLIDE_FROM_SCALE, 2 ** (1 / 96), 2 ** (-1 / 96), 2 ** (-7 / 12))`` slides up a fifth into the note."""
+    return GlideC(int(set), rate_up, rate_down, scale)
+
+
+def glide_array(glides):
+    """A contiguous ``GlideC`` array from a sequence of GlideC (a ctypes array of GlideC passes through)."""
+    if isinstance(glides, C.Array) and glides._type_ is GlideC:
+        return glides
+    glides = list(glides)
+    return (GlideC * len(glides))(*glides)
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -348,6 +371,12 @@ def load() -> C.CDLL:
     L.skred_bank_pedal_up.argtypes = [vp, i32, i32, i32, C.c_uint64, C.POINTER(OwnerMatchC), C.c_uint32, vp, vp]
     L.skred_bank_pedal_clear.argtypes = [vp, i32, i32, vp]
     L.skred_bank_download_pedals.argtypes = [vp, vp, i32, i32]
+    L.skred_glide_check.argtypes = [vp, i32, i32, C.c_uint64]
+    L.skred_bank_glide_owned.argtypes = [vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_glide_tags.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
+    L.skred_bank_glide_advance.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.skred_bank_glide_stop.argtypes = [vp, i32, i32, i32, vp]
+    L.skred_bank_download_glide.argtypes = [vp, vp, i32, i32]
     _lib = L
     return L
 
@@ -424,6 +453,14 @@ def pedal_check(call: int, n_voices: int, first: int = 0, count: int = 0, slot_v
     return int(load().skred_pedal_check(int(call), int(n_voices), int(first), int(count), int(slot_voices), int(voice_mask),
                                         C.byref(m) if m is not None else None, int(flags) & 0xFFFFFFFF,
                                         arr.ctypes.data if arr is not None else None, len(arr) if arr is not None else 0))
+
+
+def glide_check(glides, slot_voices: int, voice_mask: int) -> int:
+    """skred_glide_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for what the two starting calls would refuse about the entries
+    (None stands for a NULL array).  Pure host."""
+    arr = glide_array(glides) if glides is not None else None
+    return int(load().skred_glide_check(C.cast(arr, C.c_void_p) if arr is not None else None, len(arr) if arr is not None else 0,
+                                        int(slot_voices), int(voice_mask)))
 
 
 def ctl_each_check(each, ctls, voice_mask: int, slot_voices: Optional[int] = None) -> int:
@@ -944,6 +981,42 @@ class DeviceBank:
         count = self.n - first if count is None else count
         out = np.full(max(count, 0), 0xDEADBEEF, np.uint32)
         _check(self.L.skred_bank_download_pedals(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_pedals")
+        return out
+
+    # ---- portamento (include/skred_amd.h: skred_bank_glide_owned / _glide_tags / _glide_advance / _glide_stop) ----
+    def glide_owned(self, glides, slot_voices: int, voice_mask: int, d_slots: int, tags, d_count: int = 0, d_result: int = 0,
+                    stream: int = 0):
+        """Entry k starts glides[k] on the masked voices of d_slots[k] where that slot's owner is tags[k].  d_result (uint32[3], may
+        be 0): voices set gliding, starts withheld, slots whose owner differs."""
+        arr, t = glide_array(glides), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_glide_owned(self.h, C.cast(arr, C.c_void_p), int(slot_voices), int(voice_mask), d_slots or None,
+                                             t.ctypes.data, len(t), d_count or None, d_result or None, stream or None),
+               "skred_bank_glide_owned")
+
+    def glide_tags(self, glides, first: int, count: int, slot_voices: int, voice_mask: int, tags, d_result: int = 0, stream: int = 0):
+        """Glides by note id: glides[k] starts on the lowest slot of the range that carries tags[k]."""
+        arr, t = glide_array(glides), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_glide_tags(self.h, C.cast(arr, C.c_void_p), int(first), int(count), int(slot_voices), int(voice_mask),
+                                            t.ctypes.data, len(t), d_result or None, stream or None), "skred_bank_glide_tags")
+
+    def glide_advance(self, first: int, count: int, frames: int, d_result: int = 0, stream: int = 0):
+        """Every gliding voice of the range moves by `frames` frames: one multiply per 64 of them, the target's bits on arrival.
+        d_result (uint32[2], may be 0): voices still gliding, voices that arrived."""
+        _check(self.L.skred_bank_glide_advance(self.h, int(first), int(count), int(frames), d_result or None, stream or None),
+               "skred_bank_glide_advance")
+
+    def glide_stop(self, first: int = 0, count: Optional[int] = None, snap: bool = False, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_bank_glide_stop(self.h, int(first), int(count), int(bool(snap)), stream or None), "skred_bank_glide_stop")
+
+    def download_glide(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The glide words of [first, first + count) as a (count, 4) uint32 array: target, rate_up, rate_down, carry; waits for the
+        device.  Zeros on a bank that never started a glide."""
+        count = self.n - first if count is None else count
+        out = np.full((max(count, 0), 4), 0xDEADBEEF, np.uint32)
+        _check(self.L.skred_bank_download_glide(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_glide")
         return out
 
     def force_generic(self, on: bool = True):
