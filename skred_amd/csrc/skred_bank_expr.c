@@ -246,7 +246,7 @@ int skred_bank_ctl_match(skred_bank_t *b, const skred_ctl_t *ctl, int first, int
   if ((rc = sk_batch_begin(b, bytes, s, &bt))) return rc;
   const uint64_t lists = sk_ctl_pack(ctl, slot_voices, voice_mask, (sk_ctl_t *)bt.h);
   /* (skred_bank_ctl.c: beyond 64 workgroups the records are read from the device, not over the bus) */
-  const sk_ctl_t *src = (const sk_ctl_t *)sk_batch_send(b, &bt, bytes, count > 64 * SK_EXPR_SPAN, s);
+  const sk_ctl_t *src = (const sk_ctl_t *)sk_batch_send(b, &bt, bytes, count > 64 * SK_CONTROL_SPAN, s);
   if (!src) return SKRED_E_NO_DEVICE;
   const hipError_t e = (hipError_t)sk_launch_ctl_match(src, slot_voices, voice_mask, first, count, b->d_owner, m->value, m->mask, b->d_ro, b->d_rw,
                                                        b->d_mask[b->mask_p], d_result, bt.cnt, bt.done, bt.seq, s);
@@ -279,7 +279,7 @@ static int owned_each_launch(skred_bank_t *b, const skred_ctl_t *ctl, const skre
   const size_t rec_bytes = (size_t)slot_voices * sizeof(sk_ctl_t), each_bytes = each ? (size_t)n * sizeof(sk_each_t) : 0;
   const size_t filt_bytes = filt ? (size_t)n * sizeof(sk_filt_each_t) : 0;
   const size_t bytes = rec_bytes + each_bytes + filt_bytes + (size_t)n * sizeof(uint32_t);
-  const int wide = (int64_t)n * slot_voices > 64 * SK_EXPR_SPAN;
+  const int wide = (int64_t)n * slot_voices > 64 * SK_CONTROL_SPAN;
   sk_batch_t bt;
   int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;

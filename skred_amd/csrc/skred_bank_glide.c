@@ -63,14 +63,7 @@ static int glide_ensure(skred_bank_t *b) {
   if (b->d_glide) return SKRED_OK;
   const int rc = sk_owner_ensure(b);
   if (rc) return rc;
-  sk_glide_t *p = NULL;
-  const size_t bytes = (size_t)b->n_voices * sizeof(sk_glide_t);
-  HIP_TRY(hipMalloc((void **)&p, bytes));
-  hipError_t e = hipMemset(p, 0, bytes);
-  if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
-  if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "glide array -> %s", hipGetErrorString(e)); }
-  b->d_glide = p;
-  return SKRED_OK;
+  return sk_side_alloc((void **)&b->d_glide, (size_t)b->n_voices * sizeof(sk_glide_t), "glide array");
 }
 
 void sk_glide_free(skred_bank_t *b) {
@@ -165,12 +158,5 @@ int skred_bank_glide_stop(skred_bank_t *b, int first, int count, int snap, void 
 
 int skred_bank_download_glide(skred_bank_t *b, uint32_t *host_u32x4, int first, int count) {
   if (!b || !host_u32x4 || count < 0) return fail(SKRED_E_BAD_ARG, "download_glide: bad arguments");
-  const int rc = sk_check_window(b->n_voices, first, count, "download_glide");
-  if (rc) return rc;
-  if (count == 0) return SKRED_OK;
-  if (!b->d_glide) { memset(host_u32x4, 0, (size_t)count * sizeof(sk_glide_t)); return SKRED_OK; }
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host_u32x4, b->d_glide + first, (size_t)count * sizeof(sk_glide_t), hipMemcpyDeviceToHost));
-  return SKRED_OK;
+  return sk_side_download(b->d_glide, sizeof(sk_glide_t), b->device, b->n_voices, host_u32x4, first, count, "download_glide");
 }

@@ -71,10 +71,8 @@ int sk_owner_ensure(skred_bank_t *b) {
   if (b->d_owner) return SKRED_OK;
   uint32_t *p = NULL;
   const size_t words = (size_t)b->n_voices + SKRED_OWNER_MAX_TAGS + 2;
-  HIP_TRY(hipMalloc((void **)&p, words * sizeof(uint32_t)));
-  hipError_t e = hipMemset(p, 0, words * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
-  if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "owner array -> %s", hipGetErrorString(e)); }
+  const int rc = sk_side_alloc((void **)&p, words * sizeof(uint32_t), "owner array");
+  if (rc) return rc;
   b->d_owner = p;
   b->d_owner_slots = (int32_t *)(p + b->n_voices);
   b->d_match_pair = p + b->n_voices + SKRED_OWNER_MAX_TAGS;
@@ -124,7 +122,7 @@ int skred_bank_tag_slots(skred_bank_t *b, const int32_t *d_slots, const uint32_t
 int sk_owner_find_launch(skred_bank_t *b, int first, int count, int slot_voices, const uint32_t *tags, int n, int32_t *d_out, hipStream_t s) {
   const size_t bytes = 2 * (size_t)n * sizeof(uint32_t);
   /* one workgroup per 256 slots stages the tags: beyond a handful of workgroups they read the slot's device twin, not the bus */
-  const int wide = (count / slot_voices) > 64 * SK_OWNER_SPAN;
+  const int wide = (count / slot_voices) > 64 * SK_CONTROL_SPAN;
   sk_batch_t bt;
   const int rc = sk_batch_begin(b, bytes, s, &bt);
   if (rc) return rc;
@@ -232,24 +230,12 @@ int skred_bank_ctl_owned(skred_bank_t *b, const skred_ctl_t *ctl, int slot_voice
 
 int skred_bank_owner_clear(skred_bank_t *b, int first, int count, void *stream) {
   if (!b) return fail(SKRED_E_BAD_ARG, "owner_clear: no bank");
-  const int rc = sk_check_window(b->n_voices, first, count, "owner_clear");
-  if (rc) return rc;
-  if (count == 0 || !b->d_owner) return SKRED_OK;       /* (never tagged: every word is 0 already) */
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipMemsetAsync(b->d_owner + first, 0, (size_t)count * sizeof(uint32_t), (hipStream_t)stream));
-  return SKRED_OK;
+  return sk_side_clear(b->d_owner, sizeof(uint32_t), b->device, b->n_voices, first, count, (hipStream_t)stream, "owner_clear");
 }
 
 int skred_bank_download_owners(skred_bank_t *b, uint32_t *host_u32, int first, int count) {
   if (!b || !host_u32 || count < 0) return fail(SKRED_E_BAD_ARG, "download_owners: bad arguments");
-  const int rc = sk_check_window(b->n_voices, first, count, "download_owners");
-  if (rc) return rc;
-  if (count == 0) return SKRED_OK;
-  if (!b->d_owner) { memset(host_u32, 0, (size_t)count * sizeof(uint32_t)); return SKRED_OK; }
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host_u32, b->d_owner + first, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return SKRED_OK;
+  return sk_side_download(b->d_owner, sizeof(uint32_t), b->device, b->n_voices, host_u32, first, count, "download_owners");
 }
 
 int skred_bank_download_env_clocks(skred_bank_t *b, uint64_t *sample_start, uint64_t *sample_release, int first, int count) {

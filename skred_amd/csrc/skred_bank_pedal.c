@@ -66,14 +66,7 @@ static int pedal_ensure(skred_bank_t *b) {
   if (b->d_pedal) return SKRED_OK;
   const int rc = sk_owner_ensure(b);
   if (rc) return rc;
-  uint32_t *p = NULL;
-  const size_t bytes = (size_t)b->n_voices * sizeof(uint32_t);
-  HIP_TRY(hipMalloc((void **)&p, bytes));
-  hipError_t e = hipMemset(p, 0, bytes);
-  if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
-  if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "pedal array -> %s", hipGetErrorString(e)); }
-  b->d_pedal = p;
-  return SKRED_OK;
+  return sk_side_alloc((void **)&b->d_pedal, (size_t)b->n_voices * sizeof(uint32_t), "pedal array");
 }
 
 void sk_pedal_free(skred_bank_t *b) {
@@ -155,22 +148,10 @@ int skred_bank_pedal_up(skred_bank_t *b, int first, int count, int slot_voices, 
 
 int skred_bank_pedal_clear(skred_bank_t *b, int first, int count, void *stream) {
   if (!b) return fail(SKRED_E_BAD_ARG, "pedal_clear: no bank");
-  const int rc = sk_check_window(b->n_voices, first, count, "pedal_clear");
-  if (rc) return rc;
-  if (count == 0 || !b->d_pedal) return SKRED_OK;        /* (no pedal call yet: every word is 0 already) */
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipMemsetAsync(b->d_pedal + first, 0, (size_t)count * sizeof(uint32_t), (hipStream_t)stream));
-  return SKRED_OK;
+  return sk_side_clear(b->d_pedal, sizeof(uint32_t), b->device, b->n_voices, first, count, (hipStream_t)stream, "pedal_clear");
 }
 
 int skred_bank_download_pedals(skred_bank_t *b, uint32_t *host_u32, int first, int count) {
   if (!b || !host_u32 || count < 0) return fail(SKRED_E_BAD_ARG, "download_pedals: bad arguments");
-  const int rc = sk_check_window(b->n_voices, first, count, "download_pedals");
-  if (rc) return rc;
-  if (count == 0) return SKRED_OK;
-  if (!b->d_pedal) { memset(host_u32, 0, (size_t)count * sizeof(uint32_t)); return SKRED_OK; }
-  HIP_TRY(hipSetDevice(b->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host_u32, b->d_pedal + first, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return SKRED_OK;
+  return sk_side_download(b->d_pedal, sizeof(uint32_t), b->device, b->n_voices, host_u32, first, count, "download_pedals");
 }

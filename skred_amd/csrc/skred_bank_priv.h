@@ -2,7 +2,8 @@
  * skred_bank_priv.h -- internals shared by the translation units behind include/skred_amd.h.  Not installed.
  *   skred_bank.c         lifecycle, tables, upload / download, options, class and tape plan
  *   skred_bank_render.c  one block from request to kernels, as skred_bank_plan.c picks them
- *   skred_bank_stage.c   the staging ring and the batch path: the one way a host-written batch reaches a kernel; the _host queries' read-back
+ *   skred_bank_stage.c   the staging ring and the batch path: the one way a host-written batch reaches a kernel; the _host queries' read-back;
+ *                        the per-voice side arrays (owners, pedals, glides) of both banks: sk_side_alloc / _clear / _download
  *   skred_bank_checks.c  the argument checks the control calls share (pure host; the fixed-point bank uses them too)
  *   skred_bank_update.c  block-granular updates and the deferred queue
  *   skred_bank_idle.c    the free-voice query                  skred_bank_steal.c  the victim query
@@ -339,6 +340,12 @@ int sk_batch_end(sk_batch_t *bt, hipError_t e, const char *who, hipStream_t s);
  * room for `need` entries behind `head` words in a grow-on-demand answer buffer (h_buf NULL: no pinned twin), both banks' */
 int sk_read_back(const int32_t *d_out, int32_t *h_out, int counts, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
 int sk_answer_room(void **d_buf, void **h_buf, size_t *cap, size_t head, size_t need);
+/* ... and the per-voice side arrays (owners, pedals, glides; plain pointers: the fixed-point bank's too).  alloc: `bytes`, zeroed for
+ * every stream, or a failure under `what`.  clear: the checked window of `elem`-byte elements zeroed on `s`.  download: the checked
+ * window to `host`, zeros when the array was never allocated (d_arr NULL, which clear takes too) */
+int sk_side_alloc(void **d_arr, size_t bytes, const char *what);
+int sk_side_clear(void *d_arr, size_t elem, int device, int n_voices, int first, int count, hipStream_t s, const char *who);
+int sk_side_download(const void *d_arr, size_t elem, int device, int n_voices, void *host, int first, int count, const char *who);
 /* skred_bank_checks.c (`who`: the entry point, for the error text): K and -- `what` != NULL, its name -- a mask over the K voices;
  * the stamp bits; a list's length (n * K stays an int); a range of whole slots of K voices inside the bank, empty only where
  * allowed; a plain window for the clears and downloads */

@@ -8,8 +8,9 @@
  *   end     takes the launch's verdict: the slot is the batch's until its kernel has run; after a failed launch the stream is
  *           waited for, because a copy into the slot's device twin, or an earlier launch of the batch, may still read the slot
  *
- * Also the read-back ending of the _host queries (sk_read_back) and the room of the grow-on-demand answer buffers (sk_answer_room).
- * The fixed-point bank guards its ring with events instead (skred_fxbank_priv.h says why); nothing here serves it but those two, which
+ * Also the read-back ending of the _host queries (sk_read_back), the room of the grow-on-demand answer buffers (sk_answer_room) and
+ * the per-voice side arrays' allocation, clear and download (sk_side_alloc / _clear / _download).
+ * The fixed-point bank guards its ring with events instead (skred_fxbank_priv.h says why); nothing here serves it but those five, which
  * take plain pointers.  Its own ring and batch path, shaped like this one: skred_fx_stage.c.
  */
 #include <sched.h>
@@ -124,6 +125,41 @@ int sk_answer_room(void **d_buf, void **h_buf, size_t *cap, size_t head, size_t 
   HIP_TRY(hipMalloc(d_buf, (head + entries) * sizeof(uint32_t)));
   if (h_buf) HIP_TRY(hipHostMalloc(h_buf, (head + entries) * sizeof(uint32_t), hipHostMallocDefault));
   *cap = entries;
+  return SKRED_OK;
+}
+
+/* The per-voice side arrays of both banks (note owners, pedals, glides: one element per voice, NULL until the first call that needs
+ * them, freed with the bank), as plain pointers.  alloc: `bytes` on the current device, zeroed so that whatever stream the first
+ * caller uses sees the zeros; fails under `what`.  clear: the checked window [first, +count) of `elem`-byte elements zeroed on `s` --
+ * an array that was never allocated holds zeros already.  download: the same window to the host behind everything queued, zeros
+ * where the array was never allocated.  `who` names the entry point in the window's error text */
+int sk_side_alloc(void **d_arr, size_t bytes, const char *what) {
+  void *p = NULL;
+  HIP_TRY(hipMalloc((void **)&p, bytes));
+  hipError_t e = hipMemset(p, 0, bytes);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "%s -> %s", what, hipGetErrorString(e)); }
+  *d_arr = p;
+  return SKRED_OK;
+}
+
+int sk_side_clear(void *d_arr, size_t elem, int device, int n_voices, int first, int count, hipStream_t s, const char *who) {
+  const int rc = sk_check_window(n_voices, first, count, who);
+  if (rc) return rc;
+  if (count == 0 || !d_arr) return SKRED_OK;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipMemsetAsync((char *)d_arr + (size_t)first * elem, 0, (size_t)count * elem, s));
+  return SKRED_OK;
+}
+
+int sk_side_download(const void *d_arr, size_t elem, int device, int n_voices, void *host, int first, int count, const char *who) {
+  const int rc = sk_check_window(n_voices, first, count, who);
+  if (rc) return rc;
+  if (count == 0) return SKRED_OK;
+  if (!d_arr) { memset(host, 0, (size_t)count * elem); return SKRED_OK; }
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(host, (const char *)d_arr + (size_t)first * elem, (size_t)count * elem, hipMemcpyDeviceToHost));
   return SKRED_OK;
 }
 

@@ -1,6 +1,6 @@
 // skred_ctl_common.hpp -- what the controller kernels share (skred_ctl_kernels.hip: a range, a list, a list under the note-owner
 // guard; skred_expr_kernels.hip: a range under a masked owner match, a list with per-entry values): the records' way into LDS, the
-// field stores with their two guards, and the two counts.  One place for the stores, so that a guarded or per-entry controller
+// field stores with their two guards, and the counts.  One place for the stores, so that a guarded or per-entry controller
 // cannot drift from skred_bank_ctl_range.
 #ifndef SKRED_CTL_COMMON_HPP
 #define SKRED_CTL_COMMON_HPP
@@ -11,12 +11,10 @@
 #include "skred_launch.h"
 #include "skred_update_common.hpp"   // sk_plane_ptrs_t, sk_list_voice
 
-#define SK_CTL_SPAN 256
-
 // the K records -> LDS (the unmasked ones arrive zeroed by the host: set == 0)
 __device__ __forceinline__ void sk_ctl_stage(uint32_t *lds, const sk_ctl_t *__restrict__ recs, int K) {
   const uint32_t *src = reinterpret_cast<const uint32_t *>(recs);
-  for (int i = threadIdx.x; i < K * SK_CTL_WORDS; i += SK_CTL_SPAN) lds[i] = src[i];
+  for (int i = threadIdx.x; i < K * SK_CTL_WORDS; i += SK_CONTROL_SPAN) lds[i] = src[i];
   __syncthreads();
 }
 
@@ -75,19 +73,25 @@ __device__ __forceinline__ uint32_t sk_ctl_store(const sk_plane_ptrs_t &p, uint6
   return withheld;
 }
 
-// d_result[0] += voices written, d_result[1] += stores withheld, over the workgroup (every thread arrives: __syncthreads inside)
-__device__ __forceinline__ void sk_ctl_count(uint32_t *sums, uint32_t *d_result, bool wrote, uint32_t withheld) {
+// d_result[0] += voices written, d_result[1] += stores withheld and -- N == 3, the guarded controllers -- d_result[2] += slots missed,
+// over the workgroup (sums[N] in LDS; every thread arrives: __syncthreads inside).  A miss is the ordinary case under a guard (fifteen
+// slots of sixteen on a 16-channel range), so it goes through LDS like the other two: at most N global atomics per workgroup
+template <int N>
+__device__ __forceinline__ void sk_ctl_count(uint32_t *sums, uint32_t *d_result, bool wrote, uint32_t withheld, bool missed = false) {
+  static_assert(N == 2 || N == 3, "two counts, or three under a guard");
   const int tid = threadIdx.x;
-  if (tid < 2) sums[tid] = 0;
+  if (tid < N) sums[tid] = 0;
   __syncthreads();
   const uint32_t w = (uint32_t)__popcll(__ballot(wrote));
   const uint32_t h = (uint32_t)__popcll(__ballot(withheld >= 1)) + (uint32_t)__popcll(__ballot(withheld >= 2));
+  const uint32_t m = N == 3 ? (uint32_t)__popcll(__ballot(missed)) : 0u;
   if ((tid & 63) == 0) {
     if (w) atomicAdd(&sums[0], w);
     if (h) atomicAdd(&sums[1], h);
+    if (N == 3 && m) atomicAdd(&sums[2], m);
   }
   __syncthreads();
-  if (d_result && tid < 2 && sums[tid]) atomicAdd(d_result + tid, sums[tid]);
+  if (d_result && tid < N && sums[tid]) atomicAdd(d_result + tid, sums[tid]);
 }
 
 #endif

@@ -26,50 +26,29 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "skred_ctl_common.hpp"      // SK_CTL_SPAN, sk_ctl_stage, sk_ctl_store, sk_ctl_finite
+#include "skred_ctl_common.hpp"      // sk_ctl_stage, sk_ctl_store, sk_ctl_count, sk_ctl_finite
 #include "skred_idle_scan.hpp"       // sk_idle_count_tail, sk_idle_scatter_tail
 #include "skred_launch.h"
-#include "skred_update_common.hpp"   // sk_plane_ptrs_t, sk_stamp_store, sk_slot_valid, sk_owner_count, sk_batch_done
+#include "skred_update_common.hpp"   // sk_entry_decode, sk_entry_owned, sk_range_lane, sk_stamp_store, sk_owner_count, sk_batch_done
 
-static_assert(SK_EXPR_SPAN == SK_IDLE_SPAN && SK_EXPR_SPAN == SK_CTL_SPAN, "the shared tails and counts are written for this span");
-
-__device__ __forceinline__ bool sk_owner_matches(uint32_t w, uint32_t value, uint32_t mask) { return w != 0u && (w & mask) == value; }
-
-// sk_ctl_count with a third sum: d_result[0] += voices written, [1] += stores withheld, [2] += slots missed, over the workgroup.  A miss
-// is the ordinary case under a match guard (fifteen slots of sixteen on a 16-channel range), so it goes through LDS like the other
-// two: at most three global atomics per workgroup (every thread arrives: __syncthreads inside)
-__device__ __forceinline__ void sk_expr_ctl_count(uint32_t *sums, uint32_t *d_result, bool wrote, uint32_t withheld, bool missed) {
-  const int tid = threadIdx.x;
-  if (tid < 3) sums[tid] = 0;
-  __syncthreads();
-  const uint32_t w = (uint32_t)__popcll(__ballot(wrote));
-  const uint32_t h = (uint32_t)__popcll(__ballot(withheld >= 1)) + (uint32_t)__popcll(__ballot(withheld >= 2));
-  const uint32_t m = (uint32_t)__popcll(__ballot(missed));
-  if ((tid & 63) == 0) {
-    if (w) atomicAdd(&sums[0], w);
-    if (h) atomicAdd(&sums[1], h);
-    if (m) atomicAdd(&sums[2], m);
-  }
-  __syncthreads();
-  if (d_result && tid < 3 && sums[tid]) atomicAdd(d_result + tid, sums[tid]);
-}
+static_assert(SK_CONTROL_SPAN == SK_IDLE_SPAN, "the match list's count and scatter tails are the idle query's");
 
 // this lane's slot (its first voice in v) matches
 __device__ __forceinline__ bool sk_match_listed(const sk_match_args_t &m, int &v) {
-  const int64_t s = (int64_t)blockIdx.x * SK_EXPR_SPAN + threadIdx.x;
+  const int64_t s = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
   const bool in_range = s < m.n_slots;
   v = m.first + (int)((in_range ? s : 0) << m.k_shift);                 // (inside the bank: checked on the host)
   return in_range && sk_owner_matches(m.owner[v], m.value, m.mask);
 }
 
-__global__ __launch_bounds__(SK_EXPR_SPAN) void sk_match_count_kernel(sk_match_args_t m) {
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_match_count_kernel(sk_match_args_t m) {
   __shared__ int lds[SK_IDLE_COUNT_LDS];
   int v;
   const bool listed = sk_match_listed(m, v);
   sk_idle_count_tail(m.idle, v, listed, lds);
 }
 
-__global__ __launch_bounds__(SK_EXPR_SPAN) void sk_match_scatter_kernel(sk_match_args_t m) {
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_match_scatter_kernel(sk_match_args_t m) {
   __shared__ int lds[SK_IDLE_WAVES];
   if (blockIdx.x == 0 && threadIdx.x == 0) m.d_total[0] = m.idle.words[SK_IDLE_W_TOTAL];   // (the count launch is behind us on the stream)
   int v;
@@ -77,35 +56,30 @@ __global__ __launch_bounds__(SK_EXPR_SPAN) void sk_match_scatter_kernel(sk_match
   sk_idle_scatter_tail(m.idle, v, listed, lds);
 }
 
-__global__ __launch_bounds__(SK_EXPR_SPAN) void sk_match_stamps_kernel(const uint32_t *__restrict__ owner, uint32_t value, uint32_t omask,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_match_stamps_kernel(const uint32_t *__restrict__ owner, uint32_t value, uint32_t omask,
                                                                        int first, int count, int K, uint64_t voice_mask, uint32_t dirty,
                                                                        sk_plane_ptrs_t p, uint64_t now, uint64_t *mask, uint32_t *d_result) {
   __shared__ uint32_t sums[2];
-  const int64_t off = (int64_t)blockIdx.x * SK_EXPR_SPAN + threadIdx.x;
-  const bool in_range = off < count;
-  const int v = first + (int)(in_range ? off : 0), l = v & (K - 1);     // (first is a multiple of K)
-  const bool hit = in_range && sk_owner_matches(owner[v - l], value, omask);
-  if (hit && ((voice_mask >> l) & 1)) sk_stamp_store(p, now, mask, v, dirty);
-  const bool head = in_range && l == 0;                                 // one thread per slot counts it
-  const bool flag[2] = { head && hit, head && !hit };
+  const sk_lane_t t = sk_range_lane(first, count, K);
+  const bool hit = t.in_range && sk_owner_matches(owner[t.v - t.l], value, omask);
+  if (hit && ((voice_mask >> t.l) & 1)) sk_stamp_store(p, now, mask, t.v, dirty);
+  const bool flag[2] = { t.head && hit, t.head && !hit };
   sk_owner_count<2>(sums, d_result, flag);
 }
 
-__global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_match_kernel(const sk_ctl_t *__restrict__ recs, int K, uint64_t voice_mask, int first,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_ctl_match_kernel(const sk_ctl_t *__restrict__ recs, int K, uint64_t voice_mask, int first,
                                                                     int count, const uint32_t *__restrict__ owner, uint32_t value,
                                                                     uint32_t omask, sk_plane_ptrs_t p, uint64_t *mask, uint32_t *d_result,
                                                                     uint32_t *cnt, uint32_t *done, uint32_t seq) {
   __shared__ uint32_t lds[64 * SK_CTL_WORDS];
   __shared__ uint32_t sums[3];
   sk_ctl_stage(lds, recs, K);
-  const int64_t off = (int64_t)blockIdx.x * SK_EXPR_SPAN + threadIdx.x;
-  const bool in_range = off < count;
-  const int v = first + (int)(in_range ? off : 0), l = v & (K - 1);     // (first is a multiple of K)
-  const bool hit = in_range && sk_owner_matches(owner[v - l], value, omask);
-  const bool mine = hit && ((voice_mask >> l) & 1);
+  const sk_lane_t t = sk_range_lane(first, count, K);
+  const bool hit = t.in_range && sk_owner_matches(owner[t.v - t.l], value, omask);
+  const bool mine = hit && ((voice_mask >> t.l) & 1);
   uint32_t withheld = 0;
-  if (mine) withheld = sk_ctl_store(p, mask, v, lds + l * SK_CTL_WORDS);
-  sk_expr_ctl_count(sums, d_result, mine, withheld, in_range && !hit && l == 0);
+  if (mine) withheld = sk_ctl_store(p, mask, t.v, lds + t.l * SK_CTL_WORDS);
+  sk_ctl_count<3>(sums, d_result, mine, withheld, t.head && !hit);
   sk_batch_done(cnt, done, seq);
 }
 
@@ -118,7 +92,7 @@ template <> struct sk_each_filt_t<true> {
 };
 
 template <bool FILT>
-__global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_owned_each_kernel(const sk_ctl_t *__restrict__ recs, const sk_each_t *__restrict__ each,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_ctl_owned_each_kernel(const sk_ctl_t *__restrict__ recs, const sk_each_t *__restrict__ each,
                                                                          int k_shift, uint64_t voice_mask, const int32_t *d_slots,
                                                                          const uint32_t *__restrict__ tags, const uint32_t *__restrict__ owner,
                                                                          int n, const uint32_t *d_count, int n_voices, sk_plane_ptrs_t p,
@@ -126,19 +100,11 @@ __global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_owned_each_kernel(const s
                                                                          uint32_t seq, sk_each_filt_t<FILT> fa) {
   __shared__ uint32_t lds[64 * SK_CTL_WORDS];
   __shared__ uint32_t sums[3];
-  const int K = 1 << k_shift;
-  sk_ctl_stage(lds, recs, K);
-  const int64_t i = (int64_t)blockIdx.x * (SK_EXPR_SPAN >> k_shift) + ((int)threadIdx.x >> k_shift);
-  const int l = (int)threadIdx.x & (K - 1);
-  bool looked = i < n;
-  if (looked && d_count && (uint64_t)i >= (uint64_t)d_count[0]) looked = false;
-  int e = 0;
-  bool valid = false, owned = false;
-  if (looked) {
-    e = d_slots[i];
-    valid = sk_slot_valid(e, K, n_voices);
-    if (valid) owned = owner[e] == tags[i];
-  }
+  sk_ctl_stage(lds, recs, 1 << k_shift);
+  const sk_entry_t t = sk_entry_decode(SK_CONTROL_SPAN, k_shift, d_slots, n, d_count, n_voices);
+  const int64_t i = t.i;
+  const int l = t.l;
+  const bool owned = sk_entry_owned(owner, tags, t);
   const bool mine = owned && ((voice_mask >> l) & 1);
   uint32_t withheld = 0;
   if (mine) {
@@ -168,38 +134,25 @@ __global__ __launch_bounds__(SK_EXPR_SPAN) void sk_ctl_owned_each_kernel(const s
         r[SK_CTL_W_A2] = fa.filt[i].w[SK_FILT_W_A2];
       }
     }
-    withheld += sk_ctl_store(p, mask, e + l, r);                        // (at most 2: one for the increment, one for the amp)
+    withheld += sk_ctl_store(p, mask, t.e + l, r);                       // (at most 2: one for the increment, one for the amp)
   }
-  sk_expr_ctl_count(sums, d_result, mine, withheld, valid && !owned && l == 0);
+  sk_ctl_count<3>(sums, d_result, mine, withheld, t.valid && !owned && l == 0);
   sk_batch_done(cnt, done, seq);
 }
-
-static void sk_expr_planes(sk_plane_ptrs_t &p, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT]) {
-  for (int k = 0; k < SKP_COUNT; ++k) p.ro[k] = ro[k];
-  for (int k = 0; k < SKS_COUNT; ++k) p.rw[k] = rw[k];
-}
-
-static int sk_expr_shift(int slot_voices) {
-  int sh = 0;
-  while ((1 << sh) < slot_voices) ++sh;
-  return sh;
-}
-
-static unsigned sk_expr_grid(long long lanes) { return (unsigned)((lanes + SK_EXPR_SPAN - 1) / SK_EXPR_SPAN); }
 
 extern "C" int sk_launch_match_find(const sk_match_args_t *args, int first, int count, int slot_voices, hipStream_t stream) {
   if (count <= 0) return 0;
   sk_match_args_t m = *args;
-  m.k_shift = sk_expr_shift(slot_voices);
+  m.k_shift = sk_slot_shift(slot_voices);
   m.first = first;
   m.n_slots = count >> m.k_shift;
   m.idle.first = first; m.idle.end = first + count; m.idle.from = first;   // the list starts at the range's first slot: rank 0
   m.idle.base = first; m.idle.from_wg = 0;
-  const unsigned n_wg = sk_expr_grid(m.n_slots);
-  hipLaunchKernelGGL(sk_match_count_kernel, dim3(n_wg), dim3(SK_EXPR_SPAN), 0, stream, m);
+  const unsigned n_wg = sk_grid(m.n_slots);
+  hipLaunchKernelGGL(sk_match_count_kernel, dim3(n_wg), dim3(SK_CONTROL_SPAN), 0, stream, m);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_match_scatter_kernel, dim3(n_wg), dim3(SK_EXPR_SPAN), 0, stream, m);
+  hipLaunchKernelGGL(sk_match_scatter_kernel, dim3(n_wg), dim3(SK_CONTROL_SPAN), 0, stream, m);
   return (int)hipGetLastError();
 }
 
@@ -207,11 +160,11 @@ extern "C" int sk_launch_match_stamps(const uint32_t *owner, uint32_t value, uin
                                       uint64_t voice_mask, uint32_t dirty, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
                                       uint64_t now, uint64_t *mask_list, uint32_t *d_result, hipStream_t stream) {
   if (count <= 0) return 0;
-  const hipError_t e = hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), stream);
+  const hipError_t e = sk_result_clear(d_result, 2, stream);
   if (e != hipSuccess) return (int)e;
   sk_plane_ptrs_t p;
-  sk_expr_planes(p, ro, rw);
-  hipLaunchKernelGGL(sk_match_stamps_kernel, dim3(sk_expr_grid(count)), dim3(SK_EXPR_SPAN), 0, stream, owner, value, mask, first, count,
+  sk_planes(p, ro, rw);
+  hipLaunchKernelGGL(sk_match_stamps_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, owner, value, mask, first, count,
                      slot_voices, voice_mask, dirty, p, now, mask_list, d_result);
   return (int)hipGetLastError();
 }
@@ -220,13 +173,11 @@ extern "C" int sk_launch_ctl_match(const sk_ctl_t *d_recs, int slot_voices, uint
                                    uint32_t value, uint32_t mask, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
                                    uint64_t *mask_list, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream) {
   if (count <= 0) return 0;
-  if (d_result) {
-    const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return (int)e;
-  }
+  const hipError_t e = sk_result_clear(d_result, 3, stream);
+  if (e != hipSuccess) return (int)e;
   sk_plane_ptrs_t p;
-  sk_expr_planes(p, ro, rw);
-  hipLaunchKernelGGL(sk_ctl_match_kernel, dim3(sk_expr_grid(count)), dim3(SK_EXPR_SPAN), 0, stream, d_recs, slot_voices, voice_mask, first,
+  sk_planes(p, ro, rw);
+  hipLaunchKernelGGL(sk_ctl_match_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, d_recs, slot_voices, voice_mask, first,
                      count, owner, value, mask, p, mask_list, d_result, cnt, done, seq);
   return (int)hipGetLastError();
 }
@@ -238,22 +189,20 @@ extern "C" int sk_launch_ctl_owned_each_filter(const sk_ctl_t *d_recs, const sk_
                                                sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t *mask_list,
                                                uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
-  if (d_result) {
-    const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return (int)e;
-  }
+  const hipError_t e = sk_result_clear(d_result, 3, stream);
+  if (e != hipSuccess) return (int)e;
   sk_plane_ptrs_t p;
-  sk_expr_planes(p, ro, rw);
-  const int sh = sk_expr_shift(slot_voices), per_wg = SK_EXPR_SPAN >> sh;
-  const unsigned n_wg = (unsigned)(((long long)n + per_wg - 1) / per_wg);
+  sk_planes(p, ro, rw);
+  const int sh = sk_slot_shift(slot_voices);
+  const unsigned n_wg = sk_list_grid(n, sh);
   if (d_filt) {
     sk_each_filt_t<true> fa;
     fa.filt = d_filt;
     fa.filter_mask = filter_mask;
-    hipLaunchKernelGGL(sk_ctl_owned_each_kernel<true>, dim3(n_wg), dim3(SK_EXPR_SPAN), 0, stream, d_recs, d_each, sh, voice_mask, d_slots,
+    hipLaunchKernelGGL(sk_ctl_owned_each_kernel<true>, dim3(n_wg), dim3(SK_CONTROL_SPAN), 0, stream, d_recs, d_each, sh, voice_mask, d_slots,
                        d_tags, owner, n, d_count, n_voices, p, mask_list, d_result, cnt, done, seq, fa);
   } else {
-    hipLaunchKernelGGL(sk_ctl_owned_each_kernel<false>, dim3(n_wg), dim3(SK_EXPR_SPAN), 0, stream, d_recs, d_each, sh, voice_mask, d_slots,
+    hipLaunchKernelGGL(sk_ctl_owned_each_kernel<false>, dim3(n_wg), dim3(SK_CONTROL_SPAN), 0, stream, d_recs, d_each, sh, voice_mask, d_slots,
                        d_tags, owner, n, d_count, n_voices, p, mask_list, d_result, cnt, done, seq, sk_each_filt_t<false>());
   }
   return (int)hipGetLastError();

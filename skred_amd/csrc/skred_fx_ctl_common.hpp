@@ -1,6 +1,7 @@
 // skred_fx_ctl_common.hpp -- what the fixed-point bank's control kernels share (skred_fx_live_kernels.hip: sk_fx_stamp_list_kernel;
 // skred_fx_owner_kernels.hip: the guarded stamp; skred_fx_ctl_kernels.hip: the controllers; skred_fx_expr_kernels.hip: the masked
-// matches and the per-entry controller): the stamp's stores, the controller's stores, the list bound, the counting.
+// matches and the per-entry controller; skred_fx_pedal_kernels.hip: the pedals): the stamp's stores, the controller's stores, the list
+// bound, the counting, the launch grid.
 #ifndef SKRED_FX_CTL_COMMON_HPP
 #define SKRED_FX_CTL_COMMON_HPP
 
@@ -52,6 +53,10 @@ enum { SKX_C_PHASE_INC = 1u << 0, SKX_C_INC_SCALE = 1u << 1, SKX_C_AMP = 1u << 2
 struct skx_ctl_planes_t {
   skx_plane_t *osc, *gain, *env, *recip, *filt, *filt2;
 };
+
+// (host) workgroups of SKX_CTL_SPAN threads, one thread per voice or entry (the expression kernels' SKX_EXPR_SPAN is the same number:
+// skred_fx_expr_kernels.hip asserts it)
+static inline unsigned skx_grid(long long lanes) { return (unsigned)((lanes + SKX_CTL_SPAN - 1) / SKX_CTL_SPAN); }
 
 // (host) the planes a controller can store to, out of the bank's array
 static inline void skx_ctl_planes(skx_ctl_planes_t &p, skx_plane_t *const ro[SKX_COUNT]) {

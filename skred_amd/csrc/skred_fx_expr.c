@@ -38,7 +38,7 @@ _Static_assert(sizeof(skred_fx_filter_each_t) == sizeof(skx_filt_each_t) && size
 /* the float bank's count and scatter run on this bank's query scratch */
 _Static_assert((int)SKX_IDLE_W_TICKET == (int)SK_IDLE_W_TICKET && (int)SKX_IDLE_W_PART == (int)SK_IDLE_W_PART &&
                (int)SKX_IDLE_W_RANK == (int)SK_IDLE_W_RANK && (int)SKX_IDLE_W_TOTAL == (int)SK_IDLE_W_TOTAL &&
-               (int)SKX_IDLE_W_COUNT == (int)SK_IDLE_W_COUNT && SKX_IDLE_SPAN == SK_EXPR_SPAN,
+               (int)SKX_IDLE_W_COUNT == (int)SK_IDLE_W_COUNT && SKX_IDLE_SPAN == SK_CONTROL_SPAN,
                "the fixed-point query scratch must have the shape sk_launch_match_find needs");
 
 static int each_check(const skred_fx_ctl_each_t *each, int n, const skred_fx_ctl_t *ctl, const char *who) {
@@ -130,7 +130,7 @@ static int find_match_launch(skred_fxbank_t *fx, int first, int count, const skr
   if (rc) return rc;
   if ((rc = skx_idle_scratch(fx, s))) return rc;
   /* one lane per voice from `first`: (count + 255) / 256 workgroups, never more than a query of the whole bank takes */
-  if ((count + SK_EXPR_SPAN - 1) / SK_EXPR_SPAN > fx->idle_wgs) return fail(SKRED_E_RANGE, "fx find_match: scratch too small");   /* (unreachable) */
+  if ((count + SK_CONTROL_SPAN - 1) / SK_CONTROL_SPAN > fx->idle_wgs) return fail(SKRED_E_RANGE, "fx find_match: scratch too small");   /* (unreachable) */
   sk_match_args_t a;
   memset(&a, 0, sizeof(a));
   a.idle.words = fx->d_idle;

@@ -29,12 +29,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "skred_fx_ctl_common.hpp"   // skx_stamp_store, skx_ctl_store, skx_ctl_planes, skx_list_looked, skx_count
+#include "skred_fx_ctl_common.hpp"   // skx_stamp_store, skx_ctl_store, skx_ctl_planes, skx_list_looked, skx_count, skx_grid
 #include "skred_fx_layout.h"
+#include "skred_launch.h"            // sk_owner_matches
 
 static_assert(SKX_EXPR_SPAN == SKX_CTL_SPAN, "skx_count and the launch geometry are written for this span");
-
-__device__ __forceinline__ bool skx_owner_matches(uint32_t w, uint32_t value, uint32_t mask) { return w != 0u && (w & mask) == value; }
 
 // this lane's voice of the range (in v; inside the bank: checked on the host) matches
 __device__ __forceinline__ bool skx_match_hit(const uint32_t *__restrict__ owner, uint32_t value, uint32_t mask, int first, int count,
@@ -42,7 +41,7 @@ __device__ __forceinline__ bool skx_match_hit(const uint32_t *__restrict__ owner
   const int64_t off = (int64_t)blockIdx.x * SKX_EXPR_SPAN + threadIdx.x;
   in_range = off < count;
   v = first + (int)(in_range ? off : 0);
-  return in_range && skx_owner_matches(owner[v], value, mask);
+  return in_range && sk_owner_matches(owner[v], value, mask);
 }
 
 __global__ __launch_bounds__(SKX_EXPR_SPAN) void sk_fx_match_stamps_kernel(const uint32_t *__restrict__ owner, uint32_t value, uint32_t omask,
@@ -122,15 +121,13 @@ __global__ __launch_bounds__(SKX_EXPR_SPAN) void sk_fx_ctl_owned_each_kernel(con
   skx_count<3>(sums, d_result, val);
 }
 
-static unsigned skx_expr_grid(long long lanes) { return (unsigned)((lanes + SKX_EXPR_SPAN - 1) / SKX_EXPR_SPAN); }
-
 // d_result[2] (required) is zeroed on `stream` ahead of the kernel: voices stamped, voices of the range that did not match
 extern "C" int skx_launch_match_stamps(const uint32_t *owner, uint32_t value, uint32_t mask, int first, int count, uint32_t stamps,
                                        skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, uint32_t *d_result, hipStream_t stream) {
   if (count <= 0) return 0;
   const hipError_t e = hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_fx_match_stamps_kernel, dim3(skx_expr_grid(count)), dim3(SKX_EXPR_SPAN), 0, stream, owner, value, mask, first, count,
+  hipLaunchKernelGGL(sk_fx_match_stamps_kernel, dim3(skx_grid(count)), dim3(SKX_EXPR_SPAN), 0, stream, owner, value, mask, first, count,
                      stamps, time_plane, rw0, now, d_result);
   return (int)hipGetLastError();
 }
@@ -145,7 +142,7 @@ extern "C" int skx_launch_ctl_match(const skx_ctl_t *d_rec, int first, int count
   }
   skx_ctl_planes_t p;
   skx_ctl_planes(p, ro);
-  hipLaunchKernelGGL(sk_fx_ctl_match_kernel, dim3(skx_expr_grid(count)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, first, count, owner, value, mask,
+  hipLaunchKernelGGL(sk_fx_ctl_match_kernel, dim3(skx_grid(count)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, first, count, owner, value, mask,
                      p, d_result);
   return (int)hipGetLastError();
 }
@@ -168,10 +165,10 @@ extern "C" int skx_launch_ctl_owned_each_filter(const skx_ctl_t *d_rec, const sk
   if (d_filt) {
     skx_each_filt_t<true> fa;
     fa.filt = d_filt;
-    hipLaunchKernelGGL(sk_fx_ctl_owned_each_kernel<true>, dim3(skx_expr_grid(n)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, d_each, d_voices,
+    hipLaunchKernelGGL(sk_fx_ctl_owned_each_kernel<true>, dim3(skx_grid(n)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, d_each, d_voices,
                        d_tags, owner, n, d_count, n_voices, p, d_result, fa);
   } else {
-    hipLaunchKernelGGL(sk_fx_ctl_owned_each_kernel<false>, dim3(skx_expr_grid(n)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, d_each, d_voices,
+    hipLaunchKernelGGL(sk_fx_ctl_owned_each_kernel<false>, dim3(skx_grid(n)), dim3(SKX_EXPR_SPAN), 0, stream, d_rec, d_each, d_voices,
                        d_tags, owner, n, d_count, n_voices, p, d_result, skx_each_filt_t<false>());
   }
   return (int)hipGetLastError();

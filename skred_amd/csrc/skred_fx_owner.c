@@ -23,10 +23,8 @@ int skx_owner_ensure(skred_fxbank_t *fx) {
   if (fx->d_owner) return SKRED_OK;
   uint32_t *p = NULL;
   const size_t words = (size_t)fx->n_voices + SKRED_OWNER_MAX_TAGS + 2;   /* the owners, _release_tags' list, _find_match's pair */
-  HIP_TRY(hipMalloc((void **)&p, words * sizeof(uint32_t)));
-  hipError_t e = hipMemset(p, 0, words * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
-  if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "fx owner array -> %s", hipGetErrorString(e)); }
+  const int rc = sk_side_alloc((void **)&p, words * sizeof(uint32_t), "fx owner array");
+  if (rc) return rc;
   fx->d_owner = p;
   fx->d_owner_found = (int32_t *)(p + fx->n_voices);
   fx->d_match_pair = p + fx->n_voices + SKRED_OWNER_MAX_TAGS;
@@ -150,24 +148,12 @@ int skred_fxbank_release_tags(skred_fxbank_t *fx, int first, int count, const ui
 
 int skred_fxbank_owner_clear(skred_fxbank_t *fx, int first, int count, void *stream) {
   if (!fx) return fail(SKRED_E_BAD_ARG, "fx owner_clear: no bank");
-  const int rc = sk_check_window(fx->n_voices, first, count, "fx owner_clear");
-  if (rc) return rc;
-  if (count == 0 || !fx->d_owner) return SKRED_OK;      /* (never tagged: every word is 0 already) */
-  HIP_TRY(hipSetDevice(fx->device));
-  HIP_TRY(hipMemsetAsync(fx->d_owner + first, 0, (size_t)count * sizeof(uint32_t), (hipStream_t)stream));
-  return SKRED_OK;
+  return sk_side_clear(fx->d_owner, sizeof(uint32_t), fx->device, fx->n_voices, first, count, (hipStream_t)stream, "fx owner_clear");
 }
 
 int skred_fxbank_download_owners(skred_fxbank_t *fx, uint32_t *host_u32, int first, int count) {
   if (!fx || !host_u32 || count < 0) return fail(SKRED_E_BAD_ARG, "fx download_owners: bad arguments");
-  const int rc = sk_check_window(fx->n_voices, first, count, "fx download_owners");
-  if (rc) return rc;
-  if (count == 0) return SKRED_OK;
-  if (!fx->d_owner) { memset(host_u32, 0, (size_t)count * sizeof(uint32_t)); return SKRED_OK; }
-  HIP_TRY(hipSetDevice(fx->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host_u32, fx->d_owner + first, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return SKRED_OK;
+  return sk_side_download(fx->d_owner, sizeof(uint32_t), fx->device, fx->n_voices, host_u32, first, count, "fx download_owners");
 }
 
 int skred_fxbank_download_params(skred_fxbank_t *fx, skred_fxpt_bank_t *h, uint32_t *recip_out, int src_first, int dst_first, int count) {

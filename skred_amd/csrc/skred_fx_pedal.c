@@ -34,14 +34,7 @@ static int skx_pedal_ensure(skred_fxbank_t *fx) {
   if (fx->d_pedal) return SKRED_OK;
   const int rc = skx_owner_ensure(fx);
   if (rc) return rc;
-  uint32_t *p = NULL;
-  const size_t bytes = (size_t)fx->n_voices * sizeof(uint32_t);
-  HIP_TRY(hipMalloc((void **)&p, bytes));
-  hipError_t e = hipMemset(p, 0, bytes);
-  if (e == hipSuccess) e = hipDeviceSynchronize();       /* (whatever stream the first caller uses sees the zeros) */
-  if (e != hipSuccess) { (void)hipFree(p); return fail(SKRED_E_NO_DEVICE, "fx pedal array -> %s", hipGetErrorString(e)); }
-  fx->d_pedal = p;
-  return SKRED_OK;
+  return sk_side_alloc((void **)&fx->d_pedal, (size_t)fx->n_voices * sizeof(uint32_t), "fx pedal array");
 }
 
 void skx_pedal_free(skred_fxbank_t *fx) {
@@ -115,22 +108,10 @@ int skred_fxbank_pedal_up(skred_fxbank_t *fx, int first, int count, const skred_
 
 int skred_fxbank_pedal_clear(skred_fxbank_t *fx, int first, int count, void *stream) {
   if (!fx) return fail(SKRED_E_BAD_ARG, "fx pedal_clear: no bank");
-  const int rc = sk_check_window(fx->n_voices, first, count, "fx pedal_clear");
-  if (rc) return rc;
-  if (count == 0 || !fx->d_pedal) return SKRED_OK;       /* (no pedal call yet: every word is 0 already) */
-  HIP_TRY(hipSetDevice(fx->device));
-  HIP_TRY(hipMemsetAsync(fx->d_pedal + first, 0, (size_t)count * sizeof(uint32_t), (hipStream_t)stream));
-  return SKRED_OK;
+  return sk_side_clear(fx->d_pedal, sizeof(uint32_t), fx->device, fx->n_voices, first, count, (hipStream_t)stream, "fx pedal_clear");
 }
 
 int skred_fxbank_download_pedals(skred_fxbank_t *fx, uint32_t *host_u32, int first, int count) {
   if (!fx || !host_u32 || count < 0) return fail(SKRED_E_BAD_ARG, "fx download_pedals: bad arguments");
-  const int rc = sk_check_window(fx->n_voices, first, count, "fx download_pedals");
-  if (rc) return rc;
-  if (count == 0) return SKRED_OK;
-  if (!fx->d_pedal) { memset(host_u32, 0, (size_t)count * sizeof(uint32_t)); return SKRED_OK; }
-  HIP_TRY(hipSetDevice(fx->device));
-  HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host_u32, fx->d_pedal + first, (size_t)count * sizeof(uint32_t), hipMemcpyDeviceToHost));
-  return SKRED_OK;
+  return sk_side_download(fx->d_pedal, sizeof(uint32_t), fx->device, fx->n_voices, host_u32, first, count, "fx download_pedals");
 }

@@ -25,14 +25,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "skred_launch.h"
-#include "skred_fx_ctl_common.hpp"     // skx_stamp_store, skx_list_looked, skx_count
+#include "skred_launch.h"              // SK_PEDAL_*, sk_owner_matches
+#include "skred_fx_ctl_common.hpp"     // skx_stamp_store, skx_list_looked, skx_count, skx_grid
 #include "skred_fx_steal_common.hpp"   // skx_steal_held
 #include "skred_fx_layout.h"
 
 static_assert(SKX_CTL_SPAN == 256 && SKX_CTL_SPAN % 64 == 0, "skx_count and the launch geometry are written for this span");
-
-__device__ __forceinline__ bool skx_pedal_matches(uint32_t w, uint32_t value, uint32_t mask) { return w != 0u && (w & mask) == value; }
 
 __global__ __launch_bounds__(SKX_CTL_SPAN) void sk_fx_pedal_stamps_kernel(const uint32_t *__restrict__ owner, uint32_t *pedal,
                                                                           const int32_t *d_voices, const uint32_t *__restrict__ tags, int n,
@@ -67,7 +65,7 @@ __global__ __launch_bounds__(SKX_CTL_SPAN) void sk_fx_pedal_match_kernel(const u
   const int64_t off = (int64_t)blockIdx.x * SKX_CTL_SPAN + threadIdx.x;
   const bool in_range = off < count;
   const int v = first + (int)(in_range ? off : 0);                      // (inside the bank: checked on the host)
-  const bool hit = in_range && skx_pedal_matches(owner[v], value, omask);
+  const bool hit = in_range && sk_owner_matches(owner[v], value, omask);
   const uint32_t word = hit ? pedal[v] : 0u;
   if constexpr (UP) {
     uint32_t next = word;
@@ -88,15 +86,13 @@ __global__ __launch_bounds__(SKX_CTL_SPAN) void sk_fx_pedal_match_kernel(const u
   }
 }
 
-static unsigned skx_pedal_grid(long long lanes) { return (unsigned)((lanes + SKX_CTL_SPAN - 1) / SKX_CTL_SPAN); }
-
 extern "C" int skx_launch_pedal_stamps(const uint32_t *owner, uint32_t *pedal, const int32_t *d_voices, const uint32_t *d_tags, int n,
                                        const uint32_t *d_count, int n_voices, int hold_all, skx_plane_t *time_plane, skx_plane_t *rw0,
                                        uint64_t now, uint32_t *d_result, hipStream_t stream) {
   if (n <= 0) return 0;
   const hipError_t e = hipMemsetAsync(d_result, 0, 4 * sizeof(uint32_t), stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_fx_pedal_stamps_kernel, dim3(skx_pedal_grid(n)), dim3(SKX_CTL_SPAN), 0, stream, owner, pedal, d_voices, d_tags, n,
+  hipLaunchKernelGGL(sk_fx_pedal_stamps_kernel, dim3(skx_grid(n)), dim3(SKX_CTL_SPAN), 0, stream, owner, pedal, d_voices, d_tags, n,
                      d_count, n_voices, hold_all, time_plane, rw0, now, d_result);
   return (int)hipGetLastError();
 }
@@ -107,7 +103,7 @@ extern "C" int skx_launch_pedal_latch(const uint32_t *owner, uint32_t *pedal, ui
   if (count <= 0) return 0;
   const hipError_t e = hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_fx_pedal_match_kernel<false>, dim3(skx_pedal_grid(count)), dim3(SKX_CTL_SPAN), 0, stream, owner, pedal, value, mask,
+  hipLaunchKernelGGL(sk_fx_pedal_match_kernel<false>, dim3(skx_grid(count)), dim3(SKX_CTL_SPAN), 0, stream, owner, pedal, value, mask,
                      first, count, 0u, osc, time_plane, rw0, (uint64_t)0, d_result);
   return (int)hipGetLastError();
 }
@@ -118,7 +114,7 @@ extern "C" int skx_launch_pedal_up(const uint32_t *owner, uint32_t *pedal, uint3
   if (count <= 0) return 0;
   const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_fx_pedal_match_kernel<true>, dim3(skx_pedal_grid(count)), dim3(SKX_CTL_SPAN), 0, stream, owner, pedal, value, mask,
+  hipLaunchKernelGGL(sk_fx_pedal_match_kernel<true>, dim3(skx_grid(count)), dim3(SKX_CTL_SPAN), 0, stream, owner, pedal, value, mask,
                      first, count, flags, (const skx_plane_t *)nullptr, time_plane, rw0, now, d_result);
   return (int)hipGetLastError();
 }

@@ -137,6 +137,11 @@ int sk_check_window(int n_voices, int first, int count, const char *who);
  * behind `head` words in a grow-on-demand answer buffer (h_buf NULL: no pinned twin) */
 int sk_read_back(const int32_t *d_out, int32_t *h_out, int counts, int max_out, int bound, int32_t *out, hipStream_t s, const char *who);
 int sk_answer_room(void **d_buf, void **h_buf, size_t *cap, size_t head, size_t need);
+/* ... and the per-voice side arrays (owners, pedals): allocated and zeroed for every stream, a checked window cleared on a stream, a
+ * checked window downloaded (zeros when d_arr is NULL) */
+int sk_side_alloc(void **d_arr, size_t bytes, const char *what);
+int sk_side_clear(void *d_arr, size_t elem, int device, int n_voices, int first, int count, hipStream_t s, const char *who);
+int sk_side_download(const void *d_arr, size_t elem, int device, int n_voices, void *host, int first, int count, const char *who);
 
 /* skred_fx_kernels.hip, skred_fx_live_kernels.hip */
 int skx_launch_stamp(const int32_t *d_ids, int n, int which, skx_plane_t *time_plane, skx_plane_t *rw0, uint64_t now, hipStream_t stream);

@@ -25,7 +25,7 @@
 #include <stdint.h>
 
 #include "skred_launch.h"
-#include "skred_update_common.hpp"   // sk_slot_valid, sk_owner_count, sk_batch_done
+#include "skred_update_common.hpp"   // sk_entry_decode, sk_entry_owned, sk_owner_count, sk_batch_done, the launch helpers
 
 #define SK_GLIDE_ABS 0x7fffffffu
 
@@ -37,47 +37,31 @@ __device__ __forceinline__ uint32_t sk_glide_mul(uint32_t a, uint32_t b) {
 }
 __device__ __forceinline__ uint32_t *sk_glide_inc(sk_plane_t *osc, int v) { return &osc[v].w[0]; }
 
-__global__ __launch_bounds__(SK_GLIDE_SPAN) void sk_glide_clear_kernel(sk_glide_t *glide, const int32_t *d_slots, int n,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_glide_clear_kernel(sk_glide_t *glide, const int32_t *d_slots, int n,
                                                                        const uint32_t *d_count, int k_shift, int n_voices) {
-  const int K = 1 << k_shift;
-  const int64_t i = (int64_t)blockIdx.x * (SK_GLIDE_SPAN >> k_shift) + ((int)threadIdx.x >> k_shift);
-  const int l = (int)threadIdx.x & (K - 1);
-  bool looked = i < n;
-  if (looked && d_count && (uint64_t)i >= (uint64_t)d_count[0]) looked = false;
-  if (looked) {
-    const int e = d_slots[i];
-    if (sk_slot_valid(e, K, n_voices)) *reinterpret_cast<uint4 *>(&glide[e + l]) = make_uint4(0u, 0u, 0u, 0u);
-  }
+  const sk_entry_t t = sk_entry_decode(SK_CONTROL_SPAN, k_shift, d_slots, n, d_count, n_voices);
+  if (t.valid) *reinterpret_cast<uint4 *>(&glide[t.e + t.l]) = make_uint4(0u, 0u, 0u, 0u);
 }
 
-__global__ __launch_bounds__(SK_GLIDE_SPAN) void sk_glide_start_kernel(sk_glide_t *glide, const sk_glide_each_t *__restrict__ each,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_glide_start_kernel(sk_glide_t *glide, const sk_glide_each_t *__restrict__ each,
                                                                        int k_shift, uint64_t voice_mask, const int32_t *d_slots,
                                                                        const uint32_t *__restrict__ tags,
                                                                        const uint32_t *__restrict__ owner, int n, const uint32_t *d_count,
                                                                        int n_voices, sk_plane_t *osc, uint32_t *d_result, uint32_t *cnt,
                                                                        uint32_t *done, uint32_t seq) {
-  __shared__ uint4 ent[SK_GLIDE_SPAN];                                  // set, rate_up, rate_down, scale of this workgroup's entries
+  __shared__ uint4 ent[SK_CONTROL_SPAN];                                  // set, rate_up, rate_down, scale of this workgroup's entries
   __shared__ uint32_t sums[3];
-  const int K = 1 << k_shift, per_wg = SK_GLIDE_SPAN >> k_shift;
+  const int per_wg = SK_CONTROL_SPAN >> k_shift;
   const int64_t base = (int64_t)blockIdx.x * per_wg;
   if ((int)threadIdx.x < per_wg && base + (int)threadIdx.x < n)
     ent[threadIdx.x] = *reinterpret_cast<const uint4 *>(&each[base + (int)threadIdx.x].w[0]);
   __syncthreads();
-  const int j = (int)threadIdx.x >> k_shift, l = (int)threadIdx.x & (K - 1);
-  const int64_t i = base + j;
-  bool looked = i < n;
-  if (looked && d_count && (uint64_t)i >= (uint64_t)d_count[0]) looked = false;
-  int e = 0;
-  bool valid = false, owned = false;
-  if (looked) {
-    e = d_slots[i];
-    valid = sk_slot_valid(e, K, n_voices);
-    if (valid) owned = owner[e] == tags[i];                             // (tags are non-zero: an untagged slot never matches)
-  }
+  const sk_entry_t t = sk_entry_decode(SK_CONTROL_SPAN, k_shift, d_slots, n, d_count, n_voices);   // (t.i == base + the entry's place)
+  const bool owned = sk_entry_owned(owner, tags, t);
   bool started = false, withheld = false;
-  if (owned && ((voice_mask >> l) & 1)) {
-    const int v = e + l;
-    const uint4 g = ent[j];
+  if (owned && ((voice_mask >> t.l) & 1)) {
+    const int v = t.e + t.l;
+    const uint4 g = ent[(int)threadIdx.x >> k_shift];
     const uint32_t inc = *sk_glide_inc(osc, v);
     uint32_t target, next = inc;
     if (g.x & SK_GLIDE_FROM_SCALE) {
@@ -95,15 +79,15 @@ __global__ __launch_bounds__(SK_GLIDE_SPAN) void sk_glide_start_kernel(sk_glide_
       withheld = true;
     }
   }
-  const bool flag[3] = { started, withheld, valid && !owned && l == 0 };
+  const bool flag[3] = { started, withheld, t.valid && !owned && t.l == 0 };
   sk_owner_count<3>(sums, d_result, flag);
   sk_batch_done(cnt, done, seq);
 }
 
-__global__ __launch_bounds__(SK_GLIDE_SPAN) void sk_glide_advance_kernel(sk_glide_t *glide, sk_plane_t *osc, int first, int count,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_glide_advance_kernel(sk_glide_t *glide, sk_plane_t *osc, int first, int count,
                                                                          uint32_t frames, uint32_t *d_result) {
   __shared__ uint32_t sums[2];
-  const int64_t off = (int64_t)blockIdx.x * SK_GLIDE_SPAN + threadIdx.x;
+  const int64_t off = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
   bool still = false, arrived = false;
   if (off < count) {
     const int v = first + (int)off;
@@ -140,8 +124,8 @@ __global__ __launch_bounds__(SK_GLIDE_SPAN) void sk_glide_advance_kernel(sk_glid
   sk_owner_count<2>(sums, d_result, flag);
 }
 
-__global__ __launch_bounds__(SK_GLIDE_SPAN) void sk_glide_stop_kernel(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int snap) {
-  const int64_t off = (int64_t)blockIdx.x * SK_GLIDE_SPAN + threadIdx.x;
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_glide_stop_kernel(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int snap) {
+  const int64_t off = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
   if (off >= count) return;
   const int v = first + (int)off;
   const uint4 g = *reinterpret_cast<const uint4 *>(&glide[v]);
@@ -150,25 +134,11 @@ __global__ __launch_bounds__(SK_GLIDE_SPAN) void sk_glide_stop_kernel(sk_glide_t
   *reinterpret_cast<uint4 *>(&glide[v]) = make_uint4(0u, 0u, 0u, 0u);
 }
 
-static int sk_glide_shift(int slot_voices) {
-  int sh = 0;
-  while ((1 << sh) < slot_voices) ++sh;
-  return sh;
-}
-
-static unsigned sk_glide_grid(long long lanes) { return (unsigned)((lanes + SK_GLIDE_SPAN - 1) / SK_GLIDE_SPAN); }
-
-// one thread per entry and voice of its slot: SK_GLIDE_SPAN >> shift entries per workgroup
-static unsigned sk_glide_list_grid(int n, int sh) {
-  const int per_wg = SK_GLIDE_SPAN >> sh;
-  return (unsigned)(((long long)n + per_wg - 1) / per_wg);
-}
-
 extern "C" int sk_launch_glide_clear(sk_glide_t *glide, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices,
                                      int n_voices, hipStream_t stream) {
   if (n <= 0) return 0;
-  const int sh = sk_glide_shift(slot_voices);
-  hipLaunchKernelGGL(sk_glide_clear_kernel, dim3(sk_glide_list_grid(n, sh)), dim3(SK_GLIDE_SPAN), 0, stream, glide, d_slots, n, d_count, sh,
+  const int sh = sk_slot_shift(slot_voices);
+  hipLaunchKernelGGL(sk_glide_clear_kernel, dim3(sk_list_grid(n, sh)), dim3(SK_CONTROL_SPAN), 0, stream, glide, d_slots, n, d_count, sh,
                      n_voices);
   return (int)hipGetLastError();
 }
@@ -178,12 +148,10 @@ extern "C" int sk_launch_glide_start(sk_glide_t *glide, const sk_glide_each_t *d
                                      int n_voices, sk_plane_t *osc, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq,
                                      hipStream_t stream) {
   if (n <= 0) return 0;
-  if (d_result) {
-    const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int sh = sk_glide_shift(slot_voices);
-  hipLaunchKernelGGL(sk_glide_start_kernel, dim3(sk_glide_list_grid(n, sh)), dim3(SK_GLIDE_SPAN), 0, stream, glide, d_each, sh, voice_mask,
+  const hipError_t e = sk_result_clear(d_result, 3, stream);
+  if (e != hipSuccess) return (int)e;
+  const int sh = sk_slot_shift(slot_voices);
+  hipLaunchKernelGGL(sk_glide_start_kernel, dim3(sk_list_grid(n, sh)), dim3(SK_CONTROL_SPAN), 0, stream, glide, d_each, sh, voice_mask,
                      d_slots, d_tags, owner, n, d_count, n_voices, osc, d_result, cnt, done, seq);
   return (int)hipGetLastError();
 }
@@ -191,17 +159,15 @@ extern "C" int sk_launch_glide_start(sk_glide_t *glide, const sk_glide_each_t *d
 extern "C" int sk_launch_glide_advance(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int num_frames, uint32_t *d_result,
                                        hipStream_t stream) {
   if (count <= 0) return 0;
-  if (d_result) {
-    const hipError_t e = hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(sk_glide_advance_kernel, dim3(sk_glide_grid(count)), dim3(SK_GLIDE_SPAN), 0, stream, glide, osc, first, count,
+  const hipError_t e = sk_result_clear(d_result, 2, stream);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(sk_glide_advance_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, glide, osc, first, count,
                      (uint32_t)num_frames, d_result);
   return (int)hipGetLastError();
 }
 
 extern "C" int sk_launch_glide_stop(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int snap, hipStream_t stream) {
   if (count <= 0) return 0;
-  hipLaunchKernelGGL(sk_glide_stop_kernel, dim3(sk_glide_grid(count)), dim3(SK_GLIDE_SPAN), 0, stream, glide, osc, first, count, snap);
+  hipLaunchKernelGGL(sk_glide_stop_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, glide, osc, first, count, snap);
   return (int)hipGetLastError();
 }

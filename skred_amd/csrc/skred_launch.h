@@ -229,6 +229,9 @@ int sk_launch_slot_notes(const sk_note_t *d_notes, int n, int slot_voices, uint6
                          const uint32_t *d_count, int first_entry, int n_voices, sk_plane_t *const ro[SKP_COUNT],
                          sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask, int32_t *d_assigned, uint32_t *d_result,
                          uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* threads per workgroup of every control kernel below that takes a slot list or a range of slots: the stamps on listed slots, the
+ * controllers, the owner, expression, pedal and glide kernels (skred_update_common.hpp: sk_entry_decode, sk_range_lane, sk_grid) */
+#define SK_CONTROL_SPAN 256
 /* sk_launch_stamp_list on the masked voices of the first min(n, d_count[0]) listed slots (d_count NULL: n); entries that are no
  * slot of the bank are skipped */
 int sk_launch_slot_stamps(const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, uint64_t voice_mask, int n_voices,
@@ -290,7 +293,6 @@ int sk_launch_ctl_slots(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_
  * owner[n_voices]: one word per voice, a slot's owner at its first voice, 0 nobody.  Only these launches read or write it.
  * d_tags and the other staged arrays may be the pinned staging buffer; cnt / done / seq as for sk_launch_update. */
 #define SK_OWNER_MAX_TAGS 1024
-#define SK_OWNER_SPAN 256          /* threads per workgroup of the owner kernels */
 /* owner[d_slots[k]] = d_tags[k] for the first min(n, d_count[0]) entries (d_count NULL: n) that are slots of the bank; d_result[2]
  * (or NULL; zeroed on `stream` ahead of the kernel) += slots tagged, entries that are no slot */
 int sk_launch_owner_tag(uint32_t *owner, const int32_t *d_slots, const uint32_t *d_tags, int n, const uint32_t *d_count, int slot_voices,
@@ -316,7 +318,6 @@ int sk_launch_ctl_owned(const sk_ctl_t *d_recs, int slot_voices, uint64_t voice_
 /* ---- channels and per-note expression (skred_bank_expr.c -> skred_expr_kernels.hip; include/skred_amd.h: skred_bank_find_match /
  * _stamp_match / _ctl_match / _ctl_owned_each / _ctl_tags_each) ----
  * A slot matches when owner != 0 && (owner & mask) == value.  The ranges are whole slots inside the bank (checked on the host). */
-#define SK_EXPR_SPAN 256           /* threads per workgroup of the expression kernels */
 /* the ordered list of the matching slots: one lane per SLOT, skred_idle_scan.hpp's count and scatter.  `idle` holds the bank's idle
  * scratch (words, counts, offsets), d_voices (the list), max_out, and d_count = two scratch words the count pass fills as it does
  * for an idle query; first / end / from / base / from_wg are set by the launcher.  d_total[0] = the total, written by the second
@@ -375,7 +376,6 @@ int sk_launch_ctl_owned_each_filter(const sk_ctl_t *d_recs, const sk_each_t *d_e
 #define SK_PEDAL_LIFT_SUSTAIN   (1u << 0)
 #define SK_PEDAL_LIFT_SOSTENUTO (1u << 1)
 #define SK_PEDAL_SUSTAIN_DOWN   (1u << 2)
-#define SK_PEDAL_SPAN 256          /* threads per workgroup of the pedal kernels */
 /* pedal[d_slots[k]] = 0 under sk_launch_owner_tag's list rule: launched behind it by a bank that has a pedal array */
 int sk_launch_pedal_clear(uint32_t *pedal, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
                           hipStream_t stream);
@@ -414,7 +414,6 @@ enum { SK_GLIDE_E_SET = 0, SK_GLIDE_E_RATE_UP, SK_GLIDE_E_RATE_DOWN, SK_GLIDE_E_
 typedef struct {
   uint32_t w[SK_GLIDE_E_WORDS];
 } sk_glide_each_t;
-#define SK_GLIDE_SPAN 256          /* threads per workgroup of the glide kernels */
 /* glide[d_slots[k] + l] = 0, l < slot_voices, under sk_launch_owner_tag's list rule: launched behind it by a bank that has a glide
  * array */
 int sk_launch_glide_clear(sk_glide_t *glide, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
@@ -456,5 +455,11 @@ int sk_launch_rec_convert(const float *rec, long frames, int n_voices, const int
 
 #ifdef __cplusplus
 }
+#endif
+
+#ifdef __HIPCC__
+/* an owner word w MATCHES (value, mask): somebody owns the slot, and the masked tag is the one asked for -- both banks' masked
+ * matches (channels, pedals) */
+__device__ __forceinline__ bool sk_owner_matches(uint32_t w, uint32_t value, uint32_t mask) { return w != 0u && (w & mask) == value; }
 #endif
 #endif

@@ -63,16 +63,10 @@ __global__ __launch_bounds__(SK_NOTE_SPAN) void sk_notes_kernel(const sk_note_t 
 __global__ __launch_bounds__(256) void sk_stamp_list_kernel(const int32_t *d_voices, int n, const uint32_t *d_count, int n_voices,
                                                             uint32_t dirty, sk_plane_ptrs_t p, uint64_t now, uint64_t *mask) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  if (d_count && (uint32_t)i >= d_count[0]) return;
+  if (!sk_list_looked(i, n, d_count)) return;
   const int v = d_voices[i];
   if (v < 0 || v >= n_voices) return;
   sk_stamp_store(p, now, mask, v, dirty);
-}
-
-static void sk_note_planes(sk_plane_ptrs_t &p, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT]) {
-  for (int k = 0; k < SKP_COUNT; ++k) p.ro[k] = ro[k];
-  for (int k = 0; k < SKS_COUNT; ++k) p.rw[k] = rw[k];
 }
 
 extern "C" int sk_launch_notes(const sk_note_t *d_notes, int n, const int32_t *d_voices, const uint32_t *d_count, int first_entry,
@@ -81,7 +75,7 @@ extern "C" int sk_launch_notes(const sk_note_t *d_notes, int n, const int32_t *d
                                uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
   sk_plane_ptrs_t p;
-  sk_note_planes(p, ro, rw);
+  sk_planes(p, ro, rw);
   const unsigned n_wg = (unsigned)((n + SK_NOTE_SPAN - 1) / SK_NOTE_SPAN);
   if (n_wg > 1) {
     const hipError_t e = hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), stream);
@@ -97,7 +91,7 @@ extern "C" int sk_launch_stamp_list(const int32_t *d_voices, int n, const uint32
                                     hipStream_t stream) {
   if (n <= 0) return 0;
   sk_plane_ptrs_t p;
-  sk_note_planes(p, ro, rw);
+  sk_planes(p, ro, rw);
   hipLaunchKernelGGL(sk_stamp_list_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_voices, n, d_count, n_voices,
                      dirty, p, now, mask);
   return (int)hipGetLastError();

@@ -23,16 +23,15 @@
 #include <stdint.h>
 
 #include "skred_launch.h"
-#include "skred_update_common.hpp"   // sk_plane_ptrs_t, sk_stamp_store, sk_slot_valid, sk_owner_count, sk_batch_done
+#include "skred_update_common.hpp"   // the list rule, sk_entry_decode, sk_entry_owned, sk_stamp_store, sk_owner_count, sk_batch_done
 
-__global__ __launch_bounds__(SK_OWNER_SPAN) void sk_owner_tag_kernel(uint32_t *owner, const int32_t *d_slots,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_owner_tag_kernel(uint32_t *owner, const int32_t *d_slots,
                                                                      const uint32_t *__restrict__ tags, int n, const uint32_t *d_count,
                                                                      int K, int n_voices, uint32_t *d_result, uint32_t *cnt,
                                                                      uint32_t *done, uint32_t seq) {
   __shared__ uint32_t sums[2];
-  const int64_t i = (int64_t)blockIdx.x * SK_OWNER_SPAN + threadIdx.x;
-  bool looked = i < n;
-  if (looked && d_count && (uint64_t)i >= (uint64_t)d_count[0]) looked = false;
+  const int64_t i = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
+  const bool looked = sk_list_looked(i, n, d_count);
   bool valid = false;
   if (looked) {
     const int e = d_slots[i];
@@ -44,17 +43,17 @@ __global__ __launch_bounds__(SK_OWNER_SPAN) void sk_owner_tag_kernel(uint32_t *o
   sk_batch_done(cnt, done, seq);
 }
 
-__global__ __launch_bounds__(SK_OWNER_SPAN) void sk_owner_find_kernel(const uint32_t *__restrict__ owner, int first, int n_slots,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_owner_find_kernel(const uint32_t *__restrict__ owner, int first, int n_slots,
                                                                       int k_shift, const uint32_t *__restrict__ sorted,
                                                                       const uint32_t *__restrict__ perm, int n, int padded,
                                                                       uint32_t *d_out, uint32_t *cnt, uint32_t *done, uint32_t seq) {
   __shared__ uint32_t lds_tag[SK_OWNER_MAX_TAGS];
   __shared__ uint32_t lds_perm[SK_OWNER_MAX_TAGS];
-  const int64_t s = (int64_t)blockIdx.x * SK_OWNER_SPAN + threadIdx.x;
+  const int64_t s = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
   const int v = first + (int)((s < n_slots ? s : 0) << k_shift);        // (inside the bank: checked on the host)
   const uint32_t w = s < n_slots ? owner[v] : 0u;
   if (__syncthreads_or(w != 0u)) {                                      // (uniform over the workgroup)
-    for (int i = threadIdx.x; i < padded; i += SK_OWNER_SPAN) {
+    for (int i = threadIdx.x; i < padded; i += SK_CONTROL_SPAN) {
       lds_tag[i] = i < n ? sorted[i] : 0xFFFFFFFFu;
       lds_perm[i] = i < n ? perm[i] : 0u;
     }
@@ -69,47 +68,28 @@ __global__ __launch_bounds__(SK_OWNER_SPAN) void sk_owner_find_kernel(const uint
   sk_batch_done(cnt, done, seq);
 }
 
-__global__ __launch_bounds__(SK_OWNER_SPAN) void sk_owner_stamps_kernel(const uint32_t *__restrict__ owner, const int32_t *d_slots,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_owner_stamps_kernel(const uint32_t *__restrict__ owner, const int32_t *d_slots,
                                                                         const uint32_t *__restrict__ tags, int n, const uint32_t *d_count,
                                                                         int k_shift, uint64_t voice_mask, int n_voices, uint32_t dirty,
                                                                         sk_plane_ptrs_t p, uint64_t now, uint64_t *mask,
                                                                         uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq) {
   __shared__ uint32_t sums[3];
-  const int K = 1 << k_shift;
-  const int64_t i = (int64_t)blockIdx.x * (SK_OWNER_SPAN >> k_shift) + ((int)threadIdx.x >> k_shift);
-  const int l = (int)threadIdx.x & (K - 1);
-  bool looked = i < n;
-  if (looked && d_count && (uint64_t)i >= (uint64_t)d_count[0]) looked = false;
-  bool valid = false, mine = false;
-  int e = 0;
-  if (looked) {
-    e = d_slots[i];
-    valid = sk_slot_valid(e, K, n_voices);
-    if (valid) mine = owner[e] == tags[i];                              // (tags are non-zero: an untagged slot never matches)
-  }
-  if (mine && ((voice_mask >> l) & 1)) sk_stamp_store(p, now, mask, e + l, dirty);
-  const bool head = looked && l == 0;                                   // one thread per entry counts it
-  const bool flag[3] = { head && mine, head && valid && !mine, head && !valid };
+  const sk_entry_t t = sk_entry_decode(SK_CONTROL_SPAN, k_shift, d_slots, n, d_count, n_voices);
+  const bool mine = sk_entry_owned(owner, tags, t);
+  if (mine && ((voice_mask >> t.l) & 1)) sk_stamp_store(p, now, mask, t.e + t.l, dirty);
+  const bool head = t.looked && t.l == 0;                               // one thread per entry counts it
+  const bool flag[3] = { head && mine, head && t.valid && !mine, head && !t.valid };
   sk_owner_count<3>(sums, d_result, flag);
   sk_batch_done(cnt, done, seq);
-}
-
-static int sk_owner_shift(int slot_voices) {
-  int sh = 0;
-  while ((1 << sh) < slot_voices) ++sh;
-  return sh;
 }
 
 extern "C" int sk_launch_owner_tag(uint32_t *owner, const int32_t *d_slots, const uint32_t *d_tags, int n, const uint32_t *d_count,
                                    int slot_voices, int n_voices, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq,
                                    hipStream_t stream) {
   if (n <= 0) return 0;
-  if (d_result) {
-    const hipError_t e = hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  const unsigned n_wg = (unsigned)(((long long)n + SK_OWNER_SPAN - 1) / SK_OWNER_SPAN);
-  hipLaunchKernelGGL(sk_owner_tag_kernel, dim3(n_wg), dim3(SK_OWNER_SPAN), 0, stream, owner, d_slots, d_tags, n, d_count, slot_voices,
+  const hipError_t e = sk_result_clear(d_result, 2, stream);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(sk_owner_tag_kernel, dim3(sk_grid(n)), dim3(SK_CONTROL_SPAN), 0, stream, owner, d_slots, d_tags, n, d_count, slot_voices,
                      n_voices, d_result, cnt, done, seq);
   return (int)hipGetLastError();
 }
@@ -120,11 +100,10 @@ extern "C" int sk_launch_owner_find(const uint32_t *owner, int first, int count,
   if (n <= 0 || n > SK_OWNER_MAX_TAGS || count <= 0) return 0;
   const hipError_t e = hipMemsetAsync(d_out, 0xFF, (size_t)n * sizeof(int32_t), stream);
   if (e != hipSuccess) return (int)e;
-  const int sh = sk_owner_shift(slot_voices), n_slots = count >> sh;
+  const int sh = sk_slot_shift(slot_voices), n_slots = count >> sh;
   int padded = 1;
   while (padded < n) padded <<= 1;
-  const unsigned n_wg = (unsigned)(((long long)n_slots + SK_OWNER_SPAN - 1) / SK_OWNER_SPAN);
-  hipLaunchKernelGGL(sk_owner_find_kernel, dim3(n_wg), dim3(SK_OWNER_SPAN), 0, stream, owner, first, n_slots, sh, d_sorted, d_perm, n,
+  hipLaunchKernelGGL(sk_owner_find_kernel, dim3(sk_grid(n_slots)), dim3(SK_CONTROL_SPAN), 0, stream, owner, first, n_slots, sh, d_sorted, d_perm, n,
                      padded, reinterpret_cast<uint32_t *>(d_out), cnt, done, seq);
   return (int)hipGetLastError();
 }
@@ -134,14 +113,12 @@ extern "C" int sk_launch_owner_stamps(const uint32_t *owner, const int32_t *d_sl
                                       sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask, uint32_t *d_result, uint32_t *cnt,
                                       uint32_t *done, uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
-  const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
+  const hipError_t e = sk_result_clear(d_result, 3, stream);
   if (e != hipSuccess) return (int)e;
   sk_plane_ptrs_t p;
-  for (int k = 0; k < SKP_COUNT; ++k) p.ro[k] = ro[k];
-  for (int k = 0; k < SKS_COUNT; ++k) p.rw[k] = rw[k];
-  const int sh = sk_owner_shift(slot_voices), per_wg = SK_OWNER_SPAN >> sh;
-  const unsigned n_wg = (unsigned)(((long long)n + per_wg - 1) / per_wg);
-  hipLaunchKernelGGL(sk_owner_stamps_kernel, dim3(n_wg), dim3(SK_OWNER_SPAN), 0, stream, owner, d_slots, d_tags, n, d_count, sh,
+  sk_planes(p, ro, rw);
+  const int sh = sk_slot_shift(slot_voices);
+  hipLaunchKernelGGL(sk_owner_stamps_kernel, dim3(sk_list_grid(n, sh)), dim3(SK_CONTROL_SPAN), 0, stream, owner, d_slots, d_tags, n, d_count, sh,
                      voice_mask, n_voices, dirty, p, now, mask, d_result, cnt, done, seq);
   return (int)hipGetLastError();
 }

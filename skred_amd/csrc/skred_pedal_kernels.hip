@@ -31,46 +31,32 @@
 
 #include "skred_launch.h"
 #include "skred_steal_common.hpp"    // sk_steal_live, sk_steal_clocks
-#include "skred_update_common.hpp"   // sk_plane_ptrs_t, sk_stamp_store, sk_slot_valid, sk_owner_count, sk_batch_done
+#include "skred_update_common.hpp"   // the list rule, sk_entry_decode, sk_entry_owned, sk_range_lane, sk_stamp_store, sk_owner_count, sk_batch_done
 
-__device__ __forceinline__ bool sk_pedal_matches(uint32_t w, uint32_t value, uint32_t mask) { return w != 0u && (w & mask) == value; }
-
-__global__ __launch_bounds__(SK_PEDAL_SPAN) void sk_pedal_clear_kernel(uint32_t *pedal, const int32_t *d_slots, int n,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_pedal_clear_kernel(uint32_t *pedal, const int32_t *d_slots, int n,
                                                                        const uint32_t *d_count, int K, int n_voices) {
-  const int64_t i = (int64_t)blockIdx.x * SK_PEDAL_SPAN + threadIdx.x;
-  bool looked = i < n;
-  if (looked && d_count && (uint64_t)i >= (uint64_t)d_count[0]) looked = false;
-  if (looked) {
+  const int64_t i = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
+  if (sk_list_looked(i, n, d_count)) {
     const int e = d_slots[i];
     if (sk_slot_valid(e, K, n_voices)) pedal[e] = 0u;
   }
 }
 
-__global__ __launch_bounds__(SK_PEDAL_SPAN) void sk_pedal_stamps_kernel(const uint32_t *__restrict__ owner, uint32_t *pedal,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_pedal_stamps_kernel(const uint32_t *__restrict__ owner, uint32_t *pedal,
                                                                         const int32_t *d_slots, const uint32_t *__restrict__ tags, int n,
                                                                         const uint32_t *d_count, int k_shift, uint64_t voice_mask,
                                                                         int n_voices, int hold_all, sk_plane_ptrs_t p, uint64_t now,
                                                                         uint64_t *mask, uint32_t *d_result, uint32_t *cnt, uint32_t *done,
                                                                         uint32_t seq) {
   __shared__ uint32_t sums[4];
-  const int K = 1 << k_shift;
-  const int64_t i = (int64_t)blockIdx.x * (SK_PEDAL_SPAN >> k_shift) + ((int)threadIdx.x >> k_shift);
-  const int l = (int)threadIdx.x & (K - 1);
-  bool looked = i < n;
-  if (looked && d_count && (uint64_t)i >= (uint64_t)d_count[0]) looked = false;
-  bool valid = false, mine = false;
-  int e = 0;
-  if (looked) {
-    e = d_slots[i];
-    valid = sk_slot_valid(e, K, n_voices);
-    if (valid) mine = owner[e] == tags[i];                              // (tags are non-zero: an untagged slot never matches)
-  }
-  const uint32_t word = mine ? pedal[e] : 0u;
+  const sk_entry_t t = sk_entry_decode(SK_CONTROL_SPAN, k_shift, d_slots, n, d_count, n_voices);
+  const bool mine = sk_entry_owned(owner, tags, t);
+  const uint32_t word = mine ? pedal[t.e] : 0u;
   const bool hold = mine && (hold_all != 0 || (word & SK_PEDAL_LATCHED));
-  if (mine && !hold && ((voice_mask >> l) & 1)) sk_stamp_store(p, now, mask, e + l, SKU_STAMP_RELEASE);
-  if (hold && l == 0 && !(word & SK_PEDAL_PENDING)) pedal[e] = word | SK_PEDAL_PENDING;
-  const bool head = looked && l == 0;                                   // one thread per entry counts it
-  const bool flag[4] = { head && mine && !hold, head && valid && !mine, head && !valid, head && hold };
+  if (mine && !hold && ((voice_mask >> t.l) & 1)) sk_stamp_store(p, now, mask, t.e + t.l, SKU_STAMP_RELEASE);
+  if (hold && t.l == 0 && !(word & SK_PEDAL_PENDING)) pedal[t.e] = word | SK_PEDAL_PENDING;
+  const bool head = t.looked && t.l == 0;                               // one thread per entry counts it
+  const bool flag[4] = { head && mine && !hold, head && t.valid && !mine, head && !t.valid, head && hold };
   sk_owner_count<4>(sums, d_result, flag);
   sk_batch_done(cnt, done, seq);
 }
@@ -83,19 +69,18 @@ __device__ __forceinline__ void sk_pedal_view(sk_steal_args_t &a, const sk_plane
 }
 
 template <bool UP>
-__global__ __launch_bounds__(SK_PEDAL_SPAN) void sk_pedal_match_kernel(const uint32_t *__restrict__ owner, uint32_t *pedal, uint32_t value,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_pedal_match_kernel(const uint32_t *__restrict__ owner, uint32_t *pedal, uint32_t value,
                                                                        uint32_t omask, int first, int count, int K, uint64_t voice_mask,
                                                                        uint32_t flags, sk_plane_ptrs_t p, uint64_t now, uint64_t *mask,
                                                                        uint32_t *d_result) {
   __shared__ uint32_t sums[UP ? 3 : 2];
-  const int64_t off = (int64_t)blockIdx.x * SK_PEDAL_SPAN + threadIdx.x;
-  const bool in_range = off < count;
-  const int v = first + (int)(in_range ? off : 0), l = v & (K - 1);     // (first is a multiple of K)
+  const sk_lane_t t = sk_range_lane(first, count, K);                  // (head: counts the slot and stores its word)
+  const int v = t.v, l = t.l;
+  const bool head = t.head;
   const int lane = (int)threadIdx.x & 63;                               // (lane - l: the lane of the slot's first voice)
-  const bool hit = in_range && sk_pedal_matches(owner[v - l], value, omask);
+  const bool hit = t.in_range && sk_owner_matches(owner[v - l], value, omask);
   const uint32_t word = hit ? pedal[v - l] : 0u;
   const bool masked = (voice_mask >> l) & 1;
-  const bool head = in_range && l == 0;                                 // one thread per slot counts it and stores its word
   if constexpr (UP) {
     uint32_t next = word;
     if (flags & SK_PEDAL_LIFT_SOSTENUTO) next &= ~SK_PEDAL_LATCHED;
@@ -126,23 +111,10 @@ __global__ __launch_bounds__(SK_PEDAL_SPAN) void sk_pedal_match_kernel(const uin
   }
 }
 
-static void sk_pedal_planes(sk_plane_ptrs_t &p, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT]) {
-  for (int k = 0; k < SKP_COUNT; ++k) p.ro[k] = ro[k];
-  for (int k = 0; k < SKS_COUNT; ++k) p.rw[k] = rw[k];
-}
-
-static int sk_pedal_shift(int slot_voices) {
-  int sh = 0;
-  while ((1 << sh) < slot_voices) ++sh;
-  return sh;
-}
-
-static unsigned sk_pedal_grid(long long lanes) { return (unsigned)((lanes + SK_PEDAL_SPAN - 1) / SK_PEDAL_SPAN); }
-
 extern "C" int sk_launch_pedal_clear(uint32_t *pedal, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
                                      hipStream_t stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(sk_pedal_clear_kernel, dim3(sk_pedal_grid(n)), dim3(SK_PEDAL_SPAN), 0, stream, pedal, d_slots, n, d_count, slot_voices,
+  hipLaunchKernelGGL(sk_pedal_clear_kernel, dim3(sk_grid(n)), dim3(SK_CONTROL_SPAN), 0, stream, pedal, d_slots, n, d_count, slot_voices,
                      n_voices);
   return (int)hipGetLastError();
 }
@@ -152,13 +124,12 @@ extern "C" int sk_launch_pedal_stamps(const uint32_t *owner, uint32_t *pedal, co
                                       sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask,
                                       uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
-  const hipError_t e = hipMemsetAsync(d_result, 0, 4 * sizeof(uint32_t), stream);
+  const hipError_t e = sk_result_clear(d_result, 4, stream);
   if (e != hipSuccess) return (int)e;
   sk_plane_ptrs_t p;
-  sk_pedal_planes(p, ro, rw);
-  const int sh = sk_pedal_shift(slot_voices), per_wg = SK_PEDAL_SPAN >> sh;
-  const unsigned n_wg = (unsigned)(((long long)n + per_wg - 1) / per_wg);
-  hipLaunchKernelGGL(sk_pedal_stamps_kernel, dim3(n_wg), dim3(SK_PEDAL_SPAN), 0, stream, owner, pedal, d_slots, d_tags, n, d_count, sh,
+  sk_planes(p, ro, rw);
+  const int sh = sk_slot_shift(slot_voices);
+  hipLaunchKernelGGL(sk_pedal_stamps_kernel, dim3(sk_list_grid(n, sh)), dim3(SK_CONTROL_SPAN), 0, stream, owner, pedal, d_slots, d_tags, n, d_count, sh,
                      voice_mask, n_voices, hold_all, p, now, mask, d_result, cnt, done, seq);
   return (int)hipGetLastError();
 }
@@ -167,11 +138,11 @@ extern "C" int sk_launch_pedal_latch(const uint32_t *owner, uint32_t *pedal, uin
                                      int slot_voices, uint64_t voice_mask, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT],
                                      uint32_t *d_result, hipStream_t stream) {
   if (count <= 0) return 0;
-  const hipError_t e = hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), stream);
+  const hipError_t e = sk_result_clear(d_result, 2, stream);
   if (e != hipSuccess) return (int)e;
   sk_plane_ptrs_t p;
-  sk_pedal_planes(p, ro, rw);
-  hipLaunchKernelGGL(sk_pedal_match_kernel<false>, dim3(sk_pedal_grid(count)), dim3(SK_PEDAL_SPAN), 0, stream, owner, pedal, value, mask,
+  sk_planes(p, ro, rw);
+  hipLaunchKernelGGL(sk_pedal_match_kernel<false>, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, owner, pedal, value, mask,
                      first, count, slot_voices, voice_mask, 0u, p, (uint64_t)0, (uint64_t *)nullptr, d_result);
   return (int)hipGetLastError();
 }
@@ -181,11 +152,11 @@ extern "C" int sk_launch_pedal_up(const uint32_t *owner, uint32_t *pedal, uint32
                                   sk_plane_t *const rw[SKS_COUNT], uint64_t now, uint64_t *mask_list, uint32_t *d_result,
                                   hipStream_t stream) {
   if (count <= 0) return 0;
-  const hipError_t e = hipMemsetAsync(d_result, 0, 3 * sizeof(uint32_t), stream);
+  const hipError_t e = sk_result_clear(d_result, 3, stream);
   if (e != hipSuccess) return (int)e;
   sk_plane_ptrs_t p;
-  sk_pedal_planes(p, ro, rw);
-  hipLaunchKernelGGL(sk_pedal_match_kernel<true>, dim3(sk_pedal_grid(count)), dim3(SK_PEDAL_SPAN), 0, stream, owner, pedal, value, mask,
+  sk_planes(p, ro, rw);
+  hipLaunchKernelGGL(sk_pedal_match_kernel<true>, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, owner, pedal, value, mask,
                      first, count, slot_voices, voice_mask, flags, p, now, mask_list, d_result);
   return (int)hipGetLastError();
 }

@@ -31,7 +31,7 @@
 #include "skred_idle_common.hpp"   // sk_idle_pred: the predicate of one voice
 #include "skred_idle_scan.hpp"     // counts, offsets, rank of `from`, scatter
 #include "skred_launch.h"
-#include "skred_update_common.hpp" // sk_note_store, sk_stamp_store, sk_slot_valid, sk_batch_done
+#include "skred_update_common.hpp" // sk_note_store, sk_stamp_store, sk_slot_valid, sk_entry_decode, sk_batch_done, the launch helpers
 
 // this lane is the first voice of an idle slot (v: its voice; a slot never straddles a wavefront: spans start at a multiple of 64)
 __device__ __forceinline__ bool sk_slot_listed(const sk_slot_args_t &s, int v, bool in_range) {
@@ -94,27 +94,11 @@ __global__ __launch_bounds__(SK_NOTE_SPAN) void sk_slot_notes_kernel(const sk_no
   sk_batch_done(cnt, done, seq);
 }
 
-__global__ __launch_bounds__(256) void sk_slot_stamps_kernel(const int32_t *d_slots, int n, const uint32_t *d_count, int k_shift,
-                                                             uint64_t voice_mask, int n_voices, uint32_t dirty, sk_plane_ptrs_t p,
-                                                             uint64_t now, uint64_t *mask) {
-  const int K = 1 << k_shift;
-  const int i = (int)blockIdx.x * (256 >> k_shift) + ((int)threadIdx.x >> k_shift), l = (int)threadIdx.x & (K - 1);
-  if (i >= n) return;
-  if (d_count && (uint32_t)i >= d_count[0]) return;
-  const int e = d_slots[i];
-  if (!sk_slot_valid(e, K, n_voices) || !((voice_mask >> l) & 1)) return;
-  sk_stamp_store(p, now, mask, e + l, dirty);
-}
-
-static void sk_slot_planes(sk_plane_ptrs_t &p, sk_plane_t *const ro[SKP_COUNT], sk_plane_t *const rw[SKS_COUNT]) {
-  for (int k = 0; k < SKP_COUNT; ++k) p.ro[k] = ro[k];
-  for (int k = 0; k < SKS_COUNT; ++k) p.rw[k] = rw[k];
-}
-
-static int sk_slot_shift(int slot_voices) {
-  int sh = 0;
-  while ((1 << sh) < slot_voices) ++sh;
-  return sh;
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_slot_stamps_kernel(const int32_t *d_slots, int n, const uint32_t *d_count, int k_shift,
+                                                                         uint64_t voice_mask, int n_voices, uint32_t dirty,
+                                                                         sk_plane_ptrs_t p, uint64_t now, uint64_t *mask) {
+  const sk_entry_t t = sk_entry_decode(SK_CONTROL_SPAN, k_shift, d_slots, n, d_count, n_voices);
+  if (t.valid && ((voice_mask >> t.l) & 1)) sk_stamp_store(p, now, mask, t.e + t.l, dirty);
 }
 
 extern "C" int sk_launch_slots(const sk_slot_args_t *args, hipStream_t stream) {
@@ -135,7 +119,7 @@ extern "C" int sk_launch_slot_notes(const sk_note_t *d_notes, int n, int slot_vo
                                     uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
   sk_plane_ptrs_t p;
-  sk_slot_planes(p, ro, rw);
+  sk_planes(p, ro, rw);
   const int sh = sk_slot_shift(slot_voices), per_wg = SK_NOTE_SPAN >> sh;
   const unsigned n_wg = (unsigned)(((long long)n + per_wg - 1) / per_wg);
   if (n_wg > 1) {
@@ -152,10 +136,9 @@ extern "C" int sk_launch_slot_stamps(const int32_t *d_slots, int n, const uint32
                                      uint64_t now, uint64_t *mask, hipStream_t stream) {
   if (n <= 0) return 0;
   sk_plane_ptrs_t p;
-  sk_slot_planes(p, ro, rw);
-  const int sh = sk_slot_shift(slot_voices), per_wg = 256 >> sh;
-  const unsigned n_wg = (unsigned)(((long long)n + per_wg - 1) / per_wg);
-  hipLaunchKernelGGL(sk_slot_stamps_kernel, dim3(n_wg), dim3(256), 0, stream, d_slots, n, d_count, sh, voice_mask, n_voices, dirty, p, now,
+  sk_planes(p, ro, rw);
+  const int sh = sk_slot_shift(slot_voices);
+  hipLaunchKernelGGL(sk_slot_stamps_kernel, dim3(sk_list_grid(n, sh)), dim3(SK_CONTROL_SPAN), 0, stream, d_slots, n, d_count, sh, voice_mask, n_voices, dirty, p, now,
                      mask);
   return (int)hipGetLastError();
 }

@@ -80,8 +80,7 @@ extern "C" int sk_launch_stamp(const int32_t *d_ids, int n, uint32_t dirty, sk_p
                                uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
   sk_plane_ptrs_t p;
-  for (int k = 0; k < SKP_COUNT; ++k) p.ro[k] = ro[k];
-  for (int k = 0; k < SKS_COUNT; ++k) p.rw[k] = rw[k];
+  sk_planes(p, ro, rw);
   hipLaunchKernelGGL(sk_stamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_ids, n, dirty, p, now, mask, cnt, done, seq);
   return (int)hipGetLastError();
 }
@@ -91,8 +90,7 @@ extern "C" int sk_launch_update(const sk_update_t *d_updates, int n, sk_plane_t 
                                 uint32_t seq, hipStream_t stream) {
   if (n <= 0) return 0;
   sk_plane_ptrs_t p;
-  for (int k = 0; k < SKP_COUNT; ++k) p.ro[k] = ro[k];
-  for (int k = 0; k < SKS_COUNT; ++k) p.rw[k] = rw[k];
+  sk_planes(p, ro, rw);
   hipLaunchKernelGGL(sk_update_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, d_updates, n, p, now, mask, cnt, done, seq);
   return (int)hipGetLastError();
 }
