@@ -639,6 +639,101 @@ int  skred_fxbank_pedal_up(skred_fxbank_t *fx, int first, int count, const skred
 int  skred_fxbank_pedal_clear(skred_fxbank_t *fx, int first, int count, void *stream);
 int  skred_fxbank_download_pedals(skred_fxbank_t *fx, uint32_t *host_u32, int first, int count);
 
+/* ---- portamento: pitch glides that advance and land on the device, in integers ------------------------------------------------
+ *
+ * The fixed-point twin of the float bank's section "portamento" (include/skred_amd.h: skred_glide_check .. skred_bank_download_glide),
+ * per voice -- this bank has no slots, so no slot_voices and no masks.  The float definition rests on one fp32 product per step, on
+ * signs and on non-finite values; none of that exists here.  THIS is the place of record for the integer definition: the same bits on
+ * every machine, an exact landing, and increments that do not depend on how the host cuts its blocks.  The only other route on this
+ * bank is one skred_fxbank_ctl_tags_each(SKRED_EACH_INC_SCALE) per block from the host, which must keep the list of gliding notes,
+ * never lands on the struck key's increment (a Q16 multiply of a truncated product), and stalls outright on small increments,
+ * where (inc * 65542) >> 16 == inc.
+ *
+ * STATE.  glide[n_voices] is an array of four uint32 per voice in device memory (one 16-byte word): target, up_q32, down_q32, carry.
+ * target == 0 means "not gliding": a phase_inc of 0 is a voice without pitch and is never a legal start or target.  The first call
+ * that starts a glide (skred_fxbank_glide_owned / _glide_tags with n > 0) allocates the array (16 bytes per voice) beside the owner
+ * and pedal arrays and zero-fills it, and ensures the owner array too; that call waits for the device once.  It is freed with the
+ * bank.  Only the calls of this section (and the clear below) read or write it, and the only bank word they store is phase_inc, as a
+ * word store: its neighbours in the plane keep their bits.  No render kernel reads the array; a bank that never starts a glide
+ * allocates nothing more and launches nothing more than it did before this section existed.
+ *
+ * ENTRY.  skred_fx_glide_t: `set` holds exactly one of three bits.  With inc = the voice's phase_inc as the device holds it:
+ *   SKRED_FX_GLIDE_FROM_SCALE  target = inc, then inc = ((uint64)inc * scale_q16) >> 16 -- slide INTO the note from the previous key.
+ *                              scale_q16 is SKRED_EACH_INC_SCALE's Q16: 65536 = 1.0.
+ *   SKRED_FX_GLIDE_TO_SCALE    target = ((uint64)(gliding ? the old target : inc) * scale_q16) >> 16; inc stays.  A chain of these
+ *                              composes on the old target, not on wherever the glide happens to be.
+ *   SKRED_FX_GLIDE_TO_INC      target = target_inc; inc stays.  Legato onto a key whose increment the host knows -- the bank is per
+ *                              voice, so it does -- and the glided note lands on the struck note's bits.  Q16 TO_SCALE cannot promise
+ *                              that landing.
+ * up_q32 and down_q32 (both non-zero) are the rates: 1 + up_q32 / 2^32 and 1 - down_q32 / 2^32 per 64 frames, far finer than Q16.
+ * A start whose inc, new inc or target would be 0 or above 0xFFFFFFFF stores nothing and is counted as withheld: the voice and its
+ * glide words stay as they were.  A start that stores sets carry = 0 and replaces a glide the voice was in.
+ *
+ * ADVANCE BY F FRAMES.  For every voice of [first, first + count) with target != 0:
+ *   1. c = carry + F; c >> 6 steps are taken; the new carry is c & 63.
+ *   2. Before the first step (and when there is none to take), a voice with inc == 0 or inc == target arrives at once.
+ *   3. A step with inc < target:  next = inc + max(1, ((uint64)inc * up_q32) >> 32), in 64 bits; the voice arrives when next >= target.
+ *   4. A step with inc > target:  next = inc - max(1, ((uint64)inc * down_q32) >> 32); the voice arrives when next <= target.
+ *      (down_q32 <= 2^32 - 1: the subtrahend never exceeds inc.)
+ *   5. On arrival the target's bits are stored in phase_inc and the four words are zeroed.
+ *   6. Otherwise the last `next` is stored (only if it differs from what the voice held) and carry is written.
+ * max(1, ...) guarantees progress: an LFO-rate increment cannot stall.  The loop runs at most F / 64 + 1 times.  Because of the
+ * carry, the increment at every multiple of 64 frames does not depend on the block sizes the host advances by.
+ *
+ * A NEW NOTE CLEARS THE WORDS.  Once the array exists, every tag launch of the bank (skred_fxbank_tag_list, the tags of
+ * skred_fxbank_note_on_channel) is followed on its stream by a launch that zeroes the four words of every voice it tagged -- the same
+ * list under the same list rule, right where the pedal word is cleared.  A thief or a re-struck key does not inherit a glide.  The
+ * order for mono legato is therefore skred_fxbank_note_on_channel, then skred_fxbank_glide_tags(FROM_SCALE).
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_fxbank_update; host arrays travel through the staging ring; nothing
+ * waits for the device except the download and the first allocation; results are pure functions of the state, whatever the order of
+ * arrival; one stream at a time per bank.  On a shard: through skred_fxshard_bank(), with that rank's local indices.
+ *
+ * skred_fx_glide_check       pure host: SKRED_OK, or SKRED_E_BAD_ARG for NULL glide, n < 0, and per entry: `set` not exactly one of
+ *                            the three bits, a non-zero reserved word, up_q32 == 0 or down_q32 == 0, scale_q16 == 0 on the two scale
+ *                            forms, target_inc == 0 on TO_INC.  Values the form does not use are not looked at.
+ * skred_fxbank_glide_owned   looks at the entries below min(n, *d_count_or_null); entry k starts glide[k] on d_voices[k] where that is
+ *                            a voice of the bank whose owner is tags[k].  d_result (device uint32[3], may be NULL; cleared on the
+ *                            stream ahead of the kernel): [0] voices set gliding, [1] starts withheld, [2] voices whose owner differs.
+ *                            A voice listed twice is UNSPECIFIED.  Refused before anything touches the device: NULL bank or list,
+ *                            what skred_owner_tags_check refuses (NULL tags, n < 0, a zero tag), n > INT32_MAX / 64, what
+ *                            skred_fx_glide_check refuses -- in that order.  n == 0: SKRED_OK, nothing is done.
+ * skred_fxbank_glide_tags    glides by note id: skred_fxbank_release_tags' find pass over [first, first + count) into the same
+ *                            scratch -- the lowest voice of the range per tag, or -1 -- then the call above on that list.  glide[k]
+ *                            goes with tags[k]: the tags travel sorted, and the entries are permuted with them on the host.  Tags
+ *                            unique, none zero, n <= SKRED_OWNER_MAX_TAGS.  d_result as above; [2] is 0.  Refused: NULL bank, the
+ *                            tags, n and the entries as above, then SKRED_E_RANGE for an empty range or one outside the bank.
+ * skred_fxbank_glide_advance the advance pass; call it once per rendered block with the block's frames.  num_frames 1 .. 65536.
+ *                            d_result (device uint32[2], may be NULL; cleared ahead of the kernel): [0] voices still gliding,
+ *                            [1] voices that arrived.  It ships no bytes and takes no slot of the ring.  On a bank without the array:
+ *                            SKRED_OK, and d_result is cleared on the stream.  Refused: NULL bank, num_frames out of range
+ *                            (SKRED_E_BAD_ARG), an empty range or one outside the bank (SKRED_E_RANGE).
+ * skred_fxbank_glide_stop    glide[first .. first + count) = 0 on `stream`; snap != 0: a gliding voice's phase_inc = its target
+ *                            first.  Nothing to do on a bank without the array.  SKRED_E_RANGE: count < 0 or a range outside the bank.
+ * skred_fxbank_download_glide  the words of [first, first + count) into host_u32x4 (4 * count words); waits for the device; zeros on
+ *                            a bank without the array.
+ * LIMITS, documented, not fixed: a SKRED_CTL_PHASE_INC / _INC_SCALE bend of a gliding voice is undone on arrival (the target's bits
+ * are stored); the host view of phase_inc goes stale -- skred_fxbank_download_params reads it back; glides belong with tagged notes
+ * (an untagged voice cannot be reached).  Out of scope: the drop-in mode, deferred items, pattern steps, per-frame glides. */
+#define SKRED_FX_GLIDE_FROM_SCALE (1u << 0)
+#define SKRED_FX_GLIDE_TO_SCALE   (1u << 1)
+#define SKRED_FX_GLIDE_TO_INC     (1u << 2)
+typedef struct skred_fx_glide {           /* 32 bytes */
+  uint32_t set;                           /* exactly one SKRED_FX_GLIDE_* */
+  uint32_t up_q32, down_q32;              /* per 64 frames: x (1 + up / 2^32), x (1 - down / 2^32); both non-zero */
+  uint32_t scale_q16;                     /* FROM_SCALE, TO_SCALE: 65536 = 1.0 */
+  uint32_t target_inc;                    /* TO_INC */
+  uint32_t reserved[3];                   /* 0 */
+} skred_fx_glide_t;
+int  skred_fx_glide_check(const skred_fx_glide_t *glide, int n);
+int  skred_fxbank_glide_owned(skred_fxbank_t *fx, const skred_fx_glide_t *glide, const int32_t *d_voices, const uint32_t *tags, int n,
+                              const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+int  skred_fxbank_glide_tags(skred_fxbank_t *fx, const skred_fx_glide_t *glide, int first, int count, const uint32_t *tags, int n,
+                             uint32_t *d_result, void *stream);
+int  skred_fxbank_glide_advance(skred_fxbank_t *fx, int first, int count, int num_frames, uint32_t *d_result, void *stream);
+int  skred_fxbank_glide_stop(skred_fxbank_t *fx, int first, int count, int snap, void *stream);
+int  skred_fxbank_download_glide(skred_fxbank_t *fx, uint32_t *host_u32x4, int first, int count);
+
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);
 float skred_fxbank_last_render_ms(skred_fxbank_t *fx);

@@ -126,4 +126,18 @@ typedef struct { uint32_t w[SKX_EACH_WORDS]; } skx_each_t;   /* 32 bytes */
 enum { SKX_FILT_W_B0 = 0, SKX_FILT_W_B1, SKX_FILT_W_B2, SKX_FILT_W_A1, SKX_FILT_W_A2, SKX_FILT_WORDS = 8 };
 typedef struct { uint32_t w[SKX_FILT_WORDS]; } skx_filt_each_t;   /* 32 bytes */
 #define SKX_EXPR_SPAN 256          /* voices or entries (and threads) per workgroup of the expression kernels */
+
+/* ---- portamento (skred_fx_glide_kernels.hip; include/skred_amd_fxpt.h: skred_fxbank_glide_owned / _glide_tags / _glide_advance /
+ * _glide_stop) ----
+ * glide[n_voices]: four words per voice (one 16-byte load) beside the owner array, target == 0 "not gliding".  The float bank's
+ * sk_glide_t has the same shape (checked in skred_fx_glide.c): its clear kernel serves this array too */
+enum { SKX_GLIDE_TARGET = 0, SKX_GLIDE_UP, SKX_GLIDE_DOWN, SKX_GLIDE_CARRY, SKX_GLIDE_WORDS = 4 };
+typedef struct { uint32_t w[SKX_GLIDE_WORDS]; } skx_glide_t;   /* 16 bytes */
+/* a per-entry record is skred_fx_glide_t word for word (layout and bits checked at compile time in skred_fx_glide.c): 32 bytes, so that
+ * set, up_q32, down_q32, scale_q16 are one aligned 16-byte load.  The bits equal SKRED_FX_GLIDE_* */
+#define SKX_GLIDE_FROM_SCALE (1u << 0)
+#define SKX_GLIDE_TO_SCALE   (1u << 1)
+#define SKX_GLIDE_TO_INC     (1u << 2)
+enum { SKX_GLIDE_E_SET = 0, SKX_GLIDE_E_UP, SKX_GLIDE_E_DOWN, SKX_GLIDE_E_SCALE, SKX_GLIDE_E_TARGET_INC, SKX_GLIDE_E_WORDS = 8 };
+typedef struct { uint32_t w[SKX_GLIDE_E_WORDS]; } skx_glide_each_t;   /* 32 bytes */
 #endif

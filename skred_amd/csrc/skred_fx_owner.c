@@ -53,6 +53,8 @@ int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint
   hipError_t e = (hipError_t)sk_launch_owner_tag(fx->d_owner, d_voices, src, n, d_count, 1, fx->n_voices, d_result, NULL, NULL, 0, s);
   /* a new note clears its voice's pedal word (skred_fx_pedal.c): the same list under the same rule, once the bank has the array */
   if (e == hipSuccess && fx->d_pedal) e = (hipError_t)sk_launch_pedal_clear(fx->d_pedal, d_voices, n, d_count, 1, fx->n_voices, s);
+  /* ... and does not inherit a glide (skred_fx_glide.c): the float bank's clear kernel, the array's shape being the same */
+  if (e == hipSuccess && fx->d_glide) e = (hipError_t)sk_launch_glide_clear((sk_glide_t *)fx->d_glide, d_voices, n, d_count, 1, fx->n_voices, s);
   return skx_batch_end(&bt, e, who, s);
 }
 

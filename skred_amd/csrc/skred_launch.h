@@ -23,6 +23,8 @@
  *   skred_glide_kernels.hip   sk_launch_glide_clear, sk_launch_glide_start, sk_launch_glide_advance, sk_launch_glide_stop
  *   skred_fx_pedal_kernels.hip  skx_launch_pedal_stamps, skx_launch_pedal_latch, skx_launch_pedal_up (sk_launch_pedal_clear by
  *                             skred_fx_owner.c too)
+ *   skred_fx_glide_kernels.hip  skx_launch_glide_start, skx_launch_glide_advance, skx_launch_glide_stop (prototypes in
+ *                             skred_fxbank_priv.h; sk_launch_glide_clear by skred_fx_owner.c too)
  *
  * Every launcher returns the hipError_t of the launch as an int.  The render, list and master-stage launchers are called by
  * skred_bank_render.c (as skred_bank_plan.c decides), sk_launch_pack_zero too; the rest by skred_bank_update.c, skred_bank_idle.c,

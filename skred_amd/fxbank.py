@@ -47,9 +47,12 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_find_steal_match", "skred_fxbank_find_steal_match_host", "skred_fxbank_note_on_channel",
                   "skred_fxbank_stamp_owned_pedal", "skred_fxbank_release_tags_pedal", "skred_fxbank_pedal_latch",
                   "skred_fxbank_pedal_up", "skred_fxbank_pedal_clear", "skred_fxbank_download_pedals",
+                  "skred_fxbank_glide_owned", "skred_fxbank_glide_tags", "skred_fxbank_glide_advance", "skred_fxbank_glide_stop",
+                  "skred_fxbank_download_glide",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
 FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
-                       "skred_fx_ctl_each_check", "skred_fx_filter_each_check", "skred_fx_chan_check", "skred_fx_pedal_check"]                                                                     # pure host: no bank, no device
+                       "skred_fx_ctl_each_check", "skred_fx_filter_each_check", "skred_fx_chan_check", "skred_fx_pedal_check",
+                       "skred_fx_glide_check"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -68,6 +71,7 @@ CTL_REFUSED = 0x3F00
 EACH_INC_SCALE, EACH_AMP_SCALE, EACH_VELOCITY, EACH_PAN = 1, 2, 4, 8
 EACH_ALL = 15
 CHAN_NO_CAP = 0xFFFFFFFF                          # SKRED_CHAN_NO_CAP: a cap that never limits
+FX_GLIDE_FROM_SCALE, FX_GLIDE_TO_SCALE, FX_GLIDE_TO_INC = 1, 2, 4   # SKRED_FX_GLIDE_*: exactly one per entry
 FX_CTL_SPAN = 256                                 # voices or entries per workgroup of the controller and guarded-stamp kernels
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
@@ -206,6 +210,32 @@ def fx_pedal_check(call: int, n_voices: int, first: int = 0, count: int = 0, m: 
                                                   int(flags), t.ctypes.data if t is not None else None, int(n)))
 
 
+class FxGlideC(C.Structure):
+    """ctypes image of ``skred_fx_glide_t`` (32 bytes): `set` is exactly one of FX_GLIDE_FROM_SCALE, _TO_SCALE and _TO_INC."""
+    _fields_ = [("set", C.c_uint32), ("up_q32", C.c_uint32), ("down_q32", C.c_uint32), ("scale_q16", C.c_uint32),
+                ("target_inc", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+def glide(set: int, up_q32: int, down_q32: int, scale_q16: int = 0, target_inc: int = 0) -> FxGlideC:
+    """One glide: ``glide(FX_GLIDE_FROM_SCALE, 31000000, 31000000, 43740)`` slides up a fifth into the note."""
+    return FxGlideC(int(set), int(up_q32), int(down_q32), int(scale_q16), int(target_inc))
+
+
+def glide_array(glides):
+    """A contiguous ``FxGlideC`` array from a sequence of FxGlideC (a ctypes array of FxGlideC passes through)."""
+    if isinstance(glides, C.Array) and glides._type_ is FxGlideC:
+        return glides
+    glides = list(glides)
+    return (FxGlideC * len(glides))(*glides)
+
+
+def fx_glide_check(glides, n: Optional[int] = None) -> int:
+    """skred_fx_glide_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device.  ``glides`` None: a NULL array."""
+    arr = glide_array(glides) if glides is not None else None
+    n = (len(arr) if arr is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_glide_check(C.cast(arr, C.c_void_p) if arr is not None else None, int(n)))
+
+
 class FxNoteC(C.Structure):
     """ctypes image of ``skred_fx_note_t`` (32 bytes)."""
     _fields_ = [("phase_inc", C.c_uint32), ("velocity_q15", C.c_int32), ("phase", C.c_uint32), ("pan_left_q15", C.c_int32),
@@ -336,6 +366,12 @@ def _bind(L):
     L.skred_fxbank_pedal_up.argtypes = [vp, i32, i32, vp, C.c_uint32, vp, vp]
     L.skred_fxbank_pedal_clear.argtypes = [vp, i32, i32, vp]
     L.skred_fxbank_download_pedals.argtypes = [vp, vp, i32, i32]
+    L.skred_fx_glide_check.argtypes = [vp, i32]
+    L.skred_fxbank_glide_owned.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_glide_tags.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+    L.skred_fxbank_glide_advance.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.skred_fxbank_glide_stop.argtypes = [vp, i32, i32, i32, vp]
+    L.skred_fxbank_download_glide.argtypes = [vp, vp, i32, i32]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -695,6 +731,40 @@ class DeviceFxBank:
         count = self.n - first if count is None else count
         out = np.full(max(count, 0), 0xABABABAB, np.uint32)
         _check(self.L.skred_fxbank_download_pedals(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_pedals")
+        return out
+
+    # ---- portamento (include/skred_amd_fxpt.h: skred_fxbank_glide_owned / _glide_tags / _glide_advance / _glide_stop) ----
+    def glide_owned(self, glides, d_voices: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """Entry k starts glides[k] on d_voices[k] where that voice's owner is tags[k].  d_result (uint32[3], may be 0) = voices set
+        gliding, starts withheld, voices whose owner differs."""
+        arr, t = glide_array(glides), _tags(tags)
+        assert len(arr) == len(t), "one glide per tag"
+        _check(self.L.skred_fxbank_glide_owned(self.h, C.cast(arr, C.c_void_p), d_voices or None, t.ctypes.data, len(t), d_count or None,
+                                               d_result or None, stream or None), "skred_fxbank_glide_owned")
+
+    def glide_tags(self, glides, first: int, count: int, tags, d_result: int = 0, stream: int = 0):
+        """Glides by note id: glides[k] starts on the lowest voice of the range that carries tags[k]."""
+        arr, t = glide_array(glides), _tags(tags)
+        assert len(arr) == len(t), "one glide per tag"
+        _check(self.L.skred_fxbank_glide_tags(self.h, C.cast(arr, C.c_void_p), int(first), int(count), t.ctypes.data, len(t),
+                                              d_result or None, stream or None), "skred_fxbank_glide_tags")
+
+    def glide_advance(self, first: int, count: int, frames: int, d_result: int = 0, stream: int = 0):
+        """Every gliding voice of the range moves on by `frames` frames (one step per 64) or lands on its target.  d_result
+        (uint32[2], may be 0) = still gliding, arrived."""
+        _check(self.L.skred_fxbank_glide_advance(self.h, int(first), int(count), int(frames), d_result or None, stream or None),
+               "skred_fxbank_glide_advance")
+
+    def glide_stop(self, first: int = 0, count: Optional[int] = None, snap: bool = False, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_fxbank_glide_stop(self.h, int(first), int(count), int(bool(snap)), stream or None), "skred_fxbank_glide_stop")
+
+    def download_glide(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The glide words of [first, first + count) as a (count, 4) uint32 array: target, up_q32, down_q32, carry; waits for the
+        device.  Zeros on a bank that never started a glide."""
+        count = self.n - first if count is None else count
+        out = np.full((max(count, 0), 4), 0xABABABAB, np.uint32)
+        _check(self.L.skred_fxbank_download_glide(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_glide")
         return out
 
 

@@ -1957,8 +1957,73 @@ def fxpedal():
     db.close()
 
 
+def fxglide():
+    """Portamento on bank_fx(2**20), every voice sounding and tagged over 16 channels (tag = channel << 24 | voice // 16 + 1), 256
+    notes of one channel gliding: the `glide` mode on the fixed-point bank.  (a) skred_fxbank_glide_tags of the 256 tags, and
+    skred_fxbank_glide_advance by 64 frames over one channel's range (a sixteenth of the bank), over the whole bank with the 256
+    voices gliding, over the whole bank with nothing gliding and on a bank without the array, beside the route the bank had before:
+    one skred_fxbank_ctl_tags_each(SKRED_EACH_INC_SCALE) of the 256 tags per block; (b) the 64-frame block after an advance beside a
+    steady block before and after it; (c) skred_fxbank_tag_list of 256 voices before the bank has a glide array and with the clear
+    launch behind it.  Medians of 12 with minimum and maximum; host time held, and stream time between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES = 1 << 20, 64, 16, 256
+    bank, pool, c0 = X.bank_fx(n)
+    db, bare = X.DeviceFxBank(n), X.DeviceFxBank(n)
+    for d in (db, bare):
+        d.set_tables(pool); d.upload(bank); d.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    everyone = torch.arange(n, dtype=torch.int32, device="cuda")
+    db.tag_list(everyone.data_ptr(), tags)
+    at = np.flatnonzero(v % CHANNELS == 2)[::7][:NOTES]                          # 256 notes of channel 3
+    note_tags, note_voices = tags[at].copy(), at.astype(np.int32)
+    dl_notes = torch.from_numpy(note_voices).cuda()
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    # a slow slide into each note from a fifth below: a third of a semitone per second, so that nobody arrives while the lines are timed
+    r = 2.0 ** (0.33 / 12.0 * 64.0 / 48000.0)
+    up, down = max(1, int((r - 1.0) * 2.0 ** 32)), max(1, int((1.0 - 1.0 / r) * 2.0 ** 32))
+    glides = X.glide_array([X.glide(X.FX_GLIDE_FROM_SCALE, up, down, int(2.0 ** (-7.0 / 12.0) * 65536.0)) for _ in range(NOTES)])
+    each = X.fx_each_array([X.fx_each(X.EACH_INC_SCALE, inc_scale_q16=65542) for _ in range(NOTES)])
+    torch.cuda.synchronize()
+
+    restore = lambda: db.upload(bank)                                             # noqa: E731 (the struck increments back)
+    start = lambda: db.glide_tags(glides, 0, n, note_tags, res.data_ptr())        # noqa: E731
+    armed = lambda: (restore(), start())                                          # noqa: E731
+
+    def line(label, call, words, before=None):
+        ms, held = _fx_timed(call, before)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {res.cpu().numpy().tolist()[:words]}")
+
+    print(f"fx {n} voices all sounding, tagged over {CHANNELS} channels ({n // CHANNELS} notes each); {NOTES} notes of one channel glide")
+    line(f"(c) tag_list of {NOTES} voices, no glide array yet", lambda: db.tag_list(dl_notes.data_ptr(), note_tags), 0)
+    line("(a) glide_advance by 64 frames on a bank without the array (a clear of d_result)", lambda: bare.glide_advance(0, n, F, res.data_ptr()), 2)
+    line(f"(a) glide_tags of {NOTES} tags", start, 3, restore)
+    line(f"(c) tag_list of {NOTES} voices with the clear launch behind it", lambda: db.tag_list(dl_notes.data_ptr(), note_tags), 0)
+    armed()
+    line(f"(a) glide_advance by 64 frames over a sixteenth of the bank ({n // CHANNELS} voices)",
+         lambda: db.glide_advance(int(note_voices[0]), n // CHANNELS, F, res.data_ptr()), 2)
+    armed()
+    line(f"(a) glide_advance by 64 frames over the whole bank, {NOTES} voices gliding", lambda: db.glide_advance(0, n, F, res.data_ptr()), 2)
+    db.glide_stop(0, n, True)
+    line("(a) glide_advance by 64 frames over the whole bank, nothing gliding", lambda: db.glide_advance(0, n, F, res.data_ptr()), 2)
+    restore()
+    line(f"(a) the route before: ctl_tags_each(INC_SCALE) of the {NOTES} tags, once per block",
+         lambda: db.ctl_tags_each(None, each, 0, n, note_tags, res.data_ptr()), 3)
+
+    db.upload(bank); db.set_sample_count(c0)
+    start()
+    _fx_block_after(db, out, F, None, 8)
+    before = _fx_block_after(db, out, F)
+    after = _fx_block_after(db, out, F, lambda: db.glide_advance(0, n, F, res.data_ptr()))
+    later = _fx_block_after(db, out, F)
+    print(f"  (b) the {F}-frame block after an advance ({NOTES} increments moved): {_fx_stats(after)}; a steady block before it: "
+          f"{_fx_stats(before)}; after it: {_fx_stats(later)}")
+    db.close(); bare.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
