@@ -406,7 +406,9 @@ int  skred_bank_set_probe(skred_bank_t *bank, const int32_t *voices, int n, floa
  * Refused: a voice outside the bank (SKRED_E_RANGE); n > SKRED_TAPS_MAX, or NULL pointers with n > 0 (SKRED_E_BAD_ARG); taps while
  * a probe is set and a probe while taps are set (SKRED_E_BAD_ARG for the second setter); a render with taps set and a stem buffer
  * (SKRED_E_UNSUPPORTED: the stems already contain the taps; the bank stays usable).  n = 0 ends it.  Not in the fixed-point bank,
- * shards or the drop-in mode. */
+ * shards or the drop-in mode.  The call WAITS FOR THE DEVICE (a block in flight may still read the old list): a host that must not
+ * wait sets the taps once, on a buffer sized for its longest block, and queues a device-to-device copy of d_taps on the render
+ * stream behind each block. */
 #define SKRED_TAPS_MAX 64
 int  skred_bank_set_taps(skred_bank_t *bank, const int32_t *voices, int n, float *d_taps);
 int  skred_bank_last_taps(const skred_bank_t *bank);     /* taps written by the latest block, 0: none */
@@ -1216,7 +1218,14 @@ int  skred_bank_download_pedals(skred_bank_t *bank, uint32_t *host_u32, int firs
  * A NEW NOTE CLEARS THE WORDS.  Once the array exists, every tag launch of the bank (skred_bank_tag_slots, the tags of
  * skred_bank_note_on_channel) is followed on its stream by a launch that zeroes the glide words of all K voices of every slot it
  * tagged (the pedal word's rule): a thief or a key struck again does not inherit its victim's glide.  The order for mono legato is
- * therefore skred_bank_note_on_channel, then skred_bank_glide_tags(SKRED_GLIDE_FROM_SCALE).
+ * therefore skred_bank_note_on_channel, then skred_bank_glide_tags(SKRED_GLIDE_FROM_SCALE).  On a bank that has a pedal array too
+ * the tag kernel, the pedal clear and the glide clear run in that order inside one staged batch; each clear reads the list and the
+ * count word only, so neither depends on the other.
+ *
+ * A RELEASE LEAVES THE WORDS ALONE.  A note-off (by list, by note id, by match) and a pedal-up stamp the envelope and touch nothing
+ * else: a released note and a note whose note-off is pending glide on, through the tail, until the glide arrives, a tag launch takes
+ * the slot or skred_bank_glide_stop ends it.  skred_bank_pedal_latch reads HELD from the envelope alone: a gliding note is latched
+ * like any other.  The steal queries rank a gliding slot by its envelope clocks, as they rank a pending one.
  *
  * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring, so the
  * caller's memory is free on return; nothing waits for the device but the download and the first allocation; one stream at a time per

@@ -30,11 +30,11 @@ B_TAGS = np.array([0x1000 + k for k in range(B_COUNT)], np.uint32)
 C_TAGS_BASE = 0x70000000
 
 
-def bank():
-    """bank_patch("3sk") with every copy sounding since long ago, except A_SLOTS, whose members are at rest."""
-    b, tables, g = banks.bank_patch("3sk", N)
+def bank(n=N, rest=A_SLOTS):
+    """bank_patch("3sk") with every copy sounding since long ago, except the slots `rest`, whose members are at rest."""
+    b, tables, g = banks.bank_patch("3sk", n)
     now = int(g.synth_sample_count)
-    v = np.arange(N)
+    v = np.arange(n)
     sel = np.isin(v % K, MEMBERS)
     e = b["voice_amp_envelope"]
     b["voice_use_amp_envelope"][sel] = 1
@@ -45,7 +45,7 @@ def bank():
     e["sample_start"][sel] = (now - 40000 - ((v[sel] // K) * 37) % 1000).astype(np.uint64)
     e["sample_release"][sel] = np.uint64(0)
     b["voice_smoother_smoothing"][sel] = np.float32(0.5)
-    rest = sel & np.isin(v - v % K, A_SLOTS)
+    rest = sel & np.isin(v - v % K, rest)
     e["is_active"][rest] = 0
     b["voice_smoother_gain"][rest] = np.float32(0.0)
     return b, tables, g
