@@ -1232,7 +1232,8 @@ int  skred_bank_download_pedals(skred_bank_t *bank, uint32_t *host_u32, int firs
  * bank.  A slot, K = slot_voices, voice_mask and tags mean what they mean in the sections above.
  *
  * Limits: glides belong with tagged notes.  A SKRED_CTL_PHASE_INC / _INC_SCALE bend of a gliding voice is undone on arrival (the
- * target's bits are stored): bend the target with SKRED_GLIDE_TO_SCALE.  The host view of voice_phase_inc goes stale, as for
+ * target's bits are stored): bend the target with SKRED_GLIDE_TO_SCALE, or bend with the calls of the pitch-wheel section below, which
+ * a glide carries to its target.  The host view of voice_phase_inc goes stale, as for
  * SKRED_CTL_INC_SCALE; skred_bank_download_ctl reads it back.  On a shard: through skred_shard_bank(), with that rank's local indices.
  * This section is the float bank's alone: a fixed-point twin of these calls is a follow-up.  Also out of scope: the drop-in mode (it
  * keeps voice_glissando_* as dead data), deferred items and pattern steps. */
@@ -1275,6 +1276,96 @@ int  skred_bank_glide_stop(skred_bank_t *bank, int first, int count, int snap, v
 /* The glide words of [first, first + count) into host_u32x4 (4 * count words: target, rate_up, rate_down, carry per voice); waits
  * for the device, like skred_bank_download_owners; zeros on a bank that never started a glide. */
 int  skred_bank_download_glide(skred_bank_t *bank, uint32_t *host_u32x4, int first, int count);
+
+/* ---- pitch wheel: bends that return to the key's bits and compose with glides -----------------------------------------------
+ *
+ * SKRED_CTL_INC_SCALE / SKRED_EACH_INC_SCALE multiply the increment the device holds, and that is all a host can do to a note it did
+ * not place itself.  As a pitch wheel the route has three defects.  A bend never comes back: up by r and back by 1 / r leaves
+ * fl(fl(inc * r) * fl(1 / r)), which is not inc for most values, and after a few hundred wheel messages every note of the channel is
+ * detuned against a freshly struck note on the same key.  Bends are relative: the host has to remember the last wheel position per
+ * channel and send ratios of ratios, and a note stolen and struck again between two messages gets the wrong one.  And a bend of a
+ * gliding voice is undone on arrival (the portamento section's limits).  The calls of this section keep the KEY's increment beside
+ * the one the oscillator reads and derive the sounding increment as key * ratio with one multiply, every time.
+ *
+ * bend[n_voices] is an array of two words PER VOICE (one uint2: key, ratio -- fp32 bit patterns) in device memory that only the calls
+ * of this section and the glide kernels read or write.  key == 0 (all bits) means "not bent".  The bank allocates the array (8 bytes
+ * per voice, behind the glide array in the bank's record; the owner array first, when no owner call came before) on the first
+ * skred_bank_bend_match / _bend_owned_each / _bend_tags_each call and zero-fills it; that call waits for the device once, as the
+ * first owner, pedal and glide calls do.  No render kernel, report, probe, tap or planner rule reads the array, and a bend stores
+ * nothing but finite non-zero increments (SKRED_CTL_INC_SCALE's argument): blocks rendered with and without bend calls that move
+ * nothing are bit-identical, and a bend call leaves the planner's reports alone.  A bank that never bends launches nothing more and
+ * allocates nothing.
+ *
+ * ABSOLUTE BEND of voice v to ratio r, with inc = voice_phase_inc as the device holds it:
+ *   1. k = key[v] ? key[v] : inc -- the first bend captures the key.
+ *   2. r's bits are those of 1.0f: inc = k is stored, but only if key[v] != 0, and both words are cleared.  The wheel at centre
+ *      restores the key's bits and leaves no state.
+ *   3. otherwise p = k * r, ONE fp32 multiply, round to nearest, never fused.  k zero or not finite, or p zero or not finite: the
+ *      bend is WITHHELD and counted, and the voice and its words stay exactly as they were.  Else inc = p, key[v] = k, ratio[v] = r.
+ * The ratio is absolute: the host sends the wheel's position, never a ratio of positions, and the same message twice is the same
+ * bits twice.  A voice counts as stored or restored when step 3 stored it or step 2 found key[v] != 0.
+ *
+ * A NEW NOTE CLEARS THE WORDS.  Once the array exists, every tag launch of the bank (skred_bank_tag_slots, the tags of
+ * skred_bank_note_on_channel) is followed on its stream by a launch that zeroes the bend words of all K voices of every slot it
+ * tagged -- the pedal and glide rule, beside their two clears in one staged batch; each clear reads the list and the count word
+ * only.  Without it a thief's first bend would restore its victim's key.  A note struck under a deflected wheel is therefore
+ * skred_bank_note_on_channel, then skred_bank_bend_tags_each with the channel's current ratio, then -- optionally, last --
+ * skred_bank_glide_tags(SKRED_GLIDE_FROM_SCALE).
+ *
+ * GLIDES UNDER A BEND.  On a bank with a bend array the glide calls read it: on a voice with key != 0 every place the portamento
+ * section says inc reads and writes KEY instead -- skred_bank_glide_owned / _tags with FROM_SCALE: target = key, key = key * scale;
+ * with TO_SCALE: target = (gliding ? the old target : key) * scale, key stays; skred_bank_glide_advance: the step loop runs on key,
+ * and on arrival key = the target's bits; skred_bank_glide_stop with snap: key = target.  After a start that was not withheld, after
+ * every advance of a gliding voice and after a snap of one, the sounding increment is stored again as key * ratio: one multiply,
+ * and that one store is withheld (uncounted; key and the glide words stand) where the product is zero or not finite.  So a glide
+ * under a bend lands on target * ratio, and the wheel back at centre then gives the target's bits exactly.  On voices with key == 0,
+ * and on a bank without a bend array, the glide calls store the bytes they always stored.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring, so the
+ * caller's memory is free on return; nothing waits for the device but the download and the first allocation; one stream at a time
+ * per bank.  A slot, K = slot_voices, voice_mask, tags and matches mean what they mean in the sections above.  Every d_result
+ * (device, uint32[3], may be NULL) is cleared on the stream ahead of the kernel: [0] voices stored or restored, [1] bends withheld,
+ * [2] slots not owned (the _each calls) or slots of the range that did not match (skred_bank_bend_match).
+ *
+ * Limits: a SKRED_CTL_PHASE_INC / _INC_SCALE store on a bent voice is overwritten by the next bend (which multiplies the key it
+ * captured): bend with these calls instead.  A release leaves the words alone, as for glides: a released note follows the wheel
+ * through its tail.  Bends belong with tagged notes.  The host view of voice_phase_inc goes stale; skred_bank_download_ctl reads it
+ * back.  On a shard: through skred_shard_bank(), with that rank's local indices.  This section is the float bank's alone: a
+ * fixed-point twin, the drop-in mode, deferred items and pattern steps are follow-ups. */
+/* Pure host: SKRED_OK, or what the bending calls refuse about K, the mask and the ratios, in this order.  SKRED_E_BAD_ARG: a NULL
+ * array; SKRED_E_RANGE: a bad K (not a power of two in 1 .. 64); SKRED_E_BAD_ARG: a voice_mask that is 0 or has bits at or above K, a
+ * ratio that is not finite or <= 0, n < 0. */
+int  skred_bend_check(const float *ratios, int n, int slot_voices, uint64_t voice_mask);
+/* The channel wheel: the rule above, to `ratio`, on every voice_mask voice of every slot of [first, first + count) whose owner
+ * matches m.  Geometry, guard and counting are skred_bank_ctl_match's; d_result[2] counts the slots that did not match.  The planner
+ * is told nothing.
+ * Refused, in this order: SKRED_E_BAD_ARG: NULL bank or match; SKRED_E_RANGE: a bad K; SKRED_E_BAD_ARG: a bad voice_mask, a ratio
+ * that is not finite or <= 0, what skred_owner_match_check refuses; SKRED_E_RANGE: first or count not a multiple of K, count <= 0, a
+ * range outside the bank. */
+int  skred_bank_bend_match(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t voice_mask, const skred_owner_match_t *m,
+                           float ratio, uint32_t *d_result, void *stream);
+/* Per-note bend (MPE): entry k (of the first min(n, *d_count_or_null)) acts on d_slots[k] only if that is a slot of the bank AND
+ * owner[slot] == tags[k] (non-zero); it applies the rule, to ratios[k], on every voice_mask voice of the slot.  d_result[2] counts
+ * the slots whose owner differs.  A slot named twice: UNSPECIFIED.  The planner is told nothing.
+ * Refused, in this order: SKRED_E_BAD_ARG: NULL bank, ratios, list or tags; SKRED_E_RANGE: a bad K; SKRED_E_BAD_ARG: a bad
+ * voice_mask, a ratio that is not finite or <= 0, a zero tag, n < 0 or n > INT32_MAX / 64.  n == 0: SKRED_OK. */
+int  skred_bank_bend_owned_each(skred_bank_t *bank, const float *ratios, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
+                                const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+/* Per-note bend by note id: skred_bank_find_owned of the tags over [first, first + count) into scratch the bank owns, then the call
+ * above on that list -- built as skred_bank_glide_tags is.  ratios[k] goes with tags[k]: the tags travel sorted, the ratios are
+ * permuted with them on the host.  Tags unique, none zero, n <= SKRED_OWNER_MAX_TAGS; each tag reaches at most ONE slot, the lowest
+ * that carries it.  d_result[2] is 0.
+ * Refused: as above, then SKRED_E_BAD_ARG: n > SKRED_OWNER_MAX_TAGS, a tag that appears twice; then SKRED_E_RANGE: first or count
+ * not a multiple of K, count <= 0, a range outside the bank. */
+int  skred_bank_bend_tags_each(skred_bank_t *bank, const float *ratios, int first, int count, int slot_voices, uint64_t voice_mask,
+                               const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+/* The bend words of [first, first + count) are cleared on `stream`; with snap != 0 a bent voice's increment is set to its key first
+ * (the wheel at centre, without the guard).  Nothing to do on a bank without a bend array.  SKRED_E_BAD_ARG: NULL bank;
+ * SKRED_E_RANGE: count < 0 or a range outside the bank. */
+int  skred_bank_bend_clear(skred_bank_t *bank, int first, int count, int snap, void *stream);
+/* The bend words of [first, first + count) into host_u32x2 (2 * count words: key, ratio per voice); waits for the device, like
+ * skred_bank_download_owners; zeros on a bank that never bent. */
+int  skred_bank_download_bend(skred_bank_t *bank, uint32_t *host_u32x2, int first, int count);
 
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *

@@ -8,7 +8,8 @@
  * starts a glide.  The glide array is no part of the bank the planner knows: no class, counter, lane word or report depends on it.
  * The calls tell the bank nothing either: the one plane word they store is voice_phase_inc, they store finite values only, and an
  * increment lists nobody (skred_bank_ctl.c has the measurement behind SKRED_CTL_INC_SCALE's rule).  The hook that clears a re-tagged
- * slot's words is in skred_bank_owner.c (sk_owner_tag_launch).
+ * slot's words is in skred_bank_owner.c (sk_owner_tag_launch).  On a bank that has a pitch-wheel array (skred_bank_bend.c) the three
+ * launches take it, and a bent voice's glide runs on its key.
  *
  * Out of scope: the fixed-point bank, the drop-in mode, deferred items and pattern steps.
  */
@@ -93,7 +94,7 @@ static int start_launch(skred_bank_t *b, const skred_glide_t *glide, const uint3
   memcpy(h + each_bytes, tags, (size_t)n * sizeof(uint32_t));
   const char *src = (const char *)sk_batch_send(b, &bt, bytes, 0, s);   /* (every byte is read by one workgroup) */
   if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)sk_launch_glide_start(b->d_glide, (const sk_glide_each_t *)src, slot_voices, voice_mask, d_slots,
+  const hipError_t e = (hipError_t)sk_launch_glide_start(b->d_glide, b->d_bend, (const sk_glide_each_t *)src, slot_voices, voice_mask, d_slots,
                                                          (const uint32_t *)(src + each_bytes), b->d_owner, n, d_count, b->n_voices,
                                                          b->d_ro[SKP_OSC], d_result, bt.cnt, bt.done, bt.seq, s);
   return sk_batch_end(&bt, e, who, s);                    /* (an increment lists nobody: the planner's reports stand) */
@@ -140,7 +141,7 @@ int skred_bank_glide_advance(skred_bank_t *b, int first, int count, int num_fram
     return SKRED_OK;
   }
   HIP_TRY(hipSetDevice(b->device));
-  const hipError_t e = (hipError_t)sk_launch_glide_advance(b->d_glide, b->d_ro[SKP_OSC], first, count, num_frames, d_result, (hipStream_t)stream);
+  const hipError_t e = (hipError_t)sk_launch_glide_advance(b->d_glide, b->d_bend, b->d_ro[SKP_OSC], first, count, num_frames, d_result, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "glide_advance launch -> %s", hipGetErrorString(e));
   return SKRED_OK;                                         /* (finite increments only: the planner's reports stand) */
 }
@@ -151,7 +152,7 @@ int skred_bank_glide_stop(skred_bank_t *b, int first, int count, int snap, void 
   if (rc) return rc;
   if (count == 0 || !b->d_glide) return SKRED_OK;          /* (no glide was ever started: every word is 0 already) */
   HIP_TRY(hipSetDevice(b->device));
-  const hipError_t e = (hipError_t)sk_launch_glide_stop(b->d_glide, b->d_ro[SKP_OSC], first, count, snap != 0, (hipStream_t)stream);
+  const hipError_t e = (hipError_t)sk_launch_glide_stop(b->d_glide, b->d_bend, b->d_ro[SKP_OSC], first, count, snap != 0, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "glide_stop launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
 }

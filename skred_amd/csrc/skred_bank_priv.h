@@ -13,6 +13,7 @@
  *   skred_bank_expr.c    channels and per-note expression: masked owner matches, per-entry controller values and filter coefficients
  *   skred_bank_pedal.c   pedals: note-offs held back per slot, sostenuto's latch, the pedal-up
  *   skred_bank_glide.c   portamento: per-voice glides, started under the owner guard, advanced and landed on the device
+ *   skred_bank_bend.c    the pitch wheel: absolute bends that keep the key's bits beside the sounding increment
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -207,6 +208,9 @@ struct skred_bank {
   /* portamento (skred_bank_glide.c), allocated and zeroed by the first call that starts a glide */
   sk_glide_t *d_glide;              /* [n_voices] target, rate_up, rate_down, carry per voice; target 0: not gliding; NULL: no glide was
                                        ever started, and the tag launches clear nothing; no render kernel reads it */
+  /* the pitch wheel (skred_bank_bend.c), allocated and zeroed by the first call that bends */
+  sk_bend_t *d_bend;                /* [n_voices] key, ratio per voice; key 0: not bent; NULL: no voice was ever bent, the tag launches
+                                       clear nothing and the glide launches run as they always ran; no render kernel reads it */
 };
 
 /* per-voice classification (host shadow) */
@@ -306,6 +310,10 @@ void sk_pedal_free(skred_bank_t *b);
  * glide[j]), the four named words as they stand, the reserved ones zero.  Pure host */
 void sk_glide_free(skred_bank_t *b);
 void sk_glide_pack(const skred_glide_t *glide, int n, const uint32_t *perm, sk_glide_each_t *out);
+/* skred_bank_bend.c: the bend array (skred_bank_destroy); n checked ratios as they travel -- out[j] = the bits of ratios[perm[j]]
+ * (perm NULL: ratios[j]).  Pure host */
+void sk_bend_free(skred_bank_t *b);
+void sk_bend_pack(const float *ratios, int n, const uint32_t *perm, uint32_t *out);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);

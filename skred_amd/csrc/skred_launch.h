@@ -21,6 +21,7 @@
  *   skred_expr_kernels.hip    sk_launch_match_find, sk_launch_match_stamps, sk_launch_ctl_match, sk_launch_ctl_owned_each_filter
  *   skred_pedal_kernels.hip   sk_launch_pedal_clear, sk_launch_pedal_stamps, sk_launch_pedal_latch, sk_launch_pedal_up
  *   skred_glide_kernels.hip   sk_launch_glide_clear, sk_launch_glide_start, sk_launch_glide_advance, sk_launch_glide_stop
+ *   skred_bend_kernels.hip    sk_launch_bend_clear, sk_launch_bend_match, sk_launch_bend_each, sk_launch_bend_range_clear
  *   skred_fx_pedal_kernels.hip  skx_launch_pedal_stamps, skx_launch_pedal_latch, skx_launch_pedal_up (sk_launch_pedal_clear by
  *                             skred_fx_owner.c too)
  *   skred_fx_glide_kernels.hip  skx_launch_glide_start, skx_launch_glide_advance, skx_launch_glide_stop (prototypes in
@@ -416,22 +417,51 @@ enum { SK_GLIDE_E_SET = 0, SK_GLIDE_E_RATE_UP, SK_GLIDE_E_RATE_DOWN, SK_GLIDE_E_
 typedef struct {
   uint32_t w[SK_GLIDE_E_WORDS];
 } sk_glide_each_t;
+/* The pitch wheel's two words per voice (below): the glide launches take the array too -- NULL on a bank without one, and then, as on
+ * every voice whose key word is 0, they store the bytes they always stored */
+enum { SK_BEND_KEY = 0, SK_BEND_RATIO, SK_BEND_WORDS = 2 };
+typedef struct {
+  uint32_t w[SK_BEND_WORDS];
+} sk_bend_t;
 /* glide[d_slots[k] + l] = 0, l < slot_voices, under sk_launch_owner_tag's list rule: launched behind it by a bank that has a glide
  * array */
 int sk_launch_glide_clear(sk_glide_t *glide, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
                           hipStream_t stream);
 /* entry k starts d_each[k]'s glide (16-byte aligned) on the voice_mask voices of d_slots[k] where that is a slot whose owner is
  * d_tags[k]; d_result[3] (may be NULL; zeroed on `stream` ahead of the kernel) += voices set gliding, starts withheld, slots whose
- * owner differs */
-int sk_launch_glide_start(sk_glide_t *glide, const sk_glide_each_t *d_each, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
-                          const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, sk_plane_t *osc,
-                          uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+ * owner differs.  bend != NULL: the BEND instantiation -- on a voice with a key the glide runs on the key, and the increment is
+ * stored again as key * ratio */
+int sk_launch_glide_start(sk_glide_t *glide, sk_bend_t *bend, const sk_glide_each_t *d_each, int slot_voices, uint64_t voice_mask,
+                          const int32_t *d_slots, const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count,
+                          int n_voices, sk_plane_t *osc, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq,
+                          hipStream_t stream);
 /* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] (may be NULL; zeroed on `stream` ahead
- * of the kernel) += voices still gliding, voices that arrived */
-int sk_launch_glide_advance(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int num_frames, uint32_t *d_result,
-                            hipStream_t stream);
-/* glide[first .. first + count) = 0; snap != 0: a gliding voice's increment = its target first */
-int sk_launch_glide_stop(sk_glide_t *glide, sk_plane_t *osc, int first, int count, int snap, hipStream_t stream);
+ * of the kernel) += voices still gliding, voices that arrived; bend as above */
+int sk_launch_glide_advance(sk_glide_t *glide, sk_bend_t *bend, sk_plane_t *osc, int first, int count, int num_frames,
+                            uint32_t *d_result, hipStream_t stream);
+/* glide[first .. first + count) = 0; snap != 0: a gliding voice's increment (bend: its key) = its target first */
+int sk_launch_glide_stop(sk_glide_t *glide, sk_bend_t *bend, sk_plane_t *osc, int first, int count, int snap, hipStream_t stream);
+
+/* ---- pitch wheel (skred_bank_bend.c -> skred_bend_kernels.hip; include/skred_amd.h: skred_bank_bend_match / _bend_owned_each /
+ * _bend_tags_each / _bend_clear) ----
+ * bend[n_voices]: key, ratio per voice (one 8-byte load).  Only these launches and the glide launches read or write it; the words
+ * they store into the planes are voice_phase_inc's (SKP_OSC word 0): finite non-zero products or a key's bits. */
+/* bend[d_slots[k] + l] = 0, l < slot_voices, under sk_launch_owner_tag's list rule: launched behind it by a bank that has a bend
+ * array */
+int sk_launch_bend_clear(sk_bend_t *bend, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
+                         hipStream_t stream);
+/* the absolute bend to `ratio` (fp32 bits) on the voice_mask voices of the slots of [first, first + count) whose owner matches;
+ * d_result[3] (may be NULL; zeroed on `stream` ahead of the kernel) += voices stored or restored, bends withheld, slots of the range
+ * that did not match */
+int sk_launch_bend_match(sk_bend_t *bend, uint32_t ratio, int slot_voices, uint64_t voice_mask, int first, int count,
+                         const uint32_t *owner, uint32_t value, uint32_t mask, sk_plane_t *osc, uint32_t *d_result, hipStream_t stream);
+/* entry k bends the voice_mask voices of d_slots[k] to d_ratios[k] (fp32 bits) where that is a slot whose owner is d_tags[k];
+ * d_result[3] as above, [2]: slots whose owner differs */
+int sk_launch_bend_each(sk_bend_t *bend, const uint32_t *d_ratios, int slot_voices, uint64_t voice_mask, const int32_t *d_slots,
+                        const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, sk_plane_t *osc,
+                        uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
+/* bend[first .. first + count) = 0; snap != 0: a bent voice's increment = its key first */
+int sk_launch_bend_range_clear(sk_bend_t *bend, sk_plane_t *osc, int first, int count, int snap, hipStream_t stream);
 
 /* ---- pedals on the fixed-point bank (skred_fx_pedal.c -> skred_fx_pedal_kernels.hip; include/skred_amd_fxpt.h:
  * skred_fxbank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up) ----

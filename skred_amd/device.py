@@ -51,12 +51,13 @@ ABI_SYMBOLS = [
     "skred_bank_stamp_owned_pedal", "skred_bank_release_tags_pedal", "skred_bank_pedal_latch", "skred_bank_pedal_up",
     "skred_bank_pedal_clear", "skred_bank_download_pedals",
     "skred_bank_glide_owned", "skred_bank_glide_tags", "skred_bank_glide_advance", "skred_bank_glide_stop", "skred_bank_download_glide",
+    "skred_bank_bend_match", "skred_bank_bend_owned_each", "skred_bank_bend_tags_each", "skred_bank_bend_clear", "skred_bank_download_bend",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
                     "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check",
                     "skred_filter_each_check", "skred_filter_coeffs",
-                    "skred_chan_check", "skred_pedal_check", "skred_glide_check"]
+                    "skred_chan_check", "skred_pedal_check", "skred_glide_check", "skred_bend_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -377,6 +378,12 @@ def load() -> C.CDLL:
     L.skred_bank_glide_advance.argtypes = [vp, i32, i32, i32, vp, vp]
     L.skred_bank_glide_stop.argtypes = [vp, i32, i32, i32, vp]
     L.skred_bank_download_glide.argtypes = [vp, vp, i32, i32]
+    L.skred_bend_check.argtypes = [vp, i32, i32, C.c_uint64]
+    L.skred_bank_bend_match.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, C.c_float, vp, vp]
+    L.skred_bank_bend_owned_each.argtypes = [vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_bend_tags_each.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
+    L.skred_bank_bend_clear.argtypes = [vp, i32, i32, i32, vp]
+    L.skred_bank_download_bend.argtypes = [vp, vp, i32, i32]
     _lib = L
     return L
 
@@ -461,6 +468,19 @@ def glide_check(glides, slot_voices: int, voice_mask: int) -> int:
     arr = glide_array(glides) if glides is not None else None
     return int(load().skred_glide_check(C.cast(arr, C.c_void_p) if arr is not None else None, len(arr) if arr is not None else 0,
                                         int(slot_voices), int(voice_mask)))
+
+
+def ratio_array(ratios) -> np.ndarray:
+    """The per-entry ratios of bend_owned_each / bend_tags_each as a contiguous float32 array."""
+    return np.ascontiguousarray(ratios, dtype=np.float32).reshape(-1)
+
+
+def bend_check(ratios, slot_voices: int, voice_mask: int) -> int:
+    """skred_bend_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for what the bending calls would refuse about K, the mask and
+    the ratios (None stands for a NULL array).  Pure host."""
+    arr = ratio_array(ratios) if ratios is not None else None
+    return int(load().skred_bend_check(arr.ctypes.data if arr is not None else None, len(arr) if arr is not None else 0,
+                                       int(slot_voices), int(voice_mask)))
 
 
 def ctl_each_check(each, ctls, voice_mask: int, slot_voices: Optional[int] = None) -> int:
@@ -1017,6 +1037,43 @@ class DeviceBank:
         count = self.n - first if count is None else count
         out = np.full((max(count, 0), 4), 0xDEADBEEF, np.uint32)
         _check(self.L.skred_bank_download_glide(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_glide")
+        return out
+
+    # ---- pitch wheel (include/skred_amd.h: skred_bank_bend_match / _bend_owned_each / _bend_tags_each / _bend_clear) ----
+    def bend_match(self, first: int, count: int, slot_voices: int, voice_mask: int, m: OwnerMatchC, ratio: float, d_result: int = 0,
+                   stream: int = 0):
+        """The channel wheel: the masked voices of every matching slot of the range sound at key * ratio; ratio 1.0 restores the key's
+        bits.  d_result (uint32[3], may be 0): voices stored or restored, bends withheld, slots that did not match."""
+        _check(self.L.skred_bank_bend_match(self.h, int(first), int(count), int(slot_voices), int(voice_mask), C.byref(m), float(ratio),
+                                            d_result or None, stream or None), "skred_bank_bend_match")
+
+    def bend_owned_each(self, ratios, slot_voices: int, voice_mask: int, d_slots: int, tags, d_count: int = 0, d_result: int = 0,
+                        stream: int = 0):
+        """Entry k bends the masked voices of d_slots[k] to ratios[k] where that slot's owner is tags[k].  d_result (uint32[3], may be
+        0): voices stored or restored, bends withheld, slots whose owner differs."""
+        arr, t = ratio_array(ratios), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_bend_owned_each(self.h, arr.ctypes.data, int(slot_voices), int(voice_mask), d_slots or None,
+                                                 t.ctypes.data, len(t), d_count or None, d_result or None, stream or None),
+               "skred_bank_bend_owned_each")
+
+    def bend_tags_each(self, ratios, first: int, count: int, slot_voices: int, voice_mask: int, tags, d_result: int = 0, stream: int = 0):
+        """Per-note bend by note id: ratios[k] reaches the lowest slot of the range that carries tags[k]."""
+        arr, t = ratio_array(ratios), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_bend_tags_each(self.h, arr.ctypes.data, int(first), int(count), int(slot_voices), int(voice_mask),
+                                                t.ctypes.data, len(t), d_result or None, stream or None), "skred_bank_bend_tags_each")
+
+    def bend_clear(self, first: int = 0, count: Optional[int] = None, snap: bool = False, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_bank_bend_clear(self.h, int(first), int(count), int(bool(snap)), stream or None), "skred_bank_bend_clear")
+
+    def download_bend(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The bend words of [first, first + count) as a (count, 2) uint32 array: key, ratio; waits for the device.  Zeros on a bank
+        that never bent."""
+        count = self.n - first if count is None else count
+        out = np.full((max(count, 0), 2), 0xDEADBEEF, np.uint32)
+        _check(self.L.skred_bank_download_bend(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_bend")
         return out
 
     def force_generic(self, on: bool = True):

@@ -1878,6 +1878,121 @@ def glide():
     db.close()
 
 
+def bend():
+    """The pitch wheel on bank_patch("3sk", 2**20), every copy sounding and tagged over 16 channels (tag = channel << 24 | slot + 1):
+    the `glide` mode's bank.  (a) skred_bank_bend_match of one channel beside skred_bank_ctl_match(SKRED_CTL_INC_SCALE) on the same
+    channel, and skred_bank_bend_tags_each of 256 notes beside skred_bank_ctl_tags_each(SKRED_EACH_INC_SCALE); (b) skred_bank_glide_advance
+    over the whole bank with 256 notes gliding, before the bank has a bend array and with one (the notes bent); (c) skred_bank_tag_slots
+    of 256 slots with the glide clear behind it and with the bend clear as the third; (d) the 64-frame block after a bend beside a
+    steady block.  Medians of 12 with minimum and maximum; host time held, and stream time between events."""
+    D = device
+    n, K, REPS, F, CHANNELS, NOTES = 1 << 20, 4, 12, 64, 16, 256
+    VOICES = 0xF
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = np.uint64(now - 40000)
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g); db.upload(bank)
+    slots = np.arange(0, n, K, dtype=np.int32)
+    idx = np.arange(len(slots), dtype=np.uint32)
+    tags = (((idx % CHANNELS) + 1) << 24 | (idx // CHANNELS + 1)).astype(np.uint32)
+    dl_all = torch.from_numpy(slots).cuda()
+    db.tag_slots(dl_all.data_ptr(), tags, K)
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    out = torch.zeros(F, 2, device="cuda")
+    at = np.flatnonzero(idx % CHANNELS == 2)[::7][:NOTES]                       # 256 notes of channel 3
+    note_tags, note_slots = tags[at].copy(), slots[at].copy()
+    dl_notes = torch.from_numpy(note_slots).cuda()
+    chan = D.owner_match(3 << 24, 0xFF000000)
+    up = 2.0 ** (1.0 / 12.0)
+    rate = 2.0 ** (1.0 / 96.0)
+    slide = D.glide_array([D.glide(D.GLIDE_FROM_SCALE, rate, 1.0 / rate, 2.0 ** (-7.0 / 12.0))] * NOTES)
+    scale_rec = [D.ctl(D.CTL_INC_SCALE, inc_scale=up)] * K
+    scale_each = D.ctl_each_array([D.ctl_each(D.EACH_INC_SCALE, inc_scale=up)] * NOTES)
+    ratios = np.full(NOTES, up, np.float32)
+    torch.cuda.synchronize()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def stats(x):
+        return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f})"
+
+    def series(call, before=None):
+        host, stream = [], []
+        for it in range(2 + REPS):
+            if before is not None:
+                before()
+            torch.cuda.synchronize()
+            h, s_ms = timed(call)
+            if it >= 2:
+                host.append(h); stream.append(s_ms)
+        return f"host time held {stats(host)}; stream time between events {stats(stream)}"
+
+    start = lambda: db.glide_tags(slide, 0, n, K, VOICES, note_tags, res.data_ptr())   # noqa: E731
+    land = lambda: db.glide_stop(0, n, True)                                           # noqa: E731
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, every copy sounding, tagged over {CHANNELS} channels ({n // K // CHANNELS} notes each); "
+          f"medians of {REPS}")
+    print(f"  (a) ctl_match(INC_SCALE) of one channel over the whole bank: "
+          f"{series(lambda: db.ctl_match(scale_rec, 0, n, VOICES, chan, res.data_ptr()))}; d_result = {res.cpu().numpy()[:3].tolist()}")
+    print(f"  (a) ctl_tags_each(INC_SCALE) of {NOTES} tags: "
+          f"{series(lambda: db.ctl_tags_each(None, scale_each, 0, n, VOICES, note_tags, K, res.data_ptr()))}; d_result = {res.cpu().numpy()[:3].tolist()}")
+    db.upload(bank)
+    start()
+    print(f"  (b) glide_advance by {F} frames over the whole bank, {NOTES * K} voices gliding, no bend array yet: "
+          f"{series(lambda: db.glide_advance(0, n, F, res.data_ptr()), lambda: (land(), start()))}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    land()
+    print(f"  (c) tag_slots of {NOTES} slots with the glide clear behind it: {series(lambda: db.tag_slots(dl_notes.data_ptr(), note_tags, K))}")
+    print(f"  (a) bend_match of one channel over the whole bank: "
+          f"{series(lambda: db.bend_match(0, n, K, VOICES, chan, up, res.data_ptr()))}; d_result = {res.cpu().numpy()[:3].tolist()}")
+    print(f"  (a) bend_match of one channel back to the centre: "
+          f"{series(lambda: db.bend_match(0, n, K, VOICES, chan, 1.0, res.data_ptr()), lambda: db.bend_match(0, n, K, VOICES, chan, up))}; "
+          f"d_result = {res.cpu().numpy()[:3].tolist()}")
+    print(f"  (a) bend_tags_each of {NOTES} tags: "
+          f"{series(lambda: db.bend_tags_each(ratios, 0, n, K, VOICES, note_tags, res.data_ptr()))}; d_result = {res.cpu().numpy()[:3].tolist()}")
+    land(); start()
+    print(f"  (b) glide_advance by {F} frames over the whole bank, {NOTES * K} voices gliding under a bend: "
+          f"{series(lambda: db.glide_advance(0, n, F, res.data_ptr()), lambda: (land(), start()))}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    land()
+    print(f"  (b) glide_advance by {F} frames over the whole bank with a bend array, nothing gliding: "
+          f"{series(lambda: db.glide_advance(0, n, F, res.data_ptr()))}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    print(f"  (c) tag_slots of {NOTES} slots with the bend clear as the third launch: {series(lambda: db.tag_slots(dl_notes.data_ptr(), note_tags, K))}")
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+
+    db.upload(bank)
+    db.bend_clear(0, n, False)
+    for _ in range(8):
+        block()
+    steady = [block() for _ in range(REPS)]
+    after = []
+    for k in range(REPS):
+        block()
+        db.bend_match(0, n, K, VOICES, chan, 2.0 ** ((k % 5 - 2) / 24.0) if k % 5 != 2 else up, res.data_ptr())
+        after.append(block())
+    moved = res.cpu().numpy()[:3].tolist()
+    db.bend_match(0, n, K, VOICES, chan, 1.0)
+    steady2 = [block() for _ in range(REPS)]
+    print(f"  (d) the {F}-frame block after bend_match (d_result = {moved}): {stats(after)}; a steady block before: {stats(steady)}; "
+          f"after the centre: {stats(steady2)}; kernel {db.last_kernel()}, list violations {db.list_violations()}")
+    db.close()
+
+
 def fxpedal():
     """Pedals on bank_fx(2**20), every voice sounding and tagged over 16 channels (tag = channel << 24 | voice // 16 + 1), 256
     note-offs of one channel held back, then the pedal goes up: the `pedal` mode on the fixed-point bank.  (a) each new call beside
@@ -2023,7 +2138,7 @@ def fxglide():
 
 
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
