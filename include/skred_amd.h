@@ -1330,8 +1330,9 @@ int  skred_bank_download_glide(skred_bank_t *bank, uint32_t *host_u32x4, int fir
  * Limits: a SKRED_CTL_PHASE_INC / _INC_SCALE store on a bent voice is overwritten by the next bend (which multiplies the key it
  * captured): bend with these calls instead.  A release leaves the words alone, as for glides: a released note follows the wheel
  * through its tail.  Bends belong with tagged notes.  The host view of voice_phase_inc goes stale; skred_bank_download_ctl reads it
- * back.  On a shard: through skred_shard_bank(), with that rank's local indices.  This section is the float bank's alone: a
- * fixed-point twin, the drop-in mode, deferred items and pattern steps are follow-ups. */
+ * back.  On a shard: through skred_shard_bank(), with that rank's local indices.  The fixed-point twin is
+ * include/skred_amd_fxpt.h's section "pitch wheel" (skred_fxbank_bend_*: Q24 ratios, integer products); the drop-in mode, deferred
+ * items and pattern steps are follow-ups. */
 /* Pure host: SKRED_OK, or what the bending calls refuse about K, the mask and the ratios, in this order.  SKRED_E_BAD_ARG: a NULL
  * array; SKRED_E_RANGE: a bad K (not a power of two in 1 .. 64); SKRED_E_BAD_ARG: a voice_mask that is 0 or has bits at or above K, a
  * ratio that is not finite or <= 0, n < 0. */

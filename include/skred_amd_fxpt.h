@@ -713,7 +713,8 @@ int  skred_fxbank_download_pedals(skred_fxbank_t *fx, uint32_t *host_u32, int fi
  * skred_fxbank_download_glide  the words of [first, first + count) into host_u32x4 (4 * count words); waits for the device; zeros on
  *                            a bank without the array.
  * LIMITS, documented, not fixed: a SKRED_CTL_PHASE_INC / _INC_SCALE bend of a gliding voice is undone on arrival (the target's bits
- * are stored); the host view of phase_inc goes stale -- skred_fxbank_download_params reads it back; glides belong with tagged notes
+ * are stored) -- a bend of the section "pitch wheel" below is not: the glide then runs on the key and lands on target * ratio;
+ * the host view of phase_inc goes stale -- skred_fxbank_download_params reads it back; glides belong with tagged notes
  * (an untagged voice cannot be reached).  Out of scope: the drop-in mode, deferred items, pattern steps, per-frame glides. */
 #define SKRED_FX_GLIDE_FROM_SCALE (1u << 0)
 #define SKRED_FX_GLIDE_TO_SCALE   (1u << 1)
@@ -733,6 +734,95 @@ int  skred_fxbank_glide_tags(skred_fxbank_t *fx, const skred_fx_glide_t *glide, 
 int  skred_fxbank_glide_advance(skred_fxbank_t *fx, int first, int count, int num_frames, uint32_t *d_result, void *stream);
 int  skred_fxbank_glide_stop(skred_fxbank_t *fx, int first, int count, int snap, void *stream);
 int  skred_fxbank_download_glide(skred_fxbank_t *fx, uint32_t *host_u32x4, int first, int count);
+
+/* ---- pitch wheel: bends that return to the key's bits and compose with glides, in integers ---------------------------------------
+ *
+ * The fixed-point twin of the float bank's section "pitch wheel" (include/skred_amd.h: skred_bend_check .. skred_bank_download_bend),
+ * per voice -- this bank has no slots, so no slot_voices and no masks.  THIS is the place of record for the integer definition.  The
+ * only other bend route on this bank is SKRED_CTL_INC_SCALE / SKRED_EACH_INC_SCALE, phase_inc = (phase_inc * q16) >> 16 on whatever
+ * the device holds, and it (a) never comes back: every message truncates, so up by r and back by 1/r leaves a smaller increment, the
+ * loss has one sign and grows with every wheel message, and after a sweep the channel is flat against a freshly struck key; (b) is
+ * relative: the host must remember the last position per channel and send ratios of ratios, and a note stolen and struck again between
+ * two messages gets the wrong one; (c) is coarse: Q16 resolves 0.026 cent at unity, a 14-bit wheel over +-2 semitones steps by 0.024
+ * cent, so adjacent positions collide, and on small increments (inc * 65542) >> 16 == inc, the stall the glide section names; (d) is
+ * undone on arrival when the voice glides.  A bend of this section is ABSOLUTE: the wheel at centre gives the key's bits, on every
+ * machine, after any number of messages.
+ *
+ * STATE.  bend[n_voices] is an array of two uint32 per voice in device memory (one 8-byte word): key, ratio_q24.  key == 0 means "not
+ * bent": a phase_inc of 0 is a voice without pitch and is never a legal key.  The first skred_fxbank_bend_match / _bend_owned_each /
+ * _bend_tags_each call with work to do allocates the array (8 bytes per voice) beside the owner, pedal and glide arrays and zero-fills
+ * it, and ensures the owner array too; that call waits for the device once.  It is freed with the bank.  Only the calls of this
+ * section, the clear below and the glide calls read or write it, and the only bank word they store is phase_inc, as a word store: its
+ * neighbours in the plane keep their bits.  No render kernel reads the array; a bank that never bends allocates nothing more and
+ * launches nothing more than it did before this section existed.
+ *
+ * RATIO.  Q24: SKRED_FX_BEND_ONE = 1 << 24 is the centre; legal values are 1 .. 0xFFFFFFFF (just under 8 octaves up).  Q24 and not
+ * SKRED_CTL_INC_SCALE's Q16 because Q16 cannot tell adjacent positions of a 14-bit wheel apart (above): Q24 resolves 0.0001 cent at
+ * unity.  The product key * ratio_q24 is below 2^64 for every key and ratio, so it is formed exactly in 64 bits.
+ *
+ * THE RULE.  The absolute bend of voice v to r, with inc = phase_inc as the device holds it:
+ *   1. k = key[v] ? key[v] : inc -- the first bend captures the key.
+ *   2. r == SKRED_FX_BEND_ONE: where key[v] != 0, phase_inc = key[v] is stored; both words are cleared.  The voice counts as restored
+ *      only if key[v] != 0: the centre on a voice that was never bent stores nothing and counts nothing.
+ *   3. Otherwise p = ((uint64)k * r) >> 24.  k == 0, p == 0 or p > 0xFFFFFFFF: the bend is WITHHELD and counted, and the voice and its
+ *      words stay exactly as they were.  Else phase_inc = p, key[v] = k, ratio[v] = r.  Exactly 0xFFFFFFFF and exactly 1 are stored.
+ * The same message twice gives the same bits twice; any sequence of bends followed by the centre gives the key's bits and zero words.
+ *
+ * A NEW NOTE CLEARS THE WORDS.  Once the array exists, every tag launch of the bank (skred_fxbank_tag_list, the tags of
+ * skred_fxbank_note_on_channel) is followed on its stream by a launch that zeroes the two words of every voice it tagged -- the same
+ * list under the same list rule, right where the pedal word and the glide words are cleared.  Without it a thief's first bend would
+ * find its victim's key and the centre would restore it.  A note struck under a deflected wheel is therefore, in this order:
+ * skred_fxbank_note_on_channel, skred_fxbank_bend_tags_each with the channel's ratio, optionally skred_fxbank_glide_tags(FROM_SCALE).
+ *
+ * GLIDES UNDER A BEND.  On a bank that has a bend array the glide calls read it.  On a voice with key != 0, every place the portamento
+ * section says `inc` reads and writes `key` instead: FROM_SCALE: target = key, key = (key * scale_q16) >> 16; TO_SCALE: target =
+ * ((gliding ? the old target : key) * scale_q16) >> 16; TO_INC unchanged; the advance's steps, its arrive-at-once test and its
+ * "stored only if it differs" rule run on key, and on arrival key = target; a stop with snap: key = target.  The sounding increment is
+ * then stored again as phase_inc = ((uint64)key * ratio_q24) >> 24 at three points: after a start that was not withheld, after every
+ * advance of a gliding voice, after a snap.  Where that product is 0 or above 0xFFFFFFFF only that one store is withheld, uncounted;
+ * key and the glide words stand.  So a glide under a bend lands on (target * ratio_q24) >> 24, and the centre then gives the target's
+ * bits.  Voices with key == 0, and banks without a bend array, store the bytes they stored before this section existed.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_fxbank_update; host arrays travel through the staging ring; nothing
+ * waits for the device except the download and the first allocation; results are pure functions of the state, whatever the order of
+ * arrival; one stream at a time per bank.  On a shard: through skred_fxshard_bank(), with that rank's local indices.  Every d_result
+ * is a device uint32[3], may be NULL, and is cleared on the stream ahead of the kernel: [0] voices stored or restored, [1] bends
+ * withheld, [2] see each call.
+ *
+ * skred_fx_bend_check          pure host: SKRED_OK, or SKRED_E_BAD_ARG for a NULL array, n < 0, or a ratio of 0.
+ * skred_fxbank_bend_match      the channel wheel: THE RULE to ratio_q24 on every voice of [first, first + count) with owner != 0 and
+ *                              (owner & m->mask) == m->value; geometry, guard and counting as skred_fxbank_ctl_match.  d_result[2]:
+ *                              voices of the range that did not match.  It ships no bytes and takes no slot of the ring.  Refused, in
+ *                              this order: NULL bank or match, ratio 0, what skred_owner_match_check refuses, SKRED_E_RANGE for an
+ *                              empty range or one outside the bank.
+ * skred_fxbank_bend_owned_each looks at the entries below min(n, *d_count_or_null); entry k bends d_voices[k] to ratios_q24[k] where
+ *                              that is a voice of the bank whose owner is tags[k].  d_result[2]: voices whose owner differs.  A voice
+ *                              listed twice is UNSPECIFIED.  Refused, in skred_fxbank_glide_owned's order: NULL bank or list, what
+ *                              skred_owner_tags_check refuses (NULL tags, n < 0, a zero tag), n > INT32_MAX / 64, what
+ *                              skred_fx_bend_check refuses.  n == 0: SKRED_OK, nothing is done.
+ * skred_fxbank_bend_tags_each  bends by note id, built as skred_fxbank_glide_tags is: skred_fxbank_release_tags' find pass over
+ *                              [first, first + count) into the same scratch -- the lowest voice of the range per tag, or -1 -- then
+ *                              the call above on that list.  ratios_q24[k] goes with tags[k]: the tags travel sorted, and the ratios
+ *                              are permuted with them on the host.  Tags unique, none zero, n <= SKRED_OWNER_MAX_TAGS.  d_result[2] is
+ *                              0.  Refused: NULL bank, the tags, n and the ratios as above, then SKRED_E_RANGE for an empty range or
+ *                              one outside the bank.
+ * skred_fxbank_bend_clear      bend[first .. first + count) = 0 on `stream`; snap != 0: a bent voice's phase_inc = its key first.
+ *                              Nothing to do on a bank without the array.  SKRED_E_RANGE: count < 0 or a range outside the bank.
+ * skred_fxbank_download_bend   the words of [first, first + count) into host_u32x2 (2 * count words); waits for the device; zeros on a
+ *                              bank that never bent.
+ * LIMITS, documented, not fixed: a SKRED_CTL_PHASE_INC / _INC_SCALE store on a bent voice is overwritten by the next bend, centre or
+ * glide step of that voice (the key's bits rule); the host view of phase_inc goes stale -- skred_fxbank_download_params reads it
+ * back; the per-note calls belong with tagged notes.  Out of scope: the drop-in mode, deferred items, pattern steps. */
+#define SKRED_FX_BEND_ONE (1u << 24)
+int  skred_fx_bend_check(const uint32_t *ratios_q24, int n);
+int  skred_fxbank_bend_match(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, uint32_t ratio_q24, uint32_t *d_result,
+                             void *stream);
+int  skred_fxbank_bend_owned_each(skred_fxbank_t *fx, const uint32_t *ratios_q24, const int32_t *d_voices, const uint32_t *tags, int n,
+                                  const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+int  skred_fxbank_bend_tags_each(skred_fxbank_t *fx, const uint32_t *ratios_q24, int first, int count, const uint32_t *tags, int n,
+                                 uint32_t *d_result, void *stream);
+int  skred_fxbank_bend_clear(skred_fxbank_t *fx, int first, int count, int snap, void *stream);
+int  skred_fxbank_download_bend(skred_fxbank_t *fx, uint32_t *host_u32x2, int first, int count);
 
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);

@@ -8,7 +8,8 @@
  * and tags' way through the batch path (skred_fx_stage.c), the launches.  The two starting calls ship their entries and tags in
  * batches; the advance and the stop ship no bytes and so take no slot of the ring.  Nothing here waits for the device except the
  * download and the allocation of the array by the first call that starts a glide.  The hook that clears a re-tagged voice's words is in
- * skred_fx_owner.c (skx_owner_tag_launch).
+ * skred_fx_owner.c (skx_owner_tag_launch).  Every glide launch takes the bank's pitch-wheel array (skred_fx_bend.c; NULL on a bank that
+ * never bent, and then the kernels are the ones they were).
  *
  * Out of scope: the drop-in mode, deferred items, pattern steps and per-frame glides.
  */
@@ -96,7 +97,7 @@ int skred_fxbank_glide_owned(skred_fxbank_t *fx, const skred_fx_glide_t *glide, 
   memcpy(h + each_bytes, tags, (size_t)n * sizeof(uint32_t));
   const char *src = (const char *)skx_batch_send(&bt, bytes, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)skx_launch_glide_start(fx->d_glide, (const skx_glide_each_t *)src, d_voices, (const uint32_t *)(src + each_bytes),
+  const hipError_t e = (hipError_t)skx_launch_glide_start(fx->d_glide, fx->d_bend, (const skx_glide_each_t *)src, d_voices, (const uint32_t *)(src + each_bytes),
                                                           fx->d_owner, n, d_count_or_null, fx->n_voices, fx->d_ro[SKX_OSC], d_result, s);
   return skx_batch_end(&bt, e, "fx glide_owned", s);
 }
@@ -127,7 +128,7 @@ int skred_fxbank_glide_tags(skred_fxbank_t *fx, const skred_fx_glide_t *glide, i
   const skx_glide_each_t *src = (const skx_glide_each_t *)skx_batch_send(&ent, bytes, s);
   /* entry j is the lowest voice that carries sorted[j], or -1: the guard holds on every entry that is a voice */
   if (src && e == hipSuccess)
-    e = (hipError_t)skx_launch_glide_start(fx->d_glide, src, fx->d_owner_found, (const uint32_t *)find.sl->d + 2 * (size_t)n, fx->d_owner, n,
+    e = (hipError_t)skx_launch_glide_start(fx->d_glide, fx->d_bend, src, fx->d_owner_found, (const uint32_t *)find.sl->d + 2 * (size_t)n, fx->d_owner, n,
                                            NULL, fx->n_voices, fx->d_ro[SKX_OSC], d_result, s);
   rc = skx_batch_end(&ent, e, "fx glide_tags", s);
   const int rc_find = skx_batch_end(&find, hipSuccess, "fx glide_tags", s);
@@ -147,7 +148,7 @@ int skred_fxbank_glide_advance(skred_fxbank_t *fx, int first, int count, int num
     return SKRED_OK;
   }
   HIP_TRY(hipSetDevice(fx->device));
-  const hipError_t e = (hipError_t)skx_launch_glide_advance(fx->d_glide, fx->d_ro[SKX_OSC], first, count, num_frames, d_result, (hipStream_t)stream);
+  const hipError_t e = (hipError_t)skx_launch_glide_advance(fx->d_glide, fx->d_bend, fx->d_ro[SKX_OSC], first, count, num_frames, d_result, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx glide_advance launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
 }
@@ -158,7 +159,7 @@ int skred_fxbank_glide_stop(skred_fxbank_t *fx, int first, int count, int snap, 
   if (rc) return rc;
   if (count == 0 || !fx->d_glide) return SKRED_OK;         /* (no glide was ever started: every word is 0 already) */
   HIP_TRY(hipSetDevice(fx->device));
-  const hipError_t e = (hipError_t)skx_launch_glide_stop(fx->d_glide, fx->d_ro[SKX_OSC], first, count, snap != 0, (hipStream_t)stream);
+  const hipError_t e = (hipError_t)skx_launch_glide_stop(fx->d_glide, fx->d_bend, fx->d_ro[SKX_OSC], first, count, snap != 0, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx glide_stop launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
 }

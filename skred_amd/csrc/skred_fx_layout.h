@@ -140,4 +140,13 @@ typedef struct { uint32_t w[SKX_GLIDE_WORDS]; } skx_glide_t;   /* 16 bytes */
 #define SKX_GLIDE_TO_INC     (1u << 2)
 enum { SKX_GLIDE_E_SET = 0, SKX_GLIDE_E_UP, SKX_GLIDE_E_DOWN, SKX_GLIDE_E_SCALE, SKX_GLIDE_E_TARGET_INC, SKX_GLIDE_E_WORDS = 8 };
 typedef struct { uint32_t w[SKX_GLIDE_E_WORDS]; } skx_glide_each_t;   /* 32 bytes */
+
+/* ---- pitch wheel (skred_fx_bend_kernels.hip; include/skred_amd_fxpt.h: skred_fxbank_bend_match / _bend_owned_each / _bend_tags_each /
+ * _bend_clear) ----
+ * bend[n_voices]: two words per voice (one 8-byte load) beside the glide array: key (the unbent phase_inc; 0 "not bent") and ratio_q24.
+ * The float bank's sk_bend_t has the same shape (checked in skred_fx_bend.c): its clear kernel serves this array too.  The glide
+ * launches take the array as well -- NULL on a bank without one */
+enum { SKX_BEND_KEY = 0, SKX_BEND_RATIO, SKX_BEND_WORDS = 2 };
+typedef struct { uint32_t w[SKX_BEND_WORDS]; } skx_bend_t;     /* 8 bytes */
+#define SKX_BEND_ONE (1u << 24)    /* the wheel at centre (equals SKRED_FX_BEND_ONE: checked in skred_fx_bend.c) */
 #endif

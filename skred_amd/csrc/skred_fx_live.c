@@ -52,6 +52,7 @@ void skx_live_free(skred_fxbank_t *fx) {
   skx_owner_free(fx);
   skx_pedal_free(fx);
   skx_glide_free(fx);
+  skx_bend_free(fx);
 }
 
 /* note-ons / note-offs of voices the host names: ids only (stamping a voice twice with the same clock is idempotent) */

@@ -55,6 +55,8 @@ int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint
   if (e == hipSuccess && fx->d_pedal) e = (hipError_t)sk_launch_pedal_clear(fx->d_pedal, d_voices, n, d_count, 1, fx->n_voices, s);
   /* ... and does not inherit a glide (skred_fx_glide.c): the float bank's clear kernel, the array's shape being the same */
   if (e == hipSuccess && fx->d_glide) e = (hipError_t)sk_launch_glide_clear((sk_glide_t *)fx->d_glide, d_voices, n, d_count, 1, fx->n_voices, s);
+  /* ... nor a bend (skred_fx_bend.c): a thief's first bend would take its victim's key, and the centre would restore it */
+  if (e == hipSuccess && fx->d_bend) e = (hipError_t)sk_launch_bend_clear((sk_bend_t *)fx->d_bend, d_voices, n, d_count, 1, fx->n_voices, s);
   return skx_batch_end(&bt, e, who, s);
 }
 

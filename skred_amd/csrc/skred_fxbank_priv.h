@@ -1,7 +1,8 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
  * skred_fx_stage.c: the staging ring and the batch path; skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c:
  * voice stealing; skred_fx_owner.c: note owners; skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression;
- * skred_fx_pedal.c: pedals; skred_fx_glide.c: portamento; channel polyphony lives in skred_fx_steal.c). */
+ * skred_fx_pedal.c: pedals; skred_fx_glide.c: portamento; skred_fx_bend.c: the pitch wheel; channel polyphony lives in
+ * skred_fx_steal.c). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -55,6 +56,7 @@ struct skred_fxbank {
   uint32_t *d_match_pair;                    /* ... and behind that the two words the count pass of skred_fxbank_find_match fills */
   uint32_t *d_pedal;                         /* pedals (skred_fx_pedal.c): one word per voice, SKRED_PEDAL_*; NULL until the first call that needs it */
   skx_glide_t *d_glide;                      /* portamento (skred_fx_glide.c): four words per voice; NULL until the first call that starts a glide */
+  skx_bend_t *d_bend;                        /* the pitch wheel (skred_fx_bend.c): two words per voice; NULL until the first call that bends */
   long long *d_mix; size_t mix_cap;
   int32_t *d_stems; size_t stems_cap;
   uint64_t count;
@@ -123,6 +125,10 @@ void skx_pedal_free(skred_fxbank_t *fx);
  * j), the five named words as they stand, the rest zero.  Pure host */
 void skx_glide_free(skred_fxbank_t *fx);
 void skx_glide_pack(const skred_fx_glide_t *glide, int n, const uint32_t *perm, skx_glide_each_t *out);
+/* skred_fx_bend.c: the bend array, freed with the bank; and the checked ratios as they travel -- out[j] = ratios[perm[j]] (perm NULL:
+ * j).  Pure host */
+void skx_bend_free(skred_fxbank_t *fx);
+void skx_bend_pack(const uint32_t *ratios_q24, int n, const uint32_t *perm, uint32_t *out);
 /* skred_fx_ctl.c: the checked record as it travels (the reserved words carry the reciprocals).  Pure host */
 void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
 /* skred_fx_expr.c: the checked entries as they travel -- out[j] = each[perm[j]] (perm NULL: j), the named values word for word, the
@@ -179,16 +185,29 @@ int skx_launch_ctl_owned_each_filter(const skx_ctl_t *d_rec, const skx_each_t *d
                                      const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
                                      skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
 /* skred_fx_glide_kernels.hip (the clear behind a tag launch is the float bank's sk_launch_glide_clear at slot_voices = 1,
- * skred_launch.h).  d_each: 16-byte aligned; each d_result may be NULL and is zeroed on `stream` ahead of its kernel */
+ * skred_launch.h).  d_each: 16-byte aligned; each d_result may be NULL and is zeroed on `stream` ahead of its kernel.  bend: the
+ * bank's pitch-wheel array, or NULL on a bank without one (the BEND = false instantiations: the kernels as they were).  With the
+ * array, on a voice whose key word is not 0 the glide runs on the key, and phase_inc is stored again as (key * ratio_q24) >> 24 */
 /* entry k starts d_each[k]'s glide on d_voices[k] where that is a voice whose owner is d_tags[k]; d_result[3] += voices set gliding,
  * starts withheld, voices whose owner differs */
-int skx_launch_glide_start(skx_glide_t *glide, const skx_glide_each_t *d_each, const int32_t *d_voices, const uint32_t *d_tags,
+int skx_launch_glide_start(skx_glide_t *glide, skx_bend_t *bend, const skx_glide_each_t *d_each, const int32_t *d_voices, const uint32_t *d_tags,
                            const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, skx_plane_t *osc, uint32_t *d_result,
                            hipStream_t stream);
 /* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] += voices still gliding, voices that arrived */
-int skx_launch_glide_advance(skx_glide_t *glide, skx_plane_t *osc, int first, int count, int num_frames, uint32_t *d_result,
+int skx_launch_glide_advance(skx_glide_t *glide, skx_bend_t *bend, skx_plane_t *osc, int first, int count, int num_frames, uint32_t *d_result,
                              hipStream_t stream);
-/* glide[first .. first + count) = 0; snap != 0: a gliding voice's increment = its target first */
-int skx_launch_glide_stop(skx_glide_t *glide, skx_plane_t *osc, int first, int count, int snap, hipStream_t stream);
+/* glide[first .. first + count) = 0; snap != 0: a gliding voice's increment (bend: its key) = its target first */
+int skx_launch_glide_stop(skx_glide_t *glide, skx_bend_t *bend, skx_plane_t *osc, int first, int count, int snap, hipStream_t stream);
+/* skred_fx_bend_kernels.hip (the clear behind a tag launch is the float bank's sk_launch_bend_clear at slot_voices = 1, skred_launch.h).
+ * Each d_result[3] may be NULL and is zeroed on `stream` ahead of its kernel: voices stored or restored, bends withheld, and */
+/* ... the absolute bend to ratio_q24 on the voices of [first, first + count) (inside the bank) whose owner matches; [2]: voices of
+ * the range that did not match */
+int skx_launch_bend_match(skx_bend_t *bend, uint32_t ratio_q24, int first, int count, const uint32_t *owner, uint32_t value, uint32_t mask,
+                          skx_plane_t *osc, uint32_t *d_result, hipStream_t stream);
+/* ... entry k bends d_voices[k] to d_ratios[k] where that is a voice whose owner is d_tags[k]; [2]: voices whose owner differs */
+int skx_launch_bend_each(skx_bend_t *bend, const uint32_t *d_ratios, const int32_t *d_voices, const uint32_t *d_tags, const uint32_t *owner,
+                         int n, const uint32_t *d_count, int n_voices, skx_plane_t *osc, uint32_t *d_result, hipStream_t stream);
+/* bend[first .. first + count) = 0; snap != 0: a bent voice's increment = its key first */
+int skx_launch_bend_range_clear(skx_bend_t *bend, skx_plane_t *osc, int first, int count, int snap, hipStream_t stream);
 
 #endif

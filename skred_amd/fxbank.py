@@ -49,10 +49,12 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_pedal_up", "skred_fxbank_pedal_clear", "skred_fxbank_download_pedals",
                   "skred_fxbank_glide_owned", "skred_fxbank_glide_tags", "skred_fxbank_glide_advance", "skred_fxbank_glide_stop",
                   "skred_fxbank_download_glide",
+                  "skred_fxbank_bend_match", "skred_fxbank_bend_owned_each", "skred_fxbank_bend_tags_each", "skred_fxbank_bend_clear",
+                  "skred_fxbank_download_bend",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
 FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
                        "skred_fx_ctl_each_check", "skred_fx_filter_each_check", "skred_fx_chan_check", "skred_fx_pedal_check",
-                       "skred_fx_glide_check"]                                                                     # pure host: no bank, no device
+                       "skred_fx_glide_check", "skred_fx_bend_check"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -72,6 +74,7 @@ EACH_INC_SCALE, EACH_AMP_SCALE, EACH_VELOCITY, EACH_PAN = 1, 2, 4, 8
 EACH_ALL = 15
 CHAN_NO_CAP = 0xFFFFFFFF                          # SKRED_CHAN_NO_CAP: a cap that never limits
 FX_GLIDE_FROM_SCALE, FX_GLIDE_TO_SCALE, FX_GLIDE_TO_INC = 1, 2, 4   # SKRED_FX_GLIDE_*: exactly one per entry
+FX_BEND_ONE = 1 << 24                             # SKRED_FX_BEND_ONE: the wheel at centre, as a Q24 ratio
 FX_CTL_SPAN = 256                                 # voices or entries per workgroup of the controller and guarded-stamp kernels
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
@@ -229,6 +232,23 @@ def glide_array(glides):
     return (FxGlideC * len(glides))(*glides)
 
 
+def bend_ratios(ratios_q24) -> np.ndarray:
+    """Q24 ratios as the calls take them: a contiguous uint32 array (FX_BEND_ONE = 1 << 24 is the centre)."""
+    return np.ascontiguousarray(np.asarray(ratios_q24, np.uint32).reshape(-1))
+
+
+def bend_ratio_q24(semitones: float) -> int:
+    """The wheel at `semitones` as a Q24 ratio; 0 semitones is exactly FX_BEND_ONE."""
+    return max(1, min(0xFFFFFFFF, int(round(2.0 ** (float(semitones) / 12.0) * (1 << 24)))))
+
+
+def fx_bend_check(ratios_q24, n: Optional[int] = None) -> int:
+    """skred_fx_bend_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device.  ``ratios_q24`` None: a NULL array."""
+    r = bend_ratios(ratios_q24) if ratios_q24 is not None else None
+    n = (len(r) if r is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_bend_check(r.ctypes.data if r is not None else None, int(n)))
+
+
 def fx_glide_check(glides, n: Optional[int] = None) -> int:
     """skred_fx_glide_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device.  ``glides`` None: a NULL array."""
     arr = glide_array(glides) if glides is not None else None
@@ -372,6 +392,12 @@ def _bind(L):
     L.skred_fxbank_glide_advance.argtypes = [vp, i32, i32, i32, vp, vp]
     L.skred_fxbank_glide_stop.argtypes = [vp, i32, i32, i32, vp]
     L.skred_fxbank_download_glide.argtypes = [vp, vp, i32, i32]
+    L.skred_fx_bend_check.argtypes = [vp, i32]
+    L.skred_fxbank_bend_match.argtypes = [vp, i32, i32, vp, C.c_uint32, vp, vp]
+    L.skred_fxbank_bend_owned_each.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_bend_tags_each.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+    L.skred_fxbank_bend_clear.argtypes = [vp, i32, i32, i32, vp]
+    L.skred_fxbank_download_bend.argtypes = [vp, vp, i32, i32]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -765,6 +791,41 @@ class DeviceFxBank:
         count = self.n - first if count is None else count
         out = np.full((max(count, 0), 4), 0xABABABAB, np.uint32)
         _check(self.L.skred_fxbank_download_glide(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_glide")
+        return out
+
+    # ---- pitch wheel (include/skred_amd_fxpt.h: skred_fxbank_bend_match / _bend_owned_each / _bend_tags_each / _bend_clear) ----
+    def bend_match(self, first: int, count: int, value: int, mask: int, ratio_q24: int, d_result: int = 0, stream: int = 0):
+        """The channel wheel: the absolute bend to ratio_q24 (FX_BEND_ONE: the centre, which gives the key's bits back) on every
+        matching voice of the range.  d_result (uint32[3], may be 0) = stored or restored, withheld, did not match."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_bend_match(self.h, int(first), int(count), C.byref(m), int(ratio_q24), d_result or None, stream or None),
+               "skred_fxbank_bend_match")
+
+    def bend_owned_each(self, ratios_q24, d_voices: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """Entry k bends d_voices[k] to ratios_q24[k] where that voice's owner is tags[k].  d_result (uint32[3], may be 0) = stored or
+        restored, withheld, voices whose owner differs."""
+        r, t = bend_ratios(ratios_q24), _tags(tags)
+        assert len(r) == len(t), "one ratio per tag"
+        _check(self.L.skred_fxbank_bend_owned_each(self.h, r.ctypes.data, d_voices or None, t.ctypes.data, len(t), d_count or None,
+                                                   d_result or None, stream or None), "skred_fxbank_bend_owned_each")
+
+    def bend_tags_each(self, ratios_q24, first: int, count: int, tags, d_result: int = 0, stream: int = 0):
+        """Bends by note id: ratios_q24[k] on the lowest voice of the range that carries tags[k]."""
+        r, t = bend_ratios(ratios_q24), _tags(tags)
+        assert len(r) == len(t), "one ratio per tag"
+        _check(self.L.skred_fxbank_bend_tags_each(self.h, r.ctypes.data, int(first), int(count), t.ctypes.data, len(t), d_result or None,
+                                                  stream or None), "skred_fxbank_bend_tags_each")
+
+    def bend_clear(self, first: int = 0, count: Optional[int] = None, snap: bool = False, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_fxbank_bend_clear(self.h, int(first), int(count), int(bool(snap)), stream or None), "skred_fxbank_bend_clear")
+
+    def download_bend(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The bend words of [first, first + count) as a (count, 2) uint32 array: key, ratio_q24; waits for the device.  Zeros on a
+        bank that never bent."""
+        count = self.n - first if count is None else count
+        out = np.full((max(count, 0), 2), 0xABABABAB, np.uint32)
+        _check(self.L.skred_fxbank_download_bend(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_bend")
         return out
 
 

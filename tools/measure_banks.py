@@ -2137,8 +2137,86 @@ def fxglide():
     db.close(); bare.close()
 
 
+def fxbend():
+    """The pitch wheel on bank_fx(2**20), every voice sounding and tagged over 16 channels as in `fxexpr` / `fxglide`: the `bend` mode
+    on the fixed-point bank.  Each new call beside its INC_SCALE counterpart in the same run: (a) skred_fxbank_bend_match of one
+    channel over the whole bank against skred_fxbank_ctl_match(SKRED_CTL_INC_SCALE) of the same channel; (b)
+    skred_fxbank_bend_tags_each of 256 notes against skred_fxbank_ctl_tags_each(SKRED_EACH_INC_SCALE) of the same tags; (c)
+    skred_fxbank_glide_advance by 64 frames over the whole bank, 256 voices gliding, on a bank with a bend array (the BEND
+    instantiation) and on one without; (d) skred_fxbank_tag_list of 256 voices with the glide clear behind it, and with the bend clear
+    as the third launch; (e) the 64-frame block after a bend_match beside a steady block before and after it.  Medians of 12 with
+    minimum and maximum; host time held, and stream time between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES = 1 << 20, 64, 16, 256
+    bank, pool, c0 = X.bank_fx(n)
+    db, plain = X.DeviceFxBank(n), X.DeviceFxBank(n)                              # plain: glides, never a bend
+    for d in (db, plain):
+        d.set_tables(pool); d.upload(bank); d.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    everyone = torch.arange(n, dtype=torch.int32, device="cuda")
+    for d in (db, plain):
+        d.tag_list(everyone.data_ptr(), tags)
+    at = np.flatnonzero(v % CHANNELS == 2)[::7][:NOTES]                          # 256 notes of channel 3
+    note_tags, note_voices = tags[at].copy(), at.astype(np.int32)
+    dl_notes = torch.from_numpy(note_voices).cuda()
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    value, mask = 3 << 24, 0xFF000000
+    r = 2.0 ** (0.33 / 12.0 * 64.0 / 48000.0)
+    up, down = max(1, int((r - 1.0) * 2.0 ** 32)), max(1, int((1.0 - 1.0 / r) * 2.0 ** 32))
+    glides = X.glide_array([X.glide(X.FX_GLIDE_FROM_SCALE, up, down, int(2.0 ** (-7.0 / 12.0) * 65536.0)) for _ in range(NOTES)])
+    each = X.fx_each_array([X.fx_each(X.EACH_INC_SCALE, inc_scale_q16=65542) for _ in range(NOTES)])
+    ratios = np.full(NOTES, X.bend_ratio_q24(0.5), np.uint32)
+    scale = X.fx_ctl(X.CTL_INC_SCALE, inc_scale_q16=65542)
+    torch.cuda.synchronize()
+
+    def line(label, call, words, before=None):
+        ms, held = _fx_timed(call, before)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {res.cpu().numpy().tolist()[:words]}")
+
+    print(f"fx {n} voices all sounding, tagged over {CHANNELS} channels ({n // CHANNELS} notes each)")
+    for d in (db, plain):
+        d.glide_tags(glides, 0, n, note_tags, res.data_ptr())                      # both banks hold a glide array, 256 voices gliding
+    line(f"(d) tag_list of {NOTES} voices, the glide clear behind it", lambda: plain.tag_list(dl_notes.data_ptr(), note_tags), 0)
+    line("(a) ctl_match(INC_SCALE) of one channel over the whole bank", lambda: db.ctl_match(scale, 0, n, value, mask, res.data_ptr()), 3,
+         lambda: db.upload(bank))
+    db.upload(bank)
+    line("(a) bend_match of one channel over the whole bank", lambda: db.bend_match(0, n, value, mask, X.bend_ratio_q24(1.0), res.data_ptr()), 3)
+    db.bend_match(0, n, value, mask, X.FX_BEND_ONE)
+    line(f"(b) ctl_tags_each(INC_SCALE) of {NOTES} tags", lambda: db.ctl_tags_each(None, each, 0, n, note_tags, res.data_ptr()), 3,
+         lambda: db.upload(bank))
+    db.upload(bank)
+    line(f"(b) bend_tags_each of {NOTES} tags", lambda: db.bend_tags_each(ratios, 0, n, note_tags, res.data_ptr()), 3)
+    line(f"(d) tag_list of {NOTES} voices, the glide and the bend clear behind it", lambda: db.tag_list(dl_notes.data_ptr(), note_tags), 0)
+    for d in (db, plain):
+        d.upload(bank)
+        d.glide_tags(glides, 0, n, note_tags, res.data_ptr())
+    db.bend_tags_each(ratios, 0, n, note_tags, res.data_ptr())                     # the gliding voices are bent: the re-derived store runs
+    line(f"(c) glide_advance by 64 frames over the whole bank, {NOTES} voices gliding, no bend array",
+         lambda: plain.glide_advance(0, n, F, res.data_ptr()), 2)
+    line(f"(c) glide_advance by 64 frames over the whole bank, {NOTES} voices gliding under a bend",
+         lambda: db.glide_advance(0, n, F, res.data_ptr()), 2)
+
+    db.glide_stop(0, n, True); db.bend_clear(0, n, True)
+    db.upload(bank); db.set_sample_count(c0)
+    _fx_block_after(db, out, F, None, 8)
+    before = _fx_block_after(db, out, F)
+    pos = [0]
+
+    def wheel():
+        pos[0] += 1
+        db.bend_match(0, n, value, mask, X.bend_ratio_q24(0.01 * (pos[0] % 100) + 0.01), res.data_ptr())
+
+    after = _fx_block_after(db, out, F, wheel)
+    later = _fx_block_after(db, out, F)
+    print(f"  (e) the {F}-frame block after a bend_match ({n // CHANNELS} increments moved): {_fx_stats(after)}; a steady block before it: "
+          f"{_fx_stats(before)}; after it: {_fx_stats(later)}")
+    db.close(); plain.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "fxbend": fxbend}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
