@@ -1005,7 +1005,8 @@ int  skred_bank_ctl_tags_each(skred_bank_t *bank, const skred_ctl_t *ctl, const 
  * voice_mask).  FILTER is not a listing word: a call whose records and entries name none leaves the planner's reports alone, and
  * the block behind it is the steady block.  One set per entry: voices of one slot that need different coefficients take a record
  * of `ctl` each (SKRED_CTL_FILTER) on the lanes outside filter_mask.
- * Out of scope: the drop-in mode, deferred items and pattern steps, coefficients computed on the device.  On a shard: through
+ * Out of scope: the drop-in mode, deferred items and pattern steps.  Coefficients computed on the device: the section "filter cutoff
+ * on the device" below.  On a shard: through
  * skred_shard_bank(), with that rank's local indices.  The fixed-point bank has the twin (include/skred_amd_fxpt.h:
  * skred_fxbank_ctl_owned_each_filter / _ctl_tags_each_filter). */
 typedef struct skred_filter_each { float b0, b1, b2, a1, a2; uint32_t reserved[3]; } skred_filter_each_t;   /* 32 bytes, reserved 0 */
@@ -1367,6 +1368,162 @@ int  skred_bank_bend_clear(skred_bank_t *bank, int first, int count, int snap, v
 /* The bend words of [first, first + count) into host_u32x2 (2 * count words: key, ratio per voice); waits for the device, like
  * skred_bank_download_owners; zeros on a bank that never bent. */
 int  skred_bank_download_bend(skred_bank_t *bank, uint32_t *host_u32x2, int first, int count);
+
+/* ---- filter cutoff on the device: key-tracked cutoffs that glide and land ------------------------------------------------------
+ *
+ * SKRED_CTL_FILTER and skred_filter_each_t bring five finished coefficients, which the host computes with skred_filter_coeffs (libm's
+ * sinf / cosf).  A cutoff that follows each note's own pitch therefore needs the increment the device holds (a download after a
+ * glide or a bend), a cutoff that moves needs one per-note upload per block, and a host-driven ramp of libm results lands on no
+ * particular bits.  The calls of this section keep the CUTOFF beside the voice -- the normalised angular cutoff w = 2 pi f / rate in
+ * radians per frame, the resonance q and the mode -- and compute the coefficients on the device with arithmetic that is defined here
+ * operation by operation, so that the device, skred_filter_coeffs_w and tests/cutoff_model.py give the same bits.
+ *
+ * THE ARITHMETIC (skred_filter_coeffs_w(mode, w, q)).  Every multiply, add, subtract and divide is ONE correctly rounded fp32
+ * operation (round to nearest even, never fused); a negation flips the sign bit.
+ *   1. range reduction to [0, pi / 2]:  if w > SKRED_CUTOFF_HALF_PI: r = (SKRED_CUTOFF_PI_HI - w) + SKRED_CUTOFF_PI_LO (the difference
+ *      first: it is exact for w in [pi / 2, 3]) and the cosine below changes its sign; else r = w.
+ *   2. z = r * r.
+ *   3. sine, Horner in z:  p = S4;  p = p * z + S3;  p = p * z + S2;  p = p * z + S1;  sn = r + (r * z) * p.
+ *   4. cosine, Horner in z:  c = C5;  c = c * z + C4;  c = c * z + C3;  c = c * z + C2;  c = c * z + C1;  c = 1 + z * c;
+ *      cs = c, or -c behind the reduction of step 1.
+ *   5. skred_filter_coeffs' sequence, unchanged:  alpha = sn / (2 * q);  a0 = 1 + alpha;
+ *        mode 1 (low-pass):  d = 1 - cs;  b0 = d / 2;  b1 = d;  b2 = b0        mode 2 (high-pass):  s = 1 + cs;  b0 = s / 2;  b1 = -s;  b2 = b0
+ *        mode 3 (band-pass): b0 = alpha;  b1 = 0;  b2 = -alpha                  mode 4 (notch):      b0 = 1;  b1 = -2 * cs;  b2 = 1
+ *        mode 5 (all-pass):  b0 = 1 - alpha;  b1 = -2 * cs;  b2 = 1 + alpha
+ *      out5 = b0 / a0,  b1 / a0,  b2 / a0,  (-2 * cs) / a0,  (1 - alpha) / a0.
+ * The constants are the literals below.  THE BOX: w in [SKRED_CUTOFF_W_MIN, SKRED_CUTOFF_W_MAX], q in [SKRED_CUTOFF_Q_MIN,
+ * SKRED_CUTOFF_Q_MAX].  Inside it no intermediate is denormal, no divisor is zero (alpha lies in about [4.8e-7, 32]) and every
+ * coefficient is finite, which is all the planner asks of the words.
+ *
+ * ACCURACY, measured by tests/test_cutoff_cpu.py on a grid of 201 values of w (both ends, 72 values spread geometrically over the box,
+ * SKRED_CUTOFF_HALF_PI and the 64 fp32 values on either side of that seam) x 17 values of q (both ends, geometric) x 5 modes, against
+ * an fp64 evaluation of the same formulas on the same fp32 (w, q): the largest absolute error of each coefficient, of this function
+ * and of skred_filter_coeffs(mode, w, q, 2 pi) (libm).  The test holds every entry of the first table to at most 4 x the second's.
+ *                     skred_filter_coeffs_w                              skred_filter_coeffs (the yardstick)
+ *   mode    b0       b1       b2       a1       a2           b0       b1       b2       a1       a2
+ *   1    8.2e-08  1.6e-07  8.2e-08  2.7e-07  8.7e-08      9.3e-08  1.9e-07  9.3e-08  2.4e-07  9.0e-08
+ *   2    1.2e-07  2.4e-07  1.2e-07  2.7e-07  8.7e-08      1.2e-07  2.4e-07  1.2e-07  2.4e-07  9.0e-08
+ *   3    7.7e-08  0        7.7e-08  2.7e-07  8.7e-08      7.7e-08  0        7.7e-08  2.4e-07  9.0e-08
+ *   4    8.3e-08  2.7e-07  8.3e-08  2.7e-07  8.7e-08      8.3e-08  2.4e-07  8.3e-08  2.4e-07  9.0e-08
+ *   5    8.7e-08  2.7e-07  0        2.7e-07  8.7e-08      9.0e-08  2.4e-07  0        2.4e-07  9.0e-08
+ * The largest ratio is 1.12 (a1, and b1 where it is -2 cs / a0): the factor of 4 is met with a degree-9 sine and a degree-10 cosine.
+ * Stability (|a2| < 1 and |a1| < 1 + a2) holds on the whole grid for modes 1 .. 5.
+ *
+ * cut[n_voices] is an array of eight words PER VOICE (two uint4: w, target, rate_up, rate_down as fp32 bit patterns; carry 0 .. 63, q,
+ * mode, a reserved 0) in device memory that only the calls of this section read or write.  w == 0 (all bits) means "no device cutoff",
+ * target == 0 "not moving".  The bank allocates the array (32 bytes per voice; the owner array first, when no owner call came before)
+ * on the first skred_bank_cutoff_match / _cutoff_owned_each / _cutoff_tags_each call and zero-fills it; that call waits for the device
+ * once.  No render kernel, report, probe, tap or planner rule reads the array, the calls store nothing but finite coefficient words,
+ * and FILTER is not a listing word: a cutoff call leaves the planner's reports alone, and the block behind it is the steady block.
+ * The filter memory (x1 x2 y1 y2) is untouched; velocity, smoothing and cz_distortion, the neighbours of the five words, keep their
+ * bits; a voice whose filter is bypassed keeps the words without reading them.  A bank that never calls these allocates and launches
+ * nothing more.
+ *
+ * A RECORD ON VOICE v (skred_cutoff_t; the voices are those of filter_mask in a slot the guard lets through):
+ *   1. v has no cutoff word (w == 0) and the record does not name BOTH SKRED_CUTOFF_Q and SKRED_CUTOFF_MODE: WITHHELD and counted.
+ *   2. q = the record's with SKRED_CUTOFF_Q, else the voice's; mode likewise with SKRED_CUTOFF_MODE.
+ *   3. SKRED_CUTOFF_ABS: wn = value.  SKRED_CUTOFF_TRACK: k = the key word of a bent voice (the pitch-wheel section), else
+ *      voice_phase_inc -- the word a glide runs on.  k zero or not finite: WITHHELD and counted.  wn = |k| * value, ONE multiply; a
+ *      product outside the box (an infinite one too) is CLAMPED to the nearer end and counted.  The host supplies value = harmonic *
+ *      2 pi / table_size of the patch voice -- a ratio, never an increment -- and full keyboard tracking survives glides and stealing
+ *      without a read-back.
+ *   4. SKRED_CUTOFF_GLIDE on a voice that has a cutoff word: target = wn, rate_up, rate_down = the record's, carry = 0; w and the
+ *      coefficients stand until the next advance.  Otherwise (no GLIDE, or the voice's first cutoff): w = wn, target = rate_up =
+ *      rate_down = carry = 0 -- any movement stops -- and the five coefficient words = THE ARITHMETIC(mode, wn, q).
+ * A withheld record leaves the voice and its eight words exactly as they were.
+ *
+ * ADVANCE BY F FRAMES (skred_bank_cutoff_advance), for every moving voice of a range: c = carry + F, m = c >> 6.  m times, stopping at
+ * arrival: w < target: w = w * rate_up, arrived if w >= target; w > target: w = w * rate_down, arrived if w <= target; w == target:
+ * arrived.  On arrival w = THE TARGET'S BITS and target, rates and carry are cleared; else carry = c & 63.  Then the coefficients are
+ * computed ONCE from that final w (also when m == 0).  The rates are per 64 frames, and w at every multiple of 64 frames does not
+ * depend on how the host cuts its blocks; a voice that has landed holds the bits of a voice set with SKRED_CUTOFF_ABS at the target.
+ * A voice that does not move costs one 16-byte load.  The cutoff moves once per block, as every control here does.
+ *
+ * A NEW NOTE CLEARS THE WORDS.  Once the array exists, every tag launch of the bank is followed on its stream by a launch that zeroes
+ * all eight words of all K voices of every slot it tagged (the pedal, glide and bend rule, beside their clears): a thief or a key
+ * struck again does not inherit a moving cutoff.  The coefficients stay what they were, as today.  The order for a tracked note is
+ * skred_bank_note_on_channel, then skred_bank_bend_tags_each / skred_bank_glide_tags, then skred_bank_cutoff_tags_each.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring; nothing
+ * waits for the device but the download and the first allocation; one stream at a time per bank; the same state gives the same bytes.
+ * d_result of the three record calls (device, uint32[4], may be NULL; cleared on the stream ahead of the kernel): [0] voices set or
+ * started, [1] records withheld, [2] slots not owned (the _each calls) or slots of the range that did not match, [3] cutoffs clamped.
+ *
+ * Limits: a tracked cutoff is computed when the call runs and does not follow later bends or glides: send it again.  A
+ * SKRED_CTL_FILTER store (or per-entry coefficients) on a voice with a cutoff word is overwritten by that voice's next moving
+ * advance, and otherwise leaves w stale.  A release leaves the words alone.  Not built: the fixed-point bank, the drop-in mode,
+ * deferred items and pattern steps.  On a shard: through skred_shard_bank(), with that rank's local indices. */
+#define SKRED_CUTOFF_W_MIN 0x1p-10f
+#define SKRED_CUTOFF_W_MAX 3.0f
+#define SKRED_CUTOFF_Q_MIN 0x1p-6f
+#define SKRED_CUTOFF_Q_MAX 0x1p10f
+#define SKRED_CUTOFF_RATE_MIN 0x1p-4f      /* the box of rate_down and rate_up: a factor of 16 per 64 frames either way */
+#define SKRED_CUTOFF_RATE_MAX 0x1p4f
+#define SKRED_CUTOFF_HALF_PI 0x1.921fb6p+0f
+#define SKRED_CUTOFF_PI_HI 0x1.921fb6p+1f
+#define SKRED_CUTOFF_PI_LO -0x1.777a5cp-24f
+#define SKRED_CUTOFF_S1 -0x1.555548p-3f
+#define SKRED_CUTOFF_S2 0x1.110e6ap-7f
+#define SKRED_CUTOFF_S3 -0x1.9f5ff4p-13f
+#define SKRED_CUTOFF_S4 0x1.5cf92cp-19f
+#define SKRED_CUTOFF_C1 -0x1p-1f
+#define SKRED_CUTOFF_C2 0x1.555548p-5f
+#define SKRED_CUTOFF_C3 -0x1.6c138p-10f
+#define SKRED_CUTOFF_C4 0x1.9f6f7ep-16f
+#define SKRED_CUTOFF_C5 -0x1.18003p-22f
+/* Pure host, THE ARITHMETIC above.  out5 = b0 b1 b2 a1 a2.  Returns SKRED_OK; 1 for mode 0 (bypass: out5 is left as it is, as
+ * skred_filter_coeffs leaves it); SKRED_E_BAD_ARG for a NULL out5 or a mode outside 0 .. 5; SKRED_E_RANGE for a w or q that is not
+ * finite or lies outside the box.  skred_filter_coeffs and the drop-in mode stay as they are. */
+int  skred_filter_coeffs_w(int mode, float w, float q, float out5[5]);
+enum { SKRED_CUTOFF_ABS = 1u << 0,     /* w = value */
+       SKRED_CUTOFF_TRACK = 1u << 1,   /* w = |k| * value, k the voice's key increment: exactly one of ABS and TRACK */
+       SKRED_CUTOFF_GLIDE = 1u << 2,   /* the computed w is the TARGET, reached at rate_up / rate_down per 64 frames */
+       SKRED_CUTOFF_Q = 1u << 3,       /* the record names q */
+       SKRED_CUTOFF_MODE = 1u << 4 };  /* the record names mode (1 .. 5) */
+typedef struct skred_cutoff { uint32_t set; float value, q; uint32_t mode; float rate_up, rate_down; uint32_t reserved[2]; } skred_cutoff_t;   /* 32 bytes */
+/* Pure host: SKRED_OK, or what the record calls refuse about K, the masks and the n records, in this order.  SKRED_E_BAD_ARG: a NULL
+ * array, n < 0; SKRED_E_RANGE: a bad K (not a power of two in 1 .. 64); SKRED_E_BAD_ARG: a voice_mask or a filter_mask that is 0 or
+ * has bits at or above K; in a record: unknown bits in set, SKRED_CUTOFF_ABS with SKRED_CUTOFF_TRACK or neither, first_time != 0 and
+ * not both SKRED_CUTOFF_Q and SKRED_CUTOFF_MODE; a reserved word that is not 0; a named value that is not finite (value always; q
+ * with Q; the rates with GLIDE); SKRED_E_RANGE: a named q outside the box, an ABS value outside the box, a TRACK value <= 0, a mode
+ * outside 1 .. 5, a rate under GLIDE outside [SKRED_CUTOFF_RATE_MIN, SKRED_CUTOFF_RATE_MAX]; SKRED_E_BAD_ARG: rate_up <= 1 or
+ * rate_down >= 1 under GLIDE; last, a filter_mask with a bit outside voice_mask.  voice_mask: the voices of a slot the patch plays
+ * (the note-on's mask); the entry points themselves take filter_mask alone and check it against all K lanes.  first_time: the
+ * caller states that the voices have no cutoff word yet -- the entry points cannot know (they pass 0), and there the kernel
+ * withholds and counts instead. */
+int  skred_cutoff_check(const skred_cutoff_t *rec, int n, int slot_voices, uint64_t voice_mask, uint64_t filter_mask, int first_time);
+/* The channel sweep: the record on every filter_mask voice of every slot of [first, first + count) whose owner matches m.  Geometry,
+ * guard and counting are skred_bank_ctl_match's; the record is a kernel argument.  The planner is told nothing.
+ * Refused, in this order: SKRED_E_BAD_ARG: NULL bank, match or record; SKRED_E_RANGE: a bad K; SKRED_E_BAD_ARG: a bad filter_mask;
+ * SKRED_E_RANGE: first or count not a multiple of K, count <= 0, a range outside the bank; then what skred_cutoff_check refuses about
+ * the record; then what skred_owner_match_check refuses. */
+int  skred_bank_cutoff_match(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t filter_mask, const skred_owner_match_t *m,
+                             const skred_cutoff_t *rec, uint32_t *d_result, void *stream);
+/* One record per entry: entry k (of the first min(n, *d_count_or_null)) acts on d_slots[k] only if that is a slot of the bank AND
+ * owner[slot] == tags[k] (non-zero).  A slot named twice: UNSPECIFIED.
+ * Refused, in this order: SKRED_E_BAD_ARG: NULL bank, records, list or tags, n < 0; SKRED_E_RANGE: a bad K; SKRED_E_BAD_ARG: a bad
+ * filter_mask; what skred_cutoff_check refuses about the records; a zero tag, n > INT32_MAX / 64.  n == 0: SKRED_OK. */
+int  skred_bank_cutoff_owned_each(skred_bank_t *bank, const skred_cutoff_t *recs, int slot_voices, uint64_t filter_mask,
+                                  const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result,
+                                  void *stream);
+/* By note id: skred_bank_find_owned of the tags over [first, first + count) into scratch the bank owns, then the call above on that
+ * list.  recs[k] goes with tags[k]: the tags travel sorted, the records are permuted with them on the host.  1 ..
+ * SKRED_OWNER_MAX_TAGS tags, unique, none zero; d_result[2] is 0.  Refused: as above with the range behind the masks, then a repeated
+ * tag or n > SKRED_OWNER_MAX_TAGS. */
+int  skred_bank_cutoff_tags_each(skred_bank_t *bank, const skred_cutoff_t *recs, int first, int count, int slot_voices, uint64_t filter_mask,
+                                 const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+/* The advance pass above over the voices [first, first + count): purely per voice, no K.  d_result (device, uint32[2], may be NULL;
+ * cleared on the stream ahead of the kernel): [0] voices still moving after the pass, [1] voices that arrived in it.  The host calls
+ * it once per block.  On a bank without a cutoff array: SKRED_OK, d_result (if given) is cleared on the stream, nothing is launched.
+ * SKRED_E_BAD_ARG: NULL bank, num_frames outside 1 .. 65536; SKRED_E_RANGE: count <= 0 or a range outside the bank. */
+int  skred_bank_cutoff_advance(skred_bank_t *bank, int first, int count, int num_frames, uint32_t *d_result, void *stream);
+/* Every movement of [first, first + count) ends on `stream`: target, rates and carry are cleared, w, q and mode stay; with snap != 0 a
+ * moving voice's w is set to its target and its coefficients computed first.  Nothing to do on a bank without a cutoff array.
+ * SKRED_E_BAD_ARG: NULL bank; SKRED_E_RANGE: count < 0 or a range outside the bank. */
+int  skred_bank_cutoff_stop(skred_bank_t *bank, int first, int count, int snap, void *stream);
+/* The cutoff words of [first, first + count) into host_u32x8 (8 * count words); waits for the device, like
+ * skred_bank_download_owners; zeros on a bank that never set a cutoff. */
+int  skred_bank_download_cutoff(skred_bank_t *bank, uint32_t *host_u32x8, int first, int count);
 
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *

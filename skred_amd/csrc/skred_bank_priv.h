@@ -14,6 +14,7 @@
  *   skred_bank_pedal.c   pedals: note-offs held back per slot, sostenuto's latch, the pedal-up
  *   skred_bank_glide.c   portamento: per-voice glides, started under the owner guard, advanced and landed on the device
  *   skred_bank_bend.c    the pitch wheel: absolute bends that keep the key's bits beside the sounding increment
+ *   skred_bank_cutoff.c  filter cutoff on the device: key-tracked cutoffs that glide and land, coefficients computed where the voice lives
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -211,6 +212,9 @@ struct skred_bank {
   /* the pitch wheel (skred_bank_bend.c), allocated and zeroed by the first call that bends */
   sk_bend_t *d_bend;                /* [n_voices] key, ratio per voice; key 0: not bent; NULL: no voice was ever bent, the tag launches
                                        clear nothing and the glide launches run as they always ran; no render kernel reads it */
+  /* filter cutoff (skred_bank_cutoff.c), allocated and zeroed by the first call that sets a cutoff */
+  sk_cut_t *d_cut;                  /* [n_voices] w, target, rate_up, rate_down, carry, q, mode, 0 per voice; w 0: no device cutoff; NULL:
+                                       no cutoff was ever set, and the tag launches clear nothing; no render kernel reads it */
 };
 
 /* per-voice classification (host shadow) */
@@ -314,6 +318,10 @@ void sk_glide_pack(const skred_glide_t *glide, int n, const uint32_t *perm, sk_g
  * (perm NULL: ratios[j]).  Pure host */
 void sk_bend_free(skred_bank_t *b);
 void sk_bend_pack(const float *ratios, int n, const uint32_t *perm, uint32_t *out);
+/* skred_bank_cutoff.c: the cutoff array (skred_bank_destroy); n checked records as they travel -- out[j] = rec[perm[j]] (perm NULL:
+ * rec[j]), the named words as they stand, the others zero.  Pure host */
+void sk_cutoff_free(skred_bank_t *b);
+void sk_cutoff_pack(const skred_cutoff_t *rec, int n, const uint32_t *perm, sk_cut_each_t *out);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);

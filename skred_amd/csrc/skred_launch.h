@@ -22,6 +22,8 @@
  *   skred_pedal_kernels.hip   sk_launch_pedal_clear, sk_launch_pedal_stamps, sk_launch_pedal_latch, sk_launch_pedal_up
  *   skred_glide_kernels.hip   sk_launch_glide_clear, sk_launch_glide_start, sk_launch_glide_advance, sk_launch_glide_stop
  *   skred_bend_kernels.hip    sk_launch_bend_clear, sk_launch_bend_match, sk_launch_bend_each, sk_launch_bend_range_clear
+ *   skred_cutoff_kernels.hip  sk_launch_cutoff_clear, sk_launch_cutoff_match, sk_launch_cutoff_each, sk_launch_cutoff_advance,
+ *                             sk_launch_cutoff_stop
  *   skred_fx_pedal_kernels.hip  skx_launch_pedal_stamps, skx_launch_pedal_latch, skx_launch_pedal_up (sk_launch_pedal_clear by
  *                             skred_fx_owner.c too)
  *   skred_fx_glide_kernels.hip  skx_launch_glide_start, skx_launch_glide_advance, skx_launch_glide_stop (prototypes in
@@ -462,6 +464,68 @@ int sk_launch_bend_each(sk_bend_t *bend, const uint32_t *d_ratios, int slot_voic
                         uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
 /* bend[first .. first + count) = 0; snap != 0: a bent voice's increment = its key first */
 int sk_launch_bend_range_clear(sk_bend_t *bend, sk_plane_t *osc, int first, int count, int snap, hipStream_t stream);
+
+/* ---- filter cutoff on the device (skred_bank_cutoff.c -> skred_cutoff_kernels.hip; include/skred_amd.h: skred_bank_cutoff_match /
+ * _cutoff_owned_each / _cutoff_tags_each / _cutoff_advance / _cutoff_stop) ----
+ * cut[n_voices]: eight words per voice (two 16-byte loads) beside the bend array.  Only these launches read or write it; the words
+ * they store into the planes are the five biquad coefficients (SKP_GAIN words 2, 3; SKP_FILT words 0 .. 2), finite by construction.
+ * The constants equal SKRED_CUTOFF_* (checked at compile time in skred_bank_cutoff.c); skred_cutoff_common.hpp has the arithmetic. */
+enum { SK_CUT_W = 0, SK_CUT_TARGET, SK_CUT_RATE_UP, SK_CUT_RATE_DOWN, SK_CUT_CARRY, SK_CUT_Q, SK_CUT_MODE, SK_CUT_RESERVED, SK_CUT_WORDS = 8 };
+typedef struct {
+  uint32_t w[SK_CUT_WORDS];
+} sk_cut_t;
+/* A record is skred_cutoff_t word for word: 32 bytes, set value q mode one aligned 16-byte load, the two rates the next 8 bytes */
+#define SK_CUTOFF_ABS   (1u << 0)
+#define SK_CUTOFF_TRACK (1u << 1)
+#define SK_CUTOFF_GLIDE (1u << 2)
+#define SK_CUTOFF_Q     (1u << 3)
+#define SK_CUTOFF_MODE  (1u << 4)
+#define SK_CUTOFF_ALL   ((1u << 5) - 1u)
+enum { SK_CUT_E_SET = 0, SK_CUT_E_VALUE, SK_CUT_E_Q, SK_CUT_E_MODE, SK_CUT_E_RATE_UP, SK_CUT_E_RATE_DOWN, SK_CUT_E_WORDS = 8 };
+typedef struct {
+  uint32_t w[SK_CUT_E_WORDS];
+} sk_cut_each_t;
+#define SK_CUTOFF_W_MIN 0x1p-10f
+#define SK_CUTOFF_W_MAX 3.0f
+#define SK_CUTOFF_HALF_PI 0x1.921fb6p+0f
+#define SK_CUTOFF_PI_HI 0x1.921fb6p+1f
+#define SK_CUTOFF_PI_LO -0x1.777a5cp-24f
+#define SK_CUTOFF_S1 -0x1.555548p-3f
+#define SK_CUTOFF_S2 0x1.110e6ap-7f
+#define SK_CUTOFF_S3 -0x1.9f5ff4p-13f
+#define SK_CUTOFF_S4 0x1.5cf92cp-19f
+#define SK_CUTOFF_C1 -0x1p-1f
+#define SK_CUTOFF_C2 0x1.555548p-5f
+#define SK_CUTOFF_C3 -0x1.6c138p-10f
+#define SK_CUTOFF_C4 0x1.9f6f7ep-16f
+#define SK_CUTOFF_C5 -0x1.18003p-22f
+/* the planes the cutoff launches touch: SKP_OSC (read: voice_phase_inc), SKP_GAIN and SKP_FILT (the coefficient words) */
+typedef struct {
+  const sk_plane_t *osc;
+  sk_plane_t *gain, *filt;
+} sk_cut_planes_t;
+/* cut[d_slots[k] + l] = 0 (both halves), l < slot_voices, under sk_launch_owner_tag's list rule: launched behind it by a bank that has
+ * a cutoff array */
+int sk_launch_cutoff_clear(sk_cut_t *cut, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
+                           hipStream_t stream);
+/* the record on the filter_mask voices of the slots of [first, first + count) whose owner matches; bend: the pitch-wheel array or
+ * NULL (TRACK reads a bent voice's key).  d_result[4] (may be NULL; zeroed on `stream` ahead of the kernel) += voices set or started,
+ * records withheld, slots of the range that did not match, cutoffs clamped */
+int sk_launch_cutoff_match(sk_cut_t *cut, const sk_bend_t *bend, const sk_cut_each_t *rec, int slot_voices, uint64_t filter_mask, int first,
+                           int count, const uint32_t *owner, uint32_t value, uint32_t mask, const sk_cut_planes_t *planes,
+                           uint32_t *d_result, hipStream_t stream);
+/* entry k applies d_each[k] (16-byte aligned) on the filter_mask voices of d_slots[k] where that is a slot whose owner is d_tags[k];
+ * d_result[4] as above, [2]: slots whose owner differs */
+int sk_launch_cutoff_each(sk_cut_t *cut, const sk_bend_t *bend, const sk_cut_each_t *d_each, int slot_voices, uint64_t filter_mask,
+                          const int32_t *d_slots, const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count,
+                          int n_voices, const sk_cut_planes_t *planes, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq,
+                          hipStream_t stream);
+/* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] (may be NULL; zeroed on `stream` ahead of
+ * the kernel) += voices still moving, voices that arrived */
+int sk_launch_cutoff_advance(sk_cut_t *cut, const sk_cut_planes_t *planes, int first, int count, int num_frames, uint32_t *d_result,
+                             hipStream_t stream);
+/* target, rates and carry of [first, first + count) = 0; snap != 0: a moving voice's w = its target and its coefficients first */
+int sk_launch_cutoff_stop(sk_cut_t *cut, const sk_cut_planes_t *planes, int first, int count, int snap, hipStream_t stream);
 
 /* ---- pedals on the fixed-point bank (skred_fx_pedal.c -> skred_fx_pedal_kernels.hip; include/skred_amd_fxpt.h:
  * skred_fxbank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up) ----

@@ -52,12 +52,15 @@ ABI_SYMBOLS = [
     "skred_bank_pedal_clear", "skred_bank_download_pedals",
     "skred_bank_glide_owned", "skred_bank_glide_tags", "skred_bank_glide_advance", "skred_bank_glide_stop", "skred_bank_download_glide",
     "skred_bank_bend_match", "skred_bank_bend_owned_each", "skred_bank_bend_tags_each", "skred_bank_bend_clear", "skred_bank_download_bend",
+    "skred_bank_cutoff_match", "skred_bank_cutoff_owned_each", "skred_bank_cutoff_tags_each", "skred_bank_cutoff_advance",
+    "skred_bank_cutoff_stop", "skred_bank_download_cutoff",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
                     "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check",
                     "skred_filter_each_check", "skred_filter_coeffs",
-                    "skred_chan_check", "skred_pedal_check", "skred_glide_check", "skred_bend_check"]
+                    "skred_chan_check", "skred_pedal_check", "skred_glide_check", "skred_bend_check",
+                    "skred_cutoff_check", "skred_filter_coeffs_w"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -232,6 +235,32 @@ def glide_array(glides):
     return (GlideC * len(glides))(*glides)
 
 
+# SKRED_CUTOFF_* (skred_bank_cutoff_match / _cutoff_owned_each / _cutoff_tags_each)
+CUTOFF_ABS, CUTOFF_TRACK, CUTOFF_GLIDE, CUTOFF_Q, CUTOFF_MODE = 1, 2, 4, 8, 16
+CUTOFF_W_MIN, CUTOFF_W_MAX, CUTOFF_Q_MIN, CUTOFF_Q_MAX = 2.0 ** -10, 3.0, 2.0 ** -6, 2.0 ** 10
+CUTOFF_RATE_MIN, CUTOFF_RATE_MAX = 2.0 ** -4, 2.0 ** 4
+
+
+class CutoffC(C.Structure):
+    """ctypes image of ``skred_cutoff_t`` (32 bytes): `set` names ABS or TRACK, and GLIDE, Q, MODE as the record brings them."""
+    _fields_ = [("set", C.c_uint32), ("value", C.c_float), ("q", C.c_float), ("mode", C.c_uint32), ("rate_up", C.c_float),
+                ("rate_down", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
+def cutoff(set: int, value: float, q: float = 0.0, mode: int = 0, rate_up: float = 0.0, rate_down: float = 0.0) -> CutoffC:
+    """One cutoff record: ``cutoff(CUTOFF_TRACK | CUTOFF_Q | CUTOFF_MODE, 4 * 2 * pi / table_size, 0.9, 1)`` is a low-pass at four
+    times each note's own frequency."""
+    return CutoffC(int(set), value, q, int(mode), rate_up, rate_down)
+
+
+def cutoff_array(recs):
+    """A contiguous ``CutoffC`` array from a sequence of CutoffC (a ctypes array of CutoffC passes through)."""
+    if isinstance(recs, C.Array) and recs._type_ is CutoffC:
+        return recs
+    recs = list(recs)
+    return (CutoffC * len(recs))(*recs)
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -384,6 +413,14 @@ def load() -> C.CDLL:
     L.skred_bank_bend_tags_each.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
     L.skred_bank_bend_clear.argtypes = [vp, i32, i32, i32, vp]
     L.skred_bank_download_bend.argtypes = [vp, vp, i32, i32]
+    L.skred_filter_coeffs_w.argtypes = [i32, C.c_float, C.c_float, C.POINTER(C.c_float)]
+    L.skred_cutoff_check.argtypes = [vp, i32, i32, C.c_uint64, C.c_uint64, i32]
+    L.skred_bank_cutoff_match.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, vp, vp, vp]
+    L.skred_bank_cutoff_owned_each.argtypes = [vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_cutoff_tags_each.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
+    L.skred_bank_cutoff_advance.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.skred_bank_cutoff_stop.argtypes = [vp, i32, i32, i32, vp]
+    L.skred_bank_download_cutoff.argtypes = [vp, vp, i32, i32]
     _lib = L
     return L
 
@@ -512,6 +549,24 @@ def filter_coeffs(mode: int, freq: float, resonance: float, sample_rate: float):
         return None
     _check(rc, "skred_filter_coeffs")
     return tuple(np.float32(x) for x in out)
+
+
+def filter_coeffs_w(mode: int, w: float, q: float):
+    """skred_filter_coeffs_w: (b0, b1, b2, a1, a2) as np.float32 from the normalised angular cutoff w = 2 pi f / rate, by the
+    arithmetic the device uses (include/skred_amd.h, "filter cutoff on the device").  None for mode 0.  Pure host."""
+    out = (C.c_float * 5)()
+    rc = int(load().skred_filter_coeffs_w(int(mode), float(w), float(q), out))
+    if rc == 1:
+        return None
+    _check(rc, "skred_filter_coeffs_w")
+    return tuple(np.float32(x) for x in out)
+
+
+def cutoff_check(recs, slot_voices: int, voice_mask: int, filter_mask: int, first_time: bool = False) -> int:
+    """skred_cutoff_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for what the record calls would refuse.  Pure host."""
+    arr = cutoff_array(recs) if recs is not None else None
+    return int(load().skred_cutoff_check(C.cast(arr, C.c_void_p) if arr is not None else None, len(arr) if arr is not None else 0,
+                                         int(slot_voices), int(voice_mask), int(filter_mask), int(bool(first_time))))
 
 
 class DeviceBank:
@@ -1067,6 +1122,47 @@ class DeviceBank:
     def bend_clear(self, first: int = 0, count: Optional[int] = None, snap: bool = False, stream: int = 0):
         count = self.n - first if count is None else count
         _check(self.L.skred_bank_bend_clear(self.h, int(first), int(count), int(bool(snap)), stream or None), "skred_bank_bend_clear")
+
+    # ---- filter cutoff on the device (include/skred_amd.h: skred_bank_cutoff_match / _cutoff_owned_each / _cutoff_tags_each / ...) ----
+    def cutoff_match(self, first: int, count: int, slot_voices: int, filter_mask: int, m: OwnerMatchC, rec: CutoffC, d_result: int = 0,
+                     stream: int = 0):
+        """The channel sweep: `rec` on the filter_mask voices of every slot of the range whose owner matches.  d_result (uint32[4], may
+        be 0): voices set or started, records withheld, slots that did not match, cutoffs clamped."""
+        _check(self.L.skred_bank_cutoff_match(self.h, int(first), int(count), int(slot_voices), int(filter_mask), C.byref(m), C.byref(rec),
+                                              d_result or None, stream or None), "skred_bank_cutoff_match")
+
+    def cutoff_owned_each(self, recs, slot_voices: int, filter_mask: int, d_slots: int, tags, d_count: int = 0, d_result: int = 0,
+                          stream: int = 0):
+        """Entry k applies recs[k] on the masked voices of d_slots[k] where that slot's owner is tags[k]."""
+        arr, t = cutoff_array(recs), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_cutoff_owned_each(self.h, C.cast(arr, C.c_void_p), int(slot_voices), int(filter_mask), d_slots or None,
+                                                   t.ctypes.data, len(t), d_count or None, d_result or None, stream or None),
+               "skred_bank_cutoff_owned_each")
+
+    def cutoff_tags_each(self, recs, first: int, count: int, slot_voices: int, filter_mask: int, tags, d_result: int = 0, stream: int = 0):
+        """By note id: recs[k] reaches the lowest slot of the range that carries tags[k]."""
+        arr, t = cutoff_array(recs), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_cutoff_tags_each(self.h, C.cast(arr, C.c_void_p), int(first), int(count), int(slot_voices), int(filter_mask),
+                                                  t.ctypes.data, len(t), d_result or None, stream or None), "skred_bank_cutoff_tags_each")
+
+    def cutoff_advance(self, first: int, count: int, frames: int, d_result: int = 0, stream: int = 0):
+        """The advance pass by `frames` frames; d_result (uint32[2], may be 0): voices still moving, voices that arrived."""
+        _check(self.L.skred_bank_cutoff_advance(self.h, int(first), int(count), int(frames), d_result or None, stream or None),
+               "skred_bank_cutoff_advance")
+
+    def cutoff_stop(self, first: int = 0, count: Optional[int] = None, snap: bool = False, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_bank_cutoff_stop(self.h, int(first), int(count), int(bool(snap)), stream or None), "skred_bank_cutoff_stop")
+
+    def download_cutoff(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The cutoff words of [first, first + count) as a (count, 8) uint32 array: w, target, rate_up, rate_down, carry, q, mode, 0;
+        waits for the device.  Zeros on a bank that never set a cutoff."""
+        count = self.n - first if count is None else count
+        out = np.zeros((count, 8), np.uint32)
+        _check(self.L.skred_bank_download_cutoff(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_cutoff")
+        return out
 
     def download_bend(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """The bend words of [first, first + count) as a (count, 2) uint32 array: key, ratio; waits for the device.  Zeros on a bank

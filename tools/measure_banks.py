@@ -1993,6 +1993,140 @@ def bend():
     db.close()
 
 
+def cutoff():
+    """Filter cutoff on the device on bank_patch("3sk", 2**20) with the carriers filtered, every copy sounding and tagged over 16
+    channels: the `bend` mode's bank.  (a) skred_bank_cutoff_tags_each(TRACK) of 256 notes beside the parent's route for the same notes
+    (skred_filter_coeffs per note on the host, then skred_bank_ctl_tags_each_filter); (b) skred_bank_cutoff_match(TRACK) of one channel
+    beside the parent's only route (download_ctl behind a device wait, coefficients per note on the host, ctl_tags_each_filter in
+    batches of 1024 tags); (c) skred_bank_cutoff_advance by 64 frames over a sixteenth of the bank, over the whole bank with 1024 voices
+    moving and with nothing moving, beside skred_bank_glide_advance on the same ranges and one ctl_tags_each_filter per block; (d)
+    skred_bank_tag_slots of 256 slots without and with the cutoff clear behind it; (e) the 64-frame block after an advance beside
+    steady blocks.  Medians of 12 with minimum and maximum; host time held, and stream time between events."""
+    D = device
+    n, K, REPS, F, CHANNELS, NOTES, RATE = 1 << 20, 4, 12, 64, 16, 256, 44100.0
+    CARRIERS = 0x7
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = np.uint64(now - 40000)
+    bank["voice_filter_mode"][sel] = 1
+    for c, x in zip(("b0", "b1", "b2", "a1", "a2"), D.filter_coeffs(1, 2000.0, 0.707, RATE)):
+        bank["voice_filter"][c][sel] = x
+    size = int(bank["voice_table_size"][0])
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g); db.upload(bank)
+    slots = np.arange(0, n, K, dtype=np.int32)
+    idx = np.arange(len(slots), dtype=np.uint32)
+    tags = (((idx % CHANNELS) + 1) << 24 | (idx // CHANNELS + 1)).astype(np.uint32)
+    dl_all = torch.from_numpy(slots).cuda()
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    out = torch.zeros(F, 2, device="cuda")
+    on3 = np.flatnonzero(idx % CHANNELS == 2)
+    at = on3[::7][:NOTES]                                                       # 256 notes of channel 3
+    note_tags, note_slots = tags[at].copy(), slots[at].copy()
+    dl_notes = torch.from_numpy(note_slots).cuda()
+    chan = D.owner_match(3 << 24, 0xFF000000)
+    value = 4.0 * 2.0 * np.pi / size
+    QM = D.CUTOFF_Q | D.CUTOFF_MODE
+    track = D.cutoff(D.CUTOFF_TRACK | QM, value, 0.9, 1)
+    track_notes = D.cutoff_array([track] * NOTES)
+    sweep = D.cutoff(D.CUTOFF_ABS | D.CUTOFF_GLIDE, 2.5, rate_up=1.0005, rate_down=0.9995)
+    slide = D.glide_array([D.glide(D.GLIDE_TO_SCALE, 1.00001, 0.99999, 2.0)] * NOTES)
+    torch.cuda.synchronize()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def stats(x):
+        return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f})"
+
+    def series(call, before=None):
+        host, stream = [], []
+        for it in range(2 + REPS):
+            if before is not None:
+                before()
+            torch.cuda.synchronize()
+            h, s_ms = timed(call)
+            if it >= 2:
+                host.append(h); stream.append(s_ms)
+        return f"host time held {stats(host)}; stream time between events {stats(stream)}"
+
+    def host_coeffs(incs):
+        return D.filter_each_array([D.filter_each(*D.filter_coeffs(1, abs(float(i)) * 4.0 * RATE / size, 0.9, RATE)) for i in incs])
+
+    def parent_notes():                                          # the host knows these notes' increments: the note-on's
+        filt = host_coeffs(bank["voice_phase_inc"][note_slots])
+        db.ctl_tags_each_filter(None, None, filt, 0, n, CARRIERS, 0x1, note_tags, K, res.data_ptr())
+
+    def parent_channel():                                        # after glides and bends the increments are device state
+        got = bank.copy()
+        db.download_ctl(got)
+        filt = host_coeffs(got["voice_phase_inc"][slots[on3]])
+        for lo in range(0, len(on3), 1024):
+            db.ctl_tags_each_filter(None, None, filt[lo:lo + 1024], 0, n, CARRIERS, 0x1, tags[on3[lo:lo + 1024]], K)
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, carriers filtered, every copy sounding, tagged over {CHANNELS} channels "
+          f"({n // K // CHANNELS} notes each); medians of {REPS}")
+    print(f"  (d) tag_slots of {NOTES} slots, no cutoff array yet: {series(lambda: db.tag_slots(dl_notes.data_ptr(), note_tags, K))}")
+    db.tag_slots(dl_all.data_ptr(), tags, K)
+    print(f"  (a) the parent's route for {NOTES} notes (skred_filter_coeffs per note + ctl_tags_each_filter; one set per entry: the first carrier only): {series(parent_notes)}")
+    print(f"  (a) cutoff_tags_each(TRACK) of {NOTES} notes: "
+          f"{series(lambda: db.cutoff_tags_each(track_notes, 0, n, K, CARRIERS, note_tags, res.data_ptr()))}; d_result = {res.cpu().numpy().tolist()}")
+    print(f"  (b) the parent's route for one channel ({len(on3)} notes: download_ctl, coefficients on the host, {-(-len(on3) // 1024)} uploads): "
+          f"{series(parent_channel)}")
+    print(f"  (b) cutoff_match(TRACK) of one channel over the whole bank: "
+          f"{series(lambda: db.cutoff_match(0, n, K, CARRIERS, chan, track, res.data_ptr()))}; d_result = {res.cpu().numpy().tolist()}")
+    print(f"  (d) tag_slots of {NOTES} slots with the cutoff clear behind it: {series(lambda: db.tag_slots(dl_notes.data_ptr(), note_tags, K))}")
+    db.cutoff_tags_each(track_notes, 0, n, K, 0xF, note_tags)
+    print(f"  (c) cutoff_advance by {F} frames over the whole bank, nothing moving: "
+          f"{series(lambda: db.cutoff_advance(0, n, F, res.data_ptr()))}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    db.cutoff_tags_each(D.cutoff_array([sweep] * NOTES), 0, n, K, 0xF, note_tags, res.data_ptr())
+    started = res.cpu().numpy().tolist()
+    print(f"  (c) cutoff_advance by {F} frames over the whole bank, {started[0]} voices moving: "
+          f"{series(lambda: db.cutoff_advance(0, n, F, res.data_ptr()))}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    print(f"  (c) cutoff_advance by {F} frames over a sixteenth of the bank: "
+          f"{series(lambda: db.cutoff_advance(0, n // 16, F, res.data_ptr()))}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    db.glide_tags(slide, 0, n, K, 0xF, note_tags, res.data_ptr())
+    print(f"  (c) glide_advance by {F} frames over the whole bank, {NOTES * K} voices gliding: "
+          f"{series(lambda: db.glide_advance(0, n, F, res.data_ptr()))}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    print(f"  (c) glide_advance by {F} frames over a sixteenth of the bank: {series(lambda: db.glide_advance(0, n // 16, F, res.data_ptr()))}")
+    db.glide_stop(0, n, False)
+    print(f"  (c) glide_advance by {F} frames over the whole bank, nothing gliding: {series(lambda: db.glide_advance(0, n, F, res.data_ptr()))}")
+    host_filt = host_coeffs(bank["voice_phase_inc"][note_slots])
+    print(f"  (c) one ctl_tags_each_filter of {NOTES} notes per block (coefficients given, first carrier only): "
+          f"{series(lambda: db.ctl_tags_each_filter(None, None, host_filt, 0, n, CARRIERS, 0x1, note_tags, K, res.data_ptr()))}")
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+
+    for _ in range(8):
+        block()
+    steady = [block() for _ in range(REPS)]
+    after = []
+    for k in range(REPS):
+        block()
+        db.cutoff_advance(0, n, F, res.data_ptr())
+        after.append(block())
+    moved = res.cpu().numpy()[:2].tolist()
+    db.cutoff_stop(0, n, False)
+    steady2 = [block() for _ in range(REPS)]
+    print(f"  (e) the {F}-frame block after cutoff_advance (d_result = {moved}): {stats(after)}; a steady block before: {stats(steady)}; "
+          f"after the stop: {stats(steady2)}; kernel {db.last_kernel()}, list violations {db.list_violations()}")
+    db.close()
+
+
 def fxpedal():
     """Pedals on bank_fx(2**20), every voice sounding and tagged over 16 channels (tag = channel << 24 | voice // 16 + 1), 256
     note-offs of one channel held back, then the pedal goes up: the `pedal` mode on the fixed-point bank.  (a) each new call beside
@@ -2216,7 +2350,7 @@ def fxbend():
 
 
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "fxbend": fxbend}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "cutoff": cutoff, "fxbend": fxbend}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
