@@ -1451,8 +1451,9 @@ int  skred_bank_download_bend(skred_bank_t *bank, uint32_t *host_u32x2, int firs
  *
  * Limits: a tracked cutoff is computed when the call runs and does not follow later bends or glides: send it again.  A
  * SKRED_CTL_FILTER store (or per-entry coefficients) on a voice with a cutoff word is overwritten by that voice's next moving
- * advance, and otherwise leaves w stale.  A release leaves the words alone.  Not built: the fixed-point bank, the drop-in mode,
- * deferred items and pattern steps.  On a shard: through skred_shard_bank(), with that rank's local indices. */
+ * advance, and otherwise leaves w stale.  A release leaves the words alone.  The fixed-point bank has its own integer twin
+ * (include/skred_amd_fxpt.h, section "filter cutoff").  Not built: the drop-in mode, deferred items and pattern steps.  On a
+ * shard: through skred_shard_bank(), with that rank's local indices. */
 #define SKRED_CUTOFF_W_MIN 0x1p-10f
 #define SKRED_CUTOFF_W_MAX 3.0f
 #define SKRED_CUTOFF_Q_MIN 0x1p-6f

@@ -472,8 +472,9 @@ int  skred_fxbank_ctl_tags_each(skred_fxbank_t *fx, const skred_fx_ctl_t *ctl, c
  *                                     excepted) and what skred_fx_filter_each_check refuses.  n == 0: SKRED_OK.
  * skred_fxbank_ctl_tags_each_filter   skred_fxbank_ctl_tags_each with filt[k] beside tags[k]: the tags travel sorted, and filt is
  *                                     permuted on the host with each by the same permutation.  Refusals of both.
- * Out of scope: the deferred queue and pattern steps, the drop-in mode, coefficients computed on the device (skred_filter_coeffs of
- * include/skred_amd.h computes fp32 coefficients on the host; their conversion to Q2.30 is the host's, as for skred_fxbank_upload).
+ * Out of scope: the deferred queue and pattern steps, the drop-in mode.  Coefficients computed on the device, in integers, from a
+ * cutoff kept beside the voice: section "filter cutoff" below (these calls go on bringing finished words, which the host makes with
+ * skred_filter_coeffs of include/skred_amd.h in fp32 and converts to Q2.30 itself, as for skred_fxbank_upload).
  * LIMIT, as for the controllers: the host view goes stale; skred_fxbank_download_params reads the values back. */
 typedef struct skred_fx_filter_each {     /* 32 bytes */
   int32_t  b0_q30, b1_q30, b2_q30, a1_q30, a2_q30;
@@ -823,6 +824,181 @@ int  skred_fxbank_bend_tags_each(skred_fxbank_t *fx, const uint32_t *ratios_q24,
                                  uint32_t *d_result, void *stream);
 int  skred_fxbank_bend_clear(skred_fxbank_t *fx, int first, int count, int snap, void *stream);
 int  skred_fxbank_download_bend(skred_fxbank_t *fx, uint32_t *host_u32x2, int first, int count);
+
+/* ---- filter cutoff: key-tracked cutoffs that glide and land, coefficients computed on the device, in integers ----------------------
+ *
+ * The fixed-point twin of the float bank's section "filter cutoff on the device" (include/skred_amd.h: skred_filter_coeffs_w ..
+ * skred_bank_download_cutoff), per voice -- no slots, no masks.  THIS is the place of record for the integer definition.  The other
+ * filter route of this bank (SKRED_CTL_FILTER, skred_fx_filter_each_t) brings five finished Q2.30 words that the host made with libm in
+ * fp32: "cutoff = 4 x the note's own frequency" after a glide or a bend needs a download of phase_inc, a sweep is one upload per
+ * block, and the words depend on the host's libm.  The calls of this section keep the CUTOFF beside the voice and compute the five
+ * words on the device with the integer arithmetic below: the same bits on every machine.
+ *
+ * FORMATS.  w_q29: uint32, the angular cutoff 2 pi f / rate in radians per frame, Q29; THE BOX is [SKRED_FX_CUTOFF_W_MIN,
+ * SKRED_FX_CUTOFF_W_MAX] = [2^19, 3 * 2^29], the float box [2^-10, 3].  q_q16: uint32, box [2^10, 2^26] = [2^-6, 2^10].  mode 1 .. 5 as
+ * in the float section (low-pass, high-pass, band-pass, notch, all-pass).
+ *
+ * THE ARITHMETIC (skred_fx_filter_coeffs_w(mode, w_q29, q_q16)).  Integers only.  A SIGNED product x is rounded by (x + 2^(s-1)) >> s
+ * with an arithmetic shift (a floor): to nearest, ties towards plus infinity.  With each step, the bound of what it forms:
+ *   1. range reduction: w_q29 > SKRED_FX_CUTOFF_HALF_PI_Q29: r = SKRED_FX_CUTOFF_PI_Q29 - w_q29 (exact; the cosine below changes its
+ *      sign), else r = w_q29.  r <= 843314857 < 2^30.
+ *   2. z = (r * r + 2^27) >> 28: (r / 2)^2 in Q32 (r^2 in Q30).  r * r < 2^60; z <= 2.4675 * 2^30 < 2^32: a uint32.  The polynomials
+ *      run in (r / 2)^2 < 0.617, so that no power of z amplifies the rounding of a constant.
+ *   3. sine, Horner in z on Q31 words:  p = S5;  p = ((p * z + 2^31) >> 32) + S4;  .. + S3;  .. + S2;  .. + S1;
+ *      sinc = 2^31 + ((p * z + 2^31) >> 32) -- sin(r) / r in Q31, in [0.6366 * 2^31, 2^31).  |p| <= |S1| < 2^30.5 at every step, every
+ *      product |p * z| < 2^62.5: an int64.  rs = r * sinc: sin(w) in Q60, < 2^61.
+ *   4. cosine, Horner in z on Q31 words:  c = C6;  c = ((c * z + 2^31) >> 32) + C5;  .. + C4;  .. + C3;  .. + C2;
+ *      t = (c * z + 2^31) >> 32;  cos = 2^31 - z + ((t * z + 2^31) >> 32) -- cos(r) in Q31; the term -2 (r / 2)^2 is z itself in Q31 and
+ *      is taken exactly, outside the Horner chain (its coefficient 2 would not fit a Q31 word).  |c| <= C2 < 2^30.5, |c * z| < 2^62.5,
+ *      |t| < 2^30, |t * z| < 2^62; 0 < cos <= 2^31.  cs = -cos behind the reduction of step 1, else cos: cos(w) in Q31.
+ *   5. skred_filter_coeffs' sequence in integers.  alpha = (rs + (den >> 1)) / den with den = q_q16 << 15 (2 q in Q30; <= 2^41): sn /
+ *      (2 q) in Q30 to nearest, straight from the Q60 sine -- a sine rounded to Q30 first would have its half unit multiplied by up to
+ *      32.  rs + (den >> 1) < 2^62.  alpha lies in [2^9, 2^35 + 64) -- near pi / 2 the sine's polynomial overshoots 1 by up to 5e-10, which
+ *      1 / (2 q) = 32 turns into 17 units --: 36 bits.  a0 = 2^30 + alpha: in (2^30, 2^30 + 2^35 + 64), 36 bits.
+ *      The numerators, signed, |n| <= a0 or <= 2^32:
+ *        mode 1:  d = 2^31 - cs (Q31);  b0 = d / 2,  b1 = d,  b2 = b0            mode 2:  s = 2^31 + cs (Q31);  b0 = s / 2,  b1 = -s,  b2 = b0
+ *        mode 3:  b0 = alpha,  b1 = 0,  b2 = -alpha                              mode 4:  b0 = 2^30,  b1 = -cs (-2 cos w in Q30),  b2 = b0
+ *        mode 5:  b0 = 2^30 - alpha,  b1 = -cs,  b2 = a0 (36 bits)
+ *        a1 = -cs,  a2 = 2^30 - alpha  in every mode.
+ *   6. FIVE ROUNDED QUOTIENTS by a0, each Q(n, s) = round(|n| * 2^(s + 2) / a0) with the sign of n put back -- ONE rule for negative
+ *      numerators: the magnitude is rounded to nearest, ties away from zero.  s = 28 for a Q30 numerator, 27 for a Q31 one (d, s), 26
+ *      for its half (d / 2, s / 2: no bit of d is dropped).  |n| * 2^30 does not fit 64 bits (a0 * 2^30 is 2^66), so the divide is
+ *      made in two steps:  qa = (|n| << s) / a0,  ra = the remainder;  Q = (qa << 2) + ((ra << 2) + (a0 >> 1)) / a0.
+ *      |n| << s < (2^30 + 2^35 + 64) * 2^28 < 2^63.05: an unsigned 64-bit word holds it.  qa < 2^29 (|n| < 2 a0 everywhere);  ra < a0;
+ *      (ra << 2) + (a0 >> 1) < 2^38.2;  Q < 2^31.1, clamped to int32 (only mode 1's b1 and mode 2's -b1 reach the clamp, at 2 - 2^-30).
+ *      Mode 3's b1 is 0 and mode 5's b2 is 2^30 exactly.  No divisor is zero.
+ * Nothing above leaves 64 bits anywhere in the box; tests/test_fx_cutoff_cpu.py evaluates every step in unbounded integers on the grid,
+ * a random set and all corners and holds each to the width stated here.  Nine 64-bit divides per voice at most.
+ *
+ * ACCURACY, measured by tests/test_fx_cutoff_cpu.py on the float section's grid mapped to these formats (201 values of w_q29: both
+ * ends, 72 spread geometrically, the pi / 2 seam and its 64 neighbours on either side; 17 values of q_q16; 5 modes) against an fp64
+ * evaluation of the RBJ formulas on the exact rationals w_q29 / 2^29 and q_q16 / 2^16: the largest absolute error of each word in
+ * units of 2^-30, of this function and of the route this bank had before (the same inputs converted to fp32, skred_filter_coeffs,
+ * rounded to Q2.30 as the host rounds them).  The test holds every entry of the first table to at most 4 x the second's.
+ *                     skred_fx_filter_coeffs_w                      fp32 skred_filter_coeffs, rounded (the yardstick)
+ *   mode    b0     b1     b2     a1     a2                 b0      b1      b2      a1      a2
+ *   1     0.80   1.31   0.80   2.12   1.45               99.4   198.8    99.4   243.8    93.8
+ *   2     1.02   1.67   1.02   2.12   1.45              113.1   226.2   113.1   243.8    93.8
+ *   3     0.98   0      0.98   2.12   1.45               89.0     0      89.0   243.8    93.8
+ *   4     0.98   2.12   0.98   2.12   1.45               89.5   243.8    89.5   243.8    93.8
+ *   5     1.45   2.12   0      2.12   1.45               93.8   243.8     0     243.8    93.8
+ * The largest ratio is 0.015: the integer route is some 70 times closer to fp64 than fp32 coefficients rounded to Q2.30 can be.
+ * Stability (|a2| < 2^30 and |a1| < 2^30 + a2) holds on the whole grid for modes 1 .. 5, and every word fits int32.
+ *
+ * STATE.  cut[n_voices] is an array of eight uint32 per voice (two 16-byte words): w_q29 (0: "no device cutoff"), target_q29 (0: "not
+ * moving"), up_q32, down_q32 | carry (0 .. 63), q_q16, mode, a reserved 0.  The first skred_fxbank_cutoff_match / _cutoff_owned_each /
+ * _cutoff_tags_each call with work to do allocates it (32 bytes per voice; the owner array first, when no owner call came before) and
+ * zero-fills it; that call waits for the device once.  It is freed with the bank.  Only the calls of this section and the clear below
+ * read or write it.  The only bank words they store are b0_q30 b1_q30 b2_q30 a1_q30 a2_q30 (the whole coefficient plane word and the
+ * a2 word): filter_mode, the delay line and every neighbouring word keep their bits, so the render instantiation stays right, and a
+ * voice with filter_mode == 0 keeps the words without reading them.  A bank that never calls these allocates nothing more and
+ * launches nothing more than it did before this section existed.
+ *
+ * A RECORD ON VOICE v (skred_fx_cutoff_t), the float section's steps 1 - 4 in integers:
+ *   1. v has no cutoff word (w_q29 == 0) and the record does not name BOTH SKRED_FX_CUTOFF_Q and SKRED_FX_CUTOFF_MODE: WITHHELD and
+ *      counted.
+ *   2. q = the record's with SKRED_FX_CUTOFF_Q, else the voice's; mode likewise with SKRED_FX_CUTOFF_MODE.
+ *   3. SKRED_FX_CUTOFF_ABS: wn = value (a w_q29 in the box).  SKRED_FX_CUTOFF_TRACK: k = the key word of a bent voice (section "pitch
+ *      wheel"), else phase_inc -- the word a glide runs on.  k == 0: WITHHELD and counted.  wn = ((uint64)k * value) >> 27 with value
+ *      = track_q24 = harmonic * 2 pi in Q24: phase_inc / 2^32 is cycles per frame, so w = 2 pi * harmonic * k / 2^32 radians per frame
+ *      and in Q29 that is k * (harmonic * 2 pi * 2^24) / 2^27.  A uint32 track_q24 reaches harmonic 256 / 2 pi, about the 40th; the
+ *      product is below 2^64.  wn outside the box is CLAMPED to the nearer end and counted.
+ *   4. SKRED_FX_CUTOFF_GLIDE on a voice that has a cutoff word: target = wn, the rates are the record's, carry = 0; w and the
+ *      coefficients stand until the next advance.  Otherwise (no GLIDE, or the voice's first cutoff): w = wn, target = up = down =
+ *      carry = 0 -- any movement stops -- and the five words = THE ARITHMETIC(mode, wn, q).
+ * A withheld record leaves the voice and all eight words exactly as they were.
+ *
+ * ADVANCE BY F FRAMES (skred_fxbank_cutoff_advance), the portamento's rule on w, for every moving voice of a range: c = carry + F, and
+ * c >> 6 steps are taken, stopping at arrival.  w == target: arrived at once.  Up: next = w + max(1, ((uint64)w * up_q32) >> 32),
+ * arrived if next >= target.  Down: next = w - max(1, ((uint64)w * down_q32) >> 32), arrived if next <= target.  On arrival w = THE
+ * TARGET'S BITS and target, rates and carry are zeroed; else carry = c & 63.  Then the coefficients are computed ONCE from that final
+ * w (also when no step was taken).  w at every multiple of 64 frames does not depend on how the host cuts its blocks; a voice that
+ * has landed holds the bits of a voice set with SKRED_FX_CUTOFF_ABS at the target.  A voice that does not move costs one 16-byte load.
+ *
+ * A NEW NOTE CLEARS THE WORDS.  Once the array exists, every tag launch of the bank is followed on its stream by a launch that zeroes
+ * all eight words of every voice it tagged, beside the pedal, glide and bend clears: a thief or a key struck again does not inherit
+ * a moving cutoff.  The coefficients stay what they were.  The order for a tracked note is skred_fxbank_note_on_channel, then
+ * skred_fxbank_bend_tags_each / skred_fxbank_glide_tags, then skred_fxbank_cutoff_tags_each.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_fxbank_update; host arrays travel through the staging ring; nothing
+ * waits for the device but the download and the first allocation; the same state gives the same bytes; one stream at a time per
+ * bank.  On a shard: through skred_fxshard_bank(), with that rank's local indices.  d_result of the three record calls (device,
+ * uint32[4], may be NULL; cleared on the stream ahead of the kernel): [0] voices set or started, [1] records withheld, [2] voices not
+ * owned (the _each calls) or voices of the range that did not match, [3] cutoffs clamped.
+ *
+ * skred_fx_filter_coeffs_w        pure host, THE ARITHMETIC.  out5 = b0 b1 b2 a1 a2.  SKRED_OK; 1 for mode 0 (bypass: out5 is left as it
+ *                                 is); SKRED_E_BAD_ARG for a NULL out5 or a mode outside 0 .. 5; SKRED_E_RANGE for a w_q29 or q_q16
+ *                                 outside the box.
+ * skred_fx_cutoff_check           pure host: SKRED_OK, or what the record calls refuse about n records, in this order.
+ *                                 SKRED_E_BAD_ARG: a NULL array, n < 0; in a record: unknown bits in set, ABS with TRACK or neither,
+ *                                 first_time != 0 and not both Q and MODE, a reserved word that is not 0; SKRED_E_RANGE: a named
+ *                                 q_q16 outside the box, an ABS value outside the box, a TRACK value of 0, a named mode outside
+ *                                 1 .. 5; SKRED_E_BAD_ARG: a zero up_q32 or down_q32 under GLIDE.  first_time: the caller states that
+ *                                 the voices have no cutoff word yet -- the entry points cannot know (they pass 0), and there the
+ *                                 kernel withholds and counts instead.
+ * skred_fxbank_cutoff_match       the channel sweep: the record on every voice of [first, first + count) with owner != 0 and (owner &
+ *                                 m->mask) == m->value; geometry, guard and counting as skred_fxbank_bend_match; the record is a
+ *                                 kernel argument and takes no slot of the ring.  Refused, in this order: NULL bank, match or record,
+ *                                 what skred_fx_cutoff_check refuses, what skred_owner_match_check refuses, SKRED_E_RANGE for an
+ *                                 empty range or one outside the bank.
+ * skred_fxbank_cutoff_owned_each  looks at the entries below min(n, *d_count_or_null); entry k brings recs[k] to d_voices[k] where
+ *                                 that is a voice of the bank whose owner is tags[k].  A voice listed twice is UNSPECIFIED.  Refused,
+ *                                 in skred_fxbank_bend_owned_each's order: NULL bank or list, what skred_owner_tags_check refuses,
+ *                                 n > INT32_MAX / 64, what skred_fx_cutoff_check refuses.  n == 0: SKRED_OK, nothing is done.
+ * skred_fxbank_cutoff_tags_each   by note id: skred_fxbank_release_tags' find pass over [first, first + count) into the same scratch,
+ *                                 then the call above on that list.  recs[k] goes with tags[k]: the tags travel sorted, the records
+ *                                 are permuted with them on the host.  Tags unique, none zero, n <= SKRED_OWNER_MAX_TAGS; d_result[2]
+ *                                 is 0.  Refused: as above, then SKRED_E_RANGE for an empty range or one outside the bank.
+ * skred_fxbank_cutoff_advance     the advance pass over [first, first + count).  d_result (device, uint32[2], may be NULL; cleared on
+ *                                 the stream ahead of the kernel): [0] voices still moving, [1] voices that arrived.  On a bank
+ *                                 without the array: SKRED_OK, d_result (if given) is cleared on the stream, nothing is launched.
+ *                                 SKRED_E_BAD_ARG: NULL bank, num_frames outside 1 .. 65536; SKRED_E_RANGE: count <= 0 or a range
+ *                                 outside the bank.
+ * skred_fxbank_cutoff_stop        every movement of [first, first + count) ends on `stream`: target, rates and carry are cleared, w,
+ *                                 q and mode stay; snap != 0: a moving voice's w = its target and its coefficients are computed
+ *                                 first.  Nothing to do on a bank without the array.  SKRED_E_RANGE: count < 0 or a range outside.
+ * skred_fxbank_download_cutoff    the words of [first, first + count) into host_u32x8 (8 * count words); waits for the device; zeros
+ *                                 on a bank that never set a cutoff.
+ * LIMITS, documented, not fixed: a tracked cutoff is computed when the call runs and does not follow later bends or glides: send it
+ * again.  A SKRED_CTL_FILTER store (or per-entry coefficients) on a voice with a cutoff word is overwritten by that voice's next
+ * moving advance, and otherwise leaves w stale.  A release leaves the words alone.  Out of scope: the drop-in mode, deferred items,
+ * pattern steps. */
+#define SKRED_FX_CUTOFF_W_MIN (1u << 19)
+#define SKRED_FX_CUTOFF_W_MAX (3u << 29)
+#define SKRED_FX_CUTOFF_Q_MIN (1u << 10)
+#define SKRED_FX_CUTOFF_Q_MAX (1u << 26)
+#define SKRED_FX_CUTOFF_PI_Q29 1686629713u          /* round(pi * 2^29) */
+#define SKRED_FX_CUTOFF_HALF_PI_Q29 843314857u      /* round(pi / 2 * 2^29) */
+#define SKRED_FX_CUTOFF_S1 (-1431655761ll)          /* Q31 coefficients of sin(r) / r - 1 in (r / 2)^2: about -4/3!, 16/5!, -64/7!, .. */
+#define SKRED_FX_CUTOFF_S2 286331072ll
+#define SKRED_FX_CUTOFF_S3 (-27269072ll)
+#define SKRED_FX_CUTOFF_S4 1513217ll
+#define SKRED_FX_CUTOFF_S5 (-52533ll)
+#define SKRED_FX_CUTOFF_C2 1431655759ll             /* Q31 coefficients of cos(r) - 1 + 2 (r / 2)^2: about 16/4!, -64/6!, 256/8!, .. */
+#define SKRED_FX_CUTOFF_C3 (-190887371ll)
+#define SKRED_FX_CUTOFF_C4 13634516ll
+#define SKRED_FX_CUTOFF_C5 (-605274ll)
+#define SKRED_FX_CUTOFF_C6 17511ll
+enum { SKRED_FX_CUTOFF_ABS = 1u << 0,     /* w = value, a w_q29 */
+       SKRED_FX_CUTOFF_TRACK = 1u << 1,   /* w = (k * value) >> 27, k the voice's key increment, value a track_q24: exactly one of ABS and TRACK */
+       SKRED_FX_CUTOFF_GLIDE = 1u << 2,   /* the computed w is the TARGET, reached by up_q32 / down_q32 per 64 frames */
+       SKRED_FX_CUTOFF_Q = 1u << 3,       /* the record names q_q16 */
+       SKRED_FX_CUTOFF_MODE = 1u << 4 };  /* the record names mode (1 .. 5) */
+typedef struct skred_fx_cutoff {          /* 32 bytes */
+  uint32_t set, value, q_q16, mode, up_q32, down_q32;
+  uint32_t reserved[2];                   /* 0 */
+} skred_fx_cutoff_t;
+int  skred_fx_filter_coeffs_w(int mode, uint32_t w_q29, uint32_t q_q16, int32_t out5[5]);
+int  skred_fx_cutoff_check(const skred_fx_cutoff_t *rec, int n, int first_time);
+int  skred_fxbank_cutoff_match(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, const skred_fx_cutoff_t *rec,
+                               uint32_t *d_result, void *stream);
+int  skred_fxbank_cutoff_owned_each(skred_fxbank_t *fx, const skred_fx_cutoff_t *recs, const int32_t *d_voices, const uint32_t *tags, int n,
+                                    const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+int  skred_fxbank_cutoff_tags_each(skred_fxbank_t *fx, const skred_fx_cutoff_t *recs, int first, int count, const uint32_t *tags, int n,
+                                   uint32_t *d_result, void *stream);
+int  skred_fxbank_cutoff_advance(skred_fxbank_t *fx, int first, int count, int num_frames, uint32_t *d_result, void *stream);
+int  skred_fxbank_cutoff_stop(skred_fxbank_t *fx, int first, int count, int snap, void *stream);
+int  skred_fxbank_download_cutoff(skred_fxbank_t *fx, uint32_t *host_u32x8, int first, int count);
 
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);

@@ -15,8 +15,8 @@
 //                               inc) * scale) >> 16.  TO_INC: target = target_inc.  64-bit products; where inc, the new inc or the
 //                               target is 0 or above 0xFFFFFFFF nothing is stored and the start counts as withheld.
 //   sk_fx_glide_advance_kernel  one thread per voice of the range.  A voice that does not glide costs its 16-byte load and nothing else.
-//                               A gliding one loads its increment, takes up to (carry + F) >> 6 steps -- one 32 x 32 -> high-word
-//                               multiply, a max and an add or subtract per 64 frames -- and stores the last increment (only if it
+//                               A gliding one loads its increment, takes up to (carry + F) >> 6 steps -- skx_step_64: one 32 x 32 ->
+//                               high-word multiply, a max and an add or subtract per 64 frames -- and stores the last increment (only if it
 //                               differs) and the carry, or on arrival the target's bits and four zero words.
 //   sk_fx_glide_stop_kernel     one thread per voice of the range: the words cleared, with snap the target stored first.
 //
@@ -35,6 +35,7 @@
 
 #include "skred_fx_layout.h"
 #include "skred_launch.h"
+#include "skred_fx_step_common.hpp"     // skx_step_64: the 64-frame step, stated once for the glide and the filter cutoff
 #include "skred_update_common.hpp"   // sk_entry_decode, sk_entry_owned, sk_owner_count, sk_grid, sk_list_grid, sk_result_clear
 
 static_assert(sizeof(skx_glide_t) == 16 && sizeof(skx_glide_each_t) == 32, "one 16-byte load per voice, one per entry");
@@ -121,19 +122,7 @@ __global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_glide_advance_kernel(sk
       uint32_t inc = inc0;
       bool there = inc == 0u || inc == target;
       const uint32_t c = g.w + frames;                                  // (carry <= 63, frames <= 65536)
-      for (uint32_t m = c >> 6; m && !there; --m) {
-        if (inc < target) {
-          const uint32_t d = __umulhi(inc, g.y);
-          const uint64_t next = (uint64_t)inc + (uint64_t)(d ? d : 1u);
-          there = next >= (uint64_t)target;
-          inc = (uint32_t)next;                                         // (not there: next < target, 32 bits hold it)
-        } else {
-          const uint32_t d = __umulhi(inc, g.z);                        // (d < inc: the difference cannot wrap)
-          const uint32_t next = inc - (d ? d : 1u);
-          there = next <= target;
-          inc = next;
-        }
-      }
+      for (uint32_t m = c >> 6; m && !there; --m) there = skx_step_64(inc, target, g.y, g.z);   // (the step the filter cutoff shares)
       if (there) {
         *word = target;
         *reinterpret_cast<uint4 *>(&glide[v]) = make_uint4(0u, 0u, 0u, 0u);

@@ -149,4 +149,37 @@ typedef struct { uint32_t w[SKX_GLIDE_E_WORDS]; } skx_glide_each_t;   /* 32 byte
 enum { SKX_BEND_KEY = 0, SKX_BEND_RATIO, SKX_BEND_WORDS = 2 };
 typedef struct { uint32_t w[SKX_BEND_WORDS]; } skx_bend_t;     /* 8 bytes */
 #define SKX_BEND_ONE (1u << 24)    /* the wheel at centre (equals SKRED_FX_BEND_ONE: checked in skred_fx_bend.c) */
+
+/* ---- filter cutoff (skred_fx_cutoff_kernels.hip; include/skred_amd_fxpt.h: skred_fxbank_cutoff_match / _cutoff_owned_each /
+ * _cutoff_tags_each / _cutoff_advance / _cutoff_stop) ----
+ * cut[n_voices]: eight words per voice (two 16-byte loads) beside the bend array: w_q29 (0 "no device cutoff"), target_q29 (0 "not
+ * moving"), up_q32, down_q32 | carry (0 .. 63), q_q16, mode, 0.  The float bank's sk_cut_t has the same shape (checked in
+ * skred_fx_cutoff.c): its clear kernel serves this array too */
+enum { SKX_CUT_W = 0, SKX_CUT_TARGET, SKX_CUT_UP, SKX_CUT_DOWN, SKX_CUT_CARRY, SKX_CUT_Q, SKX_CUT_MODE, SKX_CUT_RESERVED, SKX_CUT_WORDS = 8 };
+typedef struct { uint32_t w[SKX_CUT_WORDS]; } skx_cut_t;   /* 32 bytes */
+/* a record is skred_fx_cutoff_t word for word (layout and bits checked at compile time in skred_fx_cutoff.c): 32 bytes, so that set,
+ * value, q_q16, mode are one aligned 16-byte load.  The bits equal SKRED_FX_CUTOFF_* */
+#define SKX_CUTOFF_ABS   (1u << 0)
+#define SKX_CUTOFF_TRACK (1u << 1)
+#define SKX_CUTOFF_GLIDE (1u << 2)
+#define SKX_CUTOFF_Q     (1u << 3)
+#define SKX_CUTOFF_MODE  (1u << 4)
+#define SKX_CUTOFF_ALL   ((1u << 5) - 1u)
+enum { SKX_CUT_E_SET = 0, SKX_CUT_E_VALUE, SKX_CUT_E_Q, SKX_CUT_E_MODE, SKX_CUT_E_UP, SKX_CUT_E_DOWN, SKX_CUT_E_WORDS = 8 };
+typedef struct { uint32_t w[SKX_CUT_E_WORDS]; } skx_cut_each_t;   /* 32 bytes */
+/* THE ARITHMETIC's constants (equal to SKRED_FX_CUTOFF_*: checked in skred_fx_cutoff.c) */
+#define SKX_CUTOFF_W_MIN (1u << 19)
+#define SKX_CUTOFF_W_MAX (3u << 29)
+#define SKX_CUTOFF_PI_Q29 1686629713u
+#define SKX_CUTOFF_HALF_PI_Q29 843314857u
+#define SKX_CUTOFF_S1 (-1431655761ll)
+#define SKX_CUTOFF_S2 286331072ll
+#define SKX_CUTOFF_S3 (-27269072ll)
+#define SKX_CUTOFF_S4 1513217ll
+#define SKX_CUTOFF_S5 (-52533ll)
+#define SKX_CUTOFF_C2 1431655759ll
+#define SKX_CUTOFF_C3 (-190887371ll)
+#define SKX_CUTOFF_C4 13634516ll
+#define SKX_CUTOFF_C5 (-605274ll)
+#define SKX_CUTOFF_C6 17511ll
 #endif

@@ -57,6 +57,8 @@ int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint
   if (e == hipSuccess && fx->d_glide) e = (hipError_t)sk_launch_glide_clear((sk_glide_t *)fx->d_glide, d_voices, n, d_count, 1, fx->n_voices, s);
   /* ... nor a bend (skred_fx_bend.c): a thief's first bend would take its victim's key, and the centre would restore it */
   if (e == hipSuccess && fx->d_bend) e = (hipError_t)sk_launch_bend_clear((sk_bend_t *)fx->d_bend, d_voices, n, d_count, 1, fx->n_voices, s);
+  /* ... nor a cutoff word (skred_fx_cutoff.c): a thief or a key struck again does not inherit a moving cutoff; the coefficients stay */
+  if (e == hipSuccess && fx->d_cut) e = (hipError_t)sk_launch_cutoff_clear((sk_cut_t *)fx->d_cut, d_voices, n, d_count, 1, fx->n_voices, s);
   return skx_batch_end(&bt, e, who, s);
 }
 

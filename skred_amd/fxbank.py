@@ -51,10 +51,12 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_download_glide",
                   "skred_fxbank_bend_match", "skred_fxbank_bend_owned_each", "skred_fxbank_bend_tags_each", "skred_fxbank_bend_clear",
                   "skred_fxbank_download_bend",
+                  "skred_fxbank_cutoff_match", "skred_fxbank_cutoff_owned_each", "skred_fxbank_cutoff_tags_each",
+                  "skred_fxbank_cutoff_advance", "skred_fxbank_cutoff_stop", "skred_fxbank_download_cutoff",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
 FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
                        "skred_fx_ctl_each_check", "skred_fx_filter_each_check", "skred_fx_chan_check", "skred_fx_pedal_check",
-                       "skred_fx_glide_check", "skred_fx_bend_check"]                                                                     # pure host: no bank, no device
+                       "skred_fx_glide_check", "skred_fx_bend_check", "skred_fx_cutoff_check", "skred_fx_filter_coeffs_w"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -75,6 +77,9 @@ EACH_ALL = 15
 CHAN_NO_CAP = 0xFFFFFFFF                          # SKRED_CHAN_NO_CAP: a cap that never limits
 FX_GLIDE_FROM_SCALE, FX_GLIDE_TO_SCALE, FX_GLIDE_TO_INC = 1, 2, 4   # SKRED_FX_GLIDE_*: exactly one per entry
 FX_BEND_ONE = 1 << 24                             # SKRED_FX_BEND_ONE: the wheel at centre, as a Q24 ratio
+# filter cutoff: SKRED_FX_CUTOFF_* -- the set bits and the integer boxes (w_q29: Q29 radians per frame; q_q16)
+FX_CUTOFF_ABS, FX_CUTOFF_TRACK, FX_CUTOFF_GLIDE, FX_CUTOFF_Q, FX_CUTOFF_MODE = 1, 2, 4, 8, 16
+FX_CUTOFF_W_MIN, FX_CUTOFF_W_MAX, FX_CUTOFF_Q_MIN, FX_CUTOFF_Q_MAX = 1 << 19, 3 << 29, 1 << 10, 1 << 26
 FX_CTL_SPAN = 256                                 # voices or entries per workgroup of the controller and guarded-stamp kernels
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
@@ -249,6 +254,39 @@ def fx_bend_check(ratios_q24, n: Optional[int] = None) -> int:
     return int(_bind(load()).skred_fx_bend_check(r.ctypes.data if r is not None else None, int(n)))
 
 
+class FxCutoffC(C.Structure):
+    """ctypes image of ``skred_fx_cutoff_t`` (32 bytes): `set` holds exactly one of FX_CUTOFF_ABS and FX_CUTOFF_TRACK."""
+    _fields_ = [("set", C.c_uint32), ("value", C.c_uint32), ("q_q16", C.c_uint32), ("mode", C.c_uint32), ("up_q32", C.c_uint32),
+                ("down_q32", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+def fx_cutoff(set: int, value: int, q_q16: int = 0, mode: int = 0, up_q32: int = 0, down_q32: int = 0) -> FxCutoffC:
+    """One record: ``fx_cutoff(FX_CUTOFF_TRACK | FX_CUTOFF_Q | FX_CUTOFF_MODE, track_q24, 2 << 16, 1)`` is a low-pass that follows the key."""
+    return FxCutoffC(int(set), int(value), int(q_q16), int(mode), int(up_q32), int(down_q32))
+
+
+def fx_cutoff_array(recs):
+    """A contiguous ``FxCutoffC`` array from a sequence of FxCutoffC (a ctypes array of FxCutoffC passes through)."""
+    if isinstance(recs, C.Array) and recs._type_ is FxCutoffC:
+        return recs
+    recs = list(recs)
+    return (FxCutoffC * len(recs))(*recs)
+
+
+def fx_cutoff_check(recs, n: Optional[int] = None, first_time: bool = False) -> int:
+    """skred_fx_cutoff_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host, no device.  ``recs`` None: a NULL array."""
+    arr = fx_cutoff_array(recs) if recs is not None else None
+    n = (len(arr) if arr is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_cutoff_check(C.cast(arr, C.c_void_p) if arr is not None else None, int(n), int(bool(first_time))))
+
+
+def fx_filter_coeffs_w(mode: int, w_q29: int, q_q16: int):
+    """skred_fx_filter_coeffs_w: (return code, the five Q2.30 words b0 b1 b2 a1 a2 as an int32 array).  Pure host, no device."""
+    out = np.zeros(5, np.int32)
+    rc = int(_bind(load()).skred_fx_filter_coeffs_w(int(mode), int(w_q29), int(q_q16), out.ctypes.data))
+    return rc, out
+
+
 def fx_glide_check(glides, n: Optional[int] = None) -> int:
     """skred_fx_glide_check: 0, or SKRED_E_BAD_ARG (-2).  Pure host, no device.  ``glides`` None: a NULL array."""
     arr = glide_array(glides) if glides is not None else None
@@ -398,6 +436,14 @@ def _bind(L):
     L.skred_fxbank_bend_tags_each.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
     L.skred_fxbank_bend_clear.argtypes = [vp, i32, i32, i32, vp]
     L.skred_fxbank_download_bend.argtypes = [vp, vp, i32, i32]
+    L.skred_fx_cutoff_check.argtypes = [vp, i32, i32]
+    L.skred_fx_filter_coeffs_w.argtypes = [i32, C.c_uint32, C.c_uint32, vp]
+    L.skred_fxbank_cutoff_match.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.skred_fxbank_cutoff_owned_each.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_cutoff_tags_each.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+    L.skred_fxbank_cutoff_advance.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.skred_fxbank_cutoff_stop.argtypes = [vp, i32, i32, i32, vp]
+    L.skred_fxbank_download_cutoff.argtypes = [vp, vp, i32, i32]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -826,6 +872,47 @@ class DeviceFxBank:
         count = self.n - first if count is None else count
         out = np.full((max(count, 0), 2), 0xABABABAB, np.uint32)
         _check(self.L.skred_fxbank_download_bend(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_bend")
+        return out
+
+    # ---- filter cutoff (include/skred_amd_fxpt.h: skred_fxbank_cutoff_match / _cutoff_owned_each / _cutoff_tags_each / _cutoff_advance /
+    # _cutoff_stop) ----
+    def cutoff_match(self, first: int, count: int, value: int, mask: int, rec: FxCutoffC, d_result: int = 0, stream: int = 0):
+        """The channel sweep: the record on every matching voice of the range.  d_result (uint32[4], may be 0) = set or started,
+        withheld, did not match, clamped."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_cutoff_match(self.h, int(first), int(count), C.byref(m), C.byref(rec), d_result or None, stream or None),
+               "skred_fxbank_cutoff_match")
+
+    def cutoff_owned_each(self, recs, d_voices: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """Entry k brings recs[k] to d_voices[k] where that voice's owner is tags[k].  d_result (uint32[4], may be 0) = set or started,
+        withheld, voices whose owner differs, clamped."""
+        arr, t = fx_cutoff_array(recs), _tags(tags)
+        assert len(arr) == len(t), "one record per tag"
+        _check(self.L.skred_fxbank_cutoff_owned_each(self.h, C.cast(arr, C.c_void_p), d_voices or None, t.ctypes.data, len(t), d_count or None,
+                                                     d_result or None, stream or None), "skred_fxbank_cutoff_owned_each")
+
+    def cutoff_tags_each(self, recs, first: int, count: int, tags, d_result: int = 0, stream: int = 0):
+        """By note id: recs[k] on the lowest voice of the range that carries tags[k]."""
+        arr, t = fx_cutoff_array(recs), _tags(tags)
+        assert len(arr) == len(t), "one record per tag"
+        _check(self.L.skred_fxbank_cutoff_tags_each(self.h, C.cast(arr, C.c_void_p), int(first), int(count), t.ctypes.data, len(t),
+                                                    d_result or None, stream or None), "skred_fxbank_cutoff_tags_each")
+
+    def cutoff_advance(self, first: int, count: int, frames: int, d_result: int = 0, stream: int = 0):
+        """The advance pass by `frames`: d_result (uint32[2], may be 0) = still moving, arrived."""
+        _check(self.L.skred_fxbank_cutoff_advance(self.h, int(first), int(count), int(frames), d_result or None, stream or None),
+               "skred_fxbank_cutoff_advance")
+
+    def cutoff_stop(self, first: int = 0, count: Optional[int] = None, snap: bool = False, stream: int = 0):
+        count = self.n - first if count is None else count
+        _check(self.L.skred_fxbank_cutoff_stop(self.h, int(first), int(count), int(bool(snap)), stream or None), "skred_fxbank_cutoff_stop")
+
+    def download_cutoff(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The cutoff words of [first, first + count) as a (count, 8) uint32 array: w_q29, target_q29, up_q32, down_q32, carry, q_q16,
+        mode, 0; waits for the device.  Zeros on a bank that never set a cutoff."""
+        count = self.n - first if count is None else count
+        out = np.full((max(count, 0), 8), 0xABABABAB, np.uint32)
+        _check(self.L.skred_fxbank_download_cutoff(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_cutoff")
         return out
 
 

@@ -2349,8 +2349,94 @@ def fxbend():
     db.close(); plain.close()
 
 
+def fxcutoff():
+    """Filter cutoff on bank_fx(2**20) with filters, every voice sounding and tagged over 16 channels as in `fxglide` / `fxbend`: the
+    `cutoff` mode on the fixed-point bank.  (a) skred_fxbank_cutoff_tags_each(TRACK) of 256 notes beside the route the bank had
+    before: 256 coefficient sets on the host (fxbank.q30_coeffs at 4 x each note's frequency) and skred_fxbank_ctl_tags_each_filter;
+    (b) skred_fxbank_cutoff_match(TRACK) of one channel beside a download of the parameters, the channel's coefficients on the host
+    and an update of its voices; (c) skred_fxbank_cutoff_advance by 64 frames over the whole bank with nothing moving, 1 024 voices
+    moving and a sixteenth of the bank moving, skred_fxbank_glide_advance beside it in the same states; (d) the 64-frame block after
+    an advance beside steady blocks before and after it.  Medians of 12 with minimum and maximum; host time held, and stream time
+    between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES, SR = 1 << 20, 64, 16, 256, 48000
+    bank, pool, c0 = X.bank_fx(n)
+    db = X.DeviceFxBank(n)
+    db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+    out = torch.zeros(F, 2, dtype=torch.int64, device="cuda")
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    everyone = torch.arange(n, dtype=torch.int32, device="cuda")
+    db.tag_list(everyone.data_ptr(), tags)
+    chan = np.flatnonzero(v % CHANNELS == 2)                                     # channel 3
+    at = chan[::7][:NOTES]
+    note_tags = tags[at].copy()
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    value, mask = 3 << 24, 0xFF000000
+    track4 = int(round(4.0 * 2.0 * np.pi * (1 << 24)))
+    both = X.FX_CUTOFF_Q | X.FX_CUTOFF_MODE
+    first = X.fx_cutoff(X.FX_CUTOFF_TRACK | both, track4, 2 << 16, 1)
+    recs = X.fx_cutoff_array([first] * NOTES)
+    r = 2.0 ** (0.33 / 12.0 * 64.0 / SR)                                         # a third of a semitone per second: nobody arrives while timed
+    up, down = max(1, int((r - 1.0) * 2.0 ** 32)), max(1, int((1.0 - 1.0 / r) * 2.0 ** 32))
+    sweep = X.fx_cutoff(X.FX_CUTOFF_TRACK | X.FX_CUTOFF_GLIDE, 2 * track4, 0, 0, up, down)
+    glides = X.glide_array([X.glide(X.FX_GLIDE_FROM_SCALE, up, down, int(2.0 ** (-7.0 / 12.0) * 65536.0)) for _ in range(1024)])
+    view = bank.copy()
+    torch.cuda.synchronize()
+
+    def host_coeffs(idx):
+        freq = 4.0 * view["phase_inc"][idx].astype(np.float64) / 4294967296.0 * SR
+        return X.q30_coeffs(np.ones(len(idx), np.int32), np.minimum(freq, 0.45 * SR).astype(np.float32), np.full(len(idx), 2.0, np.float32), SR)
+
+    def parent_notes():                                                          # the host knows these notes' increments: the note-on's
+        c = host_coeffs(at)
+        filt = X.fx_filter_each_array([X.fx_filter_each(*(int(c[k][i]) for k in ("b0_q30", "b1_q30", "b2_q30", "a1_q30", "a2_q30"))) for i in range(NOTES)])
+        db.ctl_tags_each_filter(None, None, filt, 0, n, note_tags, res.data_ptr())
+
+    def parent_channel():                                                        # after glides and bends the increments are device state
+        db.download_params(view)
+        c = host_coeffs(chan)
+        for k in c:
+            view[k][chan] = c[k]
+        db.update(view, chan.astype(np.int32), X.DIRTY_PARAMS)
+
+    def line(label, call, words, before=None):
+        ms, held = _fx_timed(call, before)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {res.cpu().numpy().tolist()[:words]}")
+
+    print(f"fx {n} voices with filters, all sounding, tagged over {CHANNELS} channels ({n // CHANNELS} notes each)")
+    line(f"(a) the route before: {NOTES} coefficient sets on the host + ctl_tags_each_filter", parent_notes, 3)
+    line(f"(a) cutoff_tags_each(TRACK) of {NOTES} tags", lambda: db.cutoff_tags_each(recs, 0, n, note_tags, res.data_ptr()), 4)
+    line(f"(b) the route before: download_params, {len(chan)} coefficient sets on the host, update of the channel", parent_channel, 0)
+    line("(b) cutoff_match(TRACK) of one channel over the whole bank", lambda: db.cutoff_match(0, n, value, mask, first, res.data_ptr()), 4)
+    db.glide_tags(glides[:NOTES], 0, n, note_tags, res.data_ptr()); db.glide_stop(0, n, True)     # the glide array exists, nothing glides
+    line("(c) cutoff_advance by 64 frames over the whole bank, nothing moving", lambda: db.cutoff_advance(0, n, F, res.data_ptr()), 2)
+    line("(c) glide_advance by 64 frames over the whole bank, nothing gliding", lambda: db.glide_advance(0, n, F, res.data_ptr()), 2)
+    many = chan[:1024]
+    db.cutoff_tags_each(X.fx_cutoff_array([sweep] * 1024), 0, n, tags[many], res.data_ptr())
+    db.glide_tags(glides, 0, n, tags[many], res.data_ptr())
+    line("(c) cutoff_advance by 64 frames over the whole bank, 1024 voices moving", lambda: db.cutoff_advance(0, n, F, res.data_ptr()), 2)
+    line("(c) glide_advance by 64 frames over the whole bank, 1024 voices gliding", lambda: db.glide_advance(0, n, F, res.data_ptr()), 2)
+    db.cutoff_match(0, n, value, mask, sweep, res.data_ptr())
+    for k in range(0, len(chan), 1024):
+        db.glide_tags(glides, 0, n, tags[chan[k:k + 1024]], res.data_ptr())
+    line(f"(c) cutoff_advance by 64 frames over the whole bank, a sixteenth of it ({len(chan)} voices) moving", lambda: db.cutoff_advance(0, n, F, res.data_ptr()), 2)
+    line(f"(c) glide_advance by 64 frames over the whole bank, a sixteenth of it ({len(chan)} voices) gliding", lambda: db.glide_advance(0, n, F, res.data_ptr()), 2)
+
+    db.glide_stop(0, n, True); db.cutoff_stop(0, n, False)
+    db.upload(bank); db.set_sample_count(c0)
+    db.cutoff_tags_each(X.fx_cutoff_array([sweep] * 1024), 0, n, tags[many], res.data_ptr())
+    _fx_block_after(db, out, F, None, 8)
+    before = _fx_block_after(db, out, F)
+    after = _fx_block_after(db, out, F, lambda: db.cutoff_advance(0, n, F, res.data_ptr()))
+    later = _fx_block_after(db, out, F)
+    print(f"  (d) the {F}-frame block after an advance (1024 voices' coefficients moved): {_fx_stats(after)}; a steady block before it: "
+          f"{_fx_stats(before)}; after it: {_fx_stats(later)}")
+    db.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "cutoff": cutoff, "fxbend": fxbend}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "cutoff": cutoff, "fxbend": fxbend, "fxcutoff": fxcutoff}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
