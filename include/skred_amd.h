@@ -1451,7 +1451,8 @@ int  skred_bank_download_bend(skred_bank_t *bank, uint32_t *host_u32x2, int firs
  *
  * Limits: a tracked cutoff is computed when the call runs and does not follow later bends or glides: send it again.  A
  * SKRED_CTL_FILTER store (or per-entry coefficients) on a voice with a cutoff word is overwritten by that voice's next moving
- * advance, and otherwise leaves w stale.  A release leaves the words alone.  The fixed-point bank has its own integer twin
+ * advance, and otherwise leaves w stale.  A release leaves the words alone -- unless the voice has a filter envelope (the next
+ * section), whose release stage the advance pass starts from the voice's release clock.  The fixed-point bank has its own integer twin
  * (include/skred_amd_fxpt.h, section "filter cutoff").  Not built: the drop-in mode, deferred items and pattern steps.  On a
  * shard: through skred_shard_bank(), with that rank's local indices. */
 #define SKRED_CUTOFF_W_MIN 0x1p-10f
@@ -1525,6 +1526,118 @@ int  skred_bank_cutoff_stop(skred_bank_t *bank, int first, int count, int snap, 
 /* The cutoff words of [first, first + count) into host_u32x8 (8 * count words); waits for the device, like
  * skred_bank_download_owners; zeros on a bank that never set a cutoff. */
 int  skred_bank_download_cutoff(skred_bank_t *bank, uint32_t *host_u32x8, int first, int count);
+
+/* ---- filter envelope: per-note cutoff contours that follow the gate ---------------------------------------------------------------
+ *
+ * The cutoff section above sets a cutoff, tracks the key and glides to ONE target.  A subtractive voice wants a contour per note: the
+ * cutoff opens from a floor to a peak at the note-on, falls to a sustain level while the key is held, and closes after the note-off.
+ * With the cutoff calls alone the host sends one SKRED_CUTOFF_GLIDE per stage and has to time them -- and the last one it cannot time:
+ * under a sustain or sostenuto pedal, after skred_bank_stamp_match, skred_bank_release_tags or a steal the host does not know when, or
+ * whether, a slot's release clock was stamped.  The device knows: sample_release lies beside every voice, and every note-off path of
+ * the control plane ends in a stamp of that word.  So the contour is a small program kept beside the voice; the per-block pass the
+ * cutoff already has (skred_bank_cutoff_advance) steps it, and the release stage starts from the voice's own release clock.
+ *
+ * fenv[n_voices] is an array of eight words PER VOICE (two uint4: stage, w_peak, w_sustain, w_end -- the levels as fp32 bit patterns
+ * inside the cutoff box; rate_attack, rate_decay, rate_release, a reserved 0) in device memory that only the calls of this section and
+ * the cutoff calls read or write.  stage: 0 no envelope (all eight words are 0 then), 1 attack, 2 decay, 3 sustain, 4 release.  The
+ * bank allocates the array (32 bytes per voice; the cutoff and owner arrays first, when they do not exist yet) on the first
+ * skred_bank_fenv_match / _fenv_owned_each / _fenv_tags_each call and zero-fills it; that call may wait for the device once.  The
+ * envelope MOVES THE VOICE'S CUTOFF WORDS (w, target, the two rates, carry) and through them the five coefficient words; it has no
+ * arithmetic of its own: a step is the cutoff advance's one multiply, a coefficient store is THE ARITHMETIC(mode, w, q) of the cutoff
+ * section.  No render kernel, report, probe, tap or planner rule reads the array, and what the cutoff section says about the
+ * planner, the filter memory and the neighbouring words holds here.  A bank that never calls these allocates and launches nothing
+ * more, and every entry point behaves on it as it did.
+ *
+ * ENTERING A STAGE with level T and rate r (per 64 frames), from the voice's w:
+ *   the stage LANDS AT ONCE -- w = T's bits, and the next stage is entered by this rule -- if w == T, or r > 1 and w > T, or r < 1 and
+ *   w < T (the rate points away from the level).  Otherwise target = T and rate_up = rate_down = r.
+ *     attack (1):  T = w_peak,    r = rate_attack;   next: decay
+ *     decay (2):   T = w_sustain, r = rate_decay;    next: sustain
+ *     sustain (3): target = rate_up = rate_down = 0: the voice rests, not moving, and the stage word stays 3
+ *     release (4): T = w_end,     r = rate_release;  next: none -- when the release lands ALL EIGHT fenv words are cleared, target,
+ *                  rates and carry are 0, and w keeps w_end's bits: the voice is a voice set with SKRED_CUTOFF_ABS at w_end.
+ *   carry is kept across stage changes: the note keeps its 64-frame grid from the record to the end of the release.
+ *
+ * A RECORD ON VOICE v (skred_fenv_t; the voices are those of filter_mask in a slot the guard lets through):
+ *   1. v has no cutoff word (w == 0): WITHHELD and counted; both arrays of the voice stay as they were.  The base cutoff, q and mode
+ *      come from skred_bank_cutoff_* first.
+ *   2. w_now = the voice's w when the kernel runs.  SKRED_FENV_ABS: the four levels start, peak, sustain, end are w values.
+ *      SKRED_FENV_REL: each level = w_now * value, ONE multiply each; a product outside the box is CLAMPED to the nearer end, and the
+ *      VOICE is counted once however many of its levels were clamped.  A tracked base therefore gives a tracked contour.  Exactly one
+ *      of ABS and REL is named.  Without SKRED_FENV_START the start level is neither computed nor clamped.
+ *   3. SKRED_FENV_START: w = the start level at once.  Otherwise the contour starts from w_now (and `start` must be 0).
+ *   4. Any movement the voice had ends: carry = 0, the fenv words = 1, the three levels, the three rates, 0, and the attack is ENTERED
+ *      by the rule above.  Stages that land at once chain, as far as sustain (the release is entered by the advance pass only).
+ *   5. If w changed, the five coefficient words = THE ARITHMETIC(mode, w, q), once, from the final w.
+ *
+ * ADVANCE BY F FRAMES.  skred_bank_cutoff_advance is the one per-block pass.  On a bank with an fenv array, for every voice of the
+ * range with stage != 0:
+ *   1. stage is 1 .. 3 and the voice's sample_release != 0: the release is ENTERED first (it may land at once, which ends the contour).
+ *   2. c = carry + F, m = c >> 6.  m times, while the voice has a target: w = w * rate, ONE multiply; arrived at the target if w >=
+ *      target going up, w <= target going down; on arrival w = THE TARGET'S BITS and the next stage is ENTERED; the remaining steps
+ *      continue in it.  (Sustain has no target: the remaining steps do nothing.)
+ *   3. carry = c & 63 -- through sustain too, which is what keeps the grid -- or 0 when the contour ended.
+ *   4. If the voice was moving when the pass began or step 1 entered the release, the coefficients are computed ONCE from the final w.
+ *      A voice resting in sustain stores no coefficient.
+ * A voice with stage == 0 is advanced by the cutoff section's rule.  d_result keeps its meaning: [0] voices moving after the pass
+ * (a target != 0: a voice resting in sustain is not moving), [1] voices that arrived at any stage's level in the pass, stepped or at
+ * once; a voice that arrives at several levels in one pass counts once.
+ * THE STATED PROPERTY: for a fixed sequence of control calls at fixed frame positions and a block cut at every call, w at every
+ * multiple of 64 frames from the record on does not depend on where else the host cuts its blocks.
+ * Cost: a voice with stage == 0 costs its one 16-byte cutoff load and one 4-byte fenv load; one with a contour two more 16-byte
+ * loads of fenv, the second half of its cutoff words and the 8 bytes of its release clock.
+ * A trigger stamp alone does not restart a contour (a releasing contour goes on releasing); a new record does.
+ *
+ * WHO ENDS AN ENVELOPE.  Once the array exists, every tag launch of the bank is followed on its stream by a launch that zeroes all
+ * eight fenv words of all K voices of every slot it tagged -- the sixth clear, beside the owner, pedal, glide, bend and cutoff ones: a
+ * thief or a key struck again inherits no contour.  skred_bank_cutoff_match / _cutoff_owned_each / _cutoff_tags_each zero the fenv
+ * words of the voices they set or start (a withheld record leaves them), skred_bank_cutoff_stop those of every voice of its range:
+ * a cutoff call on an enveloped voice ends the contour and then does what it always did.  The order for a note is
+ * skred_bank_note_on_channel, then skred_bank_bend_tags_each / skred_bank_glide_tags, then skred_bank_cutoff_tags_each, then
+ * skred_bank_fenv_tags_each.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_bank_update; host arrays travel through its staging ring; nothing
+ * waits for the device but the download and the first allocation; one stream at a time per bank; the same state gives the same bytes.
+ * d_result of the three record calls (device, uint32[4], may be NULL; cleared on the stream ahead of the kernel): [0] voices started,
+ * [1] records withheld, [2] slots not owned (the _each calls) or slots of the range that did not match, [3] voices clamped.
+ *
+ * Limits: REL levels are computed when the record runs and do not follow later bends or glides: send the record again.  A
+ * SKRED_CTL_FILTER store on a voice with a moving contour is overwritten by the next advance.  Not built: the fixed-point bank, the
+ * drop-in mode, deferred items and pattern steps.  On a shard: through skred_shard_bank(), with that rank's local indices. */
+enum { SKRED_FENV_ABS = 1u << 0,      /* the four levels are w values inside the box */
+       SKRED_FENV_REL = 1u << 1,      /* each level = w_now * value: exactly one of ABS and REL */
+       SKRED_FENV_START = 1u << 2 };  /* w = the start level at once; without it `start` must be 0 */
+typedef struct skred_fenv { uint32_t set; float start, peak, sustain, end, rate_attack, rate_decay, rate_release; } skred_fenv_t;   /* 32 bytes */
+/* Pure host: SKRED_OK, or what the record calls refuse about K, the masks and the n records, in this order.  SKRED_E_BAD_ARG: a NULL
+ * array, n < 0; SKRED_E_RANGE: a bad K (not a power of two in 1 .. 64); SKRED_E_BAD_ARG: a voice_mask or a filter_mask that is 0 or
+ * has bits at or above K; in a record: unknown bits in set, SKRED_FENV_ABS with SKRED_FENV_REL or neither; start != 0 without
+ * SKRED_FENV_START; a value that is not finite (the levels named, the three rates); SKRED_E_RANGE: an ABS level outside the box, a REL
+ * value <= 0, a rate outside [SKRED_CUTOFF_RATE_MIN, SKRED_CUTOFF_RATE_MAX]; SKRED_E_BAD_ARG: a rate equal to 1; last, a filter_mask
+ * with a bit outside voice_mask.  voice_mask: the voices of a slot the patch plays (the note-on's mask); the entry points themselves
+ * take filter_mask alone and check it against all K lanes. */
+int  skred_fenv_check(const skred_fenv_t *recs, int n, int slot_voices, uint64_t voice_mask, uint64_t filter_mask);
+/* The channel sweep: the record on every filter_mask voice of every slot of [first, first + count) whose owner matches m.  Geometry,
+ * guard and counting are skred_bank_cutoff_match's; the record is a kernel argument.  The planner is told nothing.
+ * Refused, in this order: SKRED_E_BAD_ARG: NULL bank, match or record; SKRED_E_RANGE: a bad K; SKRED_E_BAD_ARG: a bad filter_mask;
+ * SKRED_E_RANGE: first or count not a multiple of K, count <= 0, a range outside the bank; then what skred_fenv_check refuses about
+ * the record; then what skred_owner_match_check refuses. */
+int  skred_bank_fenv_match(skred_bank_t *bank, int first, int count, int slot_voices, uint64_t filter_mask, const skred_owner_match_t *m,
+                           const skred_fenv_t *rec, uint32_t *d_result, void *stream);
+/* One record per entry: entry k (of the first min(n, *d_count_or_null)) acts on d_slots[k] only if that is a slot of the bank AND
+ * owner[slot] == tags[k] (non-zero).  A slot named twice: UNSPECIFIED.
+ * Refused, in this order: SKRED_E_BAD_ARG: NULL bank, records, list or tags, n < 0; SKRED_E_RANGE: a bad K; SKRED_E_BAD_ARG: a bad
+ * filter_mask; what skred_fenv_check refuses about the records; a zero tag, n > INT32_MAX / 64.  n == 0: SKRED_OK. */
+int  skred_bank_fenv_owned_each(skred_bank_t *bank, const skred_fenv_t *recs, int slot_voices, uint64_t filter_mask, const int32_t *d_slots,
+                                const uint32_t *tags, int n, const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+/* By note id: skred_bank_find_owned of the tags over [first, first + count) into scratch the bank owns, then the call above on that
+ * list.  recs[k] goes with tags[k]: the tags travel sorted, the records are permuted with them on the host.  1 ..
+ * SKRED_OWNER_MAX_TAGS tags, unique, none zero; d_result[2] is 0.  Refused: as above with the range behind the masks, then a repeated
+ * tag or n > SKRED_OWNER_MAX_TAGS. */
+int  skred_bank_fenv_tags_each(skred_bank_t *bank, const skred_fenv_t *recs, int first, int count, int slot_voices, uint64_t filter_mask,
+                               const uint32_t *tags, int n, uint32_t *d_result, void *stream);
+/* The fenv words of [first, first + count) into host_u32x8 (8 * count words); waits for the device, like
+ * skred_bank_download_cutoff; zeros on a bank without the array. */
+int  skred_bank_download_fenv(skred_bank_t *bank, uint32_t *host_u32x8, int first, int count);
 
 /* ---- voices sharded over the GPUs of one node (BASELINE config 3) -----------------------------------
  *

@@ -181,6 +181,7 @@ void skred_bank_destroy(skred_bank_t *b) {
   sk_glide_free(b);
   sk_bend_free(b);
   sk_cutoff_free(b);
+  sk_fenv_free(b);
   for (int i = 0; i < SK_UPD_RING; i++) {
     if (b->upd[i].d) hipFree(b->upd[i].d);
     if (b->upd[i].h) hipHostFree(b->upd[i].h);

@@ -10,6 +10,8 @@
  * device except the download and the allocation of the array by the first call that sets a cutoff.  The cutoff array is no part of
  * the bank the planner knows, and the calls tell the bank nothing: they store finite coefficient words only, and FILTER lists nobody
  * (skred_bank_expr.c, section C).  The hook that clears a re-tagged slot's words is in skred_bank_owner.c (sk_owner_tag_launch).
+ * On a bank that has a filter-envelope array (skred_bank_fenv.c) the launches receive it: a cutoff call ends the contours of the
+ * voices it sets, starts or stops, and the advance pass steps the others.
  *
  * Out of scope: the fixed-point bank, the drop-in mode, deferred items and pattern steps.
  */
@@ -127,7 +129,7 @@ int skred_cutoff_check(const skred_cutoff_t *rec, int n, int slot_voices, uint64
 }
 
 /* every lane of a slot: what the entry points hold filter_mask against */
-static uint64_t all_lanes(int K) { return K >= 1 && K < 64 ? (1ull << K) - 1ull : ~0ull; }
+uint64_t sk_all_lanes(int K) { return K >= 1 && K < 64 ? (1ull << K) - 1ull : ~0ull; }
 
 /* The checked records as they travel: out[j] = rec[perm[j]] (perm NULL: j), set and value as they stand, q, mode and the rates where
  * named, the rest zero.  Pure host */
@@ -145,7 +147,7 @@ void sk_cutoff_pack(const skred_cutoff_t *rec, int n, const uint32_t *perm, sk_c
 }
 
 /* the array, allocated and zeroed by the first call that sets a cutoff (the owner array first, when no owner call came before) */
-static int cutoff_ensure(skred_bank_t *b) {
+int sk_cutoff_ensure(skred_bank_t *b) {
   if (b->d_cut) return SKRED_OK;
   const int rc = sk_owner_ensure(b);
   if (rc) return rc;
@@ -157,7 +159,7 @@ void sk_cutoff_free(skred_bank_t *b) {
   b->d_cut = NULL;
 }
 
-static sk_cut_planes_t planes_of(const skred_bank_t *b) {
+sk_cut_planes_t sk_cutoff_planes(const skred_bank_t *b) {
   const sk_cut_planes_t p = { b->d_ro[SKP_OSC], b->d_ro[SKP_GAIN], b->d_ro[SKP_FILT] };
   return p;
 }
@@ -167,7 +169,7 @@ static int each_check(const skred_bank_t *b, const skred_cutoff_t *recs, int K, 
                       int ranged, int first, int count, const char *who) {
   if (!b) return fail(SKRED_E_BAD_ARG, "%s: no bank", who);
   if (!tags) return fail(SKRED_E_BAD_ARG, "%s: no tags", who);
-  int rc = cut_check(recs, n, K, all_lanes(K), filter_mask, 0, ranged ? b->n_voices : -1, first, count, who);
+  int rc = cut_check(recs, n, K, sk_all_lanes(K), filter_mask, 0, ranged ? b->n_voices : -1, first, count, who);
   if (rc) return rc;
   for (int k = 0; k < n; k++)
     if (!tags[k]) return fail(SKRED_E_BAD_ARG, "%s: tag %d is 0 (0 means nobody)", who, k);
@@ -187,8 +189,8 @@ static int each_launch(skred_bank_t *b, const skred_cutoff_t *recs, const uint32
   memcpy(h + rec_bytes, tags, (size_t)n * sizeof(uint32_t));
   const char *src = (const char *)sk_batch_send(b, &bt, bytes, 0, s);   /* (every byte is read by one workgroup) */
   if (!src) return SKRED_E_NO_DEVICE;
-  const sk_cut_planes_t p = planes_of(b);
-  const hipError_t e = (hipError_t)sk_launch_cutoff_each(b->d_cut, b->d_bend, (const sk_cut_each_t *)src, K, filter_mask, d_slots,
+  const sk_cut_planes_t p = sk_cutoff_planes(b);
+  const hipError_t e = (hipError_t)sk_launch_cutoff_each(b->d_cut, b->d_bend, b->d_fenv, (const sk_cut_each_t *)src, K, filter_mask, d_slots,
                                                          (const uint32_t *)(src + rec_bytes), b->d_owner, n, d_count, b->n_voices, &p, d_result,
                                                          bt.cnt, bt.done, bt.seq, s);
   return sk_batch_end(&bt, e, who, s);                    /* (FILTER lists nobody: the planner's reports stand) */
@@ -198,16 +200,16 @@ int skred_bank_cutoff_match(skred_bank_t *b, int first, int count, int slot_voic
                             const skred_cutoff_t *rec, uint32_t *d_result, void *stream) {
   if (!b) return fail(SKRED_E_BAD_ARG, "cutoff_match: no bank");
   if (!m) return fail(SKRED_E_BAD_ARG, "cutoff_match: no match");
-  int rc = cut_check(rec, 1, slot_voices, all_lanes(slot_voices), filter_mask, 0, b->n_voices, first, count, "cutoff_match");
+  int rc = cut_check(rec, 1, slot_voices, sk_all_lanes(slot_voices), filter_mask, 0, b->n_voices, first, count, "cutoff_match");
   if (rc) return rc;
   if ((rc = skred_owner_match_check(m))) return rc;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = cutoff_ensure(b))) return rc;
+  if ((rc = sk_cutoff_ensure(b))) return rc;
   sk_cut_each_t r;
   sk_cutoff_pack(rec, 1, NULL, &r);
-  const sk_cut_planes_t p = planes_of(b);
-  const hipError_t e = (hipError_t)sk_launch_cutoff_match(b->d_cut, b->d_bend, &r, slot_voices, filter_mask, first, count, b->d_owner, m->value,
-                                                          m->mask, &p, d_result, (hipStream_t)stream);
+  const sk_cut_planes_t p = sk_cutoff_planes(b);
+  const hipError_t e = (hipError_t)sk_launch_cutoff_match(b->d_cut, b->d_bend, b->d_fenv, &r, slot_voices, filter_mask, first, count, b->d_owner,
+                                                          m->value, m->mask, &p, d_result, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "cutoff_match launch -> %s", hipGetErrorString(e));
   return SKRED_OK;                                         /* (finite coefficients only: the planner's reports stand) */
 }
@@ -219,7 +221,7 @@ int skred_bank_cutoff_owned_each(skred_bank_t *b, const skred_cutoff_t *recs, in
   if (rc) return rc;
   if (n == 0) return SKRED_OK;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = cutoff_ensure(b))) return rc;
+  if ((rc = sk_cutoff_ensure(b))) return rc;
   return each_launch(b, recs, NULL, slot_voices, filter_mask, d_slots, tags, n, d_count_or_null, d_result, "cutoff_owned_each", (hipStream_t)stream);
 }
 
@@ -234,7 +236,7 @@ int skred_bank_cutoff_tags_each(skred_bank_t *b, const skred_cutoff_t *recs, int
   (void)sk_owner_pack(tags, n, sorted, perm);
   hipStream_t s = (hipStream_t)stream;
   HIP_TRY(hipSetDevice(b->device));
-  if ((rc = cutoff_ensure(b))) return rc;
+  if ((rc = sk_cutoff_ensure(b))) return rc;
   if ((rc = sk_owner_find_launch(b, first, count, slot_voices, sorted, n, b->d_owner_slots, s))) return rc;
   /* entry j is the lowest slot that carries sorted[j], or -1: the guard holds on every entry that is a slot */
   return each_launch(b, recs, perm, slot_voices, filter_mask, b->d_owner_slots, sorted, n, NULL, d_result, "cutoff_tags_each", s);
@@ -252,8 +254,9 @@ int skred_bank_cutoff_advance(skred_bank_t *b, int first, int count, int num_fra
     return SKRED_OK;
   }
   HIP_TRY(hipSetDevice(b->device));
-  const sk_cut_planes_t p = planes_of(b);
-  const hipError_t e = (hipError_t)sk_launch_cutoff_advance(b->d_cut, &p, first, count, num_frames, d_result, (hipStream_t)stream);
+  const sk_cut_planes_t p = sk_cutoff_planes(b);
+  const hipError_t e = (hipError_t)sk_launch_cutoff_advance(b->d_cut, b->d_fenv, b->d_ro[SKP_ENV_S], &p, first, count, num_frames, d_result,
+                                                            (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "cutoff_advance launch -> %s", hipGetErrorString(e));
   return SKRED_OK;                                         /* (finite coefficients only: the planner's reports stand) */
 }
@@ -264,8 +267,8 @@ int skred_bank_cutoff_stop(skred_bank_t *b, int first, int count, int snap, void
   if (rc) return rc;
   if (count == 0 || !b->d_cut) return SKRED_OK;            /* (no cutoff was ever set: nothing moves) */
   HIP_TRY(hipSetDevice(b->device));
-  const sk_cut_planes_t p = planes_of(b);
-  const hipError_t e = (hipError_t)sk_launch_cutoff_stop(b->d_cut, &p, first, count, snap != 0, (hipStream_t)stream);
+  const sk_cut_planes_t p = sk_cutoff_planes(b);
+  const hipError_t e = (hipError_t)sk_launch_cutoff_stop(b->d_cut, b->d_fenv, &p, first, count, snap != 0, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "cutoff_stop launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
 }

@@ -90,7 +90,8 @@ void sk_owner_free(skred_bank_t *b) {
  * that has a pedal array (skred_bank_pedal.c) clears the tagged slots' pedal words right behind it: a new note starts with no bit
  * of the note it replaces; a bank that has a glide array (skred_bank_glide.c) clears the glide words of the slots' voices likewise,
  * and one that has a bend array (skred_bank_bend.c) the bend words: a thief's first bend must not restore its victim's key; one that
- * has a cutoff array (skred_bank_cutoff.c) the cutoff words: a thief does not inherit a moving cutoff */
+ * has a cutoff array (skred_bank_cutoff.c) the cutoff words: a thief does not inherit a moving cutoff; one that has a filter-envelope
+ * array (skred_bank_fenv.c) the fenv words: nor a contour */
 int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t *tags, int n, const uint32_t *d_count, int slot_voices,
                         uint32_t *d_result, const char *who, hipStream_t s) {
   int rc = sk_owner_ensure(b);
@@ -107,6 +108,7 @@ int sk_owner_tag_launch(skred_bank_t *b, const int32_t *d_slots, const uint32_t 
   if (e == hipSuccess && b->d_glide) e = (hipError_t)sk_launch_glide_clear(b->d_glide, d_slots, n, d_count, slot_voices, b->n_voices, s);
   if (e == hipSuccess && b->d_bend) e = (hipError_t)sk_launch_bend_clear(b->d_bend, d_slots, n, d_count, slot_voices, b->n_voices, s);
   if (e == hipSuccess && b->d_cut) e = (hipError_t)sk_launch_cutoff_clear(b->d_cut, d_slots, n, d_count, slot_voices, b->n_voices, s);
+  if (e == hipSuccess && b->d_fenv) e = (hipError_t)sk_launch_fenv_clear(b->d_fenv, d_slots, n, d_count, slot_voices, b->n_voices, s);
   return sk_batch_end(&bt, e, who, s);
 }
 

@@ -15,6 +15,7 @@
  *   skred_bank_glide.c   portamento: per-voice glides, started under the owner guard, advanced and landed on the device
  *   skred_bank_bend.c    the pitch wheel: absolute bends that keep the key's bits beside the sounding increment
  *   skred_bank_cutoff.c  filter cutoff on the device: key-tracked cutoffs that glide and land, coefficients computed where the voice lives
+ *   skred_bank_fenv.c    filter envelope: per-note cutoff contours, stepped by the cutoff's advance pass, released by the voice's clock
  */
 #ifndef SKRED_BANK_PRIV_H
 #define SKRED_BANK_PRIV_H
@@ -215,6 +216,10 @@ struct skred_bank {
   /* filter cutoff (skred_bank_cutoff.c), allocated and zeroed by the first call that sets a cutoff */
   sk_cut_t *d_cut;                  /* [n_voices] w, target, rate_up, rate_down, carry, q, mode, 0 per voice; w 0: no device cutoff; NULL:
                                        no cutoff was ever set, and the tag launches clear nothing; no render kernel reads it */
+  /* filter envelope (skred_bank_fenv.c), allocated and zeroed by the first record call */
+  sk_fenv_t *d_fenv;                /* [n_voices] stage, w_peak, w_sustain, w_end, rate_attack, rate_decay, rate_release, 0 per voice; stage
+                                       0: no contour; NULL: no record was ever sent, the tag launches clear nothing and the cutoff
+                                       launches run as they always ran; no render kernel reads it */
 };
 
 /* per-voice classification (host shadow) */
@@ -322,6 +327,15 @@ void sk_bend_pack(const float *ratios, int n, const uint32_t *perm, uint32_t *ou
  * rec[j]), the named words as they stand, the others zero.  Pure host */
 void sk_cutoff_free(skred_bank_t *b);
 void sk_cutoff_pack(const skred_cutoff_t *rec, int n, const uint32_t *perm, sk_cut_each_t *out);
+/* ... the array, allocated and zeroed if it does not exist yet (the owner array first; the bank's device is current); the planes the
+ * cutoff and fenv launches touch; every lane of a slot (what the entry points hold filter_mask against) */
+int sk_cutoff_ensure(skred_bank_t *b);
+sk_cut_planes_t sk_cutoff_planes(const skred_bank_t *b);
+uint64_t sk_all_lanes(int K);
+/* skred_bank_fenv.c: the filter-envelope array (skred_bank_destroy); n checked records as they travel -- out[j] = rec[perm[j]] (perm
+ * NULL: rec[j]), word for word, `start` zero where it is not named.  Pure host */
+void sk_fenv_free(skred_bank_t *b);
+void sk_fenv_pack(const skred_fenv_t *rec, int n, const uint32_t *perm, sk_fenv_each_t *out);
 /* skred_bank_expr.c: n checked per-entry records as they travel -- out[j] = each[perm[j]] (perm NULL: each[j]), named values word for
  * word, the others zeroed; returns the SKRED_EACH_* bits of all of them together.  Pure host */
 uint32_t sk_each_pack(const skred_ctl_each_t *each, int n, const uint32_t *perm, sk_each_t *out);

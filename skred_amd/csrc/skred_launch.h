@@ -24,6 +24,8 @@
  *   skred_bend_kernels.hip    sk_launch_bend_clear, sk_launch_bend_match, sk_launch_bend_each, sk_launch_bend_range_clear
  *   skred_cutoff_kernels.hip  sk_launch_cutoff_clear, sk_launch_cutoff_match, sk_launch_cutoff_each, sk_launch_cutoff_advance,
  *                             sk_launch_cutoff_stop
+ *   skred_fenv_kernels.hip    sk_launch_fenv_clear, sk_launch_fenv_match, sk_launch_fenv_each (the envelope's advance is
+ *                             sk_launch_cutoff_advance with the array)
  *   skred_fx_pedal_kernels.hip  skx_launch_pedal_stamps, skx_launch_pedal_latch, skx_launch_pedal_up (sk_launch_pedal_clear by
  *                             skred_fx_owner.c too)
  *   skred_fx_glide_kernels.hip  skx_launch_glide_start, skx_launch_glide_advance, skx_launch_glide_stop (prototypes in
@@ -504,28 +506,70 @@ typedef struct {
   const sk_plane_t *osc;
   sk_plane_t *gain, *filt;
 } sk_cut_planes_t;
+/* The filter envelope's array (declared here: the cutoff launches take it; the section below has the rest).  fenv[n_voices]: eight
+ * words per voice (two 16-byte loads) beside the cutoff array; stage 0: no envelope, and then all eight words are 0 */
+enum { SK_FENV_STAGE = 0, SK_FENV_W_PEAK, SK_FENV_W_SUSTAIN, SK_FENV_W_END, SK_FENV_RATE_ATTACK, SK_FENV_RATE_DECAY, SK_FENV_RATE_RELEASE,
+       SK_FENV_RESERVED, SK_FENV_WORDS = 8 };
+enum { SK_FENV_OFF = 0, SK_FENV_ATTACK, SK_FENV_DECAY, SK_FENV_SUSTAIN, SK_FENV_RELEASE };
+typedef struct {
+  uint32_t w[SK_FENV_WORDS];
+} sk_fenv_t;
 /* cut[d_slots[k] + l] = 0 (both halves), l < slot_voices, under sk_launch_owner_tag's list rule: launched behind it by a bank that has
  * a cutoff array */
 int sk_launch_cutoff_clear(sk_cut_t *cut, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
                            hipStream_t stream);
 /* the record on the filter_mask voices of the slots of [first, first + count) whose owner matches; bend: the pitch-wheel array or
- * NULL (TRACK reads a bent voice's key).  d_result[4] (may be NULL; zeroed on `stream` ahead of the kernel) += voices set or started,
- * records withheld, slots of the range that did not match, cutoffs clamped */
-int sk_launch_cutoff_match(sk_cut_t *cut, const sk_bend_t *bend, const sk_cut_each_t *rec, int slot_voices, uint64_t filter_mask, int first,
-                           int count, const uint32_t *owner, uint32_t value, uint32_t mask, const sk_cut_planes_t *planes,
-                           uint32_t *d_result, hipStream_t stream);
+ * NULL (TRACK reads a bent voice's key); fenv: the filter-envelope array or NULL (a voice set or started loses its contour: its
+ * eight fenv words = 0).  d_result[4] (may be NULL; zeroed on `stream` ahead of the kernel) += voices set or started, records
+ * withheld, slots of the range that did not match, cutoffs clamped */
+int sk_launch_cutoff_match(sk_cut_t *cut, const sk_bend_t *bend, sk_fenv_t *fenv, const sk_cut_each_t *rec, int slot_voices,
+                           uint64_t filter_mask, int first, int count, const uint32_t *owner, uint32_t value, uint32_t mask,
+                           const sk_cut_planes_t *planes, uint32_t *d_result, hipStream_t stream);
+/* entry k applies d_each[k] (16-byte aligned) on the filter_mask voices of d_slots[k] where that is a slot whose owner is d_tags[k];
+ * fenv as above; d_result[4] as above, [2]: slots whose owner differs */
+int sk_launch_cutoff_each(sk_cut_t *cut, const sk_bend_t *bend, sk_fenv_t *fenv, const sk_cut_each_t *d_each, int slot_voices,
+                          uint64_t filter_mask, const int32_t *d_slots, const uint32_t *d_tags, const uint32_t *owner, int n,
+                          const uint32_t *d_count, int n_voices, const sk_cut_planes_t *planes, uint32_t *d_result, uint32_t *cnt,
+                          uint32_t *done, uint32_t seq, hipStream_t stream);
+/* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] (may be NULL; zeroed on `stream` ahead of
+ * the kernel) += voices still moving, voices that arrived.  fenv == NULL: the plain instantiation, the kernel of a bank without a
+ * filter-envelope array (env_s is not read); else the envelope instantiation, which steps the contours and reads sample_release
+ * (env_s: SKP_ENV_S) of the voices that have one */
+int sk_launch_cutoff_advance(sk_cut_t *cut, sk_fenv_t *fenv, const sk_plane_t *env_s, const sk_cut_planes_t *planes, int first, int count,
+                             int num_frames, uint32_t *d_result, hipStream_t stream);
+/* target, rates and carry of [first, first + count) = 0; snap != 0: a moving voice's w = its target and its coefficients first; fenv
+ * (or NULL): the eight fenv words of every voice of the range that has a contour = 0 */
+int sk_launch_cutoff_stop(sk_cut_t *cut, sk_fenv_t *fenv, const sk_cut_planes_t *planes, int first, int count, int snap, hipStream_t stream);
+
+/* ---- filter envelope (skred_bank_fenv.c -> skred_fenv_kernels.hip; include/skred_amd.h: skred_bank_fenv_match / _fenv_owned_each /
+ * _fenv_tags_each, and skred_bank_cutoff_advance on a bank that has the array) ----
+ * Only the fenv launches and the cutoff launches above read or write fenv[]; the contour moves the voice's cutoff words and through
+ * them the five coefficient words, with the cutoff section's arithmetic and nothing else (skred_fenv_common.hpp: sk_fenv_enter,
+ * sk_fenv_advance). */
+/* A record is skred_fenv_t word for word: 32 bytes, two aligned 16-byte loads */
+#define SK_FENV_ABS   (1u << 0)
+#define SK_FENV_REL   (1u << 1)
+#define SK_FENV_START (1u << 2)
+#define SK_FENV_ALL   ((1u << 3) - 1u)
+enum { SK_FENV_E_SET = 0, SK_FENV_E_START, SK_FENV_E_PEAK, SK_FENV_E_SUSTAIN, SK_FENV_E_END, SK_FENV_E_RATE_ATTACK, SK_FENV_E_RATE_DECAY,
+       SK_FENV_E_RATE_RELEASE, SK_FENV_E_WORDS = 8 };
+typedef struct {
+  uint32_t w[SK_FENV_E_WORDS];
+} sk_fenv_each_t;
+/* fenv[d_slots[k] + l] = 0 (both halves), l < slot_voices, under sk_launch_owner_tag's list rule: launched behind it by a bank that has
+ * a filter-envelope array */
+int sk_launch_fenv_clear(sk_fenv_t *fenv, const int32_t *d_slots, int n, const uint32_t *d_count, int slot_voices, int n_voices,
+                         hipStream_t stream);
+/* the record on the filter_mask voices of the slots of [first, first + count) whose owner matches.  d_result[4] (may be NULL; zeroed
+ * on `stream` ahead of the kernel) += voices started, records withheld, slots of the range that did not match, voices clamped */
+int sk_launch_fenv_match(sk_fenv_t *fenv, sk_cut_t *cut, const sk_fenv_each_t *rec, int slot_voices, uint64_t filter_mask, int first,
+                         int count, const uint32_t *owner, uint32_t value, uint32_t mask, const sk_cut_planes_t *planes, uint32_t *d_result,
+                         hipStream_t stream);
 /* entry k applies d_each[k] (16-byte aligned) on the filter_mask voices of d_slots[k] where that is a slot whose owner is d_tags[k];
  * d_result[4] as above, [2]: slots whose owner differs */
-int sk_launch_cutoff_each(sk_cut_t *cut, const sk_bend_t *bend, const sk_cut_each_t *d_each, int slot_voices, uint64_t filter_mask,
-                          const int32_t *d_slots, const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count,
-                          int n_voices, const sk_cut_planes_t *planes, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq,
-                          hipStream_t stream);
-/* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] (may be NULL; zeroed on `stream` ahead of
- * the kernel) += voices still moving, voices that arrived */
-int sk_launch_cutoff_advance(sk_cut_t *cut, const sk_cut_planes_t *planes, int first, int count, int num_frames, uint32_t *d_result,
-                             hipStream_t stream);
-/* target, rates and carry of [first, first + count) = 0; snap != 0: a moving voice's w = its target and its coefficients first */
-int sk_launch_cutoff_stop(sk_cut_t *cut, const sk_cut_planes_t *planes, int first, int count, int snap, hipStream_t stream);
+int sk_launch_fenv_each(sk_fenv_t *fenv, sk_cut_t *cut, const sk_fenv_each_t *d_each, int slot_voices, uint64_t filter_mask,
+                        const int32_t *d_slots, const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
+                        const sk_cut_planes_t *planes, uint32_t *d_result, uint32_t *cnt, uint32_t *done, uint32_t seq, hipStream_t stream);
 
 /* ---- pedals on the fixed-point bank (skred_fx_pedal.c -> skred_fx_pedal_kernels.hip; include/skred_amd_fxpt.h:
  * skred_fxbank_stamp_owned_pedal / _release_tags_pedal / _pedal_latch / _pedal_up) ----

@@ -54,13 +54,14 @@ ABI_SYMBOLS = [
     "skred_bank_bend_match", "skred_bank_bend_owned_each", "skred_bank_bend_tags_each", "skred_bank_bend_clear", "skred_bank_download_bend",
     "skred_bank_cutoff_match", "skred_bank_cutoff_owned_each", "skred_bank_cutoff_tags_each", "skred_bank_cutoff_advance",
     "skred_bank_cutoff_stop", "skred_bank_download_cutoff",
+    "skred_bank_fenv_match", "skred_bank_fenv_owned_each", "skred_bank_fenv_tags_each", "skred_bank_download_fenv",
 ]
 # ... and the one it declares outside the skred_amd_ / skred_bank_ / skred_shard_ / skred_seq_ families (pure host, no handle)
 HOST_ABI_SYMBOLS = ["skred_notes_check", "skred_steal_check", "skred_slot_query_check", "skred_slot_notes_check", "skred_slot_steal_check",
                     "skred_ctl_check", "skred_owner_tags_check", "skred_owner_match_check", "skred_ctl_each_check",
                     "skred_filter_each_check", "skred_filter_coeffs",
                     "skred_chan_check", "skred_pedal_check", "skred_glide_check", "skred_bend_check",
-                    "skred_cutoff_check", "skred_filter_coeffs_w"]
+                    "skred_cutoff_check", "skred_filter_coeffs_w", "skred_fenv_check"]
 
 # SKRED_DIRTY_* / SKRED_STAMP_* of include/skred_amd.h
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN = 1, 2, 4, 8
@@ -261,6 +262,32 @@ def cutoff_array(recs):
     return (CutoffC * len(recs))(*recs)
 
 
+# SKRED_FENV_* (skred_bank_fenv_match / _fenv_owned_each / _fenv_tags_each)
+FENV_ABS, FENV_REL, FENV_START = 1, 2, 4
+FENV_OFF, FENV_ATTACK, FENV_DECAY, FENV_SUSTAIN, FENV_RELEASE = range(5)
+
+
+class FenvC(C.Structure):
+    """ctypes image of ``skred_fenv_t`` (32 bytes): `set` names ABS or REL, and START if the contour begins at `start`."""
+    _fields_ = [("set", C.c_uint32), ("start", C.c_float), ("peak", C.c_float), ("sustain", C.c_float), ("end", C.c_float),
+                ("rate_attack", C.c_float), ("rate_decay", C.c_float), ("rate_release", C.c_float)]
+
+
+def fenv(set: int, peak: float, sustain: float, end: float, rate_attack: float, rate_decay: float, rate_release: float,
+         start: float = 0.0) -> FenvC:
+    """One filter-envelope record: ``fenv(FENV_REL, 8.0, 2.0, 1.0, 1.5, 0.9, 0.8)`` opens each note's cutoff to eight times its base,
+    falls to twice the base while the key is held and closes to the base after the note-off (rates per 64 frames)."""
+    return FenvC(int(set), start, peak, sustain, end, rate_attack, rate_decay, rate_release)
+
+
+def fenv_array(recs):
+    """A contiguous ``FenvC`` array from a sequence of FenvC (a ctypes array of FenvC passes through)."""
+    if isinstance(recs, C.Array) and recs._type_ is FenvC:
+        return recs
+    recs = list(recs)
+    return (FenvC * len(recs))(*recs)
+
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -421,6 +448,11 @@ def load() -> C.CDLL:
     L.skred_bank_cutoff_advance.argtypes = [vp, i32, i32, i32, vp, vp]
     L.skred_bank_cutoff_stop.argtypes = [vp, i32, i32, i32, vp]
     L.skred_bank_download_cutoff.argtypes = [vp, vp, i32, i32]
+    L.skred_fenv_check.argtypes = [vp, i32, i32, C.c_uint64, C.c_uint64]
+    L.skred_bank_fenv_match.argtypes = [vp, i32, i32, i32, C.c_uint64, vp, vp, vp, vp]
+    L.skred_bank_fenv_owned_each.argtypes = [vp, vp, i32, C.c_uint64, vp, vp, i32, vp, vp, vp]
+    L.skred_bank_fenv_tags_each.argtypes = [vp, vp, i32, i32, i32, C.c_uint64, vp, i32, vp, vp]
+    L.skred_bank_download_fenv.argtypes = [vp, vp, i32, i32]
     _lib = L
     return L
 
@@ -567,6 +599,13 @@ def cutoff_check(recs, slot_voices: int, voice_mask: int, filter_mask: int, firs
     arr = cutoff_array(recs) if recs is not None else None
     return int(load().skred_cutoff_check(C.cast(arr, C.c_void_p) if arr is not None else None, len(arr) if arr is not None else 0,
                                          int(slot_voices), int(voice_mask), int(filter_mask), int(bool(first_time))))
+
+
+def fenv_check(recs, slot_voices: int, voice_mask: int, filter_mask: int) -> int:
+    """skred_fenv_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4) for what the record calls would refuse.  Pure host."""
+    arr = fenv_array(recs) if recs is not None else None
+    return int(load().skred_fenv_check(C.cast(arr, C.c_void_p) if arr is not None else None, len(arr) if arr is not None else 0,
+                                       int(slot_voices), int(voice_mask), int(filter_mask)))
 
 
 class DeviceBank:
@@ -1162,6 +1201,38 @@ class DeviceBank:
         count = self.n - first if count is None else count
         out = np.zeros((count, 8), np.uint32)
         _check(self.L.skred_bank_download_cutoff(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_cutoff")
+        return out
+
+    # ---- filter envelope (include/skred_amd.h: skred_bank_fenv_match / _fenv_owned_each / _fenv_tags_each; cutoff_advance steps it) ----
+    def fenv_match(self, first: int, count: int, slot_voices: int, filter_mask: int, m: OwnerMatchC, rec: FenvC, d_result: int = 0,
+                   stream: int = 0):
+        """The channel sweep: `rec` on the filter_mask voices of every slot of the range whose owner matches.  d_result (uint32[4], may
+        be 0): voices started, records withheld, slots that did not match, voices clamped."""
+        _check(self.L.skred_bank_fenv_match(self.h, int(first), int(count), int(slot_voices), int(filter_mask), C.byref(m), C.byref(rec),
+                                            d_result or None, stream or None), "skred_bank_fenv_match")
+
+    def fenv_owned_each(self, recs, slot_voices: int, filter_mask: int, d_slots: int, tags, d_count: int = 0, d_result: int = 0,
+                        stream: int = 0):
+        """Entry k applies recs[k] on the masked voices of d_slots[k] where that slot's owner is tags[k]."""
+        arr, t = fenv_array(recs), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_fenv_owned_each(self.h, C.cast(arr, C.c_void_p), int(slot_voices), int(filter_mask), d_slots or None,
+                                                 t.ctypes.data, len(t), d_count or None, d_result or None, stream or None),
+               "skred_bank_fenv_owned_each")
+
+    def fenv_tags_each(self, recs, first: int, count: int, slot_voices: int, filter_mask: int, tags, d_result: int = 0, stream: int = 0):
+        """By note id: recs[k] reaches the lowest slot of the range that carries tags[k]."""
+        arr, t = fenv_array(recs), tag_array(tags)
+        assert len(arr) == len(t)
+        _check(self.L.skred_bank_fenv_tags_each(self.h, C.cast(arr, C.c_void_p), int(first), int(count), int(slot_voices), int(filter_mask),
+                                                t.ctypes.data, len(t), d_result or None, stream or None), "skred_bank_fenv_tags_each")
+
+    def download_fenv(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The fenv words of [first, first + count) as a (count, 8) uint32 array: stage, w_peak, w_sustain, w_end, rate_attack,
+        rate_decay, rate_release, 0; waits for the device.  Zeros on a bank without the array."""
+        count = self.n - first if count is None else count
+        out = np.zeros((count, 8), np.uint32)
+        _check(self.L.skred_bank_download_fenv(self.h, out.ctypes.data, int(first), int(count)), "skred_bank_download_fenv")
         return out
 
     def download_bend(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:

@@ -2127,6 +2127,121 @@ def cutoff():
     db.close()
 
 
+def fenv():
+    """The filter envelope on the `cutoff` mode's bank: bank_patch("3sk", 2**20) with the carriers filtered, every copy sounding and
+    tagged over 16 channels.  (a) skred_bank_fenv_tags_each of 256 notes beside the parent's route for ONE contour: three
+    skred_bank_cutoff_tags_each(GLIDE) calls and, between the first two, the read of cutoff_advance's arrival count behind a device
+    wait that times the decay (the third call the parent cannot time at all under a pedal; it is counted as if it could); (b)
+    skred_bank_cutoff_advance by 64 frames over the whole bank WITHOUT the array (the plain instantiation: the parent commit's kernel,
+    the same code and register figures) and with it: nothing enveloped, 1 024 voices moving, the whole bank resting in sustain;
+    (c) the 64-frame block after an advance beside steady blocks.  Medians of 12 with minimum and maximum; host time held, and
+    stream time between events."""
+    D = device
+    n, K, REPS, F, CHANNELS, NOTES, RATE = 1 << 20, 4, 12, 64, 16, 256, 44100.0
+    CARRIERS = 0x7
+    bank, tables, g = banks.bank_patch("3sk", n)
+    now = int(g.synth_sample_count)
+    v = np.arange(n)
+    sel = (v % K) < 3
+    e = bank["voice_amp_envelope"]
+    bank["voice_use_amp_envelope"][sel] = 1
+    e["attack_time"][sel], e["decay_time"][sel], e["sustain_level"][sel], e["release_time"][sel] = 20.0, 50.0, 0.6, 100.0
+    e["velocity"][sel], e["is_active"][sel] = 1.0, 1
+    e["sample_start"][sel] = np.uint64(now - 40000)
+    bank["voice_filter_mode"][sel] = 1
+    for c, x in zip(("b0", "b1", "b2", "a1", "a2"), D.filter_coeffs(1, 2000.0, 0.707, RATE)):
+        bank["voice_filter"][c][sel] = x
+    size = int(bank["voice_table_size"][0])
+    db = device.DeviceBank(n)
+    db.set_tables(tables); db.set_globals(g); db.upload(bank)
+    slots = np.arange(0, n, K, dtype=np.int32)
+    idx = np.arange(len(slots), dtype=np.uint32)
+    tags = (((idx % CHANNELS) + 1) << 24 | (idx // CHANNELS + 1)).astype(np.uint32)
+    dl_all = torch.from_numpy(slots).cuda()
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    out = torch.zeros(F, 2, device="cuda")
+    on3 = np.flatnonzero(idx % CHANNELS == 2)
+    note_tags = tags[on3[::7][:NOTES]].copy()                                   # 256 notes of channel 3
+    anybody = D.owner_match(0, 0)
+    QM = D.CUTOFF_Q | D.CUTOFF_MODE
+    track = D.cutoff(D.CUTOFF_TRACK | QM, 4.0 * 2.0 * np.pi / size, 0.9, 1)
+    glides = [D.cutoff_array([D.cutoff(D.CUTOFF_TRACK | D.CUTOFF_GLIDE, h * 2.0 * np.pi / size, rate_up=1.5, rate_down=0.9)] * NOTES) for h in (16.0, 8.0, 4.0)]
+    contour = D.fenv_array([D.fenv(D.FENV_REL, 4.0, 2.0, 1.0, 1.5, 0.9, 0.8)] * NOTES)
+    slow = D.fenv(D.FENV_REL, 4.0, 2.0, 1.0, 1.0005, 0.9995, 0.9995)
+    rest = D.fenv(D.FENV_REL, 1.0, 1.0, 1.0, 1.5, 0.9, 0.8)                     # every level is the base: sustain at once
+    torch.cuda.synchronize()
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        t0 = time.perf_counter()
+        call()
+        host = time.perf_counter() - t0
+        e1.record()
+        e1.synchronize()
+        return host * 1e3, e0.elapsed_time(e1)
+
+    def stats(x):
+        return f"median {np.median(x):.4f} ms (min {np.min(x):.4f}, max {np.max(x):.4f})"
+
+    def series(call, before=None):
+        host, stream = [], []
+        for it in range(2 + REPS):
+            if before is not None:
+                before()
+            torch.cuda.synchronize()
+            h, s_ms = timed(call)
+            if it >= 2:
+                host.append(h); stream.append(s_ms)
+        return f"host time held {stats(host)}; stream time between events {stats(stream)}"
+
+    def parent_contour():
+        db.cutoff_tags_each(glides[0], 0, n, K, CARRIERS, note_tags)
+        db.cutoff_advance(0, n, F, res.data_ptr())
+        res.cpu()                                                # the wait: has the attack landed?
+        db.cutoff_tags_each(glides[1], 0, n, K, CARRIERS, note_tags)
+        db.cutoff_tags_each(glides[2], 0, n, K, CARRIERS, note_tags)
+
+    def adv():
+        db.cutoff_advance(0, n, F, res.data_ptr())
+
+    print(f"3sk {n} voices = {n // K} slots of {K}, carriers filtered, every copy sounding, tagged over {CHANNELS} channels; medians of {REPS}")
+    db.tag_slots(dl_all.data_ptr(), tags, K)
+    db.cutoff_match(0, n, K, CARRIERS, anybody, track, res.data_ptr())
+    print(f"  the base: cutoff_match(TRACK) on every copy: d_result = {res.cpu().numpy().tolist()}")
+    print(f"  (b) cutoff_advance by {F} frames over the whole bank, NO fenv array (the parent's kernel), nothing moving: {series(adv)}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    print(f"  (a) the parent's route for one contour of {NOTES} notes (three cutoff_tags_each(GLIDE), one advance count read behind a wait): {series(parent_contour)}")
+    db.cutoff_stop(0, n, True)
+    print(f"  (a) fenv_tags_each of {NOTES} notes: {series(lambda: db.fenv_tags_each(contour, 0, n, K, CARRIERS, note_tags, res.data_ptr()))}; d_result = {res.cpu().numpy().tolist()}")
+    db.cutoff_stop(0, n, True)
+    print(f"  (b) cutoff_advance by {F} frames over the whole bank, the array present, nothing enveloped: {series(adv)}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    db.cutoff_tags_each(D.cutoff_array([track] * NOTES), 0, n, K, 0xF, note_tags)      # all four voices of the notes get a base: 1 024 voices
+    db.fenv_tags_each(D.fenv_array([slow] * NOTES), 0, n, K, 0xF, note_tags, res.data_ptr())
+    started = res.cpu().numpy().tolist()
+    print(f"  (b) cutoff_advance by {F} frames over the whole bank, {started[0]} voices moving in their contours: {series(adv)}; d_result = {res.cpu().numpy()[:2].tolist()}")
+
+    def block():
+        return timed(lambda: db.render_mix(F, out.data_ptr(), 2, 0, 0))[1]
+
+    for _ in range(8):
+        block()
+    steady = [block() for _ in range(REPS)]
+    after = []
+    for k in range(REPS):
+        block()
+        adv()
+        after.append(block())
+    moved = res.cpu().numpy()[:2].tolist()
+    print(f"  (c) the {F}-frame block after cutoff_advance (d_result = {moved}): {stats(after)}; a steady block before: {stats(steady)}; "
+          f"kernel {db.last_kernel()}, list violations {db.list_violations()}")
+    db.fenv_match(0, n, K, CARRIERS, anybody, rest, res.data_ptr())
+    started = res.cpu().numpy().tolist()
+    stages = db.download_fenv(0, 4096)[:, 0]
+    print(f"  (b) cutoff_advance by {F} frames over the whole bank, {started[0]} voices resting in sustain (stages of the first 4096 voices: "
+          f"{sorted(set(stages.tolist()))}): {series(adv)}; d_result = {res.cpu().numpy()[:2].tolist()}")
+    db.close()
+
+
 def fxpedal():
     """Pedals on bank_fx(2**20), every voice sounding and tagged over 16 channels (tag = channel << 24 | voice // 16 + 1), 256
     note-offs of one channel held back, then the pedal goes up: the `pedal` mode on the fixed-point bank.  (a) each new call beside
@@ -2436,7 +2551,7 @@ def fxcutoff():
 
 
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "cutoff": cutoff, "fxbend": fxbend, "fxcutoff": fxcutoff}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "cutoff": cutoff, "fenv": fenv, "fxbend": fxbend, "fxcutoff": fxcutoff}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
