@@ -1602,7 +1602,7 @@ int  skred_bank_download_cutoff(skred_bank_t *bank, uint32_t *host_u32x8, int fi
  * [1] records withheld, [2] slots not owned (the _each calls) or slots of the range that did not match, [3] voices clamped.
  *
  * Limits: REL levels are computed when the record runs and do not follow later bends or glides: send the record again.  A
- * SKRED_CTL_FILTER store on a voice with a moving contour is overwritten by the next advance.  Not built: the fixed-point bank, the
+ * SKRED_CTL_FILTER store on a voice with a moving contour is overwritten by the next advance.  Not built: the
  * drop-in mode, deferred items and pattern steps.  On a shard: through skred_shard_bank(), with that rank's local indices. */
 enum { SKRED_FENV_ABS = 1u << 0,      /* the four levels are w values inside the box */
        SKRED_FENV_REL = 1u << 1,      /* each level = w_now * value: exactly one of ABS and REL */

@@ -961,8 +961,8 @@ int  skred_fxbank_download_bend(skred_fxbank_t *fx, uint32_t *host_u32x2, int fi
  *                                 on a bank that never set a cutoff.
  * LIMITS, documented, not fixed: a tracked cutoff is computed when the call runs and does not follow later bends or glides: send it
  * again.  A SKRED_CTL_FILTER store (or per-entry coefficients) on a voice with a cutoff word is overwritten by that voice's next
- * moving advance, and otherwise leaves w stale.  A release leaves the words alone.  Out of scope: the drop-in mode, deferred items,
- * pattern steps. */
+ * moving advance, and otherwise leaves w stale.  A release leaves the words alone -- unless the voice has a filter envelope (the next
+ * section).  Out of scope: the drop-in mode, deferred items, pattern steps. */
 #define SKRED_FX_CUTOFF_W_MIN (1u << 19)
 #define SKRED_FX_CUTOFF_W_MAX (3u << 29)
 #define SKRED_FX_CUTOFF_Q_MIN (1u << 10)
@@ -999,6 +999,138 @@ int  skred_fxbank_cutoff_tags_each(skred_fxbank_t *fx, const skred_fx_cutoff_t *
 int  skred_fxbank_cutoff_advance(skred_fxbank_t *fx, int first, int count, int num_frames, uint32_t *d_result, void *stream);
 int  skred_fxbank_cutoff_stop(skred_fxbank_t *fx, int first, int count, int snap, void *stream);
 int  skred_fxbank_download_cutoff(skred_fxbank_t *fx, uint32_t *host_u32x8, int first, int count);
+
+/* ---- filter envelope: per-note cutoff contours that follow the gate, in integers -----------------------------------------------------
+ *
+ * The fixed-point twin of the float bank's section "filter envelope" (include/skred_amd.h: skred_fenv_check ..
+ * skred_bank_download_fenv), per voice -- no slots, no masks.  THIS is the place of record for the integer definition.  With the cutoff
+ * calls alone a host sends one SKRED_FX_CUTOFF_GLIDE per stage and times them itself, and the last one it cannot time: under a pedal,
+ * after skred_fxbank_stamp_match, skred_fxbank_release_tags or a steal it does not know when, or whether, a voice's release clock was
+ * stamped.  The device knows: sample_release (SKX_TIME words 2, 3) lies beside every voice and every note-off path stamps it.  So the
+ * contour is a small program kept beside the voice; skred_fxbank_cutoff_advance, the per-block pass the cutoff already has, steps it,
+ * and the release is entered from the voice's own release clock.  The envelope has NO ARITHMETIC OF ITS OWN: a step is the cutoff
+ * section's 64-frame step with up_q32 = down_q32 = the stage's rate, a level is compared as the uint32 it is, and a coefficient store
+ * is THE ARITHMETIC(mode, w_q29, q_q16) of the cutoff section.  No render kernel reads the array.
+ *
+ * STATE.  fenv[n_voices] is an array of eight uint32 per voice (two 16-byte words):
+ *     stage | w_peak | w_sustain | w_end          the levels are w_q29 values inside THE BOX of the cutoff section
+ *     rate_attack_q32 | rate_decay_q32 | rate_release_q32 | 0
+ * stage: 0 off (then all eight words are 0), 1 attack, 2 decay, 3 sustain, 4 release.  The first skred_fxbank_fenv_match /
+ * _fenv_owned_each / _fenv_tags_each call with work to do allocates it (32 bytes per voice; the owner and cutoff arrays first, when
+ * they do not exist yet) and zero-fills it; that call may wait for the device once.  It is freed with the bank.  Only the calls of
+ * this section, the cutoff calls and the clear below read or write it.  The array has the shape of the float bank's fenv array
+ * (checked at compile time), so the float bank's clear kernel serves it at one voice per slot, as it serves cut[].  A bank that never
+ * calls these allocates nothing more and launches nothing more, and every entry point behaves on it as it did, to the byte.
+ *
+ * ENTERING A STAGE with level T and rate r (a Q32 fraction of w per 64 frames), from the voice's w.  An integer rate has no direction:
+ * the direction is w < T (up) or w > T (down).
+ *   The stage LANDS AT ONCE iff w == T; the next stage is then entered by this same rule.  Otherwise target = T and up_q32 = down_q32
+ *   = r.  (T is in the box, so T != 0: "target == 0" goes on meaning "not moving".)
+ *     attack (1):  T = w_peak,    r = rate_attack_q32;   next: decay
+ *     decay (2):   T = w_sustain, r = rate_decay_q32;    next: sustain
+ *     sustain (3): target = up_q32 = down_q32 = 0: the voice rests, not moving, and the stage word stays 3
+ *     release (4): T = w_end,     r = rate_release_q32;  next: off -- when the release lands ALL EIGHT fenv words are cleared, target,
+ *                  rates and carry become 0, and w keeps the bits of w_end: the voice is bit-identical, in all eight cutoff words and
+ *                  the five coefficients, to one set with SKRED_FX_CUTOFF_ABS at w_end.
+ *   carry survives stage changes: the note keeps its 64-frame grid from the record to the end of the release.
+ *
+ * A RECORD ON VOICE v (skred_fx_fenv_t: set, start, peak, sustain, end, rate_attack_q32, rate_decay_q32, rate_release_q32):
+ *   1. v has no cutoff word (w_q29 == 0): WITHHELD and counted; both arrays of the voice stay untouched.  The base cutoff, q and mode
+ *      come from skred_fxbank_cutoff_* first.
+ *   2. w_now = the voice's w_q29 when the kernel runs.  SKRED_FX_FENV_ABS: the four levels are w_q29 values in the box.
+ *      SKRED_FX_FENV_REL: each level = ((uint64)w_now * value_q16) >> 16, value_q16 a uint32 ratio in Q16 (2^16 is "the present
+ *      cutoff"; up to 65536 x).  w_now <= 3 * 2^29 < 2^31 and value_q16 < 2^32, so THE PRODUCT IS BELOW 2^63 and the shifted level below
+ *      2^47: both fit a uint64, and the clamp is made on the 64-bit value before it is narrowed.  A level outside the box is CLAMPED to
+ *      the nearer end, and the VOICE is counted once however many of its levels were clamped.  Exactly one of ABS and REL is named.
+ *      Without SKRED_FX_FENV_START the start level is neither computed nor clamped (and must be 0 in the record).
+ *   3. Any movement the voice had ends and carry = 0.  SKRED_FX_FENV_START: w = the start level at once; otherwise the contour starts
+ *      from w_now.
+ *   4. The fenv words = 1, the three levels, the three rates, 0, and the attack is ENTERED by the rule above.  Stages that land at once
+ *      chain as far as sustain (peak == w: decay is entered; sustain == peak too: the voice rests in sustain).  The release is entered
+ *      by the advance pass only.
+ *   5. If w changed, the five coefficient words = THE ARITHMETIC(mode, w, q), once, from the final w.
+ *
+ * ADVANCE BY F FRAMES.  skred_fxbank_cutoff_advance stays the one per-block pass.  On a bank with an fenv array, for every voice of
+ * the range with stage != 0:
+ *   1. stage is 1 .. 3 and the voice's sample_release != 0 (lo | hi): the release is ENTERED first (it may land at once, which ends the
+ *      contour).
+ *   2. c = carry + F (carry <= 63, F <= 65536: below 2^17).  Then c >> 6 times, while the voice has a target: one step of the cutoff
+ *      section -- up: next = w + max(1, ((uint64)w * r) >> 32), arrived if next >= target; down: next = w - max(1, ((uint64)w * r) >>
+ *      32), arrived if next <= target.  w <= 3 * 2^29 and r < 2^32: the product is below 2^63, the step at most w - 1 (down cannot
+ *      wrap), next going up below 2 w <= 3 * 2^30 < 2^32 (formed in 64 bits all the same, as the cutoff section forms it).  On arrival w
+ *      = THE TARGET'S BITS and the next stage is ENTERED; the remaining steps continue in that stage.  (Sustain has no target: the
+ *      remaining steps do nothing.)  A stage with a target was entered with w != target and a step that does not arrive leaves w !=
+ *      target, so the step is never taken on w == target.
+ *   3. carry = c & 63 -- through sustain as well, which is what makes the property below hold -- or 0 when the contour ended.
+ *   4. If the voice had a target when the pass began, or step 1 entered the release, the coefficients are computed ONCE from the final
+ *      w.  A voice resting in sustain stores nothing.
+ * A voice with stage == 0 follows the cutoff section's rule unchanged.  d_result keeps its meaning: [0] voices with a target after the
+ * pass (a voice resting in sustain has none), [1] voices that arrived at any level in the pass, stepped or at once; each such voice
+ * counts once.  A trigger stamp alone does not restart a contour (a releasing contour goes on releasing); a new record does.
+ * THE STATED PROPERTY: for a fixed sequence of control calls at fixed frame positions and a block cut at every call, w at every
+ * multiple of 64 frames from the record on does not depend on where else the host cuts its blocks.
+ * Cost: on a bank with the array a voice with stage == 0 costs its 16-byte cutoff load and one more 4-byte load (its stage word); one
+ * with a contour the two fenv words, its second cutoff word and the 8 bytes of its release clock.  On a bank without the array the
+ * pass is the kernel it was.
+ *
+ * DECIDED HERE, beyond the proposal's text: (a) REL value_q16 is Q16 and the clamp precedes the narrowing, as step 2 states; (b) the
+ * record's steps 2 and 3 are ordered so that every REL level, the start included, is taken from w_now and not from the start level;
+ * (c) a record on a voice that already has a contour replaces it (carry = 0: the new note's grid starts at the record); (d) the
+ * advance compares a contoured voice's up_q32 only -- the two rates of such a voice are one word twice, since every cutoff record
+ * that could split them ends the contour; (e) a release that lands in the pass that enters it counts in [1] once and computes the
+ * coefficients, whether it landed at once or by steps; (f) a zero rate is refused by the check (a stage must move), a rate so small that
+ * ((uint64)w * r) >> 32 is 0 moves by 1 per 64 frames, as in the cutoff section.
+ *
+ * WHO ENDS AN ENVELOPE.  Once the array exists, every tag launch of the bank is followed on its stream by a launch that zeroes all
+ * eight fenv words of every voice it tagged, beside the pedal, glide, bend and cutoff clears: a thief or a key struck again inherits no
+ * contour.  skred_fxbank_cutoff_match / _cutoff_owned_each / _cutoff_tags_each zero the fenv words of the voices they set or start (a
+ * withheld record leaves them), skred_fxbank_cutoff_stop those of every voice of its range, moving or resting: a cutoff call on an
+ * enveloped voice ends the contour and then does what it always did.  The order for a note is skred_fxbank_note_on_channel, then
+ * skred_fxbank_bend_tags_each / skred_fxbank_glide_tags, then skred_fxbank_cutoff_tags_each, then skred_fxbank_fenv_tags_each.
+ *
+ * All calls are asynchronous on `stream` and ordered like skred_fxbank_update; host arrays travel through the staging ring; nothing
+ * waits for the device but the download and the first allocation; the same state gives the same bytes; one stream at a time per
+ * bank.  On a shard: through skred_fxshard_bank(), with that rank's local indices.  d_result of the three record calls (device,
+ * uint32[4], may be NULL; cleared on the stream ahead of the kernel): [0] voices started, [1] records withheld, [2] voices not owned
+ * (the _each calls) or voices of the range that did not match, [3] voices clamped.
+ *
+ * skred_fx_fenv_check             pure host: SKRED_OK, or what the record calls refuse about n records, in this order.
+ *                                 SKRED_E_BAD_ARG: a NULL array, n < 0; then record by record: SKRED_E_BAD_ARG: unknown bits in set;
+ *                                 ABS together with REL, or neither; start != 0 without START; SKRED_E_RANGE: an ABS level outside
+ *                                 the box (start only with START); a REL value of 0 (start only with START); SKRED_E_BAD_ARG: a zero
+ *                                 rate.
+ * skred_fxbank_fenv_match         the channel sweep: the record on every voice of [first, first + count) with owner != 0 and (owner &
+ *                                 m->mask) == m->value; geometry, guard and counting as skred_fxbank_cutoff_match; the record is a
+ *                                 kernel argument and takes no slot of the ring.  Refused, in skred_fxbank_cutoff_match's order: NULL
+ *                                 bank, match or record, what skred_fx_fenv_check refuses, what skred_owner_match_check refuses,
+ *                                 SKRED_E_RANGE for an empty range or one outside the bank.
+ * skred_fxbank_fenv_owned_each    looks at the entries below min(n, *d_count_or_null); entry k brings recs[k] to d_voices[k] where
+ *                                 that is a voice of the bank whose owner is tags[k].  A voice listed twice is UNSPECIFIED.  Refused,
+ *                                 in skred_fxbank_cutoff_owned_each's order: NULL bank or list, what skred_owner_tags_check refuses,
+ *                                 n > INT32_MAX / 64, what skred_fx_fenv_check refuses.  n == 0: SKRED_OK, nothing is done.
+ * skred_fxbank_fenv_tags_each     by note id: skred_fxbank_release_tags' find pass over [first, first + count) into the same scratch,
+ *                                 then the call above on that list.  recs[k] goes with tags[k]: the tags travel sorted, the records
+ *                                 are permuted with them on the host.  Tags unique, none zero, n <= SKRED_OWNER_MAX_TAGS; d_result[2]
+ *                                 is 0.  Refused: as above, then SKRED_E_RANGE for an empty range or one outside the bank.
+ * skred_fxbank_download_fenv      the fenv words of [first, first + count) into host_u32x8 (8 * count words); waits for the device;
+ *                                 zeros on a bank without the array.
+ * LIMITS, documented, not fixed: REL levels are computed when the record runs and do not follow later bends or glides: send the record
+ * again.  A SKRED_CTL_FILTER store on a voice with a moving contour is overwritten by the next advance.  Out of scope: the drop-in
+ * mode, deferred items, pattern steps. */
+enum { SKRED_FX_FENV_ABS = 1u << 0,      /* the four levels are w_q29 values inside the box */
+       SKRED_FX_FENV_REL = 1u << 1,      /* each level = (w_now * value_q16) >> 16, clamped: exactly one of ABS and REL */
+       SKRED_FX_FENV_START = 1u << 2 };  /* w = the start level at once; without it `start` must be 0 */
+typedef struct skred_fx_fenv {           /* 32 bytes */
+  uint32_t set, start, peak, sustain, end, rate_attack_q32, rate_decay_q32, rate_release_q32;
+} skred_fx_fenv_t;
+int  skred_fx_fenv_check(const skred_fx_fenv_t *recs, int n);
+int  skred_fxbank_fenv_match(skred_fxbank_t *fx, int first, int count, const skred_owner_match_t *m, const skred_fx_fenv_t *rec,
+                             uint32_t *d_result, void *stream);
+int  skred_fxbank_fenv_owned_each(skred_fxbank_t *fx, const skred_fx_fenv_t *recs, const int32_t *d_voices, const uint32_t *tags, int n,
+                                  const uint32_t *d_count_or_null, uint32_t *d_result, void *stream);
+int  skred_fxbank_fenv_tags_each(skred_fxbank_t *fx, const skred_fx_fenv_t *recs, int first, int count, const uint32_t *tags, int n,
+                                 uint32_t *d_result, void *stream);
+int  skred_fxbank_download_fenv(skred_fxbank_t *fx, uint32_t *host_u32x8, int first, int count);
 
 /* Same on host buffers (synchronous). */
 int  skred_fxbank_render_host(skred_fxbank_t *fx, int num_frames, int interp, int64_t *mix, int32_t *stems_or_null);

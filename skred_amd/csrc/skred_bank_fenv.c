@@ -10,7 +10,7 @@
  * skred_bank_owner.c (sk_owner_tag_launch) that clears a re-tagged slot's words.  The calls tell the bank nothing: they store finite
  * coefficient words only, and FILTER lists nobody.
  *
- * Out of scope: the fixed-point bank, the drop-in mode, deferred items and pattern steps.
+ * Out of scope: the drop-in mode, deferred items and pattern steps.
  */
 #include <math.h>
 #include <stddef.h>

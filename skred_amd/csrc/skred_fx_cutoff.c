@@ -10,6 +10,8 @@
  * compiler flag can move a bit of it.  The channel sweep's record is a kernel argument; it, the advance and the stop ship no bytes
  * and so take no slot of the ring.  Nothing here waits for the device except the download and the allocation of the array by the
  * first call that sets a cutoff.  The hook that clears a re-tagged voice's words is in skred_fx_owner.c (skx_owner_tag_launch).
+ * Every launch here takes the bank's filter-envelope array (skred_fx_fenv.c; NULL on a bank that has none): a cutoff record or a stop
+ * ends the contours it touches, and the advance steps them.
  *
  * Out of scope: the drop-in mode, deferred items and pattern steps.
  */
@@ -135,8 +137,8 @@ void skx_cutoff_pack(const skred_fx_cutoff_t *rec, int n, const uint32_t *perm, 
 }
 
 /* the array beside the bend array, allocated and zeroed by the first call that sets a cutoff (the owner array first, when no owner call
- * came before) */
-static int skx_cutoff_ensure(skred_fxbank_t *fx) {
+ * came before); skred_fx_fenv.c enters it ahead of its own array */
+int skx_cutoff_ensure(skred_fxbank_t *fx) {
   if (fx->d_cut) return SKRED_OK;
   const int rc = skx_owner_ensure(fx);
   if (rc) return rc;
@@ -169,7 +171,7 @@ int skred_fxbank_cutoff_match(skred_fxbank_t *fx, int first, int count, const sk
   if ((rc = skx_cutoff_ensure(fx))) return rc;
   skx_cut_each_t r;
   skx_cutoff_pack(rec, 1, NULL, &r);
-  const hipError_t e = (hipError_t)skx_launch_cutoff_match(fx->d_cut, fx->d_bend, &r, first, count, fx->d_owner, m->value, m->mask, fx->d_ro,
+  const hipError_t e = (hipError_t)skx_launch_cutoff_match(fx->d_cut, fx->d_bend, fx->d_fenv, &r, first, count, fx->d_owner, m->value, m->mask, fx->d_ro,
                                                            d_result, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx cutoff_match launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
@@ -193,7 +195,7 @@ int skred_fxbank_cutoff_owned_each(skred_fxbank_t *fx, const skred_fx_cutoff_t *
   memcpy(h + rec_bytes, tags, (size_t)n * sizeof(uint32_t));
   const char *src = (const char *)skx_batch_send(&bt, bytes, s);
   if (!src) return SKRED_E_NO_DEVICE;
-  const hipError_t e = (hipError_t)skx_launch_cutoff_each(fx->d_cut, fx->d_bend, (const skx_cut_each_t *)src, d_voices,
+  const hipError_t e = (hipError_t)skx_launch_cutoff_each(fx->d_cut, fx->d_bend, fx->d_fenv, (const skx_cut_each_t *)src, d_voices,
                                                           (const uint32_t *)(src + rec_bytes), fx->d_owner, n, d_count_or_null, fx->n_voices,
                                                           fx->d_ro, d_result, s);
   return skx_batch_end(&bt, e, "fx cutoff_owned_each", s);
@@ -225,7 +227,7 @@ int skred_fxbank_cutoff_tags_each(skred_fxbank_t *fx, const skred_fx_cutoff_t *r
   const skx_cut_each_t *src = (const skx_cut_each_t *)skx_batch_send(&ent, bytes, s);
   /* entry j is the lowest voice that carries sorted[j], or -1: the guard holds on every entry that is a voice */
   if (src && e == hipSuccess)
-    e = (hipError_t)skx_launch_cutoff_each(fx->d_cut, fx->d_bend, src, fx->d_owner_found, (const uint32_t *)find.sl->d + 2 * (size_t)n, fx->d_owner,
+    e = (hipError_t)skx_launch_cutoff_each(fx->d_cut, fx->d_bend, fx->d_fenv, src, fx->d_owner_found, (const uint32_t *)find.sl->d + 2 * (size_t)n, fx->d_owner,
                                            n, NULL, fx->n_voices, fx->d_ro, d_result, s);
   rc = skx_batch_end(&ent, e, "fx cutoff_tags_each", s);
   const int rc_find = skx_batch_end(&find, hipSuccess, "fx cutoff_tags_each", s);
@@ -243,7 +245,7 @@ int skred_fxbank_cutoff_advance(skred_fxbank_t *fx, int first, int count, int nu
     if (d_result) HIP_TRY(hipMemsetAsync(d_result, 0, 2 * sizeof(uint32_t), (hipStream_t)stream));
     return SKRED_OK;
   }
-  const hipError_t e = (hipError_t)skx_launch_cutoff_advance(fx->d_cut, fx->d_ro, first, count, num_frames, d_result, (hipStream_t)stream);
+  const hipError_t e = (hipError_t)skx_launch_cutoff_advance(fx->d_cut, fx->d_fenv, fx->d_ro, first, count, num_frames, d_result, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx cutoff_advance launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
 }
@@ -254,7 +256,7 @@ int skred_fxbank_cutoff_stop(skred_fxbank_t *fx, int first, int count, int snap,
   if (rc) return rc;
   if (count == 0 || !fx->d_cut) return SKRED_OK;             /* (no cutoff was ever set: nothing moves) */
   HIP_TRY(hipSetDevice(fx->device));
-  const hipError_t e = (hipError_t)skx_launch_cutoff_stop(fx->d_cut, fx->d_ro, first, count, snap != 0, (hipStream_t)stream);
+  const hipError_t e = (hipError_t)skx_launch_cutoff_stop(fx->d_cut, fx->d_fenv, fx->d_ro, first, count, snap != 0, (hipStream_t)stream);
   if (e != hipSuccess) return fail(SKRED_E_NO_DEVICE, "fx cutoff_stop launch -> %s", hipGetErrorString(e));
   return SKRED_OK;
 }

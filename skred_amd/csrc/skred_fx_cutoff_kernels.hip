@@ -18,6 +18,12 @@
 //                                stores the last w, or on arrival the target's bits, and computes the coefficients ONCE.
 //   sk_fx_cutoff_stop_kernel     one thread per voice of the range: target, rates and carry cleared; with snap w = target first.
 //
+// THE FILTER ENVELOPE (skred_fx_fenv.c, skred_fx_fenv_kernels.hip).  On a bank that has an fenv array the match, each and stop kernels
+// receive it (NULL otherwise: a wave-uniform branch, and the bytes stored are the ones stored without it) and zero the eight fenv
+// words of every voice they set, start or stop: a new cutoff ends the contour.  The advance kernel is a template: ENV = false is the
+// kernel as it was (profiles/fxcutoff_usage.txt), ENV = true loads the voice's stage word beside its first half and hands a voice that
+// has a contour to skx_fenv_advance (skred_fx_fenv_common.hpp), which also reads its release clock (SKX_TIME words 2, 3).
+//
 // Every step is exact integer arithmetic: the same bits on every machine.  Counts are sk_owner_count's.  Plain vector stores and
 // ordinary atomics only; no workgroup waits for another.
 #include <hip/hip_runtime.h>
@@ -27,23 +33,15 @@
 #include "skred_launch.h"
 #include "skred_fx_cutoff_common.hpp"
 #include "skred_fx_step_common.hpp"
+#include "skred_fx_fenv_common.hpp"   // skx_cut_planes_t, skx_cut_a / _b, skx_fenv_zero, skx_fenv_advance
 #include "skred_update_common.hpp"   // sk_entry_decode, sk_entry_owned, sk_range_lane, sk_owner_count, sk_grid, sk_list_grid, sk_result_clear
 
 static_assert(sizeof(skx_cut_t) == 32 && sizeof(skx_cut_each_t) == 32, "two 16-byte loads per voice; a record is 32 bytes");
 
-// the planes the cutoff kernels touch: phase_inc read, the coefficient words stored
-struct skx_cut_planes_t {
-  const skx_plane_t *osc;
-  skx_plane_t *filt, *filt2;
-};
-
-__device__ __forceinline__ uint4 *skx_cut_a(skx_cut_t *cut, int v) { return reinterpret_cast<uint4 *>(&cut[v].w[0]); }
-__device__ __forceinline__ uint4 *skx_cut_b(skx_cut_t *cut, int v) { return reinterpret_cast<uint4 *>(&cut[v].w[SKX_CUT_CARRY]); }
-
 // THE RULE on voice v: ra = set, value, q_q16, mode; rb = up_q32, down_q32.  Returns 1: set or started, 2: withheld; clamped: the
-// tracked product lay outside the box
-__device__ __forceinline__ int skx_cutoff_apply(skx_cut_t *cut, const skx_bend_t *bend, const skx_cut_planes_t &p, int v, const uint4 &ra,
-                                                const uint2 &rb, bool &clamped) {
+// tracked product lay outside the box.  fenv (or NULL): a voice set or started loses its contour
+__device__ __forceinline__ int skx_cutoff_apply(skx_cut_t *cut, const skx_bend_t *bend, skx_fenv_t *fenv, const skx_cut_planes_t &p, int v,
+                                                const uint4 &ra, const uint2 &rb, bool &clamped) {
   const uint4 a = *skx_cut_a(cut, v);                                    // w, target, up, down
   const uint4 b = *skx_cut_b(cut, v);                                    // carry, q, mode, 0
   const uint32_t set = ra.x;
@@ -62,6 +60,7 @@ __device__ __forceinline__ int skx_cutoff_apply(skx_cut_t *cut, const skx_bend_t
     clamped = f < SKX_CUTOFF_W_MIN || f > SKX_CUTOFF_W_MAX;
     wn = f < SKX_CUTOFF_W_MIN ? SKX_CUTOFF_W_MIN : f > SKX_CUTOFF_W_MAX ? SKX_CUTOFF_W_MAX : (uint32_t)f;
   }
+  if (fenv) skx_fenv_zero(fenv, v);
   if ((set & SKX_CUTOFF_GLIDE) && has) {                                 // a pure start: w and the coefficients stand
     *skx_cut_a(cut, v) = make_uint4(a.x, wn, rb.x, rb.y);
     *skx_cut_b(cut, v) = make_uint4(0u, q, mode, 0u);
@@ -73,20 +72,20 @@ __device__ __forceinline__ int skx_cutoff_apply(skx_cut_t *cut, const skx_bend_t
   return 1;
 }
 
-__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_match_kernel(skx_cut_t *cut, const skx_bend_t *bend, skx_cut_each_t rec, int first,
-                                                                           int count, const uint32_t *__restrict__ owner, uint32_t value,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_match_kernel(skx_cut_t *cut, const skx_bend_t *bend, skx_fenv_t *fenv, skx_cut_each_t rec,
+                                                                           int first, int count, const uint32_t *__restrict__ owner, uint32_t value,
                                                                            uint32_t omask, skx_cut_planes_t p, uint32_t *d_result) {
   __shared__ uint32_t sums[4];
   const sk_lane_t t = sk_range_lane(first, count, 1);                    // (inside the bank: checked on the host)
   const bool hit = t.in_range && sk_owner_matches(owner[t.v], value, omask);
   int did = 0;
   bool clamped = false;
-  if (hit) did = skx_cutoff_apply(cut, bend, p, t.v, make_uint4(rec.w[0], rec.w[1], rec.w[2], rec.w[3]), make_uint2(rec.w[4], rec.w[5]), clamped);
+  if (hit) did = skx_cutoff_apply(cut, bend, fenv, p, t.v, make_uint4(rec.w[0], rec.w[1], rec.w[2], rec.w[3]), make_uint2(rec.w[4], rec.w[5]), clamped);
   const bool flag[4] = { did == 1, did == 2, t.in_range && !hit, did == 1 && clamped };
   sk_owner_count<4>(sums, d_result, flag);
 }
 
-__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_each_kernel(skx_cut_t *cut, const skx_bend_t *bend,
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_each_kernel(skx_cut_t *cut, const skx_bend_t *bend, skx_fenv_t *fenv,
                                                                           const skx_cut_each_t *__restrict__ each, const int32_t *d_voices,
                                                                           const uint32_t *__restrict__ tags, const uint32_t *__restrict__ owner,
                                                                           int n, const uint32_t *d_count, int n_voices, skx_cut_planes_t p,
@@ -99,21 +98,38 @@ __global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_each_kernel(skx_
   if (owned) {
     const uint4 ra = *reinterpret_cast<const uint4 *>(&each[t.i].w[0]);
     const uint2 rb = *reinterpret_cast<const uint2 *>(&each[t.i].w[SKX_CUT_E_UP]);
-    did = skx_cutoff_apply(cut, bend, p, t.e, ra, rb, clamped);
+    did = skx_cutoff_apply(cut, bend, fenv, p, t.e, ra, rb, clamped);
   }
   const bool flag[4] = { did == 1, did == 2, t.valid && !owned, did == 1 && clamped };
   sk_owner_count<4>(sums, d_result, flag);
 }
 
+// what the ENV instantiation takes beside the rest (ENV false: an empty struct the kernel never reads)
+template <bool ENV> struct skx_cutoff_env_t {};
+template <> struct skx_cutoff_env_t<true> {
+  skx_fenv_t *fenv;
+  const skx_plane_t *time;                                               // SKX_TIME: words 2, 3 are sample_release
+};
+
+template <bool ENV>
 __global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_advance_kernel(skx_cut_t *cut, skx_cut_planes_t p, int first, int count,
-                                                                             uint32_t frames, uint32_t *d_result) {
+                                                                             uint32_t frames, uint32_t *d_result, skx_cutoff_env_t<ENV> ea) {
   __shared__ uint32_t sums[2];
   const int64_t off = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
   bool still = false, arrived = false;
   if (off < count) {
     const int v = first + (int)off;                                      // (inside the bank: checked on the host)
     const uint4 a = *skx_cut_a(cut, v);                                  // w, target, up, down
-    if (a.y != 0u) {
+    bool contour = false;
+    if constexpr (ENV) {
+      if (ea.fenv[v].w[SKX_FENV_STAGE] != 0u) {                          // (a voice without a contour: this 4-byte load and no more)
+        contour = true;
+        const uint4 fa = *skx_fenv_a(ea.fenv, v);                        // stage, w_peak, w_sustain, w_end
+        const uint2 rel = *reinterpret_cast<const uint2 *>(&ea.time[v].w[2]);
+        skx_fenv_advance(cut, ea.fenv, p, v, a, fa, (rel.x | rel.y) != 0u, frames, still, arrived);
+      }
+    }
+    if (!contour && a.y != 0u) {
       const uint4 b = *skx_cut_b(cut, v);                                // carry, q, mode, 0
       uint32_t w = a.x;
       bool there = w == a.y;
@@ -136,10 +152,12 @@ __global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_advance_kernel(s
   sk_owner_count<2>(sums, d_result, flag);
 }
 
-__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_stop_kernel(skx_cut_t *cut, skx_cut_planes_t p, int first, int count, int snap) {
+__global__ __launch_bounds__(SK_CONTROL_SPAN) void sk_fx_cutoff_stop_kernel(skx_cut_t *cut, skx_fenv_t *fenv, skx_cut_planes_t p, int first, int count,
+                                                                          int snap) {
   const int64_t off = (int64_t)blockIdx.x * SK_CONTROL_SPAN + threadIdx.x;
   if (off >= count) return;
   const int v = first + (int)off;
+  if (fenv && fenv[v].w[SKX_FENV_STAGE] != 0u) skx_fenv_zero(fenv, v);   // (a resting contour has no target: ahead of the early return)
   const uint4 a = *skx_cut_a(cut, v);
   if (a.y == 0u) return;                                                 // (not moving: rates and carry are 0 already)
   uint32_t w = a.x;
@@ -161,43 +179,53 @@ static skx_cut_planes_t skx_cut_planes(skx_plane_t *const ro[SKX_COUNT]) {
 }
 
 // d_result[4] (or NULL; zeroed on `stream` ahead of the kernel): voices set or started, records withheld, voices of the range that did
-// not match, cutoffs clamped
-extern "C" int skx_launch_cutoff_match(skx_cut_t *cut, const skx_bend_t *bend, const skx_cut_each_t *rec, int first, int count,
+// not match, cutoffs clamped.  fenv: the bank's filter-envelope array or NULL (a voice set or started loses its contour)
+extern "C" int skx_launch_cutoff_match(skx_cut_t *cut, const skx_bend_t *bend, skx_fenv_t *fenv, const skx_cut_each_t *rec, int first, int count,
                                        const uint32_t *owner, uint32_t value, uint32_t mask, skx_plane_t *const ro[SKX_COUNT],
                                        uint32_t *d_result, hipStream_t stream) {
   if (count <= 0) return 0;
   const hipError_t e = sk_result_clear(d_result, 4, stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_fx_cutoff_match_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, cut, bend, *rec, first, count, owner,
+  hipLaunchKernelGGL(sk_fx_cutoff_match_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, cut, bend, fenv, *rec, first, count, owner,
                      value, mask, skx_cut_planes(ro), d_result);
   return (int)hipGetLastError();
 }
 
 // d_result[4] as above, [2]: voices whose owner differs.  d_each: 16-byte aligned
-extern "C" int skx_launch_cutoff_each(skx_cut_t *cut, const skx_bend_t *bend, const skx_cut_each_t *d_each, const int32_t *d_voices,
+extern "C" int skx_launch_cutoff_each(skx_cut_t *cut, const skx_bend_t *bend, skx_fenv_t *fenv, const skx_cut_each_t *d_each, const int32_t *d_voices,
                                       const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices,
                                       skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream) {
   if (n <= 0) return 0;
   const hipError_t e = sk_result_clear(d_result, 4, stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_fx_cutoff_each_kernel, dim3(sk_list_grid(n, 0)), dim3(SK_CONTROL_SPAN), 0, stream, cut, bend, d_each, d_voices, d_tags,
+  hipLaunchKernelGGL(sk_fx_cutoff_each_kernel, dim3(sk_list_grid(n, 0)), dim3(SK_CONTROL_SPAN), 0, stream, cut, bend, fenv, d_each, d_voices, d_tags,
                      owner, n, d_count, n_voices, skx_cut_planes(ro), d_result);
   return (int)hipGetLastError();
 }
 
-// d_result[2] (or NULL; zeroed on `stream` ahead of the kernel): voices still moving, voices that arrived
-extern "C" int skx_launch_cutoff_advance(skx_cut_t *cut, skx_plane_t *const ro[SKX_COUNT], int first, int count, int num_frames,
+// d_result[2] (or NULL; zeroed on `stream` ahead of the kernel): voices still moving, voices that arrived.  fenv == NULL: the ENV = false
+// instantiation, the kernel of a bank without a filter-envelope array; else ENV = true
+extern "C" int skx_launch_cutoff_advance(skx_cut_t *cut, skx_fenv_t *fenv, skx_plane_t *const ro[SKX_COUNT], int first, int count, int num_frames,
                                          uint32_t *d_result, hipStream_t stream) {
   if (count <= 0) return 0;
   const hipError_t e = sk_result_clear(d_result, 2, stream);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(sk_fx_cutoff_advance_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, cut, skx_cut_planes(ro), first, count,
-                     (uint32_t)num_frames, d_result);
+  if (fenv) {
+    skx_cutoff_env_t<true> ea;
+    ea.fenv = fenv;
+    ea.time = ro[SKX_TIME];
+    hipLaunchKernelGGL(sk_fx_cutoff_advance_kernel<true>, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, cut, skx_cut_planes(ro), first,
+                       count, (uint32_t)num_frames, d_result, ea);
+  } else {
+    hipLaunchKernelGGL(sk_fx_cutoff_advance_kernel<false>, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, cut, skx_cut_planes(ro), first,
+                       count, (uint32_t)num_frames, d_result, skx_cutoff_env_t<false>());
+  }
   return (int)hipGetLastError();
 }
 
-extern "C" int skx_launch_cutoff_stop(skx_cut_t *cut, skx_plane_t *const ro[SKX_COUNT], int first, int count, int snap, hipStream_t stream) {
+extern "C" int skx_launch_cutoff_stop(skx_cut_t *cut, skx_fenv_t *fenv, skx_plane_t *const ro[SKX_COUNT], int first, int count, int snap,
+                                      hipStream_t stream) {
   if (count <= 0) return 0;
-  hipLaunchKernelGGL(sk_fx_cutoff_stop_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, cut, skx_cut_planes(ro), first, count, snap);
+  hipLaunchKernelGGL(sk_fx_cutoff_stop_kernel, dim3(sk_grid(count)), dim3(SK_CONTROL_SPAN), 0, stream, cut, fenv, skx_cut_planes(ro), first, count, snap);
   return (int)hipGetLastError();
 }

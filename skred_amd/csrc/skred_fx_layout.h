@@ -182,4 +182,23 @@ typedef struct { uint32_t w[SKX_CUT_E_WORDS]; } skx_cut_each_t;   /* 32 bytes */
 #define SKX_CUTOFF_C4 13634516ll
 #define SKX_CUTOFF_C5 (-605274ll)
 #define SKX_CUTOFF_C6 17511ll
+
+/* ---- filter envelope (skred_fx_fenv_kernels.hip, and the ENV instantiation of sk_fx_cutoff_advance_kernel; include/skred_amd_fxpt.h:
+ * skred_fxbank_fenv_match / _fenv_owned_each / _fenv_tags_each / _download_fenv) ----
+ * fenv[n_voices]: eight words per voice (two 16-byte loads) beside the cutoff array: stage, w_peak, w_sustain, w_end (w_q29 values in
+ * the box) | rate_attack_q32, rate_decay_q32, rate_release_q32, 0.  stage 0: no contour, and all eight words are 0.  The float bank's
+ * sk_fenv_t has the same shape (checked in skred_fx_fenv.c): its clear kernel serves this array too */
+enum { SKX_FENV_STAGE = 0, SKX_FENV_W_PEAK, SKX_FENV_W_SUSTAIN, SKX_FENV_W_END, SKX_FENV_RATE_ATTACK, SKX_FENV_RATE_DECAY, SKX_FENV_RATE_RELEASE,
+       SKX_FENV_RESERVED, SKX_FENV_WORDS = 8 };
+enum { SKX_FENV_OFF = 0, SKX_FENV_ATTACK, SKX_FENV_DECAY, SKX_FENV_SUSTAIN, SKX_FENV_RELEASE };
+typedef struct { uint32_t w[SKX_FENV_WORDS]; } skx_fenv_t;   /* 32 bytes */
+/* a record is skred_fx_fenv_t word for word (layout and bits checked at compile time in skred_fx_fenv.c): 32 bytes, two aligned 16-byte
+ * loads.  The bits equal SKRED_FX_FENV_* */
+#define SKX_FENV_ABS   (1u << 0)
+#define SKX_FENV_REL   (1u << 1)
+#define SKX_FENV_START (1u << 2)
+#define SKX_FENV_ALL   ((1u << 3) - 1u)
+enum { SKX_FENV_E_SET = 0, SKX_FENV_E_START, SKX_FENV_E_PEAK, SKX_FENV_E_SUSTAIN, SKX_FENV_E_END, SKX_FENV_E_RATE_ATTACK, SKX_FENV_E_RATE_DECAY,
+       SKX_FENV_E_RATE_RELEASE, SKX_FENV_E_WORDS = 8 };
+typedef struct { uint32_t w[SKX_FENV_E_WORDS]; } skx_fenv_each_t;   /* 32 bytes */
 #endif

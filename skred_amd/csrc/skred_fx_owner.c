@@ -59,6 +59,8 @@ int skx_owner_tag_launch(skred_fxbank_t *fx, const int32_t *d_voices, const uint
   if (e == hipSuccess && fx->d_bend) e = (hipError_t)sk_launch_bend_clear((sk_bend_t *)fx->d_bend, d_voices, n, d_count, 1, fx->n_voices, s);
   /* ... nor a cutoff word (skred_fx_cutoff.c): a thief or a key struck again does not inherit a moving cutoff; the coefficients stay */
   if (e == hipSuccess && fx->d_cut) e = (hipError_t)sk_launch_cutoff_clear((sk_cut_t *)fx->d_cut, d_voices, n, d_count, 1, fx->n_voices, s);
+  /* ... nor a contour (skred_fx_fenv.c): the float bank's clear kernel again, the fenv array's shape being the same */
+  if (e == hipSuccess && fx->d_fenv) e = (hipError_t)sk_launch_fenv_clear((sk_fenv_t *)fx->d_fenv, d_voices, n, d_count, 1, fx->n_voices, s);
   return skx_batch_end(&bt, e, who, s);
 }
 

@@ -65,6 +65,7 @@ void skred_fxbank_destroy(skred_fxbank_t *fx) {
   if (fx->d_gain_state) hipFree(fx->d_gain_state);
   skx_live_free(fx);
   skx_cutoff_free(fx);
+  skx_fenv_free(fx);
   if (fx->d_mix) hipFree(fx->d_mix);
   if (fx->d_stems) hipFree(fx->d_stems);
   if (fx->ev0) hipEventDestroy(fx->ev0);

@@ -1,8 +1,8 @@
 /* skred_fxbank_priv.h -- what the host files of the fixed-point bank share (skred_fxbank.c: planes, uploads, rendering;
  * skred_fx_stage.c: the staging ring and the batch path; skred_fx_live.c: updates, the free-voice list, note-ons; skred_fx_steal.c:
  * voice stealing; skred_fx_owner.c: note owners; skred_fx_ctl.c: controllers; skred_fx_expr.c: channels and per-note expression;
- * skred_fx_pedal.c: pedals; skred_fx_glide.c: portamento; skred_fx_bend.c: the pitch wheel; skred_fx_cutoff.c: filter cutoff; channel
- * polyphony lives in skred_fx_steal.c). */
+ * skred_fx_pedal.c: pedals; skred_fx_glide.c: portamento; skred_fx_bend.c: the pitch wheel; skred_fx_cutoff.c: filter cutoff; skred_fx_fenv.c:
+ * the filter envelope; channel polyphony lives in skred_fx_steal.c). */
 #ifndef SKRED_FXBANK_PRIV_H
 #define SKRED_FXBANK_PRIV_H
 
@@ -58,6 +58,7 @@ struct skred_fxbank {
   skx_glide_t *d_glide;                      /* portamento (skred_fx_glide.c): four words per voice; NULL until the first call that starts a glide */
   skx_bend_t *d_bend;                        /* the pitch wheel (skred_fx_bend.c): two words per voice; NULL until the first call that bends */
   skx_cut_t *d_cut;                          /* filter cutoff (skred_fx_cutoff.c): eight words per voice; NULL until the first call that sets a cutoff */
+  skx_fenv_t *d_fenv;                        /* the filter envelope (skred_fx_fenv.c): eight words per voice; NULL until the first record call */
   long long *d_mix; size_t mix_cap;
   int32_t *d_stems; size_t stems_cap;
   uint64_t count;
@@ -134,6 +135,12 @@ void skx_bend_pack(const uint32_t *ratios_q24, int n, const uint32_t *perm, uint
  * rec[perm[j]] (perm NULL: j), set and value as they stand, q_q16, mode and the rates where named, the rest zero.  Pure host */
 void skx_cutoff_free(skred_fxbank_t *fx);
 void skx_cutoff_pack(const skred_fx_cutoff_t *rec, int n, const uint32_t *perm, skx_cut_each_t *out);
+/* ... and the allocation of the array by the first call that needs it (the owner array first), for the filter envelope too */
+int skx_cutoff_ensure(skred_fxbank_t *fx);
+/* skred_fx_fenv.c: the filter-envelope array, freed with the bank (skred_fxbank.c); and the checked records as they travel -- out[j] =
+ * rec[perm[j]] (perm NULL: j), word for word.  Pure host */
+void skx_fenv_free(skred_fxbank_t *fx);
+void skx_fenv_pack(const skred_fx_fenv_t *rec, int n, const uint32_t *perm, skx_fenv_each_t *out);
 /* skred_fx_ctl.c: the checked record as it travels (the reserved words carry the reciprocals).  Pure host */
 void skx_ctl_pack(const skred_fx_ctl_t *ctl, skx_ctl_t *out);
 /* skred_fx_expr.c: the checked entries as they travel -- out[j] = each[perm[j]] (perm NULL: j), the named values word for word, the
@@ -217,18 +224,30 @@ int skx_launch_bend_range_clear(skx_bend_t *bend, skx_plane_t *osc, int first, i
 /* skred_fx_cutoff_kernels.hip (the clear behind a tag launch is the float bank's sk_launch_cutoff_clear at slot_voices = 1,
  * skred_launch.h).  bend: the bank's pitch-wheel array or NULL (TRACK reads a bent voice's key).  ro: the bank's planes -- phase_inc is
  * read, the five coefficient words are stored.  Each d_result may be NULL and is zeroed on `stream` ahead of its kernel: [4] voices set
- * or started, records withheld, [2] below, cutoffs clamped */
+ * or started, records withheld, [2] below, cutoffs clamped.  fenv: the bank's filter-envelope array or NULL (a voice set, started or
+ * stopped loses its contour: its eight fenv words = 0; the advance hands a voice with a contour to skx_fenv_advance) */
 /* ... the record on the voices of [first, first + count) (inside the bank) whose owner matches; [2]: voices that did not match */
-int skx_launch_cutoff_match(skx_cut_t *cut, const skx_bend_t *bend, const skx_cut_each_t *rec, int first, int count, const uint32_t *owner,
-                            uint32_t value, uint32_t mask, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
+int skx_launch_cutoff_match(skx_cut_t *cut, const skx_bend_t *bend, skx_fenv_t *fenv, const skx_cut_each_t *rec, int first, int count,
+                            const uint32_t *owner, uint32_t value, uint32_t mask, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
 /* ... entry k brings d_each[k] (16-byte aligned) to d_voices[k] where that is a voice whose owner is d_tags[k]; [2]: voices whose owner differs */
-int skx_launch_cutoff_each(skx_cut_t *cut, const skx_bend_t *bend, const skx_cut_each_t *d_each, const int32_t *d_voices, const uint32_t *d_tags,
-                           const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT],
+int skx_launch_cutoff_each(skx_cut_t *cut, const skx_bend_t *bend, skx_fenv_t *fenv, const skx_cut_each_t *d_each, const int32_t *d_voices,
+                           const uint32_t *d_tags, const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT],
                            uint32_t *d_result, hipStream_t stream);
-/* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] += voices still moving, voices that arrived */
-int skx_launch_cutoff_advance(skx_cut_t *cut, skx_plane_t *const ro[SKX_COUNT], int first, int count, int num_frames, uint32_t *d_result,
-                              hipStream_t stream);
+/* the advance pass by num_frames over [first, first + count) (inside the bank); d_result[2] += voices still moving, voices that arrived.
+ * fenv == NULL: the plain instantiation, the kernel of a bank without a filter-envelope array */
+int skx_launch_cutoff_advance(skx_cut_t *cut, skx_fenv_t *fenv, skx_plane_t *const ro[SKX_COUNT], int first, int count, int num_frames,
+                              uint32_t *d_result, hipStream_t stream);
 /* every movement of the range ends; snap != 0: a moving voice's w = its target and its coefficients computed first */
-int skx_launch_cutoff_stop(skx_cut_t *cut, skx_plane_t *const ro[SKX_COUNT], int first, int count, int snap, hipStream_t stream);
+int skx_launch_cutoff_stop(skx_cut_t *cut, skx_fenv_t *fenv, skx_plane_t *const ro[SKX_COUNT], int first, int count, int snap, hipStream_t stream);
+/* skred_fx_fenv_kernels.hip (the clear behind a tag launch is the float bank's sk_launch_fenv_clear at slot_voices = 1, skred_launch.h).
+ * ro: the bank's planes -- the five coefficient words are stored.  Each d_result may be NULL and is zeroed on `stream` ahead of its
+ * kernel: [4] voices started, records withheld, [2] below, voices clamped */
+/* ... the record on the voices of [first, first + count) (inside the bank) whose owner matches; [2]: voices that did not match */
+int skx_launch_fenv_match(skx_fenv_t *fenv, skx_cut_t *cut, const skx_fenv_each_t *rec, int first, int count, const uint32_t *owner, uint32_t value,
+                          uint32_t mask, skx_plane_t *const ro[SKX_COUNT], uint32_t *d_result, hipStream_t stream);
+/* ... entry k brings d_each[k] (16-byte aligned) to d_voices[k] where that is a voice whose owner is d_tags[k]; [2]: voices whose owner differs */
+int skx_launch_fenv_each(skx_fenv_t *fenv, skx_cut_t *cut, const skx_fenv_each_t *d_each, const int32_t *d_voices, const uint32_t *d_tags,
+                         const uint32_t *owner, int n, const uint32_t *d_count, int n_voices, skx_plane_t *const ro[SKX_COUNT],
+                         uint32_t *d_result, hipStream_t stream);
 
 #endif

@@ -53,10 +53,11 @@ FX_ABI_SYMBOLS = ["skred_fxbank_create", "skred_fxbank_destroy", "skred_fxbank_s
                   "skred_fxbank_download_bend",
                   "skred_fxbank_cutoff_match", "skred_fxbank_cutoff_owned_each", "skred_fxbank_cutoff_tags_each",
                   "skred_fxbank_cutoff_advance", "skred_fxbank_cutoff_stop", "skred_fxbank_download_cutoff",
+                  "skred_fxbank_fenv_match", "skred_fxbank_fenv_owned_each", "skred_fxbank_fenv_tags_each", "skred_fxbank_download_fenv",
                   "skred_fxshard_create", "skred_fxshard_bank", "skred_fxshard_upload"]
 FX_HOST_ABI_SYMBOLS = ["skred_fx_idle_check", "skred_fx_notes_check", "skred_fx_steal_check", "skred_fx_ctl_check",
                        "skred_fx_ctl_each_check", "skred_fx_filter_each_check", "skred_fx_chan_check", "skred_fx_pedal_check",
-                       "skred_fx_glide_check", "skred_fx_bend_check", "skred_fx_cutoff_check", "skred_fx_filter_coeffs_w"]                                                                     # pure host: no bank, no device
+                       "skred_fx_glide_check", "skred_fx_bend_check", "skred_fx_cutoff_check", "skred_fx_filter_coeffs_w", "skred_fx_fenv_check"]                                                                     # pure host: no bank, no device
 FX_STAMP_TRIGGER, FX_STAMP_RELEASE = 1, 2
 # live control: the float bank's vocabulary (include/skred_amd.h: SKRED_DIRTY_* / SKRED_STAMP_* / SKRED_IDLE_* / SKRED_NOTE_*)
 DIRTY_PARAMS, DIRTY_PHASE, DIRTY_ENV_STATE, DIRTY_PAN, DIRTY_FILTER_STATE = 1, 2, 4, 8, 16
@@ -80,6 +81,9 @@ FX_BEND_ONE = 1 << 24                             # SKRED_FX_BEND_ONE: the wheel
 # filter cutoff: SKRED_FX_CUTOFF_* -- the set bits and the integer boxes (w_q29: Q29 radians per frame; q_q16)
 FX_CUTOFF_ABS, FX_CUTOFF_TRACK, FX_CUTOFF_GLIDE, FX_CUTOFF_Q, FX_CUTOFF_MODE = 1, 2, 4, 8, 16
 FX_CUTOFF_W_MIN, FX_CUTOFF_W_MAX, FX_CUTOFF_Q_MIN, FX_CUTOFF_Q_MAX = 1 << 19, 3 << 29, 1 << 10, 1 << 26
+# filter envelope: SKRED_FX_FENV_* -- the set bits; the stage values of the first fenv word
+FX_FENV_ABS, FX_FENV_REL, FX_FENV_START = 1, 2, 4
+FX_FENV_OFF, FX_FENV_ATTACK, FX_FENV_DECAY, FX_FENV_SUSTAIN, FX_FENV_RELEASE = 0, 1, 2, 3, 4
 FX_CTL_SPAN = 256                                 # voices or entries per workgroup of the controller and guarded-stamp kernels
 FX_RING_SLOTS = 8                                 # SKRED_FX_RING_SLOTS: staging slots of the control ring
 FX_NOTE_SPAN = 256                                # notes per workgroup of the placement kernel
@@ -280,6 +284,34 @@ def fx_cutoff_check(recs, n: Optional[int] = None, first_time: bool = False) -> 
     return int(_bind(load()).skred_fx_cutoff_check(C.cast(arr, C.c_void_p) if arr is not None else None, int(n), int(bool(first_time))))
 
 
+class FxFenvC(C.Structure):
+    """ctypes image of ``skred_fx_fenv_t`` (32 bytes): `set` holds exactly one of FX_FENV_ABS and FX_FENV_REL, and FX_FENV_START or not."""
+    _fields_ = [("set", C.c_uint32), ("start", C.c_uint32), ("peak", C.c_uint32), ("sustain", C.c_uint32), ("end", C.c_uint32),
+                ("rate_attack_q32", C.c_uint32), ("rate_decay_q32", C.c_uint32), ("rate_release_q32", C.c_uint32)]
+
+
+def fx_fenv(set: int, peak: int, sustain: int, end: int, rate_attack_q32: int, rate_decay_q32: int, rate_release_q32: int,
+            start: int = 0) -> FxFenvC:
+    """One record: ``fx_fenv(FX_FENV_REL, 8 << 16, 2 << 16, 1 << 15, ra, rd, rr)`` opens to 8 x the present cutoff, falls to 2 x while the
+    key is held and closes to half of it after the note-off."""
+    return FxFenvC(int(set), int(start), int(peak), int(sustain), int(end), int(rate_attack_q32), int(rate_decay_q32), int(rate_release_q32))
+
+
+def fx_fenv_array(recs):
+    """A contiguous ``FxFenvC`` array from a sequence of FxFenvC (a ctypes array of FxFenvC passes through)."""
+    if isinstance(recs, C.Array) and recs._type_ is FxFenvC:
+        return recs
+    recs = list(recs)
+    return (FxFenvC * len(recs))(*recs)
+
+
+def fx_fenv_check(recs, n: Optional[int] = None) -> int:
+    """skred_fx_fenv_check: 0, SKRED_E_BAD_ARG (-2) or SKRED_E_RANGE (-4).  Pure host, no device.  ``recs`` None: a NULL array."""
+    arr = fx_fenv_array(recs) if recs is not None else None
+    n = (len(arr) if arr is not None else 0) if n is None else n
+    return int(_bind(load()).skred_fx_fenv_check(C.cast(arr, C.c_void_p) if arr is not None else None, int(n)))
+
+
 def fx_filter_coeffs_w(mode: int, w_q29: int, q_q16: int):
     """skred_fx_filter_coeffs_w: (return code, the five Q2.30 words b0 b1 b2 a1 a2 as an int32 array).  Pure host, no device."""
     out = np.zeros(5, np.int32)
@@ -444,6 +476,11 @@ def _bind(L):
     L.skred_fxbank_cutoff_advance.argtypes = [vp, i32, i32, i32, vp, vp]
     L.skred_fxbank_cutoff_stop.argtypes = [vp, i32, i32, i32, vp]
     L.skred_fxbank_download_cutoff.argtypes = [vp, vp, i32, i32]
+    L.skred_fx_fenv_check.argtypes = [vp, i32]
+    L.skred_fxbank_fenv_match.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.skred_fxbank_fenv_owned_each.argtypes = [vp, vp, vp, vp, i32, vp, vp, vp]
+    L.skred_fxbank_fenv_tags_each.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp]
+    L.skred_fxbank_download_fenv.argtypes = [vp, vp, i32, i32]
     L.skred_fxshard_create.argtypes = [i32, i32, i32, i32, i32, C.POINTER(vp)]
     L.skred_fxshard_bank.argtypes = [vp]
     L.skred_fxshard_bank.restype = vp
@@ -913,6 +950,38 @@ class DeviceFxBank:
         count = self.n - first if count is None else count
         out = np.full((max(count, 0), 8), 0xABABABAB, np.uint32)
         _check(self.L.skred_fxbank_download_cutoff(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_cutoff")
+        return out
+
+    # ---- filter envelope (include/skred_amd_fxpt.h: skred_fxbank_fenv_match / _fenv_owned_each / _fenv_tags_each / _download_fenv; the
+    # contour is stepped by cutoff_advance above) ----
+    def fenv_match(self, first: int, count: int, value: int, mask: int, rec: FxFenvC, d_result: int = 0, stream: int = 0):
+        """The channel sweep: the record on every matching voice of the range.  d_result (uint32[4], may be 0) = started, withheld, did
+        not match, clamped."""
+        m = OwnerMatchC(int(value), int(mask))
+        _check(self.L.skred_fxbank_fenv_match(self.h, int(first), int(count), C.byref(m), C.byref(rec), d_result or None, stream or None),
+               "skred_fxbank_fenv_match")
+
+    def fenv_owned_each(self, recs, d_voices: int, tags, d_count: int = 0, d_result: int = 0, stream: int = 0):
+        """Entry k brings recs[k] to d_voices[k] where that voice's owner is tags[k].  d_result (uint32[4], may be 0) = started, withheld,
+        voices whose owner differs, clamped."""
+        arr, t = fx_fenv_array(recs), _tags(tags)
+        assert len(arr) == len(t), "one record per tag"
+        _check(self.L.skred_fxbank_fenv_owned_each(self.h, C.cast(arr, C.c_void_p), d_voices or None, t.ctypes.data, len(t), d_count or None,
+                                                   d_result or None, stream or None), "skred_fxbank_fenv_owned_each")
+
+    def fenv_tags_each(self, recs, first: int, count: int, tags, d_result: int = 0, stream: int = 0):
+        """By note id: recs[k] on the lowest voice of the range that carries tags[k]."""
+        arr, t = fx_fenv_array(recs), _tags(tags)
+        assert len(arr) == len(t), "one record per tag"
+        _check(self.L.skred_fxbank_fenv_tags_each(self.h, C.cast(arr, C.c_void_p), int(first), int(count), t.ctypes.data, len(t),
+                                                  d_result or None, stream or None), "skred_fxbank_fenv_tags_each")
+
+    def download_fenv(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The fenv words of [first, first + count) as a (count, 8) uint32 array: stage, w_peak, w_sustain, w_end, rate_attack_q32,
+        rate_decay_q32, rate_release_q32, 0; waits for the device.  Zeros on a bank without the array."""
+        count = self.n - first if count is None else count
+        out = np.full((max(count, 0), 8), 0xABABABAB, np.uint32)
+        _check(self.L.skred_fxbank_download_fenv(self.h, out.ctypes.data, int(first), int(count)), "skred_fxbank_download_fenv")
         return out
 
 

@@ -2550,8 +2550,58 @@ def fxcutoff():
     db.close()
 
 
+def fxfenv():
+    """The filter envelope on the fixed-point bank: the time of skred_fxbank_cutoff_advance by 64 frames over bank_fx(2**20), every
+    voice tagged and holding a cutoff word, as in `fxcutoff`.  (a) a bank without an fenv array: the ENV = false kernel, the one the
+    bank had before the envelope; (b) a bank with the array and no contour: the ENV = true kernel, one more 4-byte load per voice; (c)
+    every voice of that bank in a moving stage (an attack that crawls: nobody arrives while timed), and beside it every voice of the
+    plain bank moving by a cutoff glide of the same rate -- the same steps and coefficient stores without the envelope's loads; (d)
+    skred_fxbank_fenv_match of the whole bank and skred_fxbank_fenv_tags_each of 256 notes.  (a) and (b) alternate in one session.
+    Medians of 12 with minimum and maximum; host time held, and stream time between events."""
+    from skred_amd import fxbank as X
+    n, F, CHANNELS, NOTES = 1 << 20, 64, 16, 256
+    bank, pool, c0 = X.bank_fx(n)
+    v = np.arange(n, dtype=np.int64)
+    tags = (((v % CHANNELS) + 1) << 24 | (v // CHANNELS + 1)).astype(np.uint32)
+    everyone = torch.arange(n, dtype=torch.int32, device="cuda")
+    res = torch.zeros(4, dtype=torch.int32, device="cuda")
+    base = X.fx_cutoff(X.FX_CUTOFF_ABS | X.FX_CUTOFF_Q | X.FX_CUTOFF_MODE, 1 << 24, 2 << 16, 1)
+    crawl = X.fx_fenv(X.FX_FENV_ABS, 1 << 28, 1 << 26, 1 << 22, 1, 1, 1)          # one unit of w per 64 frames: 2^28 - 2^24 steps away
+    glide = X.fx_cutoff(X.FX_CUTOFF_ABS | X.FX_CUTOFF_GLIDE, 1 << 28, 0, 0, 1, 1)
+    banks = []
+    for _ in range(2):
+        db = X.DeviceFxBank(n)
+        db.set_tables(pool); db.upload(bank); db.set_sample_count(c0)
+        db.tag_list(everyone.data_ptr(), tags)
+        db.cutoff_match(0, n, 0, 0, base, res.data_ptr())
+        banks.append(db)
+    plain, env = banks
+    env.fenv_match(0, n, 0x7F000000, 0xFF000000, crawl, res.data_ptr())            # a channel nobody is on: the array exists, no contour
+    torch.cuda.synchronize()
+    assert not env.download_fenv(0, 4096).any() and res.cpu().numpy().tolist()[:3] == [0, 0, n]
+    at = np.flatnonzero(v % CHANNELS == 2)[::7][:NOTES]
+
+    def line(label, call, words):
+        ms, held = _fx_timed(call, None)
+        print(f"  {label}: host held {_fx_stats(held)}; stream time between events {_fx_stats(ms)}; d_result = {res.cpu().numpy().tolist()[:words]}")
+        return float(np.median(ms))
+
+    print(f"fx {n} voices, all tagged, every voice with a cutoff word; cutoff_advance by {F} frames over the whole bank")
+    a, b = [], []
+    for k in range(3):                                                           # alternating: the same session, the same clocks
+        a.append(line(f"(a) no fenv array (ENV = false), nothing moving, round {k}", lambda: plain.cutoff_advance(0, n, F, res.data_ptr()), 2))
+        b.append(line(f"(b) fenv array, no contour (ENV = true), nothing moving, round {k}", lambda: env.cutoff_advance(0, n, F, res.data_ptr()), 2))
+    print(f"  (b) / (a), medians of the three rounds: {np.median(b):.4f} ms / {np.median(a):.4f} ms = {np.median(b) / np.median(a):.3f}")
+    line("(d) fenv_match of the whole bank (every voice enters the attack)", lambda: env.fenv_match(0, n, 0, 0, crawl, res.data_ptr()), 4)
+    plain.cutoff_match(0, n, 0, 0, glide, res.data_ptr())
+    line("(c) fenv array, every voice in the attack", lambda: env.cutoff_advance(0, n, F, res.data_ptr()), 2)
+    line("(c) no fenv array, every voice moving by a cutoff glide of the same rate", lambda: plain.cutoff_advance(0, n, F, res.data_ptr()), 2)
+    line(f"(d) fenv_tags_each of {NOTES} tags", lambda: env.fenv_tags_each(X.fx_fenv_array([crawl] * NOTES), 0, n, tags[at], res.data_ptr()), 4)
+    plain.close(); env.close()
+
+
 SCENARIOS = {"kernels": kernels, "crossover": crossover, "overhead": overhead, "frames": frames, "fm": fm,
-             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "cutoff": cutoff, "fenv": fenv, "fxbend": fxbend, "fxcutoff": fxcutoff}
+             "noise": noise, "live": live, "patches": patches, "linear": linear, "mid": mid, "cross": cross, "taps": taps, "idle": idle, "steal": steal, "cz": cz, "fxlive": fxlive, "fxsteal": fxsteal, "slots": slots, "slotsteal": slotsteal, "ctl": ctl, "owners": owners, "fxowners": fxowners, "fxctl": fxctl, "expr": expr, "fxexpr": fxexpr, "timbre": timbre, "fxtimbre": fxtimbre, "chan": chan, "fxchan": fxchan, "pedal": pedal, "fxpedal": fxpedal, "glide": glide, "fxglide": fxglide, "bend": bend, "cutoff": cutoff, "fenv": fenv, "fxbend": fxbend, "fxcutoff": fxcutoff, "fxfenv": fxfenv}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(SCENARIOS)
